@@ -8,10 +8,13 @@ bench.py -- UDA train-step throughput of the ESS hot path on MI355X (the metric 
 One "step" = one ESSModel.train_step (T x E2VID recurrent encoder forward, image-encoder fwd/bwd x2, decoder fwd x3 /
 bwd x3, losses, 2 x RAdam) on one synthetic batch per GPU, inputs resident in HBM before the timed region.
 Workload = BASELINE config 3/4: DSEC-shape, B=8 sequences per GPU, T=5, C=2, 480x640, K=11, DSEC branch.
-Prints ONE JSON line on rank 0 (value = voxel grids/s over all GPUs = N*B*T / max-over-ranks step time), with
-`roofline` for the time-dominant kernel (the plain 3x3 convolution of the trainable networks; the ConvLSTM gate kernel and the
-weight-gradient kernel as `roofline.others`), `step` (whole-step FLOPs against the matrix-core peak), `extra` (the fp32
-parity-grade configuration's ms/step) and `cpu_baseline` (the oracle timed on the host cores, N=1 only).
+Prints ONE JSON line on rank 0 (value = voxel grids/s over all GPUs = N*B*T / max-over-ranks step time, ms_per_step) with
+`step` (whole-step FLOPs against the matrix-core peak).  A plain run does only that: set up, warm up, time --steps steps.
+--full adds, after the timed steps, `roofline` for the time-dominant kernel (the plain 3x3 convolution of the trainable networks;
+the ConvLSTM gate kernel and the weight-gradient kernel as `roofline.others`), `extra` (the bf16 / fp32 / bf16x3 configurations'
+ms/step), `parity` and `cpu_baseline` (the oracle timed on the host cores, N=1 only).
+--dump-outputs DIR writes what the last timed step computed: DIR/loss_<name>.npy, DIR/final_loss.npy and
+DIR/params_<optimiser>.npy (the trainable parameters after the step, flat fp32; a fixed, seeded sample when larger than the budget).
 """
 import argparse
 import ctypes
@@ -49,6 +52,12 @@ def parse():
     ap.add_argument('--compute', default='mixed', choices=['bf16', 'fp32', 'bf16x3', 'mixed'],
                     help='conv contraction arithmetic: bf16 MFMA operands + fp32 accumulate (config 3), exact fp32 MFMA, or '
                          'split-operand bf16 (fp32 tensors, three bf16 MFMAs per product: the parity-grade configuration)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline steps, also measure what the headline does not need: roofline / per-kernel rates, the part '
+                         'ceiling, the bf16 / fp32 / bf16x3 (and T = 20) side configurations, the ESS_DP_FORCE plain-step comparison '
+                         'and the CPU baseline (each --no-* option below drops one of them)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (its losses and the updated trainable parameters) as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-graph', action='store_true', help='issue every step eagerly (default on one GPU: the step is captured '
@@ -56,7 +65,10 @@ def parse():
     ap.add_argument('--no-fp32-extra', action='store_true', help='skip the fp32 (parity-grade) steps reported in `extra`')
     ap.add_argument('--no-t20-extra', action='store_true', help='skip the T = 20 steps of the parity-grade configuration')
     ap.add_argument('--quick-cpu-baseline', action='store_true', help='1 warm-up + 2 timed oracle steps instead of 2 + 5')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 # argmax agreement / mIoU of each arithmetic against the fp32 CPU oracle on the trained-decoder fixture at 480x640 (tests/test_hip_bf16_separated.py,
@@ -537,6 +549,35 @@ def self_launch(args):
     return None
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, trainer, out):
+    """What the last timed step computed, as a caller of train_step sees it: the losses it returns and the trainable parameters it
+    updated in place (one flat fp32 vector per optimiser, in parameter order).  An array beyond its share of the byte budget is
+    written as a fixed sample: sorted indices of a randperm seeded with 0, the same for every build with the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    losses, _, final = out
+    arrays = {f'loss_{k}': v for k, v in sorted(losses.items())}
+    arrays['final_loss'] = final
+    for name, opt in sorted(trainer.optimizers_dict.items()):
+        arrays[f'params_{name}'] = torch.cat([p.detach().reshape(-1) for p in opt.param_groups[0]['params']])
+    arrays = {k: v.detach().float().cpu() for k, v in arrays.items()}
+    small = sum(4 * t.numel() for t in arrays.values() if t.numel() <= 1024)
+    cap = (DUMP_BUDGET_BYTES - small) // 4 // max(1, sum(1 for t in arrays.values() if t.numel() > 1024))
+    written = 0
+    for name, t in arrays.items():
+        if t.numel() > cap:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+            t = t[idx]
+        a = t.numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        written += a.nbytes
+    assert written <= DUMP_BUDGET_BYTES, written
+    return sorted(arrays)
+
+
 def main():
     args = parse()
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -639,8 +680,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     final_loss = float(out[-1])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, out)  # (before --full: its side measurements run more steps on this trainer)
     dp_forced = None
-    if dp and world == 1:
+    if args.full and dp and world == 1:
         # one rank under ESS_DP_FORCE: the same step without the data-parallel branches (one graph, no collective), re-captured on the
         # same trainer and timed the same way -> what the collectives and the three-graph split cost per step on one GPU
         ms_dp = elapsed / args.steps * 1e3
@@ -664,14 +707,14 @@ def main():
             D.force_dp(True)
 
     in_step = None
-    if rank == 0 and world == 1 and args.compute in ('bf16', 'mixed') and not args.no_roofline:
+    if args.full and rank == 0 and world == 1 and args.compute in ('bf16', 'mixed') and not args.no_roofline:
         try:
             in_step = in_step_conv_rate(trainer, batch)
         except Exception as e:  # (the launch-set loops below still report)
             in_step = {'error': f'{type(e).__name__}: {e}'}
 
     extra = {}
-    if world == 1 and args.compute == 'mixed' and not args.no_fp32_extra:
+    if args.full and world == 1 and args.compute == 'mixed' and not args.no_fp32_extra:
         # the bf16 configuration (BASELINE config 3's dtype, the headline of rounds 1-5) next to the mixed one: the SAME step, captured
         # the same way, same box, same run
         try:
@@ -697,7 +740,7 @@ def main():
             extra['bf16_error'] = f'{type(e).__name__}: {e}'
         trainer = None
         torch.cuda.empty_cache()
-    if world == 1 and args.compute in ('bf16', 'mixed') and not args.no_fp32_extra:
+    if args.full and world == 1 and args.compute in ('bf16', 'mixed') and not args.no_fp32_extra:
         # the parity-grade configuration next to the headline one: the SAME step in exact-fp32 arithmetic (fp32 MFMA, fp32 NCHW
         # tensors; logits within 1e-3 / argmax-exact / mIoU within 1e-4 of the oracle: tests/test_hip_modules.py), 1 warm-up + 3 steps
         trainer = None
@@ -802,7 +845,7 @@ def main():
             result['config']['parity_grade'] = pg
         if extra:
             result['extra'] = extra
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             result['roofline'] = roofline_blocks(args, device)
             if args.compute in ('bf16', 'mixed'):
                 pc = part_mfma_ceiling()
@@ -813,12 +856,14 @@ def main():
                 result['roofline']['in_step'] = in_step
                 if in_step.get('achieved'):
                     in_step['frac'] = round(in_step['achieved'] / peak, 4)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result['cpu_baseline'] = cpu_baseline(args)
-        # LAST key of the line (the driver keeps its tail): which arithmetic the headline belongs to and what it was checked against
-        result['parity'] = {'compute': args.compute, 'ms_per_step': round(ms, 3), 'bf16_ms_per_step': extra.get('bf16_ms_per_step'),
-                            'bf16x3_ms_per_step': extra.get('bf16x3_ms_per_step'), 'fp32_ms_per_step': extra.get('fp32_ms_per_step'),
-                            'vs_fp32_oracle': PARITY_NOTE.get(args.compute)}
+        # LAST key of a --full line (a reader that keeps only the tail still finds it): which arithmetic the headline belongs to, the
+        # side configurations timed next to it and what it was checked against
+        if args.full:
+            result['parity'] = {'compute': args.compute, 'ms_per_step': round(ms, 3), 'bf16_ms_per_step': extra.get('bf16_ms_per_step'),
+                                'bf16x3_ms_per_step': extra.get('bf16x3_ms_per_step'), 'fp32_ms_per_step': extra.get('fp32_ms_per_step'),
+                                'vs_fp32_oracle': PARITY_NOTE.get(args.compute)}
     if dp:
         dist.barrier()
         dist.destroy_process_group()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Same-box A/B of two builds of the library at step level: the shipped ess_amd/libess_hip.so against trace_tmp/libess_variant.so
 (tools/build_variant.sh), alternating, each run its own process (`bench.py` with the library path patched).
-python tools/bench_ab.py [rounds=2] [extra bench.py arguments ...]"""
+python tools/bench_ab.py [rounds=2] [extra bench.py arguments ...]  (the roofline columns need --full among them)"""
 import json
 import os
 import subprocess
@@ -18,7 +18,7 @@ if os.environ.get('ESS_AB_CHILD'):
     bench.main()
 else:
     rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 2
-    extra = sys.argv[2:] or ['--steps', '10', '--warmup', '3', '--no-cpu-baseline', '--no-fp32-extra']
+    extra = sys.argv[2:] or ['--steps', '10', '--warmup', '3', '--full', '--no-cpu-baseline', '--no-fp32-extra']
     for r in range(rounds):
         for which in ('shipped', 'variant'):
             out = subprocess.run([sys.executable, os.path.abspath(__file__)] + extra, env=dict(os.environ, ESS_AB_CHILD=which),
