@@ -15,7 +15,7 @@ import torch.nn as nn
 from torch.nn import init
 
 from ... import hip
-from ...functional import packed_weight
+from ...functional import columns, derived, packed_rows, packed_weight
 
 _ACT = {None: hip.ACT_NONE, 'relu': hip.ACT_RELU, 'sigmoid': hip.ACT_SIGMOID, 'tanh': hip.ACT_TANH}
 EPS = 1e-5
@@ -72,39 +72,31 @@ def _c8_of(t):
     return c8[0] if c8 is not None and c8[1] == t._version else None
 
 
-class _Fold:
-    """Per-output-channel (scale, shift) of an eval-mode norm folded behind a conv, packed for the kernel
-    and cached until one of the source tensors changes."""
+def _fold(spec, bias, norm_kind, norm_layer):
+    """Per-output-channel (packed scale, packed shift) of an eval-mode norm folded behind a conv (None, None without either)."""
+    src = [bias]
+    if norm_kind in ('BN', 'IN'):
+        src += [norm_layer.running_mean, norm_layer.running_var]
+    if norm_kind == 'BN':
+        src += [norm_layer.weight, norm_layer.bias]
+    src = [t for t in src if t is not None]
+    if not src:
+        return None, None
 
-    def __init__(self):
-        self._cache = {}  # spec.key -> (source versions, (packed scale, packed shift)): a module may be called with several shapes per step
-
-    def get(self, spec, bias, norm_kind, norm_layer):
-        src = [bias]
-        if norm_kind in ('BN', 'IN'):
-            src += [norm_layer.running_mean, norm_layer.running_var]
-        if norm_kind == 'BN':
-            src += [norm_layer.weight, norm_layer.bias]
-        ver = tuple((id(t), t._version, t.data_ptr()) for t in src if t is not None)
-        ent = self._cache.get(spec.key)
-        if ent is None or ent[0] != ver:
-            with torch.no_grad():
-                scale = shift = None
-                if norm_kind == 'BN':  # y = (x - rm) / sqrt(rv + eps) * g + b
-                    scale = norm_layer.weight / torch.sqrt(norm_layer.running_var + EPS)
-                    shift = norm_layer.bias - norm_layer.running_mean * scale
-                elif norm_kind == 'IN':  # InstanceNorm2d(track_running_stats=True).eval(): running stats, no affine
-                    scale = 1.0 / torch.sqrt(norm_layer.running_var + EPS)
-                    shift = -norm_layer.running_mean * scale
-                if bias is not None:
-                    shift = bias * scale + shift if scale is not None else bias
-                ps = hip.pack_rows(spec, scale.contiguous(), fill=1.0) if scale is not None else None
-                pb = hip.pack_rows(spec, shift.contiguous()) if shift is not None else None
-            if len(self._cache) >= 8:
-                self._cache.clear()
-            ent = (ver, (ps, pb))
-            self._cache[spec.key] = ent
-        return ent[1]
+    def build():
+        with torch.no_grad():
+            scale = shift = None
+            if norm_kind == 'BN':  # y = (x - rm) / sqrt(rv + eps) * g + b
+                scale = norm_layer.weight / torch.sqrt(norm_layer.running_var + EPS)
+                shift = norm_layer.bias - norm_layer.running_mean * scale
+            elif norm_kind == 'IN':  # InstanceNorm2d(track_running_stats=True).eval(): running stats, no affine
+                scale = 1.0 / torch.sqrt(norm_layer.running_var + EPS)
+                shift = -norm_layer.running_mean * scale
+            if bias is not None:
+                shift = bias * scale + shift if scale is not None else bias
+            return (hip.pack_rows(spec, scale.contiguous(), fill=1.0) if scale is not None else None,
+                    hip.pack_rows(spec, shift.contiguous()) if shift is not None else None)
+    return derived(src, ('fold', spec.key), build)
 
 
 def _norm_container(norm, ch):
@@ -156,18 +148,13 @@ class ConvLayer(nn.Module):
         nl = _norm_container(norm, out_channels)
         if nl is not None:
             self.norm_layer = nl
-        self._fold = _Fold()
 
     def forward_of_sum(self, x, skip):
         """conv(x + skip) without the elementwise pass: W (x + skip) = [W W] [x; skip], i.e. the two tensors are the two
         concat sources of one convolution whose weight is W repeated along the input channels (sum-skip ahead of the
         prediction layer, reference unet.py:8-13,178-179).  Sums the same products in a different order."""
         w = self.conv2d.weight
-        dup = getattr(self, '_dup_w', None)
-        if dup is None or dup[0] != (w._version, w.data_ptr()):
-            with torch.no_grad():
-                dup = self._dup_w = ((w._version, w.data_ptr()), torch.cat([w, w], dim=1).contiguous())
-        return self.forward(x, x1=skip, weight=dup[1])
+        return self.forward(x, x1=skip, weight=columns(w, [(0, w.shape[1])] * 2))
 
     def forward(self, x, x1=None, residual=None, want_c8=False, c8_only=False, weight=None):
         """x1: optional second source, channel-concatenated on the fly.
@@ -183,7 +170,7 @@ class ConvLayer(nn.Module):
         C1 = 0 if x1 is None else x1.shape[1]
         spec = hip.conv_spec(N, H, W, C0, C1, c.out_channels, c.kernel_size[0], c.stride[0], c.padding[0],
                              act=_ACT[self.activation])
-        scale, shift = self._fold.get(spec, c.bias, self.norm, getattr(self, 'norm_layer', None))
+        scale, shift = _fold(spec, c.bias, self.norm, getattr(self, 'norm_layer', None))
         out = torch.empty(N, c.out_channels, spec.H_out, spec.W_out, dtype=torch.float32, device=x.device)
         c8 = None
         bf = spec.desc.compute == hip.COMPUTE_BF16
@@ -208,7 +195,7 @@ class ConvLayer(nn.Module):
                 # 5x5 / stride 2 (the three downsampling convolutions of the frozen encoder, reference submodules.py:176-186) as a 3x3
                 # over the space-to-depth view of the BF16_C8 source, on the wide-tile 3x3 kernel (ESS_SRC_S2D: 16-channel chunks, the
                 # 25 real taps only) instead of the tap-paired 5x5 kernel; the same products, summed in a different order
-                sc2, sh2 = self._fold.get(s2, c.bias, self.norm, getattr(self, 'norm_layer', None))
+                sc2, sh2 = _fold(s2, c.bias, self.norm, getattr(self, 'norm_layer', None))
                 hip.conv_forward(s2, x8, None, packed_weight(s2, wt, kind=hip.W_CONV5_S2D), sc2, sh2, None, out=c8,
                                  src_fmt=hip.FMT_BF16_C8, out_fmt=hip.FMT_BF16_C8)
             elif as_out:
@@ -236,19 +223,6 @@ class ConvLayer(nn.Module):
 # means far above their spread: rounding THEM to 11 bits was the largest term of the encoder's error, tools/hybrid_rounding_ablation.py),
 # and so does the last time step's ConvLSTM for h' -- the event latents.  A [hi | lo] source enters a convolution as 2 C channels
 # against a weight whose input columns are repeated.
-_dupw_cache = {}
-
-
-def _dup_weight(key, base, cols):
-    """torch.cat([base[:, a:b] for (a, b) in cols], dim=1) of a frozen weight, cached by (key, the weight's identity and version)"""
-    ver = (id(base), base._version, base.data_ptr(), tuple(cols))
-    ent = _dupw_cache.get(key)
-    if ent is None or ent[0] != ver:
-        if len(_dupw_cache) >= 64:
-            _dupw_cache.clear()
-        with torch.no_grad():
-            ent = _dupw_cache[key] = (ver, torch.cat([base.detach()[:, a:b] for (a, b) in cols], dim=1).contiguous())
-    return ent[1]
 
 
 def _half_source(t):
@@ -271,7 +245,7 @@ def _convlayer_forward_mixed(self, x, hilo_out=False, want_fp32=False):
     is_head = hip.h16_of(x) is None and k == 5 and s == 1 and C0 <= 5 and not getattr(x, 'ess_fp32_unwritten', False)
     if is_head:
         spec = hip.conv_spec(N, H, W, C0, 0, c.out_channels, k, s, p, act=act, compute=hip.COMPUTE_F16)
-        scale, shift = self._fold.get(spec, c.bias, self.norm, getattr(self, 'norm_layer', None))
+        scale, shift = _fold(spec, c.bias, self.norm, getattr(self, 'norm_layer', None))
         h16 = hip.f16_blocks_empty(N, c.out_channels, spec.H_out, spec.W_out, x.device)
         if want_fp32:
             out = torch.empty(N, c.out_channels, spec.H_out, spec.W_out, dtype=torch.float32, device=x.device)
@@ -286,7 +260,7 @@ def _convlayer_forward_mixed(self, x, hilo_out=False, want_fp32=False):
         raise hip.EssHipError('ConvLayer(mixed): fp32 outputs exist for the head only')
     s16, hl = _half_source(x)
     Ce = C0 * (2 if hl else 1)
-    w = _dup_weight((id(self), 'dup'), c.weight, [(0, C0), (0, C0)]) if hl else c.weight
+    w = columns(c.weight, [(0, C0), (0, C0)]) if hl else c.weight
     out_fmt = hip.FMT_F16_C8_HILO if hilo_out else hip.FMT_F16_C8
     h16 = hip.f16_blocks_empty(N, c.out_channels, (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1, x.device, hilo=hilo_out)
     s2 = None
@@ -295,11 +269,11 @@ def _convlayer_forward_mixed(self, x, hilo_out=False, want_fp32=False):
         if not hip.s2d_preferred(s2):
             s2 = None
     if s2 is not None:
-        sc, sh = self._fold.get(s2, c.bias, self.norm, getattr(self, 'norm_layer', None))
+        sc, sh = _fold(s2, c.bias, self.norm, getattr(self, 'norm_layer', None))
         hip.conv_forward_h16(s2, s16, None, packed_weight(s2, w, kind=hip.W_CONV5_S2D), sc, sh, out=h16, out_fmt=out_fmt)
     else:
         spec = hip.conv_spec(N, H, W, Ce, 0, c.out_channels, k, s, p, act=act, compute=hip.COMPUTE_F16)
-        sc, sh = self._fold.get(spec, c.bias, self.norm, getattr(self, 'norm_layer', None))
+        sc, sh = _fold(spec, c.bias, self.norm, getattr(self, 'norm_layer', None))
         hip.conv_forward_h16(spec, s16, None, packed_weight(spec, w), sc, sh, out=h16, out_fmt=out_fmt)
     out = _c8_placeholder(N, c.out_channels, h16.shape[2], h16.shape[3], x.device, None)
     del out.ess_c8
@@ -324,28 +298,25 @@ def _convlstm_forward_mixed(self, input_, prev_state, lean, hilo_out):
         hs, hhl = _half_source(prev_hidden)
         C1 = hid * (2 if hhl else 1)
         cols = [(0, C)] * (2 if xhl else 1) + [(C, C + hid)] * (2 if hhl else 1)
-    w = W_ if cols == [(0, C), (C, C + hid)] else _dup_weight((id(self), xhl, hhl, prev_state is None), W_, cols)
+    w = W_ if cols == [(0, C), (C, C + hid)] else columns(W_, cols)
     hilo = bool(hilo_out and lean)
     spec = hip.conv_spec(N, H, W, Cx, C1, 4 * hid, 3, 1, 1, epi=hip.EPI_LSTM, hidden=hid, act=hip.LSTM_H_HILO if hilo else 0,
                          compute=hip.COMPUTE_F16)
     if hilo and (hid % (8 * (spec.plan.cout_tile // 32)) or spec.plan.cout_tile < 64):
         hilo = False
         spec = hip.conv_spec(N, H, W, Cx, C1, 4 * hid, 3, 1, 1, epi=hip.EPI_LSTM, hidden=hid, compute=hip.COMPUTE_F16)
-    b = self.Gates.bias
-    bkey = ('mixed', spec.plan.rows_padded, b._version, b.data_ptr())
-    if getattr(self, '_bias_mixed_ver', None) != bkey:
-        self._bias_mixed_ver, self._bias_mixed = bkey, hip.pack_rows(spec, b.detach())
+    b = packed_rows(spec, self.Gates.bias)
     new16 = hip.f16_blocks_empty(N, hid, H, W, input_.device, hilo=hilo)
     cell, sfmt = _new_cell(N, hid, H, W, input_.device, lean)
     cfmt = hip.FMT_F32_C8 if prev_cell is not None and prev_cell.dim() == 5 else hip.FMT_F32_NCHW
     if lean and sfmt == hip.FMT_F32_C8:
         hidden = _c8_placeholder(N, hid, H, W, input_.device, None)
         del hidden.ess_c8
-        hip.conv_forward_h16(spec, xs, hs, packed_weight(spec, w), None, self._bias_mixed, aux0=prev_cell, out=None, out2=cell, out_h16=new16,
+        hip.conv_forward_h16(spec, xs, hs, packed_weight(spec, w), None, b, aux0=prev_cell, out=None, out2=cell, out_h16=new16,
                              out_fmt=sfmt, aux_fmt=cfmt)
     else:
         hidden = torch.empty(N, hid, H, W, dtype=torch.float32, device=input_.device)
-        hip.conv_forward_h16(spec, xs, hs, packed_weight(spec, w), None, self._bias_mixed, aux0=prev_cell, out=hidden, out2=cell, out_h16=new16,
+        hip.conv_forward_h16(spec, xs, hs, packed_weight(spec, w), None, b, aux0=prev_cell, out=hidden, out2=cell, out_h16=new16,
                              out_fmt=sfmt, aux_fmt=cfmt)
     hip.attach_h16(hidden, new16, hilo)
     return hidden, cell
@@ -365,10 +336,7 @@ def _convgru_forward_mixed(self, input_, prev_state, lean, hilo_out):
     C1 = 0 if first else hid
     cols = [(0, C)] * (2 if xhl else 1) + ([] if first else [(C, C + hid)])
     plain = cols == [(0, C), (C, C + hid)]
-    ws = []
-    for nm, g in (('u', self.update_gate), ('r', self.reset_gate), ('o', self.out_gate)):
-        ws.append(g.weight if plain else _dup_weight((id(self), nm, xhl, first), g.weight, cols))
-    wu, wr, wo = ws
+    wu, wr, wo = (g.weight if plain else columns(g.weight, cols) for g in (self.update_gate, self.reset_gate, self.out_gate))
     hs = None if first else _half_source(prev_state)[0]
     if not first and _half_source(prev_state)[1]:
         raise hip.EssHipError('ConvGRU(mixed): a [hi | lo] hidden state feeds the decoder, not the next time step')
@@ -386,7 +354,7 @@ def _convgru_forward_mixed(self, input_, prev_state, lean, hilo_out):
     if hilo and hid % s2.plan.cout_tile:
         hilo = False
         s2 = hip.conv_spec(N, H, W, Cx, C1, hid, 3, 1, 1, epi=hip.EPI_GRU_OUT, act=uact, hidden=hid, compute=hip.COMPUTE_F16)
-    b1, b2 = self._biases(s1, s2)
+    b1, b2 = packed_rows(s1, self.update_gate.bias, self.reset_gate.bias), packed_rows(s2, self.out_gate.bias)
     pw1, pw2 = packed_weight(s1, wu, wr), packed_weight(s2, wo)
     if afmt == hip.FMT_F32_C8:
         u = hip.f16_c8_raw_empty(N, hid, H, W, dev) if uact == hip.GRU_U_F16 else hip.f32_c8_empty(N, hid, H, W, dev)
@@ -421,7 +389,6 @@ class TransposedConvLayer(nn.Module):
         nl = _norm_container(norm, out_channels)
         if nl is not None:
             self.norm_layer = nl
-        self._fold = _Fold()
 
     def forward(self, x, x1=None):
         """x1: a second source -- the layer acts on the channel concat (x, x1) (skip_type 'concat'), read by the kernel's
@@ -438,7 +405,7 @@ class TransposedConvLayer(nn.Module):
             raise hip.EssHipError('TransposedConvLayer: only k = 2p+1 geometries (output = 2x input) are supported')
         spec = hip.conv_spec(N, 2 * H, 2 * W, C, C1, t.out_channels, k, 1, k - 1 - p, hip.SRC_ZERO_UP2,
                              hip.SRC_ZERO_UP2 if x1 is not None else hip.SRC_DIRECT, act=_ACT[self.activation])
-        scale, shift = self._fold.get(spec, t.bias, self.norm, getattr(self, 'norm_layer', None))
+        scale, shift = _fold(spec, t.bias, self.norm, getattr(self, 'norm_layer', None))
         out = torch.empty(N, t.out_channels, spec.H_out, spec.W_out, dtype=torch.float32, device=x.device)
         return hip.conv_forward(spec, x, x1, packed_weight(spec, t.weight, kind=hip.W_TRANSPOSED), scale, shift, out=out)
 
@@ -460,7 +427,6 @@ class UpsampleConvLayer(nn.Module):
         nl = _norm_container(norm, out_channels)
         if nl is not None:
             self.norm_layer = nl
-        self._fold = _Fold()
 
     def _conv(self, up0, up1=None, c8_only=False):
         """c8_only (bf16 arithmetic, BF16_C8 staging): the output leaves as a BF16_C8 copy only -- for a decoder whose output is
@@ -471,7 +437,7 @@ class UpsampleConvLayer(nn.Module):
         C1 = 0 if up1 is None else (up1.shape[1] * 8 if c8 else up1.shape[1])
         spec = hip.conv_spec(N, H, W, C0, C1, c.out_channels, c.kernel_size[0], c.stride[0], c.padding[0],
                              act=_ACT[self.activation])
-        scale, shift = self._fold.get(spec, c.bias, self.norm, getattr(self, 'norm_layer', None))
+        scale, shift = _fold(spec, c.bias, self.norm, getattr(self, 'norm_layer', None))
         out = torch.empty(N, c.out_channels, spec.H_out, spec.W_out, dtype=torch.float32, device=up0.device)
         copy = hip.bf16_c8_empty(N, c.out_channels, spec.H_out, spec.W_out, up0.device) if (c8_only and c8) else None
         if copy is not None and self.activation in (None, 'relu'):  # (the BF16_C8-output epilogue: see ConvLayer.forward)
@@ -529,7 +495,6 @@ class ConvLSTM(nn.Module):
         self.input_size, self.hidden_size = input_size, hidden_size
         self.zero_tensors = {}
         self.Gates = nn.Conv2d(input_size + hidden_size, 4 * hidden_size, kernel_size, padding=kernel_size // 2)
-        self._bias_ver, self._bias = None, None
 
     def forward(self, input_, prev_state=None, lean=False):
         """lean: (bf16 arithmetic, BF16_C8 path) do not write the fp32 hidden state -- only its BF16_C8 copy and the fp32
@@ -545,10 +510,7 @@ class ConvLSTM(nn.Module):
             return self._first_step(input_, hidden, None, lean)
         prev_hidden, prev_cell = prev_state
         spec = hip.conv_spec(N, H, W, C, hid, 4 * hid, 3, 1, 1, epi=hip.EPI_LSTM, hidden=hid)
-        b = self.Gates.bias
-        ver = (spec.key, b._version, b.data_ptr())
-        if ver != self._bias_ver:
-            self._bias_ver, self._bias = ver, hip.pack_rows(spec, b.detach())
+        b = packed_rows(spec, self.Gates.bias)
         hidden = torch.empty(N, hid, H, W, dtype=torch.float32, device=input_.device)
         # bf16 arithmetic: stage x and h from their BF16_C8 copies when the producers left them (the encoder conv and
         # the previous step of this kernel do), and leave one of h' for the next time step.  Bit-identical to staging
@@ -565,11 +527,11 @@ class ConvLSTM(nn.Module):
         cell, sfmt = _new_cell(N, hid, H, W, input_.device, skip_fp32)
         cfmt = hip.FMT_F32_C8 if prev_cell is not None and prev_cell.dim() == 5 else hip.FMT_F32_NCHW
         if bf and x8 is not None and h8 is not None:
-            hip.conv_forward(spec, x8, h8, packed_weight(spec, self.Gates.weight), None, self._bias, aux0=prev_cell,
+            hip.conv_forward(spec, x8, h8, packed_weight(spec, self.Gates.weight), None, b, aux0=prev_cell,
                              out=None if skip_fp32 else hidden, out2=cell, out_bf=new8, src_fmt=hip.FMT_BF16_C8, out_fmt=sfmt,
                              aux_fmt=cfmt)
         else:
-            hip.conv_forward(spec, _fp32(input_), _fp32(prev_hidden), packed_weight(spec, self.Gates.weight), None, self._bias,
+            hip.conv_forward(spec, _fp32(input_), _fp32(prev_hidden), packed_weight(spec, self.Gates.weight), None, b,
                              aux0=prev_cell, out=None if skip_fp32 else hidden, out2=cell, out_bf=new8, out_fmt=sfmt, aux_fmt=cfmt)
         if new8 is not None:
             _attach_c8(hidden, new8)
@@ -588,15 +550,9 @@ def _new_cell(N, hid, H, W, device, blocked):
 def _convlstm_first_step(self, input_, hidden, cell, lean):
     N, C, H, W = input_.shape
     hid = self.hidden_size
-    w = self.Gates.weight
-    ver = (w._version, w.data_ptr(), C)
-    if getattr(self, '_wx_ver', None) != ver:  # the x columns of the gate weight as their own (packable) tensor
-        self._wx_ver, self._wx = ver, w.detach()[:, :C].contiguous()
+    wx = columns(self.Gates.weight, [(0, C)])  # the x columns of the gate weight as their own (packable) tensor
     spec = hip.conv_spec(N, H, W, C, 0, 4 * hid, 3, 1, 1, epi=hip.EPI_LSTM, hidden=hid)
-    b = self.Gates.bias
-    bver = (spec.key, b._version, b.data_ptr())
-    if getattr(self, '_bias0_ver', None) != bver:
-        self._bias0_ver, self._bias0 = bver, hip.pack_rows(spec, b.detach())
+    b = packed_rows(spec, self.Gates.bias)
     bf = spec.desc.compute == hip.COMPUTE_BF16 and (C % 8) == 0
     stage8 = bf and hip.c8_stageable(3, 1, 1)
     x8 = _c8_of(input_) if stage8 else None
@@ -604,10 +560,10 @@ def _convlstm_first_step(self, input_, hidden, cell, lean):
     skip_fp32 = lean and new8 is not None and stage8
     cell, sfmt = _new_cell(N, hid, H, W, input_.device, skip_fp32)
     if x8 is not None:
-        hip.conv_forward(spec, x8, None, packed_weight(spec, self._wx), None, self._bias0, aux0=None,
+        hip.conv_forward(spec, x8, None, packed_weight(spec, wx), None, b, aux0=None,
                          out=None if skip_fp32 else hidden, out2=cell, out_bf=new8, src_fmt=hip.FMT_BF16_C8, out_fmt=sfmt)
     else:
-        hip.conv_forward(spec, _fp32(input_), None, packed_weight(spec, self._wx), None, self._bias0, aux0=None,
+        hip.conv_forward(spec, _fp32(input_), None, packed_weight(spec, wx), None, b, aux0=None,
                          out=None if skip_fp32 else hidden, out2=cell, out_bf=new8, out_fmt=sfmt)
     if new8 is not None:
         _attach_c8(hidden, new8)
@@ -641,25 +597,6 @@ class ConvGRU(nn.Module):
         for g in (self.reset_gate, self.update_gate, self.out_gate):
             init.orthogonal_(g.weight)
             init.constant_(g.bias, 0.)
-        self._bias_cache = {}
-
-    def _biases(self, s1, s2):
-        bu, br, bo = self.update_gate.bias, self.reset_gate.bias, self.out_gate.bias
-        ver = (bu._version, br._version, bo._version, bu.data_ptr(), br.data_ptr(), bo.data_ptr())
-        ent = self._bias_cache.get((s1.key, s2.key))
-        if ent is None or ent[0] != ver:
-            if len(self._bias_cache) >= 8:
-                self._bias_cache.clear()
-            ent = self._bias_cache[(s1.key, s2.key)] = (ver, hip.pack_rows(s1, bu.detach(), br.detach()), hip.pack_rows(s2, bo.detach()))
-        return ent[1], ent[2]
-
-    def _x_columns(self, C):
-        """The x columns of the three gate weights as their own (packable) tensors: the first step of a sequence (h = 0)."""
-        ws = (self.update_gate.weight, self.reset_gate.weight, self.out_gate.weight)
-        ver = tuple((w._version, w.data_ptr()) for w in ws) + (C,)
-        if getattr(self, '_wx_ver', None) != ver:
-            self._wx_ver, self._wx = ver, tuple(w.detach()[:, :C].contiguous() for w in ws)
-        return self._wx
 
     def forward(self, input_, prev_state, lean=False):
         """lean: (bf16 arithmetic, BF16_C8 path) do not write the fp32 NCHW state -- only its BF16_C8 copy and the channel-blocked
@@ -684,9 +621,10 @@ class ConvGRU(nn.Module):
             uact = hip.GRU_U_F32
             s1 = hip.conv_spec(N, H, W, C, C1, 2 * hid, 3, 1, 1, epi=hip.EPI_GRU_UR, act=uact, hidden=hid)
             s2 = hip.conv_spec(N, H, W, C, C1, hid, 3, 1, 1, epi=hip.EPI_GRU_OUT, act=uact, hidden=hid)
-        b1, b2 = self._biases(s1, s2)
+        b1, b2 = packed_rows(s1, self.update_gate.bias, self.reset_gate.bias), packed_rows(s2, self.out_gate.bias)
         if first:
-            wu, wr, wo = self._x_columns(C)
+            # the x columns of the three gate weights as their own (packable) tensors
+            wu, wr, wo = (columns(g.weight, [(0, C)]) for g in (self.update_gate, self.reset_gate, self.out_gate))
         else:
             wu, wr, wo = self.update_gate.weight, self.reset_gate.weight, self.out_gate.weight
         pw1, pw2 = packed_weight(s1, wu, wr), packed_weight(s2, wo)
@@ -801,7 +739,6 @@ class ResidualBlock(nn.Module):
         self.relu = nn.ReLU(inplace=True)
         self.conv2 = nn.Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=bias)
         self.downsample = downsample
-        self._f1, self._f2 = _Fold(), _Fold()
 
     def forward(self, x, c8_only=False):
         """c8_only (bf16 arithmetic, fused norms, x carries a BF16_C8 copy): both convolutions read and write BF16_C8 tensors --
@@ -817,8 +754,8 @@ class ResidualBlock(nn.Module):
         if x8 is not None:
             s1 = hip.conv_spec(N, H, W, C, 0, self.conv1.out_channels, 3, 1, 1, act=hip.ACT_RELU)
             s2 = hip.conv_spec(N, H, W, self.conv1.out_channels, 0, self.conv2.out_channels, 3, 1, 1, act=hip.ACT_RELU)
-            sc1, sh1 = self._f1.get(s1, self.conv1.bias, 'BN' if bn else None, getattr(self, 'bn1', None))
-            sc2, sh2 = self._f2.get(s2, self.conv2.bias, 'BN' if bn else None, getattr(self, 'bn2', None))
+            sc1, sh1 = _fold(s1, self.conv1.bias, 'BN' if bn else None, getattr(self, 'bn1', None))
+            sc2, sh2 = _fold(s2, self.conv2.bias, 'BN' if bn else None, getattr(self, 'bn2', None))
             o8 = hip.bf16_c8_empty(N, self.conv1.out_channels, H, W, x.device)
             hip.conv_forward(s1, x8, None, packed_weight(s1, self.conv1.weight), sc1, sh1, out=o8, src_fmt=hip.FMT_BF16_C8,
                              out_fmt=hip.FMT_BF16_C8)
@@ -832,8 +769,8 @@ class ResidualBlock(nn.Module):
         s1 = hip.conv_spec(N, H, W, C, 0, self.conv1.out_channels, 3, 1, 1, act=hip.ACT_RELU if fused else hip.ACT_NONE)
         s2 = hip.conv_spec(N, H, W, self.conv1.out_channels, 0, self.conv2.out_channels, 3, 1, 1,
                            act=hip.ACT_RELU if fused else hip.ACT_NONE)
-        sc1, sh1 = self._f1.get(s1, self.conv1.bias, 'BN' if bn else None, getattr(self, 'bn1', None))
-        sc2, sh2 = self._f2.get(s2, self.conv2.bias, 'BN' if bn else None, getattr(self, 'bn2', None))
+        sc1, sh1 = _fold(s1, self.conv1.bias, 'BN' if bn else None, getattr(self, 'bn1', None))
+        sc2, sh2 = _fold(s2, self.conv2.bias, 'BN' if bn else None, getattr(self, 'bn2', None))
         o = torch.empty(N, self.conv1.out_channels, H, W, dtype=torch.float32, device=x.device)
         x = _fp32(x)  # (an unwritten lean-state placeholder must not be read as fp32)
         hip.conv_forward(s1, x, None, packed_weight(s1, self.conv1.weight), sc1, sh1, out=o)

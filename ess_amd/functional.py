@@ -9,8 +9,6 @@ import torch
 
 from . import hip
 
-_pack_cache = {}
-
 # When True (set by ess_amd.utils.radam.RAdam), the weight-gradient kernels add straight into an existing leaf `.grad`
 # (a view of the optimiser's flat gradient buffer) instead of materialising dW and letting AccumulateGrad add it.
 DIRECT_GRAD_ACCUM = False
@@ -88,96 +86,150 @@ def discard_deferred_wgrads():
 GRAD_READY_HOOK = None
 
 
-def packed_weight(spec, w, w2=None, kind=hip.W_CONV):
-    """Tile-major re-layout of a weight tensor, cached until the tensor is modified in place
-    (``_version`` bump: optimiser step, load_state_dict) or freed."""
-    ent = _pack_cache.get(id(w))
-    ver = (w._version, w2._version if w2 is not None else -1, w.data_ptr())
-    if ent is None or ent[0]() is not w or ent[1] != ver:
-        ent = (weakref.ref(w, lambda _, k=id(w): _pack_cache.pop(k, None)), ver, {})
-        _pack_cache[id(w)] = ent
-    key = (spec.key, kind)
-    pw = ent[2].get(key)
-    if pw is None:
-        pw = ent[2][key] = hip.pack_weights(spec, w.detach(), None if w2 is None else w2.detach(), kind)
-    return pw
+# ---- tensors derived from weights.  The kernels never read a parameter itself: they read tile-major packs, tile-padded bias rows,
+# folded eval-mode norms, and column copies of it (weight[:, :C], [w | w]) -- and packs of those copies.  All of them live in ONE
+# store with ONE validity rule: an entry is valid while every source is the same live object with the same _version, data_ptr() and
+# generation.  A kernel that rewrites a tensor through a raw pointer (the flat RAdam step, a graph replay) moves neither _version nor
+# data_ptr(): invalidate / refresh / drop_unowned bump the generation of what it wrote instead.  An entry is filed under its first
+# source, the root (weakly referenced: the entry dies with it); an entry built from a column copy is filed under the copy's root,
+# marked with the copy's transform, so dropping a parameter's entries drops the packs of its copies too.
+IDENTITY, FIRST_COLUMNS, REPEATED_COLUMNS = 0, 1, 2
+_store = {}  # id(root) -> (weakref(root), {key: _Entry})
 
 
-def packed_rows(spec, v):
-    """Tile-padded copy of a per-output-channel vector (a conv bias), cached like packed_weight."""
-    ent = _pack_cache.get(id(v))
-    ver = (v._version, -1, v.data_ptr())
-    if ent is None or ent[0]() is not v or ent[1] != ver:
-        ent = (weakref.ref(v, lambda _, k=id(v): _pack_cache.pop(k, None)), ver, {})
-        _pack_cache[id(v)] = ent
-    key = (spec.plan.rows_padded, spec.desc.epilogue, 'rows')
-    pr = ent[2].get(key)
-    if pr is None:
-        pr = ent[2][key] = hip.pack_rows(spec, v.detach())
-        pr.ess_spec = spec  # (repack() refreshes LINEAR bias rows in place through the multi-tensor launch)
-    return pr
+class _Entry:
+    __slots__ = ('refs', 'stamp', 'value', 'transform')
+
+    def __init__(self, refs, stamp, value, transform):
+        self.refs, self.stamp, self.value, self.transform = refs, stamp, value, transform
 
 
-def invalidate_packed(params):
-    """Drop cached re-layouts of tensors that a kernel modified through a raw pointer (the flat RAdam update does
-    not bump ``_version``)."""
+def _stamp(sources):
+    return tuple([(s._version, s.data_ptr(), getattr(s, '_ess_gen', 0)) for s in sources])
+
+
+def _entries(root):
+    box = _store.get(id(root))
+    return box[1] if box is not None and box[0]() is root else None
+
+
+def derived(sources, key, build, transform=IDENTITY):
+    """The cached value of build() for (sources, key); rebuilt when a source changed (see above).  A column copy (transform
+    FIRST_COLUMNS / REPEATED_COLUMNS) remembers where it came from, so whatever is derived from it is filed under its root."""
+    base = getattr(sources[0], '_ess_derived', None)
+    if base is not None:
+        refs, bkey, transform = base
+        sources = tuple(r() for r in refs) + tuple(sources[1:])
+        if any(s is None for s in sources):
+            return build()
+        key = (bkey, key)
+    root = sources[0]
+    ents = _entries(root)
+    if ents is None:
+        ents = {}
+        _store[id(root)] = (weakref.ref(root, lambda _, k=id(root): _store.pop(k, None)), ents)
+    stamp = _stamp(sources)
+    e = ents.get(key)
+    if e is not None and e.stamp == stamp and (len(sources) == 1 or all(r() is s for r, s in zip(e.refs, sources))):
+        return e.value
+    value = build()
+    refs = tuple(weakref.ref(s) for s in sources)
+    if transform != IDENTITY:
+        value._ess_derived = (refs, key, transform)
+    ents[key] = _Entry(refs, stamp, value, transform)
+    return value
+
+
+def _bump(p):
+    p._ess_gen = getattr(p, '_ess_gen', 0) + 1
+
+
+def invalidate(params):
+    """Every entry that one of `params` is a source of goes stale (a kernel rewrote them through raw pointers: a broadcast)."""
     for p in params:
-        _pack_cache.pop(id(p), None)
-        _first_cache.pop(id(p), None)
-        for key in [k for k in _dup_cache if k[0] == id(p)]:
-            _dup_cache.pop(key, None)
+        _bump(p)
+        _store.pop(id(p), None)
 
 
-_first_cache = {}
-
-
-def _first_inputs(weight, c0):
-    """Contiguous copy of weight[:, :c0] (the filters of a concat convolution's FIRST source), cached like the packed
-    layouts: used when only that source needs a data-gradient, so the kernel does not compute the other one's channels."""
-    ent = _first_cache.get(id(weight))
-    ver = (weight._version, weight.data_ptr(), c0)
-    if ent is None or ent[0]() is not weight or ent[1] != ver:
-        with torch.no_grad():
-            sub = weight.detach()[:, :c0].contiguous()
-        ent = (weakref.ref(weight, lambda _, k=id(weight): _first_cache.pop(k, None)), ver, sub)
-        _first_cache[id(weight)] = ent
-    return ent[2]
-
-
-def repack(params):
-    """After a kernel rewrote `params` through raw pointers (the flat RAdam step): refresh their cached re-layouts IN
-    PLACE with one multi-tensor launch instead of dropping them and re-packing tensor by tensor on next use (2 layouts per
-    trainable convolution: ~65 launches of ~5 us per step).  Layouts the multi-tensor kernel does not cover are dropped."""
+def refresh(params):
+    """After the flat RAdam step rewrote `params`: re-pack IN PLACE, in one multi-tensor launch, the layouts that launch covers --
+    bf16 / half LINEAR packs of a 4-D parameter itself (not 5x5), and (switch ESS_REPACK_ROWS) LINEAR bias rows of the parameter
+    itself -- instead of ~65 single-tensor packs of ~5 us on next use.  Every other entry of `params` goes stale."""
+    rows = os.environ.get('ESS_REPACK_ROWS', '1')[:1] != '0'
     jobs = []
     for p in params:
-        _first_cache.pop(id(p), None)  # derived copies: rebuilt on next use
-        for dk in [k for k in _dup_cache if k[0] == id(p)]:
-            _dup_cache.pop(dk, None)
-        ent = _pack_cache.get(id(p))
-        if ent is None or ent[0]() is not p:
+        ents = _entries(p)
+        cur = _stamp((p,))
+        _bump(p)
+        if ents is None:
             continue
-        if ent[1] != (p._version, -1, p.data_ptr()):
-            _pack_cache.pop(id(p), None)
-            continue
-        for key in list(ent[2]):
-            if key[-1] == 'rows':
-                # bias rows of a plain bf16 convolution ride in the same launch (round 5: 21 pack_rows launches per step otherwise);
-                # any other row layout is dropped and re-packed lazily
-                sp = getattr(ent[2][key], 'ess_spec', None)
-                if sp is not None and p.dim() == 1 and sp.key[11] == hip.EPI_LINEAR and sp.key[15] in (hip.COMPUTE_BF16, hip.COMPUTE_F16) and \
-                        os.environ.get('ESS_REPACK_ROWS', '1')[:1] != '0':
-                    jobs.append((sp, hip.W_ROWS, p.detach(), ent[2][key]))
-                else:
-                    del ent[2][key]
-                continue
-            skey, kind = key
-            k, epi, compute = skey[8], skey[11], skey[15]
-            if compute in (hip.COMPUTE_BF16, hip.COMPUTE_F16) and epi == hip.EPI_LINEAR and k != 5 and p.dim() == 4:
-                jobs.append((hip.spec_of(skey), kind, p.detach(), ent[2][key]))
+        for key, e in list(ents.items()):
+            job = None
+            if e.transform == IDENTITY and e.stamp == cur:  # (a single-source entry, current before the step)
+                if key[0] == 'rows':
+                    sp = e.value.ess_spec
+                    if rows and p.dim() == 1 and sp.key[11] == hip.EPI_LINEAR and sp.key[15] in (hip.COMPUTE_BF16, hip.COMPUTE_F16):
+                        job = (sp, hip.W_ROWS)
+                elif key[0] == 'pack':
+                    _, skey, kind = key
+                    if skey[15] in (hip.COMPUTE_BF16, hip.COMPUTE_F16) and skey[11] == hip.EPI_LINEAR and skey[8] != 5 and p.dim() == 4:
+                        job = (hip.spec_of(skey), kind)
+            if job is None:
+                del ents[key]
             else:
-                del ent[2][key]
+                jobs.append(job + (p.detach(), e.value))
+                e.stamp = _stamp((p,))
     if jobs:
         hip.pack_weights_multi(jobs)
+
+
+def snapshot(params):
+    """At the capture of a step that ends in refresh(params): (the keys each of `params` owns -- the entries the replays refresh --,
+    references to every derived tensor alive now -- what the recorded kernels read must outlive any eviction)."""
+    owned = {id(p): set(_entries(p) or ()) for p in params}
+    return owned, [e.value for _, ents in _store.values() for e in ents.values()]
+
+
+def drop_unowned(params, snap):
+    """After a replay rewrote `params`: entries the captured step does not own (made by eager calls between replays) go stale."""
+    for p in params:
+        _bump(p)
+        ents = _entries(p)
+        own = snap[0].get(id(p), ())
+        for key, e in list((ents or {}).items()):
+            if key in own:
+                e.stamp = _stamp((p,))
+            else:
+                del ents[key]
+
+
+def packed_weight(spec, w, w2=None, kind=hip.W_CONV):
+    """Tile-major re-layout of a weight (GRU update gate: with the reset gate's as w2)."""
+    return derived((w,) if w2 is None else (w, w2), ('pack', spec.key, kind),
+                   lambda: hip.pack_weights(spec, w.detach(), None if w2 is None else w2.detach(), kind))
+
+
+def packed_rows(spec, v, v2=None):
+    """Tile-padded copy of a per-output-channel vector (a conv bias; GRU update gate: with the reset gate's as v2)."""
+    def build():
+        pr = hip.pack_rows(spec, v.detach(), None if v2 is None else v2.detach())
+        pr.ess_spec = spec  # (refresh() re-packs LINEAR bias rows in place through the multi-tensor launch)
+        return pr
+    return derived((v,) if v2 is None else (v, v2), ('rows', spec.plan.rows_padded, spec.desc.epilogue), build)
+
+
+def columns(weight, cols):
+    """torch.cat([weight[:, a:b] for (a, b) in cols], dim=1): the first source's filters of a concat convolution (data-gradient of
+    that source alone, the first step of a recurrent block), or the input columns of a [hi | lo] source repeated -- w (hi + lo) on
+    the matrix cores is the plain convolution over the 2 C-channel source against this weight."""
+    cols = tuple(cols)
+    tf = FIRST_COLUMNS if len(cols) == 1 and cols[0][0] == 0 else REPEATED_COLUMNS
+
+    def build():
+        with torch.no_grad():
+            w = weight.detach()
+            return torch.cat([w[:, a:b] for (a, b) in cols], dim=1).contiguous()
+    return derived((weight,), ('cols', cols), build, tf)
 
 
 def _virt(x, mode):
@@ -216,27 +268,6 @@ def half_of(x):
     if c is not None:
         return c
     return hip.bf16_c8_to_f16_c8(x.detach().contiguous()), False
-
-
-_dup_cache = {}
-
-
-def _dup_columns(weight, c0, dup0, c1, dup1):
-    """weight [Cout, c0 + c1, k, k] with the input columns of a [hi | lo] source repeated: [w0 | w0 | w1 | w1] as needed -- w (hi + lo)
-    on the matrix cores is the plain convolution over the 2 C-channel source against this weight.  Cached like the packed layouts."""
-    if not (dup0 or dup1):
-        return weight
-    key = (id(weight), c0, dup0, c1, dup1)
-    ver = (weight._version, weight.data_ptr())
-    ent = _dup_cache.get(key)
-    if ent is None or ent[0]() is not weight or ent[1] != ver:
-        with torch.no_grad():
-            w = weight.detach()
-            parts = [w[:, :c0]] * (2 if dup0 else 1) + ([w[:, c0:]] * (2 if dup1 else 1) if c1 else [])
-            d = torch.cat(parts, dim=1).contiguous()
-        ent = (weakref.ref(weight, lambda _, k=key: _dup_cache.pop(k, None)), ver, d)
-        _dup_cache[key] = ent
-    return ent[2]
 
 
 def _hilo_placeholder(N, C, H, W, device, buf):
@@ -417,7 +448,6 @@ class Conv2dFn(torch.autograd.Function):
         if weight.shape[1] != C0 + C1:
             raise hip.EssHipError(f'Conv2dFn: weight expects {weight.shape[1]} input channels, got {C0}+{C1}')
         spec = hip.conv_spec(N, Hv, Wv, C0, C1, Cout, k, stride, pad, mode0, mode1)
-        shift = packed_rows(spec, bias) if bias is not None else None
         if half and c8in and hip.mixed():
             # mixed configuration (decoder convolutions): the FORWARD contraction on IEEE-half operands -- the sources' half copies
             # (the norm kernels / the frozen encoder leave them; a [hi | lo] pair enters as 2 C channels against repeated weight
@@ -426,7 +456,9 @@ class Conv2dFn(torch.autograd.Function):
             h1, hl1 = half_of(x1) if x1 is not None else (None, False)
             fspec = hip.conv_spec(N, Hv, Wv, C0 * (2 if hl0 else 1), C1 * (2 if hl1 else 1), Cout, k, stride, pad, mode0, mode1,
                                   compute=hip.COMPUTE_F16)
-            pw = packed_weight(fspec, _dup_columns(weight, C0, hl0, C1, hl1))
+            cols = [(0, C0)] * (2 if hl0 else 1) + ([(C0, C0 + C1)] * (2 if hl1 else 1) if C1 else [])
+            pw = packed_weight(fspec, columns(weight, cols) if (hl0 or hl1) else weight)
+            shift = packed_rows(fspec, bias) if bias is not None else None
             if out_c8 == PRE_NORM_HILO:
                 buf = hip.f16_blocks_empty(N, Cout, spec.H_out, spec.W_out, x0.device, hilo=True)
                 hip.conv_forward_h16(fspec, h0, h1, pw, None, shift, out=buf, out_fmt=hip.FMT_F16_C8_HILO)
@@ -442,6 +474,7 @@ class Conv2dFn(torch.autograd.Function):
         else:
             if out_c8 == PRE_NORM_HILO:
                 out_c8 = PRE_NORM
+            shift = packed_rows(spec, bias) if bias is not None else None
             out = _empty_act(N, Cout, spec.H_out, spec.W_out, x0.device, out_c8)
             hip.conv_forward(spec, x0, x1, packed_weight(spec, weight), None, shift, out=out, src_fmt=_fmt(x0),
                              out_fmt=hip.FMT_F16_C8 if out_c8 == PRE_NORM else _fmt(out))
@@ -468,7 +501,7 @@ class Conv2dFn(torch.autograd.Function):
             if C1 > 0 and need0 and not need1:
                 # only the first source wants a gradient (the second is a detached skip latent): contract with its filters
                 # alone instead of computing and discarding the other source's channels
-                wd, c_dg, split = _first_inputs(weight, C0), C0, 0
+                wd, c_dg, split = columns(weight, [(0, C0)]), C0, 0
             # a nearest-upsampled first source: its gradient is the 2x2 sum-pool of the virtual-resolution data-gradient;
             # the kernel pools in its epilogue (ACT_SUMPOOL2) instead of writing the full-resolution tensor for a pool pass
             pool0 = s == 1 and need0 and mode0 == hip.SRC_NEAREST_UP2 and (C1 == 0 or mode1 == hip.SRC_DIRECT) and \

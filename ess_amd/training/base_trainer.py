@@ -9,6 +9,7 @@ import os
 
 import torch
 
+from .. import functional as Fn
 from ..utils.saver import CheckpointSaver
 from . import distributed as D
 from .synthetic import SyntheticPairedLoader
@@ -139,15 +140,15 @@ class BaseTrainer(object):
         self._graph_adopt_packed()
         return self
 
-    # ---- packed-weight cache vs the captured step.  A replay rewrites the weights through raw pointers (the RAdam kernel) and
-    # refreshes, IN PLACE, exactly the packed copies that existed when the step was captured (functional.repack ran once, at
-    # capture time: its python half -- dropping bias rows, layouts the multi-tensor pack does not cover, the first-source filter
-    # copies -- is not part of the graph).  So (i) cache entries created by an eager forward BETWEEN replays (validation: another
-    # batch size, eval-mode specs, bias rows) are never refreshed and would go stale: they are dropped after every replay;
-    # (ii) the packed tensors the graph reads must outlive any cache eviction (load_state_dict / broadcast / invalidate_packed bump
-    # versions and would free them under the graph): the trainer holds references; (iii) when parameters or buffers were replaced
-    # or modified outside the captured step (their version counters moved), the graph's packed copies no longer match the weights:
-    # the step is re-captured (without warm-up steps) before the next replay.
+    # ---- derived weight tensors (functional.derived: packs, bias rows, column copies) vs the captured step.  A replay rewrites the
+    # weights through raw pointers (the RAdam kernel) and refreshes, IN PLACE, exactly the entries that existed when the step was
+    # captured (functional.refresh ran once, at capture time: its python half -- which entries it re-packs and which it drops -- is
+    # not part of the graph).  So (i) entries an eager call creates BETWEEN replays (validation: another batch size, eval-mode specs,
+    # bias rows, column copies and their packs) are never refreshed and would go stale: functional.drop_unowned drops them after
+    # every replay; (ii) the tensors the graph reads must outlive any eviction (load_state_dict / broadcast / invalidate): the
+    # snapshot holds references; (iii) when parameters or buffers were replaced or modified outside the captured step (their
+    # version counters moved), the graph's packed copies no longer match the weights: the step is re-captured (without warm-up
+    # steps) before the next replay.
     def _graph_models_signature(self):
         sig = []
         for m in self.models_dict.values():
@@ -155,30 +156,12 @@ class BaseTrainer(object):
                 sig.append((t.data_ptr(), t._version))
         return tuple(sig)
 
-    def _graph_adopt_packed(self):
-        from .. import functional as Fn
-        owned, keep = {}, []
-        for o in self.optimizers_dict.values():
-            for p in o.param_groups[0]['params']:
-                ent = Fn._pack_cache.get(id(p))
-                if ent is not None and ent[0]() is p:
-                    owned[id(p)] = set(ent[2])
-        for ent in Fn._pack_cache.values():  # (every packed copy alive now may be read by the recorded kernels)
-            keep.extend(ent[2].values())
-        self._g_owned, self._g_keep = owned, keep
-        self._g_sig = self._graph_models_signature()
+    def _optimised_params(self):
+        return [p for o in self.optimizers_dict.values() for p in o.param_groups[0]['params']]
 
-    def _graph_drop_foreign_packed(self):
-        from .. import functional as Fn
-        for o in self.optimizers_dict.values():
-            for p in o.param_groups[0]['params']:
-                Fn._first_cache.pop(id(p), None)
-                ent = Fn._pack_cache.get(id(p))
-                if ent is None:
-                    continue
-                own = self._g_owned.get(id(p), ())
-                for key in [k for k in ent[2] if k not in own]:
-                    del ent[2][key]
+    def _graph_adopt_packed(self):
+        self._g_snapshot = Fn.snapshot(self._optimised_params())
+        self._g_sig = self._graph_models_signature()
 
     def _replay_step(self, batch):
         flat = [t for part in batch for t in (part if isinstance(part, (list, tuple)) else [part])]
@@ -211,7 +194,7 @@ class BaseTrainer(object):
             self._g_tail.replay()
         for o in opts:
             o._prepared = False  # consumed by the replayed optimiser launch (an eager step() afterwards prepares its own scalars)
-        self._graph_drop_foreign_packed()
+        Fn.drop_unowned(self._optimised_params(), self._g_snapshot)
         vec = self._g_vec.clone()  # the graph's own buffers are overwritten by the next replay
         return {k: vec[i] for i, k in enumerate(self._g_keys)}, self._g_outputs, vec[-1]
 

@@ -217,4 +217,4 @@ def broadcast_module(module, src=0):
     with torch.no_grad():
         for t in list(module.parameters()) + list(module.buffers()):
             dist.broadcast(t.detach(), src)  # (detach() shares storage AND version counter, unlike .data)
-    Fn.invalidate_packed(module.parameters())  # cached tile-major copies of the old weights
+    Fn.invalidate(list(module.parameters()) + list(module.buffers()))  # what was derived from the old weights

@@ -13,7 +13,7 @@ from torch.optim.optimizer import Optimizer
 
 from .. import hip
 from .. import functional as _fn
-from ..functional import repack
+from ..functional import refresh
 
 
 class RAdam(Optimizer):
@@ -127,7 +127,7 @@ class RAdam(Optimizer):
         self._prepared = False
         beta1, beta2 = group['betas']
         hip.radam_step_dev(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, beta1, beta2, group['eps'], self._hyper)
-        repack(group['params'])  # the kernel wrote the weights behind autograd's back: refresh their packed copies
+        refresh(group['params'])  # the kernel wrote the weights behind autograd's back: refresh their packed copies
         self._bind_grads()
         return loss
 

@@ -63,8 +63,9 @@ def test_captured_step_is_bit_identical_to_eager(kind, mode):
         hip.set_compute('fp32')
 
 
-@pytest.mark.parametrize('kind', ['ess', 'ess_supervised'])
-def test_captured_step_interleaved_with_eager_forwards(kind):
+@pytest.mark.parametrize('kind,mode', [pytest.param('ess', 'bf16', id='ess'), pytest.param('ess_supervised', 'bf16', id='ess_supervised'),
+                                       ('ess', 'mixed'), ('ess_supervised', 'mixed')])
+def test_captured_step_interleaved_with_eager_forwards(kind, mode):
     """Replays interleaved with eager forwards (validation between training steps) and with weights replaced under the graph:
     a replay refreshes only the packed weight copies it was captured with, so cache entries an eager forward creates in between
     (another batch size, eval-mode specs, bias rows) must not survive it, and a load_state_dict after capture must reach the
@@ -74,7 +75,7 @@ def test_captured_step_interleaved_with_eager_forwards(kind):
     try:
         runs = []
         for graph in (False, True):
-            tr = _trainer(kind, 'bf16', shape)
+            tr = _trainer(kind, mode, shape)
             b0 = _batch(kind, shape, 300)
             if graph:
                 tr.enable_step_graph(b0, warmup=2)

@@ -656,3 +656,75 @@ def test_data_parallel_world8_gloo_buckets_validation_broadcast():
         assert changed == 1.0, (r, row)  # every non-zero rank's weights were replaced by rank 0's
         assert n_b == 3.0 and max_fired == 3.0, (r, row)  # all three buckets were issued from inside the (simulated) backward
     assert all(w == ws[0] for w in ws)
+
+
+def test_derived_weight_store_contract():
+    """functional.derived: one store, one validity rule for every tensor derived from a weight (CPU tensors, a counting build)."""
+    import gc
+
+    from ess_amd import functional as Fn
+    w, b = torch.randn(4, 6, 3, 3), torch.randn(4)
+    builds = []
+
+    def get(sources, key='k'):
+        return Fn.derived(sources, key, lambda: builds.append(key) or torch.zeros(1))
+    # an in-place op (_version) and a replaced .data (data_ptr) rebuild the entry
+    v = get((w,))
+    assert get((w,)) is v and len(builds) == 1
+    w.mul_(1.0)
+    assert get((w,)) is not v and len(builds) == 2
+    w.data = w.data.clone()
+    get((w,))
+    get((w,))
+    assert len(builds) == 3
+    # invalidate: of the root, and of a non-root source only
+    get((w, b), 'wb')
+    assert len(builds) == 4
+    Fn.invalidate([w])
+    get((w,))
+    get((w, b), 'wb')
+    assert len(builds) == 6
+    Fn.invalidate([b])
+    get((w,))
+    assert len(builds) == 6
+    get((w, b), 'wb')
+    assert len(builds) == 7
+    # a derivation chain is filed under its root: dropping the root's entries drops the packs of its copies
+    cols = Fn.columns(w, [(0, 2), (0, 2)])
+    assert torch.equal(cols, torch.cat([w[:, :2], w[:, :2]], 1)) and Fn.columns(w, [(0, 2), (0, 2)]) is cols
+    first = Fn.columns(w, [(0, 2)])
+    assert torch.equal(first, w[:, :2])
+    get((cols,), 'pack')
+    get((first,), 'pack')
+    get((cols,), 'pack')
+    assert len(builds) == 9
+    ents = Fn._entries(w)
+    assert ents[(('cols', ((0, 2), (0, 2))), 'pack')].transform == Fn.REPEATED_COLUMNS
+    assert ents[(('cols', ((0, 2),)), 'pack')].transform == Fn.FIRST_COLUMNS
+    Fn.invalidate([w])
+    assert Fn._entries(w) is None
+    get((Fn.columns(w, [(0, 2), (0, 2)]),), 'pack')
+    assert len(builds) == 10
+    # snapshot / drop_unowned: owned keys survive (their entries stay valid), everything else under the parameter is dropped
+    get((w,))
+    snap = Fn.snapshot([w])
+    assert all(k in snap[0][id(w)] for k in Fn._entries(w))
+    owned = get((w,))
+    get((w,), 'eager')
+    get((Fn.columns(w, [(0, 3)]),), 'pack')
+    n = len(builds)
+    Fn.drop_unowned([w], snap)
+    assert get((w,)) is owned and len(builds) == n
+    assert ('eager' not in Fn._entries(w)) and (('cols', ((0, 3),)), 'pack') not in Fn._entries(w)
+    get((w,), 'eager')
+    assert len(builds) == n + 1
+    # refresh keeps no pack of a column copy (nothing here is a layout the multi-tensor launch re-packs: no launch)
+    get((Fn.columns(w, [(0, 3)]),), 'pack')
+    Fn.refresh([w])
+    assert Fn._entries(w) == {}
+    # entries die with their root
+    del snap, owned, v, cols, first
+    rid = id(w)
+    del w
+    gc.collect()
+    assert rid not in Fn._store
