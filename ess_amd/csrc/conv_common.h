@@ -1508,9 +1508,16 @@ inline int validate(const EssConvDesc* d) {
                   "conv(f16): 16-bit tensors of a half-operand convolution are ESS_FMT_F16_C8");
     ESS_CHECK_ARG(d->act != ESS_ACT_SUMPOOL2 || d->epilogue != ESS_EPI_LINEAR, "conv(f16): no pooled (data-gradient) form");
     ESS_CHECK_ARG(d->mode0 != ESS_SRC_ZERO_UP2 && d->mode1 != ESS_SRC_ZERO_UP2, "conv(f16): no zero-inserted sources");
-    if (d->epilogue == ESS_EPI_LINEAR && d->fmt_out == ESS_FMT_F16_C8_HILO)
+    if (d->epilogue == ESS_EPI_LINEAR && d->fmt_out == ESS_FMT_F16_C8_HILO) {
       ESS_CHECK_ARG(d->out_split == 0 && (d->act == ESS_ACT_NONE || d->act == ESS_ACT_RELU) && (d->C_out % 64) == 0,
                     "conv(f16): a [hi | lo] output needs act in {none, relu}, no out_split, C_out %% 64 == 0");
+      // the lo blocks are written by the straight-line epilogue only, which needs every channel of a workgroup's tile: the plan's tile
+      // (make_plan: 128 channels once a doubled [hi | lo] source reaches 512 input channels) must divide C_out
+      const ResolvedDesc rt = resolve_compute(d);
+      const int cot = pick_mb(&rt.d) * 32;
+      ESS_CHECK_ARG((d->C_out % cot) == 0, "conv(f16): a [hi | lo] output needs whole channel tiles: C_out %d is not a multiple of the plan's %d-channel tile",
+                    d->C_out, cot);
+    }
     if (d->epilogue == ESS_EPI_LSTM) ESS_CHECK_ARG(d->act == 0 || d->act == ESS_LSTM_H_HILO, "conv(f16, LSTM): act is 0 or ESS_LSTM_H_HILO");
     if (d->epilogue == ESS_EPI_GRU_UR) ESS_CHECK_ARG(d->act == ESS_GRU_U_F32 || d->act == ESS_GRU_U_F16, "conv(f16, GRU_UR): act is ESS_GRU_U_F32 or ESS_GRU_U_F16");
     const ResolvedDesc r = resolve_compute(d);

@@ -423,10 +423,18 @@ __global__ __launch_bounds__(256) void c8_reduce_kernel(const u32x4n* __restrict
         unpack8x(xv[u], f, xf16);
         if (MODE == 0) {
           if (xcb > 0) {  // (uniform)
+            // hi + lo carries ~22 significant bits: its fp32 square and fp32 partial sums round, and E[x^2] - m^2 amplifies that
+            // rounding by m^2 / sigma^2 (the event latents: 6-30 sigma) -- measured biased, not random: a near-constant channel's rstd
+            // 1 % off.  The pair's sums go to fp64 directly (exact squares; this path only serves planes above 5120 pixels)
             float l[8];
             unpack8h(xl[u], l);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) f[j] += l[j];
+            for (int j = 0; j < 8; ++j) {
+              const double v = (double)f[j] + (double)l[j];
+              s0[j] += v;
+              s1[j] = fma(v, v, s1[j]);
+            }
+            continue;
           }
 #pragma unroll
           for (int j = 0; j < 8; ++j) { p0[j] += f[j]; p1[j] = fmaf(f[j], f[j], p1[j]); }

@@ -266,7 +266,7 @@ def _convlayer_forward_mixed(self, x, hilo_out=False, want_fp32=False):
     s2 = None
     if (k, s, p) == (5, 2, 2) and Ce % 32 == 0 and c.out_channels % 64 == 0 and not (H % 2 or W % 2) and _S2D_MODE != '0':
         s2 = hip.conv_spec(N, H // 2, W // 2, 4 * Ce, 0, c.out_channels, 3, 1, 1, mode0=hip.SRC_S2D, act=act, compute=hip.COMPUTE_F16)
-        if not hip.s2d_preferred(s2):
+        if not (_S2D_MODE == '2' or hip.s2d_preferred(s2)):  # (switch 2 pins the form, as _s2d_spec does)
             s2 = None
     if s2 is not None:
         sc, sh = _fold(s2, c.bias, self.norm, getattr(self, 'norm_layer', None))

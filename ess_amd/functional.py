@@ -459,6 +459,8 @@ class Conv2dFn(torch.autograd.Function):
             cols = [(0, C0)] * (2 if hl0 else 1) + ([(C0, C0 + C1)] * (2 if hl1 else 1) if C1 else [])
             pw = packed_weight(fspec, columns(weight, cols) if (hl0 or hl1) else weight)
             shift = packed_rows(fspec, bias) if bias is not None else None
+            if out_c8 == PRE_NORM_HILO and Cout % fspec.plan.cout_tile:
+                out_c8 = PRE_NORM  # (a [hi | lo] output needs whole channel tiles of the plan: validate() in conv_common.h)
             if out_c8 == PRE_NORM_HILO:
                 buf = hip.f16_blocks_empty(N, Cout, spec.H_out, spec.W_out, x0.device, hilo=True)
                 hip.conv_forward_h16(fspec, h0, h1, pw, None, shift, out=buf, out_fmt=hip.FMT_F16_C8_HILO)

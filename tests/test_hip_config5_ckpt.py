@@ -82,6 +82,16 @@ def test_config5_T20_recurrent_state_drift_vs_oracle(rtype):
 
 @pytest.mark.parametrize('rtype,C,H', [('convlstm', 2, 480), ('convgru', 2, 480), ('convlstm', 5, 440)])
 def test_config5_T20_full_size_lean_steps_and_step(rtype, C, H):
+    _config5_T20(rtype, C, H, 'bf16')
+
+
+@pytest.mark.parametrize('rtype,C,H', [('convlstm', 2, 480), ('convgru', 2, 480)])
+def test_config5_T20_full_size_lean_steps_and_step_mixed(rtype, C, H):
+    """the same in the mixed configuration: the deepest level's [hi | lo] pair on the last 3 of the 20 steps"""
+    _config5_T20(rtype, C, H, 'mixed')
+
+
+def _config5_T20(rtype, C, H, mode):
     """Config 5 shape on one GPU (B = 8, T = 20, 2x480x640, bf16; ConvLSTM and the ConvGRU variant the config names) and the
     reference's OWN default shape (nr_events_data 20, nr_temporal_bins 5, 440x640: config/settings_DSEC.yaml:6-7,15 -- 55-row
     eighth-resolution planes, 5-channel head): the 19 lean encoder-only steps + the full last step are deterministic, finite, equal
@@ -92,7 +102,7 @@ def test_config5_T20_full_size_lean_steps_and_step(rtype, C, H):
     from ess_amd.training.ess_trainer import ESSModel
     from ess_amd.training.synthetic import make_batch
     B, T, W, K = 8, 20, 640, 11
-    hip.set_compute('bf16')
+    hip.set_compute(mode)
     try:
         cfg = O.e2vid_config(num_bins=C, recurrent_block_type=rtype)
         sd = O.synth_state_dict(O.e2vid_param_shapes(cfg), 72)

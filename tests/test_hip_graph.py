@@ -173,6 +173,15 @@ def test_data_parallel_captured_step_matches_eager(kind, mode):
 
 
 def test_data_parallel_captured_step_full_size():
+    _dp_captured_step_full_size('bf16')
+
+
+def test_data_parallel_captured_step_full_size_mixed():
+    """the same in the mixed configuration"""
+    _dp_captured_step_full_size('mixed')
+
+
+def _dp_captured_step_full_size(mode):
     """The same two-rank comparison at the config-3 shape (DSEC: T = 5, 2 x 480 x 640, K = 11, bf16) with B = 4 per rank: the 3-graph
     captured data-parallel step (capture-pool memory, `_graph_adopt_packed`, flat-gradient all-reduce between the replays) has
     met a full-size multi-rank step; ranks agree, losses finite, peak memory per rank reported.  One GPU, gloo: no RCCL here."""
@@ -182,7 +191,7 @@ def test_data_parallel_captured_step_full_size():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, ESS_DIST_BACKEND='gloo', MASTER_ADDR='127.0.0.1')
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-                        '--master-port', '29543', os.path.join(root, 'tests', 'dp_graph_worker.py'), 'ess', 'bf16', 'full'],
+                        '--master-port', '29543', os.path.join(root, 'tests', 'dp_graph_worker.py'), 'ess', mode, 'full'],
                        cwd=root, env=env, capture_output=True, text=True, timeout=1500)
     lines = [ln for ln in r.stdout.splitlines() if 'RANK' in ln]
     print('\n'.join(lines))
@@ -219,3 +228,8 @@ def test_rccl_one_rank_dp_step_matches_plain(kind, mode):
 def test_rccl_one_rank_dp_step_full_size():
     """The same at the config-3 shape (B = 4, T = 5, 2 x 480 x 640, K = 11, bf16): 9.5 M gradient floats through ncclAllReduce per step."""
     _run_rccl_worker(['ess', 'bf16', 'full'], 1500)
+
+
+def test_rccl_one_rank_dp_step_full_size_mixed():
+    """the same in the mixed configuration"""
+    _run_rccl_worker(['ess', 'mixed', 'full'], 1500)

@@ -572,6 +572,15 @@ def test_config3_bf16_vs_oracle_and_bf16_reference():
 # are the size-independent properties of the path: determinism, batch independence (recurrent state, InstanceNorm and
 # every conv tile are per-sample), equality of the BF16_C8-staged and fp32-staged encoder, and bf16-vs-fp32 agreement.
 def test_full_size_encoder_properties():
+    _full_size_encoder_properties('bf16')
+
+
+def test_full_size_encoder_properties_mixed():
+    """the same properties in the mixed configuration (half operands, [hi | lo] pairs at the deepest level, the space-to-depth form at B = 8)"""
+    _full_size_encoder_properties('mixed')
+
+
+def _full_size_encoder_properties(low):
     from ess_amd import hip
     B, T, C, H, W = 8, 3, 2, 480, 640
     cfg = O.e2vid_config(num_bins=C)
@@ -592,7 +601,7 @@ def test_full_size_encoder_properties():
         return [lat[k].clone() for k in (1, 2, 4, 8)] + [s[1].clone() for s in states]
 
     outs = {}
-    for mode in ('fp32', 'bf16'):
+    for mode in ('fp32', low):
         hip.set_compute(mode)
         try:
             a = run(ev)
@@ -615,7 +624,7 @@ def test_full_size_encoder_properties():
                 assert all(torch.equal(x, y) for x, y in zip(a, a2)), 'forcing the space-to-depth form changes a launch that already took it'
                 assert all(torch.equal(x[3:4], y) for x, y in zip(a2, one2)), f'{mode}: sample 3 depends on its batch (one form on both sides)'
                 del a2, one2
-            if mode == 'bf16':
+            if mode == low:
                 # the BF16_C8-staged and the fp32-staged encoder contract the same bf16 operands; on the SAME kernels they are bit-identical.
                 # (The 5x5 / stride-2 convolutions of the BF16_C8-only flow run as the space-to-depth 3x3 -- ESS_SRC_S2D, another summation
                 # order than the tap-paired kernel an fp32-staged step takes -- so the bit comparison is made with that form switched off,
@@ -635,12 +644,21 @@ def test_full_size_encoder_properties():
             outs[mode] = a
         finally:
             hip.set_compute('fp32')
-    for x32, x16 in zip(outs['fp32'], outs['bf16']):
+    for x32, x16 in zip(outs['fp32'], outs[low]):
         assert relerr(x16, x32) < 3e-2
-    assert all(torch.isfinite(x).all() for x in outs['bf16'])
+    assert all(torch.isfinite(x).all() for x in outs[low])
 
 
 def test_full_size_uda_step_reproducible_and_batch_consistent():
+    _full_size_uda_step('bf16')
+
+
+def test_full_size_uda_step_reproducible_and_batch_consistent_mixed():
+    """the same in the mixed configuration (the benchmarked arithmetic)"""
+    _full_size_uda_step('mixed')
+
+
+def _full_size_uda_step(mode):
     """BASELINE config 3 at full size (B=8, T=5, 2x480x640, K=11, bf16 operands): two independently built trainers
     fed the same seeded batch produce the same losses step after step (weight gradients and norm statistics reduce in a
     fixed order; only the fp64 atomics of the loss reductions may reorder, far below the 1e-6 tolerance), every loss is finite,
@@ -650,7 +668,7 @@ def test_full_size_uda_step_reproducible_and_batch_consistent():
     from ess_amd.training.ess_trainer import ESSModel
     from ess_amd.training.synthetic import make_batch
     B, T, C, H, W, K = 8, 5, 2, 480, 640, 11
-    hip.set_compute('bf16')
+    hip.set_compute(mode)
     try:
         runs = []
         for rep in range(2):

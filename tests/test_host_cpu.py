@@ -67,6 +67,37 @@ def test_conv_plan_and_validation_on_host(built_lib):
     assert lib.ess_version() == 110
 
 
+def test_hilo_output_plans_keep_whole_channel_tiles(built_lib):
+    """A [hi | lo] (ESS_FMT_F16_C8_HILO) output's lo blocks are written by the straight-line epilogue only, which needs every channel of
+    a workgroup's tile: every HILO-output descriptor the plan accepts has C_out a multiple of its plan's cout_tile, every other one is
+    refused with a message.  The sweep crosses C_out with doubled [hi | lo] sources on both sides of the 512 input channels at which
+    the plan moves to 128-channel tiles."""
+    from ess_amd import hip
+    lib = hip.lib()
+    plan = hip.EssConvPlan()
+    accepted, refused = set(), set()
+    for k, s, p in ((3, 1, 1), (5, 2, 2), (1, 1, 0), (3, 2, 1)):
+        for C0, C1 in ((256, 0), (512, 0), (384, 128), (256, 256), (512, 256), (128, 64), (64, 0)):
+            for Co in (11, 32, 64, 96, 128, 192, 256, 320, 384, 512):
+                spec = hip.conv_spec(2, 24, 40, C0, C1, Co, k, s, p, compute=hip.COMPUTE_F16)
+                d = spec.desc_fmt(hip.FMT_F16_C8, hip.FMT_F16_C8_HILO, hip.FMT_F32_NCHW)
+                rc = lib.ess_conv2d_plan(ctypes.byref(d), ctypes.byref(plan))
+                if rc == 0:
+                    assert Co % plan.cout_tile == 0 and plan.cout_tile == spec.plan.cout_tile, (k, s, C0, C1, Co, plan.cout_tile)
+                    accepted.add((k, C0 + C1, Co))
+                else:
+                    assert rc == -22 and b'[hi | lo] output' in lib.ess_last_error(), (k, s, C0, C1, Co, lib.ess_last_error())
+                    refused.add((k, C0 + C1, Co))
+    # the edge itself: C_out = 320 behind a doubled 256-channel source (512 stored channels: 128-channel tiles) is refused, C_out = 256
+    # (the product's shape) and C_out = 192 / 320 below 512 input channels (64-channel tiles) are planned
+    assert (3, 512, 320) in refused and (3, 768, 320) in refused and (3, 512, 192) in accepted
+    assert {(3, 512, 256), (3, 256, 192), (3, 256, 320), (3, 192, 192)} <= accepted
+    assert (3, 256, 11) in refused and (3, 256, 96) in refused  # (C_out % 64)
+    # the product's decoder asks for a pair output only where its plan allows one (functional.Conv2dFn falls back to one half copy)
+    fspec = hip.conv_spec(8, 60, 80, 512, 0, 320, 3, 1, 1, compute=hip.COMPUTE_F16)
+    assert 320 % fspec.plan.cout_tile != 0
+
+
 def test_product_refuses_cpu_tensors(built_lib):
     from ess_amd import hip
     with pytest.raises(hip.EssHipError, match='no CPU path'):
