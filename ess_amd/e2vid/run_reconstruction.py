@@ -23,7 +23,7 @@ import torch
 
 from .. import hip
 from .image_reconstructor import ImageReconstructor
-from .model.submodules import _attach_c8, _c8_of
+from .model.submodules import _attach_c8, _c8_of, _mark_fp32_unwritten
 
 
 def events_to_voxel_grid_device(events, num_bins, width, height, device):
@@ -48,7 +48,88 @@ def iter_windows_fixed_size(events, num_events):
         yield events[i:i + num_events]
 
 
-class StreamingReconstructor:
+_PARTS = ('h', 'c8', 'h16', 'f32c8', 'c')
+
+
+class GraphedWindowState:
+    """What the streaming drivers share (StreamingReconstructor here, StreamingSegmenter in ess_amd/run_segmentation.py): the
+    recurrent state of `self.rec` (an ImageReconstructor) carried in STATIC buffers, and the capture of one window's work -- a
+    warm-up run on a side stream whose effect on the carried state is undone, then the recording -- as a hipGraph on the current
+    stream.  A subclass provides `_window(ev) -> (outputs, states)`: one window's device work on the static input `ev`."""
+
+    _static = None
+    _g = None
+
+    def _state_tensors(self, states):
+        """the device tensors of a state list that the next step reads, per level: h (the fp32 hidden state, None where a lean step
+        left an unwritten placeholder), its BF16_C8 copy, its half copy ('mixed'), its channel-blocked fp32 form (lean ConvGRU),
+        the cell c -- each None where absent; + (hilo of the half copy, the hidden state's shape)"""
+        out = []
+        for s in states:
+            h, c = (s[0], s[1]) if isinstance(s, (tuple, list)) else (s, None)
+            h16 = hip.h16_of(h)
+            out.append(({'h': None if getattr(h, 'ess_fp32_unwritten', False) else h, 'c8': _c8_of(h), 'h16': None if h16 is None else h16[0],
+                         'f32c8': getattr(h, 'ess_f32c8', None), 'c': c}, bool(h16 is not None and h16[1]), tuple(h.shape)))
+        return out
+
+    @staticmethod
+    def _attach(st):
+        """(re-)tie a static level's copies to its hidden-state tensor: the attachments follow the tensor's version"""
+        parts, hilo, _, sh = st
+        if parts['c8'] is not None:
+            _attach_c8(sh, parts['c8'])
+        if parts['h16'] is not None:
+            hip.attach_h16(sh, parts['h16'], hilo)
+        if parts['f32c8'] is not None:
+            sh.ess_f32c8 = parts['f32c8']
+
+    def _adopt_state(self, states):
+        """Copy a step's output state into the static buffers (allocated on first use) and make THEM the carried state."""
+        new = self._state_tensors(states)
+        if self._static is None:
+            self._static = []
+            for parts, hilo, shape in new:
+                sp = {k: None if t is None else torch.empty_like(t) for k, t in parts.items()}
+                sh = sp['h']
+                if sh is None:  # (a lean state: the fp32 hidden tensor is a placeholder without memory, the copies are the state)
+                    sh = torch.empty((), dtype=torch.float32, device=self.device).expand(shape)
+                    _mark_fp32_unwritten(sh)
+                self._static.append((sp, hilo, shape, sh))
+        carried = []
+        for st, (parts, hilo, shape) in zip(self._static, new):
+            sp, s_hilo, s_shape, sh = st
+            if [t is None for t in sp.values()] != [t is None for t in parts.values()] or s_hilo != hilo or s_shape != shape:
+                raise hip.EssHipError('streaming: a step left its recurrent state in another form than the static buffers were made for')
+            for k in _PARTS:
+                if sp[k] is not None:
+                    sp[k].copy_(parts[k])
+            self._attach(st)  # (after the copies: the attachments are tied to the tensor's version)
+            carried.append(sh if sp['c'] is None else (sh, sp['c']))
+        self.rec.last_states_for_each_channel['grayscale'] = carried
+
+    def _capture(self, example):
+        self._in = example.clone()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        saved = [{k: None if t is None else t.clone() for k, t in st[0].items()} for st in self._static]
+        with torch.cuda.stream(side):  # (one eager run of the generic step on a side stream before the capture, torch's recipe)
+            _, st = self._window(self._in)
+            self._adopt_state(st)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        for st, sv in zip(self._static, saved):  # undo the warm-up step's effect on the carried state
+            for k in _PARTS:
+                if st[0][k] is not None:
+                    st[0][k].copy_(sv[k])
+            self._attach(st)  # (the restore bumped the tensors' versions)
+        self._g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._g):
+            outputs, st = self._window(self._in)
+            self._adopt_state(st)
+        self._outputs = outputs
+
+
+class StreamingReconstructor(GraphedWindowState):
     """One sequence, one window at a time; the recurrent state persists between calls (reference run_reconstruction.py:84-112).
 
     update(event_tensor [1, num_bins, H, W] or [num_bins, H, W]) -> (image [1, 1, H, W], latent dict) ; reset() drops the state."""
@@ -103,51 +184,15 @@ class StreamingReconstructor:
             lat = lat.clone()
         return self._out_img.clone(), lat
 
-    # ---- hipGraph mode: static input, static state buffers; one recorded window = step + state carry
-    def _state_tensors(self, states):
-        """the device tensors of a state list that the next step reads: per level (h fp32, its BF16_C8 copy or None, c or None)"""
-        out = []
-        for s in states:
-            h, c = (s[0], s[1]) if isinstance(s, (tuple, list)) else (s, None)
-            out.append((h, _c8_of(h), c))
-        return out
+    # ---- hipGraph mode: static input, static state buffers; one recorded window = step + state carry (GraphedWindowState)
+    def _window(self, ev):
+        img, states, latent = self.rec.update_reconstruction(ev)
+        return (img, latent), states
 
-    def _adopt_state(self, states):
-        """Copy a step's output state into the static buffers (allocated on first use) and make THEM the carried state."""
-        new = self._state_tensors(states)
-        if getattr(self, '_static', None) is None:
-            self._static = [(torch.empty_like(h), None if h8 is None else torch.empty_like(h8), None if c is None else torch.empty_like(c))
-                            for h, h8, c in new]
-        carried = []
-        for (sh, sh8, sc), (h, h8, c) in zip(self._static, new):
-            sh.copy_(h)
-            if sh8 is not None:
-                sh8.copy_(h8)
-                _attach_c8(sh, sh8)  # (after the copy: the attachment is tied to the tensor's version)
-            if sc is not None:
-                sc.copy_(c)
-            carried.append(sh if sc is None else (sh, sc))
-        self.rec.last_states_for_each_channel['grayscale'] = carried
+    @property
+    def _out_img(self):
+        return self._outputs[0]
 
-    def _capture(self, example):
-        self._in = example.clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        saved = [tuple(None if t is None else t.clone() for t in lvl) for lvl in self._static]
-        with torch.cuda.stream(side):  # (one eager run of the generic step on a side stream before the capture, torch's recipe)
-            _, st, _ = self.rec.update_reconstruction(self._in)
-            self._adopt_state(st)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        for lvl, sv in zip(self._static, saved):  # undo the warm-up step's effect on the carried state
-            for t, s in zip(lvl, sv):
-                if t is not None:
-                    t.copy_(s)
-        for sh, sh8, _ in self._static:
-            if sh8 is not None:
-                _attach_c8(sh, sh8)  # (the restore bumped the tensors' versions)
-        self._g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._g):
-            img, st, latent = self.rec.update_reconstruction(self._in)
-            self._adopt_state(st)
-        self._out_img, self._out_latent = img, latent
+    @property
+    def _out_latent(self):
+        return self._outputs[1]

@@ -72,7 +72,7 @@ EXPORTS = [
     'ess_batchnorm_train_backward_c8', 'ess_l1_loss_c8', 'ess_augment_image_label', 'ess_radam_step_dev', 'ess_upsample_bilinear2x_add_c8',
     'ess_upsample_bilinear2x_add_c8_from_c8', 'ess_add_bf16', 'ess_event_normalize_slices', 'ess_sum_scalars',
     'ess_label_confusion', 'ess_augment_perspective_filter', 'ess_tuning_set', 'ess_tuning_get', 'ess_conv2d_s2d_preferred',
-    'ess_to_f16_c8', 'ess_bf16_c8_to_f16_c8', 'ess_f16_c8_to_bf16_c8', 'ess_instnorm_forward_c8_mixed',
+    'ess_to_f16_c8', 'ess_bf16_c8_to_f16_c8', 'ess_f16_c8_to_bf16_c8', 'ess_instnorm_forward_c8_mixed', 'ess_seg_head',
 ]
 
 
@@ -161,6 +161,7 @@ def lib():
             'ess_radam_step_dev': [P, P, P, P, I64, F, F, F, P, P],
             'ess_upsample_bilinear2x_add_c8': [P, P, P, I, I, I, I, P],
             'ess_upsample_bilinear2x_add_c8_from_c8': [P, P, P, I, I, I, I, P],
+            'ess_seg_head': [P, I, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
         }
         for name, argtypes in sig.items():
             fn = getattr(L, name)
@@ -814,6 +815,64 @@ def argmax_confusion(logits, labels=None, conf=None, ignore_index=255, want_pred
     _check(lib().ess_argmax_confusion(ptr(logits), ptr(labels, torch.int64), ptr(pred, torch.int64), ptr(conf, torch.int64),
                                       N, K, H * W, int(ignore_index), stream()), 'ess_argmax_confusion')
     return pred
+
+
+SEG_HEAD_MAX_K = 64
+
+
+def seg_head(x, C, weight, bias, out_hw=None, window=None, palette=None, want_confidence=False):
+    """Fused class head at inference (ess_seg_head): labels = first argmax_k (bias[k] + sum_c weight[k, c] x[c]) per output pixel,
+    without the scores ever being written -> (labels uint8 [N, H_out, W_out], colour uint8 [N, H_out, W_out, 3] or None, confidence
+    fp32 [N, H_out, W_out] or None).
+    x: the activation in front of the 1x1 class convolution, C channels: fp32 NCHW, BF16_C8, or F16_C8 (a float16 tensor
+    [N, C/8, H, W, 8], or the bfloat16-typed container of f16_c8_empty); weight [K, C] (or the convolution's [K, C, 1, 1]) and bias
+    [K]: the plain fp32 parameters -- the kernel rounds the weight to the source's operand type itself.
+    window (y0, x0, h, w): the part of the source plane the output is taken from (default: all of it); out_hw: the output size
+    (default: the window's) -- source pixels by hip.resize_nearest's index rule inside the window, so labels equal
+    argmax(resize_nearest(scores)).  palette: uint8 [K, 3] on the device -> colour = palette[labels].  want_confidence: the softmax
+    probability of the winning class."""
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise EssHipError('seg_head: x must be a CUDA(HIP) tensor; there is no CPU path')
+    if x.dim() == 5 and x.shape[-1] == 8 and x.dtype in (torch.bfloat16, torch.float16):
+        fmt = FMT_F16_C8 if (x.dtype == torch.float16 or is_f16_c8(x)) else FMT_BF16_C8
+        N, nb, H, W, _ = x.shape
+        if not 0 < C <= nb * 8:
+            raise EssHipError(f'seg_head: C={C} channels do not fit the source\'s {nb} blocks of 8')
+        if nb != (C + 7) // 8:
+            raise EssHipError(f'seg_head: C={C} channels need {(C + 7) // 8} blocks of 8, x has {nb}')
+    elif x.dim() == 4 and x.dtype == torch.float32:
+        fmt = FMT_F32_NCHW
+        N, Cx, H, W = x.shape
+        if Cx != C:
+            raise EssHipError(f'seg_head: C={C} but x has {Cx} channels')
+    else:
+        raise EssHipError(f'seg_head: x must be fp32 NCHW, BF16_C8 or F16_C8, got {x.dtype}{tuple(x.shape)}')
+    if weight.dim() == 4 and weight.shape[2:] == (1, 1):
+        weight = weight.view(weight.shape[0], weight.shape[1])
+    if weight.dim() != 2 or weight.shape[1] != C:
+        raise EssHipError(f'seg_head: weight must be [K, C={C}], got {tuple(weight.shape)}')
+    K = weight.shape[0]
+    if not 0 < K <= SEG_HEAD_MAX_K:
+        raise EssHipError(f'seg_head: weight has K={K} classes, at most {SEG_HEAD_MAX_K} are supported')
+    if bias is None or tuple(bias.shape) != (K,):
+        raise EssHipError(f'seg_head: bias must be [K={K}], got {None if bias is None else tuple(bias.shape)}')
+    if palette is not None and (not torch.is_tensor(palette) or palette.dtype != torch.uint8 or tuple(palette.shape) != (K, 3)):
+        got = f'{palette.dtype}{tuple(palette.shape)}' if torch.is_tensor(palette) else type(palette).__name__
+        raise EssHipError(f'seg_head: palette must be a uint8 [K={K}, 3] tensor, got {got}')
+    y0, x0, h, w = (0, 0, H, W) if window is None else (int(v) for v in window)
+    if y0 < 0 or x0 < 0 or h <= 0 or w <= 0 or y0 + h > H or x0 + w > W:
+        raise EssHipError(f'seg_head: window {(y0, x0, h, w)} leaves the {H} x {W} source plane')
+    Ho, Wo = (h, w) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+    if Ho <= 0 or Wo <= 0:
+        raise EssHipError(f'seg_head: out_hw {(Ho, Wo)} is empty')
+    dev = x.device
+    labels = torch.empty(N, Ho, Wo, dtype=torch.uint8, device=dev)
+    colour = torch.empty(N, Ho, Wo, 3, dtype=torch.uint8, device=dev) if palette is not None else None
+    conf = torch.empty(N, Ho, Wo, dtype=torch.float32, device=dev) if want_confidence else None
+    _check(lib().ess_seg_head(ptr(x, x.dtype, allow_none=False), fmt, ptr(weight.detach(), allow_none=False), ptr(bias.detach(), allow_none=False),
+                              ptr(palette, torch.uint8), ptr(labels, torch.uint8), ptr(colour, torch.uint8), ptr(conf), N, C, K, H, W,
+                              y0, x0, h, w, Ho, Wo, stream()), 'ess_seg_head')
+    return labels, colour, conf
 
 
 # ------------------------------------------------------------------------------------------ 'mixed' configuration (ESS_COMPUTE_F16)

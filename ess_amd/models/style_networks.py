@@ -119,37 +119,70 @@ class SemSegE2VID(nn.Module):
         frozen encoder's staging copies, or converted), out[2] / out[4] are returned in that form (hip.from_bf16_c8 gives
         the reference's fp32 NCHW view), out[1] (the logits) is fp32 NCHW in either configuration."""
         sz_in = input_dict[1].shape[3]
+        out = {8: input_dict[8]}
+        x = self._trunk(input_dict, out, sz_in)
+        c5 = self.decoder_scale_5[0]
+        x = Fn.conv2d(x, c5.weight, c5.bias, 1, 0, out_c8=False, half=True)  # the logits: fp32 NCHW for the loss / metric kernels
+        self.update_skip_dict(out, x, sz_in)
+        return out
+
+    def _trunk(self, input_dict, out, sz_in):
+        """Everything up to and including decoder_scale_4 -> the activation the 1x1 class convolution reads.  out: forward's result
+        dict (out[4] / out[2] are recorded, each forked from the tensor the next stage reads), or None (predict: no dict, no fork)."""
         x = input_dict[8]
-        out = {8: x}
         c8 = Fn.c8_mode()
         lat = (lambda t, deep=False: Fn.as_c8(t, want_hilo=deep).contiguous()) if c8 else (lambda t, deep=False: t.contiguous())
         x = lat(x, True)  # (mixed configuration: the 1/8 latent enters as a [hi | lo] half pair)
+
+        def record(x):
+            # out[4] / out[2] feed the next stage AND (through the returned dict) the cycle losses: Fn.fork sums the two
+            # gradients in one library launch instead of autograd's accumulation add
+            if out is None:
+                return x
+            x, xo = Fn.fork(x)
+            self.update_skip_dict(out, xo, sz_in)
+            return x
+
         if self.skip_connect:
             x = self.decoder_scale_1[0](x, first=True)
             for blk in list(self.decoder_scale_1)[1:]:
                 x = blk(x)
             x = self.decoder_scale_2[0].forward_fused(x, lat(input_dict[4]), up=True)
-            # out[4] / out[2] feed the next stage AND (through the returned dict) the cycle losses: Fn.fork sums the two
-            # gradients in one library launch instead of autograd's accumulation add
-            x, xo = Fn.fork(self.decoder_scale_2[1](x))
-            self.update_skip_dict(out, xo, sz_in)
+            x = record(self.decoder_scale_2[1](x))
             x = self.decoder_scale_3[0].forward_fused(x, lat(input_dict[2]), up=True)
-            x, xo = Fn.fork(self.decoder_scale_3[1](x))
-            self.update_skip_dict(out, xo, sz_in)
+            x = record(self.decoder_scale_3[1](x))
             x = self.decoder_scale_4[0].forward_fused(x, None, up=True)
         else:
             x = self.decoder_scale_1[0](x, first=True)
             for blk in list(self.decoder_scale_1)[1:]:
                 x = blk(x)
-            x, xo = Fn.fork(self.decoder_scale_2[1].forward_fused(x, None, up=True))
-            self.update_skip_dict(out, xo, sz_in)
-            x, xo = Fn.fork(self.decoder_scale_3[1].forward_fused(x, None, up=True))
-            self.update_skip_dict(out, xo, sz_in)
+            x = record(self.decoder_scale_2[1].forward_fused(x, None, up=True))
+            x = record(self.decoder_scale_3[1].forward_fused(x, None, up=True))
             x = self.decoder_scale_4[1].forward_fused(x, None, up=True)
-        c5 = self.decoder_scale_5[0]
-        x = Fn.conv2d(x, c5.weight, c5.bias, 1, 0, out_c8=False, half=True)  # the logits: fp32 NCHW for the loss / metric kernels
-        self.update_skip_dict(out, x, sz_in)
-        return out
+        return x
+
+    def predict(self, input_dict, out_hw=None, window=None, palette=None, want_confidence=False):
+        """Forward-only labels from latents {1, 2, 4, 8}: forward's layers up to decoder_scale_4, then the fused class head
+        (hip.seg_head: 1x1 convolution with decoder_scale_5's weight and bias, nearest resize, first argmax) instead of the logits ->
+        (labels uint8 [N, H_out, W_out], colour uint8 [N, H_out, W_out, 3] or None, confidence fp32 [N, H_out, W_out] or None);
+        window / out_hw / palette / want_confidence: see hip.seg_head.  Runs under torch.no_grad(), in train or eval mode alike
+        (InstanceNorm keeps no running statistics), reads the packed weights forward reads; the head contracts the operands
+        forward's last convolution contracts in each configuration (the half copy in 'mixed', the BF16_C8 tensor in 'bf16', fp32
+        otherwise; 'bf16x3' runs it in plain fp32 where forward uses split operands without the lo x lo products)."""
+        with torch.no_grad():
+            x = self._trunk(input_dict, None, input_dict[1].shape[3])
+            c5 = self.decoder_scale_5[0]
+            if hip.is_c8(x):
+                C = x.shape[1] * 8
+                if hip.mixed():
+                    h, hilo = Fn.half_of(x)
+                    if hilo:
+                        raise hip.EssHipError('SemSegE2VID.predict: the last activation came as a [hi | lo] half pair')
+                    x = h
+            else:
+                C = x.shape[1]
+            return hip.seg_head(x.contiguous(), C, c5.weight, c5.bias, out_hw=out_hw, window=window, palette=palette,
+                                want_confidence=want_confidence)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -428,6 +428,22 @@ int ess_resize_nearest(const float* x, float* y, int32_t planes, int32_t H_in, i
 int ess_argmax_confusion(const float* logits, const int64_t* labels, int64_t* pred_lbl, int64_t* conf,
                          int32_t N, int32_t K, int32_t hw, int32_t ignore_index, ess_stream_t stream);
 
+/* Fused class head at inference -- PURELY ADDITIVE to ABI 110 (ess_version() is unchanged; no existing entry point changes):
+ * per output pixel z_k = bias[k] + sum_c weight[k][c] x[c] (the 1x1 convolution decoder_scale_5 of SemSegE2VID,
+ * models/style_networks.py:66,87), label = the FIRST argmax_k z_k -- without writing the scores.  Replaces, for a caller that wants
+ * labels and not logits, conv1x1 -> F.interpolate(nearest) -> argmax (training/ess_trainer.py:424-493).
+ * x: fmt ESS_FMT_F32_NCHW [N][C][H][W] fp32, ESS_FMT_BF16_C8 or ESS_FMT_F16_C8 [N][ceil(C/8)][H][W][8].  weight [K][C], bias [K]: the
+ * plain fp32 parameters; the kernel rounds the weight to the operand type of the source while loading it (bfloat16 / IEEE half
+ * saturating at +-65504 / none) and masks c >= C; fp32 accumulation.  K <= 64; K x C must fit 64 KiB of LDS as floats.
+ * Source pixel of output pixel (oy, ox): (win_y0 + min(floor(oy * (float)win_h / H_out), win_h - 1), win_x0 + ...) -- the index rule
+ * of ess_resize_nearest inside the window (win_y0, win_x0, win_h, win_w) of the source plane, so that labels equal "resize the
+ * scores, then argmax"; the identity plus an offset when the sizes agree.
+ * labels: uint8 [N][H_out][W_out] (required).  colour (nullable; needs palette, uint8 [K][3]): uint8 [N][H_out][W_out][3] =
+ * palette[label].  confidence (nullable): fp32 [N][H_out][W_out] = 1 / sum_k exp(z_k - z_max), the winner's softmax probability. */
+int ess_seg_head(const void* x, int32_t fmt, const float* weight, const float* bias, const uint8_t* palette, uint8_t* labels,
+                 uint8_t* colour, float* confidence, int32_t N, int32_t C, int32_t K, int32_t H, int32_t W, int32_t win_y0,
+                 int32_t win_x0, int32_t win_h, int32_t win_w, int32_t H_out, int32_t W_out, ess_stream_t stream);
+
 /* confusion-matrix accumulation from GIVEN predictions (evaluation/metrics.py:4-24, semseg_compute_confusion): pred_lbl,
  * labels int64 [total]; conf int64 [K][K] accumulated (conf[label][pred]) over labels != ignore_index.          */
 int ess_label_confusion(const int64_t* pred_lbl, const int64_t* labels, int64_t* conf, int64_t total, int32_t K,

@@ -1,0 +1,100 @@
+#!/usr/bin/env python
+"""Latency of streaming event segmentation (B = 1, 5 x 480 x 640, K = 11, skip_connect=True): per event window voxel grid +
+normalisation + recurrent step + semantic decoder + labels.  Two ways, in ONE process, alternating:
+
+  segmenter    ess_amd.run_segmentation.StreamingSegmenter (encoder-only step, fused class head), eager issue and hipGraph replay;
+  composed     what the package's older public pieces give: StreamingReconstructor.update (full UNet step, eager / replayed)
+               -> SemSegE2VID.forward -> hip.argmax_confusion(want_pred=True).
+
+Per (configuration, mode, way): `--reps` repetitions of `--windows` windows after `--warmup` windows, each repetition timed with the
+host clock between device synchronisations; median and range over the repetitions, ms per window.  One JSON line.
+usage: python tools/bench_seg_stream.py [--compute mixed,bf16 --windows 40 --warmup 8 --reps 3 --recurrent convlstm]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--height', type=int, default=480)
+    ap.add_argument('--width', type=int, default=640)
+    ap.add_argument('--bins', type=int, default=5)
+    ap.add_argument('--classes', type=int, default=11)
+    ap.add_argument('--events', type=int, default=107520, help='events per window (as tools/bench_stream.py)')
+    ap.add_argument('--windows', type=int, default=40)
+    ap.add_argument('--warmup', type=int, default=8)
+    ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--recurrent', default='convlstm')
+    ap.add_argument('--compute', default='mixed,bf16')
+    a = ap.parse_args()
+    from ess_amd import hip
+    from ess_amd.e2vid.model.model import E2VIDRecurrent
+    from ess_amd.e2vid.options.inference_options import default_options
+    from ess_amd.e2vid.run_reconstruction import StreamingReconstructor, events_to_voxel_grid_device
+    from ess_amd.models.style_networks import SemSegE2VID
+    from ess_amd.run_segmentation import StreamingSegmenter
+    cfg = dict(num_bins=a.bins, skip_type='sum', num_encoders=3, base_num_channels=32, num_residual_blocks=2, norm='BN',
+               use_upsample_conv=True, recurrent_block_type=a.recurrent)
+    g = np.random.default_rng(0)
+    n = a.events
+    wins = []
+    for w in range(4):
+        t = np.sort(g.uniform(0, 0.03, n)) + 0.03 * w
+        wins.append(torch.from_numpy(np.stack([t, g.integers(0, a.width, n).astype(np.float64), g.integers(0, a.height, n).astype(np.float64),
+                                               g.integers(0, 2, n).astype(np.float64)], 1)).cuda())
+    dev = torch.device('cuda:0')
+    out = {'shape': f'B=1 {a.bins}x{a.height}x{a.width} K={a.classes}', 'events_per_window': n, 'recurrent': a.recurrent,
+           'windows': a.windows, 'warmup': a.warmup, 'reps': a.reps, 'ms_per_window': {}}
+
+    def timed(step):
+        for i in range(a.warmup):
+            step(wins[i % 4])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(a.windows):
+            step(wins[i % 4])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / a.windows * 1e3
+
+    for compute in a.compute.split(','):
+        hip.set_compute(compute)
+        try:
+            for mode in ('eager', 'graph'):
+                torch.manual_seed(6)
+                enc = E2VIDRecurrent(dict(cfg))
+                dec = SemSegE2VID(256, a.classes, skip_connect=True, skip_type='concat')
+                seg = StreamingSegmenter(enc, dec, a.height, a.width, default_options(), graph=mode == 'graph')
+                torch.manual_seed(6)
+                rec = StreamingReconstructor(E2VIDRecurrent(dict(cfg)), a.height, a.width, default_options(), graph=mode == 'graph')
+                dec2 = SemSegE2VID(256, a.classes, skip_connect=True, skip_type='concat').cuda().eval()
+
+                def composed(events):
+                    grid = events_to_voxel_grid_device(events, a.bins, a.width, a.height, dev)
+                    _, latent = rec.update(grid)
+                    with torch.no_grad():
+                        return hip.argmax_confusion(dec2(latent)[1], want_pred=True)
+
+                ways = {'segmenter': seg.update_from_events, 'composed': composed}
+                ms = {k: [] for k in ways}
+                for _ in range(a.reps):  # alternating: drift of the box hits both ways alike
+                    for k, fn in ways.items():
+                        ms[k].append(timed(fn))
+                for k, v in ms.items():
+                    out['ms_per_window'][f'{compute}/{mode}/{k}'] = {'median': round(statistics.median(v), 4), 'min': round(min(v), 4),
+                                                                     'max': round(max(v), 4)}
+                del seg, rec
+        finally:
+            hip.set_compute('fp32')
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()
