@@ -779,9 +779,14 @@ class SymJSFn(torch.autograd.Function):
 
 class L1Fn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, a, b, weight=1.0):
+    def forward(ctx, a, b, weight=1.0, channels=None):
         if hip.is_c8(a):
-            loss, da = hip.l1_loss_c8(a, b, a.numel(), ctx.needs_input_grad[0], float(weight))
+            # the mean runs over the REAL elements: a BF16_C8 tensor does not record how many of its last block's channels are padding
+            N, nb, H, W, _ = a.shape
+            C = -1 if channels is None else int(channels)  # (l1_loss refuses a BF16_C8 pair without the count)
+            if not (nb - 1) * 8 < C <= nb * 8:
+                raise hip.EssHipError(f'l1_loss: {C} channels do not fill {nb} blocks of 8')
+            loss, da = hip.l1_loss_c8(a, b, N * C * H * W, ctx.needs_input_grad[0], float(weight))
         else:
             loss, da = hip.l1_loss(a, b, ctx.needs_input_grad[0], float(weight))
         ctx.save_for_backward(da)
@@ -790,7 +795,7 @@ class L1Fn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         da, = ctx.saved_tensors
-        return _times(da, g), None, None
+        return _times(da, g), None, None, None
 
 
 def task_loss(logits, labels, ignore_index=255, use_dice=True, use_ce=True, weight=1.0):
@@ -804,12 +809,21 @@ def sym_js_div(a, b, weight=1.0):
     return SymJSFn.apply(a.contiguous(), b.contiguous(), weight)
 
 
-def l1_loss(a, b, weight=1.0):
+def l1_loss(a, b, weight=1.0, channels=None):
+    """weight * mean |a - b| over the real elements; gradient flows to `a` only.  channels: the logical channel count of BF16_C8
+    operands.  Such a tensor does not record how many channels of its last 8-channel block are padding, and the padding must not
+    count in the mean: a BF16_C8 pair without `channels` is refused.  When one operand is fp32 NCHW its shape supplies the count;
+    `channels` is not read for two fp32 operands."""
     if b.requires_grad:
         raise hip.EssHipError('l1_loss: the second argument must not require grad')
     if hip.is_c8(a) != hip.is_c8(b):  # one side already lives in the bf16 configuration's stored form: compare there
+        if channels is None:
+            channels = (b if hip.is_c8(a) else a).shape[1]
         a, b = as_c8(a), as_c8(b)
+    elif hip.is_c8(a) and channels is None:
+        raise hip.EssHipError('l1_loss: BF16_C8 operands need channels= (the logical channel count: the mean runs over the real '
+                              'elements, and the tensors do not say how much of their last block is padding)')
     for t in (a, b):  # (a lean latent whose fp32 values were never written must have gone through as_c8 above)
         if getattr(t, 'ess_fp32_unwritten', False):
             raise hip.EssHipError('l1_loss: the tensor exists as a staging copy only (lean recurrent state); its fp32 values were never written')
-    return L1Fn.apply(a.contiguous(), b.contiguous(), weight)
+    return L1Fn.apply(a.contiguous(), b.contiguous(), weight, channels)

@@ -49,7 +49,11 @@ class symJSDivLoss(torch.nn.Module):
 
 
 class L1Loss(torch.nn.Module):
-    """torch.nn.L1Loss() as used for the cycle losses (training/ess_trainer.py:28,217-253)."""
+    """torch.nn.L1Loss() as used for the cycle losses (training/ess_trainer.py:28,217-253).  channels: the logical channel count of
+    BF16_C8 operands; left out, every 8-channel block counts as full -- true of what the trainers compare (latents and decoder
+    activations: Fn.as_c8 and the layers that make them know whole blocks only).  Fn.l1_loss itself never assumes it."""
 
-    def forward(self, predict, target, weight=1.0):
-        return Fn.l1_loss(predict, Fn.detach_keep_c8(target), weight)
+    def forward(self, predict, target, weight=1.0, channels=None):
+        if channels is None and Fn.hip.is_c8(predict) and Fn.hip.is_c8(target):
+            channels = predict.shape[1] * 8
+        return Fn.l1_loss(predict, Fn.detach_keep_c8(target), weight, channels)

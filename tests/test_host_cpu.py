@@ -671,7 +671,10 @@ def test_data_parallel_world8_gloo_buckets_validation_broadcast():
     import torch.multiprocessing as mp
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    port = 33500 + os.getpid() % 2000
+    import socket
+    with socket.socket() as sk:  # a port that was free a moment ago, as test_forced_dp_one_rank_gloo takes its own
+        sk.bind(('127.0.0.1', 0))
+        port = sk.getsockname()[1]
     world = 8
     procs = [ctx.Process(target=_dp8_worker, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
