@@ -34,15 +34,19 @@ void ess_allow_lds_impl(const void* kernel, size_t bytes) {
 namespace essconv { void set_wide_mode(int m); int wide_mode(); int device_cus(); }
 void set_in_small_threads(int v);
 int in_small_threads();
+void set_norm_split_wgs(int v);
+int norm_split_wgs();
 extern "C" int ess_tuning_set(const char* key, int32_t value) {
   if (key && !strcmp(key, "conv_wide")) { essconv::set_wide_mode(value); return ESS_OK; }
   if (key && !strcmp(key, "in_small_threads")) { set_in_small_threads(value); return ESS_OK; }
+  if (key && !strcmp(key, "norm_split_wgs")) { set_norm_split_wgs(value); return ESS_OK; }
   ess_set_error("tuning_set: unknown key '%s'", key ? key : "(null)");
   return ESS_EINVAL;
 }
 extern "C" int ess_tuning_get(const char* key, int32_t* value) {
   if (key && value && !strcmp(key, "conv_wide")) { *value = essconv::wide_mode(); return ESS_OK; }
   if (key && value && !strcmp(key, "in_small_threads")) { *value = in_small_threads(); return ESS_OK; }
+  if (key && value && !strcmp(key, "norm_split_wgs")) { *value = norm_split_wgs(); return ESS_OK; }
   if (key && value && !strcmp(key, "device_cus")) { *value = essconv::device_cus(); return ESS_OK; }  // (read-only: the dispatcher's CU count)
   ess_set_error("tuning_get: unknown key '%s'", key ? key : "(null)");
   return ESS_EINVAL;

@@ -793,9 +793,27 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_c8_kernel(const u32x4n* __re
   }
 }
 
+}  // namespace
+// "norm_split_wgs" (ESS_NORM_SPLIT_WGS, default 1024): workgroups the split statistics pass aims at.  The slices per (sample, channel
+// block) follow from it AND from the number of groups N * CB, i.e. from the batch size -- another summation order of the same fp64
+// partial sums.  ESS_NORM_SPLIT_BY_PLANE (a target no launch reaches) leaves the plane size alone to decide: one form for every batch
+// size.  A value <= 0 returns to the process's own setting (the environment variable, else 1024).
+static std::atomic<int> g_split_wgs{-1};
+int norm_split_wgs() {
+  int v = g_split_wgs.load(std::memory_order_relaxed);
+  if (v < 0) {
+    const char* e = getenv("ESS_NORM_SPLIT_WGS");
+    v = e ? atoi(e) : 1024;
+    g_split_wgs.store(v, std::memory_order_relaxed);
+  }
+  return v;
+}
+void set_norm_split_wgs(int v) { g_split_wgs.store(v > 0 ? v : -1, std::memory_order_relaxed); }  // (-1: read the environment again)
+namespace {
+
 inline int split_for8(int groups, int hw) {
   // workgroups the statistics pass aims at (x slices per group) and the smallest slice (ESS_NORM_SPLIT_WGS / ESS_NORM_SPLIT_MINV: tuning)
-  static const int target = [] { const char* e = getenv("ESS_NORM_SPLIT_WGS"); return e ? atoi(e) : 1024; }();
+  const int target = norm_split_wgs();
   static const int minv = [] { const char* e = getenv("ESS_NORM_SPLIT_MINV"); return e ? atoi(e) : 1024; }();
   int s = (target + groups - 1) / groups;
   const int maxs = (hw + minv - 1) / minv;  // at least `minv` pixel vectors per slice

@@ -247,7 +247,7 @@ __global__ void add_kernel(const float* __restrict__ a, const float* __restrict_
 }
 
 // workspace: double[3] = {count, sum, sumsq}
-__global__ __launch_bounds__(256) void evnorm_reduce_kernel(const float* __restrict__ x, int64_t n, double* ws) {
+__device__ __forceinline__ void evnorm_reduce_body(const float* __restrict__ x, int64_t n, double* ws) {
   __shared__ double red[16];
   double c = 0, s = 0, ss = 0;
   if ((n & 3) == 0 && (((uintptr_t)x) & 15) == 0) {  // 16-byte loads; zeros contribute nothing to either sum
@@ -267,6 +267,10 @@ __global__ __launch_bounds__(256) void evnorm_reduce_kernel(const float* __restr
   s = block_sum_d(s, red);
   ss = block_sum_d(ss, red);
   if (threadIdx.x == 0) { atomicAdd(ws, c); atomicAdd(ws + 1, s); atomicAdd(ws + 2, ss); }
+}
+
+__global__ __launch_bounds__(256) void evnorm_reduce_kernel(const float* __restrict__ x, int64_t n, double* ws) {
+  evnorm_reduce_body(x, n, ws);
 }
 
 __global__ void evnorm_apply_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n, const double* ws) {
@@ -484,6 +488,80 @@ extern "C" int ess_event_normalize_slices(const float* x, float* y, int32_t B, i
   hipLaunchKernelGGL(evnorm_slices_reduce_kernel, dim3(grid_for(n / 4, 256, 128), (unsigned)T), dim3(256), 0, st, x, B, T, chunk, (double*)workspace);
   hipLaunchKernelGGL(evnorm_slices_apply_kernel, dim3(grid_for(n / 4, 256, 1024), (unsigned)T), dim3(256), 0, st, x, y, B, T, chunk, (const double*)workspace);
   return ess_launch_status("event_normalize_slices");
+}
+
+namespace {
+// Per-SAMPLE normalisation of S independent streams' voxel grids: x, y = [S][chunk], blockIdx.y = sample, workspace double[S][3].
+// Sample s must come out bit-identical to ess_event_normalize on that sample alone, so the reduction repeats that kernel's
+// decomposition for n = chunk: the launch gives every sample the grid ess_event_normalize would size from chunk (NOT from
+// S * chunk), each thread walks the same elements in the same order, and the block sums and the three atomics per workgroup are
+// the same.  mode (nullable): a sample with mode[s] == 0 is not read; its y is zero-filled.
+__global__ __launch_bounds__(256) void evnorm_samples_reduce_kernel(const float* __restrict__ x, int64_t chunk, const int32_t* __restrict__ mode,
+                                                                    double* ws) {
+  const int smp = blockIdx.y;
+  if (mode && mode[smp] == 0) return;
+  evnorm_reduce_body(x + (int64_t)smp * chunk, chunk, ws + 3 * smp);
+}
+
+__global__ void evnorm_samples_apply_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t chunk, const int32_t* __restrict__ mode,
+                                            const double* ws) {
+  const int smp = blockIdx.y;
+  const bool hold = mode && mode[smp] == 0;
+  const double cnt = hold ? 0.0 : ws[3 * smp];
+  float mean = 0.f, sd = 1.f;
+  const bool on = cnt > 0;
+  if (on) {  // fp32 arithmetic on the totals, as the reference does (inference_utils.py:104-105)
+    const float fs = (float)ws[3 * smp + 1], fss = (float)ws[3 * smp + 2], fc = (float)cnt;
+    mean = fs / fc;
+    sd = sqrtf(fss / fc - mean * mean);
+  }
+  x += (int64_t)smp * chunk;
+  y += (int64_t)smp * chunk;
+  if ((chunk & 3) == 0 && ((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0) {
+    const f32x4* x4 = (const f32x4*)x;
+    f32x4* y4 = (f32x4*)y;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (chunk >> 2); i += (int64_t)gridDim.x * blockDim.x) {
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (!hold) {
+        v = x4[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = on ? (v[j] != 0.f ? (v[j] - mean) / sd : 0.f) : v[j];
+      }
+      y4[i] = v;
+    }
+  } else {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < chunk; i += (int64_t)gridDim.x * blockDim.x) {
+      float v = 0.f;
+      if (!hold) {
+        v = x[i];
+        v = on ? (v != 0.f ? (v - mean) / sd : 0.f) : v;
+      }
+      y[i] = v;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int ess_event_normalize_samples(const float* x, float* y, int32_t S, int64_t chunk, const int32_t* mode, void* workspace,
+                                           ess_stream_t stream) {
+  ESS_CHECK_ARG(x && y && workspace, "event_normalize_samples: null tensor or workspace");
+  ESS_CHECK_ARG(S > 0 && S <= 65535, "event_normalize_samples: S=%d samples (1..65535)", (int)S);
+  ESS_CHECK_ARG(chunk > 0, "event_normalize_samples: chunk=%lld", (long long)chunk);
+  hipStream_t st = (hipStream_t)stream;
+  {
+    hipError_t e = hipMemsetAsync(workspace, 0, (size_t)S * 3 * sizeof(double), st);
+    if (e != hipSuccess) {
+      ess_set_error("event_normalize_samples: memset failed: %s", hipGetErrorString(e));
+      return ESS_ELAUNCH;
+    }
+  }
+  // (the reduce grid per sample is the one ess_event_normalize launches for n = chunk: see the kernel)
+  hipLaunchKernelGGL(evnorm_samples_reduce_kernel, dim3(grid_for(chunk / 4, 256, 128), (unsigned)S), dim3(256), 0, st, x, chunk, mode,
+                     (double*)workspace);
+  hipLaunchKernelGGL(evnorm_samples_apply_kernel, dim3(grid_for(chunk / 4, 256, 1024), (unsigned)S), dim3(256), 0, st, x, y, chunk, mode,
+                     (const double*)workspace);
+  return ess_launch_status("event_normalize_samples");
 }
 
 // fp32 NCHW -> BF16_C8 ([N][ceil(C/8)][H][W][8] bfloat16, tail channels zero): one thread = one pixel vector.

@@ -73,6 +73,7 @@ EXPORTS = [
     'ess_upsample_bilinear2x_add_c8_from_c8', 'ess_add_bf16', 'ess_event_normalize_slices', 'ess_sum_scalars',
     'ess_label_confusion', 'ess_augment_perspective_filter', 'ess_tuning_set', 'ess_tuning_get', 'ess_conv2d_s2d_preferred',
     'ess_to_f16_c8', 'ess_bf16_c8_to_f16_c8', 'ess_f16_c8_to_bf16_c8', 'ess_instnorm_forward_c8_mixed', 'ess_seg_head',
+    'ess_event_normalize_samples', 'ess_state_carry_masked',
 ]
 
 
@@ -162,6 +163,8 @@ def lib():
             'ess_upsample_bilinear2x_add_c8': [P, P, P, I, I, I, I, P],
             'ess_upsample_bilinear2x_add_c8_from_c8': [P, P, P, I, I, I, I, P],
             'ess_seg_head': [P, I, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
+            'ess_event_normalize_samples': [P, P, I, I64, P, P, P],
+            'ess_state_carry_masked': [P, P, P, I, I, P, P],
         }
         for name, argtypes in sig.items():
             fn = getattr(L, name)
@@ -634,6 +637,91 @@ def event_normalize_slices(x, T):
     return y
 
 
+def _stream_modes(mode, S, what):
+    """the per-stream mode words of a batched call: a contiguous int32 [S] device tensor"""
+    if not torch.is_tensor(mode) or not mode.is_cuda:
+        raise EssHipError(f'{what}: mode must be a CUDA(HIP) int32 tensor; there is no CPU path')
+    if mode.dtype != torch.int32 or tuple(mode.shape) != (S,) or not mode.is_contiguous():
+        raise EssHipError(f'{what}: mode must be a contiguous int32 [{S}] tensor, got {mode.dtype}{tuple(mode.shape)}')
+    return mode
+
+
+def event_normalize_samples(x, mode=None, out=None):
+    """EventPreprocessor's normalisation per SAMPLE of x [S, C, H, W] (S independent event streams in one batch): each sample is
+    bit-identical to event_normalize(x[s:s+1]).  mode: int32 [S] on the device or None; a sample with mode[s] == 0 (CARRY_HOLD: no
+    window this round) is not read and comes out zero-filled.  One reduce + one map launch, no host synchronisation."""
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise EssHipError('event_normalize_samples: x must be a CUDA(HIP) tensor; there is no CPU path')
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
+        raise EssHipError(f'event_normalize_samples: x must be a non-empty contiguous fp32 [S, C, H, W] tensor, got {x.dtype}{tuple(x.shape)}')
+    S = x.shape[0]
+    if mode is not None:
+        _stream_modes(mode, S, 'event_normalize_samples')
+    if out is None:
+        out = torch.empty_like(x)
+    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or out.shape != x.shape or not out.is_contiguous():
+        raise EssHipError(f'event_normalize_samples: out must be a contiguous fp32 CUDA(HIP) tensor of x\'s shape {tuple(x.shape)}')
+    ws = workspace(24 * S, x.device, 'evnorm_samples')
+    _check(lib().ess_event_normalize_samples(ptr(x), ptr(out), S, x[0].numel(), ptr(mode, torch.int32), c_void_p(ws.data_ptr()), stream()),
+           'ess_event_normalize_samples')
+    return out
+
+
+CARRY_HOLD, CARRY_TAKE, CARRY_ZERO = 0, 1, 2
+STATE_CARRY_MAX_TENSORS = 16
+
+
+class StateCarryTable:
+    """The checked host tables of one ess_state_carry_masked call, built once for a fixed set of tensors (a streaming driver's static
+    state buffers and the buffers its captured step writes): dst / src lists of equally shaped tensors whose FIRST dimension is the
+    stream index (any dtype: fp32 NCHW states, BF16_C8 / F16_C8 copies incl. [hi | lo], F32_C8); src None: ZERO / HOLD only.  The
+    tensors are kept alive by the table."""
+
+    def __init__(self, dst, src=None):
+        what = 'state_carry_masked'
+        dst = list(dst)
+        n = len(dst)
+        if not 1 <= n <= STATE_CARRY_MAX_TENSORS:
+            raise EssHipError(f'{what}: {n} tensors (1..{STATE_CARRY_MAX_TENSORS} per call)')
+        if src is not None:
+            src = list(src)
+            if len(src) != n:
+                raise EssHipError(f'{what}: {len(src)} source tensors for {n} destinations')
+        S = None
+        for i, d in enumerate(dst):
+            for name, t in (('dst', d),) + ((('src', src[i]),) if src is not None else ()):
+                if not torch.is_tensor(t) or not t.is_cuda:
+                    raise EssHipError(f'{what}: {name}[{i}] must be a CUDA(HIP) tensor; there is no CPU path')
+                if t.dim() < 1 or t.numel() == 0 or not t.is_contiguous():
+                    raise EssHipError(f'{what}: {name}[{i}] must be a non-empty contiguous tensor with the stream index first, got {tuple(t.shape)}')
+            if src is not None and (src[i].shape != d.shape or src[i].dtype != d.dtype):
+                raise EssHipError(f'{what}: src[{i}] is {src[i].dtype}{tuple(src[i].shape)}, dst[{i}] is {d.dtype}{tuple(d.shape)}')
+            if S is None:
+                S = d.shape[0]
+            elif d.shape[0] != S:
+                raise EssHipError(f'{what}: dst[{i}] has {d.shape[0]} streams, dst[0] has {S}')
+            nb = d[0].numel() * d.element_size()
+            if nb % 16:
+                raise EssHipError(f'{what}: dst[{i}] has {nb} bytes per stream, not a multiple of 16')
+        self.n, self.S, self.dst, self.src = n, S, dst, src
+        self.bytes_per_sample = [d[0].numel() * d.element_size() for d in dst]
+        self._dst = (c_void_p * n)(*[d.data_ptr() for d in dst])
+        self._src = (c_void_p * n)(*[t.data_ptr() for t in src]) if src is not None else None
+        self._bytes = (c_int64 * n)(*self.bytes_per_sample)
+
+    def run(self, mode):
+        _stream_modes(mode, self.S, 'state_carry_masked')
+        _check(lib().ess_state_carry_masked(self._dst, self._src, self._bytes, self.n, self.S, ptr(mode, torch.int32), stream()),
+               'ess_state_carry_masked')
+
+
+def state_carry_masked(dst, src, mode):
+    """Per stream s (the first dimension of every tensor): mode[s] == CARRY_TAKE: dst[i][s] = src[i][s]; CARRY_ZERO: dst[i][s] = 0;
+    CARRY_HOLD: dst[i][s] untouched -- for all (<= 16) tensors in ONE launch, the mode words read on the device (int32 [S]).  src
+    None: no stream may TAKE.  A caller that repeats the call on the same tensors keeps a StateCarryTable and calls its run()."""
+    StateCarryTable(dst, src).run(mode)
+
+
 # ------------------------------------------------------------------------------------------ events -> voxel grids
 def _slice_offsets(offsets, n_events, device):
     off = torch.as_tensor(offsets, dtype=torch.int64)
@@ -788,8 +876,14 @@ def resize_nearest(x, size):
     return y
 
 
+NORM_SPLIT_BY_PLANE = 1 << 30  # ESS_NORM_SPLIT_BY_PLANE: tuning_set('norm_split_wgs', ...) -- the plane size alone decides the split
+
+
 def tuning_set(key, value):
-    """Process-wide kernel-choice switch (include/ess_hip.h: results are identical for every setting)."""
+    """Process-wide kernel-choice switch (include/ess_hip.h).  'conv_wide': results are identical for every setting;
+    'in_small_threads' and 'norm_split_wgs' change the summation order of the norm statistics, i.e. results in their last bits
+    ('norm_split_wgs': NORM_SPLIT_BY_PLANE makes that order independent of the batch size; a value <= 0 returns to the process's own
+    setting)."""
     _check(lib().ess_tuning_set(key.encode(), int(value)), 'ess_tuning_set')
 
 

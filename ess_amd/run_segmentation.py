@@ -23,12 +23,21 @@ graph=True records one window (normalise, step, state carry into static buffers,
 replays it; the first window of a sequence runs eagerly (no previous state: different launches).  Results are bit-identical to the
 eager path.  The compute configuration (hip.set_compute) is read when a window runs; a captured graph keeps the one it was
 recorded under.  File readers, image writers and displays are out of scope, as for the reconstruction driver.
+
+MultiStreamSegmenter serves S independent event streams (a stereo pair, a vehicle rig, a replay farm) as ONE batch per round.  What
+makes a stream's results independent of the batch it rides in: per-sample normalisation statistics (hip.event_normalize_samples,
+bit-identical per sample to the single-stream kernel), and a recurrent state that lives in static [S, ...] buffers from
+construction and is steered per stream by mode words in device memory (hip.state_carry_masked: HOLD / TAKE / ZERO).  A restart is a
+ZEROED state, not an absent one -- the reference's ConvLSTM / ConvGRU create a zero state when prev_state is None
+(e2vid/model/submodules.py:196-207, 255-262) -- so every window, the first included, runs the ordinary with-state launches and one
+captured graph serves them all.  An idle stream rides along on a zero grid and its new state is discarded: it costs its share of
+the batch's compute (compacting the batch is not done).
 """
 import torch
 
 from . import hip
 from .e2vid.image_reconstructor import ImageReconstructor
-from .e2vid.run_reconstruction import GraphedWindowState, events_to_voxel_grid_device
+from .e2vid.run_reconstruction import _PARTS, GraphedWindowState, events_to_voxel_grid_device
 
 
 class SegmentationResult:
@@ -40,6 +49,29 @@ class SegmentationResult:
 
     def clone(self):
         return SegmentationResult(*(None if t is None else t.clone() for t in (self.labels, self.colour, self.confidence)))
+
+
+def _models_from_checkpoints(e2vid_path, ess_checkpoint_path, settings_or_kwargs):
+    """-> (encoder, decoder, height, width, options, palette): see StreamingSegmenter.from_checkpoints"""
+    from .e2vid.options.inference_options import default_options
+    from .e2vid.utils.loading_utils import load_model
+    from .models.style_networks import SemSegE2VID
+    s = settings_or_kwargs
+    if isinstance(s, dict):
+        K, height, width = s['num_classes'], s['height'], s['width']
+        skip, skip_type = s.get('skip_connect', True), s.get('skip_type', 'concat')
+        options, palette = s.get('options'), s.get('palette')
+    else:
+        K, (height, width) = s.semseg_num_classes, s.img_size_b
+        skip, skip_type = s.skip_connect_task, s.skip_connect_task_type
+        options, palette = getattr(s, 'e2vid_options', None), getattr(s, 'semseg_color_map', None)
+    encoder, _ = load_model(e2vid_path)
+    decoder = SemSegE2VID(input_c=256, output_c=K, skip_connect=skip, skip_type=skip_type)
+    ckpt = torch.load(ess_checkpoint_path, map_location='cpu', weights_only=False)  # (utils/saver.py: one entry per model name)
+    if 'back_end' not in ckpt:
+        raise hip.EssHipError(f"{ess_checkpoint_path} has no 'back_end' entry (CheckpointSaver layout)")
+    decoder.load_state_dict(ckpt['back_end'])
+    return encoder, decoder, height, width, options if options is not None else default_options(), palette
 
 
 class StreamingSegmenter(GraphedWindowState):
@@ -76,26 +108,9 @@ class StreamingSegmenter(GraphedWindowState):
         Settings object (semseg_num_classes, skip_connect_task, skip_connect_task_type, img_size_b, semseg_color_map, optionally
         e2vid options) or a dict with num_classes, height, width and optionally skip_connect (True), skip_type ('concat'),
         options, palette; further keyword arguments go to the constructor."""
-        from .e2vid.options.inference_options import default_options
-        from .e2vid.utils.loading_utils import load_model
-        from .models.style_networks import SemSegE2VID
-        s = settings_or_kwargs
-        if isinstance(s, dict):
-            K, height, width = s['num_classes'], s['height'], s['width']
-            skip, skip_type = s.get('skip_connect', True), s.get('skip_type', 'concat')
-            options, palette = s.get('options'), s.get('palette')
-        else:
-            K, (height, width) = s.semseg_num_classes, s.img_size_b
-            skip, skip_type = s.skip_connect_task, s.skip_connect_task_type
-            options, palette = getattr(s, 'e2vid_options', None), getattr(s, 'semseg_color_map', None)
-        encoder, _ = load_model(e2vid_path)
-        decoder = SemSegE2VID(input_c=256, output_c=K, skip_connect=skip, skip_type=skip_type)
-        ckpt = torch.load(ess_checkpoint_path, map_location='cpu', weights_only=False)  # (utils/saver.py: one entry per model name)
-        if 'back_end' not in ckpt:
-            raise hip.EssHipError(f"{ess_checkpoint_path} has no 'back_end' entry (CheckpointSaver layout)")
-        decoder.load_state_dict(ckpt['back_end'])
+        encoder, decoder, height, width, options, palette = _models_from_checkpoints(e2vid_path, ess_checkpoint_path, settings_or_kwargs)
         kw.setdefault('palette', palette)
-        return cls(encoder, decoder, height, width, options if options is not None else default_options(), **kw)
+        return cls(encoder, decoder, height, width, options, **kw)
 
     def reset(self):
         self.rec.last_states_for_each_channel = {'grayscale': None}
@@ -138,3 +153,241 @@ class StreamingSegmenter(GraphedWindowState):
         self.n_windows += 1
         res = SegmentationResult(*self._outputs)
         return res.clone() if self.copy_outputs else res
+
+
+# ---------------------------------------------------------------------------------------------- S streams in one batch
+class MultiSegmentationResult:
+    """labels uint8 [S, H, W]; colour uint8 [S, H, W, 3] or None (no palette); confidence fp32 [S, H, W] or None; valid: a host
+    tuple of S bools -- stream s had a window this round.  The rows of the other (idle) streams are UNSPECIFIED."""
+    __slots__ = ('labels', 'colour', 'confidence', 'valid')
+
+    def __init__(self, labels, colour=None, confidence=None, valid=()):
+        self.labels, self.colour, self.confidence, self.valid = labels, colour, confidence, tuple(bool(v) for v in valid)
+
+    def clone(self):
+        return MultiSegmentationResult(*(None if t is None else t.clone() for t in (self.labels, self.colour, self.confidence)),
+                                       valid=self.valid)
+
+
+def stream_modes(pending, active):
+    """The per-stream mode words of one round, from host lists of bools -> (mode_pre, mode_post, pending after the round).
+    mode_pre steers the state carry in FRONT of the step: CARRY_ZERO for a stream that restarts now (a pending restart meets an
+    active window), CARRY_HOLD otherwise; mode_post steers the normalisation and the carry BEHIND it: CARRY_TAKE for an active stream
+    (its new state is kept), CARRY_HOLD for an idle one (zero grid, new state discarded).  A pending restart of an idle stream stays
+    pending."""
+    if len(pending) != len(active):
+        raise hip.EssHipError(f'stream_modes: {len(pending)} pending flags for {len(active)} streams')
+    pre = [hip.CARRY_ZERO if (p and a) else hip.CARRY_HOLD for p, a in zip(pending, active)]
+    post = [hip.CARRY_TAKE if a else hip.CARRY_HOLD for a in active]
+    return pre, post, [bool(p and not a) for p, a in zip(pending, active)]
+
+
+def check_active(active, n_streams):
+    """active: None (every stream) or S truth values on the host -> list of S bools"""
+    if active is None:
+        return [True] * n_streams
+    if torch.is_tensor(active):
+        active = active.tolist()
+    active = list(active)
+    if len(active) != n_streams:
+        raise hip.EssHipError(f'active has {len(active)} entries, the segmenter serves n_streams={n_streams}')
+    return [bool(a) for a in active]
+
+
+def check_stream_grids(shape, n_streams, num_bins, height, width):
+    if tuple(shape) != (n_streams, num_bins, height, width):
+        raise hip.EssHipError(f'expected [{n_streams}, {num_bins}, {height}, {width}] voxel grids (one per stream), got {tuple(shape)}')
+
+
+def check_stream_events(events, n_streams):
+    """events: S entries, each [N, 4] rows (t, x, y, polarity) or None / empty (idle) -> (list of [N, 4] tensors or None, active)"""
+    if not isinstance(events, (list, tuple)) or len(events) != n_streams:
+        n = len(events) if isinstance(events, (list, tuple)) else type(events).__name__
+        raise hip.EssHipError(f'events must be a list with one entry per stream: got {n}, the segmenter serves n_streams={n_streams}')
+    out = []
+    for s, e in enumerate(events):
+        if e is not None:
+            e = torch.as_tensor(e)
+            if e.dim() != 2 or e.shape[1] != 4:
+                raise hip.EssHipError(f'events[{s}] must be [N, 4] rows (t, x, y, polarity) or None, got {tuple(e.shape)}')
+            if e.shape[0] == 0:
+                e = None
+        out.append(e)
+    return out, [e is not None for e in out]
+
+
+class MultiStreamSegmenter(GraphedWindowState):
+    """n_streams independent sequences, one ROUND (one window of every active stream) at a time, as one batch.
+    update(grids [S, num_bins, H, W], active=None) / update_from_events(list of S [N, 4] arrays or None) -> MultiSegmentationResult;
+    reset(streams=None): these streams (default: all) start from a zero state at their next active window.
+
+    Each stream's labels, colours and confidences are those it would get alone in a MultiStreamSegmenter(n_streams=1): normalisation
+    statistics are per stream and the layers' arithmetic per sample.  Bit for bit that holds where no kernel choice follows the batch
+    size.  Two do at large sizes (measured at 480 x 640, B = 8 against B = 1: some tens of labels of 307 200, confidences to 5e-4): the
+    form of the encoder's 5x5 / stride-2 convolutions (pin it with submodules.set_s2d_mode('2')) and the slice count of the decoder's
+    split InstanceNorm statistics (pin it with hip.tuning_set('norm_split_wgs', hip.NORM_SPLIT_BY_PLANE)).  Both switches are
+    process-wide, so the driver leaves them to the deployment; with both pinned the S = 8 and S = 1 results are equal.  Idle streams (active[s] false, or None in update_from_events) ride along on a zero grid; their
+    state is left as it was and their result rows are unspecified.  The state's form depends on the compute configuration, which
+    is therefore fixed at construction: update() refuses another one.  graph=True: the round's device work is captured ONCE (n_captures
+    stays 1) and every later round -- whatever its mix of advancing, idle and restarting streams -- is two small input copies and one
+    replay.  Other arguments: see StreamingSegmenter."""
+
+    def __init__(self, encoder, decoder, height, width, options, n_streams, device=None, graph=False, copy=True, palette=None,
+                 want_confidence=False, out_hw=None):
+        if not isinstance(n_streams, int) or isinstance(n_streams, bool) or n_streams < 1:
+            raise hip.EssHipError(f'n_streams={n_streams!r}: a positive number of streams is needed')
+        self.n_streams = n_streams
+        self.copy_outputs = bool(copy)
+        self.device = device if device is not None else torch.device('cuda:0')
+        self.model = encoder.to(self.device).eval()
+        self.decoder = decoder.to(self.device).eval()
+        self.rec = ImageReconstructor(self.model, height, width, encoder.num_bins, self.device, options)
+        if self.rec.no_recurrent:
+            raise hip.EssHipError('MultiStreamSegmenter: options.no_recurrent leaves no state to carry; use StreamingSegmenter')
+        if self.rec.event_preprocessor.no_normalize:
+            raise hip.EssHipError('MultiStreamSegmenter: options.no_normalize is not supported (the normalisation launch is what zero-fills idle streams)')
+        self.height, self.width, self.num_bins = height, width, encoder.num_bins
+        crop = self.rec.crop
+        self.window = (crop.iy0, crop.ix0, crop.iy1 - crop.iy0, crop.ix1 - crop.ix0)
+        self.out_hw = None if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+        self.palette = None if palette is None else torch.as_tensor(palette).to(self.device).contiguous()
+        self.want_confidence = bool(want_confidence)
+        self.use_graph = graph
+        self.n_windows = 0   # rounds
+        self.n_captures = 0  # hipGraph captures (graph mode: 1 from the first round on)
+        self.last_latent = None  # (eager rounds: the latents handed to decoder.predict, for inspection)
+        self.compute = hip.compute_name()
+        S = n_streams
+        self._in = torch.zeros(S, self.num_bins, height, width, dtype=torch.float32, device=self.device)
+        self._modes = torch.zeros(2, S, dtype=torch.int32, device=self.device)  # [0]: in front of the step, [1]: behind it
+        self._pending = [True] * S
+        self._build_state()
+
+    @classmethod
+    def from_checkpoints(cls, e2vid_path, ess_checkpoint_path, settings_or_kwargs, n_streams, **kw):
+        """as StreamingSegmenter.from_checkpoints, plus the number of streams"""
+        encoder, decoder, height, width, options, palette = _models_from_checkpoints(e2vid_path, ess_checkpoint_path, settings_or_kwargs)
+        kw.setdefault('palette', palette)
+        return cls(encoder, decoder, height, width, options, n_streams, **kw)
+
+    # ---- state: static [S, ...] buffers from construction, never None
+    def _step(self, ev):
+        """one encoder-only step of the whole batch from the carried state; the carried state stays the static buffers"""
+        rec = self.rec
+        _, states, latent = rec._step(ev, False, False, final_lean=not hip.mixed())
+        rec.last_states_for_each_channel['grayscale'] = self._carried
+        return states, latent
+
+    def _build_state(self):
+        """Learn the state's forms from the zero-input step (run once without and once WITH a state: the form must be a fixed point of
+        the with-state step, which is the only one a round runs), make the static buffers the carried state, then ZERO everything."""
+        rec = self.rec
+        rec.last_states_for_each_channel = {'grayscale': None}
+        self._carried = None
+        with torch.no_grad():
+            ev = rec.crop.pad(self._in)
+            if not ev.is_contiguous():
+                ev = ev.contiguous()
+            states, _ = self._step(ev)
+            self._adopt_state(states)  # (allocates the static buffers in the forms this step left)
+            self._carried = rec.last_states_for_each_channel['grayscale']
+            states, _ = self._step(ev)
+            self._src_parts(states)  # (raises when the with-state step leaves another form)
+        self._dst = [st[0][k] for st in self._static for k in _PARTS if st[0][k] is not None]
+        self._pre = hip.StateCarryTable(self._dst)  # (no source: ZERO / HOLD)
+        self._modes[0].fill_(hip.CARRY_ZERO)
+        self._pre.run(self._modes[0])
+        self._modes.zero_()
+
+    def _src_parts(self, states):
+        """the tensors of a step's output state, in the order of the static buffers (self._dst) -- refused when the forms differ"""
+        src = []
+        for st, (parts, hilo, shape) in zip(self._static, self._state_tensors(states)):
+            sp, s_hilo, s_shape, _ = st
+            if [t is None for t in sp.values()] != [t is None for t in parts.values()] or s_hilo != hilo or s_shape != shape:
+                raise hip.EssHipError('streaming: a step left its recurrent state in another form than the static buffers were made for')
+            src += [parts[k] for k in _PARTS if sp[k] is not None]
+        return src
+
+    def reset(self, streams=None):
+        for s in (range(self.n_streams) if streams is None else streams):
+            if not 0 <= int(s) < self.n_streams:
+                raise hip.EssHipError(f'reset: stream {s} of n_streams={self.n_streams}')
+            self._pending[int(s)] = True
+
+    # ---- one round
+    def _round(self):
+        """the device work of one round on the static input and mode buffers -> (labels, colour, confidence)"""
+        rec, pre = self.rec, self.rec.event_preprocessor
+        with torch.no_grad():
+            self._pre.run(self._modes[0])  # restarting streams: state = 0
+            ev = self._in
+            for x, y in pre.hot_pixel_locations:
+                ev[:, :, y, x] = 0
+            if pre.flip:
+                ev = torch.flip(ev, dims=[2, 3]).contiguous()
+            ev = rec.crop.pad(hip.event_normalize_samples(ev, self._modes[1]))  # (idle streams: a zero grid)
+            if not ev.is_contiguous():
+                ev = ev.contiguous()
+            states, latent = self._step(ev)
+            src = self._src_parts(states)  # (taken in front of predict, which may attach further copies to the latents)
+            self.last_latent = latent
+            out = self.decoder.predict(latent, out_hw=self.out_hw, window=self.window, palette=self.palette,
+                                       want_confidence=self.want_confidence)
+            hip.StateCarryTable(self._dst, src).run(self._modes[1])  # active streams: state = new state
+        return out
+
+    def _capture(self):
+        """GraphedWindowState's recipe -- one eager run on a side stream, then the recording on the current stream -- with the
+        warm-up run's effect on the state avoided instead of undone: every stream is on HOLD during it."""
+        self._modes.zero_()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._round()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self._g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._g):
+            self._outputs = self._round()
+        self.last_latent = None
+        self.n_captures += 1
+
+    def update(self, grids, active=None):
+        if not torch.is_tensor(grids):
+            raise hip.EssHipError(f'grids must be a tensor [{self.n_streams}, {self.num_bins}, {self.height}, {self.width}], got {type(grids).__name__}')
+        check_stream_grids(grids.shape, self.n_streams, self.num_bins, self.height, self.width)
+        active = check_active(active, self.n_streams)
+        if hip.compute_name() != self.compute:
+            raise hip.EssHipError(f"MultiStreamSegmenter: built in the '{self.compute}' configuration (its state buffers have that form), "
+                                  f"called in '{hip.compute_name()}'")
+        pre, post, self._pending = stream_modes(self._pending, active)
+        if self.use_graph and self._g is None:
+            self._capture()
+        self._modes.copy_(torch.tensor([pre, post], dtype=torch.int32), non_blocking=True)
+        self._in.copy_(grids, non_blocking=True)
+        if self.use_graph:
+            self._g.replay()
+            out = self._outputs
+        else:
+            out = self._round()
+        self.n_windows += 1
+        res = MultiSegmentationResult(*out, valid=active)
+        return res.clone() if (self.use_graph and self.copy_outputs) else res
+
+    def update_from_events(self, events):
+        """events: S entries, [N, 4] rows (t, x, y, polarity) of the stream's window or None (idle).  All grids are built by ONE
+        hip.voxel_grid_temporal call over the concatenated events; an idle stream is an empty slice (an all-zero grid)."""
+        evs, active = check_stream_events(events, self.n_streams)
+        if not any(active):
+            return self.update(self._in, active)  # (nothing is read of an idle stream's grid)
+        offsets = [0]
+        for e in evs:
+            offsets.append(offsets[-1] + (0 if e is None else e.shape[0]))
+        ev = torch.cat([e.to(torch.float64) for e in evs if e is not None]).to(self.device)
+        t = ev[:, 0].contiguous()
+        x = ev[:, 1].to(torch.int32).contiguous()
+        y = ev[:, 2].to(torch.int32).contiguous()
+        p = ev[:, 3].to(torch.float32).contiguous()
+        grids = hip.voxel_grid_temporal(x, y, t, p, offsets, self.num_bins, self.height, self.width, separate_pol=False)
+        return self.update(grids, active)

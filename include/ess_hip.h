@@ -327,6 +327,37 @@ int ess_event_normalize(const float* x, float* y, int64_t n, void* workspace, es
  * copies), y = [T][B][chunk] (slice t = a contiguous [B, C, H, W] tensor), statistics per slice over the whole batch.
  * workspace: T * 24 bytes.                                                                          */
 int ess_event_normalize_slices(const float* x, float* y, int32_t B, int32_t T, int64_t chunk, void* workspace, ess_stream_t stream);
+/* The same normalisation PER SAMPLE, for S independent event streams batched into one tensor -- PURELY ADDITIVE to ABI 110:
+ * x, y = [S][chunk] with chunk = C*H*W; sample s gets its own non-zero mean / std (an all-zero sample is copied unchanged).
+ * Per sample the call repeats ess_event_normalize(x + s*chunk, y + s*chunk, chunk) exactly: the reduction gives every sample the
+ * workgroup count, the per-thread element walk and the block sums that call uses for n = chunk (its grid is sized from the element
+ * count, so a grid sized from S*chunk would add other partial sums), and the map is the same expression.  A stream's values then do
+ * not depend on whether or with whom it was batched -- to the extent ess_event_normalize repeats itself: both add their <= 128
+ * workgroup partial sums with fp64 atomics in arrival order, so the fp64 totals can differ in their last bit from run to run before
+ * they are rounded to fp32 (no difference has been seen in the results).  mode (device, int32 [S], nullable = every sample active): a sample with mode[s] == 0 is NOT READ and
+ * its y is zero-filled (a stream without a window this round: the encoder still sees a defined input).
+ * workspace: S * 24 bytes, zeroed by the call.  Three stream operations (memset, reduce, map); no host synchronisation.          */
+int ess_event_normalize_samples(const float* x, float* y, int32_t S, int64_t chunk, const int32_t* mode, void* workspace,
+                                ess_stream_t stream);
+
+/* Masked carry of a batched recurrent state -- PURELY ADDITIVE to ABI 110.  All levels and all parts of the state (fp32 NCHW h and
+ * c, the BF16_C8 copy, the F16_C8 copy incl. its [hi | lo] form, F32_C8) in ONE launch, steered per sample by a mode word in
+ * DEVICE memory, so that a captured launch stays valid while the set of advancing / idle / restarting streams changes.
+ * dst, src, bytes_per_sample: HOST arrays of n_tensors (1..16) entries; they reach the kernel by value (nothing of them needs to
+ * outlive the call, also under stream capture).  Every carried form has the sample index outermost: tensor i = n_samples
+ * contiguous records of bytes_per_sample[i] bytes.  mode: device int32 [n_samples]:
+ *   ESS_CARRY_HOLD (0, and any other word)  the sample's dst bytes are neither read nor written;
+ *   ESS_CARRY_TAKE (1)                      dst record = src record;
+ *   ESS_CARRY_ZERO (2)                      dst record = 0; src is not read.
+ * src may be NULL when no sample is TAKE; the mode words live on the device, so the entry point cannot refuse a TAKE word that
+ * meets a NULL src: such a sample is left as it was (a HOLD).  With a src table every entry must be a pointer.
+ * Pointers and bytes_per_sample must be multiples of 16 (every state form is: planes are padded to /8), and the ranges
+ * [dst[i], dst[i] + n_samples * bytes) and [src[i], src[i] + n_samples * bytes) must be disjoint; each is checked on the host,
+ * ESS_EINVAL with a message otherwise.  A workgroup owns one (tensor, sample, segment), reads mode[sample] once and
+ * moves 16-byte vectors; no host synchronisation.                                                                                */
+enum { ESS_CARRY_HOLD = 0, ESS_CARRY_TAKE = 1, ESS_CARRY_ZERO = 2 };
+int ess_state_carry_masked(void* const* dst, const void* const* src, const int64_t* bytes_per_sample, int32_t n_tensors,
+                           int32_t n_samples, const int32_t* mode, ess_stream_t stream);
 
 /* ---- events -> voxel grid on the device (the step in front of the encoder) --------------------
  * All slices of a batch in one launch: events concatenated structure-of-arrays, slice s = [slice_offsets[s],
@@ -449,12 +480,19 @@ int ess_seg_head(const void* x, int32_t fmt, const float* weight, const float* b
 int ess_label_confusion(const int64_t* pred_lbl, const int64_t* labels, int64_t* conf, int64_t total, int32_t K,
                         int32_t ignore_index, ess_stream_t stream);
 
-/* ---- tuning switches: process-wide kernel choices that never change a result (every setting runs the same arithmetic in the
- * same order).  "conv_wide": 0 = the 64 x 256-pixel-tile 3x3 kernel always, 1 = the wide-tile kernel where its round count wins
+/* ---- tuning switches: process-wide kernel choices that run the same arithmetic ("conv_wide": in the same order, bit-identical
+ * results; the norm keys below: in another summation order).  "conv_wide": 0 = the 64 x 256-pixel-tile 3x3 kernel always, 1 = the wide-tile kernel where its round count wins
  * (default; environment ESS_CONV_WIDE), 2 = the wide-tile kernel wherever it applies.  ess_tuning_get also answers the read-only
  * key "device_cus" (the compute-unit count the dispatcher's round model uses: queried from the device, 256 on MI355X).
  * "in_small_threads": 256 | 512 (default; environment ESS_IN_SMALL_THREADS) | 1024 -- threads of the fused single-plane InstanceNorm
- * kernels on planes of at most 5120 pixels; the settings differ in the summation order of the statistics only (fp32 rounding).  */
+ * kernels on planes of at most 5120 pixels; the settings differ in the summation order of the statistics only (fp32 rounding).
+ * "norm_split_wgs": the workgroups the split statistics pass of the BF16_C8 norm kernels aims at (default 1024; environment
+ * ESS_NORM_SPLIT_WGS).  The slices a plane is summed in follow from it and from N * ceil(C/8): the statistics of ONE sample depend, in
+ * the summation order of their fp64 partial sums, on the batch size it came in.  ESS_NORM_SPLIT_BY_PLANE lets the plane size alone
+ * decide -- for a caller whose per-sample results must not depend on the batch size in the last bit (multi-stream serving against a
+ * B = 1 check); a value <= 0 returns to the process's own setting (the environment variable, else 1024).  Unlike "conv_wide", the
+ * last two keys DO change results in the last bits: same sums, another order.  */
+#define ESS_NORM_SPLIT_BY_PLANE (1 << 30)
 int ess_tuning_set(const char* key, int32_t value);
 int ess_tuning_get(const char* key, int32_t* value);
 

@@ -8,7 +8,15 @@ normalisation + recurrent step + semantic decoder + labels.  Two ways, in ONE pr
 
 Per (configuration, mode, way): `--reps` repetitions of `--windows` windows after `--warmup` windows, each repetition timed with the
 host clock between device synchronisations; median and range over the repetitions, ms per window.  One JSON line.
-usage: python tools/bench_seg_stream.py [--compute mixed,bf16 --windows 40 --warmup 8 --reps 3 --recurrent convlstm]"""
+
+--streams S[,S...] measures multi-stream serving INSTEAD: per stream count, one ROUND = one window of each of S streams, two ways,
+alternating in the same process with the same repetition scheme:
+
+  multi        ess_amd.run_segmentation.MultiStreamSegmenter(n_streams=S).update_from_events, eager issue and hipGraph replay;
+  round_robin  S independent replayed StreamingSegmenters (graph=True) served one after the other -- what the package offered before.
+
+Reported: ms per round and aggregate windows / s.
+usage: python tools/bench_seg_stream.py [--compute mixed,bf16 --windows 40 --warmup 8 --reps 3 --recurrent convlstm --streams 1,2,4,8]"""
 import argparse
 import json
 import os
@@ -34,13 +42,14 @@ def main():
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--recurrent', default='convlstm')
     ap.add_argument('--compute', default='mixed,bf16')
+    ap.add_argument('--streams', default=None, help='comma-separated stream counts: measure MultiStreamSegmenter against round-robin serving')
     a = ap.parse_args()
     from ess_amd import hip
     from ess_amd.e2vid.model.model import E2VIDRecurrent
     from ess_amd.e2vid.options.inference_options import default_options
     from ess_amd.e2vid.run_reconstruction import StreamingReconstructor, events_to_voxel_grid_device
     from ess_amd.models.style_networks import SemSegE2VID
-    from ess_amd.run_segmentation import StreamingSegmenter
+    from ess_amd.run_segmentation import MultiStreamSegmenter, StreamingSegmenter
     cfg = dict(num_bins=a.bins, skip_type='sum', num_encoders=3, base_num_channels=32, num_residual_blocks=2, norm='BN',
                use_upsample_conv=True, recurrent_block_type=a.recurrent)
     g = np.random.default_rng(0)
@@ -63,6 +72,11 @@ def main():
             step(wins[i % 4])
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / a.windows * 1e3
+
+    if a.streams:
+        multi_stream(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, StreamingSegmenter, default_options)
+        print(json.dumps(out))
+        return
 
     for compute in a.compute.split(','):
         hip.set_compute(compute)
@@ -94,6 +108,55 @@ def main():
         finally:
             hip.set_compute('fp32')
     print(json.dumps(out))
+
+
+def multi_stream(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, StreamingSegmenter, default_options):
+    out['shape'] = f'S streams of {a.bins}x{a.height}x{a.width} K={a.classes}'
+    del out['ms_per_window']
+    out['ms_per_round'], out['windows_per_s'] = {}, {}
+
+    def models():
+        torch.manual_seed(6)
+        return E2VIDRecurrent(dict(cfg)), SemSegE2VID(256, a.classes, skip_connect=True, skip_type='concat')
+
+    def timed(step):  # a round: stream s gets window (i + s) % 4
+        for i in range(a.warmup):
+            step(i)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(a.windows):
+            step(i)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / a.windows * 1e3
+
+    for compute in a.compute.split(','):
+        hip.set_compute(compute)
+        try:
+            for S in (int(v) for v in a.streams.split(',')):
+                solos = [StreamingSegmenter(*models(), a.height, a.width, default_options(), graph=True) for _ in range(S)]
+                multis = {mode: MultiStreamSegmenter(*models(), a.height, a.width, default_options(), S, graph=mode == 'graph')
+                          for mode in ('eager', 'graph')}
+
+                def round_robin(i):
+                    for s, seg in enumerate(solos):
+                        seg.update_from_events(wins[(i + s) % 4])
+
+                ways = {'round_robin/graph': round_robin}
+                for mode, seg in multis.items():
+                    ways[f'multi/{mode}'] = (lambda seg: lambda i: seg.update_from_events([wins[(i + s) % 4] for s in range(S)]))(seg)
+                ms = {k: [] for k in ways}
+                for _ in range(a.reps):  # alternating: drift of the box hits every way alike
+                    for k, fn in ways.items():
+                        ms[k].append(timed(fn))
+                for k, v in ms.items():
+                    med = statistics.median(v)
+                    out['ms_per_round'][f'{compute}/S={S}/{k}'] = {'median': round(med, 4), 'min': round(min(v), 4), 'max': round(max(v), 4)}
+                    out['windows_per_s'][f'{compute}/S={S}/{k}'] = round(S / med * 1e3, 1)
+                assert all(seg.n_captures == (1 if mode == 'graph' else 0) for mode, seg in multis.items())
+                del solos, multis, ways
+                torch.cuda.empty_cache()
+        finally:
+            hip.set_compute('fp32')
 
 
 if __name__ == '__main__':
