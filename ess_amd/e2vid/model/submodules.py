@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 from torch.nn import init
 
-from ... import hip
+from ... import copies, hip
 from ...functional import columns, derived, packed_rows, packed_weight
 
 _ACT = {None: hip.ACT_NONE, 'relu': hip.ACT_RELU, 'sigmoid': hip.ACT_SIGMOID, 'tanh': hip.ACT_TANH}
@@ -27,49 +27,10 @@ def _inference_only(*tensors):
                                   'torch.no_grad() in ESS: training/ess_trainer.py:52-54,277-280)')
 
 
-def _attach_c8(t, c8):
-    """Remember the BF16_C8 staging copy of a freshly written fp32 tensor (and the tensor version it belongs to)."""
-    t.ess_c8 = (c8, t._version)
-
-
-def _mark_fp32_unwritten(t):
-    """`t` was allocated but only its BF16_C8 copy was computed (a tensor whose single consumer stages from the copy)."""
-    t.ess_fp32_unwritten = True
-
-
-def _c8_placeholder(N, C, H, W, device, c8):
-    """The fp32 NCHW tensor of an activation that exists as a BF16_C8 copy only: a stride-0 view of ONE element (no memory behind
-    it), carrying shape, device and the copy; `_fp32` refuses its values."""
-    t = torch.empty((), dtype=torch.float32, device=device).expand(N, C, H, W)
-    _attach_c8(t, c8)
-    _mark_fp32_unwritten(t)
-    return t
-
-
-def _fp32(t):
-    """The fp32 tensor itself -- refused when only the BF16_C8 copy of it exists."""
-    if getattr(t, 'ess_fp32_unwritten', False):
-        raise hip.EssHipError('this tensor was produced as a BF16_C8 copy only (lean recurrent state / internal activation); '
-                              'its fp32 values do not exist')
-    return t
-
-
 def _fp32_any(t):
     """fp32 values of `t`: the tensor itself, or -- when only its BF16_C8 copy was produced -- the copy converted back."""
-    if t is None:
-        return None
-    if getattr(t, 'ess_fp32_unwritten', False):
-        c8 = _c8_of(t)
-        if c8 is None:
-            return _fp32(t)  # (raises)
-        return hip.from_bf16_c8(c8, t.shape[1])
-    return t
-
-
-def _c8_of(t):
-    """The staging copy of `t`, unless `t` was modified in place since the producing kernel wrote both."""
-    c8 = getattr(t, 'ess_c8', None)
-    return c8[0] if c8 is not None and c8[1] == t._version else None
+    r = copies.of(t)
+    return hip.from_bf16_c8(r.c8, t.shape[1]) if r.unwritten and r.c8 is not None else copies.require_fp32(t)
 
 
 def _fold(spec, bias, norm_kind, norm_layer):
@@ -159,9 +120,9 @@ class ConvLayer(nn.Module):
     def forward(self, x, x1=None, residual=None, want_c8=False, c8_only=False, weight=None):
         """x1: optional second source, channel-concatenated on the fly.
         want_c8: (bf16 arithmetic only) also emit the output as a BF16_C8 staging copy, attached to the returned
-        tensor as `.ess_c8`, for a following 3x3 / 5x5 convolution to stage from (see ConvLSTM.forward).
+        tensor (`copies.of(out).c8`), for a following 3x3 / 5x5 convolution to stage from (see ConvLSTM.forward).
         c8_only: (with want_c8, bf16 arithmetic) do not write the fp32 output at all -- for an activation whose only
-        consumer stages from the copy; the returned tensor is a placeholder that refuses fp32 use (`_fp32`)."""
+        consumer stages from the copy; the returned tensor is a placeholder that refuses fp32 use (`copies.require_fp32`)."""
         _inference_only(x, x1)
         _check_eval(self, self.norm)
         c = self.conv2d
@@ -177,11 +138,11 @@ class ConvLayer(nn.Module):
         if want_c8 and bf:
             c8 = hip.bf16_c8_empty(N, c.out_channels, spec.H_out, spec.W_out, x.device)
         k = c.kernel_size[0]
-        x8 = _c8_of(x) if bf and x1 is None and hip.c8_stageable(k, c.stride[0], c.padding[0]) else None
+        x8 = copies.of(x).c8 if bf and x1 is None and hip.c8_stageable(k, c.stride[0], c.padding[0]) else None
         if bf and x1 is not None and (C0 % 8) == 0 and hip.c8_stageable(k, c.stride[0], c.padding[0]):
             # both concat sources from their producers' BF16_C8 copies (the prediction layer over decoder output + head: half the
             # bytes of the two fp32 tensors, and the decoder output need not exist in fp32 at all); bit-identical operands
-            a8, b8 = _c8_of(x), _c8_of(x1)
+            a8, b8 = copies.of(x).c8, copies.of(x1).c8
             if a8 is not None and b8 is not None:
                 hip.conv_forward(spec, a8, b8, packed_weight(spec, wt), scale, shift, residual, out=out, src_fmt=hip.FMT_BF16_C8)
                 return out
@@ -205,32 +166,29 @@ class ConvLayer(nn.Module):
                 hip.conv_forward(spec, x8, None, packed_weight(spec, wt), scale, shift, residual,
                                  out=None if skip_fp32 else out, out_bf=c8, src_fmt=hip.FMT_BF16_C8)
         elif as_out:
-            hip.conv_forward(spec, _fp32(x), None if x1 is None else _fp32(x1), packed_weight(spec, wt), scale, shift, None, out=c8,
-                             out_fmt=hip.FMT_BF16_C8)
+            hip.conv_forward(spec, copies.require_fp32(x), None if x1 is None else copies.require_fp32(x1), packed_weight(spec, wt),
+                             scale, shift, None, out=c8, out_fmt=hip.FMT_BF16_C8)
         else:
-            hip.conv_forward(spec, _fp32(x), None if x1 is None else _fp32(x1), packed_weight(spec, wt), scale, shift,
-                             residual, out=None if skip_fp32 else out, out_bf=c8)
+            hip.conv_forward(spec, copies.require_fp32(x), None if x1 is None else copies.require_fp32(x1), packed_weight(spec, wt),
+                             scale, shift, residual, out=None if skip_fp32 else out, out_bf=c8)
         if c8 is not None:
-            _attach_c8(out, c8)
+            copies.attach(out, c8=c8)
         if skip_fp32:
-            _mark_fp32_unwritten(out)
+            copies.attach(out, unwritten=True)
         return out
 
 
 # ---- 'mixed' configuration (hip.set_compute('mixed'), round 6): the recurrent part of the frozen encoder -- head, the stride-2
-# convolutions, the ConvLSTM gates -- on IEEE-half operands (ESS_COMPUTE_F16).  Activations travel as F16_C8 copies (`.ess_h16` =
-# (tensor, version, hilo)); the convolution in front of a recurrent block writes a [hi | lo] half pair (its post-ReLU values carry
-# means far above their spread: rounding THEM to 11 bits was the largest term of the encoder's error, tools/hybrid_rounding_ablation.py),
-# and so does the last time step's ConvLSTM for h' -- the event latents.  A [hi | lo] source enters a convolution as 2 C channels
-# against a weight whose input columns are repeated.
+# convolutions, the ConvLSTM gates -- on IEEE-half operands (ESS_COMPUTE_F16).  Activations travel as F16_C8 copies
+# (`copies.of(t).h16` = (tensor, hilo), valid while t is unmodified); the convolution in front of a recurrent block writes a [hi | lo]
+# half pair (its post-ReLU values carry means far above their spread: rounding THEM to 11 bits was the largest term of the encoder's
+# error, tools/hybrid_rounding_ablation.py), and so does the last time step's ConvLSTM for h' -- the event latents.  A [hi | lo]
+# source enters a convolution as 2 C channels against a weight whose input columns are repeated.
 
 
 def _half_source(t):
     """(F16_C8 tensor, hilo) of an activation inside the mixed encoder: the producer's copy, else its fp32 values converted"""
-    h = hip.h16_of(t)
-    if h is not None:
-        return h
-    return hip.to_f16_c8(_fp32(t).contiguous()), False
+    return copies.of(t).h16 or (hip.to_f16_c8(copies.require_fp32(t).contiguous()), False)
 
 
 def _convlayer_forward_mixed(self, x, hilo_out=False, want_fp32=False):
@@ -242,7 +200,7 @@ def _convlayer_forward_mixed(self, x, hilo_out=False, want_fp32=False):
     k, s, p = c.kernel_size[0], c.stride[0], c.padding[0]
     act = _ACT[self.activation]
     N, C0, H, W = x.shape
-    is_head = hip.h16_of(x) is None and k == 5 and s == 1 and C0 <= 5 and not getattr(x, 'ess_fp32_unwritten', False)
+    is_head = copies.of(x).h16 is None and k == 5 and s == 1 and C0 <= 5 and not copies.of(x).unwritten
     if is_head:
         spec = hip.conv_spec(N, H, W, C0, 0, c.out_channels, k, s, p, act=act, compute=hip.COMPUTE_F16)
         scale, shift = _fold(spec, c.bias, self.norm, getattr(self, 'norm_layer', None))
@@ -253,9 +211,8 @@ def _convlayer_forward_mixed(self, x, hilo_out=False, want_fp32=False):
         else:
             hip.conv_forward_h16(spec, x.contiguous(), None, packed_weight(spec, c.weight), scale, shift, out=h16, out_fmt=hip.FMT_F16_C8,
                                  src_fp32=True)
-            out = _c8_placeholder(N, c.out_channels, spec.H_out, spec.W_out, x.device, None)
-            del out.ess_c8
-        return hip.attach_h16(out, h16, False)
+            out = copies.placeholder((N, c.out_channels, spec.H_out, spec.W_out), x.device)
+        return copies.attach(out, h16=(h16, False))
     if want_fp32:
         raise hip.EssHipError('ConvLayer(mixed): fp32 outputs exist for the head only')
     s16, hl = _half_source(x)
@@ -275,9 +232,7 @@ def _convlayer_forward_mixed(self, x, hilo_out=False, want_fp32=False):
         spec = hip.conv_spec(N, H, W, Ce, 0, c.out_channels, k, s, p, act=act, compute=hip.COMPUTE_F16)
         sc, sh = _fold(spec, c.bias, self.norm, getattr(self, 'norm_layer', None))
         hip.conv_forward_h16(spec, s16, None, packed_weight(spec, w), sc, sh, out=h16, out_fmt=out_fmt)
-    out = _c8_placeholder(N, c.out_channels, h16.shape[2], h16.shape[3], x.device, None)
-    del out.ess_c8
-    return hip.attach_h16(out, h16, hilo_out)
+    return copies.placeholder((N, c.out_channels, h16.shape[2], h16.shape[3]), x.device, h16=(h16, bool(hilo_out)))
 
 
 def _convlstm_forward_mixed(self, input_, prev_state, lean, hilo_out):
@@ -310,15 +265,14 @@ def _convlstm_forward_mixed(self, input_, prev_state, lean, hilo_out):
     cell, sfmt = _new_cell(N, hid, H, W, input_.device, lean)
     cfmt = hip.FMT_F32_C8 if prev_cell is not None and prev_cell.dim() == 5 else hip.FMT_F32_NCHW
     if lean and sfmt == hip.FMT_F32_C8:
-        hidden = _c8_placeholder(N, hid, H, W, input_.device, None)
-        del hidden.ess_c8
+        hidden = copies.placeholder((N, hid, H, W), input_.device)
         hip.conv_forward_h16(spec, xs, hs, packed_weight(spec, w), None, b, aux0=prev_cell, out=None, out2=cell, out_h16=new16,
                              out_fmt=sfmt, aux_fmt=cfmt)
     else:
         hidden = torch.empty(N, hid, H, W, dtype=torch.float32, device=input_.device)
         hip.conv_forward_h16(spec, xs, hs, packed_weight(spec, w), None, b, aux0=prev_cell, out=hidden, out2=cell, out_h16=new16,
                              out_fmt=sfmt, aux_fmt=cfmt)
-    hip.attach_h16(hidden, new16, hilo)
+    copies.attach(hidden, h16=(new16, hilo))
     return hidden, cell
 
 
@@ -340,10 +294,10 @@ def _convgru_forward_mixed(self, input_, prev_state, lean, hilo_out):
     hs = None if first else _half_source(prev_state)[0]
     if not first and _half_source(prev_state)[1]:
         raise hip.EssHipError('ConvGRU(mixed): a [hi | lo] hidden state feeds the decoder, not the next time step')
-    hb = None if first else getattr(prev_state, 'ess_f32c8', None)
+    hb = copies.of(prev_state).f32c8
     blocked = first or hb is not None
     afmt = hip.FMT_F32_C8 if blocked else hip.FMT_F32_NCHW
-    h32 = hb if blocked else _fp32(prev_state)
+    h32 = hb if blocked else copies.require_fp32(prev_state)
     uact = hip.GRU_U_F16
     s1 = hip.conv_spec(N, H, W, Cx, C1, 2 * hid, 3, 1, 1, epi=hip.EPI_GRU_UR, act=uact, hidden=hid, compute=hip.COMPUTE_F16)
     if hid % (s1.plan.cout_tile // 2):
@@ -366,13 +320,11 @@ def _convgru_forward_mixed(self, input_, prev_state, lean, hilo_out):
     if lean and blocked:
         nb = hip.f32_c8_empty(N, hid, H, W, dev)
         hip.conv_forward_h16(s2, xs, rh16, pw2, None, b2, aux0=h32, aux1=u, out=nb, out_h16=new16, out_fmt=hip.FMT_F32_C8, aux_fmt=afmt)
-        new_state = _c8_placeholder(N, hid, H, W, dev, None)
-        del new_state.ess_c8
-        new_state.ess_f32c8 = nb
+        new_state = copies.placeholder((N, hid, H, W), dev, f32c8=nb)
     else:
         new_state = torch.empty(N, hid, H, W, dtype=torch.float32, device=dev)
         hip.conv_forward_h16(s2, xs, rh16, pw2, None, b2, aux0=h32, aux1=u, out=new_state, out_h16=new16, out_fmt=hip.FMT_F32_NCHW, aux_fmt=afmt)
-    hip.attach_h16(new_state, new16, hilo)
+    copies.attach(new_state, h16=(new16, hilo))
     return new_state
 
 
@@ -447,8 +399,7 @@ class UpsampleConvLayer(nn.Module):
             hip.conv_forward(spec, up0, up1, packed_weight(spec, c.weight), scale, shift, out=None if copy is not None else out,
                              out_bf=copy, src_fmt=hip.FMT_BF16_C8 if c8 else hip.FMT_F32_NCHW)
         if copy is not None:
-            _attach_c8(out, copy)
-            _mark_fp32_unwritten(out)
+            copies.attach(out, c8=copy, unwritten=True)
         return out
 
     def _up(self, x, skip=None):
@@ -458,9 +409,9 @@ class UpsampleConvLayer(nn.Module):
         k = self.conv2d.kernel_size[0]
         if hip.get_compute() == 'bf16' and x.shape[1] % 8 == 0 and not (x.shape[3] & 1) and \
                 hip.c8_stageable(k, self.conv2d.stride[0], self.conv2d.padding[0]):
-            x8, s8 = _c8_of(x), (None if skip is None else _c8_of(skip))
+            x8, s8 = copies.of(x).c8, (None if skip is None else copies.of(skip).c8)
             if x8 is not None and skip is not None and s8 is None:
-                s8 = hip.to_bf16_c8(_fp32(skip))
+                s8 = hip.to_bf16_c8(copies.require_fp32(skip))
             if x8 is not None:
                 return hip.upsample_bilinear2x_add_c8_from_c8(x8, s8)
             return hip.upsample_bilinear2x_add_c8(_fp32_any(x), _fp32_any(skip))
@@ -519,7 +470,7 @@ class ConvLSTM(nn.Module):
         # (clone, detach, arithmetic) simply has no copy any more and takes the fp32 path.
         bf = spec.desc.compute == hip.COMPUTE_BF16 and (C % 8) == 0
         stage8 = bf and hip.c8_stageable(3, 1, 1)
-        x8, h8 = (_c8_of(input_), _c8_of(prev_hidden)) if stage8 else (None, None)
+        x8, h8 = (copies.of(input_).c8, copies.of(prev_hidden).c8) if stage8 else (None, None)
         new8 = hip.bf16_c8_empty(N, hid, H, W, input_.device) if bf else None
         skip_fp32 = lean and new8 is not None and stage8
         # a lean step's cell state travels to the next time step only: channel-blocked fp32 (FMT_F32_C8 -- the epilogue reads and
@@ -531,12 +482,12 @@ class ConvLSTM(nn.Module):
                              out=None if skip_fp32 else hidden, out2=cell, out_bf=new8, src_fmt=hip.FMT_BF16_C8, out_fmt=sfmt,
                              aux_fmt=cfmt)
         else:
-            hip.conv_forward(spec, _fp32(input_), _fp32(prev_hidden), packed_weight(spec, self.Gates.weight), None, b,
-                             aux0=prev_cell, out=None if skip_fp32 else hidden, out2=cell, out_bf=new8, out_fmt=sfmt, aux_fmt=cfmt)
+            hip.conv_forward(spec, copies.require_fp32(input_), copies.require_fp32(prev_hidden), packed_weight(spec, self.Gates.weight),
+                             None, b, aux0=prev_cell, out=None if skip_fp32 else hidden, out2=cell, out_bf=new8, out_fmt=sfmt, aux_fmt=cfmt)
         if new8 is not None:
-            _attach_c8(hidden, new8)
+            copies.attach(hidden, c8=new8)
         if skip_fp32:
-            _mark_fp32_unwritten(hidden)
+            copies.attach(hidden, unwritten=True)
         return hidden, cell
 
 
@@ -555,7 +506,7 @@ def _convlstm_first_step(self, input_, hidden, cell, lean):
     b = packed_rows(spec, self.Gates.bias)
     bf = spec.desc.compute == hip.COMPUTE_BF16 and (C % 8) == 0
     stage8 = bf and hip.c8_stageable(3, 1, 1)
-    x8 = _c8_of(input_) if stage8 else None
+    x8 = copies.of(input_).c8 if stage8 else None
     new8 = hip.bf16_c8_empty(N, hid, H, W, input_.device) if bf else None
     skip_fp32 = lean and new8 is not None and stage8
     cell, sfmt = _new_cell(N, hid, H, W, input_.device, skip_fp32)
@@ -563,12 +514,12 @@ def _convlstm_first_step(self, input_, hidden, cell, lean):
         hip.conv_forward(spec, x8, None, packed_weight(spec, wx), None, b, aux0=None,
                          out=None if skip_fp32 else hidden, out2=cell, out_bf=new8, src_fmt=hip.FMT_BF16_C8, out_fmt=sfmt)
     else:
-        hip.conv_forward(spec, _fp32(input_), None, packed_weight(spec, wx), None, b, aux0=None,
+        hip.conv_forward(spec, copies.require_fp32(input_), None, packed_weight(spec, wx), None, b, aux0=None,
                          out=None if skip_fp32 else hidden, out2=cell, out_bf=new8, out_fmt=sfmt)
     if new8 is not None:
-        _attach_c8(hidden, new8)
+        copies.attach(hidden, c8=new8)
     if skip_fp32:
-        _mark_fp32_unwritten(hidden)
+        copies.attach(hidden, unwritten=True)
     return hidden, cell
 
 
@@ -580,8 +531,8 @@ class ConvGRU(nn.Module):
     """Two fused kernels: (update, reset) gates -> (u, r*h); candidate -> h'.  Reference: submodules.py:233-273.
 
     bf16 arithmetic keeps the recurrent state in three forms, as the ConvLSTM does with (h, c): the BF16_C8 copy the gate /
-    candidate convolutions stage (`.ess_c8`), the fp32 values the epilogues blend with (`h' = h (1 - u) + o u` stays an fp32
-    recurrence: channel-blocked fp32 `.ess_f32c8` between lean time steps, plain NCHW planes otherwise), and -- unless the step is
+    candidate convolutions stage (`copies.of(h).c8`), the fp32 values the epilogues blend with (`h' = h (1 - u) + o u` stays an fp32
+    recurrence: channel-blocked fp32 `f32c8` between lean time steps, plain NCHW planes otherwise), and -- unless the step is
     lean -- the fp32 NCHW tensor the reference returns.  u travels between the two kernels as channel-blocked fp32, r*h as the
     BF16_C8 tensor the candidate convolution would round it to anyway; neither the concat nor an fp32 r*h exist in memory."""
 
@@ -629,15 +580,15 @@ class ConvGRU(nn.Module):
             wu, wr, wo = self.update_gate.weight, self.reset_gate.weight, self.out_gate.weight
         pw1, pw2 = packed_weight(s1, wu, wr), packed_weight(s2, wo)
         bf = s1.desc.compute == hip.COMPUTE_BF16 and (C % 8) == 0 and (hid % 8) == 0 and hip.c8_stageable(3, 1, 1)
-        x8 = _c8_of(input_) if bf else None
-        h8 = _c8_of(prev_state) if (bf and not first) else None
+        x8 = copies.of(input_).c8 if bf else None
+        h8 = copies.of(prev_state).c8 if (bf and not first) else None
         if x8 is not None and (first or h8 is not None):
             # ---- BF16_C8 path: x / h / r*h staged as 16-byte pixel vectors, fp32 state operands channel-blocked where they can be
-            hb = None if first else getattr(prev_state, 'ess_f32c8', None)  # channel-blocked fp32 h (left by a lean step)
+            hb = copies.of(prev_state).f32c8  # channel-blocked fp32 h (left by a lean step)
             if first or hb is not None:
                 h32, afmt = hb, hip.FMT_F32_C8
             else:
-                h32, afmt = _fp32(prev_state), hip.FMT_F32_NCHW
+                h32, afmt = copies.require_fp32(prev_state), hip.FMT_F32_NCHW
             if afmt == hip.FMT_F32_C8:
                 u = hip.f16_c8_raw_empty(N, hid, H, W, dev) if s1.desc.act == hip.GRU_U_F16 else hip.f32_c8_empty(N, hid, H, W, dev)
             else:
@@ -651,16 +602,15 @@ class ConvGRU(nn.Module):
                 nb = hip.f32_c8_empty(N, hid, H, W, dev)
                 hip.conv_forward(s2, x8, rh8, pw2, None, b2, aux0=h32, aux1=u, out=nb, out_bf=new8, src_fmt=hip.FMT_BF16_C8,
                                  out_fmt=hip.FMT_F32_C8, aux_fmt=afmt)
-                new_state.ess_f32c8 = nb
-                _mark_fp32_unwritten(new_state)
+                copies.attach(new_state, f32c8=nb, unwritten=True)
             else:
                 hip.conv_forward(s2, x8, rh8, pw2, None, b2, aux0=h32, aux1=u, out=new_state, out_bf=new8, src_fmt=hip.FMT_BF16_C8,
                                  out_fmt=hip.FMT_F32_NCHW, aux_fmt=afmt)
-            _attach_c8(new_state, new8)
+            copies.attach(new_state, c8=new8)
             return new_state
         # ---- fp32 NCHW sources (exact-fp32 arithmetic; or a state that went through user code and lost its copies)
-        x = _fp32(input_)
-        h = None if first else _fp32(prev_state)
+        x = copies.require_fp32(input_)
+        h = None if first else copies.require_fp32(prev_state)
         u = torch.empty(N, hid, H, W, dtype=torch.float32, device=dev)
         rh = None if first else torch.empty_like(u)
         hip.conv_forward(s1, x, h, pw1, None, b1, aux0=h, out=u, out2=rh)
@@ -668,7 +618,7 @@ class ConvGRU(nn.Module):
         new8 = hip.bf16_c8_empty(N, hid, H, W, dev) if bf else None
         hip.conv_forward(s2, x, rh, pw2, None, b2, aux0=h, aux1=u, out=new_state, out_bf=new8)
         if new8 is not None:
-            _attach_c8(new_state, new8)
+            copies.attach(new_state, c8=new8)
         return new_state
 
 
@@ -703,7 +653,7 @@ def _rcl_prev_has_c8(self, prev_state):
     """True when the recurrent block will take the BF16_C8 path for this step (zero state, or a state that still carries its copy)."""
     if prev_state is None:
         return True
-    return _c8_of(prev_state[0] if self.recurrent_block_type == 'convlstm' else prev_state) is not None
+    return copies.of(prev_state[0] if self.recurrent_block_type == 'convlstm' else prev_state).c8 is not None
 
 
 RecurrentConvLayer._prev_has_c8 = _rcl_prev_has_c8
@@ -750,7 +700,7 @@ class ResidualBlock(nn.Module):
         if bn and self.training:
             raise NotImplementedError('E2VID BatchNorm only exists in eval mode here; call .eval() on the encoder')
         fused = self.norm != 'IN'
-        x8 = _c8_of(x) if (c8_only and fused and hip.get_compute() == 'bf16' and C % 8 == 0 and hip.c8_stageable(3, 1, 1)) else None
+        x8 = copies.of(x).c8 if (c8_only and fused and hip.get_compute() == 'bf16' and C % 8 == 0 and hip.c8_stageable(3, 1, 1)) else None
         if x8 is not None:
             s1 = hip.conv_spec(N, H, W, C, 0, self.conv1.out_channels, 3, 1, 1, act=hip.ACT_RELU)
             s2 = hip.conv_spec(N, H, W, self.conv1.out_channels, 0, self.conv2.out_channels, 3, 1, 1, act=hip.ACT_RELU)
@@ -763,8 +713,7 @@ class ResidualBlock(nn.Module):
             hip.conv_forward(s2, o8, None, packed_weight(s2, self.conv2.weight), sc2, sh2, x8, out=out8, src_fmt=hip.FMT_BF16_C8,
                              out_fmt=hip.FMT_BF16_C8)
             out = torch.empty(N, self.conv2.out_channels, H, W, dtype=torch.float32, device=x.device)
-            _attach_c8(out, out8)
-            _mark_fp32_unwritten(out)
+            copies.attach(out, c8=out8, unwritten=True)
             return out
         s1 = hip.conv_spec(N, H, W, C, 0, self.conv1.out_channels, 3, 1, 1, act=hip.ACT_RELU if fused else hip.ACT_NONE)
         s2 = hip.conv_spec(N, H, W, self.conv1.out_channels, 0, self.conv2.out_channels, 3, 1, 1,
@@ -772,7 +721,7 @@ class ResidualBlock(nn.Module):
         sc1, sh1 = _fold(s1, self.conv1.bias, 'BN' if bn else None, getattr(self, 'bn1', None))
         sc2, sh2 = _fold(s2, self.conv2.bias, 'BN' if bn else None, getattr(self, 'bn2', None))
         o = torch.empty(N, self.conv1.out_channels, H, W, dtype=torch.float32, device=x.device)
-        x = _fp32(x)  # (an unwritten lean-state placeholder must not be read as fp32)
+        x = copies.require_fp32(x)  # (an unwritten lean-state placeholder must not be read as fp32)
         hip.conv_forward(s1, x, None, packed_weight(s1, self.conv1.weight), sc1, sh1, out=o)
         if not fused:
             o, _ = hip.instnorm_forward(o, None, 1, EPS)

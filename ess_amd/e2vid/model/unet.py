@@ -11,7 +11,7 @@ import os
 import torch
 import torch.nn as nn
 
-from ... import hip
+from ... import copies, hip
 from .submodules import ConvLayer, RecurrentConvLayer, ResidualBlock, TransposedConvLayer, UpsampleConvLayer
 
 _ACT = {'sigmoid': hip.ACT_SIGMOID, 'tanh': hip.ACT_TANH, 'relu': hip.ACT_RELU}
@@ -69,8 +69,7 @@ class BaseUNet(nn.Module):
         for resblock in self.resblocks:
             x = resblock(x, c8_only=True) if c8_chain else resblock(x)
         # ... and the last one too when the prediction layer can stage both of its sources (decoder output, head) from copies
-        from .submodules import _c8_of
-        pred_c8 = c8_chain and _c8_of(head) is not None and hip.c8_stageable(1, 1, 0) and self.base_num_channels % 8 == 0
+        pred_c8 = c8_chain and copies.of(head).c8 is not None and hip.c8_stageable(1, 1, 0) and self.base_num_channels % 8 == 0
         for i, decoder in enumerate(self.decoders):
             last = i == len(self.decoders) - 1
             x = self._skip_decode(decoder, x, blocks[self.num_encoders - i - 1], c8_only=c8_chain and (pred_c8 or not last))
@@ -137,14 +136,13 @@ class UNetRecurrent(BaseUNet):
         (S normalised slices stacked along the batch axis) -> (head copies, conv copies) as BF16_C8 tensors [S*B, ...], or None when
         the lean BF16_C8 path is not available (exact-fp32 arithmetic, diagnostic switches).  forward(..., prefix=(head_t, conv_t))
         then starts at the first recurrent block.  Two launches for S slices instead of 2 S."""
-        from .submodules import _c8_of
         ok = hip.get_compute() == 'bf16' and not hip.mixed() and hip.c8_stageable(3, 1, 1) and hip.c8_stageable(5, 2, 2) and \
             self.encoder_output_sizes[0] % 8 == 0 and self.base_num_channels % 8 == 0
         if not ok:
             return None
         h = self.head(x_all, want_c8=True, c8_only=True)
         x0 = self.encoders[0].conv(h, want_c8=True, c8_only=True)
-        return _c8_of(h), _c8_of(x0)
+        return copies.of(h).c8, copies.of(x0).c8
 
     def forward(self, x, prev_states, encoder_only=False, lean=False, prefix=None, lean_state=False):
         """lean (needs encoder_only; effective in bf16 arithmetic): the step's only purpose is the
@@ -165,7 +163,7 @@ class UNetRecurrent(BaseUNet):
         c8_ok = hip.get_compute() == 'bf16' and hip.c8_stageable(3, 1, 1) and hip.c8_stageable(5, 2, 2)
         lean = lean and c8_ok
         # (lean_state on a full step: the tail must be the all-BF16_C8 chain -- upsample-conv decoders, fused norms; a module that
-        # would read the fp32 hidden state refuses the unwritten placeholder loudly: submodules._fp32)
+        # would read the fp32 hidden state refuses the unwritten placeholder loudly: copies.require_fp32)
         # ... and the upsampling passes take their BF16_C8 form for even plane widths only (an odd-width plane is upsampled from
         # fp32 values: those of a lean state would be the bf16-rounded copy's -- close, not bit-identical)
         wid = None if x is None else x.shape[3]
@@ -175,11 +173,10 @@ class UNetRecurrent(BaseUNet):
         if prefix is not None:  # (lean steps only: head and first conv were computed for all slices at once, forward_prefix)
             if not lean:
                 raise ValueError('prefix needs a lean step')
-            from .submodules import _c8_placeholder
             h8, c8 = prefix
             N, H, W = h8.shape[0], h8.shape[2], h8.shape[3]
-            x = _c8_placeholder(N, self.base_num_channels, H, W, h8.device, h8)
-            x_conv0 = _c8_placeholder(N, self.encoder_output_sizes[0], c8.shape[2], c8.shape[3], c8.device, c8)
+            x = copies.placeholder((N, self.base_num_channels, H, W), h8.device, c8=h8)
+            x_conv0 = copies.placeholder((N, self.encoder_output_sizes[0], c8.shape[2], c8.shape[3]), c8.device, c8=c8)
         else:
             x = self.head(x, want_c8=True, c8_only=lean)  # the first encoder conv stages from the BF16_C8 copy (bf16 arithmetic)
         head = x
@@ -206,7 +203,6 @@ def _unet_recurrent_forward_mixed(self, x, prev_states, encoder_only, lean, lean
     blocks, upsample-conv decoders, prediction layer: reference unet.py:165-181) on the bf16 kernels from BF16_C8 copies of the hidden
     states.  lean: the step only advances the state; lean_state: its hidden states need no fp32 form (then the last step's copies of h'
     -- the event latents -- leave as [hi | lo] half pairs)."""
-    from .submodules import _c8_of, _attach_c8
     import os
     # WHERE the [hi | lo] pairs are used: by default at the DEEPEST level only -- the convolution feeding its ConvLSTM and, on the last
     # step, its h' (the 1/8-resolution latent).  tools/hybrid_rounding_ablation.py (levels / latents sections): on the trained fixture
@@ -240,9 +236,9 @@ def _unet_recurrent_forward_mixed(self, x, prev_states, encoder_only, lean, lean
     if encoder_only:
         return None, states, latent
     for b in blocks:  # the tail stages BF16_C8 copies
-        h = hip.h16_of(b)
-        if h is not None and _c8_of(b) is None:
-            _attach_c8(b, hip.f16_c8_to_bf16_c8(h[0], hilo=h[1]))
+        h = copies.of(b).h16
+        if h is not None and copies.of(b).c8 is None:
+            copies.attach(b, c8=hip.f16_c8_to_bf16_c8(h[0], hilo=h[1]))
     return self._tail(x, blocks, head), states, latent
 
 

@@ -21,9 +21,8 @@ data handling, outside the hot path: `iter_windows_fixed_size` covers the in-mem
 """
 import torch
 
-from .. import hip
+from .. import copies, hip
 from .image_reconstructor import ImageReconstructor
-from .model.submodules import _attach_c8, _c8_of, _mark_fp32_unwritten
 
 
 def events_to_voxel_grid_device(events, num_bins, width, height, device):
@@ -67,21 +66,17 @@ class GraphedWindowState:
         out = []
         for s in states:
             h, c = (s[0], s[1]) if isinstance(s, (tuple, list)) else (s, None)
-            h16 = hip.h16_of(h)
-            out.append(({'h': None if getattr(h, 'ess_fp32_unwritten', False) else h, 'c8': _c8_of(h), 'h16': None if h16 is None else h16[0],
-                         'f32c8': getattr(h, 'ess_f32c8', None), 'c': c}, bool(h16 is not None and h16[1]), tuple(h.shape)))
+            r = copies.of(h)
+            h16, hilo = r.h16 or (None, False)
+            out.append(({'h': None if r.unwritten else h, 'c8': r.c8, 'h16': h16, 'f32c8': r.f32c8, 'c': c}, hilo, tuple(h.shape)))
         return out
 
     @staticmethod
     def _attach(st):
-        """(re-)tie a static level's copies to its hidden-state tensor: the attachments follow the tensor's version"""
+        """(re-)tie a static level's copies to its hidden-state tensor: the record follows the tensor's version"""
         parts, hilo, _, sh = st
-        if parts['c8'] is not None:
-            _attach_c8(sh, parts['c8'])
-        if parts['h16'] is not None:
-            hip.attach_h16(sh, parts['h16'], hilo)
-        if parts['f32c8'] is not None:
-            sh.ess_f32c8 = parts['f32c8']
+        found = {'c8': parts['c8'], 'h16': None if parts['h16'] is None else (parts['h16'], hilo), 'f32c8': parts['f32c8']}
+        copies.attach(sh, **{k: v for k, v in found.items() if v is not None})
 
     def _adopt_state(self, states):
         """Copy a step's output state into the static buffers (allocated on first use) and make THEM the carried state."""
@@ -92,8 +87,7 @@ class GraphedWindowState:
                 sp = {k: None if t is None else torch.empty_like(t) for k, t in parts.items()}
                 sh = sp['h']
                 if sh is None:  # (a lean state: the fp32 hidden tensor is a placeholder without memory, the copies are the state)
-                    sh = torch.empty((), dtype=torch.float32, device=self.device).expand(shape)
-                    _mark_fp32_unwritten(sh)
+                    sh = copies.placeholder(shape, self.device)
                 self._static.append((sp, hilo, shape, sh))
         carried = []
         for st, (parts, hilo, shape) in zip(self._static, new):

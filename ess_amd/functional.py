@@ -7,7 +7,7 @@ import weakref
 
 import torch
 
-from . import hip
+from . import copies, hip
 
 # When True (set by ess_amd.utils.radam.RAdam), the weight-gradient kernels add straight into an existing leaf `.grad`
 # (a view of the optimiser's flat gradient buffer) instead of materialising dW and letting AccumulateGrad add it.
@@ -263,19 +263,14 @@ def mixed():
 
 def half_of(x):
     """(F16_C8 tensor, hilo) holding the values of the BF16_C8 activation `x` for a half-operand convolution: the copy its producer
-    left (`.ess_h16`: 11 or, [hi | lo], ~22 significant bits), else the BF16_C8 values themselves converted (exact)."""
-    c = hip.h16_of(x)
-    if c is not None:
-        return c
-    return hip.bf16_c8_to_f16_c8(x.detach().contiguous()), False
+    left (`copies.of(x).h16`: 11 or, [hi | lo], ~22 significant bits), else the BF16_C8 values themselves converted (exact)."""
+    return copies.of(x).h16 or (hip.bf16_c8_to_f16_c8(x.detach().contiguous()), False)
 
 
 def _hilo_placeholder(N, C, H, W, device, buf):
     """The autograd-visible tensor of a [hi | lo] pre-norm output: shape and dtype of the BF16_C8 tensor its gradient has, no memory
-    behind it (stride 0); the half pair travels as `.ess_hilo` -- only the norm kernels read it."""
-    t = torch.empty((), dtype=torch.bfloat16, device=device).expand(N, C // 8, H, W, 8)
-    t.ess_hilo = buf
-    return t
+    behind it (stride 0); the half pair travels as the record's `pair` -- only the norm kernels read it."""
+    return copies.attach(torch.empty((), dtype=torch.bfloat16, device=device).expand(N, C // 8, H, W, 8), pair=buf)
 
 
 def _empty_act(N, C, H, W, device, c8):
@@ -325,7 +320,7 @@ class FromC8Fn(torch.autograd.Function):
 
 def as_c8(x, want_hilo=False):
     """`x` as a BF16_C8 tensor: itself, the staging copy its producer left next to an fp32 tensor (frozen encoder latents:
-    `.ess_c8`, valid while the tensor is unmodified and needs no gradient), or a converted copy (autograd-aware)."""
+    `copies.of(x).c8`, read only for a tensor that needs no gradient), or a converted copy (autograd-aware)."""
     if hip.is_c8(x):
         return x
     if x.shape[1] % 8:
@@ -334,29 +329,27 @@ def as_c8(x, want_hilo=False):
         # mixed configuration, an event latent (fp32 NCHW, possibly an unwritten placeholder carrying only its half copy): the
         # BF16_C8 tensor the backward / skip / loss consumers read, with the [hi | lo] half pair the forward convolutions read
         # want_hilo: the consumer's operand should be a [hi | lo] pair (the 1/8-resolution latent: channel means far above the spread)
-        h = hip.h16_of(x)
+        r = copies.of(x)
+        h = r.h16
         want_hilo = bool(want_hilo) or (h is not None and h[1])  # (a producer's [hi | lo] copy serves every consumer)
-        cached = getattr(x, 'ess_mixed_c8', None)
-        if cached is not None and cached[1] == (x._version, want_hilo):
-            return cached[0]
-        unwritten = getattr(x, 'ess_fp32_unwritten', False)
-        fresh = h is None or (want_hilo and not h[1] and not unwritten)
+        if r.mixed is not None and r.mixed[1] == want_hilo:
+            return r.mixed[0]
+        fresh = h is None or (want_hilo and not h[1] and not r.unwritten)
         if fresh:
-            if unwritten:
+            if r.unwritten:
                 raise hip.EssHipError('as_c8(mixed): the tensor has neither fp32 values nor a half copy')
-            h = (hip.to_f16_c8(x.contiguous(), hilo=bool(want_hilo)), bool(want_hilo))
-        c8 = getattr(x, 'ess_c8', None)
-        if c8 is not None and c8[1] == x._version and not fresh:
-            c8t = c8[0]  # (the BF16_C8 copy the encoder's reconstruction tail already made of this very half copy: no second conversion)
+            h = (hip.to_f16_c8(x.contiguous(), hilo=want_hilo), want_hilo)
+        if r.c8 is not None and not fresh:
+            c8t = r.c8  # (the BF16_C8 copy the encoder's reconstruction tail already made of this very half copy: no second conversion)
         else:
             c8t = hip.f16_c8_to_bf16_c8(h[0], hilo=h[1])
-        hip.attach_h16(c8t, h[0], h[1])
-        x.ess_mixed_c8 = (c8t, (x._version, bool(want_hilo)))
+        copies.attach(c8t, h16=h)
+        copies.attach(x, mixed=(c8t, want_hilo))
         return c8t
-    c8 = getattr(x, 'ess_c8', None)
-    if c8 is not None and c8[1] == x._version and not x.requires_grad:
-        return c8[0]
-    if getattr(x, 'ess_fp32_unwritten', False):
+    r = copies.of(x)
+    if r.c8 is not None and not x.requires_grad:
+        return r.c8
+    if r.unwritten:
         raise hip.EssHipError('as_c8: the tensor was produced as a staging copy only and the copy is gone (modified / detached without '
                               'detach_keep_c8): its fp32 values were never written')
     return ToC8Fn.apply(x)
@@ -368,16 +361,7 @@ def from_c8(x, C=None):
 
 def detach_keep_c8(x):
     """x.detach() that does not lose the producer's BF16_C8 staging copy (python attributes do not survive detach())."""
-    d = x.detach()
-    c8 = getattr(x, 'ess_c8', None)
-    if c8 is not None and c8[1] == x._version:
-        d.ess_c8 = (c8[0], d._version)
-    if getattr(x, 'ess_fp32_unwritten', False):
-        d.ess_fp32_unwritten = True
-    h = getattr(x, 'ess_h16', None)
-    if h is not None and h[1] == x._version:
-        d.ess_h16 = (h[0], d._version, h[2])
-    return d
+    return copies.carry(x.detach(), x, 'c8', 'h16', 'unwritten')
 
 
 class ForkFn(torch.autograd.Function):
@@ -390,12 +374,7 @@ class ForkFn(torch.autograd.Function):
         # unused aliases (e.g. the image task backward consumes pred[1] only) must arrive as None in backward, not as
         # materialised zero tensors: a zero fill plus an add pass per unused fork otherwise
         ctx.set_materialize_grads(False)
-        outs = tuple(x.detach() for _ in range(n))
-        h = hip.h16_of(x)
-        if h is not None:  # (mixed configuration: the aliases keep the producer's half copy)
-            for o in outs:
-                hip.attach_h16(o, h[0], h[1])
-        return outs
+        return tuple(copies.carry(x.detach(), x, 'h16') for _ in range(n))  # (mixed configuration: the aliases keep the producer's half copy)
 
     @staticmethod
     def backward(ctx, *gs):
@@ -632,16 +611,16 @@ class InstanceNormFn(torch.autograd.Function):
         x_f16 = bool(x_f16) or hip.is_f16_c8(x)
         if _blocked(x) and hip.mixed():
             # mixed configuration: the result leaves twice -- BF16_C8 (the tensor autograd sees: weight gradient, skip, losses) and
-            # F16_C8 (`.ess_h16`: what the next half-operand convolution reads); a [hi | lo] pre-norm input comes as x.ess_hilo
-            buf = getattr(x, 'ess_hilo', None)
+            # F16_C8 (the record's `h16`: what the next half-operand convolution reads); a [hi | lo] pre-norm input comes as x's `pair`
+            buf = copies.of(x).pair
             xin, x_fmt = (buf, 2) if buf is not None else (x, 1 if x_f16 else 0)
             res = residual
             if residual is not None:
-                h = hip.h16_of(residual)
+                h = copies.of(residual).h16
                 if h is not None:  # the skip operand's half values (a [hi | lo] latent: the kernel adds its hi parts)
                     res = h[0]
             y, y16, stats = hip.instnorm_forward_c8_mixed(xin, _channels(x), res, relu, eps, x_fmt)
-            hip.attach_h16(y, y16, False)
+            copies.attach(y, h16=(y16, False))
             ctx.relu, ctx.x_f16 = relu, x_fmt
             ctx.save_for_backward(xin, stats)
             return y
@@ -824,6 +803,6 @@ def l1_loss(a, b, weight=1.0, channels=None):
         raise hip.EssHipError('l1_loss: BF16_C8 operands need channels= (the logical channel count: the mean runs over the real '
                               'elements, and the tensors do not say how much of their last block is padding)')
     for t in (a, b):  # (a lean latent whose fp32 values were never written must have gone through as_c8 above)
-        if getattr(t, 'ess_fp32_unwritten', False):
+        if copies.of(t).unwritten:
             raise hip.EssHipError('l1_loss: the tensor exists as a staging copy only (lean recurrent state); its fp32 values were never written')
     return L1Fn.apply(a.contiguous(), b.contiguous(), weight, channels)

@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from .. import functional as Fn
-from .. import hip
+from .. import copies, hip
 from .submodules import InterpolationLayer
 
 
@@ -67,9 +67,8 @@ class INSResBlock(nn.Module):
         if first and pre == Fn.PRE_NORM and Fn.mixed() and c1.out_channels % 64 == 0:
             pre1 = Fn.PRE_NORM_HILO
         y, skip = Fn.conv2d_passthrough(x, c1.weight, c1.bias, c1.stride[0], 1, out_c8=pre1, half=True)
-        hx = hip.h16_of(x)
-        if hx is not None and hip.h16_of(skip) is None:  # (an input handed through an autograd.Function comes back as a new alias: keep its half copy)
-            hip.attach_h16(skip, hx[0], hx[1])
+        if copies.of(skip).h16 is None:  # (an input handed through an autograd.Function comes back as a new alias: keep its half copy)
+            copies.carry(skip, x, 'h16')
         y = Fn.instance_norm(y, None, True, self.model[1].eps, x_f16=pre == Fn.PRE_NORM)
         y = Fn.conv2d(y, c2.weight, c2.bias, 1, 1, out_c8=pre, half=True)
         return Fn.instance_norm(y, skip, False, self.model[4].eps, x_f16=pre == Fn.PRE_NORM)  # IN(.) + residual in one pass

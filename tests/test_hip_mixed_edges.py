@@ -219,7 +219,7 @@ def test_conv2dfn_hilo_request_on_partial_channel_tiles(H):
     give one: C_out = 320 behind a doubled 256-channel source takes 128-channel tiles (512 input channels), and the plan refuses a pair
     output on a half-filled tile.  The function writes one half copy instead -- within its rounding of the fp64 convolution of hi + lo --
     and still writes the pair where the tiles are whole (C_out = 256)."""
-    from ess_amd import functional as Fn
+    from ess_amd import copies, functional as Fn
     N, C, Hh, W = 1, 256, 9, 19
     g = torch.Generator().manual_seed(320)
     x = torch.randn(N, C, Hh, W, generator=g) + 1.5
@@ -235,11 +235,11 @@ def test_conv2dfn_hilo_request_on_partial_channel_tiles(H):
             torch.cuda.synchronize()
             ref = F.conv2d(unblock_hilo(pair, C), hfr(w).double(), b.double(), 1, 1)
             if Cout == 320:
-                assert H.is_f16_c8(out) and getattr(out, 'ess_hilo', None) is None
+                assert H.is_f16_c8(out) and copies.of(out).pair is None
                 got = H.f16_c8_to_float(out, Cout).cpu().double()
                 tol = 2 ** -11
             else:
-                got = unblock_hilo(out.ess_hilo, Cout)
+                got = unblock_hilo(copies.of(out).pair, Cout)
                 tol = 2 ** -20
             err = ((got - ref).abs() / ref.abs().clamp(min=1.0)).max().item()
             assert err <= tol * 1.5 + 3e-6, (Cout, err)

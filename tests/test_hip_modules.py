@@ -854,7 +854,7 @@ def test_sequence_call_matches_per_slice_loop(shape):
             assert all(torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) for a, b in zip(st2, st1))
             # final_lean (the trainers): the last step's recurrent blocks in their lean form too -- image and latents bit-identical
             # (hidden states as BF16_C8 copies: the values every consumer stages anyway), with and without the image tail
-            from ess_amd.e2vid.model.submodules import _c8_of
+            from ess_amd import copies
             for need_image in (True, False):
                 rec.last_states_for_each_channel = {'grayscale': None}
                 img1n, _, lat1n = rec.update_reconstruction_sequence(ev, T, need_image=need_image)
@@ -864,11 +864,11 @@ def test_sequence_call_matches_per_slice_loop(shape):
                     assert torch.equal(img3, img1n)
                 assert torch.equal(lat3[1], lat1n[1])
                 for k in (2, 4, 8):
-                    ran_lean = getattr(lat3[k], 'ess_fp32_unwritten', False)
+                    ran_lean = copies.of(lat3[k]).unwritten
                     if mode == 'bf16' and H % 8 == 0 and ((W >> 3) % 2 == 0 or not need_image):
                         assert ran_lean, k  # the lean form did run (padded / odd-width planes may or may not take it)
                     if ran_lean:
-                        assert torch.equal(_c8_of(lat3[k]).view(torch.int16), _c8_of(lat1n[k]).view(torch.int16)), k
+                        assert torch.equal(copies.of(lat3[k]).c8.view(torch.int16), copies.of(lat1n[k]).c8.view(torch.int16)), k
                     else:
                         assert torch.equal(lat3[k], lat1n[k]), k
         finally:

@@ -256,14 +256,14 @@ def test_replay_equals_eager_on_the_schedule(rtype, mode):
 # ---------------------------------------------------------------------------------------------- 4. against the single-stream driver
 def _latent_values(hip, lat):
     """fp32 values of the latents {1, 2, 4, 8} handed to predict, whatever form the configuration leaves them in"""
-    from ess_amd.e2vid.model.submodules import _c8_of
+    from ess_amd import copies
     out = []
     for k in (1, 2, 4, 8):
         t = lat[k]
-        if not getattr(t, 'ess_fp32_unwritten', False):
+        if not copies.of(t).unwritten:
             out.append(t.float())
             continue
-        c8, h16 = _c8_of(t), hip.h16_of(t)
+        c8, h16 = copies.of(t).c8, copies.of(t).h16
         if c8 is not None:
             out.append(c8.float())
         else:

@@ -21,7 +21,7 @@ def main():
     ap.add_argument('--layers', action='store_true')
     a = ap.parse_args()
     from oracle import ess_oracle as O
-    from ess_amd import hip
+    from ess_amd import copies, hip
     from ess_amd.e2vid.model.model import E2VIDRecurrent
     from ess_amd.e2vid.model.submodules import set_s2d_mode
     from ess_amd.e2vid.options.inference_options import default_options
@@ -48,12 +48,13 @@ def main():
     def forms(t):
         out = {}
         if torch.is_tensor(t):
-            if not getattr(t, 'ess_fp32_unwritten', False) and any(t.stride()):
+            r = copies.of(t)
+            if not r.unwritten and any(t.stride()):
                 out['self'] = t
-            for name in ('ess_c8', 'ess_h16'):
-                v = getattr(t, name, None)
-                if v is not None:
-                    out[name] = v[0]
+            if r.c8 is not None:
+                out['c8'] = r.c8
+            if r.h16 is not None:
+                out['h16'] = r.h16[0]
         return out
 
     def run(n, graph, spy=None):
