@@ -108,7 +108,7 @@ class ImageReconstructor:
             for i in range(T):
                 last = i == T - 1
                 if unet is not None:
-                    unet.steps_left = T - 1 - i  # ('mixed': where the deepest level's operand pair is used -- unet._forward_mixed)
+                    unet.steps_left = T - 1 - i  # ('mixed': where the deepest level's operand pair is used -- UNetRecurrent.forward)
                 if slices is not None:
                     ev = slices[i]
                 else:

@@ -8,6 +8,7 @@ children are parameter containers only: every forward is a fused libess_hip.so l
 under no_grad in ESS (training/ess_trainer.py:52-54,277-280), so these modules are inference-only:
 asking autograd to differentiate through them raises.
 """
+import collections
 import os
 
 import torch
@@ -85,7 +86,7 @@ def set_s2d_mode(mode):
     return prev
 
 
-def _s2d_spec(N, k, stride, pad, cin, cout, H, W, act):
+def _s2d_spec(N, k, stride, pad, cin, cout, H, W, act, compute=None):
     """The ESS_SRC_S2D spec of a 5x5 / stride-2 / pad-2 convolution where that form exists AND is the faster one for this launch
     (hip.s2d_preferred: it needs a launch that fills the chip), else None.  Switch ESS_CONV5_S2D: 0 = never, 2 = wherever it exists.
     The two forms add the same products in different orders: the choice depends on the batch size and on the device's compute-unit
@@ -94,8 +95,71 @@ def _s2d_spec(N, k, stride, pad, cin, cout, H, W, act):
     mode = _S2D_MODE
     if (k, stride, pad) != (5, 2, 2) or cin % 32 or cout % 64 or H % 2 or W % 2 or mode == '0':
         return None
-    s2 = hip.conv_spec(N, H // 2, W // 2, 4 * cin, 0, cout, 3, 1, 1, mode0=hip.SRC_S2D, act=act)
+    s2 = hip.conv_spec(N, H // 2, W // 2, 4 * cin, 0, cout, 3, 1, 1, mode0=hip.SRC_S2D, act=act, compute=compute)
     return s2 if (mode == '2' or hip.s2d_preferred(s2)) else None
+
+
+# ---- The 16-bit operand kind of an encoder step.  The recurrent part of the frozen encoder -- head, the stride-2 convolutions, the
+# ConvLSTM / ConvGRU gates -- contracts either bf16 operands (configurations 'bf16', and 'fp32' / 'bf16x3', which are this kind with the
+# copies switched off) or IEEE-half operands (configuration 'mixed', ESS_COMPUTE_F16).  Either way an activation travels between the
+# launches as a channel-blocked 16-bit copy in its record (copies.py): field `c8`, or field `h16` = (tensor, hilo).  Only the half kind
+# writes [hi | lo] pairs: the convolution in front of a recurrent block (its post-ReLU values carry means far above their spread:
+# rounding THEM to 11 bits was the largest term of the encoder's error, tools/hybrid_rounding_ablation.py) and the last time step's
+# h' -- the event latents.  A pair enters a convolution as 2 C channels against a weight whose input columns are repeated.
+# Whoever STARTS a step chooses the kind (operand_kind) and hands it down; ConvLayer defaults to bf16 -- the tail that only feeds the
+# reconstruction runs on the bf16 kernels in every configuration.
+Kind = collections.namedtuple('Kind', 'compute field fmt pairs')  # (conv_spec's compute, the record field, the source format, pairs?)
+BF16 = Kind(None, 'c8', hip.FMT_BF16_C8, False)
+HALF = Kind(hip.COMPUTE_F16, 'h16', hip.FMT_F16_C8, True)
+
+
+def operand_kind():
+    return HALF if hip.mixed() else BF16
+
+
+def _copies_on(k, *channels):
+    """Does a launch of kind k read / write 16-bit copies?  half: always; bf16: in bf16 arithmetic, over whole 8-channel blocks."""
+    return k is HALF or (hip.get_compute() == 'bf16' and not any(c % 8 for c in channels))
+
+
+def _source(k, t, staged=True):
+    """Source of kind k -> (tensor, hilo, format): the producer's copy; without one the half kind converts the fp32 values, the bf16
+    kind (or `staged` off: copies switched off, a geometry that cannot stage BF16_C8) stages the fp32 tensor itself."""
+    r = copies.of(t)
+    if k is HALF:
+        s, hilo = r.h16 or (hip.to_f16_c8(copies.require_fp32(t).contiguous()), False)
+        return s, hilo, k.fmt
+    if staged and r.c8 is not None:
+        return r.c8, False, k.fmt
+    return copies.require_fp32(t), False, hip.FMT_F32_NCHW
+
+
+def _copy_empty(k, N, C, H, W, device, hilo=False):
+    return hip.f16_blocks_empty(N, C, H, W, device, hilo=hilo) if k is HALF else hip.bf16_c8_empty(N, C, H, W, device)
+
+
+def _attach_copy(k, t, copy, hilo=False):
+    return copies.attach(t, **{k.field: (copy, hilo) if k is HALF else copy})
+
+
+def _fp32_out(shape, device, skip):
+    """The fp32 tensor of an output -- with `skip` one that exists as copies only (copies.require_fp32 refuses its values)."""
+    return copies.placeholder(shape, device) if skip else torch.empty(shape, dtype=torch.float32, device=device)
+
+
+def _gate_weight(w, C, hid, x_pair, h_pair, first):
+    """The weight of a convolution over cat(x [C channels], h [hid channels]) for the operands as they arrive: the x columns alone on the
+    first step of a sequence (h = 0 adds exact zeros: half the MFMA work, no zero state tensors), repeated for a [hi | lo] source."""
+    cols = [(0, C)] * (2 if x_pair else 1) + ([] if first else [(C, C + hid)] * (2 if h_pair else 1))
+    return w if cols == [(0, C), (C, C + hid)] else columns(w, cols)
+
+
+def _launch(k, spec, src0, src1, packed_w, scale, shift, residual=None, copy=None, src_fmt=hip.FMT_F32_NCHW, **kw):
+    """Launch of kind k (through the module attributes: bench.py times them in the step); copy: the output's 16-bit copy."""
+    if k is HALF:
+        return hip.conv_forward_h16(spec, src0, src1, packed_w, scale, shift, residual, out_h16=copy,
+                                    src_fp32=src_fmt == hip.FMT_F32_NCHW, **kw)
+    return hip.conv_forward(spec, src0, src1, packed_w, scale, shift, residual, out_bf=copy, src_fmt=src_fmt, **kw)
 
 
 class ConvLayer(nn.Module):
@@ -117,215 +181,65 @@ class ConvLayer(nn.Module):
         w = self.conv2d.weight
         return self.forward(x, x1=skip, weight=columns(w, [(0, w.shape[1])] * 2))
 
-    def forward(self, x, x1=None, residual=None, want_c8=False, c8_only=False, weight=None):
-        """x1: optional second source, channel-concatenated on the fly.
-        want_c8: (bf16 arithmetic only) also emit the output as a BF16_C8 staging copy, attached to the returned
-        tensor (`copies.of(out).c8`), for a following 3x3 / 5x5 convolution to stage from (see ConvLSTM.forward).
-        c8_only: (with want_c8, bf16 arithmetic) do not write the fp32 output at all -- for an activation whose only
-        consumer stages from the copy; the returned tensor is a placeholder that refuses fp32 use (`copies.require_fp32`)."""
+    def forward(self, x, x1=None, residual=None, want_c8=False, c8_only=False, weight=None, hilo_out=False, kind=BF16):
+        """x1: optional second source, channel-concatenated on the fly (bf16 kind).
+        want_c8: also emit the output as a 16-bit staging copy of `kind` (bf16 kind: in bf16 arithmetic only), attached to the returned
+        tensor (`copies.of(out).c8` / `.h16`), for a following 3x3 / 5x5 convolution to stage from (see ConvLSTM.forward).
+        c8_only: (with want_c8) do not write the fp32 output at all -- for an activation whose only consumer stages from the copy;
+        the returned tensor is a placeholder that refuses fp32 use (`copies.require_fp32`).
+        hilo_out: (half kind, c8_only) the copy as a [hi | lo] pair.
+        The half kind has two forms: the 5x5 head over the fp32 voxel grid (rounded to half inside the kernel), whose fp32 output
+        exists unless c8_only, and an encoder convolution from its source's half copy, copy-only."""
         _inference_only(x, x1)
         _check_eval(self, self.norm)
-        c = self.conv2d
+        k, c = kind, self.conv2d
         wt = c.weight if weight is None else weight  # (forward_of_sum: the weight repeated for the two sources)
+        ks, st, p, Cout, act = c.kernel_size[0], c.stride[0], c.padding[0], c.out_channels, _ACT[self.activation]
         N, C0, H, W = x.shape
         C1 = 0 if x1 is None else x1.shape[1]
-        spec = hip.conv_spec(N, H, W, C0, C1, c.out_channels, c.kernel_size[0], c.stride[0], c.padding[0],
-                             act=_ACT[self.activation])
-        scale, shift = _fold(spec, c.bias, self.norm, getattr(self, 'norm_layer', None))
-        out = torch.empty(N, c.out_channels, spec.H_out, spec.W_out, dtype=torch.float32, device=x.device)
-        c8 = None
-        bf = spec.desc.compute == hip.COMPUTE_BF16
-        if want_c8 and bf:
-            c8 = hip.bf16_c8_empty(N, c.out_channels, spec.H_out, spec.W_out, x.device)
-        k = c.kernel_size[0]
-        x8 = copies.of(x).c8 if bf and x1 is None and hip.c8_stageable(k, c.stride[0], c.padding[0]) else None
-        if bf and x1 is not None and (C0 % 8) == 0 and hip.c8_stageable(k, c.stride[0], c.padding[0]):
+        Ho, Wo = (H + 2 * p - ks) // st + 1, (W + 2 * p - ks) // st + 1
+        on = _copies_on(k)
+        stage = on and hip.c8_stageable(ks, st, p)
+        r, src1 = copies.of(x), None
+        if k is HALF and r.h16 is None and (ks, st) == (5, 1) and C0 <= 5 and not r.unwritten:
+            src, hl, fmt = x.contiguous(), False, hip.FMT_F32_NCHW  # (the head: the image itself)
+        elif x1 is None:
+            src, hl, fmt = _source(k, x, stage)  # the producer's copy: bit-identical operands, cheaper loads
+        else:
             # both concat sources from their producers' BF16_C8 copies (the prediction layer over decoder output + head: half the
             # bytes of the two fp32 tensors, and the decoder output need not exist in fp32 at all); bit-identical operands
-            a8, b8 = copies.of(x).c8, copies.of(x1).c8
+            a8, b8 = (r.c8, copies.of(x1).c8) if stage and C0 % 8 == 0 else (None, None)
             if a8 is not None and b8 is not None:
-                hip.conv_forward(spec, a8, b8, packed_weight(spec, wt), scale, shift, residual, out=out, src_fmt=hip.FMT_BF16_C8)
-                return out
-        skip_fp32 = c8_only and c8 is not None
-        # copy-only outputs without a residual leave through the BF16_C8-OUTPUT epilogue (16-byte stores, 32-bit offsets) instead of
-        # the fp32 epilogue's optional copy (8-byte stores): the same values (acc * scale + shift, ReLU, round to nearest even)
-        as_out = skip_fp32 and residual is None and self.activation in (None, 'relu')
-        if x8 is not None:  # stage from the producer's BF16_C8 copy (bit-identical, cheaper loads)
-            s2 = _s2d_spec(N, k, c.stride[0], c.padding[0], C0, c.out_channels, H, W, _ACT[self.activation]) if as_out else None
-            if s2 is not None:
-                # 5x5 / stride 2 (the three downsampling convolutions of the frozen encoder, reference submodules.py:176-186) as a 3x3
-                # over the space-to-depth view of the BF16_C8 source, on the wide-tile 3x3 kernel (ESS_SRC_S2D: 16-channel chunks, the
-                # 25 real taps only) instead of the tap-paired 5x5 kernel; the same products, summed in a different order
-                sc2, sh2 = _fold(s2, c.bias, self.norm, getattr(self, 'norm_layer', None))
-                hip.conv_forward(s2, x8, None, packed_weight(s2, wt, kind=hip.W_CONV5_S2D), sc2, sh2, None, out=c8,
-                                 src_fmt=hip.FMT_BF16_C8, out_fmt=hip.FMT_BF16_C8)
-            elif as_out:
-                hip.conv_forward(spec, x8, None, packed_weight(spec, wt), scale, shift, None, out=c8, src_fmt=hip.FMT_BF16_C8,
-                                 out_fmt=hip.FMT_BF16_C8)
+                src, src1, hl, fmt = a8, b8, False, k.fmt
             else:
-                hip.conv_forward(spec, x8, None, packed_weight(spec, wt), scale, shift, residual,
-                                 out=None if skip_fp32 else out, out_bf=c8, src_fmt=hip.FMT_BF16_C8)
-        elif as_out:
-            hip.conv_forward(spec, copies.require_fp32(x), None if x1 is None else copies.require_fp32(x1), packed_weight(spec, wt),
-                             scale, shift, None, out=c8, out_fmt=hip.FMT_BF16_C8)
-        else:
-            hip.conv_forward(spec, copies.require_fp32(x), None if x1 is None else copies.require_fp32(x1), packed_weight(spec, wt),
-                             scale, shift, residual, out=None if skip_fp32 else out, out_bf=c8)
-        if c8 is not None:
-            copies.attach(out, c8=c8)
-        if skip_fp32:
-            copies.attach(out, unwritten=True)
-        return out
-
-
-# ---- 'mixed' configuration (hip.set_compute('mixed'), round 6): the recurrent part of the frozen encoder -- head, the stride-2
-# convolutions, the ConvLSTM gates -- on IEEE-half operands (ESS_COMPUTE_F16).  Activations travel as F16_C8 copies
-# (`copies.of(t).h16` = (tensor, hilo), valid while t is unmodified); the convolution in front of a recurrent block writes a [hi | lo]
-# half pair (its post-ReLU values carry means far above their spread: rounding THEM to 11 bits was the largest term of the encoder's
-# error, tools/hybrid_rounding_ablation.py), and so does the last time step's ConvLSTM for h' -- the event latents.  A [hi | lo]
-# source enters a convolution as 2 C channels against a weight whose input columns are repeated.
-
-
-def _half_source(t):
-    """(F16_C8 tensor, hilo) of an activation inside the mixed encoder: the producer's copy, else its fp32 values converted"""
-    return copies.of(t).h16 or (hip.to_f16_c8(copies.require_fp32(t).contiguous()), False)
-
-
-def _convlayer_forward_mixed(self, x, hilo_out=False, want_fp32=False):
-    """ConvLayer on half operands.  x: the fp32 NCHW voxel grid (the 5x5 head: rounded to half inside the kernel) or an activation
-    carrying a half copy.  -> fp32 tensor (a placeholder unless want_fp32) carrying the output's half copy ([hi | lo] with hilo_out)."""
-    _inference_only(x)
-    _check_eval(self, self.norm)
-    c = self.conv2d
-    k, s, p = c.kernel_size[0], c.stride[0], c.padding[0]
-    act = _ACT[self.activation]
-    N, C0, H, W = x.shape
-    is_head = copies.of(x).h16 is None and k == 5 and s == 1 and C0 <= 5 and not copies.of(x).unwritten
-    if is_head:
-        spec = hip.conv_spec(N, H, W, C0, 0, c.out_channels, k, s, p, act=act, compute=hip.COMPUTE_F16)
+                src, src1, hl, fmt = copies.require_fp32(x), copies.require_fp32(x1), False, hip.FMT_F32_NCHW
+        hilo = k.pairs and bool(hilo_out)
+        copy = _copy_empty(k, N, Cout, Ho, Wo, x.device, hilo) if want_c8 and on else None
+        skip = c8_only and copy is not None
+        # copy-only outputs without a residual leave through the 16-bit-OUTPUT epilogue (16-byte stores, 32-bit offsets) instead of
+        # the fp32 epilogue's optional copy (8-byte stores): the same values (acc * scale + shift, ReLU, round to nearest even)
+        as_out = skip and residual is None and self.activation in (None, 'relu')
+        if k is HALF and (x1 is not None or not (as_out or fmt == hip.FMT_F32_NCHW)):
+            raise hip.EssHipError('ConvLayer(half operands): one source, and fp32 outputs exist for the head only')
+        Ce = C0 * (2 if hl else 1)
+        w = columns(wt, [(0, C0)] * 2) if hl else wt
+        # 5x5 / stride 2 (the three downsampling convolutions of the frozen encoder, reference submodules.py:176-186) as a 3x3 over the
+        # space-to-depth view of the 16-bit source, on the wide-tile 3x3 kernel (ESS_SRC_S2D: 16-channel chunks, the 25 real taps
+        # only) instead of the tap-paired 5x5 kernel; the same products, summed in a different order
+        spec = _s2d_spec(N, ks, st, p, Ce, Cout, H, W, act, k.compute) if as_out and x1 is None and fmt == k.fmt else None
+        wkind = hip.W_CONV if spec is None else hip.W_CONV5_S2D
+        if spec is None:
+            spec = hip.conv_spec(N, H, W, Ce, C1, Cout, ks, st, p, act=act, compute=k.compute)
         scale, shift = _fold(spec, c.bias, self.norm, getattr(self, 'norm_layer', None))
-        h16 = hip.f16_blocks_empty(N, c.out_channels, spec.H_out, spec.W_out, x.device)
-        if want_fp32:
-            out = torch.empty(N, c.out_channels, spec.H_out, spec.W_out, dtype=torch.float32, device=x.device)
-            hip.conv_forward_h16(spec, x.contiguous(), None, packed_weight(spec, c.weight), scale, shift, out=out, out_h16=h16, src_fp32=True)
+        pw = packed_weight(spec, w, kind=wkind)
+        out = _fp32_out((N, Cout, Ho, Wo), x.device, skip)
+        if as_out:
+            _launch(k, spec, src, src1, pw, scale, shift, out=copy, src_fmt=fmt, out_fmt=hip.FMT_F16_C8_HILO if hilo else k.fmt)
         else:
-            hip.conv_forward_h16(spec, x.contiguous(), None, packed_weight(spec, c.weight), scale, shift, out=h16, out_fmt=hip.FMT_F16_C8,
-                                 src_fp32=True)
-            out = copies.placeholder((N, c.out_channels, spec.H_out, spec.W_out), x.device)
-        return copies.attach(out, h16=(h16, False))
-    if want_fp32:
-        raise hip.EssHipError('ConvLayer(mixed): fp32 outputs exist for the head only')
-    s16, hl = _half_source(x)
-    Ce = C0 * (2 if hl else 1)
-    w = columns(c.weight, [(0, C0), (0, C0)]) if hl else c.weight
-    out_fmt = hip.FMT_F16_C8_HILO if hilo_out else hip.FMT_F16_C8
-    h16 = hip.f16_blocks_empty(N, c.out_channels, (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1, x.device, hilo=hilo_out)
-    s2 = None
-    if (k, s, p) == (5, 2, 2) and Ce % 32 == 0 and c.out_channels % 64 == 0 and not (H % 2 or W % 2) and _S2D_MODE != '0':
-        s2 = hip.conv_spec(N, H // 2, W // 2, 4 * Ce, 0, c.out_channels, 3, 1, 1, mode0=hip.SRC_S2D, act=act, compute=hip.COMPUTE_F16)
-        if not (_S2D_MODE == '2' or hip.s2d_preferred(s2)):  # (switch 2 pins the form, as _s2d_spec does)
-            s2 = None
-    if s2 is not None:
-        sc, sh = _fold(s2, c.bias, self.norm, getattr(self, 'norm_layer', None))
-        hip.conv_forward_h16(s2, s16, None, packed_weight(s2, w, kind=hip.W_CONV5_S2D), sc, sh, out=h16, out_fmt=out_fmt)
-    else:
-        spec = hip.conv_spec(N, H, W, Ce, 0, c.out_channels, k, s, p, act=act, compute=hip.COMPUTE_F16)
-        sc, sh = _fold(spec, c.bias, self.norm, getattr(self, 'norm_layer', None))
-        hip.conv_forward_h16(spec, s16, None, packed_weight(spec, w), sc, sh, out=h16, out_fmt=out_fmt)
-    return copies.placeholder((N, c.out_channels, h16.shape[2], h16.shape[3]), x.device, h16=(h16, bool(hilo_out)))
-
-
-def _convlstm_forward_mixed(self, input_, prev_state, lean, hilo_out):
-    """ConvLSTM step on half operands: x (a [hi | lo] pair from the encoder convolution) and h_prev from their half copies; fp32 cell
-    state as in the bf16 configuration.  lean: no fp32 hidden tensor (placeholder + half copy + channel-blocked cell); hilo_out (lean
-    only): the half copy of h' as a [hi | lo] pair -- the latents of the sequence's last step."""
-    _inference_only(input_)
-    N, C, H, W = input_.shape
-    hid = self.hidden_size
-    xs, xhl = _half_source(input_)
-    Cx = C * (2 if xhl else 1)
-    W_ = self.Gates.weight
-    if prev_state is None:
-        hs, hhl, C1, prev_cell = None, False, 0, None
-        cols = [(0, C)] * (2 if xhl else 1)
-    else:
-        prev_hidden, prev_cell = prev_state
-        hs, hhl = _half_source(prev_hidden)
-        C1 = hid * (2 if hhl else 1)
-        cols = [(0, C)] * (2 if xhl else 1) + [(C, C + hid)] * (2 if hhl else 1)
-    w = W_ if cols == [(0, C), (C, C + hid)] else columns(W_, cols)
-    hilo = bool(hilo_out and lean)
-    spec = hip.conv_spec(N, H, W, Cx, C1, 4 * hid, 3, 1, 1, epi=hip.EPI_LSTM, hidden=hid, act=hip.LSTM_H_HILO if hilo else 0,
-                         compute=hip.COMPUTE_F16)
-    if hilo and (hid % (8 * (spec.plan.cout_tile // 32)) or spec.plan.cout_tile < 64):
-        hilo = False
-        spec = hip.conv_spec(N, H, W, Cx, C1, 4 * hid, 3, 1, 1, epi=hip.EPI_LSTM, hidden=hid, compute=hip.COMPUTE_F16)
-    b = packed_rows(spec, self.Gates.bias)
-    new16 = hip.f16_blocks_empty(N, hid, H, W, input_.device, hilo=hilo)
-    cell, sfmt = _new_cell(N, hid, H, W, input_.device, lean)
-    cfmt = hip.FMT_F32_C8 if prev_cell is not None and prev_cell.dim() == 5 else hip.FMT_F32_NCHW
-    if lean and sfmt == hip.FMT_F32_C8:
-        hidden = copies.placeholder((N, hid, H, W), input_.device)
-        hip.conv_forward_h16(spec, xs, hs, packed_weight(spec, w), None, b, aux0=prev_cell, out=None, out2=cell, out_h16=new16,
-                             out_fmt=sfmt, aux_fmt=cfmt)
-    else:
-        hidden = torch.empty(N, hid, H, W, dtype=torch.float32, device=input_.device)
-        hip.conv_forward_h16(spec, xs, hs, packed_weight(spec, w), None, b, aux0=prev_cell, out=hidden, out2=cell, out_h16=new16,
-                             out_fmt=sfmt, aux_fmt=cfmt)
-    copies.attach(hidden, h16=(new16, hilo))
-    return hidden, cell
-
-
-def _convgru_forward_mixed(self, input_, prev_state, lean, hilo_out):
-    """ConvGRU step on half operands (the two fused launches of ConvGRU.forward): x from its half copy (a [hi | lo] pair at the deepest
-    level: repeated weight columns in both launches), h and r*h as half copies, the fp32 recurrence h' = h (1 - u) + o u on channel-
-    blocked fp32 states between lean steps, u between the launches as IEEE half.  hilo_out (lean only): the copy of h' as a [hi | lo] pair."""
-    _inference_only(input_)
-    N, C, H, W = input_.shape
-    hid = self.hidden_size
-    dev = input_.device
-    first = prev_state is None
-    xs, xhl = _half_source(input_)
-    Cx = C * (2 if xhl else 1)
-    C1 = 0 if first else hid
-    cols = [(0, C)] * (2 if xhl else 1) + ([] if first else [(C, C + hid)])
-    plain = cols == [(0, C), (C, C + hid)]
-    wu, wr, wo = (g.weight if plain else columns(g.weight, cols) for g in (self.update_gate, self.reset_gate, self.out_gate))
-    hs = None if first else _half_source(prev_state)[0]
-    if not first and _half_source(prev_state)[1]:
-        raise hip.EssHipError('ConvGRU(mixed): a [hi | lo] hidden state feeds the decoder, not the next time step')
-    hb = copies.of(prev_state).f32c8
-    blocked = first or hb is not None
-    afmt = hip.FMT_F32_C8 if blocked else hip.FMT_F32_NCHW
-    h32 = hb if blocked else copies.require_fp32(prev_state)
-    uact = hip.GRU_U_F16
-    s1 = hip.conv_spec(N, H, W, Cx, C1, 2 * hid, 3, 1, 1, epi=hip.EPI_GRU_UR, act=uact, hidden=hid, compute=hip.COMPUTE_F16)
-    if hid % (s1.plan.cout_tile // 2):
-        uact = hip.GRU_U_F32
-        s1 = hip.conv_spec(N, H, W, Cx, C1, 2 * hid, 3, 1, 1, epi=hip.EPI_GRU_UR, act=uact, hidden=hid, compute=hip.COMPUTE_F16)
-    hilo = bool(hilo_out and lean and blocked)
-    s2 = hip.conv_spec(N, H, W, Cx, C1, hid, 3, 1, 1, epi=hip.EPI_GRU_OUT, act=uact | (hip.GRU_H_HILO if hilo else 0), hidden=hid, compute=hip.COMPUTE_F16)
-    if hilo and hid % s2.plan.cout_tile:
-        hilo = False
-        s2 = hip.conv_spec(N, H, W, Cx, C1, hid, 3, 1, 1, epi=hip.EPI_GRU_OUT, act=uact, hidden=hid, compute=hip.COMPUTE_F16)
-    b1, b2 = packed_rows(s1, self.update_gate.bias, self.reset_gate.bias), packed_rows(s2, self.out_gate.bias)
-    pw1, pw2 = packed_weight(s1, wu, wr), packed_weight(s2, wo)
-    if afmt == hip.FMT_F32_C8:
-        u = hip.f16_c8_raw_empty(N, hid, H, W, dev) if uact == hip.GRU_U_F16 else hip.f32_c8_empty(N, hid, H, W, dev)
-    else:
-        u = torch.empty(N, hid, H, W, dtype=torch.float32, device=dev)
-    rh16 = None if first else hip.f16_blocks_empty(N, hid, H, W, dev)
-    hip.conv_forward_h16(s1, xs, hs, pw1, None, b1, aux0=h32, out=u, out2=None, out_h16=rh16, out_fmt=afmt, aux_fmt=afmt)
-    new16 = hip.f16_blocks_empty(N, hid, H, W, dev, hilo=hilo)
-    if lean and blocked:
-        nb = hip.f32_c8_empty(N, hid, H, W, dev)
-        hip.conv_forward_h16(s2, xs, rh16, pw2, None, b2, aux0=h32, aux1=u, out=nb, out_h16=new16, out_fmt=hip.FMT_F32_C8, aux_fmt=afmt)
-        new_state = copies.placeholder((N, hid, H, W), dev, f32c8=nb)
-    else:
-        new_state = torch.empty(N, hid, H, W, dtype=torch.float32, device=dev)
-        hip.conv_forward_h16(s2, xs, rh16, pw2, None, b2, aux0=h32, aux1=u, out=new_state, out_h16=new16, out_fmt=hip.FMT_F32_NCHW, aux_fmt=afmt)
-    copies.attach(new_state, h16=(new16, hilo))
-    return new_state
+            _launch(k, spec, src, src1, pw, scale, shift, residual, out=None if skip else out, copy=copy, src_fmt=fmt)
+        if copy is not None:
+            _attach_copy(k, out, copy, hilo)
+        return out
 
 
 class TransposedConvLayer(nn.Module):
@@ -447,47 +361,50 @@ class ConvLSTM(nn.Module):
         self.zero_tensors = {}
         self.Gates = nn.Conv2d(input_size + hidden_size, 4 * hidden_size, kernel_size, padding=kernel_size // 2)
 
-    def forward(self, input_, prev_state=None, lean=False):
-        """lean: (bf16 arithmetic, BF16_C8 path) do not write the fp32 hidden state -- only its BF16_C8 copy and the fp32
-        cell; for a time step whose state is consumed by the next step of this module and nothing else."""
+    def forward(self, input_, prev_state=None, lean=False, hilo_out=False, kind=None):
+        """lean: (16-bit copies on) do not write the fp32 hidden state -- only its 16-bit copy and the fp32 cell; for a time step
+        whose state is consumed by the next step of this module and nothing else.
+        hilo_out: (half kind, lean) the copy of h' as a [hi | lo] pair -- the latents of a sequence's last step."""
         _inference_only(input_)
+        k = kind or operand_kind()
         N, C, H, W = input_.shape
-        hid = self.hidden_size
-        if prev_state is None:
-            # first step of a sequence: h = 0 and c = 0 (a NULL cell pointer reads as zeros), so the h half of the contraction
-            # adds exact zeros -- run the gate conv over x alone with the x columns of the weight: bit-identical, half the MFMA
-            # work of this launch, and no zero state tensors (the reference caches them, submodules.py:196-207)
-            hidden = torch.empty(N, hid, H, W, dtype=torch.float32, device=input_.device)
-            return self._first_step(input_, hidden, None, lean)
-        prev_hidden, prev_cell = prev_state
-        spec = hip.conv_spec(N, H, W, C, hid, 4 * hid, 3, 1, 1, epi=hip.EPI_LSTM, hidden=hid)
+        hid, dev = self.hidden_size, input_.device
+        # first step of a sequence: h = 0 and c = 0 (a NULL cell pointer reads as zeros), so the h half of the contraction adds exact
+        # zeros -- the gate conv runs over x alone with the x columns of the weight (_gate_weight; the reference caches zero state
+        # tensors instead, submodules.py:196-207)
+        first = prev_state is None
+        prev_hidden, prev_cell = (None, None) if first else prev_state
+        # x and h from their 16-bit copies when the producers left them (the encoder conv and the previous step of this kernel do),
+        # and one of h' for the next time step.  bf16 kind: bit-identical to staging from the fp32 tensors -- the copies hold exactly
+        # the bf16 operands the MFMA would be fed anyway -- but the tile loads are 16-byte vectors instead of 8 strided dwords.  A
+        # state tensor that went through user code (clone, detach, arithmetic) simply has no copy any more: then BOTH sources are
+        # staged from fp32 (half kind: the one without a copy is converted).
+        on = _copies_on(k, C)
+        xs, xhl, fmt = _source(k, input_, on)
+        hs, hhl, hfmt = (None, False, fmt) if first else _source(k, prev_hidden, on)
+        if hfmt != fmt:
+            xs, hs, fmt = copies.require_fp32(input_), copies.require_fp32(prev_hidden), hip.FMT_F32_NCHW
+        Cx, C1 = C * (2 if xhl else 1), 0 if first else hid * (2 if hhl else 1)
+        w = _gate_weight(self.Gates.weight, C, hid, xhl, hhl, first)
+        hilo = k.pairs and bool(hilo_out and lean)
+        spec = hip.conv_spec(N, H, W, Cx, C1, 4 * hid, 3, 1, 1, epi=hip.EPI_LSTM, hidden=hid, act=hip.LSTM_H_HILO if hilo else 0,
+                             compute=k.compute)
+        if hilo and (hid % (8 * (spec.plan.cout_tile // 32)) or spec.plan.cout_tile < 64):  # (no pair copy of h' on such tiles)
+            hilo = False
+            spec = hip.conv_spec(N, H, W, Cx, C1, 4 * hid, 3, 1, 1, epi=hip.EPI_LSTM, hidden=hid, compute=k.compute)
         b = packed_rows(spec, self.Gates.bias)
-        hidden = torch.empty(N, hid, H, W, dtype=torch.float32, device=input_.device)
-        # bf16 arithmetic: stage x and h from their BF16_C8 copies when the producers left them (the encoder conv and
-        # the previous step of this kernel do), and leave one of h' for the next time step.  Bit-identical to staging
-        # from the fp32 tensors -- the copies hold exactly the bf16 operands the MFMA would be fed anyway -- but the
-        # tile loads are 16-byte vectors instead of 8 strided dwords.  A state tensor that went through user code
-        # (clone, detach, arithmetic) simply has no copy any more and takes the fp32 path.
-        bf = spec.desc.compute == hip.COMPUTE_BF16 and (C % 8) == 0
-        stage8 = bf and hip.c8_stageable(3, 1, 1)
-        x8, h8 = (copies.of(input_).c8, copies.of(prev_hidden).c8) if stage8 else (None, None)
-        new8 = hip.bf16_c8_empty(N, hid, H, W, input_.device) if bf else None
-        skip_fp32 = lean and new8 is not None and stage8
+        new = _copy_empty(k, N, hid, H, W, dev, hilo) if on else None
         # a lean step's cell state travels to the next time step only: channel-blocked fp32 (FMT_F32_C8 -- the epilogue reads and
         # writes a lane's 4 channels of a pixel as ONE 16-byte access instead of four 4-byte ones into four planes)
-        cell, sfmt = _new_cell(N, hid, H, W, input_.device, skip_fp32)
+        cell, sfmt = _new_cell(N, hid, H, W, dev, lean and on)
         cfmt = hip.FMT_F32_C8 if prev_cell is not None and prev_cell.dim() == 5 else hip.FMT_F32_NCHW
-        if bf and x8 is not None and h8 is not None:
-            hip.conv_forward(spec, x8, h8, packed_weight(spec, self.Gates.weight), None, b, aux0=prev_cell,
-                             out=None if skip_fp32 else hidden, out2=cell, out_bf=new8, src_fmt=hip.FMT_BF16_C8, out_fmt=sfmt,
-                             aux_fmt=cfmt)
-        else:
-            hip.conv_forward(spec, copies.require_fp32(input_), copies.require_fp32(prev_hidden), packed_weight(spec, self.Gates.weight),
-                             None, b, aux0=prev_cell, out=None if skip_fp32 else hidden, out2=cell, out_bf=new8, out_fmt=sfmt, aux_fmt=cfmt)
-        if new8 is not None:
-            copies.attach(hidden, c8=new8)
-        if skip_fp32:
-            copies.attach(hidden, unwritten=True)
+        # (the half kernels drop the fp32 h' next to a channel-blocked cell only: with ESS_CELL_C8=0 the half kind writes it)
+        skip = lean and on and (k is BF16 or sfmt == hip.FMT_F32_C8)
+        hidden = _fp32_out((N, hid, H, W), dev, skip)
+        _launch(k, spec, xs, hs, packed_weight(spec, w), None, b, aux0=prev_cell, out=None if skip else hidden, out2=cell, copy=new,
+                src_fmt=fmt, out_fmt=sfmt, aux_fmt=cfmt)
+        if new is not None:
+            _attach_copy(k, hidden, new, hilo)
         return hidden, cell
 
 
@@ -498,43 +415,14 @@ def _new_cell(N, hid, H, W, device, blocked):
     return torch.empty(N, hid, H, W, dtype=torch.float32, device=device), hip.FMT_F32_NCHW
 
 
-def _convlstm_first_step(self, input_, hidden, cell, lean):
-    N, C, H, W = input_.shape
-    hid = self.hidden_size
-    wx = columns(self.Gates.weight, [(0, C)])  # the x columns of the gate weight as their own (packable) tensor
-    spec = hip.conv_spec(N, H, W, C, 0, 4 * hid, 3, 1, 1, epi=hip.EPI_LSTM, hidden=hid)
-    b = packed_rows(spec, self.Gates.bias)
-    bf = spec.desc.compute == hip.COMPUTE_BF16 and (C % 8) == 0
-    stage8 = bf and hip.c8_stageable(3, 1, 1)
-    x8 = copies.of(input_).c8 if stage8 else None
-    new8 = hip.bf16_c8_empty(N, hid, H, W, input_.device) if bf else None
-    skip_fp32 = lean and new8 is not None and stage8
-    cell, sfmt = _new_cell(N, hid, H, W, input_.device, skip_fp32)
-    if x8 is not None:
-        hip.conv_forward(spec, x8, None, packed_weight(spec, wx), None, b, aux0=None,
-                         out=None if skip_fp32 else hidden, out2=cell, out_bf=new8, src_fmt=hip.FMT_BF16_C8, out_fmt=sfmt)
-    else:
-        hip.conv_forward(spec, copies.require_fp32(input_), None, packed_weight(spec, wx), None, b, aux0=None,
-                         out=None if skip_fp32 else hidden, out2=cell, out_bf=new8, out_fmt=sfmt)
-    if new8 is not None:
-        copies.attach(hidden, c8=new8)
-    if skip_fp32:
-        copies.attach(hidden, unwritten=True)
-    return hidden, cell
-
-
-ConvLSTM._first_step = _convlstm_first_step
-ConvLSTM.forward_mixed = _convlstm_forward_mixed
-
-
 class ConvGRU(nn.Module):
     """Two fused kernels: (update, reset) gates -> (u, r*h); candidate -> h'.  Reference: submodules.py:233-273.
 
-    bf16 arithmetic keeps the recurrent state in three forms, as the ConvLSTM does with (h, c): the BF16_C8 copy the gate /
-    candidate convolutions stage (`copies.of(h).c8`), the fp32 values the epilogues blend with (`h' = h (1 - u) + o u` stays an fp32
-    recurrence: channel-blocked fp32 `f32c8` between lean time steps, plain NCHW planes otherwise), and -- unless the step is
-    lean -- the fp32 NCHW tensor the reference returns.  u travels between the two kernels as channel-blocked fp32, r*h as the
-    BF16_C8 tensor the candidate convolution would round it to anyway; neither the concat nor an fp32 r*h exist in memory."""
+    With 16-bit copies on, the recurrent state exists in three forms, as the ConvLSTM's does with (h, c): the 16-bit copy the gate /
+    candidate convolutions stage (`copies.of(h).c8` / `.h16`), the fp32 values the epilogues blend with (`h' = h (1 - u) + o u` stays an
+    fp32 recurrence: channel-blocked fp32 `f32c8` between lean time steps, plain NCHW planes otherwise), and -- unless the step is
+    lean -- the fp32 NCHW tensor the reference returns.  u travels between the two kernels as a channel-blocked tensor, r*h as the
+    16-bit tensor the candidate convolution would round it to anyway; neither the concat nor an fp32 r*h exist in memory."""
 
     def __init__(self, input_size, hidden_size, kernel_size):
         super().__init__()
@@ -549,77 +437,79 @@ class ConvGRU(nn.Module):
             init.orthogonal_(g.weight)
             init.constant_(g.bias, 0.)
 
-    def forward(self, input_, prev_state, lean=False):
-        """lean: (bf16 arithmetic, BF16_C8 path) do not write the fp32 NCHW state -- only its BF16_C8 copy and the channel-blocked
-        fp32 form; for a time step whose state is consumed by the next step of this module and nothing else."""
+    def forward(self, input_, prev_state, lean=False, hilo_out=False, kind=None):
+        """lean: (16-bit copies on) do not write the fp32 NCHW state -- only its 16-bit copy and the channel-blocked fp32 form; for a
+        time step whose state is consumed by the next step of this module and nothing else.
+        hilo_out: (half kind, lean) the copy of h' as a [hi | lo] pair."""
         _inference_only(input_)
+        k = kind or operand_kind()
         N, C, H, W = input_.shape
-        hid = self.hidden_size
-        dev = input_.device
-        first = prev_state is None
+        hid, dev = self.hidden_size, input_.device
         # first step of a sequence: h = 0, so r*h = 0 whatever r is and the h halves of all three contractions add exact zeros --
         # both kernels run over x alone with the x columns of the weights (half the MFMA work, no zero tensors; the reset rows of
         # the first kernel are computed and dropped)
-        C1 = 0 if first else hid
-        # bf16 arithmetic: the update gate travels between the two launches rounded to IEEE half (ESS_GRU_U_F16: an F16_C8 tensor where
-        # the states are channel-blocked, the rounded value in the fp32 tensor otherwise -- the same bits either way); switch ESS_GRU_U16=0
-        uact = hip.GRU_U_F16 if (hip.get_compute() == 'bf16' and os.environ.get('ESS_GRU_U16', '1')[:1] != '0') else hip.GRU_U_F32
-        s1 = hip.conv_spec(N, H, W, C, C1, 2 * hid, 3, 1, 1, epi=hip.EPI_GRU_UR, act=uact, hidden=hid)
-        s2 = hip.conv_spec(N, H, W, C, C1, hid, 3, 1, 1, epi=hip.EPI_GRU_OUT, act=uact, hidden=hid)
-        if uact == hip.GRU_U_F16 and hid % (s1.plan.cout_tile // 2):
+        first = prev_state is None
+        on = _copies_on(k, C, hid)
+        xs, xhl, fmt = _source(k, input_, on)
+        hs, hhl, hfmt = (None, False, fmt) if first else _source(k, prev_state, on)
+        if hhl:
+            raise hip.EssHipError('ConvGRU: a [hi | lo] hidden state feeds the decoder, not the next time step')
+        Cx, C1 = C * (2 if xhl else 1), 0 if first else hid
+        # the update gate travels between the two launches rounded to IEEE half (ESS_GRU_U_F16: an F16_C8 tensor where the states are
+        # channel-blocked, the rounded value in the fp32 tensor otherwise -- the same bits either way); bf16 kind: in bf16 arithmetic,
+        # switch ESS_GRU_U16=0 (the half kind does not read the switch)
+        u16 = k is HALF or (hip.get_compute() == 'bf16' and os.environ.get('ESS_GRU_U16', '1')[:1] != '0')
+        uact = hip.GRU_U_F16 if u16 else hip.GRU_U_F32
+        s1 = hip.conv_spec(N, H, W, Cx, C1, 2 * hid, 3, 1, 1, epi=hip.EPI_GRU_UR, act=uact, hidden=hid, compute=k.compute)
+        if u16 and hid % (s1.plan.cout_tile // 2):
             # (an F16_C8 u exists in the straight-line epilogues only: every hidden channel of a workgroup's tile real -- the library
             # refuses the combination otherwise; E2VID's 64 / 128 / 256 hidden channels qualify)
             uact = hip.GRU_U_F32
-            s1 = hip.conv_spec(N, H, W, C, C1, 2 * hid, 3, 1, 1, epi=hip.EPI_GRU_UR, act=uact, hidden=hid)
-            s2 = hip.conv_spec(N, H, W, C, C1, hid, 3, 1, 1, epi=hip.EPI_GRU_OUT, act=uact, hidden=hid)
+            s1 = hip.conv_spec(N, H, W, Cx, C1, 2 * hid, 3, 1, 1, epi=hip.EPI_GRU_UR, act=uact, hidden=hid, compute=k.compute)
+        hb = None if first else copies.of(prev_state).f32c8  # channel-blocked fp32 h (left by a lean step)
+        blocked = first or hb is not None
+        hilo = k.pairs and bool(hilo_out and lean and blocked)
+        s2 = hip.conv_spec(N, H, W, Cx, C1, hid, 3, 1, 1, epi=hip.EPI_GRU_OUT, act=uact | (hip.GRU_H_HILO if hilo else 0), hidden=hid,
+                           compute=k.compute)
+        if hilo and hid % s2.plan.cout_tile:
+            hilo = False
+            s2 = hip.conv_spec(N, H, W, Cx, C1, hid, 3, 1, 1, epi=hip.EPI_GRU_OUT, act=uact, hidden=hid, compute=k.compute)
         b1, b2 = packed_rows(s1, self.update_gate.bias, self.reset_gate.bias), packed_rows(s2, self.out_gate.bias)
-        if first:
-            # the x columns of the three gate weights as their own (packable) tensors
-            wu, wr, wo = (columns(g.weight, [(0, C)]) for g in (self.update_gate, self.reset_gate, self.out_gate))
-        else:
-            wu, wr, wo = self.update_gate.weight, self.reset_gate.weight, self.out_gate.weight
+        wu, wr, wo = (_gate_weight(g.weight, C, hid, xhl, False, first) for g in (self.update_gate, self.reset_gate, self.out_gate))
         pw1, pw2 = packed_weight(s1, wu, wr), packed_weight(s2, wo)
-        bf = s1.desc.compute == hip.COMPUTE_BF16 and (C % 8) == 0 and (hid % 8) == 0 and hip.c8_stageable(3, 1, 1)
-        x8 = copies.of(input_).c8 if bf else None
-        h8 = copies.of(prev_state).c8 if (bf and not first) else None
-        if x8 is not None and (first or h8 is not None):
-            # ---- BF16_C8 path: x / h / r*h staged as 16-byte pixel vectors, fp32 state operands channel-blocked where they can be
-            hb = copies.of(prev_state).f32c8  # channel-blocked fp32 h (left by a lean step)
-            if first or hb is not None:
-                h32, afmt = hb, hip.FMT_F32_C8
-            else:
-                h32, afmt = copies.require_fp32(prev_state), hip.FMT_F32_NCHW
-            if afmt == hip.FMT_F32_C8:
-                u = hip.f16_c8_raw_empty(N, hid, H, W, dev) if s1.desc.act == hip.GRU_U_F16 else hip.f32_c8_empty(N, hid, H, W, dev)
-            else:
-                u = torch.empty(N, hid, H, W, dtype=torch.float32, device=dev)
-            rh8 = None if first else hip.bf16_c8_empty(N, hid, H, W, dev)
-            hip.conv_forward(s1, x8, h8, pw1, None, b1, aux0=h32, out=u, out2=None, out_bf=rh8, src_fmt=hip.FMT_BF16_C8,
-                             out_fmt=afmt, aux_fmt=afmt)
-            new8 = hip.bf16_c8_empty(N, hid, H, W, dev)
-            new_state = torch.empty(N, hid, H, W, dtype=torch.float32, device=dev)
-            if lean:
-                nb = hip.f32_c8_empty(N, hid, H, W, dev)
-                hip.conv_forward(s2, x8, rh8, pw2, None, b2, aux0=h32, aux1=u, out=nb, out_bf=new8, src_fmt=hip.FMT_BF16_C8,
-                                 out_fmt=hip.FMT_F32_C8, aux_fmt=afmt)
-                copies.attach(new_state, f32c8=nb, unwritten=True)
-            else:
-                hip.conv_forward(s2, x8, rh8, pw2, None, b2, aux0=h32, aux1=u, out=new_state, out_bf=new8, src_fmt=hip.FMT_BF16_C8,
-                                 out_fmt=hip.FMT_F32_NCHW, aux_fmt=afmt)
-            copies.attach(new_state, c8=new8)
-            return new_state
-        # ---- fp32 NCHW sources (exact-fp32 arithmetic; or a state that went through user code and lost its copies)
-        x = copies.require_fp32(input_)
-        h = None if first else copies.require_fp32(prev_state)
-        u = torch.empty(N, hid, H, W, dtype=torch.float32, device=dev)
-        rh = None if first else torch.empty_like(u)
-        hip.conv_forward(s1, x, h, pw1, None, b1, aux0=h, out=u, out2=rh)
-        new_state = torch.empty_like(u)
-        new8 = hip.bf16_c8_empty(N, hid, H, W, dev) if bf else None
-        hip.conv_forward(s2, x, rh, pw2, None, b2, aux0=h, aux1=u, out=new_state, out_bf=new8)
-        if new8 is not None:
-            copies.attach(new_state, c8=new8)
-        return new_state
+        shape = (N, hid, H, W)
+        if fmt == hip.FMT_F32_NCHW or hfmt != fmt:
+            # ---- fp32 NCHW sources (bf16 kind: exact-fp32 arithmetic; or a state that went through user code and lost its copies)
+            x = copies.require_fp32(input_)
+            h = None if first else copies.require_fp32(prev_state)
+            u = torch.empty(shape, dtype=torch.float32, device=dev)
+            rh = None if first else torch.empty_like(u)
+            _launch(k, s1, x, h, pw1, None, b1, aux0=h, out=u, out2=rh)
+            new_state = torch.empty_like(u)
+            new = _copy_empty(k, N, hid, H, W, dev) if on else None
+            _launch(k, s2, x, rh, pw2, None, b2, aux0=h, aux1=u, out=new_state, copy=new)
+            return new_state if new is None else _attach_copy(k, new_state, new)
+        # ---- 16-bit sources: x / h / r*h staged as 16-byte pixel vectors, fp32 state operands channel-blocked where they can be
+        afmt = hip.FMT_F32_C8 if blocked else hip.FMT_F32_NCHW
+        h32 = hb if blocked else copies.require_fp32(prev_state)
+        if blocked:
+            u = hip.f16_c8_raw_empty(N, hid, H, W, dev) if uact == hip.GRU_U_F16 else hip.f32_c8_empty(N, hid, H, W, dev)
+        else:
+            u = torch.empty(shape, dtype=torch.float32, device=dev)
+        rh = None if first else _copy_empty(k, N, hid, H, W, dev)
+        _launch(k, s1, xs, hs, pw1, None, b1, aux0=h32, out=u, out2=None, copy=rh, src_fmt=fmt, out_fmt=afmt, aux_fmt=afmt)
+        new = _copy_empty(k, N, hid, H, W, dev, hilo)
+        # (the half kind's lean form reads channel-blocked states only; the bf16 kind's also starts from fp32 NCHW planes)
+        skip = lean and (k is BF16 or blocked)
+        new_state = _fp32_out(shape, dev, skip)
+        if skip:
+            nb = hip.f32_c8_empty(N, hid, H, W, dev)
+            _launch(k, s2, xs, rh, pw2, None, b2, aux0=h32, aux1=u, out=nb, copy=new, src_fmt=fmt, out_fmt=hip.FMT_F32_C8, aux_fmt=afmt)
+            copies.attach(new_state, f32c8=nb)
+        else:
+            _launch(k, s2, xs, rh, pw2, None, b2, aux0=h32, aux1=u, out=new_state, copy=new, src_fmt=fmt, out_fmt=hip.FMT_F32_NCHW,
+                    aux_fmt=afmt)
+        return _attach_copy(k, new_state, new, hilo)
 
 
 class RecurrentConvLayer(nn.Module):
@@ -634,39 +524,25 @@ class RecurrentConvLayer(nn.Module):
         self.conv = ConvLayer(in_channels, out_channels, kernel_size, stride, padding, activation, norm)
         self.recurrent_block = block(input_size=out_channels, hidden_size=out_channels, kernel_size=3)
 
-    def forward(self, x, prev_state, lean=False, x_conv=None):
+    def _prev_has_c8(self, prev_state):
+        """True when the recurrent block will take the BF16_C8 path for this step (zero state, or a state that still carries its copy)."""
+        if prev_state is None:
+            return True
+        return copies.of(prev_state[0] if self.recurrent_block_type == 'convlstm' else prev_state).c8 is not None
+
+    def forward(self, x, prev_state, lean=False, x_conv=None, hilo_out=False, x_hilo=False, kind=None):
         """x_conv: the conv output computed ahead of time (time-batched prefix, UNetRecurrent.forward_prefix): a placeholder
-        carrying its BF16_C8 copy; `x` is then ignored."""
-        # the conv output never leaves this module: in bf16 arithmetic the recurrent block stages it from the BF16_C8 copy
-        # (a 64 | 128 | 256-channel tensor, always a whole number of 8-channel blocks), so its fp32 form is not written
-        if x_conv is not None:
-            x = x_conv
-        else:
-            x = self.conv(x, want_c8=True, c8_only=self.conv.conv2d.out_channels % 8 == 0 and hip.c8_stageable(3, 1, 1) and
-                          self._prev_has_c8(prev_state))
-        state = self.recurrent_block(x, prev_state, lean=lean)
-        x = state[0] if self.recurrent_block_type == 'convlstm' else state
-        return x, state
-
-
-def _rcl_prev_has_c8(self, prev_state):
-    """True when the recurrent block will take the BF16_C8 path for this step (zero state, or a state that still carries its copy)."""
-    if prev_state is None:
-        return True
-    return copies.of(prev_state[0] if self.recurrent_block_type == 'convlstm' else prev_state).c8 is not None
-
-
-RecurrentConvLayer._prev_has_c8 = _rcl_prev_has_c8
-
-
-def _rcl_forward_mixed(self, x, prev_state, lean=False, hilo_out=False, x_hilo=True):
-    """the mixed configuration's step (see _convlayer_forward_mixed): conv -> half copy ([hi | lo] pair with x_hilo) -> ConvLSTM on half operands"""
-    xc = self.conv.forward_mixed(x, hilo_out=x_hilo)
-    state = self.recurrent_block.forward_mixed(xc, prev_state, lean, hilo_out)
-    return (state[0] if self.recurrent_block_type == 'convlstm' else state), state
-
-
-RecurrentConvLayer.forward_mixed = _rcl_forward_mixed
+        carrying its BF16_C8 copy; `x` is then ignored.
+        x_hilo / hilo_out (half kind): the conv output / the copy of a lean step's h' as a [hi | lo] pair."""
+        k = kind or operand_kind()
+        # the conv output never leaves this module: the recurrent block stages it from the 16-bit copy (a 64 | 128 | 256-channel
+        # tensor, always a whole number of 8-channel blocks), so its fp32 form is not written (bf16 kind: unless the block will stage
+        # fp32 tensors this step; the half kind converts a state that lost its copy instead)
+        if x_conv is None:
+            x_conv = self.conv(x, want_c8=True, hilo_out=x_hilo, kind=k, c8_only=k is HALF or (
+                self.conv.conv2d.out_channels % 8 == 0 and hip.c8_stageable(3, 1, 1) and self._prev_has_c8(prev_state)))
+        state = self.recurrent_block(x_conv, prev_state, lean=lean, hilo_out=hilo_out, kind=k)
+        return (state[0] if self.recurrent_block_type == 'convlstm' else state), state
 
 
 class ResidualBlock(nn.Module):
@@ -731,6 +607,3 @@ class ResidualBlock(nn.Module):
             out, _ = hip.instnorm_forward(out, x, 2, EPS)
         return out
 
-
-ConvLayer.forward_mixed = _convlayer_forward_mixed
-ConvGRU.forward_mixed = _convgru_forward_mixed

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from ... import copies, hip
-from .submodules import ConvLayer, RecurrentConvLayer, ResidualBlock, TransposedConvLayer, UpsampleConvLayer
+from .submodules import BF16, HALF, ConvLayer, RecurrentConvLayer, ResidualBlock, TransposedConvLayer, UpsampleConvLayer, operand_kind
 
 _ACT = {'sigmoid': hip.ACT_SIGMOID, 'tanh': hip.ACT_TANH, 'relu': hip.ACT_RELU}
 
@@ -130,13 +130,15 @@ class UNetRecurrent(BaseUNet):
         self.build_decoders()
         self.build_prediction_layer()
 
+    steps_left = None  # (time steps that follow the next forward() in its sequence; None: unknown)
+
     def forward_prefix(self, x_all):
         """The part of a time step that depends on the step's voxel grid only -- head conv and the first encoder's stride-2 conv
         (reference unet.py:131-139: `x = self.head(x)`, `encoder.conv`) -- for MANY time slices at once: x_all = [S*B, C, H, W]
         (S normalised slices stacked along the batch axis) -> (head copies, conv copies) as BF16_C8 tensors [S*B, ...], or None when
-        the lean BF16_C8 path is not available (exact-fp32 arithmetic, diagnostic switches).  forward(..., prefix=(head_t, conv_t))
-        then starts at the first recurrent block.  Two launches for S slices instead of 2 S."""
-        ok = hip.get_compute() == 'bf16' and not hip.mixed() and hip.c8_stageable(3, 1, 1) and hip.c8_stageable(5, 2, 2) and \
+        the lean BF16_C8 path is not available (exact-fp32 arithmetic, half operands, diagnostic switches).  forward(...,
+        prefix=(head_t, conv_t)) then starts at the first recurrent block.  Two launches for S slices instead of 2 S."""
+        ok = hip.get_compute() == 'bf16' and operand_kind() is BF16 and hip.c8_stageable(3, 1, 1) and hip.c8_stageable(5, 2, 2) and \
             self.encoder_output_sizes[0] % 8 == 0 and self.base_num_channels % 8 == 0
         if not ok:
             return None
@@ -144,23 +146,15 @@ class UNetRecurrent(BaseUNet):
         x0 = self.encoders[0].conv(h, want_c8=True, c8_only=True)
         return copies.of(h).c8, copies.of(x0).c8
 
-    def forward(self, x, prev_states, encoder_only=False, lean=False, prefix=None, lean_state=False):
-        """lean (needs encoder_only; effective in bf16 arithmetic): the step's only purpose is the
-        recurrent state for the NEXT step, so the fp32 forms of the head output and of the hidden states are not written
-        (their BF16_C8 copies and the fp32 cell states are); `latent` is None.  Result-identical for the steps t < T-1 of
-        a sequence: the next step stages x and h from the copies anyway.
-        lean_state (any step, the last one of a training sequence in particular): only the RECURRENT BLOCKS run their lean form --
-        hidden states leave as BF16_C8 copies (+ channel-blocked fp32 cells), their fp32 NCHW tensors are unwritten placeholders.
-        Everything downstream in this package stages the copies (residual blocks, decoders, the semantic decoder, the L1 latent
-        losses), so the outputs are bit-identical; a caller that wants fp32 hidden states keeps lean_state off."""
-        if lean and not encoder_only:
-            raise ValueError('lean needs encoder_only')
-        if hip.mixed():
-            if prefix is not None:
-                raise ValueError("the time-batched prefix does not exist in the 'mixed' configuration")
-            return self._forward_mixed(x, prev_states, encoder_only, lean, lean_state)
-        # every consumer of the unwritten fp32 tensors must be able to stage their BF16_C8 copies (diagnostic switches may forbid it)
-        c8_ok = hip.get_compute() == 'bf16' and hip.c8_stageable(3, 1, 1) and hip.c8_stageable(5, 2, 2)
+    def _lean_plan(self, k, x, encoder_only, lean, lean_state):
+        """-> (lean, no_fp32) as the step runs them.  no_fp32: may the hidden states go without an fp32 form?  Every consumer of the
+        unwritten tensors must then be able to stage their 16-bit copies.  The two kinds answer by DIFFERENT rules, and nothing says
+        the difference is intended: the half kind's is the looser one -- it asks neither the diagnostic switches
+        (c8_stageable) nor for a tail that reads copies on even plane widths, so on a full step over odd-width planes it says yes
+        where the bf16 kind writes the fp32 states."""
+        if k is HALF:
+            return lean, lean or (lean_state and self.use_upsample_conv and self.norm != 'IN')
+        c8_ok = hip.get_compute() == 'bf16' and hip.c8_stageable(3, 1, 1) and hip.c8_stageable(5, 2, 2)  # (switches may forbid it)
         lean = lean and c8_ok
         # (lean_state on a full step: the tail must be the all-BF16_C8 chain -- upsample-conv decoders, fused norms; a module that
         # would read the fp32 hidden state refuses the unwritten placeholder loudly: copies.require_fp32)
@@ -168,7 +162,26 @@ class UNetRecurrent(BaseUNet):
         # fp32 values: those of a lean state would be the bf16-rounded copy's -- close, not bit-identical)
         wid = None if x is None else x.shape[3]
         even = wid is not None and all(((wid >> i) & 1) == 0 for i in range(1, self.num_encoders + 1))
-        lean_state = lean or (lean_state and c8_ok and (encoder_only or (self._tail_reads_copies() and even)))
+        return lean, lean or (lean_state and c8_ok and (encoder_only or (self._tail_reads_copies() and even)))
+
+    def forward(self, x, prev_states, encoder_only=False, lean=False, prefix=None, lean_state=False):
+        """One time step; the 16-bit operand kind of its recurrent part (head, stride-2 convolutions, gates: submodules.operand_kind)
+        is chosen here, the tail that only feeds the reconstruction runs on the bf16 kernels from BF16_C8 copies either way.
+        lean (needs encoder_only; effective with 16-bit copies on): the step's only purpose is the
+        recurrent state for the NEXT step, so the fp32 forms of the head output and of the hidden states are not written
+        (their 16-bit copies and the fp32 cell states are); `latent` is None.  Result-identical for the steps t < T-1 of
+        a sequence: the next step stages x and h from the copies anyway.
+        lean_state (any step, the last one of a training sequence in particular): only the RECURRENT BLOCKS run their lean form --
+        hidden states leave as 16-bit copies (+ channel-blocked fp32 cells), their fp32 NCHW tensors are unwritten placeholders; half
+        kind: the last step's copies of h' -- the event latents -- then leave as [hi | lo] pairs.
+        Everything downstream in this package stages the copies (residual blocks, decoders, the semantic decoder, the L1 latent
+        losses), so the outputs are bit-identical; a caller that wants fp32 hidden states keeps lean_state off."""
+        if lean and not encoder_only:
+            raise ValueError('lean needs encoder_only')
+        k = operand_kind()
+        if k is HALF and prefix is not None:
+            raise ValueError("the time-batched prefix does not exist in the 'mixed' configuration")
+        lean, no_fp32 = self._lean_plan(k, x, encoder_only, lean, lean_state)
         x_conv0 = None
         if prefix is not None:  # (lean steps only: head and first conv were computed for all slices at once, forward_prefix)
             if not lean:
@@ -178,13 +191,28 @@ class UNetRecurrent(BaseUNet):
             x = copies.placeholder((N, self.base_num_channels, H, W), h8.device, c8=h8)
             x_conv0 = copies.placeholder((N, self.encoder_output_sizes[0], c8.shape[2], c8.shape[3]), c8.device, c8=c8)
         else:
-            x = self.head(x, want_c8=True, c8_only=lean)  # the first encoder conv stages from the BF16_C8 copy (bf16 arithmetic)
+            x = self.head(x, want_c8=True, c8_only=lean, kind=k)  # the first encoder conv stages from the 16-bit copy
         head = x
         if prev_states is None:
             prev_states = [None] * self.num_encoders
+        # half kind, WHERE the [hi | lo] pairs are used: by default at the DEEPEST level only -- the convolution feeding its recurrent
+        # block and, on the last step, its h' (the 1/8-resolution latent).  tools/hybrid_rounding_ablation.py (levels / latents
+        # sections): on the trained fixture that level alone carries the effect (10 flips of 307200 against 13 with pairs at all three
+        # levels, 37 with none; latents: 11 with the 1/8 latent alone, 13 with all, 40 with none); ESS_MIXED_HILO=all puts pairs at
+        # every level (+ 0.3 ms per time step at B = 8)
+        # WHEN: the pair that feeds the deepest block matters on the LAST steps of a sequence only -- the state forgets what earlier
+        # steps rounded.  Same tool, `steps` section (T = 5; pair at the last 0 / 1 / 2 / 3 / 4 / 5 steps): 35 / 20 / 14 / 11 / 12 / 11
+        # flips.  A caller that knows how many steps follow says so (ImageReconstructor.update_reconstruction_sequence sets
+        # steps_left); the pair is then used on the last pair_steps() steps (default 3, ESS_MIXED_PAIR_STEPS=all: every step).  A step
+        # whose position is unknown (streaming inference: every step's output is consumed) always uses it.
+        hilo_all = k.pairs and os.environ.get('ESS_MIXED_HILO', 'deepest') == 'all'
+        left, keep = self.steps_left, pair_steps()
+        paired = hilo_all or left is None or keep is None or left < keep
         blocks, states = [], []
         for i, encoder in enumerate(self.encoders):
-            x, state = encoder(x, prev_states[i], lean=lean_state, x_conv=x_conv0 if i == 0 else None)
+            deep = k.pairs and (hilo_all or i == self.num_encoders - 1)
+            x, state = encoder(x, prev_states[i], lean=no_fp32, x_conv=x_conv0 if i == 0 else None, hilo_out=deep and not lean,
+                               x_hilo=deep and paired, kind=k)
             blocks.append(x)
             states.append(state)
         if lean:
@@ -194,56 +222,13 @@ class UNetRecurrent(BaseUNet):
             latent[2 ** (i + 1)] = b
         if encoder_only:
             return None, states, latent
+        for b in blocks:  # the tail stages BF16_C8 copies: attach them where a block left a half copy only
+            h = copies.of(b).h16
+            if h is not None and copies.of(b).c8 is None:
+                copies.attach(b, c8=hip.f16_c8_to_bf16_c8(h[0], hilo=h[1]))
         return self._tail(x, blocks, head), states, latent
 
 
-def _unet_recurrent_forward_mixed(self, x, prev_states, encoder_only, lean, lean_state):
-    """One time step of the 'mixed' configuration (hip.set_compute('mixed')): head, stride-2 convolutions and ConvLSTM gates on IEEE-half
-    operands (submodules._convlayer_forward_mixed / _convlstm_forward_mixed), the tail that only feeds the reconstruction (residual
-    blocks, upsample-conv decoders, prediction layer: reference unet.py:165-181) on the bf16 kernels from BF16_C8 copies of the hidden
-    states.  lean: the step only advances the state; lean_state: its hidden states need no fp32 form (then the last step's copies of h'
-    -- the event latents -- leave as [hi | lo] half pairs)."""
-    import os
-    # WHERE the [hi | lo] pairs are used: by default at the DEEPEST level only -- the convolution feeding its ConvLSTM and, on the last
-    # step, its h' (the 1/8-resolution latent).  tools/hybrid_rounding_ablation.py (levels / latents sections): on the trained fixture
-    # that level alone carries the effect (10 flips of 307200 against 13 with pairs at all three levels, 37 with none; latents: 11 with
-    # the 1/8 latent alone, 13 with all, 40 with none); ESS_MIXED_HILO=all puts pairs at every level (+ 0.3 ms per time step at B = 8)
-    hilo_all = os.environ.get('ESS_MIXED_HILO', 'deepest') == 'all'
-    # WHEN: the pair that feeds the deepest ConvLSTM matters on the LAST steps of a sequence only -- the state forgets what earlier steps
-    # rounded.  Same tool, `steps` section (T = 5; pair at the last 0 / 1 / 2 / 3 / 4 / 5 steps): 35 / 20 / 14 / 11 / 12 / 11 flips.  A caller
-    # that knows how many steps follow says so (ImageReconstructor.update_reconstruction_sequence sets steps_left); the pair is then
-    # used on the last pair_steps() steps (default 3, ESS_MIXED_PAIR_STEPS=all: every step).  A step whose position is unknown
-    # (streaming inference: every step's output is consumed) always uses it.
-    left, keep = self.steps_left, pair_steps()
-    paired = left is None or keep is None or left < keep
-    final = not lean
-    no_fp32 = lean or (lean_state and self.use_upsample_conv and self.norm != 'IN')
-    head = self.head.forward_mixed(x, want_fp32=final)
-    if prev_states is None:
-        prev_states = [None] * self.num_encoders
-    blocks, states = [], []
-    x = head
-    for i, encoder in enumerate(self.encoders):
-        deep = hilo_all or i == self.num_encoders - 1
-        x, state = encoder.forward_mixed(x, prev_states[i], lean=no_fp32, hilo_out=final and deep, x_hilo=deep and (paired or hilo_all))
-        blocks.append(x)
-        states.append(state)
-    if lean:
-        return None, states, None
-    latent = {1: head}
-    for i, b in enumerate(blocks):
-        latent[2 ** (i + 1)] = b
-    if encoder_only:
-        return None, states, latent
-    for b in blocks:  # the tail stages BF16_C8 copies
-        h = copies.of(b).h16
-        if h is not None and copies.of(b).c8 is None:
-            copies.attach(b, c8=hip.f16_c8_to_bf16_c8(h[0], hilo=h[1]))
-    return self._tail(x, blocks, head), states, latent
-
-
-UNetRecurrent._forward_mixed = _unet_recurrent_forward_mixed
-UNetRecurrent.steps_left = None  # (time steps that follow the next forward() in its sequence; None: unknown)
 _PAIR_STEPS = os.environ.get('ESS_MIXED_PAIR_STEPS', '3')
 
 

@@ -325,7 +325,7 @@ def test_conv_lstm_f16_edges(H, case):
     for act in (H.LSTM_H_HILO, 0):
         spec = H.conv_spec(N, Hh, W, 2 * C, C1, 4 * hid, 3, 1, 1, epi=H.EPI_LSTM, hidden=hid, compute=H.COMPUTE_F16)
         if act and (hid % (8 * (spec.plan.cout_tile // 32)) or spec.plan.cout_tile < 64):
-            continue  # (no pair copy of h' on such tiles: the product writes one half copy there, submodules._convlstm_forward_mixed)
+            continue  # (no pair copy of h' on such tiles: the product writes one half copy there, submodules.ConvLSTM.forward)
         spec = H.conv_spec(N, Hh, W, 2 * C, C1, 4 * hid, 3, 1, 1, epi=H.EPI_LSTM, hidden=hid, act=act, compute=H.COMPUTE_F16)
         cell = H.f32_c8_empty(N, hid, Hh, W, 'cuda').fill_(NAN)
         new16 = H.f16_blocks_empty(N, hid, Hh, W, 'cuda', hilo=act == H.LSTM_H_HILO).fill_(NAN)
@@ -346,7 +346,7 @@ def test_conv_lstm_f16_edges(H, case):
 
 @pytest.mark.parametrize('case', REC_CASES)
 def test_conv_gru_f16_edges(H, case):
-    """One ConvGRU step on half operands, as the mixed configuration runs it (submodules._convgru_forward_mixed): GRU_UR writes the update
+    """One ConvGRU step on half operands, as the mixed configuration runs it (submodules.ConvGRU.forward, half kind): GRU_UR writes the update
     gate u (IEEE half with GRU_U_F16 where whole gate tiles allow, else fp32) and the half copy of r * h; GRU_OUT reads them and writes
     h' = h (1 - u) + u tanh(o) (fp32 channel-blocked + half copy, or a [hi | lo] copy with GRU_H_HILO).  Each launch against fp64 on the
     operands it reads: u within its storage rounding of sigma (2^-11 u / fp32) + 2e-6, r * h within 2^-11 |r h| + 2e-6, h' within 3e-5

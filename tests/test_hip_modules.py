@@ -873,3 +873,42 @@ def test_sequence_call_matches_per_slice_loop(shape):
                         assert torch.equal(lat3[k], lat1n[k]), k
         finally:
             hip.set_compute('fp32')
+
+
+@pytest.mark.parametrize('mode', ['bf16', 'mixed'])
+def test_convgru_lean_steps_leave_the_last_step_unchanged(mode):
+    """ConvGRU encoder, B = 2, T = 3, 2 bins, 48 x 64: a sequence whose steps t < T-1 are lean (no fp32 state, channel-blocked fp32 h and
+    an IEEE-half update gate between the two launches) against one that writes every fp32 tensor -- the last step's four latents and
+    three states bit for bit (the fp32 tensors where written, else the 16-bit copies as integers).  ConvGRU.forward claims it ("the
+    same bits either way"); the full-size properties test checks it for the ConvLSTM only."""
+    from ess_amd import copies, hip
+    B, T, C, H, W = 2, 3, 2, 48, 64
+    cfg = O.e2vid_config(num_bins=C, recurrent_block_type='convgru')
+    sd = O.synth_state_dict(O.e2vid_param_shapes(cfg), 67)
+    ev, _, _, _ = O.synth_batch(B, T, C, H, W, 6, seed=37)
+    ev = ev.cuda()
+
+    def bits(t):
+        r = copies.of(t)
+        if not r.unwritten:
+            return t.clone()
+        copy = r.c8 if r.c8 is not None else r.h16[0]
+        return copy.view(torch.int16).clone()
+
+    def run(lean):
+        model = _e2vid(cfg, sd)
+        states = None
+        with torch.no_grad():
+            for t in range(T):
+                skip = lean and t < T - 1
+                _, states, lat = model(ev[:, t * C:(t + 1) * C].contiguous(), states, encoder_only=skip, lean=skip)
+        return [bits(lat[k]) for k in (1, 2, 4, 8)] + [bits(s) for s in states]
+
+    hip.set_compute(mode)
+    try:
+        full, lean = run(False), run(True)
+    finally:
+        hip.set_compute('fp32')
+    assert len(full) == len(lean) == 7
+    for i, (a, b) in enumerate(zip(full, lean)):
+        assert a.dtype == b.dtype and torch.equal(a, b), i
