@@ -851,12 +851,33 @@ __global__ __launch_bounds__(THREADS) void wgrad_reduce_kernel(const float* ws, 
   }
 }
 
-struct WPlan {
-  int twl, tiles_x, tiles_y, ntiles, IH, IW, plx, co_tiles, ci_tiles, nsplit, lds_bytes;
-  bool taps_variant, bf16, bf16_1x1, small1x1, small1x1_mfma, c8, small1x1_c8;
-  int pyv, pxv, rv;
-  size_t slab_floats;
+// Which kernel runs: one value per kernel that can be launched (the <KS, S> of the fp32 tile kernel follows from the descriptor).
+enum WRoute {
+  W_F32_TILE,       // wgrad_f32_kernel<KS, S>: fp32 tensors, k in {1, 3}, stride in {1, 2}
+  W_TAPS7,          // wgrad_taps_kernel<7, 2>: the single-channel 7x7 stem (fp32 X; dY fp32 or BF16_C8)
+  W_BF16_K3,        // wgrad_bf16_k3s1_kernel: fp32 tensors staged as bf16, 3x3 / stride 1 / pad 1, any geometry
+  W_BF16_K3_FAST,   // wgrad_bf16_k3s1_fast_kernel<9>: the same on rows of 8 pixels
+  W_BF16_K1,        // wgrad_bf16_k3s1_fast_kernel<1>: 1x1 / stride 1 as the centre tap of that kernel
+  W_C8_K3,          // wgrad_c8_ws_kernel: both tensors BF16_C8, 3x3 / stride 1 / pad 1, LDS-DMA staging (also one parity phase of a stride 2)
+  W_C8_K1,          // wgrad_c8_kernel<1, TWL>: both tensors BF16_C8, 1x1 / pad 0, register staging
+  W_SMALL1X1,       // wgrad_small1x1_kernel: 1x1 heads (C_out <= 16, C_in <= 64)
+  W_SMALL1X1_MFMA,  // wgrad_small1x1_mfma_kernel: ... C_in <= 32 on whole 64-pixel groups (16-byte aligned tensors: see wgrad_run)
+  W_SMALL1X1_C8X    // wgrad_small1x1_c8_kernel: the 1x1 head with a BF16_C8 X and an fp32 dY
 };
+// the kernels with 128-pixel tiles, 512-register waves and the (pyv, pxv, rv) tile pitches of WgradBArgs
+inline bool tile128(WRoute r) { return r == W_BF16_K3 || r == W_BF16_K3_FAST || r == W_BF16_K1 || r == W_C8_K3 || r == W_C8_K1; }
+
+struct WPlan {
+  EssConvDesc d;    // what the kernels run: compute type resolved, one parity phase in place of a stride-2 BF16_C8 3x3
+  WRoute route;
+  bool phases;      // four launches of d, one per pixel-parity phase of the input
+  WgradBArgs args;  // the kernel arguments but for the tensors, the slabs and the phase (wfill)
+  unsigned grid;    // (C_out tile, C_in tile) pairs x nsplit
+  int lds_bytes;    // dynamic LDS of the launch, all stages (W_C8_K3 ignores it: wgrad_c8_k3_launch has the kernel's own constant)
+  size_t ws_bytes;  // nsplit slabs of [taps][C_out][C_in] + [C_out] floats
+};
+
+inline bool k3s1p1(const EssConvDesc* d) { return d->ksize == 3 && d->stride == 1 && d->pad == 1; }
 
 // 3x3 / stride 2 / pad 1 on BF16_C8 tensors (ResNet layer2/3 entry convs): four launches of the stride-1 LDS-DMA kernel, one per
 // pixel-parity phase X_pq[y][x] = X[2y+p][2x+q] of the input (gathered by the DMA: WgradArgs.ps) -- tap (ky, kx) of the stride-2
@@ -868,8 +889,19 @@ inline bool s2_phases(const EssConvDesc* d) {
 }
 inline EssConvDesc s2_phase_desc(const EssConvDesc* d) {
   EssConvDesc p = *d;
-  p.stride = 1; p.H_in = d->H_out; p.W_in = d->W_out;
+  p.stride = 1; p.H_in = d->H_out; p.W_in = d->W_out; p.mode1 = ESS_SRC_DIRECT;
   return p;
+}
+inline TapMap s2_phase_taps(int p, int q) {
+  TapMap tm{};
+  tm.mapped = 1;
+  for (int t = 0; t < 9; ++t) {
+    const int kyp = t / 3, kxp = t % 3;
+    const int ky = p == 0 ? (kyp == 1 ? 1 : -1) : (kyp == 0 ? 0 : kyp == 1 ? 2 : -1);
+    const int kx = q == 0 ? (kxp == 1 ? 1 : -1) : (kxp == 0 ? 0 : kxp == 1 ? 2 : -1);
+    tm.m[t] = (signed char)((ky < 0 || kx < 0) ? -1 : ky * 3 + kx);
+  }
+  return tm;
 }
 
 int wvalidate(const EssConvDesc* d) {
@@ -889,8 +921,7 @@ int wvalidate(const EssConvDesc* d) {
     ESS_CHECK_ARG(d->C1 == 0 || d->fmt1 == d->fmt0, "wgrad: both sources of a concat must use the same format");
     ESS_CHECK_ARG(d->C1 == 0 || (d->C0 % 8) == 0, "wgrad: the first BF16_C8 source of a concat must have a multiple of 8 channels");
     if (xc8 && dc8)
-      ESS_CHECK_ARG((d->ksize == 3 && d->stride == 1 && d->pad == 1) || (d->ksize == 1 && d->pad == 0 && d->mode0 == ESS_SRC_DIRECT && d->C1 == 0) ||
-                        s2_phases(d),
+      ESS_CHECK_ARG(k3s1p1(d) || (d->ksize == 1 && d->pad == 0 && d->mode0 == ESS_SRC_DIRECT && d->C1 == 0) || s2_phases(d),
                     "wgrad(BF16_C8): 3x3 / stride 1 / pad 1, 3x3 / stride 2 / pad 1 on even extents (one direct source) and 1x1 / pad 0 convolutions only");
     else if (xc8)
       ESS_CHECK_ARG(d->ksize == 1 && d->stride == 1 && d->pad == 0 && d->C1 == 0 && d->mode0 == ESS_SRC_DIRECT && d->C_out <= 32 && cin <= 32,
@@ -901,335 +932,283 @@ int wvalidate(const EssConvDesc* d) {
   return ESS_OK;
 }
 
-WPlan wplan(const EssConvDesc* d) {
-  WPlan w{};
-  const int cin = d->C0 + d->C1, KS = d->ksize, S = d->stride;
-  w.taps_variant = (cin == 1 && KS == 7);
-  w.small1x1 = KS == 1 && S == 1 && d->pad == 0 && d->C1 == 0 && d->mode0 == ESS_SRC_DIRECT && d->C_out <= 16 && cin <= 64;
-  w.bf16 = d->compute == ESS_COMPUTE_BF16 && KS == 3 && S == 1 && d->pad == 1;
+// The kernel of a validated descriptor whose compute type is resolved (FP32 / BF16) and whose stride-2 phases are taken apart.
+WRoute wroute(const EssConvDesc* d) {
+  const int cin = d->C0 + d->C1, KS = d->ksize;
+  const bool xc8 = d->fmt0 == ESS_FMT_BF16_C8, dc8 = d->fmt_out == ESS_FMT_BF16_C8;
+  if (xc8 && dc8) return KS == 3 ? W_C8_K3 : W_C8_K1;
+  if (xc8) return W_SMALL1X1_C8X;
+  const bool k1s1p0 = KS == 1 && d->stride == 1 && d->pad == 0;
+  if (k1s1p0 && d->C1 == 0 && d->mode0 == ESS_SRC_DIRECT && d->C_out <= 16 && cin <= 64)
+    return cin <= 32 && ((d->H_out * d->W_out) % 64) == 0 ? W_SMALL1X1_MFMA : W_SMALL1X1;
+  // rows of 8 pixels, direct / nearest-upsampled sources: what the fast fp32-staged kernel needs
+  const bool rows8 = (d->W_in % 8) == 0 && (d->W_out % 8) == 0 && d->mode0 != ESS_SRC_ZERO_UP2 && d->mode1 != ESS_SRC_ZERO_UP2;
+  if (d->compute == ESS_COMPUTE_BF16 && k3s1p1(d)) return rows8 ? W_BF16_K3_FAST : W_BF16_K3;
   // 1x1 / stride 1 with at least a tile of channels: the centre tap of the same kernel (the fp32 tile kernel ran the ResNet
-  // downsample gradients at 10 TFLOP/s); needs the fast variant's geometry (rows of 8 pixels, direct / upsampled sources)
-  w.bf16_1x1 = d->compute == ESS_COMPUTE_BF16 && KS == 1 && S == 1 && d->pad == 0 && !w.small1x1 && (d->W_in % 8) == 0 &&
-               (d->W_out % 8) == 0 && d->mode0 != ESS_SRC_ZERO_UP2 && d->mode1 != ESS_SRC_ZERO_UP2;
-  w.bf16 = w.bf16 || w.bf16_1x1;
-  w.c8 = d->fmt0 == ESS_FMT_BF16_C8 && d->fmt_out == ESS_FMT_BF16_C8;  // both operands BF16_C8: conv_wgrad_c8.hip
-  w.small1x1_c8 = d->fmt0 == ESS_FMT_BF16_C8 && d->fmt_out != ESS_FMT_BF16_C8;
-  if (w.c8) { w.bf16 = true; w.bf16_1x1 = KS == 1; w.small1x1 = false; }
-  if (w.small1x1_c8) { w.bf16 = w.bf16_1x1 = false; w.small1x1 = true; }
-  const int npx = w.bf16 ? 128 : 64;
+  // downsample gradients at 10 TFLOP/s)
+  if (d->compute == ESS_COMPUTE_BF16 && k1s1p0 && rows8) return W_BF16_K1;
+  if (cin == 1 && KS == 7) return W_TAPS7;
+  return W_F32_TILE;
+}
+
+// ESS_COMPUTE_BF16X3: 3x3 / stride 1 / pad 1 on the fp32-staged bf16 kernels with split operands, everything else exact fp32
+WPlan wplan(const EssConvDesc* desc) {
+  WPlan w{};
+  w.d = *desc;
+  if (desc->compute == ESS_COMPUTE_BF16X3) {
+    w.args.split = k3s1p1(desc);
+    w.d.compute = w.args.split ? ESS_COMPUTE_BF16 : ESS_COMPUTE_FP32;
+  }
+  w.phases = s2_phases(&w.d);
+  if (w.phases) w.d = s2_phase_desc(&w.d);
+  const EssConvDesc* d = &w.d;
+  w.route = wroute(d);
+  WgradArgs& a = w.args.w;
+  a.N = d->N; a.Hin = d->H_in; a.Win = d->W_in; a.C0 = d->C0; a.C1 = d->C1; a.mode0 = d->mode0; a.mode1 = d->mode1;
+  a.Cout = d->C_out; a.Hout = d->H_out; a.Wout = d->W_out;
+  // the 1x1 forms of the 3x3 kernels keep their tile geometry: the X tile starts one row / column before the output tile
+  a.pad = (w.route == W_BF16_K1 || w.route == W_C8_K1) ? 1 : d->pad;
+  a.dy_c8 = d->fmt_out == ESS_FMT_BF16_C8;
+  a.ps = w.phases;
+  const int cin = d->C0 + d->C1, KS = d->ksize, S = d->stride;
+  const bool wide = tile128(w.route);
+  const int npx = wide ? 128 : 64;
   // pixel tile of 64 (fp32) / 128 (bf16): pick the width that wastes the least
   double best = 1e300;
-  for (int twl = 5; twl >= (w.bf16 ? 4 : 3); --twl) {
+  for (int twl = 5; twl >= (wide ? 4 : 3); --twl) {
     const int tw = 1 << twl, th = npx >> twl;
     const double c = (double)ceil_div(d->W_out, tw) * tw * ceil_div(d->H_out, th) * th + 1e-3 * (5 - twl);
-    if (c < best) { best = c; w.twl = twl; }
+    if (c < best) { best = c; a.twl = twl; }
   }
-  if (w.c8 && KS == 3) w.twl = 4;  // the LDS-DMA kernel: 16 x 8 tiles (least halo, two workgroups per CU)
-  const int tw = 1 << w.twl, th = npx >> w.twl;
-  w.tiles_x = ceil_div(d->W_out, tw); w.tiles_y = ceil_div(d->H_out, th);
-  w.ntiles = d->N * w.tiles_x * w.tiles_y;
-  w.IH = (th - 1) * S + KS; w.IW = (tw - 1) * S + KS;
-  w.plx = (w.IH * w.IW) | 1;
-  w.co_tiles = ceil_div(d->C_out, 64);
-  w.ci_tiles = w.taps_variant ? 1 : ceil_div(cin, 64);
-  w.slab_floats = (size_t)KS * KS * d->C_out * cin + d->C_out;
-  const int pairs = w.co_tiles * w.ci_tiles;
-  // the bf16 kernel runs one workgroup per CU (512-register waves): aim at one full round of the 256 CUs
-  int ns = w.bf16 ? ceil_div(256, pairs) : ceil_div(2048, pairs);
-  if (ns > w.ntiles) ns = w.ntiles;
-  const size_t cap = ((size_t)64 << 20) / (w.slab_floats * 4);
+  if (w.route == W_C8_K3) a.twl = 4;  // the LDS-DMA kernel: 16 x 8 tiles (least halo, two workgroups per CU)
+  const int tw = 1 << a.twl, th = npx >> a.twl;
+  a.tiles_x = ceil_div(d->W_out, tw); a.tiles_y = ceil_div(d->H_out, th);
+  a.ntiles = d->N * a.tiles_x * a.tiles_y;
+  a.IH = (th - 1) * S + KS; a.IW = (tw - 1) * S + KS;
+  a.plx = (a.IH * a.IW) | 1;
+  a.ci_tiles = w.route == W_TAPS7 ? 1 : ceil_div(cin, 64);
+  a.npairs = ceil_div(d->C_out, 64) * a.ci_tiles;
+  const size_t slab_floats = (size_t)KS * KS * d->C_out * cin + d->C_out;
+  // the bf16 kernels run one workgroup per CU (512-register waves): aim at one full round of the 256 CUs
+  int ns = wide ? ceil_div(256, a.npairs) : ceil_div(2048, a.npairs);
+  if (ns > a.ntiles) ns = a.ntiles;
+  const size_t cap = ((size_t)64 << 20) / (slab_floats * 4);
   if ((size_t)ns > cap) ns = (int)(cap ? cap : 1);
   if (ns < 1) ns = 1;
-  w.nsplit = ns;
-  if (w.small1x1) {
+  if (w.route == W_SMALL1X1 || w.route == W_SMALL1X1_C8X) {  // (W_SMALL1X1_C8X: 33 KB of LDS per workgroup, four per CU)
     const int chunks = d->N * ceil_div(d->H_out * d->W_out, 128);
-    w.nsplit = chunks < 1024 ? chunks : 1024;
-    w.small1x1_mfma = cin <= 32 && ((d->H_out * d->W_out) % 64) == 0;
-    if (w.small1x1_c8) {
-      w.small1x1_mfma = false;
-      if (w.nsplit > 1024) w.nsplit = 1024;  // (33 KB of LDS per workgroup: four per CU)
-    }
-    if (w.small1x1_mfma) {  // one slab per workgroup of 4 waves, two workgroups per CU
-      const int groups = d->N * (d->H_out * d->W_out / 64);
-      w.nsplit = groups < 4 * 512 ? ceil_div(groups, 4) : 512;
-    }
+    ns = chunks < 1024 ? chunks : 1024;
+  } else if (w.route == W_SMALL1X1_MFMA) {  // one slab per workgroup of 4 waves, two workgroups per CU
+    const int groups = d->N * (d->H_out * d->W_out / 64);
+    ns = groups < 4 * 512 ? ceil_div(groups, 4) : 512;
   }
-  w.lds_bytes = (64 * 65 + (w.taps_variant ? w.IH * w.IW : 64 * w.plx)) * 4;
-  if (w.bf16) {
-    w.rv = tw / 8 + 2;
-    w.pyv = (th * tw / 8) | 1;
-    w.pxv = ((th + 2) * w.rv) | 1;
-    w.lds_bytes = 64 * (w.pyv + w.pxv) * 16;
+  a.nsplit = ns;
+  w.grid = (unsigned)(a.npairs * ns);
+  w.ws_bytes = (size_t)ns * slab_floats * 4;
+  w.lds_bytes = (64 * 65 + (w.route == W_TAPS7 ? a.IH * a.IW : 64 * a.plx)) * 4;
+  if (wide) {
+    w.args.rv = tw / 8 + 2;
+    w.args.pyv = (th * tw / 8) | 1;
+    w.args.pxv = ((th + 2) * w.args.rv) | 1;
+    w.lds_bytes = 64 * (w.args.pyv + w.args.pxv) * 16 * (w.route == W_BF16_K3 ? 1 : 2);  // (two LDS stages, but for the general fp32-staged kernel)
   }
   return w;
 }
 
-template <typename K>
-int raise_lds(K kernel, int bytes) {
-  if (bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) {
-      ess_set_error("hipFuncSetAttribute(%d B LDS): %s", bytes, hipGetErrorString(e));
-      return ESS_ELAUNCH;
-    }
-  }
+// One (X, dY) set of a call: x1 is the second source of a concat
+struct WgradSet { const void* x0; const void* x1; const void* dy; };
+
+// Kernel arguments of one launch: set `s`, parity phase `ph` (w.phases only), the bias slabs behind the weight slabs when `bias`
+WgradBArgs wfill(const WPlan& w, const WgradSet& s, void* workspace, bool bias, int ph) {
+  WgradBArgs b = w.args;
+  WgradArgs& a = b.w;
+  a.src0 = (const float*)s.x0; a.src1 = a.C1 ? (const float*)s.x1 : nullptr; a.dy = (const float*)s.dy;
+  a.ws = (float*)workspace;
+  a.ws_b = bias ? a.ws + (size_t)a.nsplit * w.d.ksize * w.d.ksize * a.Cout * (a.C0 + a.C1) : nullptr;
+  a.pp = ph >> 1; a.pq = ph & 1;
+  return b;
+}
+
+template <typename K, typename... A>
+int wgo(K kernel, dim3 grid, int lds_bytes, hipStream_t st, const A&... args) {
+  const int rc = wgrad_raise_lds(kernel, lds_bytes);
+  if (rc) return rc;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), lds_bytes, st, args...);
   return ESS_OK;
 }
 
-}  // namespace
-
-// ESS_COMPUTE_BF16X3: 3x3 / stride 1 / pad 1 on the fp32-staged bf16 kernels with split operands, everything else exact fp32
-static EssConvDesc wresolve(const EssConvDesc* d, bool* split) {
-  EssConvDesc r = *d;
-  *split = false;
-  if (d->compute == ESS_COMPUTE_BF16X3) {
-    *split = d->ksize == 3 && d->stride == 1 && d->pad == 1;
-    r.compute = *split ? ESS_COMPUTE_BF16 : ESS_COMPUTE_FP32;
+int wlaunch(const WPlan& w, WRoute route, const WgradBArgs& b, hipStream_t st) {
+  const EssConvDesc& d = w.d;
+  const dim3 grid(w.grid);
+  const int px = d.H_out * d.W_out, nsplit = b.w.nsplit;
+  int rc = ESS_OK;
+  switch (route) {
+    case W_F32_TILE: {  // (wvalidate: k is 1 or 3, the stride 1 or 2)
+      const auto kernel = d.ksize == 3 ? (d.stride == 1 ? wgrad_f32_kernel<3, 1> : wgrad_f32_kernel<3, 2>)
+                                       : (d.stride == 1 ? wgrad_f32_kernel<1, 1> : wgrad_f32_kernel<1, 2>);
+      rc = wgo(kernel, grid, w.lds_bytes, st, b.w);
+      break;
+    }
+    case W_TAPS7: rc = wgo(wgrad_taps_kernel<7, 2>, grid, w.lds_bytes, st, b.w); break;
+    case W_BF16_K3: rc = wgo(wgrad_bf16_k3s1_kernel, grid, w.lds_bytes, st, b); break;
+    case W_BF16_K3_FAST: rc = wgo(wgrad_bf16_k3s1_fast_kernel<9>, grid, w.lds_bytes, st, b); break;
+    case W_BF16_K1: rc = wgo(wgrad_bf16_k3s1_fast_kernel<1>, grid, w.lds_bytes, st, b); break;
+    case W_C8_K3: rc = wgrad_c8_k3_launch(b, grid, st); break;
+    case W_C8_K1: rc = wgrad_c8_k1_launch(b, d.stride, w.lds_bytes, grid, st); break;
+    case W_SMALL1X1: rc = wgo(wgrad_small1x1_kernel, dim3(nsplit), 0, st, b.w, ceil_div(px, 128), d.N * ceil_div(px, 128)); break;
+    case W_SMALL1X1_MFMA: rc = wgo(wgrad_small1x1_mfma_kernel, dim3(nsplit), 0, st, b.w, px / 64, d.N * (px / 64)); break;
+    case W_SMALL1X1_C8X: rc = wgrad_small1x1_c8_launch(b.w, nsplit, st); break;
   }
-  return r;
+  return rc ? rc : ess_launch_status("conv2d_wgrad");
 }
 
-// Split operands through the BF16_C8 kernel (conv_wgrad_c8.hip: LDS-DMA staging, twice the rate of the fp32-staged kernels): X and
-// dY are split ONCE into hi / lo BF16_C8 copies (workspace), then three accumulating launches -- (dY_hi, X_hi), (dY_hi, X_lo),
-// (dY_lo, X_hi).  Needs whole 8-channel blocks where the BF16_C8 kernels do; otherwise the fp32-staged kernels make three passes.
-int ess_split_bf16_c8_internal(const float* x, void* hi, void* lo, int N, int C, int H, int W, hipStream_t st);
-static bool split_via_c8(const EssConvDesc* d) {
-  static const bool on = [] { const char* e = getenv("ESS_X3_WGRAD_C8"); return !(e && e[0] == '0'); }();
-  return on && d->compute == ESS_COMPUTE_BF16X3 && d->ksize == 3 && d->stride == 1 && d->pad == 1 && (d->C1 == 0 || (d->C0 % 8) == 0) &&
-         d->mode0 != ESS_SRC_ZERO_UP2 && d->mode1 != ESS_SRC_ZERO_UP2 && (d->C1 == 0 || d->mode1 == ESS_SRC_DIRECT);
+// dw (+)= the ordered sum of the slabs; tm: identity (TapMap{}) or the taps a parity phase lands in
+int wreduce(const WPlan& w, const WgradArgs& a, float* dw, float* db, int accumulate, const TapMap& tm, hipStream_t st) {
+  const int T = w.d.ksize * w.d.ksize, CC = w.d.C_out * (w.d.C0 + w.d.C1);
+  const int nblk_w = ceil_div(CC, 64), nblk_b = a.ws_b ? ceil_div(w.d.C_out, 64) : 0;
+  if (T == 9 && CC >= 32768)
+    hipLaunchKernelGGL((wgrad_reduce_kernel<64, 9, 256>), dim3((unsigned)(nblk_w + nblk_b)), dim3(256), 0, st, a.ws, a.ws_b, dw, db, a.nsplit, T,
+                       CC, w.d.C_out, nblk_w, accumulate, tm);
+  else
+    hipLaunchKernelGGL((wgrad_reduce_kernel<64, 1, 1024>), dim3((unsigned)(nblk_w + nblk_b), (unsigned)T), dim3(1024), 0, st, a.ws, a.ws_b, dw, db,
+                       a.nsplit, T, CC, w.d.C_out, nblk_w, accumulate, tm);
+  return ess_launch_status("conv2d_wgrad_reduce");
 }
-static EssConvDesc c8_desc(const EssConvDesc* d) {
+
+bool env_on(const char* name) {  // a diagnostic switch: on unless the variable starts with '0'
+  const char* e = getenv(name);
+  return !(e && e[0] == '0');
+}
+
+// Split operands (ESS_COMPUTE_BF16X3) through the BF16_C8 kernel (conv_wgrad_c8.hip: LDS-DMA staging, twice the rate of the fp32-staged
+// kernels): X and dY are split ONCE into hi / lo BF16_C8 copies (workspace), then the sets (dY_hi, X_hi), (dY_hi, X_lo), (dY_lo, X_hi).
+// Needs whole 8-channel blocks where the BF16_C8 kernels do; otherwise the fp32-staged kernels contract every tile three times.
+bool split_via_c8(const EssConvDesc* d) {
+  static const bool on = env_on("ESS_X3_WGRAD_C8");
+  return on && d->compute == ESS_COMPUTE_BF16X3 && k3s1p1(d) && (d->C1 == 0 || (d->C0 % 8) == 0) && d->mode0 != ESS_SRC_ZERO_UP2 &&
+         d->mode1 != ESS_SRC_ZERO_UP2 && (d->C1 == 0 || d->mode1 == ESS_SRC_DIRECT);
+}
+EssConvDesc c8_desc(const EssConvDesc* d) {
   EssConvDesc c = *d;
   c.compute = ESS_COMPUTE_BF16;
   c.fmt0 = c.fmt1 = c.fmt_out = ESS_FMT_BF16_C8;
   return c;
 }
-static size_t c8_copy_bytes(int N, int C, int H, int W) { return (((size_t)N * ((C + 7) / 8) * H * W * 16) + 255) & ~(size_t)255; }
-struct SplitCopies { size_t x0, x1, dy, total; };
-static SplitCopies split_copies(const EssConvDesc* d) {
-  SplitCopies s{};
+// workspace of a split_via_c8 call: slabs | X0 hi | X0 lo | X1 hi | X1 lo | dY hi | dY lo, each 256-byte aligned
+struct SplitCopy { int C, H, W; size_t bytes; };  // one tensor's hi (and lo) BF16_C8 copy
+struct SplitLayout { size_t slabs, total; SplitCopy t[3]; };  // t: X0, X1 (C = 0 without a second source), dY
+SplitLayout split_layout(const EssConvDesc* d) {
+  const EssConvDesc dc = c8_desc(d);
   const int s0 = d->mode0 != ESS_SRC_DIRECT ? 1 : 0, s1 = d->mode1 != ESS_SRC_DIRECT ? 1 : 0;
-  s.x0 = c8_copy_bytes(d->N, d->C0, d->H_in >> s0, d->W_in >> s0);
-  s.x1 = d->C1 ? c8_copy_bytes(d->N, d->C1, d->H_in >> s1, d->W_in >> s1) : 0;
-  s.dy = c8_copy_bytes(d->N, d->C_out, d->H_out, d->W_out);
-  s.total = 2 * (s.x0 + s.x1 + s.dy);
+  SplitLayout s{(wplan(&dc).ws_bytes + 255) & ~(size_t)255, 0,
+                {{d->C0, d->H_in >> s0, d->W_in >> s0, 0}, {d->C1, d->H_in >> s1, d->W_in >> s1, 0}, {d->C_out, d->H_out, d->W_out, 0}}};
+  s.total = s.slabs;
+  for (SplitCopy& t : s.t) {
+    t.bytes = (((size_t)d->N * ((t.C + 7) / 8) * t.H * t.W * 16) + 255) & ~(size_t)255;
+    s.total += 2 * t.bytes;
+  }
   return s;
 }
 
-// the lo copies of a fused split-operand call, handed to the BF16_C8 3x3 launch of the SAME thread's nested entry (no public
-// signature changes; null outside that nested call)
-struct WgradPasses { int npass, bias_mask; const void* dy[3]; const void* x0[3]; const void* x1[3]; mutable bool used; };  // used: the nested launch took the passes
-static thread_local const WgradPasses* g_passes = nullptr;
+int wgrad_split_via_c8(const EssConvDesc* d, const WgradSet& s, float* dw, float* db, int accumulate, void* workspace, size_t workspace_bytes,
+                       hipStream_t st);
+
+// dw (+)= sum over the sets of wgrad(x_q, dy_q), db (+)= sum over the sets in bias_mask of sum(dy_q): validate, plan, fill, launch,
+// reduce.  The LDS-DMA 3x3 kernel takes all sets in ONE launch (it walks the tile list once per set into the same accumulators: one
+// prologue, one slab set, one reduce); every other route makes one accumulating pass per set.
+int wgrad_run(const EssConvDesc* d, int n_sets, const WgradSet* sets, int bias_mask, float* dw, float* db, int accumulate, void* workspace,
+              size_t workspace_bytes, hipStream_t st) {
+  int rc = wvalidate(d);
+  if (rc) return rc;
+  ESS_CHECK_ARG(dw && workspace, "wgrad: null pointer");
+  uintptr_t bits = 0;
+  for (int q = 0; q < n_sets; ++q) {
+    ESS_CHECK_ARG(sets[q].x0 && sets[q].dy, "wgrad: null pointer");
+    ESS_CHECK_ARG(d->C1 == 0 || sets[q].x1, "wgrad: second source missing");
+    bits |= (uintptr_t)sets[q].x0 | (uintptr_t)sets[q].dy | (d->C1 ? (uintptr_t)sets[q].x1 : 0);
+  }
+  if (split_via_c8(d)) {  // (every set makes its own hi / lo copies)
+    for (int q = 0; q < n_sets; ++q)
+      if ((rc = wgrad_split_via_c8(d, sets[q], dw, ((bias_mask >> q) & 1) ? db : nullptr, q ? 1 : accumulate, workspace, workspace_bytes, st))) return rc;
+    return ESS_OK;
+  }
+  const WPlan w = wplan(d);
+  ESS_CHECK_ARG(workspace_bytes >= w.ws_bytes, "wgrad: workspace too small");
+  ESS_CHECK_ARG(w.lds_bytes <= 160 * 1024, "wgrad: LDS tile %d B too large", w.lds_bytes);
+  if (w.d.fmt0 == ESS_FMT_BF16_C8 || w.d.fmt_out == ESS_FMT_BF16_C8)
+    ESS_CHECK_ARG((bits & 15) == 0, "wgrad: BF16_C8 tensors must be 16-byte aligned");
+  if (w.route == W_TAPS7) {
+    ESS_CHECK_ARG(w.d.stride == 2, "wgrad: 7x7 stem variant is stride 2 only");
+    ESS_CHECK_ARG(!db, "wgrad: the stem variant has no bias gradient");
+  }
+  const bool one_launch = n_sets > 1 && w.route == W_C8_K3 && !w.phases;
+  for (int q = 0; q < (one_launch ? 1 : n_sets); ++q) {
+    // the MFMA form of the small 1x1 loads 16 bytes at a time: tensors that are not so aligned take the scalar form on the same slabs
+    const bool misaligned = (((uintptr_t)sets[q].x0 | (uintptr_t)sets[q].dy) & 15) != 0;
+    const WRoute route = (w.route == W_SMALL1X1_MFMA && misaligned) ? W_SMALL1X1 : w.route;
+    for (int ph = 0; ph < (w.phases ? 4 : 1); ++ph) {
+      const bool bias = db && ph == 0 && (one_launch || ((bias_mask >> q) & 1));
+      WgradBArgs b = wfill(w, sets[q], workspace, bias, ph);
+      if (one_launch) {
+        b.npass = n_sets; b.bias_mask = bias_mask;
+        for (int i = 0; i < n_sets; ++i) { b.p_dy[i] = sets[i].dy; b.p_x0[i] = sets[i].x0; b.p_x1[i] = d->C1 ? sets[i].x1 : nullptr; }
+      }
+      if ((rc = wlaunch(w, route, b, st))) return rc;
+      if ((rc = wreduce(w, b.w, dw, db, (q || accumulate) ? 1 : 0, w.phases ? s2_phase_taps(ph >> 1, ph & 1) : TapMap{}, st))) return rc;
+    }
+  }
+  return ESS_OK;
+}
+
+// d and the tensors are checked (wgrad_run)
+int wgrad_split_via_c8(const EssConvDesc* d, const WgradSet& s, float* dw, float* db, int accumulate, void* workspace,
+                              size_t workspace_bytes, hipStream_t st) {
+  int rc;
+  ESS_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, "wgrad: the workspace must be 256-byte aligned");
+  const SplitLayout sl = split_layout(d);
+  ESS_CHECK_ARG(workspace_bytes >= sl.total, "wgrad: workspace too small");
+  const void* src[3] = {s.x0, s.x1, s.dy};
+  char* hi[3]; char* lo[3];
+  char* p = (char*)workspace + sl.slabs;
+  for (int i = 0; i < 3; ++i) {
+    const SplitCopy& t = sl.t[i];
+    hi[i] = p; lo[i] = p + t.bytes; p += 2 * t.bytes;
+    if (t.C && (rc = ess_split_bf16_c8_internal((const float*)src[i], hi[i], lo[i], d->N, t.C, t.H, t.W, st))) return rc;
+  }
+  const EssConvDesc dc = c8_desc(d);
+  const WgradSet sets[3] = {{hi[0], hi[1], hi[2]}, {lo[0], lo[1], hi[2]}, {hi[0], hi[1], lo[2]}};
+  const int bias_mask = 0b101;  // dY_hi is contracted twice, the bias gradient takes it once
+  // ONE launch for the three sets; ESS_X3_WGRAD_FUSED=0: three accumulating calls, which write and reduce the slabs three times
+  static const bool fused = env_on("ESS_X3_WGRAD_FUSED");
+  if (fused) return wgrad_run(&dc, 3, sets, bias_mask, dw, db, accumulate, workspace, sl.slabs, st);
+  for (int q = 0; q < 3; ++q)
+    if ((rc = wgrad_run(&dc, 1, &sets[q], (bias_mask >> q) & 1, dw, db, q ? 1 : accumulate, workspace, sl.slabs, st))) return rc;
+  return ESS_OK;
+}
+
+}  // namespace
 
 extern "C" size_t ess_conv2d_wgrad_workspace(const EssConvDesc* d) {
   if (wvalidate(d)) return 0;
-  if (split_via_c8(d)) {
-    const EssConvDesc dc = c8_desc(d);
-    const size_t slabs = (ess_conv2d_wgrad_workspace(&dc) + 255) & ~(size_t)255;
-    return slabs ? slabs + split_copies(d).total : 0;
-  }
-  bool osplit;
-  const EssConvDesc dres = wresolve(d, &osplit);
-  d = &dres;
-  const EssConvDesc dp = s2_phases(d) ? s2_phase_desc(d) : *d;
-  const WPlan w = wplan(&dp);
-  return (size_t)w.nsplit * w.slab_floats * 4;
+  return split_via_c8(d) ? split_layout(d).total : wplan(d).ws_bytes;
 }
 
-extern "C" int ess_conv2d_wgrad(const EssConvDesc* d, const void* src0_, const void* src1_, const void* dy_, float* dw,
-                                float* db, int accumulate, void* workspace, size_t workspace_bytes, ess_stream_t stream) {
-  const float* src0 = (const float*)src0_; const float* src1 = (const float*)src1_; const float* dy = (const float*)dy_;
-  int rc = wvalidate(d);
-  if (rc) return rc;
-  if (split_via_c8(d)) {
-    ESS_CHECK_ARG(src0 && dy && dw && workspace, "wgrad: null pointer");
-    ESS_CHECK_ARG(d->C1 == 0 || src1, "wgrad: second source missing");
-    ESS_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, "wgrad: the workspace must be 256-byte aligned");
-    const EssConvDesc dc = c8_desc(d);
-    const size_t slabs = (ess_conv2d_wgrad_workspace(&dc) + 255) & ~(size_t)255;
-    const SplitCopies sc = split_copies(d);
-    ESS_CHECK_ARG(slabs && workspace_bytes >= slabs + sc.total, "wgrad: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)workspace + slabs;
-    char* x0h = base; char* x0l = x0h + sc.x0;
-    char* x1h = x0l + sc.x0; char* x1l = x1h + sc.x1;
-    char* dyh = x1l + sc.x1; char* dyl = dyh + sc.dy;
-    const int s0 = d->mode0 != ESS_SRC_DIRECT ? 1 : 0, s1 = d->mode1 != ESS_SRC_DIRECT ? 1 : 0;
-    if ((rc = ess_split_bf16_c8_internal(src0, x0h, x0l, d->N, d->C0, d->H_in >> s0, d->W_in >> s0, st))) return rc;
-    if (d->C1 && (rc = ess_split_bf16_c8_internal(src1, x1h, x1l, d->N, d->C1, d->H_in >> s1, d->W_in >> s1, st))) return rc;
-    if ((rc = ess_split_bf16_c8_internal(dy, dyh, dyl, d->N, d->C_out, d->H_out, d->W_out, st))) return rc;
-    // ONE launch of the LDS-DMA kernel walking the tile list three times (WgradBArgs::x3): one slab set, one reduce (round 5; the
-    // three accumulating launches of round 4 wrote and reduced the slabs three times: ESS_X3_WGRAD_FUSED=0 brings them back)
-    static const bool fused = [] { const char* e = getenv("ESS_X3_WGRAD_FUSED"); return !(e && e[0] == '0'); }();
-    if (fused) {
-      const void* x1h_ = d->C1 ? x1h : nullptr; const void* x1l_ = d->C1 ? x1l : nullptr;
-      const WgradPasses ps{3, 0b101, {dyh, dyh, dyl}, {x0h, x0l, x0h}, {x1h_, x1l_, x1h_}, false};
-      g_passes = &ps;
-      rc = ess_conv2d_wgrad(&dc, x0h, x1h_, dyh, dw, db, accumulate, workspace, slabs, stream);
-      g_passes = nullptr;
-      if (rc || ps.used) return rc;
-      // (the plan did not take the LDS-DMA kernel: the first set is done, the other two follow as accumulating launches)
-      if ((rc = ess_conv2d_wgrad(&dc, x0l, x1l_, dyh, dw, nullptr, 1, workspace, slabs, stream))) return rc;
-      return ess_conv2d_wgrad(&dc, x0h, x1h_, dyl, dw, db, 1, workspace, slabs, stream);
-    }
-    if ((rc = ess_conv2d_wgrad(&dc, x0h, d->C1 ? x1h : nullptr, dyh, dw, db, accumulate, workspace, slabs, stream))) return rc;
-    if ((rc = ess_conv2d_wgrad(&dc, x0l, d->C1 ? x1l : nullptr, dyh, dw, nullptr, 1, workspace, slabs, stream))) return rc;
-    return ess_conv2d_wgrad(&dc, x0h, d->C1 ? x1h : nullptr, dyl, dw, db, 1, workspace, slabs, stream);
-  }
-  bool osplit;
-  const EssConvDesc dres = wresolve(d, &osplit);
-  d = &dres;
-  ESS_CHECK_ARG(src0 && dy && dw && workspace, "wgrad: null pointer");
-  ESS_CHECK_ARG(d->C1 == 0 || src1, "wgrad: second source missing");
-  if (s2_phases(d)) {
-    const EssConvDesc dp = s2_phase_desc(d);
-    const WPlan w = wplan(&dp);
-    ESS_CHECK_ARG(workspace_bytes >= (size_t)w.nsplit * w.slab_floats * 4, "wgrad: workspace too small");
-    ESS_CHECK_ARG((((uintptr_t)src0 | (uintptr_t)dy) & 15) == 0, "wgrad: BF16_C8 tensors must be 16-byte aligned");
-    const int cin = d->C0, CC = d->C_out * cin;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)(w.co_tiles * w.ci_tiles * w.nsplit));
-    for (int ph = 0; ph < 4; ++ph) {
-      const int p = ph >> 1, q = ph & 1;
-      WgradBArgs bb{};
-      WgradArgs& a = bb.w;
-      a.src0 = src0; a.src1 = nullptr; a.dy = dy; a.ws = (float*)workspace;
-      a.ws_b = (db && ph == 0) ? a.ws + (size_t)w.nsplit * 9 * CC : nullptr;
-      a.N = d->N; a.Hin = dp.H_in; a.Win = dp.W_in; a.C0 = d->C0; a.C1 = 0; a.mode0 = ESS_SRC_DIRECT; a.mode1 = ESS_SRC_DIRECT;
-      a.Cout = d->C_out; a.Hout = d->H_out; a.Wout = d->W_out; a.pad = 1;
-      a.twl = w.twl; a.tiles_x = w.tiles_x; a.tiles_y = w.tiles_y; a.ntiles = w.ntiles;
-      a.IH = w.IH; a.IW = w.IW; a.plx = w.plx; a.ci_tiles = w.ci_tiles; a.npairs = w.co_tiles * w.ci_tiles; a.nsplit = w.nsplit;
-      a.dy_c8 = 1; a.ps = 1; a.pp = p; a.pq = q;
-      bb.pyv = w.pyv; bb.pxv = w.pxv; bb.rv = w.rv;
-        if ((rc = wgrad_c8_launch(bb, 9, 1, 2 * w.lds_bytes, grid, st))) return rc;
-      TapMap tm{};
-      tm.mapped = 1;
-      for (int t = 0; t < 9; ++t) {
-        const int kyp = t / 3, kxp = t % 3;
-        const int ky = p == 0 ? (kyp == 1 ? 1 : -1) : (kyp == 0 ? 0 : kyp == 1 ? 2 : -1);
-        const int kx = q == 0 ? (kxp == 1 ? 1 : -1) : (kxp == 0 ? 0 : kxp == 1 ? 2 : -1);
-        tm.m[t] = (signed char)((ky < 0 || kx < 0) ? -1 : ky * 3 + kx);
-      }
-      const int nblk_w = ceil_div(CC, 64), nblk_b = a.ws_b ? ceil_div(d->C_out, 64) : 0;
-      if (CC >= 32768)
-        hipLaunchKernelGGL((wgrad_reduce_kernel<64, 9, 256>), dim3((unsigned)(nblk_w + nblk_b)), dim3(256), 0, st, a.ws, a.ws_b, dw, db, w.nsplit, 9,
-                           CC, d->C_out, nblk_w, accumulate, tm);
-      else
-        hipLaunchKernelGGL((wgrad_reduce_kernel<64, 1, 1024>), dim3((unsigned)(nblk_w + nblk_b), 9u), dim3(1024), 0, st, a.ws, a.ws_b, dw, db,
-                           w.nsplit, 9, CC, d->C_out, nblk_w, accumulate, tm);
-    }
-    return ess_launch_status("conv2d_wgrad(3x3 stride 2 by phases)");
-  }
-  const WPlan w = wplan(d);
-  ESS_CHECK_ARG(workspace_bytes >= (size_t)w.nsplit * w.slab_floats * 4, "wgrad: workspace too small");
-  ESS_CHECK_ARG(w.lds_bytes <= 160 * 1024, "wgrad: LDS tile %d B too large", w.lds_bytes);
-  const int cin = d->C0 + d->C1, T = d->ksize * d->ksize;
-  WgradArgs a{};
-  a.src0 = src0; a.src1 = src1; a.dy = dy;
-  a.ws = (float*)workspace;
-  a.ws_b = db ? a.ws + (size_t)w.nsplit * T * d->C_out * cin : nullptr;
-  a.N = d->N; a.Hin = d->H_in; a.Win = d->W_in; a.C0 = d->C0; a.C1 = d->C1; a.mode0 = d->mode0; a.mode1 = d->mode1;
-  a.Cout = d->C_out; a.Hout = d->H_out; a.Wout = d->W_out; a.pad = d->pad;
-  a.twl = w.twl; a.tiles_x = w.tiles_x; a.tiles_y = w.tiles_y; a.ntiles = w.ntiles;
-  a.IH = w.IH; a.IW = w.IW; a.plx = w.plx; a.ci_tiles = w.ci_tiles; a.npairs = w.co_tiles * w.ci_tiles; a.nsplit = w.nsplit;
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)(w.co_tiles * w.ci_tiles * w.nsplit));
-#define ESS_WG(KS_, S_)                                                                               \
-  do {                                                                                                \
-    if ((rc = raise_lds(wgrad_f32_kernel<KS_, S_>, w.lds_bytes))) return rc;                         \
-    hipLaunchKernelGGL((wgrad_f32_kernel<KS_, S_>), grid, dim3(256), w.lds_bytes, st, a);             \
-  } while (0)
-  a.dy_c8 = d->fmt_out == ESS_FMT_BF16_C8;
-  if (d->fmt0 == ESS_FMT_BF16_C8 || a.dy_c8)
-    ESS_CHECK_ARG(((((uintptr_t)src0) | ((uintptr_t)src1) | ((uintptr_t)dy)) & 15) == 0, "wgrad: BF16_C8 tensors must be 16-byte aligned");
-  if (w.small1x1_c8) {
-    if ((rc = wgrad_small1x1_c8_launch(a, w.nsplit, st))) return rc;
-  } else if (w.c8) {
-    WgradBArgs bb{};
-    bb.w = a; bb.pyv = w.pyv; bb.pxv = w.pxv; bb.rv = w.rv;
-    if (w.bf16_1x1) bb.w.pad = 1;  // tile geometry of the 3x3 kernel: the X tile starts one row / column before the output tile
-    if (g_passes) {
-      ESS_CHECK_ARG(!w.bf16_1x1 && d->stride == 1, "wgrad: several (dY, X) sets in one launch exist for the 3x3 / stride-1 LDS-DMA kernel only");
-      bb.npass = g_passes->npass; bb.bias_mask = g_passes->bias_mask;
-      g_passes->used = true;
-      for (int q = 0; q < 3; ++q) { bb.p_dy[q] = g_passes->dy[q]; bb.p_x0[q] = g_passes->x0[q]; bb.p_x1[q] = g_passes->x1[q]; }
-    }
-    if ((rc = wgrad_c8_launch(bb, w.bf16_1x1 ? 1 : 9, d->stride, 2 * w.lds_bytes, grid, st))) return rc;
-  } else if (w.small1x1 && w.small1x1_mfma && ((((uintptr_t)a.src0) | ((uintptr_t)a.dy)) & 15) == 0) {
-    const int per_img = d->H_out * d->W_out / 64;
-    hipLaunchKernelGGL(wgrad_small1x1_mfma_kernel, dim3(w.nsplit), dim3(256), 0, st, a, per_img, d->N * per_img);
-  } else if (w.small1x1) {
-    const int per_img = ceil_div(d->H_out * d->W_out, 128);
-    hipLaunchKernelGGL(wgrad_small1x1_kernel, dim3(w.nsplit), dim3(256), 0, st, a, per_img, d->N * per_img);
-  } else if (w.bf16) {
-    WgradBArgs bb{};
-    bb.w = a; bb.pyv = w.pyv; bb.pxv = w.pxv; bb.rv = w.rv;
-    bb.split = osplit ? 1 : 0;
-    const bool fast = (d->W_in % 8) == 0 && (d->W_out % 8) == 0 && d->mode0 != ESS_SRC_ZERO_UP2 && d->mode1 != ESS_SRC_ZERO_UP2;
-    if (w.bf16_1x1) {
-      bb.w.pad = 1;  // tile geometry of the 3x3 kernel: the X tile starts one row / column before the output tile
-      if ((rc = raise_lds(wgrad_bf16_k3s1_fast_kernel<1>, 2 * w.lds_bytes))) return rc;
-      hipLaunchKernelGGL(wgrad_bf16_k3s1_fast_kernel<1>, grid, dim3(256), 2 * w.lds_bytes, st, bb);
-    } else if (fast) {
-      if ((rc = raise_lds(wgrad_bf16_k3s1_fast_kernel<9>, 2 * w.lds_bytes))) return rc;  // two LDS stages
-      hipLaunchKernelGGL(wgrad_bf16_k3s1_fast_kernel<9>, grid, dim3(256), 2 * w.lds_bytes, st, bb);
-    } else {
-      if ((rc = raise_lds(wgrad_bf16_k3s1_kernel, w.lds_bytes))) return rc;
-      hipLaunchKernelGGL(wgrad_bf16_k3s1_kernel, grid, dim3(256), w.lds_bytes, st, bb);
-    }
-  } else if (w.taps_variant) {
-    ESS_CHECK_ARG(d->stride == 2, "wgrad: 7x7 stem variant is stride 2 only");
-    if ((rc = raise_lds(wgrad_taps_kernel<7, 2>, w.lds_bytes))) return rc;
-    hipLaunchKernelGGL((wgrad_taps_kernel<7, 2>), grid, dim3(256), w.lds_bytes, st, a);
-    // the taps variant has no bias path
-    a.ws_b = nullptr;
-  } else if (d->ksize == 3 && d->stride == 1) ESS_WG(3, 1);
-  else if (d->ksize == 3 && d->stride == 2) ESS_WG(3, 2);
-  else if (d->ksize == 1 && d->stride == 1) ESS_WG(1, 1);
-  else ESS_WG(1, 2);
-#undef ESS_WG
-  rc = ess_launch_status("conv2d_wgrad");
-  if (rc) return rc;
-  ESS_CHECK_ARG(!(w.taps_variant && db), "wgrad: the stem variant has no bias gradient");
-  const int CC = d->C_out * cin;
-  const bool wide = T == 9 && CC >= 32768;
-  const int E = 64;
-  const int nblk_w = ceil_div(CC, E), nblk_b = (db && a.ws_b) ? ceil_div(d->C_out, E) : 0;
-  if (wide)
-    hipLaunchKernelGGL((wgrad_reduce_kernel<64, 9, 256>), dim3((unsigned)(nblk_w + nblk_b)), dim3(256), 0, st, a.ws, a.ws_b, dw, db, w.nsplit, T,
-                       CC, d->C_out, nblk_w, accumulate, TapMap{});
-  else
-    hipLaunchKernelGGL((wgrad_reduce_kernel<64, 1, 1024>), dim3((unsigned)(nblk_w + nblk_b), (unsigned)T), dim3(1024), 0, st, a.ws, a.ws_b, dw, db,
-                       w.nsplit, T, CC, d->C_out, nblk_w, accumulate, TapMap{});
-  return ess_launch_status("conv2d_wgrad_reduce");
+extern "C" int ess_conv2d_wgrad(const EssConvDesc* d, const void* src0, const void* src1, const void* dy, float* dw, float* db,
+                                int accumulate, void* workspace, size_t workspace_bytes, ess_stream_t stream) {
+  const WgradSet s{src0, src1, dy};
+  return wgrad_run(d, 1, &s, 1, dw, db, accumulate, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
-
-// Two (or three) (dY, X) sets of the SAME convolution into one weight gradient: dw (+)= sum_s wgrad(X_s, dY_s).  BF16_C8 3x3 / stride 1
-// / pad 1 (the LDS-DMA kernel): ONE launch walks the tile list once per set -- one prologue, one slab set, one reduce --; any other
-// geometry: one accumulating call per set.  The decoder's two weight-gradient passes of a UDA step use it (functional.py, deferred
-// weight gradients).
+// Two (or three) (dY, X) sets of the SAME convolution into one weight gradient: the decoder's two weight-gradient passes of a UDA step
+// use it (functional.py, deferred weight gradients).
 extern "C" int ess_conv2d_wgrad_sets(const EssConvDesc* d, int32_t n_sets, const void* const* src0, const void* const* src1,
                                      const void* const* dy, float* dw, float* db, int32_t accumulate, void* workspace,
                                      size_t workspace_bytes, ess_stream_t stream) {
   ESS_CHECK_ARG(d && src0 && dy && n_sets >= 1 && n_sets <= 3, "wgrad_sets: 1 to 3 sets");
-  for (int q = 0; q < n_sets; ++q) ESS_CHECK_ARG(src0[q] && dy[q] && (d->C1 == 0 || (src1 && src1[q])), "wgrad_sets: null tensor in set %d", q);
-  const bool one_launch = n_sets > 1 && d->compute == ESS_COMPUTE_BF16 && d->fmt0 == ESS_FMT_BF16_C8 && d->fmt_out == ESS_FMT_BF16_C8 &&
-                          d->ksize == 3 && d->stride == 1 && d->pad == 1 && !g_passes;
-  if (one_launch) {
-    WgradPasses ps{n_sets, (1 << n_sets) - 1, {}, {}, {}, false};
-    for (int q = 0; q < n_sets; ++q) { ps.dy[q] = dy[q]; ps.x0[q] = src0[q]; ps.x1[q] = d->C1 ? src1[q] : nullptr; }
-    g_passes = &ps;
-    int rc = ess_conv2d_wgrad(d, src0[0], d->C1 ? src1[0] : nullptr, dy[0], dw, db, accumulate, workspace, workspace_bytes, stream);
-    g_passes = nullptr;
-    if (rc || ps.used) return rc;
-    for (int q = 1; q < n_sets; ++q)  // (the plan did not take the LDS-DMA kernel: set 0 is done, the others accumulate)
-      if ((rc = ess_conv2d_wgrad(d, src0[q], d->C1 ? src1[q] : nullptr, dy[q], dw, db, 1, workspace, workspace_bytes, stream))) return rc;
-    return ESS_OK;
-  }
+  WgradSet sets[3];
   for (int q = 0; q < n_sets; ++q) {
-    const int rc = ess_conv2d_wgrad(d, src0[q], d->C1 ? src1[q] : nullptr, dy[q], dw, db, q ? 1 : accumulate, workspace, workspace_bytes, stream);
-    if (rc) return rc;
+    ESS_CHECK_ARG(src0[q] && dy[q] && (d->C1 == 0 || (src1 && src1[q])), "wgrad_sets: null tensor in set %d", q);
+    sets[q] = WgradSet{src0[q], d->C1 ? src1[q] : nullptr, dy[q]};
   }
-  return ESS_OK;
+  return wgrad_run(d, n_sets, sets, (1 << n_sets) - 1, dw, db, accumulate, workspace, workspace_bytes, (hipStream_t)stream);
 }

@@ -625,23 +625,22 @@ __global__ __launch_bounds__(256) void wgrad_small1x1_c8_kernel(const WgradArgs 
 
 }  // namespace
 
-template <int TAPS, int TWL>
-static void wgrad_c8_go(const WgradBArgs& b, int sx, int lds_bytes, dim3 grid, hipStream_t st) {
-  if (lds_bytes > 64 * 1024) (void)hipFuncSetAttribute((const void*)wgrad_c8_kernel<TAPS, TWL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  hipLaunchKernelGGL((wgrad_c8_kernel<TAPS, TWL>), grid, dim3(256), lds_bytes, st, b, sx);
+int wgrad_c8_k3_launch(const WgradBArgs& b, dim3 grid, hipStream_t st) {
+  if (b.w.twl != 4) { ess_set_error("wgrad(BF16_C8, 3x3): stride 1, 16-wide pixel tiles"); return ESS_EINVAL; }
+  constexpr int NST = 4, lds = NST * DmaGeom::STAGE;
+  static_assert(lds <= 160 * 1024, "LDS stages of the weight-gradient kernel");
+  const int rc = wgrad_raise_lds(wgrad_c8_ws_kernel<NST>, lds);
+  if (rc) return rc;
+  hipLaunchKernelGGL((wgrad_c8_ws_kernel<NST>), grid, dim3(512), lds, st, b);
+  return ess_launch_status("conv2d_wgrad(BF16_C8, LDS-DMA, loader waves)");
 }
 
-int wgrad_c8_launch(const WgradBArgs& b, int taps, int sx, int lds_bytes, dim3 grid, hipStream_t st) {
-  if (taps == 9) {  // 3x3 / stride 1: the LDS-DMA kernel with loader waves (16 x 8 pixel tiles)
-    if (b.w.twl != 4 || sx != 1) { ess_set_error("wgrad(BF16_C8, 3x3): stride 1, 16-wide pixel tiles"); return ESS_EINVAL; }
-    constexpr int NST = 4, lds = NST * DmaGeom::STAGE;
-    static_assert(lds <= 160 * 1024, "LDS stages of the weight-gradient kernel");
-    (void)hipFuncSetAttribute((const void*)wgrad_c8_ws_kernel<NST>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    hipLaunchKernelGGL((wgrad_c8_ws_kernel<NST>), grid, dim3(512), lds, st, b);
-    return ess_launch_status("conv2d_wgrad(BF16_C8, LDS-DMA, loader waves)");
-  }
+int wgrad_c8_k1_launch(const WgradBArgs& b, int sx, int lds_bytes, dim3 grid, hipStream_t st) {
   if (b.w.twl != 4 && b.w.twl != 5) { ess_set_error("wgrad(BF16_C8): pixel tiles are 16 or 32 wide"); return ESS_EINVAL; }
-  if (b.w.twl == 5) wgrad_c8_go<1, 5>(b, sx, lds_bytes, grid, st); else wgrad_c8_go<1, 4>(b, sx, lds_bytes, grid, st);
+  const auto kernel = b.w.twl == 5 ? wgrad_c8_kernel<1, 5> : wgrad_c8_kernel<1, 4>;
+  const int rc = wgrad_raise_lds(kernel, lds_bytes);
+  if (rc) return rc;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), lds_bytes, st, b, sx);
   return ess_launch_status("conv2d_wgrad(BF16_C8)");
 }
 

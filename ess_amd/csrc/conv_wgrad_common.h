@@ -74,6 +74,22 @@ struct WgradBArgs {
   const void* p_x1[3];
 };
 
+// a launch with more than 64 KB of dynamic LDS has to be allowed first
+template <typename K>
+int wgrad_raise_lds(K kernel, int bytes) {
+  if (bytes > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) {
+      ess_set_error("hipFuncSetAttribute(%d B LDS): %s", bytes, hipGetErrorString(e));
+      return ESS_ELAUNCH;
+    }
+  }
+  return ESS_OK;
+}
+
 // conv_wgrad_c8.hip: launchers (the caller has validated the geometry and sized the workspace)
-int wgrad_c8_launch(const WgradBArgs& b, int taps, int sx, int lds_bytes, dim3 grid, hipStream_t st);
+int wgrad_c8_k3_launch(const WgradBArgs& b, dim3 grid, hipStream_t st);                         // 3x3 / stride 1: LDS-DMA, loader waves
+int wgrad_c8_k1_launch(const WgradBArgs& b, int sx, int lds_bytes, dim3 grid, hipStream_t st);  // 1x1 / stride sx: register staging
 int wgrad_small1x1_c8_launch(const WgradArgs& a, int nsplit, hipStream_t st);
+// pointwise.hip: fp32 NCHW -> the hi / lo BF16_C8 copies of split operands
+int ess_split_bf16_c8_internal(const float* x, void* hi, void* lo, int N, int C, int H, int W, hipStream_t st);

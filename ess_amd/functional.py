@@ -511,75 +511,79 @@ class Conv2dFn(torch.autograd.Function):
                 d0 = hip.sumpool2x2(dv0) if (mode0 == hip.SRC_NEAREST_UP2 and not (s == 1 and pool0)) else dv0
             if need1:
                 d1 = hip.sumpool2x2(dv1) if mode1 == hip.SRC_NEAREST_UP2 else dv1
-        s2_1x1 = s == 2 and k == 1 and C1 == 0 and mode0 == hip.SRC_DIRECT and not (Hv & 1) and not (Wv & 1)
-        # 3x3 / stride 2 on BF16_C8 tensors: the library runs the parity phases itself (DMA gather, taps routed by the reduce)
-        s2_lib = s == 2 and k == 3 and p == 1 and c8in and C1 == 0 and mode0 == hip.SRC_DIRECT and not (Hv & 1) and not (Wv & 1)
-        direct = needw and _direct(weight) and (not (s == 2 and k == 3) or s2_lib)
-        if direct:
-            bias = ctx.bias_ref() if ctx.bias_ref is not None else None
-            db_t = bias.grad if (needb and bias is not None and _direct(bias)) else None
-            if needb and db_t is None:
-                direct = False
-        if direct:
-            if s2_1x1 and not c8in:
-                sp1 = hip.conv_spec(N, Hv // 2, Wv // 2, C0, 0, Cout, 1, 1, 0)
-                hip.conv_wgrad(sp1, x0[:, :, ::2, ::2].contiguous(), None, dy, weight.grad, db_t, accumulate=True)
-                done = True
-            else:  # (BF16_C8: the 1x1 kernel samples the stride-2 grid itself)
-                done = True
-                defer = WGRAD_DEFER is not None and c8in and hip.is_c8(dy) and k == 3 and s == 1 and p == 1
-                held = WGRAD_DEFER.pop(id(weight), None) if defer else None
-                if held is not None and held[0].key == spec.key and held[4] is weight:
-                    # the second pass through this weight: both sets in one launch
-                    hip.conv_wgrad_sets(spec, [(held[1], held[2], held[3]), (x0, x1, dy)], weight.grad, db_t, accumulate=True)
-                elif defer and held is None and WGRAD_STASHING:
-                    WGRAD_DEFER[id(weight)] = (spec, x0, x1, dy, weight, db_t)  # (launched with the next pass, or by the flush)
-                    done = False
-                else:
-                    if held is not None:  # (another shape went through this weight first: no common launch)
-                        hip.conv_wgrad(held[0], held[1], held[2], held[3], weight.grad, held[5], accumulate=True)
-                    hip.conv_wgrad(spec, x0, x1, dy, weight.grad, db_t, accumulate=True)
-            dw = db = None
-            if done and GRAD_READY_HOOK is not None:
-                GRAD_READY_HOOK(weight)
-        elif needw or needb:
-            dw = torch.empty_like(weight)
-            db = torch.empty(Cout, dtype=torch.float32, device=dy.device) if ctx.has_bias else None
-            if s == 2 and C1 == 0 and mode0 == hip.SRC_DIRECT and not (Hv & 1) and not (Wv & 1) and not s2_lib and \
-                    ((k == 3 and p == 1) or (k == 1 and p == 0 and not c8in)):
-                _wgrad_stride2_by_phases(x0, dy, dw, db, k)
-            else:
-                hip.conv_wgrad(spec, x0, x1, dy, dw, db)
-            if not needw:
-                dw = None
-            if not needb:
-                db = None
-            # stride-2 3x3 (assembled from parity phases into a temporary): still no AccumulateGrad node -- those keep the
-            # stream they were created on, which breaks a later hipGraph capture of the step
-            if dw is not None and _direct(weight) and (db is None or (ctx.bias_ref is not None and ctx.bias_ref() is not None and _direct(ctx.bias_ref()))):
-                hip.add(weight.grad, dw, out=weight.grad)
-                if db is not None:
-                    hip.add(ctx.bias_ref().grad, db, out=ctx.bias_ref().grad)
-                dw = db = None
-                if GRAD_READY_HOOK is not None:
-                    GRAD_READY_HOOK(weight)
+        if needw or needb:
+            dw, db = _weight_gradient(ctx, x0, x1, weight, dy, needw, needb)
         if d_skip is not None and need0:  # not fusable (or no data-gradient was computed): plain sum
             d0 = d_skip if d0 is None else (hip.add_bf16(d0, d_skip.contiguous()) if c8in else hip.add(d0, d_skip.contiguous()))
         return d0, d1, dw, db, None, None, None, None, None, None, None
 
 
-def _wgrad_stride2_by_phases(x, dy, dw, db, k):
-    """Weight gradient of a stride-2 conv (ResNet 3x3/s2 pad 1 and 1x1/s2) through the stride-1 kernels: the input splits
-    into its 4 pixel-parity phases X_pq[y][x] = X[2y+p][2x+q] (each at output resolution) and tap (ky, kx) of the stride-2
+def _weight_gradient(ctx, x0, x1, weight, dy, needw, needb):
+    """The weight / bias gradient of Conv2dFn.backward: decide the route and the destination, then run.  -> (dw, db) for autograd,
+    None for what went into the leaves' .grad."""
+    spec = ctx.spec
+    (N, Hv, Wv, C0, C1, mode0, mode1, Cout, k, s, p, _, _, _, _, _) = spec.key
+    c8in = hip.is_c8(x0)
+    # route: the library call on (wspec, wx0, x1) -- or, for fp32 tensors, a stride 2 over one direct source with even extents through
+    # the stride-1 kernels: a 1x1 / pad 0 is the stride-1 call on the sub-sampled input, a 3x3 / pad 1 is assembled from the input's
+    # four parity phases.  On BF16_C8 tensors the library does both itself (the 1x1 kernel samples the stride-2 grid, the DMA gathers
+    # the phases).
+    even2 = s == 2 and C1 == 0 and mode0 == hip.SRC_DIRECT and not (Hv & 1) and not (Wv & 1)
+    phases = even2 and k == 3 and p == 1
+    wspec, wx0 = spec, x0
+    if even2 and k == 1 and p == 0 and not c8in:
+        wspec, wx0 = hip.conv_spec(N, Hv // 2, Wv // 2, C0, 0, Cout, 1, 1, 0), x0[:, :, ::2, ::2].contiguous()
+    # destination: straight into the leaves' .grad (views of the optimiser's flat buffer), or temporaries that are then added to
+    # .grad -- or returned to autograd where a leaf has no such .grad.  A 3x3 / stride 2 goes through temporaries unless the library
+    # runs its phases: still without an AccumulateGrad node -- those keep the stream they were created on, which breaks a later
+    # hipGraph capture of the step.
+    bias = ctx.bias_ref() if ctx.bias_ref is not None else None
+    grads = _direct(weight) and (not needb or (bias is not None and _direct(bias)))
+    if needw and grads and not (s == 2 and k == 3 and not (phases and c8in)):
+        db_t = bias.grad if needb else None
+        defer = WGRAD_DEFER is not None and c8in and hip.is_c8(dy) and k == 3 and s == 1 and p == 1
+        held = WGRAD_DEFER.pop(id(weight), None) if defer else None
+        if held is not None and held[0].key == spec.key and held[4] is weight:
+            # the second pass through this weight: both sets in one launch
+            hip.conv_wgrad_sets(spec, [(held[1], held[2], held[3]), (x0, x1, dy)], weight.grad, db_t, accumulate=True)
+        elif defer and held is None and WGRAD_STASHING:
+            WGRAD_DEFER[id(weight)] = (spec, x0, x1, dy, weight, db_t)  # (launched with the next pass, or by the flush)
+            return None, None
+        else:
+            if held is not None:  # (another shape went through this weight first: no common launch)
+                hip.conv_wgrad(held[0], held[1], held[2], held[3], weight.grad, held[5], accumulate=True)
+            hip.conv_wgrad(wspec, wx0, x1, dy, weight.grad, db_t, accumulate=True)
+        if GRAD_READY_HOOK is not None:
+            GRAD_READY_HOOK(weight)
+        return None, None
+    dw = torch.empty_like(weight)
+    db = torch.empty(Cout, dtype=torch.float32, device=dy.device) if ctx.has_bias else None
+    if phases and not c8in:
+        _wgrad_stride2_by_phases(x0, dy, dw, db)
+    else:
+        hip.conv_wgrad(wspec, wx0, x1, dy, dw, db)
+    if not needw:
+        dw = None
+    if not needb:
+        db = None
+    if dw is not None and grads:
+        hip.add(weight.grad, dw, out=weight.grad)
+        if db is not None:
+            hip.add(bias.grad, db, out=bias.grad)
+        dw = db = None
+        if GRAD_READY_HOOK is not None:
+            GRAD_READY_HOOK(weight)
+    return dw, db
+
+
+def _wgrad_stride2_by_phases(x, dy, dw, db):
+    """Weight gradient of a 3x3 / stride-2 / pad-1 conv (ResNet) through the stride-1 kernels: the input splits into its 4
+    pixel-parity phases X_pq[y][x] = X[2y+p][2x+q] (each at output resolution) and tap (ky, kx) of the stride-2
     filter is tap (ky', kx') of a stride-1 3x3 correlation of dY with one phase:  p = 0 if ky == 1 else 1,
     ky' = 0 if ky == 0 else 1 (same in x).  Exact; the direct stride-2 tile kernel stages 5x more input than it uses."""
     N, C, H, W = x.shape[0], _channels(x), x.shape[2], x.shape[3]
     Cout = _channels(dy)
     Ho, Wo = H // 2, W // 2
-    if k == 1:
-        spec = hip.conv_spec(N, Ho, Wo, C, 0, Cout, 1, 1, 0)
-        hip.conv_wgrad(spec, x[:, :, ::2, ::2].contiguous(), None, dy, dw, db)
-        return
     spec = hip.conv_spec(N, Ho, Wo, C, 0, Cout, 3, 1, 1)
     tmp = torch.empty_like(dw)
     for p in (0, 1):

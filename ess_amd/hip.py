@@ -411,8 +411,9 @@ def _mean_loss_ws(device):
     return workspace(LOSS_WORKSPACE_BYTES, device, 'mean_loss')
 
 
-def conv_wgrad(spec, src0, src1, dy, dw, db=None, accumulate=False):
-    """The storage formats are taken from the tensors: BF16_C8 (bfloat16, 5-D) or fp32 NCHW for the sources and for dy."""
+def _wgrad_call(spec, src0, dy):
+    """-> (descriptor, element type of X, element type of dY, workspace) of a weight-gradient call.  The storage formats are taken
+    from the tensors: BF16_C8 (bfloat16, 5-D) or fp32 NCHW for the sources and for dy."""
     sfmt = FMT_BF16_C8 if is_c8(src0) else FMT_F32_NCHW
     dfmt = FMT_BF16_C8 if is_c8(dy) else FMT_F32_NCHW
     desc = spec.desc if (sfmt, dfmt) == (FMT_F32_NCHW, FMT_F32_NCHW) else spec.desc_fmt(sfmt, dfmt)
@@ -421,7 +422,12 @@ def conv_wgrad(spec, src0, src1, dy, dw, db=None, accumulate=False):
     nbytes = lib().ess_conv2d_wgrad_workspace(byref(desc))
     if nbytes == 0:
         raise EssHipError('ess_conv2d_wgrad_workspace: ' + lib().ess_last_error().decode())
-    ws = workspace(nbytes, dy.device, 'wgrad')
+    return desc, sdt, ddt, workspace(nbytes, dy.device, 'wgrad')
+
+
+def conv_wgrad(spec, src0, src1, dy, dw, db=None, accumulate=False):
+    """dw (+)= the weight gradient of `spec` from the sources and dy (fp32 NCHW or BF16_C8 tensors), db (+)= the bias gradient."""
+    desc, sdt, ddt, ws = _wgrad_call(spec, src0, dy)
     _check(lib().ess_conv2d_wgrad(byref(desc), ptr(src0, sdt), ptr(src1, sdt), ptr(dy, ddt), ptr(dw), ptr(db), int(accumulate),
                                   c_void_p(ws.data_ptr()), c_size_t(ws.numel()), stream()), 'ess_conv2d_wgrad')
 
@@ -430,18 +436,10 @@ def conv_wgrad_sets(spec, sets, dw, db=None, accumulate=False):
     """dw (+)= sum over `sets` = [(src0, src1, dy), ...] (1..3 sets of the same convolution, same formats): BF16_C8 3x3 / stride-1 layers
     take ONE launch for all sets (ess_conv2d_wgrad_sets), anything else one accumulating launch per set."""
     src0, _, dy = sets[0]
-    sfmt = FMT_BF16_C8 if is_c8(src0) else FMT_F32_NCHW
-    dfmt = FMT_BF16_C8 if is_c8(dy) else FMT_F32_NCHW
-    desc = spec.desc if (sfmt, dfmt) == (FMT_F32_NCHW, FMT_F32_NCHW) else spec.desc_fmt(sfmt, dfmt)
-    sdt = torch.bfloat16 if sfmt == FMT_BF16_C8 else torch.float32
-    ddt = torch.bfloat16 if dfmt == FMT_BF16_C8 else torch.float32
     for (a0, a1, g) in sets:
         if is_c8(a0) != is_c8(src0) or is_c8(g) != is_c8(dy) or a0.shape != src0.shape or g.shape != dy.shape:
             raise EssHipError('conv_wgrad_sets: the sets must agree in shapes and storage formats')
-    nbytes = lib().ess_conv2d_wgrad_workspace(byref(desc))
-    if nbytes == 0:
-        raise EssHipError('ess_conv2d_wgrad_workspace: ' + lib().ess_last_error().decode())
-    ws = workspace(nbytes, dy.device, 'wgrad')
+    desc, sdt, ddt, ws = _wgrad_call(spec, src0, dy)
     n = len(sets)
     a0s = (c_void_p * n)(*[ptr(t[0], sdt).value for t in sets])
     a1s = (c_void_p * n)(*[(ptr(t[1], sdt).value if t[1] is not None else None) for t in sets])

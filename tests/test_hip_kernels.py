@@ -811,11 +811,15 @@ def test_conv5x5_split_operand_bf16x3(H, case):
     assert errs[H.COMPUTE_BF16X3] < 2e-5 and errs[H.COMPUTE_BF16X3] < errs[H.COMPUTE_BF16] / 50
 
 
-@pytest.mark.parametrize('case', [(2, 64, 0, 64, 24, 40, 0), (2, 32, 32, 96, 16, 24, 1), (1, 24, 0, 40, 17, 30, 0), (2, 128, 0, 128, 12, 24, 0)])
+@pytest.mark.parametrize('case', [(2, 64, 0, 64, 24, 40, 0), (2, 32, 32, 96, 16, 24, 1), (1, 24, 0, 40, 17, 30, 0), (2, 128, 0, 128, 12, 24, 0),
+                                  (2, 20, 16, 64, 16, 24, 0), (1, 12, 8, 40, 17, 30, 0)])
 def test_conv_wgrad_split_operand_bf16x3(H, case):
-    """The weight gradient of a 3x3 / stride-1 / pad-1 convolution with split operands (three passes of the fp32-staged bf16 kernels
-    into the same accumulators: dY_hi X_hi + dY_hi X_lo + dY_lo X_hi; both the 8-pixel-row fast form and the general one) and the
-    bias gradient (sum of dY_hi + dY_lo) against fp64 on the unrounded operands."""
+    """The weight gradient of a 3x3 / stride-1 / pad-1 convolution with split operands (dY_hi X_hi + dY_hi X_lo + dY_lo X_hi into the
+    same accumulators) and the bias gradient (sum of dY_hi + dY_lo) against fp64 on the unrounded operands.  The first four cases
+    (one source, or a concat whose first source is whole 8-channel blocks) split X and dY into hi / lo BF16_C8 copies and run the three
+    sets through one launch of the BF16_C8 LDS-DMA kernel.  The last two are concats whose first source is NOT whole blocks (20 and
+    12 channels): they contract every tile three times on the fp32-staged bf16 kernels -- (2, 20, 16, 64, 16, 24) the 8-pixel-row fast
+    form, (1, 12, 8, 40, 17, 30) the general one (W % 8 != 0)."""
     N, C0, C1, Co, Hh, Ww, m0 = case
     g = torch.Generator().manual_seed(Co + Hh)
     hs, ws_ = (Hh // 2, Ww // 2) if m0 else (Hh, Ww)

@@ -98,6 +98,83 @@ def test_hilo_output_plans_keep_whole_channel_tiles(built_lib):
     assert 320 % fspec.plan.cout_tile != 0
 
 
+_F32, _BF16, _X3 = 0, 1, 2   # ESS_COMPUTE_*
+_NCHW, _C8 = 0, 1            # ESS_FMT_F32_NCHW, ESS_FMT_BF16_C8
+# what runs, compute, X format, dY format, (N, H_in, W_in), (C0, C1, C_out), (k, stride, pad), (mode0, mode1), workspace bytes.
+# One row per weight-gradient kernel and per special case of the plan.  The byte counts were recorded from the library BEFORE kernel
+# choice moved into one function (ess_version 110): they pin nsplit and the slab size of every route, and the split-operand layout.
+_WGRAD_PLANS = [
+    ('fp32 tile 3x3 / stride 1', _F32, _NCHW, _NCHW, (2, 16, 24), (32, 0, 32), (3, 1, 1), (0, 0), 443904),
+    ('fp32 tile 3x3 / stride 2', _F32, _NCHW, _NCHW, (2, 16, 24), (32, 0, 64), (3, 2, 1), (0, 0), 295936),
+    ('fp32 tile 1x1 / stride 1', _F32, _NCHW, _NCHW, (2, 16, 24), (32, 0, 64), (1, 1, 0), (0, 0), 101376),
+    ('fp32 tile 1x1 / stride 2', _F32, _NCHW, _NCHW, (2, 16, 24), (64, 0, 128), (1, 2, 0), (0, 0), 133120),
+    ('fp32 tile, concat with an up-sampled first source', _F32, _NCHW, _NCHW, (2, 16, 24), (64, 32, 32), (3, 1, 1), (1, 0), 1328640),
+    ('fp32 tile, ragged channels, odd extents', _F32, _NCHW, _NCHW, (1, 17, 30), (12, 0, 17), (3, 1, 1), (0, 0), 66708),
+    ('fp32 tile at the 64 MB slab cap', _F32, _NCHW, _NCHW, (2, 64, 96), (512, 0, 512), (3, 1, 1), (0, 0), 66074624),
+    ('7x7 stem', _F32, _NCHW, _NCHW, (2, 32, 48), (1, 0, 64), (7, 2, 3), (0, 0), 153600),
+    ('7x7 stem, BF16_C8 dY', _BF16, _NCHW, _C8, (2, 32, 48), (1, 0, 64), (7, 2, 3), (0, 0), 153600),
+    ('fp32-staged bf16 3x3, general form (W % 8 != 0)', _BF16, _NCHW, _NCHW, (1, 17, 30), (12, 8, 40), (3, 1, 1), (0, 0), 144800),
+    ('fp32-staged bf16 3x3, general form (zero-upsampled source)', _BF16, _NCHW, _NCHW, (2, 16, 24), (32, 0, 32), (3, 1, 1), (2, 0), 295936),
+    ('fp32-staged bf16 3x3, fast form', _BF16, _NCHW, _NCHW, (2, 16, 24), (20, 16, 64), (3, 1, 1), (0, 0), 665600),
+    ('fp32-staged bf16 1x1', _BF16, _NCHW, _NCHW, (2, 16, 24), (64, 0, 128), (1, 1, 0), (0, 0), 266240),
+    ('bf16 1x1 with W % 8 != 0: the fp32 tile kernel', _BF16, _NCHW, _NCHW, (1, 17, 30), (64, 0, 128), (1, 1, 0), (0, 0), 299520),
+    ('BF16_C8 LDS-DMA 3x3', _BF16, _C8, _C8, (2, 16, 24), (32, 0, 64), (3, 1, 1), (0, 0), 591872),
+    ('BF16_C8 3x3, concat with an up-sampled first source', _BF16, _C8, _C8, (2, 16, 24), (64, 32, 64), (3, 1, 1), (1, 0), 1771520),
+    ('BF16_C8 3x3, ragged channels, odd extents', _BF16, _C8, _C8, (1, 17, 30), (12, 0, 40), (3, 1, 1), (0, 0), 104640),
+    ('BF16_C8 3x3, output smaller than one pixel tile', _BF16, _C8, _C8, (1, 5, 7), (32, 0, 32), (3, 1, 1), (0, 0), 36992),
+    ('BF16_C8 3x3, 512 -> 512', _BF16, _C8, _C8, (2, 64, 96), (512, 0, 512), (3, 1, 1), (0, 0), 37756928),
+    ('BF16_C8 3x3 / stride 2 by parity phases', _BF16, _C8, _C8, (2, 16, 24), (64, 0, 128), (3, 2, 1), (0, 0), 590848),
+    ('BF16_C8 1x1 / stride 1', _BF16, _C8, _C8, (2, 16, 24), (64, 0, 128), (1, 1, 0), (0, 0), 266240),
+    ('BF16_C8 1x1 / stride 2', _BF16, _C8, _C8, (2, 16, 24), (64, 0, 128), (1, 2, 0), (0, 0), 66560),
+    ('small 1x1', _F32, _NCHW, _NCHW, (2, 17, 30), (64, 0, 11), (1, 1, 0), (0, 0), 22880),
+    ('small 1x1 at its 1024-slab limit', _F32, _NCHW, _NCHW, (8, 120, 160), (64, 0, 16), (1, 1, 0), (0, 0), 4259840),
+    ('small 1x1 MFMA', _F32, _NCHW, _NCHW, (2, 16, 24), (32, 0, 11), (1, 1, 0), (0, 0), 4356),
+    ('small 1x1 MFMA at its 512-slab limit', _F32, _NCHW, _NCHW, (8, 120, 160), (32, 0, 6), (1, 1, 0), (0, 0), 405504),
+    ('small 1x1, BF16_C8 X and fp32 dY', _BF16, _C8, _NCHW, (2, 16, 24), (32, 0, 11), (1, 1, 0), (0, 0), 8712),
+    ('bf16x3 through BF16_C8 copies', _X3, _NCHW, _NCHW, (2, 16, 24), (32, 0, 64), (3, 1, 1), (0, 0), 886784),
+    ('bf16x3 through BF16_C8 copies, concat with an up-sampled first source', _X3, _NCHW, _NCHW, (2, 16, 24), (64, 32, 64), (3, 1, 1), (1, 0), 2115584),
+    ('bf16x3 on the fp32-staged kernels (C0 % 8 != 0), fast form', _X3, _NCHW, _NCHW, (2, 16, 24), (20, 16, 64), (3, 1, 1), (0, 0), 665600),
+    ('bf16x3 on the fp32-staged kernels (C0 % 8 != 0), general form', _X3, _NCHW, _NCHW, (1, 17, 30), (12, 8, 40), (3, 1, 1), (0, 0), 144800),
+    ('bf16x3 1x1: exact fp32', _X3, _NCHW, _NCHW, (2, 16, 24), (32, 0, 64), (1, 1, 0), (0, 0), 101376),
+    ('bf16x3 3x3 / stride 2: exact fp32', _X3, _NCHW, _NCHW, (2, 16, 24), (32, 0, 64), (3, 2, 1), (0, 0), 295936),
+]
+
+
+def _wgrad_desc(hip, comp, fx, fy, nhw, ch, ksp, modes=(0, 0)):
+    (N, H, W), (C0, C1, Co), (k, s, p) = nhw, ch, ksp
+    return hip.EssConvDesc(N, H, W, C0, C1, modes[0], modes[1], Co, (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1, k, s, p,
+                           hip.EPI_LINEAR, hip.ACT_NONE, 0, 0, comp, fx, fx, fy, _NCHW)
+
+
+@pytest.mark.parametrize('row', _WGRAD_PLANS, ids=[r[0] for r in _WGRAD_PLANS])
+def test_wgrad_plan_workspace_is_pinned(built_lib, row):
+    from ess_amd import hip
+    assert (hip.COMPUTE_FP32, hip.COMPUTE_BF16, hip.COMPUTE_BF16X3, hip.FMT_F32_NCHW, hip.FMT_BF16_C8) == (_F32, _BF16, _X3, _NCHW, _C8)
+    assert os.environ.get('ESS_X3_WGRAD_C8', '1')[:1] != '0'  # (the switch moves bf16x3 to the fp32-staged kernels: other byte counts)
+    what, comp, fx, fy, nhw, ch, ksp, modes, nbytes = row
+    d = _wgrad_desc(hip, comp, fx, fy, nhw, ch, ksp, modes)
+    assert hip.lib().ess_conv2d_wgrad_workspace(ctypes.byref(d)) == nbytes, (what, hip.lib().ess_last_error())
+
+
+@pytest.mark.parametrize('what, args, fragment', [
+    ('a BF16_C8 5x5', (_BF16, _C8, _C8, (2, 16, 24), (32, 0, 32), (5, 1, 2)), 'k=5 with C_in=32 unsupported'),
+    ('a BF16_C8 concat whose first source is not whole blocks', (_BF16, _C8, _C8, (2, 16, 24), (20, 16, 64), (3, 1, 1)),
+     'the first BF16_C8 source of a concat must have a multiple of 8 channels'),
+    ('an F16 compute type', (3, _NCHW, _NCHW, (2, 16, 24), (32, 0, 32), (3, 1, 1)), 'bad compute type'),
+    ('BF16_C8 X with fp32 dY beyond 32 channels', (_BF16, _C8, _NCHW, (2, 16, 24), (64, 0, 11), (1, 1, 0)),
+     'wgrad(BF16_C8 X, fp32 dY): the 1x1 head only'),
+])
+def test_wgrad_plan_refusals(built_lib, what, args, fragment):
+    from ess_amd import hip
+    assert hip.COMPUTE_F16 == 3
+    lib = hip.lib()
+    assert lib.ess_conv2d_wgrad_workspace(ctypes.byref(_wgrad_desc(hip, *args))) == 0, what
+    assert fragment.encode() in lib.ess_last_error(), (what, lib.ess_last_error())
+    # ... and the call itself refuses before it touches a pointer
+    assert lib.ess_conv2d_wgrad(ctypes.byref(_wgrad_desc(hip, *args)), None, None, None, None, None, 0, None, ctypes.c_size_t(0), None) == -22
+    assert fragment.encode() in lib.ess_last_error()
+
+
 def test_product_refuses_cpu_tensors(built_lib):
     from ess_amd import hip
     with pytest.raises(hip.EssHipError, match='no CPU path'):
