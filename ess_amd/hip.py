@@ -75,7 +75,7 @@ EXPORTS = [
     'ess_upsample_bilinear2x_add_c8_from_c8', 'ess_add_bf16', 'ess_event_normalize_slices', 'ess_sum_scalars',
     'ess_label_confusion', 'ess_augment_perspective_filter', 'ess_tuning_set', 'ess_tuning_get', 'ess_conv2d_s2d_preferred',
     'ess_to_f16_c8', 'ess_bf16_c8_to_f16_c8', 'ess_f16_c8_to_bf16_c8', 'ess_instnorm_forward_c8_mixed', 'ess_seg_head',
-    'ess_event_normalize_samples', 'ess_state_carry_masked',
+    'ess_event_normalize_samples', 'ess_state_carry_masked', 'ess_state_carry_indexed',
 ]
 
 
@@ -167,6 +167,7 @@ def lib():
             'ess_seg_head': [P, I, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
             'ess_event_normalize_samples': [P, P, I, I64, P, P, P],
             'ess_state_carry_masked': [P, P, P, I, I, P, P],
+            'ess_state_carry_indexed': [P, P, P, I, I, I, I, P, P, P],
         }
         for name, argtypes in sig.items():
             fn = getattr(L, name)
@@ -671,6 +672,41 @@ CARRY_HOLD, CARRY_TAKE, CARRY_ZERO = 0, 1, 2
 STATE_CARRY_MAX_TENSORS = 16
 
 
+def _carry_tensors(what, dst, src, same_streams):
+    """the tensor checks of the state-carry calls -> (dst list, src list or None, streams of dst, streams of src or None).
+    same_streams: src[i] has dst[i]'s whole shape (the masked call); else its per-stream shape, and all src share one stream count"""
+    dst = list(dst)
+    n = len(dst)
+    if not 1 <= n <= STATE_CARRY_MAX_TENSORS:
+        raise EssHipError(f'{what}: {n} tensors (1..{STATE_CARRY_MAX_TENSORS} per call)')
+    if src is not None:
+        src = list(src)
+        if len(src) != n:
+            raise EssHipError(f'{what}: {len(src)} source tensors for {n} destinations')
+    S = S_src = None
+    for i, d in enumerate(dst):
+        for name, t in (('dst', d),) + ((('src', src[i]),) if src is not None else ()):
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise EssHipError(f'{what}: {name}[{i}] must be a CUDA(HIP) tensor; there is no CPU path')
+            if t.dim() < 1 or t.numel() == 0 or not t.is_contiguous():
+                raise EssHipError(f'{what}: {name}[{i}] must be a non-empty contiguous tensor with the stream index first, got {tuple(t.shape)}')
+        if src is not None and (src[i].shape[0 if same_streams else 1:] != d.shape[0 if same_streams else 1:] or src[i].dtype != d.dtype):
+            raise EssHipError(f'{what}: src[{i}] is {src[i].dtype}{tuple(src[i].shape)}, dst[{i}] is {d.dtype}{tuple(d.shape)}')
+        if S is None:
+            S = d.shape[0]
+        elif d.shape[0] != S:
+            raise EssHipError(f'{what}: dst[{i}] has {d.shape[0]} streams, dst[0] has {S}')
+        if src is not None:
+            if S_src is None:
+                S_src = src[i].shape[0]
+            elif src[i].shape[0] != S_src:
+                raise EssHipError(f'{what}: src[{i}] has {src[i].shape[0]} streams, src[0] has {S_src}')
+        nb = d[0].numel() * d.element_size()
+        if nb % 16:
+            raise EssHipError(f'{what}: dst[{i}] has {nb} bytes per stream, not a multiple of 16')
+    return dst, src, S, S_src
+
+
 class StateCarryTable:
     """The checked host tables of one ess_state_carry_masked call, built once for a fixed set of tensors (a streaming driver's static
     state buffers and the buffers its captured step writes): dst / src lists of equally shaped tensors whose FIRST dimension is the
@@ -678,31 +714,8 @@ class StateCarryTable:
     tensors are kept alive by the table."""
 
     def __init__(self, dst, src=None):
-        what = 'state_carry_masked'
-        dst = list(dst)
+        dst, src, S, _ = _carry_tensors('state_carry_masked', dst, src, True)
         n = len(dst)
-        if not 1 <= n <= STATE_CARRY_MAX_TENSORS:
-            raise EssHipError(f'{what}: {n} tensors (1..{STATE_CARRY_MAX_TENSORS} per call)')
-        if src is not None:
-            src = list(src)
-            if len(src) != n:
-                raise EssHipError(f'{what}: {len(src)} source tensors for {n} destinations')
-        S = None
-        for i, d in enumerate(dst):
-            for name, t in (('dst', d),) + ((('src', src[i]),) if src is not None else ()):
-                if not torch.is_tensor(t) or not t.is_cuda:
-                    raise EssHipError(f'{what}: {name}[{i}] must be a CUDA(HIP) tensor; there is no CPU path')
-                if t.dim() < 1 or t.numel() == 0 or not t.is_contiguous():
-                    raise EssHipError(f'{what}: {name}[{i}] must be a non-empty contiguous tensor with the stream index first, got {tuple(t.shape)}')
-            if src is not None and (src[i].shape != d.shape or src[i].dtype != d.dtype):
-                raise EssHipError(f'{what}: src[{i}] is {src[i].dtype}{tuple(src[i].shape)}, dst[{i}] is {d.dtype}{tuple(d.shape)}')
-            if S is None:
-                S = d.shape[0]
-            elif d.shape[0] != S:
-                raise EssHipError(f'{what}: dst[{i}] has {d.shape[0]} streams, dst[0] has {S}')
-            nb = d[0].numel() * d.element_size()
-            if nb % 16:
-                raise EssHipError(f'{what}: dst[{i}] has {nb} bytes per stream, not a multiple of 16')
         self.n, self.S, self.dst, self.src = n, S, dst, src
         self.bytes_per_sample = [d[0].numel() * d.element_size() for d in dst]
         self._dst = (c_void_p * n)(*[d.data_ptr() for d in dst])
@@ -720,6 +733,52 @@ def state_carry_masked(dst, src, mode):
     CARRY_HOLD: dst[i][s] untouched -- for all (<= 16) tensors in ONE launch, the mode words read on the device (int32 [S]).  src
     None: no stream may TAKE.  A caller that repeats the call on the same tensors keeps a StateCarryTable and calls its run()."""
     StateCarryTable(dst, src).run(mode)
+
+
+CARRY_SRC_ZERO = -1
+STATE_CARRY_MAX_MOVES = 65535
+
+
+class StateMoveTable:
+    """The checked host tables of one ess_state_carry_indexed call, built once for a fixed set of tensors: as StateCarryTable, but dst
+    and src may have DIFFERENT first dimensions (all dst share one, all src share one; src[i] has dst[i]'s dtype and per-stream
+    shape) -- the home state of S streams on one side, the compact batch of a round's active streams on the other.  src None:
+    zero-fills and skips only.  The tensors are kept alive by the table."""
+
+    def __init__(self, dst, src=None):
+        dst, src, S, S_src = _carry_tensors('state_carry_indexed', dst, src, False)
+        n = len(dst)
+        self.n, self.S_dst, self.S_src, self.dst, self.src = n, S, (S_src if src is not None else 1), dst, src
+        self.bytes_per_sample = [d[0].numel() * d.element_size() for d in dst]
+        self._dst = (c_void_p * n)(*[d.data_ptr() for d in dst])
+        self._src = (c_void_p * n)(*[t.data_ptr() for t in src]) if src is not None else None
+        self._bytes = (c_int64 * n)(*self.bytes_per_sample)
+
+    def run(self, dst_index, src_index):
+        """move p: dst record dst_index[p] = src record src_index[p] (CARRY_SRC_ZERO: = 0); a dst_index outside the destination, or
+        any other src_index outside the source, skips the move.  Two contiguous int32 device tensors of equal length."""
+        what = 'state_carry_indexed'
+        for name, t in (('dst_index', dst_index), ('src_index', src_index)):
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise EssHipError(f'{what}: {name} must be a CUDA(HIP) int32 tensor; there is no CPU path')
+            if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+                raise EssHipError(f'{what}: {name} must be a contiguous int32 [n_moves] tensor, got {t.dtype}{tuple(t.shape)}')
+        n_moves = dst_index.shape[0]
+        if src_index.shape[0] != n_moves:
+            raise EssHipError(f'{what}: {n_moves} dst_index entries for {src_index.shape[0]} src_index entries')
+        if not 1 <= n_moves <= STATE_CARRY_MAX_MOVES:
+            raise EssHipError(f'{what}: {n_moves} moves (1..{STATE_CARRY_MAX_MOVES} per call)')
+        _check(lib().ess_state_carry_indexed(self._dst, self._src, self._bytes, self.n, self.S_dst, self.S_src, n_moves,
+                                             ptr(dst_index, torch.int32), ptr(src_index, torch.int32), stream()),
+               'ess_state_carry_indexed')
+
+
+def state_carry_indexed(dst, src, dst_index, src_index):
+    """For move p and every (<= 16) tensor i: dst[i][dst_index[p]] = src[i][src_index[p]], or = 0 where src_index[p] ==
+    CARRY_SRC_ZERO; a move whose dst_index is outside dst's first dimension, or whose src_index is any other word outside src's, is
+    skipped.  ONE launch, the index words read on the device (int32 [n_moves]); dst and src may have different first dimensions.
+    src None: zero-fills and skips only.  A caller that repeats the call on the same tensors keeps a StateMoveTable."""
+    StateMoveTable(dst, src).run(dst_index, src_index)
 
 
 # ------------------------------------------------------------------------------------------ events -> voxel grids

@@ -31,8 +31,14 @@ construction and is steered per stream by mode words in device memory (hip.state
 ZEROED state, not an absent one -- the reference's ConvLSTM / ConvGRU create a zero state when prev_state is None
 (e2vid/model/submodules.py:196-207, 255-262) -- so every window, the first included, runs the ordinary with-state launches and one
 captured graph serves them all.  An idle stream rides along on a zero grid and its new state is discarded: it costs its share of
-the batch's compute (compacting the batch is not done).
+the batch's compute.  With compact=True a round runs only its A active streams, as a batch of the smallest prepared size (bucket)
+>= A: an indexed gather (hip.state_carry_indexed) brings their states from the home [S, ...] buffers into work buffers, restarts and
+padded slots arriving as zeros, the step runs at the bucket's batch size, and an indexed scatter takes the new states home.  The
+plan of such a round is a function on host lists (compact_plan); a round with more active streams than the largest bucket rides
+along as before.
 """
+import collections
+
 import torch
 
 from . import hip
@@ -182,6 +188,53 @@ def stream_modes(pending, active):
     return pre, post, [bool(p and not a) for p, a in zip(pending, active)]
 
 
+def compact_buckets(n_streams, buckets=None):
+    """The batch sizes a compacting segmenter of n_streams prepares -> a tuple, ascending.  Default: the powers of two BELOW
+    n_streams (8 -> (1, 2, 4); 5 -> (1, 2, 4); 3 -> (1, 2); 2 -> (1,); 1 -> ()); a round with more active streams than the largest
+    bucket rides along at n_streams.  An explicit list must be ints, strictly increasing, each in [1, n_streams)."""
+    if buckets is None:
+        out, b = [], 1
+        while b < n_streams:
+            out.append(b)
+            b *= 2
+        return tuple(out)
+    if isinstance(buckets, (str, bytes)) or not hasattr(buckets, '__iter__'):
+        raise hip.EssHipError(f'compact_buckets={buckets!r}: a list of batch sizes is needed')
+    out = list(buckets)
+    for i, b in enumerate(out):
+        if not isinstance(b, int) or isinstance(b, bool) or not 1 <= b < n_streams:
+            raise hip.EssHipError(f'compact_buckets={out!r}: entry {b!r} is not an int in [1, n_streams={n_streams})')
+        if i and b <= out[i - 1]:
+            raise hip.EssHipError(f'compact_buckets={out!r}: the sizes must be strictly increasing')
+    return tuple(out)
+
+
+_compact_buckets = compact_buckets  # (MultiStreamSegmenter's argument of that name shadows the function)
+CompactPlan = collections.namedtuple('CompactPlan', 'bucket rows gather_dst gather_src norm_mode scatter_dst scatter_src pending_after')
+SCATTER_SKIP = -2  # a dst_index outside every destination: hip.state_carry_indexed skips the move (a padded slot)
+
+
+def compact_plan(pending, active, buckets):
+    """One compacted round, from host lists -> None or a CompactPlan.  A = the number of active streams, bucket = the smallest of
+    `buckets` >= A; none: None (the round rides along on all streams).  rows: the active stream numbers, ascending; they take slots
+    0..A-1 of the compact batch, the slots A..bucket-1 are padding.  gather_dst / gather_src steer the indexed carry home -> work in
+    front of the step: slot <- its stream's state, CARRY_SRC_ZERO for a stream that restarts now (pending and active) and for a
+    padded slot.  norm_mode: 1 for a slot with a window, 0 for a padded one (a zero grid).  scatter_dst / scatter_src steer the carry
+    new state -> home behind it: stream <- its slot, SCATTER_SKIP for a padded slot.  pending_after: as stream_modes gives it."""
+    if len(pending) != len(active):
+        raise hip.EssHipError(f'compact_plan: {len(pending)} pending flags for {len(active)} streams')
+    rows = [s for s, a in enumerate(active) if a]
+    A = len(rows)
+    b = next((b for b in buckets if b >= A), None)
+    if b is None:
+        return None
+    pad = b - A
+    return CompactPlan(bucket=b, rows=rows, gather_dst=list(range(b)),
+                       gather_src=[hip.CARRY_SRC_ZERO if pending[s] else s for s in rows] + [hip.CARRY_SRC_ZERO] * pad,
+                       norm_mode=[1] * A + [0] * pad, scatter_dst=rows + [SCATTER_SKIP] * pad, scatter_src=list(range(b)),
+                       pending_after=[bool(p and not a) for p, a in zip(pending, active)])
+
+
 def check_active(active, n_streams):
     """active: None (every stream) or S truth values on the host -> list of S bools"""
     if active is None:
@@ -230,12 +283,24 @@ class MultiStreamSegmenter(GraphedWindowState):
     state is left as it was and their result rows are unspecified.  The state's form depends on the compute configuration, which
     is therefore fixed at construction: update() refuses another one.  graph=True: the round's device work is captured ONCE (n_captures
     stays 1) and every later round -- whatever its mix of advancing, idle and restarting streams -- is two small input copies and one
-    replay.  Other arguments: see StreamingSegmenter."""
+    replay.  Other arguments: see StreamingSegmenter.
+
+    compact=True: a round with A active streams runs as a batch of the smallest bucket >= A (compact_buckets: a list of batch
+    sizes, default the powers of two below n_streams) instead of n_streams; each stream still gets, bit for bit, what it gets
+    without (the two switches above pinned: the batch size now changes from round to round).  The state stays at home in the
+    [S, ...] buffers between rounds; a round gathers the active streams' states into work buffers [largest bucket, ...] (bucket b
+    steps on their first b records), steps there and scatters the new states home: two carry launches, as before.  A round with more
+    active streams than the largest bucket -- every round with all streams active -- is the ride-along round above, unchanged.
+    graph=True: one capture per bucket and one for the ride-along round, each made when first needed or all at once by warm_up();
+    n_captures <= len(buckets) + 1.  The index tables and the compact input are static device buffers the host writes in front of
+    the round; results keep the shape [S, ...], the active rows copied to their streams' rows behind it."""
 
     def __init__(self, encoder, decoder, height, width, options, n_streams, device=None, graph=False, copy=True, palette=None,
-                 want_confidence=False, out_hw=None):
+                 want_confidence=False, out_hw=None, compact=False, compact_buckets=None):
         if not isinstance(n_streams, int) or isinstance(n_streams, bool) or n_streams < 1:
             raise hip.EssHipError(f'n_streams={n_streams!r}: a positive number of streams is needed')
+        self.compact = bool(compact)
+        self.buckets = _compact_buckets(n_streams, compact_buckets) if self.compact else ()
         self.n_streams = n_streams
         self.copy_outputs = bool(copy)
         self.device = device if device is not None else torch.device('cuda:0')
@@ -262,18 +327,23 @@ class MultiStreamSegmenter(GraphedWindowState):
         self._modes = torch.zeros(2, S, dtype=torch.int32, device=self.device)  # [0]: in front of the step, [1]: behind it
         self._pending = [True] * S
         self._build_state()
+        if self.buckets:
+            self._build_compact()
 
     @classmethod
     def from_checkpoints(cls, e2vid_path, ess_checkpoint_path, settings_or_kwargs, n_streams, **kw):
-        """as StreamingSegmenter.from_checkpoints, plus the number of streams"""
+        """as StreamingSegmenter.from_checkpoints, plus the number of streams (compact, compact_buckets: keyword arguments)"""
         encoder, decoder, height, width, options, palette = _models_from_checkpoints(e2vid_path, ess_checkpoint_path, settings_or_kwargs)
         kw.setdefault('palette', palette)
         return cls(encoder, decoder, height, width, options, n_streams, **kw)
 
     # ---- state: static [S, ...] buffers from construction, never None
-    def _step(self, ev):
-        """one encoder-only step of the whole batch from the carried state; the carried state stays the static buffers"""
+    def _step(self, ev, carried=None):
+        """one encoder-only step of the whole batch from the carried state (carried: a compact batch's work state instead); the
+        carried state stays the static buffers"""
         rec = self.rec
+        if carried is not None:
+            rec.last_states_for_each_channel['grayscale'] = carried
         _, states, latent = rec._step(ev, False, False, final_lean=not hip.mixed())
         rec.last_states_for_each_channel['grayscale'] = self._carried
         return states, latent
@@ -299,15 +369,149 @@ class MultiStreamSegmenter(GraphedWindowState):
         self._pre.run(self._modes[0])
         self._modes.zero_()
 
-    def _src_parts(self, states):
-        """the tensors of a step's output state, in the order of the static buffers (self._dst) -- refused when the forms differ"""
+    def _src_parts(self, states, static=None):
+        """the tensors of a step's output state, in the order of the static buffers (self._dst; static: a bucket's work state
+        instead) -- refused when the forms differ"""
         src = []
-        for st, (parts, hilo, shape) in zip(self._static, self._state_tensors(states)):
+        for st, (parts, hilo, shape) in zip(self._static if static is None else static, self._state_tensors(states)):
             sp, s_hilo, s_shape, _ = st
             if [t is None for t in sp.values()] != [t is None for t in parts.values()] or s_hilo != hilo or s_shape != shape:
                 raise hip.EssHipError('streaming: a step left its recurrent state in another form than the static buffers were made for')
             src += [parts[k] for k in _PARTS if sp[k] is not None]
         return src
+
+    # ---- compaction: work buffers [largest bucket, ...] of the home state's per-stream forms; bucket b steps on their first b records
+    def _build_compact(self):
+        """The work buffers, and per bucket: the carried state as leading-slice views of them (a leading slice of a stream-major
+        tensor is contiguous; copies.attach ties the copies to the view, and a lean state's placeholder is made per bucket, so ONE
+        set of buffers serves every bucket), the gather table, the index tables and the slice of the compact input.  Each
+        bucket's forms are checked as _build_state checks the home state's: the with-state step at batch b must leave them."""
+        from . import copies
+        bmax, S = self.buckets[-1], self.n_streams
+        work = [{k: None if t is None else torch.zeros((bmax,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device)
+                 for k, t in st[0].items()} for st in self._static]
+        self.compact_input = torch.zeros(bmax, self.num_bins, self.height, self.width, dtype=torch.float32, device=self.device)
+        self._bucket = {}
+        self._cg = {}  # bucket -> (graph, outputs)
+        for b in self.buckets:
+            static = []
+            for wp, (sp, hilo, shape, _) in zip(work, self._static):
+                parts = {k: None if t is None else t[:b] for k, t in wp.items()}
+                shape_b = (b,) + tuple(shape[1:])
+                sh = parts['h'] if parts['h'] is not None else copies.placeholder(shape_b, self.device)
+                st = (parts, hilo, shape_b, sh)
+                self._attach(st)
+                static.append(st)
+            carried = [st[3] if st[0]['c'] is None else (st[3], st[0]['c']) for st in static]
+            wdst = [st[0][k] for st in static for k in _PARTS if st[0][k] is not None]
+            # rows: gather_dst, gather_src, norm_mode, scatter_dst, scatter_src
+            tab = torch.zeros(5, b, dtype=torch.int32, device=self.device)
+            self._bucket[b] = (static, carried, hip.StateMoveTable(wdst, self._dst), tab)
+            self._idle_tables(b)
+            with torch.no_grad():
+                ev = self.rec.crop.pad(self.compact_input[:b])
+                if not ev.is_contiguous():
+                    ev = ev.contiguous()
+                states, _ = self._step(ev, carried)
+                self._src_parts(states, static)  # (raises when the step at batch b leaves another form)
+
+    def _idle_tables(self, b):
+        """bucket b's tables for a round that touches nothing at home: every slot padded"""
+        plan = compact_plan([False] * self.n_streams, [False] * self.n_streams, (b,))
+        self._write_tables(plan)
+
+    def _write_tables(self, plan):
+        rows = [plan.gather_dst, plan.gather_src, plan.norm_mode, plan.scatter_dst, plan.scatter_src]
+        self._bucket[plan.bucket][3].copy_(torch.tensor(rows, dtype=torch.int32), non_blocking=True)
+
+    def _round_compact(self, b):
+        """the device work of one compacted round at batch b on the static compact input and bucket b's index tables
+        -> (labels, colour, confidence) of the b slots"""
+        rec, pre = self.rec, self.rec.event_preprocessor
+        static, carried, gather, tab = self._bucket[b]
+        with torch.no_grad():
+            gather.run(tab[0], tab[1])  # slot <- its stream's state; restarting streams and padded slots: 0
+            ev = self.compact_input[:b]
+            for x, y in pre.hot_pixel_locations:
+                ev[:, :, y, x] = 0
+            if pre.flip:
+                ev = torch.flip(ev, dims=[2, 3]).contiguous()
+            ev = rec.crop.pad(hip.event_normalize_samples(ev, tab[2]))  # (padded slots: a zero grid)
+            if not ev.is_contiguous():
+                ev = ev.contiguous()
+            states, latent = self._step(ev, carried)
+            src = self._src_parts(states, static)
+            self.last_latent = latent
+            out = self.decoder.predict(latent, out_hw=self.out_hw, window=self.window, palette=self.palette,
+                                       want_confidence=self.want_confidence)
+            hip.StateMoveTable(self._dst, src).run(tab[3], tab[4])  # stream <- its slot's new state; padded slots skipped
+        return out
+
+    def _capture_compact(self, b):
+        """as _capture: the warm-up run leaves the home state untouched because every slot is padded during it"""
+        self._idle_tables(b)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._round_compact(b)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            outputs = self._round_compact(b)
+        self._cg[b] = (g, outputs)
+        self.last_latent = None
+        self.n_captures += 1
+
+    def warm_up(self):
+        """Capture every graph now (the ride-along round's and one per bucket), so that no round in service pays a capture; eager
+        mode: run each bucket once.  The home state and the pending restarts are as they were: the runs have every stream on HOLD
+        / every slot padded."""
+        self._check_compute()
+        if self.use_graph and self._g is None:
+            self._capture()
+        for b in self.buckets:
+            if not self.use_graph:
+                self._idle_tables(b)
+                self._round_compact(b)
+            elif b not in self._cg:
+                self._capture_compact(b)
+        self.last_latent = None
+
+    def _update_compact(self, plan, grids, active, compacted):
+        """one compacted round; grids: [S, ...] (compacted false: the active rows are placed into the compact input here) or the
+        compact grids [bucket, ...] themselves"""
+        b, A = plan.bucket, len(plan.rows)
+        self._pending = plan.pending_after
+        if self.use_graph and b not in self._cg:
+            self._capture_compact(b)
+        self._write_tables(plan)
+        if compacted:
+            self.compact_input[:b].copy_(grids, non_blocking=True)
+        elif A:
+            self.compact_input[:A].copy_(grids[plan.rows], non_blocking=True)
+        if self.use_graph:
+            self._cg[b][0].replay()
+            out = self._cg[b][1]
+        else:
+            out = self._round_compact(b)
+        self.n_windows += 1
+        # the A result rows to their streams' rows of an [S, ...] result; the idle rows stay unspecified
+        fresh = self.copy_outputs or not self.use_graph
+        if fresh or self._cres is None:
+            res = tuple(None if t is None else torch.empty((self.n_streams,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device) for t in out)
+            if not fresh:
+                self._cres = res
+        else:
+            res = self._cres
+        if A:
+            rows = torch.tensor(plan.rows, dtype=torch.int64).to(self.device, non_blocking=True)
+            for r, t in zip(res, out):
+                if t is not None:
+                    r.index_copy_(0, rows, t[:A])
+        return MultiSegmentationResult(*res, valid=active)
+
+    _cres = None
 
     def reset(self, streams=None):
         for s in (range(self.n_streams) if streams is None else streams):
@@ -353,14 +557,20 @@ class MultiStreamSegmenter(GraphedWindowState):
         self.last_latent = None
         self.n_captures += 1
 
+    def _check_compute(self):
+        if hip.compute_name() != self.compute:
+            raise hip.EssHipError(f"MultiStreamSegmenter: built in the '{self.compute}' configuration (its state buffers have that form), "
+                                  f"called in '{hip.compute_name()}'")
+
     def update(self, grids, active=None):
         if not torch.is_tensor(grids):
             raise hip.EssHipError(f'grids must be a tensor [{self.n_streams}, {self.num_bins}, {self.height}, {self.width}], got {type(grids).__name__}')
         check_stream_grids(grids.shape, self.n_streams, self.num_bins, self.height, self.width)
         active = check_active(active, self.n_streams)
-        if hip.compute_name() != self.compute:
-            raise hip.EssHipError(f"MultiStreamSegmenter: built in the '{self.compute}' configuration (its state buffers have that form), "
-                                  f"called in '{hip.compute_name()}'")
+        self._check_compute()
+        plan = compact_plan(self._pending, active, self.buckets) if self.buckets else None
+        if plan is not None:
+            return self._update_compact(plan, grids, active, False)
         pre, post, self._pending = stream_modes(self._pending, active)
         if self.use_graph and self._g is None:
             self._capture()
@@ -377,12 +587,17 @@ class MultiStreamSegmenter(GraphedWindowState):
 
     def update_from_events(self, events):
         """events: S entries, [N, 4] rows (t, x, y, polarity) of the stream's window or None (idle).  All grids are built by ONE
-        hip.voxel_grid_temporal call over the concatenated events; an idle stream is an empty slice (an all-zero grid)."""
+        hip.voxel_grid_temporal call over the concatenated events; an idle stream is an empty slice (an all-zero grid).  A compacted
+        round builds only its bucket's grids: the active streams' in slot order, a padded slot an empty slice."""
         evs, active = check_stream_events(events, self.n_streams)
         if not any(active):
             return self.update(self._in, active)  # (nothing is read of an idle stream's grid)
+        plan = compact_plan(self._pending, active, self.buckets) if self.buckets else None
+        if plan is not None:
+            self._check_compute()
+        slots = evs if plan is None else [evs[s] for s in plan.rows] + [None] * (plan.bucket - len(plan.rows))
         offsets = [0]
-        for e in evs:
+        for e in slots:
             offsets.append(offsets[-1] + (0 if e is None else e.shape[0]))
         ev = torch.cat([e.to(torch.float64) for e in evs if e is not None]).to(self.device)
         t = ev[:, 0].contiguous()
@@ -390,4 +605,6 @@ class MultiStreamSegmenter(GraphedWindowState):
         y = ev[:, 2].to(torch.int32).contiguous()
         p = ev[:, 3].to(torch.float32).contiguous()
         grids = hip.voxel_grid_temporal(x, y, t, p, offsets, self.num_bins, self.height, self.width, separate_pol=False)
-        return self.update(grids, active)
+        if plan is None:
+            return self.update(grids, active)
+        return self._update_compact(plan, grids, active, True)

@@ -358,6 +358,23 @@ int ess_event_normalize_samples(const float* x, float* y, int32_t S, int64_t chu
 enum { ESS_CARRY_HOLD = 0, ESS_CARRY_TAKE = 1, ESS_CARRY_ZERO = 2 };
 int ess_state_carry_masked(void* const* dst, const void* const* src, const int64_t* bytes_per_sample, int32_t n_tensors,
                            int32_t n_samples, const int32_t* mode, ess_stream_t stream);
+/* Its indexed sibling -- PURELY ADDITIVE to ABI 110: record moves between two batches of DIFFERENT sizes (the home state of S
+ * streams and the compact batch of a round's active streams), steered by two index arrays in DEVICE memory, so that one captured
+ * launch serves every set of active streams.  Host tables as above (by value in the kernel arguments).  Tensor i = n_dst_samples
+ * (dst) / n_src_samples (src) contiguous records of bytes_per_sample[i] bytes.  dst_index, src_index: device int32 [n_moves]
+ * (1..65535).  For move p, on every tensor:
+ *   dst_index[p] outside [0, n_dst_samples)   nothing is read or written (a skipped move: a padded slot);
+ *   src_index[p] == ESS_CARRY_SRC_ZERO (-1)   dst record dst_index[p] = 0; no source is read;
+ *   src_index[p] in [0, n_src_samples)        dst record dst_index[p] = src record src_index[p];
+ *   any other src_index[p]                    nothing is read or written.
+ * No index word takes the kernel outside the two ranges.  Two moves with the same valid dst_index are the caller's error (the
+ * content is unspecified, the bounds hold).  src may be NULL (zero-fills and skips only; a valid src_index then moves nothing).
+ * Host checks as above, the disjointness with each side's own record count; ESS_EINVAL with a message otherwise.  A workgroup owns
+ * one (tensor, move, segment), reads its two index words once and moves 16-byte vectors; no host synchronisation.               */
+enum { ESS_CARRY_SRC_ZERO = -1 };
+int ess_state_carry_indexed(void* const* dst, const void* const* src, const int64_t* bytes_per_sample, int32_t n_tensors,
+                            int32_t n_dst_samples, int32_t n_src_samples, int32_t n_moves, const int32_t* dst_index,
+                            const int32_t* src_index, ess_stream_t stream);
 
 /* ---- events -> voxel grid on the device (the step in front of the encoder) --------------------
  * All slices of a batch in one launch: events concatenated structure-of-arrays, slice s = [slice_offsets[s],

@@ -16,7 +16,16 @@ alternating in the same process with the same repetition scheme:
   round_robin  S independent replayed StreamingSegmenters (graph=True) served one after the other -- what the package offered before.
 
 Reported: ms per round and aggregate windows / s.
-usage: python tools/bench_seg_stream.py [--compute mixed,bf16 --windows 40 --warmup 8 --reps 3 --recurrent convlstm --streams 1,2,4,8]"""
+
+--streams S[,S...] --active k[,k...] measures rounds in which only k of the S streams have a window (round i: the streams
+(i + j) % S, j < k -- which ones rotates) INSTEAD, two ways, both replayed, warm_up() in front of the timed region, alternating in the
+same process with the same repetition scheme:
+
+  ride_along   MultiStreamSegmenter(compact=False): the round runs all S streams, the idle ones on a zero grid;
+  compact      MultiStreamSegmenter(compact=True[, compact_buckets=--buckets]): the round runs the smallest bucket >= k.
+
+usage: python tools/bench_seg_stream.py [--compute mixed,bf16 --windows 40 --warmup 8 --reps 3 --recurrent convlstm --streams 1,2,4,8
+                                         [--active 1,2,4,6,8 [--buckets 1,2,4]]]"""
 import argparse
 import json
 import os
@@ -43,7 +52,12 @@ def main():
     ap.add_argument('--recurrent', default='convlstm')
     ap.add_argument('--compute', default='mixed,bf16')
     ap.add_argument('--streams', default=None, help='comma-separated stream counts: measure MultiStreamSegmenter against round-robin serving')
+    ap.add_argument('--active', default=None, help='(with --streams) comma-separated counts of active streams per round: measure compacted '
+                                                   'against ride-along rounds')
+    ap.add_argument('--buckets', default=None, help="(with --active) the compacting segmenter's compact_buckets, comma-separated (default: its own)")
     a = ap.parse_args()
+    if a.active and not a.streams:
+        ap.error('--active needs --streams')
     from ess_amd import hip
     from ess_amd.e2vid.model.model import E2VIDRecurrent
     from ess_amd.e2vid.options.inference_options import default_options
@@ -74,7 +88,7 @@ def main():
         return (time.perf_counter() - t0) / a.windows * 1e3
 
     if a.streams:
-        multi_stream(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, StreamingSegmenter, default_options)
+        (partly_active if a.active else multi_stream)(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, StreamingSegmenter, default_options)
         print(json.dumps(out))
         return
 
@@ -154,6 +168,59 @@ def multi_stream(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiStrea
                     out['windows_per_s'][f'{compute}/S={S}/{k}'] = round(S / med * 1e3, 1)
                 assert all(seg.n_captures == (1 if mode == 'graph' else 0) for mode, seg in multis.items())
                 del solos, multis, ways
+                torch.cuda.empty_cache()
+        finally:
+            hip.set_compute('fp32')
+
+
+def partly_active(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, StreamingSegmenter, default_options):
+    out['shape'] = f'k active of S streams of {a.bins}x{a.height}x{a.width} K={a.classes}'
+    del out['ms_per_window']
+    out['ms_per_round'], out['buckets'] = {}, {}
+    buckets = None if a.buckets is None else [int(v) for v in a.buckets.split(',') if v]
+
+    def models():
+        torch.manual_seed(6)
+        return E2VIDRecurrent(dict(cfg)), SemSegE2VID(256, a.classes, skip_connect=True, skip_type='concat')
+
+    def timed(step):
+        for i in range(a.warmup):
+            step(i)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(a.windows):
+            step(i)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / a.windows * 1e3
+
+    for compute in a.compute.split(','):
+        hip.set_compute(compute)
+        try:
+            for S in (int(v) for v in a.streams.split(',')):
+                segs = {'ride_along': MultiStreamSegmenter(*models(), a.height, a.width, default_options(), S, graph=True),
+                        'compact': MultiStreamSegmenter(*models(), a.height, a.width, default_options(), S, graph=True, compact=True,
+                                                        compact_buckets=None if buckets is None else [b for b in buckets if b < S])}
+                for seg in segs.values():
+                    seg.warm_up()
+                out['buckets'][f'{compute}/S={S}'] = list(segs['compact'].buckets)
+                captures = {k: seg.n_captures for k, seg in segs.items()}
+                for k_active in (int(v) for v in a.active.split(',')):
+                    if not 0 <= k_active <= S:
+                        raise SystemExit(f'--active {k_active} of --streams {S}')
+
+                    def events(i):  # stream s gets window (i + s) % 4, as in the all-active table
+                        on = {(i + j) % S for j in range(k_active)}
+                        return [wins[(i + s) % 4] if s in on else None for s in range(S)]
+                    ways = {k: (lambda seg: lambda i: seg.update_from_events(events(i)))(seg) for k, seg in segs.items()}
+                    ms = {k: [] for k in ways}
+                    for _ in range(a.reps):  # alternating: drift of the box hits both ways alike
+                        for k, fn in ways.items():
+                            ms[k].append(timed(fn))
+                    for k, v in ms.items():
+                        out['ms_per_round'][f'{compute}/S={S}/active={k_active}/{k}'] = {
+                            'median': round(statistics.median(v), 4), 'min': round(min(v), 4), 'max': round(max(v), 4)}
+                assert captures == {k: seg.n_captures for k, seg in segs.items()}  # (no round in the timed regions paid a capture)
+                del segs, ways
                 torch.cuda.empty_cache()
         finally:
             hip.set_compute('fp32')

@@ -7,11 +7,13 @@ Run it under a kernel trace of its own -- no counters, no other tracing in that 
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/bench_state_carry.py --streams 8
 
 and hand the trace to the same script:  python tools/bench_state_carry.py --parse <dir>/**/*_kernel_trace.csv
--> per case (all-TAKE, all-HOLD, half TAKE, the copy_ sequence) the median time of one carry, the bytes it moves (read + written)
+-> per case (all-TAKE, all-HOLD, half TAKE, the indexed gather of the same half, the copy_ sequence) the median time of one carry, the bytes it moves (read + written)
 and the achieved TB/s.  The run itself also prints device-event times per carry for every case (launch gaps included), which is
 the comparison with the copy_ sequence where the runtime performs those copies without a kernel the trace lists.  The launches
 are told apart by name and order: `--reps` carries per case, the cases in the order above, a marker launch (a 1-element fill_ of
-an int64 tensor) between them."""
+an int64 tensor) between them.  indexed_half is hip.state_carry_indexed gathering the (S + 1) // 2 even records of the S-stream
+state into a batch of that size: the bytes of half_take through the indexed kernel, in the same trace run.  The run is one
+process and stops at its first error; a wrapper that runs further steps behind it chains them on its exit status."""
 import argparse
 import csv
 import json
@@ -21,7 +23,8 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-CASES = ('all_take', 'all_hold', 'half_take', 'copy_sequence')
+CASES = ('all_take', 'all_hold', 'half_take', 'indexed_half', 'copy_sequence')
+KERNEL = {'indexed_half': 'state_carry_indexed'}  # (every other kernel case: state_carry_masked)
 
 
 def run(a):
@@ -43,17 +46,24 @@ def run(a):
     table = hip.StateCarryTable(dst, src)
     per_stream = sum(table.bytes_per_sample)
     dev = dst[0].device
+    half = list(range(0, S, 2))
+    work = [torch.zeros((len(half),) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for t in dst]
+    gather = hip.StateMoveTable(work, src)
+    g_dst = torch.arange(len(half), dtype=torch.int32, device=dev)
+    g_src = torch.tensor(half, dtype=torch.int32, device=dev)
     modes = {'all_take': [1] * S, 'all_hold': [0] * S, 'half_take': [1 if s % 2 == 0 else 0 for s in range(S)]}
     marker = torch.zeros(1, dtype=torch.int64, device=dev)
     event_us = {}
     for name in CASES:
         marker.fill_(1)
-        m = None if name == 'copy_sequence' else torch.tensor(modes[name], dtype=torch.int32, device=dev)
+        m = torch.tensor(modes[name], dtype=torch.int32, device=dev) if name in modes else None
         torch.cuda.synchronize()
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(a.reps + 1)]
         ev[0].record()
         for i in range(a.reps):
-            if m is None:
+            if name == 'indexed_half':
+                gather.run(g_dst, g_src)
+            elif m is None:
                 for d, s in zip(dst, src):
                     d.copy_(s)
             else:
@@ -63,7 +73,8 @@ def run(a):
         gaps = [ev[i].elapsed_time(ev[i + 1]) * 1e3 for i in range(a.reps)]
         # (device events on the stream: a gap holds one carry plus its launch gaps -- the copy_ sequence pays one gap per tensor)
         event_us[name] = {'median': round(statistics.median(gaps), 2), 'min': round(min(gaps), 2), 'max': round(max(gaps), 2)}
-    moved = {'all_take': 2 * S * per_stream, 'all_hold': 0, 'half_take': 2 * ((S + 1) // 2) * per_stream, 'copy_sequence': 2 * S * per_stream}
+    moved = {'all_take': 2 * S * per_stream, 'all_hold': 0, 'half_take': 2 * ((S + 1) // 2) * per_stream,
+             'indexed_half': 2 * len(half) * per_stream, 'copy_sequence': 2 * S * per_stream}
     print(json.dumps({'streams': S, 'compute': a.compute, 'recurrent': a.recurrent, 'tensors': len(dst), 'reps': a.reps,
                       'state_bytes_per_stream': per_stream, 'bytes_moved': moved, 'event_us_per_carry': event_us,
                       'event_TB_per_s': {k: round(moved[k] / (event_us[k]['median'] * 1e-6) / 1e12, 3) for k in CASES}}))
@@ -83,12 +94,12 @@ def parse(a):
     for ci, name in enumerate(CASES):
         seg = rows[marks[ci] + 1:(marks[ci + 1] if ci + 1 < len(CASES) else len(rows))]
         if name == 'copy_sequence':
-            k = [r for r in seg if 'state_carry_masked' not in name_of(r)]
+            k = [r for r in seg if 'state_carry_' not in name_of(r)]
             n = a.tensors
             us = [sum(int(r['End_Timestamp']) - int(r['Start_Timestamp']) for r in k[i:i + n]) / 1e3 for i in range(0, len(k) - n + 1, n)]
             span = [(int(k[i + n - 1]['End_Timestamp']) - int(k[i]['Start_Timestamp'])) / 1e3 for i in range(0, len(k) - n + 1, n)]
         else:
-            k = [r for r in seg if 'state_carry_masked' in name_of(r)]
+            k = [r for r in seg if KERNEL.get(name, 'state_carry_masked') in name_of(r)]
             us = [(int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3 for r in k]
             span = us
         if not us:  # (same-dtype copy_ calls may run as runtime copies that a kernel trace does not list: see the run's event times)
