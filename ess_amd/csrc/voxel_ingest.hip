@@ -1,0 +1,148 @@
+// Event ingest for the captured multi-stream round: packed 16-byte event records -> the round's voxel grids, with a sum that does
+// not depend on the order the events arrive in (ess_event_ingest, include/ess_hip.h).
+//
+// voxel_temporal_kernel (voxel.hip) adds its fp32 contributions with fp32 global atomics: a voxel's value depends on which event
+// got there first, two builds of one window differ in the last bits.  Here every contribution is the SAME fp32 value (the same
+// double expressions, rounded to fp32 once), but it is added as a 64-bit integer: q = llrint(c * 2^40) into int64 acc[S][bins][H][W]
+// with global_atomic_add_x2.  Integer addition is associative, so acc -- and out = (float)acc * 2^-40, one round-to-nearest
+// conversion and an exact scaling -- is a pure function of the SET of events.  |c| in [2^-16, 1] is exact at this scale, a smaller
+// one is off by at most 2^-41.  An event adds to a voxel at most once (its two halves go to two bins), each time at most 2^40 in
+// magnitude, so capacity <= 2^22 events per stream keep |acc| <= 2^62: inside int64.
+//
+// Two launches, both shaped by the CAPACITY and the grid size alone, the per-stream event counts read on the device: no memset, no
+// host-side size, no synchronisation -- a hipGraph captures them once and replays them for every round.  acc is zeroed once by its
+// owner; the finish pass leaves it all zero again (it stores zeros back only where a sum was, so an empty region costs reads only).
+#include "common.h"
+
+namespace {
+
+constexpr int INGEST_THREADS = 256;
+constexpr int INGEST_EVENTS_PER_THREAD = 4;  // scatter: records a thread walks at full capacity, before the block cap widens it
+constexpr int INGEST_MAX_BLOCKS_X = 1024;
+constexpr int INGEST_QUADS_PER_THREAD = 4;  // finish: 4-voxel groups (2 x 16 B of acc, 16 B of out) per thread
+constexpr int64_t INGEST_MAX_CAPACITY = (int64_t)1 << 22;
+constexpr double INGEST_SCALE = 0x1p40;
+constexpr float INGEST_INV_SCALE = 0x1p-40f;
+
+// {double t; int16 x; int16 y; int32 p}, little endian, as one 16-byte word
+__device__ __forceinline__ void unpack_record(const uint4 v, double& t, int& x, int& y, int& p) {
+  t = __hiloint2double((int)v.y, (int)v.x);
+  x = (int)(short)(v.z & 0xffffu);
+  y = (int)(short)(v.z >> 16);
+  p = (int)v.w;
+}
+
+__device__ __forceinline__ double record_time(const uint4* __restrict__ rec, int64_t e) {
+  const uint4 v = rec[e];
+  return __hiloint2double((int)v.y, (int)v.x);
+}
+
+// c -> q = llrint(c * 2^40): the product is exact in fp64 (24 significant bits, exponent shift), one rounding to the integer
+__device__ __forceinline__ long long quantise(float c) { return __double2ll_rn((double)c * INGEST_SCALE); }
+
+__global__ __launch_bounds__(INGEST_THREADS) void event_scatter_kernel(const uint4* __restrict__ records, const int32_t* __restrict__ counts,
+                                                                       int64_t capacity, int nb, int H, int W,
+                                                                       long long* __restrict__ acc) {
+#pragma clang fp contract(off)  // (no fused multiply-add may change a per-event value: the results are compared as bits)
+  const int s = blockIdx.y;
+  const int cnt = counts[s];
+  if (cnt <= 0) return;  // an empty window, or INGEST_KEEP: nothing of this stream is read
+  const int64_t n = (int64_t)cnt < capacity ? (int64_t)cnt : capacity;
+  const uint4* __restrict__ rec = records + (size_t)s * capacity;
+  const double first = record_time(rec, 0);
+  double dT = record_time(rec, n - 1) - first;
+  if (dT == 0) dT = 1.0;
+  const size_t plane = (size_t)H * W;
+  long long* __restrict__ g = acc + (size_t)s * nb * plane;
+  for (int64_t e = (int64_t)blockIdx.x * INGEST_THREADS + threadIdx.x; e < n; e += (int64_t)gridDim.x * INGEST_THREADS) {
+    double t;
+    int xs, ys, p;
+    unpack_record(rec[e], t, xs, ys, p);
+    const double ts = ((double)(nb - 1) * (t - first)) / dT;
+    if (!(xs < W && xs >= 0 && ys < H && ys >= 0 && ts >= 0 && ts < nb)) continue;  // (a NaN time fails both comparisons)
+    const int ti = (int)ts;
+    const double dts = ts - ti;
+    // |polarity| = 1: the record carries -1 / +1 (any other word counts as -1, so no record can leave the int64 range)
+    const float left = (float)(1.0 - dts), right = (float)dts;
+    const float sign = p == 1 ? 1.f : -1.f;
+    long long* gp = g + (size_t)ys * W + xs;
+    const long long ql = quantise(sign * left), qr = quantise(sign * right);
+    // (ti < nb holds; a zero adds nothing)
+    if (ql != 0) atomicAdd((unsigned long long*)(gp + (size_t)ti * plane), (unsigned long long)ql);
+    if (ti + 1 < nb && qr != 0) atomicAdd((unsigned long long*)(gp + (size_t)(ti + 1) * plane), (unsigned long long)qr);
+  }
+}
+
+typedef long long i64x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float dequantise(long long a) { return (float)a * INGEST_INV_SCALE; }
+
+// VEC: per_stream is a multiple of 4, so every stream's acc / out rows start 16-byte aligned
+template <bool VEC>
+__global__ __launch_bounds__(INGEST_THREADS) void event_finish_kernel(const int32_t* __restrict__ counts, int64_t per_stream,
+                                                                      long long* __restrict__ acc, float* __restrict__ out) {
+  const int s = blockIdx.y;
+  if (counts[s] < 0) return;  // INGEST_KEEP: the grid already in `out` is the caller's; acc of this stream is zero and stays so
+  long long* __restrict__ a = acc + (size_t)s * per_stream;
+  float* __restrict__ o = out + (size_t)s * per_stream;
+  const int64_t stride = (int64_t)gridDim.x * INGEST_THREADS;
+  const int64_t i0 = (int64_t)blockIdx.x * INGEST_THREADS + threadIdx.x;
+  if constexpr (VEC) {
+    i64x2* __restrict__ a2 = (i64x2*)a;
+    f32x4* __restrict__ o4 = (f32x4*)o;
+    const i64x2 z = {0, 0};
+    for (int64_t i = i0; i < (per_stream >> 2); i += stride) {
+      const i64x2 lo = a2[2 * i], hi = a2[2 * i + 1];
+      f32x4 v;
+      v[0] = dequantise(lo[0]); v[1] = dequantise(lo[1]); v[2] = dequantise(hi[0]); v[3] = dequantise(hi[1]);
+      o4[i] = v;
+      if ((lo[0] | lo[1]) != 0) a2[2 * i] = z;
+      if ((hi[0] | hi[1]) != 0) a2[2 * i + 1] = z;
+    }
+  } else {
+    for (int64_t i = i0; i < per_stream; i += stride) {
+      const long long v = a[i];
+      o[i] = dequantise(v);
+      if (v != 0) a[i] = 0;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" size_t ess_event_ingest_workspace(int32_t n_streams, int32_t bins, int32_t height, int32_t width) {
+  if (n_streams <= 0 || bins <= 0 || height <= 0 || width <= 0) return 0;
+  return (size_t)n_streams * bins * height * width * sizeof(long long);
+}
+
+extern "C" int ess_event_ingest(const void* records, const int32_t* counts, int64_t capacity, int32_t n_streams, int32_t bins,
+                                int32_t height, int32_t width, void* acc, size_t acc_bytes, float* out, ess_stream_t stream) {
+  ESS_CHECK_ARG(records && counts && acc && out, "event_ingest: null records, counts, acc or out");
+  ESS_CHECK_ARG(n_streams >= 1 && n_streams <= 65535, "event_ingest: n_streams=%d (1..65535)", (int)n_streams);
+  ESS_CHECK_ARG(bins > 0 && height > 0 && width > 0, "event_ingest: bins=%d height=%d width=%d must be positive", (int)bins, (int)height,
+                (int)width);
+  ESS_CHECK_ARG(capacity >= 1 && capacity <= INGEST_MAX_CAPACITY,
+                "event_ingest: capacity=%lld events per stream (1..%lld: the int64 sums hold 2^22 contributions of magnitude 1 at scale 2^40)",
+                (long long)capacity, (long long)INGEST_MAX_CAPACITY);
+  const size_t need = ess_event_ingest_workspace(n_streams, bins, height, width);
+  ESS_CHECK_ARG(acc_bytes >= need, "event_ingest: acc has %zu bytes, %zu are needed", acc_bytes, need);
+  ESS_CHECK_ARG((((uintptr_t)records) & 15) == 0 && (((uintptr_t)acc) & 15) == 0 && (((uintptr_t)out) & 15) == 0,
+                "event_ingest: records, acc and out must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t per = (int64_t)bins * height * width;
+  int64_t bx = ceil_div64(capacity, (int64_t)INGEST_THREADS * INGEST_EVENTS_PER_THREAD);
+  if (bx > INGEST_MAX_BLOCKS_X) bx = INGEST_MAX_BLOCKS_X;
+  hipLaunchKernelGGL(event_scatter_kernel, dim3((unsigned)bx, (unsigned)n_streams), dim3(INGEST_THREADS), 0, st, (const uint4*)records, counts,
+                     capacity, bins, height, width, (long long*)acc);
+  int rc = ess_launch_status("event_ingest(scatter)");
+  if (rc) return rc;
+  const bool vec = (per & 3) == 0;
+  int64_t fx = ceil_div64(vec ? per >> 2 : per, (int64_t)INGEST_THREADS * INGEST_QUADS_PER_THREAD);
+  if (fx > INGEST_MAX_BLOCKS_X) fx = INGEST_MAX_BLOCKS_X;
+  const dim3 fgrid((unsigned)fx, (unsigned)n_streams);
+  if (vec)
+    hipLaunchKernelGGL(event_finish_kernel<true>, fgrid, dim3(INGEST_THREADS), 0, st, counts, per, (long long*)acc, out);
+  else
+    hipLaunchKernelGGL(event_finish_kernel<false>, fgrid, dim3(INGEST_THREADS), 0, st, counts, per, (long long*)acc, out);
+  return ess_launch_status("event_ingest(finish)");
+}

@@ -9,6 +9,7 @@ import ctypes
 import os
 from ctypes import POINTER, Structure, byref, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
+import numpy as np
 import torch
 
 from . import copies
@@ -76,6 +77,7 @@ EXPORTS = [
     'ess_label_confusion', 'ess_augment_perspective_filter', 'ess_tuning_set', 'ess_tuning_get', 'ess_conv2d_s2d_preferred',
     'ess_to_f16_c8', 'ess_bf16_c8_to_f16_c8', 'ess_f16_c8_to_bf16_c8', 'ess_instnorm_forward_c8_mixed', 'ess_seg_head',
     'ess_event_normalize_samples', 'ess_state_carry_masked', 'ess_state_carry_indexed',
+    'ess_event_ingest_workspace', 'ess_event_ingest',
 ]
 
 
@@ -118,6 +120,8 @@ def lib():
         L.ess_voxel_normalize_workspace.argtypes = [c_int32]
         L.ess_voxel_grid_trilinear_workspace.restype = c_size_t
         L.ess_voxel_grid_trilinear_workspace.argtypes = [c_int64, c_int32, c_int32, c_int32]
+        L.ess_event_ingest_workspace.restype = c_size_t
+        L.ess_event_ingest_workspace.argtypes = [c_int32, c_int32, c_int32, c_int32]
         P, F, I, I64 = c_void_p, c_float, c_int32, c_int64
         D = POINTER(EssConvDesc)
         sig = {
@@ -168,6 +172,7 @@ def lib():
             'ess_event_normalize_samples': [P, P, I, I64, P, P, P],
             'ess_state_carry_masked': [P, P, P, I, I, P, P],
             'ess_state_carry_indexed': [P, P, P, I, I, I, I, P, P, P],
+            'ess_event_ingest': [P, P, I64, I, I, I, I, P, c_size_t, P, P],
         }
         for name, argtypes in sig.items():
             fn = getattr(L, name)
@@ -823,6 +828,44 @@ def voxel_grid_temporal(x, y, t, pol, slice_offsets, bins, height, width, separa
            'ess_voxel_grid_temporal')
     if normalize:
         voxel_normalize_(out, mode=1)
+    return out
+
+
+# One event of the ingest path: ess_event_ingest's 16-byte record (include/ess_hip.h).  p is +1 / -1.
+EVENT_RECORD = np.dtype([('t', '<f8'), ('x', '<i2'), ('y', '<i2'), ('p', '<i4')])
+INGEST_KEEP = -1  # ESS_INGEST_KEEP: a count word that leaves the stream's grid in `out` as it is
+INGEST_MAX_CAPACITY = 1 << 22
+
+
+def event_ingest(records, counts, out, acc=None):
+    """Packed event records -> one signed temporal voxel grid per stream, ORDER-INDEPENDENT: each contribution is the fp32 value
+    voxel_grid_temporal(separate_pol=False) adds, summed as a 64-bit integer at scale 2^40, so out is a pure function of the set of
+    events (bit-identical run to run, batched or alone, whatever the record order between the first and the last).
+    records: device uint8 [S, capacity, 16] (EVENT_RECORD rows; datasets.data_util.pack_event_records fills them on the host);
+    counts: device int32 [S], read on the device -- n > 0: the stream's first n records, 0: an all-zero grid, INGEST_KEEP (< 0):
+    out[s] is neither read nor written; out: fp32 [S, bins, H, W], returned.  acc: a contiguous device int64 tensor of at least
+    S * bins * H * W elements that is ALL ZERO (it is again behind the call) or None: allocated and zeroed here.  Two launches
+    whose shape follows from the capacity alone, no memset and no synchronisation: capturable as they stand."""
+    for name, t in (('records', records), ('counts', counts), ('out', out)) + ((('acc', acc),) if acc is not None else ()):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise EssHipError(f'event_ingest: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+        if not t.is_contiguous():
+            raise EssHipError(f'event_ingest: {name} must be contiguous')
+    if out.dim() != 4 or out.dtype != torch.float32 or out.numel() == 0:
+        raise EssHipError(f'event_ingest: out must be a non-empty fp32 [S, bins, H, W] tensor, got {out.dtype}{tuple(out.shape)}')
+    S, bins, H, W = out.shape
+    if records.dtype != torch.uint8 or records.dim() != 3 or records.shape[0] != S or records.shape[2] != EVENT_RECORD.itemsize or records.shape[1] < 1:
+        raise EssHipError(f'event_ingest: records must be uint8 [{S}, capacity, {EVENT_RECORD.itemsize}], got {records.dtype}{tuple(records.shape)}')
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (S,):
+        raise EssHipError(f'event_ingest: counts must be int32 [{S}], got {counts.dtype}{tuple(counts.shape)}')
+    L = lib()
+    need = L.ess_event_ingest_workspace(S, bins, H, W)
+    if acc is None:
+        acc = torch.zeros(need // 8, dtype=torch.int64, device=out.device)
+    elif acc.dtype != torch.int64:
+        raise EssHipError(f'event_ingest: acc must be int64, got {acc.dtype}')
+    _check(L.ess_event_ingest(c_void_p(records.data_ptr()), ptr(counts, torch.int32), records.shape[1], S, bins, H, W,
+                              c_void_p(acc.data_ptr()), acc.numel() * 8, c_void_p(out.data_ptr()), stream()), 'ess_event_ingest')
     return out
 
 

@@ -87,7 +87,12 @@ class StreamingSegmenter(GraphedWindowState):
     encoder: an E2VIDRecurrent; decoder: a SemSegE2VID.  palette: uint8 [K, 3] (Settings.semseg_color_map; numpy or torch) -> the
     result carries colours.  out_hw: resize from the sensor-size region by the nearest rule (validation's img_size_b semantics).
     copy (graph mode): update() returns clones of the replay's static output buffers, so results held across windows stay intact;
-    copy=False hands out the buffers themselves (valid until the next update())."""
+    copy=False hands out the buffers themselves (valid until the next update()).
+
+    update_from_events builds the grid with hip.voxel_grid_temporal in front of the window (fp32 atomics: the last bits follow
+    arrival order).  The order-independent event ingest inside the captured round (event_capacity=) is MultiStreamSegmenter's: this
+    driver's first window runs eagerly outside the capture; MultiStreamSegmenter(n_streams=1, event_capacity=N) is the
+    single-stream form, at +0.02 ms per window."""
 
     def __init__(self, encoder, decoder, height, width, options, device=None, graph=False, copy=True, palette=None,
                  want_confidence=False, out_hw=None):
@@ -269,6 +274,24 @@ def check_stream_events(events, n_streams):
     return out, [e is not None for e in out]
 
 
+def _event_capacity(n, height, width):
+    """MultiStreamSegmenter's event_capacity argument, checked -> int"""
+    if not isinstance(n, int) or isinstance(n, bool) or not 1 <= n <= hip.INGEST_MAX_CAPACITY:
+        raise hip.EssHipError(f'event_capacity={n!r}: events per stream and round, an int in [1, {hip.INGEST_MAX_CAPACITY}]')
+    if height > 32767 or width > 32767:
+        raise hip.EssHipError(f'event_capacity: the event records carry int16 coordinates, {height} x {width} does not fit (<= 32767)')
+    return n
+
+
+class _IngestStage:
+    """one pinned staging set of the event ingest: records / counts (torch, pinned), their numpy views, the event recorded behind
+    the set's last upload, and the (slot, rows) pairs staged for the next one"""
+    __slots__ = ('records', 'counts', 'records_np', 'counts_np', 'done', 'used')
+
+    def __init__(self, records, counts, records_np, counts_np, done):
+        self.records, self.counts, self.records_np, self.counts_np, self.done, self.used = records, counts, records_np, counts_np, done, ()
+
+
 class MultiStreamSegmenter(GraphedWindowState):
     """n_streams independent sequences, one ROUND (one window of every active stream) at a time, as one batch.
     update(grids [S, num_bins, H, W], active=None) / update_from_events(list of S [N, 4] arrays or None) -> MultiSegmentationResult;
@@ -293,10 +316,20 @@ class MultiStreamSegmenter(GraphedWindowState):
     active streams than the largest bucket -- every round with all streams active -- is the ride-along round above, unchanged.
     graph=True: one capture per bucket and one for the ride-along round, each made when first needed or all at once by warm_up();
     n_captures <= len(buckets) + 1.  The index tables and the compact input are static device buffers the host writes in front of
-    the round; results keep the shape [S, ...], the active rows copied to their streams' rows behind it."""
+    the round; results keep the shape [S, ...], the active rows copied to their streams' rows behind it.
+
+    event_capacity=N (events per stream and round, <= 2^22; None: nothing below exists and every path is as without): the round
+    itself starts with hip.event_ingest, inside the capture (n_captures is as before).  update_from_events packs each active
+    stream's rows into pinned 16-byte records on the host (datasets.data_util.pack_event_records), copies their used prefixes and
+    the per-stream count words to static device buffers and replays; a window of more than N events is refused before anything
+    is written.  The ingest sums in 64-bit fixed point, so the grids -- and with them labels, colours and confidences -- are a pure
+    function of the events: run to run, batched or alone, compacted or not.  update(grids) writes the count word INGEST_KEEP for
+    every stream and copies the grids in as without.  Allocated once: device records [S, N, 16], counts [S], the int64 sums
+    [S, num_bins, H, W], and two pinned staging sets used alternately (the host waits for a set's last upload before rewriting
+    it); a compacted round stages its records in slot order into the first `bucket` records, padded slots with count 0."""
 
     def __init__(self, encoder, decoder, height, width, options, n_streams, device=None, graph=False, copy=True, palette=None,
-                 want_confidence=False, out_hw=None, compact=False, compact_buckets=None):
+                 want_confidence=False, out_hw=None, compact=False, compact_buckets=None, event_capacity=None):
         if not isinstance(n_streams, int) or isinstance(n_streams, bool) or n_streams < 1:
             raise hip.EssHipError(f'n_streams={n_streams!r}: a positive number of streams is needed')
         self.compact = bool(compact)
@@ -326,9 +359,74 @@ class MultiStreamSegmenter(GraphedWindowState):
         self._in = torch.zeros(S, self.num_bins, height, width, dtype=torch.float32, device=self.device)
         self._modes = torch.zeros(2, S, dtype=torch.int32, device=self.device)  # [0]: in front of the step, [1]: behind it
         self._pending = [True] * S
+        self.event_capacity = None if event_capacity is None else _event_capacity(event_capacity, height, width)
+        if self.event_capacity is not None:
+            self._build_ingest()
         self._build_state()
         if self.buckets:
             self._build_compact()
+
+    # ---- event ingest (event_capacity=N): static record / count buffers the captured round reads, pinned staging in front of them
+    event_capacity = _records = _counts = _acc = None
+
+    def _build_ingest(self):
+        """Device records [S, N, 16], counts [S] and the int64 sums of hip.event_ingest (zeroed here, once), and two pinned staging
+        sets used alternately, each with the event that marks the end of its last upload.  A compacted round reads the first
+        `bucket` records / counts of the same buffers (slot order) and the leading part of the sums."""
+        S, N = self.n_streams, self.event_capacity
+        self._records = torch.zeros(S, N, hip.EVENT_RECORD.itemsize, dtype=torch.uint8, device=self.device)
+        self._counts = torch.full((S,), hip.INGEST_KEEP, dtype=torch.int32, device=self.device)
+        self._acc = torch.zeros(S, self.num_bins, self.height, self.width, dtype=torch.int64, device=self.device)
+        self._stage = []
+        for _ in range(2):
+            rec = torch.zeros(S, N, hip.EVENT_RECORD.itemsize, dtype=torch.uint8).pin_memory()
+            cnt = torch.full((S,), hip.INGEST_KEEP, dtype=torch.int32).pin_memory()
+            self._stage.append(_IngestStage(rec, cnt, rec.numpy().view(hip.EVENT_RECORD).reshape(S, N), cnt.numpy(), torch.cuda.Event()))
+        self._stage_next = 0
+
+    def _next_stage(self):
+        """the staging set of this round, free to be rewritten: its last upload has completed (in practice long ago -- a whole
+        round lies between two uses of a set)"""
+        st = self._stage[self._stage_next]
+        self._stage_next ^= 1
+        st.done.synchronize()
+        return st
+
+    def _stage_keep(self):
+        """a round whose grids the caller provides: every count word INGEST_KEEP (None without event_capacity)"""
+        if self.event_capacity is None:
+            return None
+        st = self._next_stage()
+        st.counts_np[:] = hip.INGEST_KEEP
+        st.used = ()
+        return st
+
+    def _stage_events(self, slots):
+        """slots: per record slot (stream, or slot of a compact batch) an [N, 4] array or None -> the staging set with the rows
+        packed and the counts written; slots behind the list: count 0.  Raises before anything is written when a window does not
+        fit; nothing reaches the device here."""
+        from .datasets.data_util import pack_event_records
+        for i, e in enumerate(slots):
+            if e is not None and e.shape[0] > self.event_capacity:
+                raise hip.EssHipError(f'update_from_events: a window of {e.shape[0]} events (slot {i}) exceeds event_capacity={self.event_capacity}')
+        st = self._next_stage()
+        st.counts_np[:] = 0
+        st.used = ()  # (a refused polarity below leaves a set without uploads)
+        used = []
+        for i, e in enumerate(slots):
+            if e is not None:
+                n = pack_event_records(e, st.records_np[i])
+                st.counts_np[i] = n
+                used.append((i, n))
+        st.used = tuple(used)
+        return st
+
+    def _upload(self, st):
+        """the staged counts and the used prefix of every staged slot -> the static device buffers, on the current stream"""
+        for i, n in st.used:
+            self._records[i, :n].copy_(st.records[i, :n], non_blocking=True)
+        self._counts.copy_(st.counts, non_blocking=True)
+        st.done.record()
 
     @classmethod
     def from_checkpoints(cls, e2vid_path, ess_checkpoint_path, settings_or_kwargs, n_streams, **kw):
@@ -432,6 +530,8 @@ class MultiStreamSegmenter(GraphedWindowState):
         with torch.no_grad():
             gather.run(tab[0], tab[1])  # slot <- its stream's state; restarting streams and padded slots: 0
             ev = self.compact_input[:b]
+            if self.event_capacity is not None:  # (count words INGEST_KEEP: the grids the caller copied in stay)
+                hip.event_ingest(self._records[:b], self._counts[:b], ev, self._acc)
             for x, y in pre.hot_pixel_locations:
                 ev[:, :, y, x] = 0
             if pre.flip:
@@ -478,15 +578,20 @@ class MultiStreamSegmenter(GraphedWindowState):
                 self._capture_compact(b)
         self.last_latent = None
 
-    def _update_compact(self, plan, grids, active, compacted):
-        """one compacted round; grids: [S, ...] (compacted false: the active rows are placed into the compact input here) or the
-        compact grids [bucket, ...] themselves"""
+    def _update_compact(self, plan, grids, active, compacted, stage=None):
+        """one compacted round; grids: [S, ...] (compacted false: the active rows are placed into the compact input here), the
+        compact grids [bucket, ...] themselves, or None: the round's ingest builds them from the staged records.  stage: the
+        ingest's staging set of this round (event_capacity)"""
         b, A = plan.bucket, len(plan.rows)
         self._pending = plan.pending_after
         if self.use_graph and b not in self._cg:
             self._capture_compact(b)
         self._write_tables(plan)
-        if compacted:
+        if stage is not None:
+            self._upload(stage)
+        if grids is None:
+            pass  # (the ingest in front of the round builds compact_input[:b])
+        elif compacted:
             self.compact_input[:b].copy_(grids, non_blocking=True)
         elif A:
             self.compact_input[:A].copy_(grids[plan.rows], non_blocking=True)
@@ -526,6 +631,8 @@ class MultiStreamSegmenter(GraphedWindowState):
         with torch.no_grad():
             self._pre.run(self._modes[0])  # restarting streams: state = 0
             ev = self._in
+            if self.event_capacity is not None:  # (count words INGEST_KEEP: the grids the caller copied in stay)
+                hip.event_ingest(self._records, self._counts, ev, self._acc)
             for x, y in pre.hot_pixel_locations:
                 ev[:, :, y, x] = 0
             if pre.flip:
@@ -570,12 +677,20 @@ class MultiStreamSegmenter(GraphedWindowState):
         self._check_compute()
         plan = compact_plan(self._pending, active, self.buckets) if self.buckets else None
         if plan is not None:
-            return self._update_compact(plan, grids, active, False)
+            return self._update_compact(plan, grids, active, False, self._stage_keep())
+        return self._ride_along(grids, active, self._stage_keep())
+
+    def _ride_along(self, grids, active, stage=None):
+        """one round at the full batch; grids None: the round's ingest builds them from the staged records.  stage: the ingest's
+        staging set of this round (event_capacity)"""
         pre, post, self._pending = stream_modes(self._pending, active)
         if self.use_graph and self._g is None:
             self._capture()
         self._modes.copy_(torch.tensor([pre, post], dtype=torch.int32), non_blocking=True)
-        self._in.copy_(grids, non_blocking=True)
+        if stage is not None:
+            self._upload(stage)
+        if grids is not None:
+            self._in.copy_(grids, non_blocking=True)
         if self.use_graph:
             self._g.replay()
             out = self._outputs
@@ -589,6 +704,8 @@ class MultiStreamSegmenter(GraphedWindowState):
         """events: S entries, [N, 4] rows (t, x, y, polarity) of the stream's window or None (idle).  All grids are built by ONE
         hip.voxel_grid_temporal call over the concatenated events; an idle stream is an empty slice (an all-zero grid).  A compacted
         round builds only its bucket's grids: the active streams' in slot order, a padded slot an empty slice."""
+        if self.event_capacity is not None:
+            return self._update_from_events_ingest(events)
         evs, active = check_stream_events(events, self.n_streams)
         if not any(active):
             return self.update(self._in, active)  # (nothing is read of an idle stream's grid)
@@ -608,3 +725,16 @@ class MultiStreamSegmenter(GraphedWindowState):
         if plan is None:
             return self.update(grids, active)
         return self._update_compact(plan, grids, active, True)
+
+    def _update_from_events_ingest(self, events):
+        """event_capacity=N: each active stream's rows are packed on the host into pinned 16-byte records (a compacted round: in slot
+        order), their used prefixes and the count words are copied to the static device buffers, and the round's own first launches
+        (hip.event_ingest, inside the capture) build the grids: idle streams and padded slots have count 0, an all-zero grid.  The
+        labels are a pure function of the events: the ingest's sums do not depend on arrival order."""
+        evs, active = check_stream_events(events, self.n_streams)
+        evs = [None if e is None else e.detach().cpu().numpy() for e in evs]
+        self._check_compute()
+        plan = compact_plan(self._pending, active, self.buckets) if self.buckets else None
+        if plan is None:
+            return self._ride_along(None, active, self._stage_events(evs))
+        return self._update_compact(plan, None, active, True, self._stage_events([evs[s] for s in plan.rows]))

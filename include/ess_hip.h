@@ -405,6 +405,24 @@ size_t ess_voxel_normalize_workspace(int32_t n_slices);
 int ess_voxel_normalize(float* grid, int32_t n_slices, int64_t elems_per_slice, int32_t mode, void* workspace,
                         size_t workspace_bytes, ess_stream_t stream);
 
+/* Event ingest for a captured round -- PURELY ADDITIVE to ABI 110 (ess_version() is unchanged; no existing entry point changes).
+ * The temporal flavour above, one signed grid per stream (separate_pol = 0), with a sum that does not depend on arrival order, in
+ * two launches whose shape follows from `capacity` and the grid size alone: no memset, no host-side count, no synchronisation.
+ * records (device, 16-byte aligned): [n_streams][capacity] packed 16-byte records {double t; int16_t x; int16_t y; int32_t p},
+ * p = +1 / -1 (any other word counts as -1).  counts (device, int32 [n_streams]), read by the kernels:
+ *   counts[s] >  0: stream s has min(counts[s], capacity) events; its grid is built from them;
+ *   counts[s] == 0: an empty window: an all-zero grid;
+ *   counts[s] <  0 (ESS_INGEST_KEEP): nothing of stream s is read or written; the grid already in `out` stays.
+ * Per event the two contributions are those of ess_voxel_grid_temporal bit for bit (the same fp64 expressions rounded to fp32, the
+ * same validity test, first / last = the timestamps of the stream's records 0 and count - 1); each is added as the 64-bit integer
+ * llrint(c * 2^40) into acc (int64 [n_streams][bins][height][width], ess_event_ingest_workspace() bytes, 16-byte aligned), and
+ * out[v] = (float)acc[v] * 2^-40.  acc must be ALL ZERO on entry (the owner zeroes it once) and is all zero again behind the call.
+ * capacity <= 2^22 keeps every sum inside int64.  out: fp32 [n_streams][bins][height][width], 16-byte aligned.                  */
+enum { ESS_INGEST_KEEP = -1 };
+size_t ess_event_ingest_workspace(int32_t n_streams, int32_t bins, int32_t height, int32_t width);
+int ess_event_ingest(const void* records, const int32_t* counts, int64_t capacity, int32_t n_streams, int32_t bins, int32_t height,
+                     int32_t width, void* acc, size_t acc_bytes, float* out, ess_stream_t stream);
+
 /* ---- image-branch augmentation on the device: the geometric + photometric core of the albumentations
  * pipeline of datasets/cityscapes_loader.py:39-74 (HorizontalFlip, ShiftScaleRotate with rotate 0 and a constant-0 border,
  * centred PadIfNeeded, RandomCrop, GaussNoise, RandomBrightnessContrast), uint8 quantisation, ToTensor (/255), and for the label

@@ -24,8 +24,20 @@ same process with the same repetition scheme:
   ride_along   MultiStreamSegmenter(compact=False): the round runs all S streams, the idle ones on a zero grid;
   compact      MultiStreamSegmenter(compact=True[, compact_buckets=--buckets]): the round runs the smallest bucket >= k.
 
+--streams S[,S...] --ingest measures rounds FROM HOST EVENT ARRAYS INSTEAD: per round the wall time from S numpy [N, 4] arrays in host
+memory to synchronised labels (a device synchronisation behind every round), two ways, both replayed, alternating in the same
+process with the same repetition scheme:
+
+  parent       MultiStreamSegmenter(event_capacity=None).update_from_events: concatenate, pageable upload, column split,
+               hip.voxel_grid_temporal in front of the graph, copy of the S grids into the static input, replay;
+  ingest       MultiStreamSegmenter(event_capacity=N).update_from_events: host packing into pinned 16-byte records, S small
+               copies, replay (the voxeliser runs inside the graph).
+
+Reported: ms per round (median, min, max over the repetitions), the parent's spread, the host packing alone, and whether the ingest
+way wins by more than that spread.
+
 usage: python tools/bench_seg_stream.py [--compute mixed,bf16 --windows 40 --warmup 8 --reps 3 --recurrent convlstm --streams 1,2,4,8
-                                         [--active 1,2,4,6,8 [--buckets 1,2,4]]]"""
+                                         [--active 1,2,4,6,8 [--buckets 1,2,4]] | --streams 8 --events 100000 --ingest]"""
 import argparse
 import json
 import os
@@ -55,9 +67,13 @@ def main():
     ap.add_argument('--active', default=None, help='(with --streams) comma-separated counts of active streams per round: measure compacted '
                                                    'against ride-along rounds')
     ap.add_argument('--buckets', default=None, help="(with --active) the compacting segmenter's compact_buckets, comma-separated (default: its own)")
+    ap.add_argument('--ingest', action='store_true', help='(with --streams) rounds from host event arrays: event_capacity=--events against '
+                                                          'event_capacity=None')
     a = ap.parse_args()
     if a.active and not a.streams:
         ap.error('--active needs --streams')
+    if a.ingest and (not a.streams or a.active):
+        ap.error('--ingest needs --streams and excludes --active')
     from ess_amd import hip
     from ess_amd.e2vid.model.model import E2VIDRecurrent
     from ess_amd.e2vid.options.inference_options import default_options
@@ -87,6 +103,10 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / a.windows * 1e3
 
+    if a.ingest:
+        from_host_events(a, hip, cfg, [w.cpu().numpy() for w in wins], out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, default_options)
+        print(json.dumps(out))
+        return
     if a.streams:
         (partly_active if a.active else multi_stream)(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, StreamingSegmenter, default_options)
         print(json.dumps(out))
@@ -220,6 +240,58 @@ def partly_active(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiStre
                         out['ms_per_round'][f'{compute}/S={S}/active={k_active}/{k}'] = {
                             'median': round(statistics.median(v), 4), 'min': round(min(v), 4), 'max': round(max(v), 4)}
                 assert captures == {k: seg.n_captures for k, seg in segs.items()}  # (no round in the timed regions paid a capture)
+                del segs, ways
+                torch.cuda.empty_cache()
+        finally:
+            hip.set_compute('fp32')
+
+
+def from_host_events(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, default_options):
+    from ess_amd.datasets.data_util import pack_event_records
+    out['shape'] = f'S streams of {a.bins}x{a.height}x{a.width} K={a.classes}, rounds from host event arrays, graph replay'
+    del out['ms_per_window']
+    out['ms_per_round'], out['parent_spread_ms'], out['ingest_wins_by_more_than_parent_spread'] = {}, {}, {}
+
+    def models():
+        torch.manual_seed(6)
+        return E2VIDRecurrent(dict(cfg)), SemSegE2VID(256, a.classes, skip_connect=True, skip_type='concat')
+
+    def timed(step):  # a round: stream s gets window (i + s) % 4; every round synchronised -> the median round of the repetition
+        for i in range(a.warmup):
+            step(i)
+        torch.cuda.synchronize()
+        ms = []
+        for i in range(a.windows):
+            t0 = time.perf_counter()
+            step(i)
+            torch.cuda.synchronize()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return statistics.median(ms)
+
+    for compute in a.compute.split(','):
+        hip.set_compute(compute)
+        try:
+            for S in (int(v) for v in a.streams.split(',')):
+                segs = {'parent': MultiStreamSegmenter(*models(), a.height, a.width, default_options(), S, graph=True),
+                        'ingest': MultiStreamSegmenter(*models(), a.height, a.width, default_options(), S, graph=True, event_capacity=a.events)}
+                ways = {k: (lambda seg: lambda i: seg.update_from_events([wins[(i + s) % 4] for s in range(S)]))(seg) for k, seg in segs.items()}
+                staging = np.zeros((S, a.events), dtype=hip.EVENT_RECORD)
+
+                def pack_only(i):
+                    for s in range(S):
+                        pack_event_records(wins[(i + s) % 4], staging[s])
+                ways['host_packing_alone'] = pack_only
+                ms = {k: [] for k in ways}
+                for _ in range(a.reps):  # alternating: drift of the box hits both ways alike
+                    for k, fn in ways.items():
+                        ms[k].append(timed(fn))
+                key = f'{compute}/S={S}'
+                for k, v in ms.items():
+                    out['ms_per_round'][f'{key}/{k}'] = {'median': round(statistics.median(v), 4), 'min': round(min(v), 4), 'max': round(max(v), 4)}
+                spread = max(ms['parent']) - min(ms['parent'])
+                out['parent_spread_ms'][key] = round(spread, 4)
+                out['ingest_wins_by_more_than_parent_spread'][key] = bool(statistics.median(ms['parent']) - statistics.median(ms['ingest']) > spread)
+                assert all(seg.n_captures == 1 for seg in segs.values())
                 del segs, ways
                 torch.cuda.empty_cache()
         finally:

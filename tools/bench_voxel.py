@@ -2,7 +2,13 @@
 """Measurement for SURVEY.md 8(f)1 (events -> voxel grids): one DSEC-shape batch = B=8 sequences x T=5 slices of
 100 000 events -> [8, 5*2, 480, 640], converted by ONE call.  Prints one JSON line: events/s on the GPU (inputs
 resident in HBM), the algorithmic traffic (16 B per event + 4 B per voxel) against the HBM peak, and the oracle (a restatement of the reference's put_(accumulate) loop) timed on
-the host cores for a bounded sample.  usage: python tools/bench_voxel.py [--slices 40] [--events 100000]"""
+the host cores for a bounded sample.  usage: python tools/bench_voxel.py [--slices 40] [--events 100000]
+
+--ingest measures the temporal flavour INSTEAD, two ways on the same events (device resident), alternating: hip.voxel_grid_temporal
+(memset + fp32 atomics, separate_pol=False) and hip.event_ingest (the scatter + finish pair: 64-bit integer atomics into int64 sums,
+then the conversion pass that also zeroes the sums again); an ingest with every count 0 gives the finish pass alone, the difference
+the scatter, and from it the chip-wide rate of 64-bit integer atomics with one lane per row that the pair implies.
+usage: python tools/bench_voxel.py --ingest --slices 8 --events 100000 --bins 5"""
 import argparse
 import json
 import os
@@ -23,7 +29,10 @@ def main():
     ap.add_argument('--width', type=int, default=640)
     ap.add_argument('--reps', type=int, default=200)
     ap.add_argument('--normalize', action='store_true')
+    ap.add_argument('--ingest', action='store_true', help='hip.event_ingest against hip.voxel_grid_temporal (see above)')
     a = ap.parse_args()
+    if a.ingest:
+        return ingest(a)
     from ess_amd import hip
     from oracle import ess_oracle as O
     hip.lib()
@@ -70,6 +79,67 @@ def main():
                          'sample': f'{k} slice x {m} events through oracle.voxel_grid_trilinear'},
         'max_abs_err_vs_oracle_slice0': err,
     }))
+
+
+def ingest(a):
+    import numpy as np
+    from ess_amd import hip
+    from ess_amd.datasets.data_util import pack_event_records
+    hip.lib()
+    S, n, C, H, W = a.slices, a.events, a.bins, a.height, a.width
+    g = np.random.default_rng(0)
+    host = np.zeros((S, n), dtype=hip.EVENT_RECORD)
+    atomics = 0
+    for s in range(S):
+        t = np.sort(g.uniform(0, 0.03, n))
+        ev = np.stack([t, g.integers(0, W, n).astype(np.float64), g.integers(0, H, n).astype(np.float64), g.integers(0, 2, n).astype(np.float64)], 1)
+        pack_event_records(ev, host[s])
+        ts = (C - 1) * (t - t[0]) / (t[-1] - t[0])
+        dts = ts - np.floor(ts)
+        # (the left half always, unless it rounds to zero; the right half where its bin exists and it is not zero)
+        atomics += int(np.count_nonzero((1.0 - dts).astype(np.float32))) + int(np.count_nonzero((dts.astype(np.float32) != 0) & (np.floor(ts) + 1 < C)))
+    dev = torch.device('cuda:0')
+    records = torch.from_numpy(host.view(np.uint8).reshape(S, n, 16)).to(dev)
+    counts, zero = torch.full((S,), n, dtype=torch.int32, device=dev), torch.zeros(S, dtype=torch.int32, device=dev)
+    acc = torch.zeros(S, C, H, W, dtype=torch.int64, device=dev)
+    out = torch.empty(S, C, H, W, device=dev)
+    x = torch.from_numpy(host['x'].astype(np.int32).ravel()).to(dev)
+    y = torch.from_numpy(host['y'].astype(np.int32).ravel()).to(dev)
+    t = torch.from_numpy(host['t'].ravel().copy()).to(dev)
+    p = torch.from_numpy(host['p'].astype(np.float32).ravel()).to(dev)
+    offs = torch.tensor([i * n for i in range(S + 1)])
+    ways = {'voxel_grid_temporal': lambda: hip.voxel_grid_temporal(x, y, t, p, offs, C, H, W, separate_pol=False),
+            'event_ingest': lambda: hip.event_ingest(records, counts, out, acc=acc),
+            'event_ingest_finish_only': lambda: hip.event_ingest(records, zero, out, acc=acc)}
+    for fn in ways.values():  # warm-up: clocks, allocator
+        for _ in range(50):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in ways}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(3):  # alternating: drift of the box hits every way alike
+        for k, fn in ways.items():
+            e0.record()
+            for _ in range(a.reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / a.reps)
+    ref = hip.voxel_grid_temporal(x, y, t, p, offs, C, H, W, separate_pol=False)
+    got = hip.event_ingest(records, counts, out, acc=acc)
+    err = (got - ref).abs().max().item()
+    assert err <= 1e-5 * max(1.0, ref.abs().max().item()) and not bool(acc.any()), err
+    med = {k: sorted(v)[1] for k, v in ms.items()}
+    scatter_ms = med['event_ingest'] - med['event_ingest_finish_only']
+    print(json.dumps({
+        'metric': 'events -> voxel grids (temporal, one signed grid per stream), ms per batch', 'unit': 'ms',
+        'config': {'workload': f'{S} streams x {n} events -> [{S},{C},{H},{W}] fp32', 'reps': a.reps},
+        'ms_per_batch': {k: {'median': round(med[k], 5), 'min': round(min(v), 5), 'max': round(max(v), 5)} for k, v in ms.items()},
+        'scatter_ms': round(scatter_ms, 5), 'atomics_per_batch': atomics,
+        'int64_atomics_per_s': atomics / (scatter_ms * 1e-3) if scatter_ms > 0 else None,
+        'fp32_atomics_per_s_of_voxel_grid_temporal_incl_memset': atomics / (med['voxel_grid_temporal'] * 1e-3),
+        'finish_GBps': S * C * H * W * 12 / (med['event_ingest_finish_only'] * 1e-3) / 1e9,
+        'max_abs_diff_ingest_vs_temporal': err, 'data': 'synthetic'}))
 
 
 if __name__ == '__main__':
