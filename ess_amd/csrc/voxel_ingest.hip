@@ -1,5 +1,6 @@
-// Event ingest for the captured multi-stream round: packed 16-byte event records -> the round's voxel grids, with a sum that does
-// not depend on the order the events arrive in (ess_event_ingest, include/ess_hip.h).
+// Event ingest for the captured multi-stream round: packed 16-byte event records (ess_event_ingest) or the raw event columns a
+// camera delivers (ess_event_ingest_columns) -> the round's voxel grids, with a sum that does not depend on the order the events
+// arrive in (include/ess_hip.h).  The two sources differ in how an event is LOADED; what an event adds is one function, scatter_event.
 //
 // voxel_temporal_kernel (voxel.hip) adds its fp32 contributions with fp32 global atomics: a voxel's value depends on which event
 // got there first, two builds of one window differ in the last bits.  Here every contribution is the SAME fp32 value (the same
@@ -40,10 +41,29 @@ __device__ __forceinline__ double record_time(const uint4* __restrict__ rec, int
 // c -> q = llrint(c * 2^40): the product is exact in fp64 (24 significant bits, exponent shift), one rounding to the integer
 __device__ __forceinline__ long long quantise(float c) { return __double2ll_rn((double)c * INGEST_SCALE); }
 
+// One event's two contributions, whatever source it was loaded from: the fp64 expressions of voxel_temporal_kernel rounded to fp32,
+// each added as a 64-bit integer.  p: +1 where the word equals 1, -1 otherwise.
+__device__ __forceinline__ void scatter_event(double t, int xs, int ys, int p, double first, double dT, int nb, int H, int W, size_t plane,
+                                              long long* __restrict__ g) {
+#pragma clang fp contract(off)  // (no fused multiply-add may change a per-event value: the results are compared as bits)
+  const double ts = ((double)(nb - 1) * (t - first)) / dT;
+  if (!(xs < W && xs >= 0 && ys < H && ys >= 0 && ts >= 0 && ts < nb)) return;  // (a NaN time fails both comparisons)
+  const int ti = (int)ts;
+  const double dts = ts - ti;
+  // |polarity| = 1: the record carries -1 / +1 (any other word counts as -1, so no record can leave the int64 range)
+  const float left = (float)(1.0 - dts), right = (float)dts;
+  const float sign = p == 1 ? 1.f : -1.f;
+  long long* gp = g + (size_t)ys * W + xs;
+  const long long ql = quantise(sign * left), qr = quantise(sign * right);
+  // (ti < nb holds; a zero adds nothing)
+  if (ql != 0) atomicAdd((unsigned long long*)(gp + (size_t)ti * plane), (unsigned long long)ql);
+  if (ti + 1 < nb && qr != 0) atomicAdd((unsigned long long*)(gp + (size_t)(ti + 1) * plane), (unsigned long long)qr);
+}
+
 __global__ __launch_bounds__(INGEST_THREADS) void event_scatter_kernel(const uint4* __restrict__ records, const int32_t* __restrict__ counts,
                                                                        int64_t capacity, int nb, int H, int W,
                                                                        long long* __restrict__ acc) {
-#pragma clang fp contract(off)  // (no fused multiply-add may change a per-event value: the results are compared as bits)
+#pragma clang fp contract(off)
   const int s = blockIdx.y;
   const int cnt = counts[s];
   if (cnt <= 0) return;  // an empty window, or INGEST_KEEP: nothing of this stream is read
@@ -58,22 +78,66 @@ __global__ __launch_bounds__(INGEST_THREADS) void event_scatter_kernel(const uin
     double t;
     int xs, ys, p;
     unpack_record(rec[e], t, xs, ys, p);
-    const double ts = ((double)(nb - 1) * (t - first)) / dT;
-    if (!(xs < W && xs >= 0 && ys < H && ys >= 0 && ts >= 0 && ts < nb)) continue;  // (a NaN time fails both comparisons)
-    const int ti = (int)ts;
-    const double dts = ts - ti;
-    // |polarity| = 1: the record carries -1 / +1 (any other word counts as -1, so no record can leave the int64 range)
-    const float left = (float)(1.0 - dts), right = (float)dts;
-    const float sign = p == 1 ? 1.f : -1.f;
-    long long* gp = g + (size_t)ys * W + xs;
-    const long long ql = quantise(sign * left), qr = quantise(sign * right);
-    // (ti < nb holds; a zero adds nothing)
-    if (ql != 0) atomicAdd((unsigned long long*)(gp + (size_t)ti * plane), (unsigned long long)ql);
-    if (ti + 1 < nb && qr != 0) atomicAdd((unsigned long long*)(gp + (size_t)(ti + 1) * plane), (unsigned long long)qr);
+    scatter_event(t, xs, ys, p, first, dT, nb, H, W, plane, g);
   }
 }
 
+// ---- the column source: t [S][stride] 8 bytes, x / y [S][stride] 2 bytes, p [S][stride] 1 byte per event, as a camera or a DSEC file
+// delivers them.  formats[s] says how stream s's words are read (ESS_EVCOL_*): a device word, so one captured launch serves rounds
+// whose streams change their formats.  stride is a multiple of COLUMN_GROUP * 4, so every row of every column starts 16-byte aligned
+// and a lane's group of COLUMN_GROUP consecutive events -- 2 x 16 B of t, 8 B of x, 8 B of y, 4 B of p -- never reaches the stride.
 typedef long long i64x2 __attribute__((ext_vector_type(2)));
+constexpr int COLUMN_GROUP = 4;
+constexpr int COLUMN_STRIDE_ALIGN = 16;
+constexpr int EVCOL_T_I64 = 1, EVCOL_XY_U16 = 2;  // (ESS_EVCOL_T_I64, ESS_EVCOL_XY_U16 of include/ess_hip.h)
+
+// an int64 time enters as (double)t: exact below 2^53
+__device__ __forceinline__ double column_time(long long word, bool t_i64) { return t_i64 ? (double)word : __longlong_as_double(word); }
+
+// a uint16 coordinate enters as its unsigned value (32768.. lie outside every grid: dropped, never wrapped)
+__device__ __forceinline__ int column_coordinate(unsigned half, bool xy_u16) { return xy_u16 ? (int)half : (int)(short)half; }
+
+__global__ __launch_bounds__(INGEST_THREADS) void event_scatter_columns_kernel(const long long* __restrict__ t, const unsigned short* __restrict__ x,
+                                                                               const unsigned short* __restrict__ y,
+                                                                               const unsigned char* __restrict__ p,
+                                                                               const int32_t* __restrict__ counts,
+                                                                               const int32_t* __restrict__ formats, int64_t stride, int nb, int H,
+                                                                               int W, long long* __restrict__ acc) {
+#pragma clang fp contract(off)
+  const int s = blockIdx.y;
+  const int cnt = counts[s];
+  const int fmt = formats[s];  // (read beside the count, not behind the test on it: the two scalar loads issue together)
+  if (cnt <= 0) return;  // an empty window, or INGEST_KEEP: nothing of this stream's columns is read
+  if ((fmt & ~(EVCOL_T_I64 | EVCOL_XY_U16)) != 0) return;  // an unknown format: as count 0
+  const bool t_i64 = (fmt & EVCOL_T_I64) != 0, xy_u16 = (fmt & EVCOL_XY_U16) != 0;
+  const int64_t n = (int64_t)cnt < stride ? (int64_t)cnt : stride;
+  const size_t row = (size_t)s * stride;
+  const long long* __restrict__ ts = t + row;
+  const double first = column_time(ts[0], t_i64);
+  double dT = column_time(ts[n - 1], t_i64) - first;
+  if (dT == 0) dT = 1.0;
+  const size_t plane = (size_t)H * W;
+  long long* __restrict__ g = acc + (size_t)s * nb * plane;
+  const i64x2* __restrict__ t2 = (const i64x2*)ts;               // two events
+  const uint2* __restrict__ x4 = (const uint2*)(x + row);        // COLUMN_GROUP events
+  const uint2* __restrict__ y4 = (const uint2*)(y + row);
+  const unsigned* __restrict__ p4 = (const unsigned*)(p + row);
+  const int64_t groups = (n + COLUMN_GROUP - 1) / COLUMN_GROUP;  // (the last one may be partial: 4 * q + 3 < stride all the same)
+  for (int64_t q = (int64_t)blockIdx.x * INGEST_THREADS + threadIdx.x; q < groups; q += (int64_t)gridDim.x * INGEST_THREADS) {
+    const i64x2 ta = t2[2 * q], tb = t2[2 * q + 1];
+    const uint2 xv = x4[q], yv = y4[q];
+    const unsigned pv = p4[q];
+    const long long tw[COLUMN_GROUP] = {ta[0], ta[1], tb[0], tb[1]};
+    const unsigned xh[COLUMN_GROUP] = {xv.x & 0xffffu, xv.x >> 16, xv.y & 0xffffu, xv.y >> 16};
+    const unsigned yh[COLUMN_GROUP] = {yv.x & 0xffffu, yv.x >> 16, yv.y & 0xffffu, yv.y >> 16};
+#pragma unroll
+    for (int j = 0; j < COLUMN_GROUP; ++j) {
+      if (q * COLUMN_GROUP + j >= n) break;  // (the tail: loaded, inside the stride, never summed)
+      scatter_event(column_time(tw[j], t_i64), column_coordinate(xh[j], xy_u16), column_coordinate(yh[j], xy_u16),
+                    (int)((pv >> (8 * j)) & 0xffu), first, dT, nb, H, W, plane, g);
+    }
+  }
+}
 
 __device__ __forceinline__ float dequantise(long long a) { return (float)a * INGEST_INV_SCALE; }
 
@@ -108,6 +172,26 @@ __global__ __launch_bounds__(INGEST_THREADS) void event_finish_kernel(const int3
   }
 }
 
+// the scatter grid: from the capacity alone (a captured launch), INGEST_EVENTS_PER_THREAD events a thread at full capacity
+unsigned scatter_blocks(int64_t capacity) {
+  const int64_t bx = ceil_div64(capacity, (int64_t)INGEST_THREADS * INGEST_EVENTS_PER_THREAD);
+  return (unsigned)(bx > INGEST_MAX_BLOCKS_X ? INGEST_MAX_BLOCKS_X : bx);
+}
+
+int launch_finish(const int32_t* counts, int32_t n_streams, int32_t bins, int32_t height, int32_t width, void* acc, float* out, hipStream_t st,
+                  const char* what) {
+  const int64_t per = (int64_t)bins * height * width;
+  const bool vec = (per & 3) == 0;
+  int64_t fx = ceil_div64(vec ? per >> 2 : per, (int64_t)INGEST_THREADS * INGEST_QUADS_PER_THREAD);
+  if (fx > INGEST_MAX_BLOCKS_X) fx = INGEST_MAX_BLOCKS_X;
+  const dim3 fgrid((unsigned)fx, (unsigned)n_streams);
+  if (vec)
+    hipLaunchKernelGGL(event_finish_kernel<true>, fgrid, dim3(INGEST_THREADS), 0, st, counts, per, (long long*)acc, out);
+  else
+    hipLaunchKernelGGL(event_finish_kernel<false>, fgrid, dim3(INGEST_THREADS), 0, st, counts, per, (long long*)acc, out);
+  return ess_launch_status(what);
+}
+
 }  // namespace
 
 extern "C" size_t ess_event_ingest_workspace(int32_t n_streams, int32_t bins, int32_t height, int32_t width) {
@@ -129,20 +213,36 @@ extern "C" int ess_event_ingest(const void* records, const int32_t* counts, int6
   ESS_CHECK_ARG((((uintptr_t)records) & 15) == 0 && (((uintptr_t)acc) & 15) == 0 && (((uintptr_t)out) & 15) == 0,
                 "event_ingest: records, acc and out must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  const int64_t per = (int64_t)bins * height * width;
-  int64_t bx = ceil_div64(capacity, (int64_t)INGEST_THREADS * INGEST_EVENTS_PER_THREAD);
-  if (bx > INGEST_MAX_BLOCKS_X) bx = INGEST_MAX_BLOCKS_X;
-  hipLaunchKernelGGL(event_scatter_kernel, dim3((unsigned)bx, (unsigned)n_streams), dim3(INGEST_THREADS), 0, st, (const uint4*)records, counts,
-                     capacity, bins, height, width, (long long*)acc);
+  hipLaunchKernelGGL(event_scatter_kernel, dim3(scatter_blocks(capacity), (unsigned)n_streams), dim3(INGEST_THREADS), 0, st,
+                     (const uint4*)records, counts, capacity, bins, height, width, (long long*)acc);
   int rc = ess_launch_status("event_ingest(scatter)");
   if (rc) return rc;
-  const bool vec = (per & 3) == 0;
-  int64_t fx = ceil_div64(vec ? per >> 2 : per, (int64_t)INGEST_THREADS * INGEST_QUADS_PER_THREAD);
-  if (fx > INGEST_MAX_BLOCKS_X) fx = INGEST_MAX_BLOCKS_X;
-  const dim3 fgrid((unsigned)fx, (unsigned)n_streams);
-  if (vec)
-    hipLaunchKernelGGL(event_finish_kernel<true>, fgrid, dim3(INGEST_THREADS), 0, st, counts, per, (long long*)acc, out);
-  else
-    hipLaunchKernelGGL(event_finish_kernel<false>, fgrid, dim3(INGEST_THREADS), 0, st, counts, per, (long long*)acc, out);
-  return ess_launch_status("event_ingest(finish)");
+  return launch_finish(counts, n_streams, bins, height, width, acc, out, st, "event_ingest(finish)");
+}
+
+extern "C" int ess_event_ingest_columns(const void* t, const void* x, const void* y, const void* p, const int32_t* counts,
+                                        const int32_t* formats, int64_t stride, int32_t n_streams, int32_t bins, int32_t height,
+                                        int32_t width, void* acc, size_t acc_bytes, float* out, ess_stream_t stream) {
+  ESS_CHECK_ARG(t && x && y && p && counts && formats && acc && out,
+                "event_ingest_columns: null t, x, y, p, counts, formats, acc or out");
+  ESS_CHECK_ARG(n_streams >= 1 && n_streams <= 65535, "event_ingest_columns: n_streams=%d (1..65535)", (int)n_streams);
+  ESS_CHECK_ARG(bins > 0 && height > 0 && width > 0, "event_ingest_columns: bins=%d height=%d width=%d must be positive", (int)bins,
+                (int)height, (int)width);
+  ESS_CHECK_ARG(stride >= 1 && stride <= INGEST_MAX_CAPACITY,
+                "event_ingest_columns: stride=%lld events per stream (1..%lld: the int64 sums hold 2^22 contributions of magnitude 1 at scale 2^40)",
+                (long long)stride, (long long)INGEST_MAX_CAPACITY);
+  ESS_CHECK_ARG(stride % COLUMN_STRIDE_ALIGN == 0,
+                "event_ingest_columns: stride=%lld must be a multiple of %d (every stream's row of every column starts 16-byte aligned)",
+                (long long)stride, COLUMN_STRIDE_ALIGN);
+  const size_t need = ess_event_ingest_workspace(n_streams, bins, height, width);
+  ESS_CHECK_ARG(acc_bytes >= need, "event_ingest_columns: acc has %zu bytes, %zu are needed", acc_bytes, need);
+  ESS_CHECK_ARG(((((uintptr_t)t) | ((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)p) | ((uintptr_t)acc) | ((uintptr_t)out)) & 15) == 0,
+                "event_ingest_columns: t, x, y, p, acc and out must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(event_scatter_columns_kernel, dim3(scatter_blocks(stride), (unsigned)n_streams), dim3(INGEST_THREADS), 0, st,
+                     (const long long*)t, (const unsigned short*)x, (const unsigned short*)y, (const unsigned char*)p, counts, formats, stride,
+                     bins, height, width, (long long*)acc);
+  int rc = ess_launch_status("event_ingest_columns(scatter)");
+  if (rc) return rc;
+  return launch_finish(counts, n_streams, bins, height, width, acc, out, st, "event_ingest_columns(finish)");
 }

@@ -77,7 +77,7 @@ EXPORTS = [
     'ess_label_confusion', 'ess_augment_perspective_filter', 'ess_tuning_set', 'ess_tuning_get', 'ess_conv2d_s2d_preferred',
     'ess_to_f16_c8', 'ess_bf16_c8_to_f16_c8', 'ess_f16_c8_to_bf16_c8', 'ess_instnorm_forward_c8_mixed', 'ess_seg_head',
     'ess_event_normalize_samples', 'ess_state_carry_masked', 'ess_state_carry_indexed',
-    'ess_event_ingest_workspace', 'ess_event_ingest',
+    'ess_event_ingest_workspace', 'ess_event_ingest', 'ess_event_ingest_columns',
 ]
 
 
@@ -173,6 +173,7 @@ def lib():
             'ess_state_carry_masked': [P, P, P, I, I, P, P],
             'ess_state_carry_indexed': [P, P, P, I, I, I, I, P, P, P],
             'ess_event_ingest': [P, P, I64, I, I, I, I, P, c_size_t, P, P],
+            'ess_event_ingest_columns': [P, P, P, P, P, P, I64, I, I, I, I, P, c_size_t, P, P],
         }
         for name, argtypes in sig.items():
             fn = getattr(L, name)
@@ -866,6 +867,61 @@ def event_ingest(records, counts, out, acc=None):
         raise EssHipError(f'event_ingest: acc must be int64, got {acc.dtype}')
     _check(L.ess_event_ingest(c_void_p(records.data_ptr()), ptr(counts, torch.int32), records.shape[1], S, bins, H, W,
                               c_void_p(acc.data_ptr()), acc.numel() * 8, c_void_p(out.data_ptr()), stream()), 'ess_event_ingest')
+    return out
+
+
+# The column source of the ingest (ess_event_ingest_columns): the per-stream format word's bits, and the row stride of a capacity
+EVCOL_T_I64 = 1   # ESS_EVCOL_T_I64: t is int64 (else float64)
+EVCOL_XY_U16 = 2  # ESS_EVCOL_XY_U16: x / y are uint16 (else int16)
+EVCOL_STRIDE_ALIGN = 16
+
+
+def event_column_stride(capacity):
+    """events per stream -> the row stride of the column buffers: rounded up so that every stream's row of every column (the
+    1-byte polarities too) starts 16-byte aligned"""
+    return -(-int(capacity) // EVCOL_STRIDE_ALIGN) * EVCOL_STRIDE_ALIGN
+
+
+_EVCOL_DTYPES = {'t': (torch.int64, torch.float64), 'x': (torch.int16,) + ((torch.uint16,) if hasattr(torch, 'uint16') else ()),
+                 'p': (torch.uint8, torch.int8, torch.bool)}
+_EVCOL_DTYPES['y'] = _EVCOL_DTYPES['x']
+
+
+def event_ingest_columns(t, x, y, p, counts, formats, out, acc=None):
+    """event_ingest from raw event columns: the same grids, bit for bit, as event_ingest gives on the same events.
+    t, x, y, p: device [S, stride] -- t 8 bytes per event (int64 or float64), x / y 2 bytes (int16 or uint16), p 1 byte (uint8, int8
+    or bool); the tensors' dtypes only size the words: how stream s's words are READ says formats[s] (EVCOL_T_I64 | EVCOL_XY_U16; any
+    other bit: the stream counts as empty), a device int32 [S] read by the kernel like counts, so one captured call serves streams
+    whose formats change from round to round.  p: +1 where the byte equals 1, -1 otherwise.  stride: a multiple of 16
+    (event_column_stride).  counts, out, acc: as event_ingest."""
+    named = (('t', t), ('x', x), ('y', y), ('p', p), ('counts', counts), ('formats', formats), ('out', out))
+    for name, v in named + ((('acc', acc),) if acc is not None else ()):
+        if not torch.is_tensor(v) or not v.is_cuda:
+            raise EssHipError(f'event_ingest_columns: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+        if not v.is_contiguous():
+            raise EssHipError(f'event_ingest_columns: {name} must be contiguous')
+    if out.dim() != 4 or out.dtype != torch.float32 or out.numel() == 0:
+        raise EssHipError(f'event_ingest_columns: out must be a non-empty fp32 [S, bins, H, W] tensor, got {out.dtype}{tuple(out.shape)}')
+    S, bins, H, W = out.shape
+    if t.dim() != 2 or t.shape[0] != S or t.shape[1] < 1:
+        raise EssHipError(f'event_ingest_columns: t must be [{S}, stride], got {tuple(t.shape)}')
+    for name, v in named[:4]:
+        if v.dtype not in _EVCOL_DTYPES[name] or v.shape != t.shape:
+            raise EssHipError(f'event_ingest_columns: {name} must be {" / ".join(str(d) for d in _EVCOL_DTYPES[name])} '
+                              f'{list(t.shape)}, got {v.dtype}{tuple(v.shape)}')
+    for name, v in named[4:6]:
+        if v.dtype != torch.int32 or tuple(v.shape) != (S,):
+            raise EssHipError(f'event_ingest_columns: {name} must be int32 [{S}], got {v.dtype}{tuple(v.shape)}')
+    L = lib()
+    need = L.ess_event_ingest_workspace(S, bins, H, W)
+    if acc is None:
+        acc = torch.zeros(need // 8, dtype=torch.int64, device=out.device)
+    elif acc.dtype != torch.int64:
+        raise EssHipError(f'event_ingest_columns: acc must be int64, got {acc.dtype}')
+    _check(L.ess_event_ingest_columns(c_void_p(t.data_ptr()), c_void_p(x.data_ptr()), c_void_p(y.data_ptr()), c_void_p(p.data_ptr()),
+                                      ptr(counts, torch.int32), ptr(formats, torch.int32), t.shape[1], S, bins, H, W,
+                                      c_void_p(acc.data_ptr()), acc.numel() * 8, c_void_p(out.data_ptr()), stream()),
+           'ess_event_ingest_columns')
     return out
 
 

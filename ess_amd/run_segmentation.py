@@ -283,6 +283,44 @@ def _event_capacity(n, height, width):
     return n
 
 
+EVENT_LAYOUTS = ('records', 'columns')
+
+
+def _event_layout(layout, event_capacity):
+    """MultiStreamSegmenter's event_layout argument, checked against event_capacity (the argument as given) -> the layout"""
+    if layout not in EVENT_LAYOUTS:
+        raise hip.EssHipError(f'event_layout={layout!r}: one of {EVENT_LAYOUTS}')
+    if event_capacity is None and layout != 'records':
+        raise hip.EssHipError(f'event_layout={layout!r} needs event_capacity: without it no ingest buffers exist')
+    return layout
+
+
+def check_stream_columns(events, n_streams):
+    """events: S entries, each a datasets.data_util.EventColumns or None / empty (idle) -> (list of EventColumns or None, active)"""
+    from .datasets.data_util import EventColumns
+    if not isinstance(events, (list, tuple)) or len(events) != n_streams:
+        n = len(events) if isinstance(events, (list, tuple)) else type(events).__name__
+        raise hip.EssHipError(f'events must be a list with one entry per stream: got {n}, the segmenter serves n_streams={n_streams}')
+    out = []
+    for s, e in enumerate(events):
+        if e is not None and not isinstance(e, EventColumns):
+            raise hip.EssHipError(f"events[{s}] must be an EventColumns or None with event_layout='columns', got {type(e).__name__}: hand the "
+                                  'columns over as they arrive, EventColumns(t, x, y, p); EventColumns.from_rows converts [N, 4] rows (the slow way)')
+        out.append(e if e is not None and e.n else None)
+    return out, [e is not None for e in out]
+
+
+class _ColumnStage:
+    """one pinned staging set of the column ingest: the four columns [S, stride] and the words [2, S] (counts, formats) as torch
+    (pinned) and as numpy views, the event recorded behind the set's last upload, and the (slot, events) pairs staged for the next"""
+    __slots__ = ('cols', 'words', 'cols_np', 'counts_np', 'formats_np', 'done', 'used')
+
+    def __init__(self, cols, words, done):
+        self.cols, self.words, self.done, self.used = cols, words, done, ()
+        self.cols_np = tuple(c.numpy() for c in cols)
+        self.counts_np, self.formats_np = words.numpy()[0], words.numpy()[1]
+
+
 class _IngestStage:
     """one pinned staging set of the event ingest: records / counts (torch, pinned), their numpy views, the event recorded behind
     the set's last upload, and the (slot, rows) pairs staged for the next one"""
@@ -294,7 +332,7 @@ class _IngestStage:
 
 class MultiStreamSegmenter(GraphedWindowState):
     """n_streams independent sequences, one ROUND (one window of every active stream) at a time, as one batch.
-    update(grids [S, num_bins, H, W], active=None) / update_from_events(list of S [N, 4] arrays or None) -> MultiSegmentationResult;
+    update(grids [S, num_bins, H, W], active=None) / update_from_events(list of S [N, 4] arrays -- event_layout='columns': EventColumns -- or None) -> MultiSegmentationResult;
     reset(streams=None): these streams (default: all) start from a zero state at their next active window.
 
     Each stream's labels, colours and confidences are those it would get alone in a MultiStreamSegmenter(n_streams=1): normalisation
@@ -326,10 +364,17 @@ class MultiStreamSegmenter(GraphedWindowState):
     function of the events: run to run, batched or alone, compacted or not.  update(grids) writes the count word INGEST_KEEP for
     every stream and copies the grids in as without.  Allocated once: device records [S, N, 16], counts [S], the int64 sums
     [S, num_bins, H, W], and two pinned staging sets used alternately (the host waits for a set's last upload before rewriting
-    it); a compacted round stages its records in slot order into the first `bucket` records, padded slots with count 0."""
+    it); a compacted round stages its records in slot order into the first `bucket` records, padded slots with count 0.
+
+    event_layout='columns' (with event_capacity; 'records', the default, is the path above): update_from_events takes, per stream,
+    a datasets.data_util.EventColumns -- t float64 or int64, x / y int16 or uint16, p one byte, as a camera or a DSEC file delivers
+    them -- or None, and the round starts with hip.event_ingest_columns.  The host does no arithmetic: staging is four copies per
+    stream into pinned columns (13 bytes per event), then their used prefixes, the counts and the per-stream format words go to
+    static device columns [S, stride].  The format is a device word like the count, so streams may change their dtypes from round
+    to round under the one capture.  Labels, colours and confidences equal the record path's on the same events bit for bit."""
 
     def __init__(self, encoder, decoder, height, width, options, n_streams, device=None, graph=False, copy=True, palette=None,
-                 want_confidence=False, out_hw=None, compact=False, compact_buckets=None, event_capacity=None):
+                 want_confidence=False, out_hw=None, compact=False, compact_buckets=None, event_capacity=None, event_layout='records'):
         if not isinstance(n_streams, int) or isinstance(n_streams, bool) or n_streams < 1:
             raise hip.EssHipError(f'n_streams={n_streams!r}: a positive number of streams is needed')
         self.compact = bool(compact)
@@ -359,15 +404,16 @@ class MultiStreamSegmenter(GraphedWindowState):
         self._in = torch.zeros(S, self.num_bins, height, width, dtype=torch.float32, device=self.device)
         self._modes = torch.zeros(2, S, dtype=torch.int32, device=self.device)  # [0]: in front of the step, [1]: behind it
         self._pending = [True] * S
+        self.event_layout = _event_layout(event_layout, event_capacity)
         self.event_capacity = None if event_capacity is None else _event_capacity(event_capacity, height, width)
         if self.event_capacity is not None:
-            self._build_ingest()
+            self._build_ingest() if self.event_layout == 'records' else self._build_ingest_columns()
         self._build_state()
         if self.buckets:
             self._build_compact()
 
     # ---- event ingest (event_capacity=N): static record / count buffers the captured round reads, pinned staging in front of them
-    event_capacity = _records = _counts = _acc = None
+    event_capacity = _records = _columns = _counts = _formats = _acc = None
 
     def _build_ingest(self):
         """Device records [S, N, 16], counts [S] and the int64 sums of hip.event_ingest (zeroed here, once), and two pinned staging
@@ -383,6 +429,33 @@ class MultiStreamSegmenter(GraphedWindowState):
             cnt = torch.full((S,), hip.INGEST_KEEP, dtype=torch.int32).pin_memory()
             self._stage.append(_IngestStage(rec, cnt, rec.numpy().view(hip.EVENT_RECORD).reshape(S, N), cnt.numpy(), torch.cuda.Event()))
         self._stage_next = 0
+
+    def _build_ingest_columns(self):
+        """event_layout='columns': the four device columns [S, stride] (t as raw 8-byte words, x / y as raw 2-byte words, p as
+        bytes; stride = the capacity rounded up so that every row starts 16-byte aligned), the words [2, S] -- counts and formats,
+        one upload -- and the int64 sums of hip.event_ingest_columns, and two pinned staging sets of the same, used alternately
+        under _next_stage's rule.  A compacted round reads the first `bucket` rows."""
+        S, stride = self.n_streams, hip.event_column_stride(self.event_capacity)
+        dtypes = (torch.int64, torch.int16, torch.int16, torch.uint8)
+        self._columns = tuple(torch.zeros(S, stride, dtype=d, device=self.device) for d in dtypes)
+        self._words = torch.zeros(2, S, dtype=torch.int32, device=self.device)
+        self._counts, self._formats = self._words[0], self._words[1]
+        self._counts.fill_(hip.INGEST_KEEP)
+        self._acc = torch.zeros(S, self.num_bins, self.height, self.width, dtype=torch.int64, device=self.device)
+        self._stage = []
+        for _ in range(2):
+            words = torch.zeros(2, S, dtype=torch.int32).pin_memory()
+            words[0].fill_(hip.INGEST_KEEP)
+            self._stage.append(_ColumnStage(tuple(torch.zeros(S, stride, dtype=d).pin_memory() for d in dtypes), words, torch.cuda.Event()))
+        self._stage_next = 0
+
+    def _ingest(self, ev, b=None):
+        """the round's first launches: the static event buffers (b: their first b slots) -> the grids ev, inside the capture"""
+        cut = (lambda v: v) if b is None else (lambda v: v[:b])
+        if self._columns is not None:
+            hip.event_ingest_columns(*(cut(c) for c in self._columns), cut(self._counts), cut(self._formats), ev, self._acc)
+        else:
+            hip.event_ingest(cut(self._records), cut(self._counts), ev, self._acc)
 
     def _next_stage(self):
         """the staging set of this round, free to be rewritten: its last upload has completed (in practice long ago -- a whole
@@ -421,11 +494,37 @@ class MultiStreamSegmenter(GraphedWindowState):
         st.used = tuple(used)
         return st
 
+    def _stage_columns(self, slots):
+        """_stage_events for event_layout='columns': slots hold EventColumns or None; per staged slot four copies into the pinned
+        columns (datasets.data_util.stage_event_columns), its count and its format word"""
+        from .datasets.data_util import stage_event_columns
+        for i, e in enumerate(slots):
+            if e is not None and e.n > self.event_capacity:
+                raise hip.EssHipError(f'update_from_events: a window of {e.n} events (slot {i}) exceeds event_capacity={self.event_capacity}')
+        st = self._next_stage()
+        st.counts_np[:] = 0
+        st.formats_np[:] = 0
+        used = []
+        for i, e in enumerate(slots):
+            if e is not None:
+                st.counts_np[i] = stage_event_columns(e, *(c[i] for c in st.cols_np))
+                st.formats_np[i] = e.format
+                used.append((i, e.n))
+        st.used = tuple(used)
+        return st
+
     def _upload(self, st):
-        """the staged counts and the used prefix of every staged slot -> the static device buffers, on the current stream"""
-        for i, n in st.used:
-            self._records[i, :n].copy_(st.records[i, :n], non_blocking=True)
-        self._counts.copy_(st.counts, non_blocking=True)
+        """the staged counts (and formats) and the used prefix of every staged slot -> the static device buffers, on the current
+        stream"""
+        if self._columns is not None:
+            for i, n in st.used:
+                for dev, host in zip(self._columns, st.cols):
+                    dev[i, :n].copy_(host[i, :n], non_blocking=True)
+            self._words.copy_(st.words, non_blocking=True)
+        else:
+            for i, n in st.used:
+                self._records[i, :n].copy_(st.records[i, :n], non_blocking=True)
+            self._counts.copy_(st.counts, non_blocking=True)
         st.done.record()
 
     @classmethod
@@ -531,7 +630,7 @@ class MultiStreamSegmenter(GraphedWindowState):
             gather.run(tab[0], tab[1])  # slot <- its stream's state; restarting streams and padded slots: 0
             ev = self.compact_input[:b]
             if self.event_capacity is not None:  # (count words INGEST_KEEP: the grids the caller copied in stay)
-                hip.event_ingest(self._records[:b], self._counts[:b], ev, self._acc)
+                self._ingest(ev, b)
             for x, y in pre.hot_pixel_locations:
                 ev[:, :, y, x] = 0
             if pre.flip:
@@ -632,7 +731,7 @@ class MultiStreamSegmenter(GraphedWindowState):
             self._pre.run(self._modes[0])  # restarting streams: state = 0
             ev = self._in
             if self.event_capacity is not None:  # (count words INGEST_KEEP: the grids the caller copied in stay)
-                hip.event_ingest(self._records, self._counts, ev, self._acc)
+                self._ingest(ev)
             for x, y in pre.hot_pixel_locations:
                 ev[:, :, y, x] = 0
             if pre.flip:
@@ -727,14 +826,18 @@ class MultiStreamSegmenter(GraphedWindowState):
         return self._update_compact(plan, grids, active, True)
 
     def _update_from_events_ingest(self, events):
-        """event_capacity=N: each active stream's rows are packed on the host into pinned 16-byte records (a compacted round: in slot
-        order), their used prefixes and the count words are copied to the static device buffers, and the round's own first launches
-        (hip.event_ingest, inside the capture) build the grids: idle streams and padded slots have count 0, an all-zero grid.  The
+        """event_capacity=N: each active stream's rows are packed on the host into pinned 16-byte records (event_layout='columns':
+        its EventColumns are copied into pinned columns as they are; a compacted round: in slot order), their used prefixes and the
+        count (and format) words are copied to the static device buffers, and the round's own first launches (hip.event_ingest or
+        hip.event_ingest_columns, inside the capture) build the grids: idle streams and padded slots have count 0, an all-zero grid.  The
         labels are a pure function of the events: the ingest's sums do not depend on arrival order."""
-        evs, active = check_stream_events(events, self.n_streams)
-        evs = [None if e is None else e.detach().cpu().numpy() for e in evs]
+        if self._columns is not None:
+            (evs, active), stage = check_stream_columns(events, self.n_streams), self._stage_columns
+        else:
+            (evs, active), stage = check_stream_events(events, self.n_streams), self._stage_events
+            evs = [None if e is None else e.detach().cpu().numpy() for e in evs]
         self._check_compute()
         plan = compact_plan(self._pending, active, self.buckets) if self.buckets else None
         if plan is None:
-            return self._ride_along(None, active, self._stage_events(evs))
-        return self._update_compact(plan, None, active, True, self._stage_events([evs[s] for s in plan.rows]))
+            return self._ride_along(None, active, stage(evs))
+        return self._update_compact(plan, None, active, True, stage([evs[s] for s in plan.rows]))

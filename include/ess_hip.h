@@ -422,6 +422,20 @@ enum { ESS_INGEST_KEEP = -1 };
 size_t ess_event_ingest_workspace(int32_t n_streams, int32_t bins, int32_t height, int32_t width);
 int ess_event_ingest(const void* records, const int32_t* counts, int64_t capacity, int32_t n_streams, int32_t bins, int32_t height,
                      int32_t width, void* acc, size_t acc_bytes, float* out, ess_stream_t stream);
+/* The same ingest from the raw event columns a camera or a DSEC / DDD17 file delivers -- ADDITIVE as well, ess_version() unchanged.
+ * t, x, y, p (device, 16-byte aligned): [n_streams][stride] each; t 8 bytes, x and y 2 bytes, p 1 byte per event.  stride: the
+ * per-stream capacity, a multiple of 16 (so every stream's row of every column starts 16-byte aligned), 16..2^22.  counts: as
+ * above (a count above stride counts as stride).  formats (device, int32 [n_streams]), read by the kernel like the counts, so one
+ * captured launch serves streams whose formats change from round to round:
+ *   bit 0 (ESS_EVCOL_T_I64):  t is int64 (it enters as (double)t, exact below 2^53), else float64;
+ *   bit 1 (ESS_EVCOL_XY_U16): x / y are uint16 (32768.. lie outside every grid: dropped, not wrapped), else int16;
+ *   any other bit set: the stream is treated as count 0 (nothing of it is read, an all-zero grid).
+ * p: +1 where the byte equals 1, -1 otherwise (uint8 / bool {0, 1} and int8 {-1, +1} alike).  From there on every per-event
+ * expression is that of ess_event_ingest: the grids are bit-equal to its grids on the same events.  acc / out: as above.     */
+enum { ESS_EVCOL_T_I64 = 1, ESS_EVCOL_XY_U16 = 2 };
+int ess_event_ingest_columns(const void* t, const void* x, const void* y, const void* p, const int32_t* counts, const int32_t* formats,
+                             int64_t stride, int32_t n_streams, int32_t bins, int32_t height, int32_t width, void* acc,
+                             size_t acc_bytes, float* out, ess_stream_t stream);
 
 /* ---- image-branch augmentation on the device: the geometric + photometric core of the albumentations
  * pipeline of datasets/cityscapes_loader.py:39-74 (HorizontalFlip, ShiftScaleRotate with rotate 0 and a constant-0 border,

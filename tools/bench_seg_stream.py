@@ -25,16 +25,20 @@ same process with the same repetition scheme:
   compact      MultiStreamSegmenter(compact=True[, compact_buckets=--buckets]): the round runs the smallest bucket >= k.
 
 --streams S[,S...] --ingest measures rounds FROM HOST EVENT ARRAYS INSTEAD: per round the wall time from S numpy [N, 4] arrays in host
-memory to synchronised labels (a device synchronisation behind every round), two ways, both replayed, alternating in the same
+memory to synchronised labels (a device synchronisation behind every round), three ways, all replayed, alternating in the same
 process with the same repetition scheme:
 
   parent       MultiStreamSegmenter(event_capacity=None).update_from_events: concatenate, pageable upload, column split,
                hip.voxel_grid_temporal in front of the graph, copy of the S grids into the static input, replay;
   ingest       MultiStreamSegmenter(event_capacity=N).update_from_events: host packing into pinned 16-byte records, S small
-               copies, replay (the voxeliser runs inside the graph).
+               copies, replay (the voxeliser runs inside the graph);
+  columns      MultiStreamSegmenter(event_capacity=N, event_layout='columns').update_from_events on the SAME events held as
+               EventColumns in DSEC's dtypes (x / y uint16, p uint8, t int64 microseconds): four host copies per stream into pinned
+               columns, 4 S small copies, replay.
 
-Reported: ms per round (median, min, max over the repetitions), the parent's spread, the host packing alone, and whether the ingest
-way wins by more than that spread.
+Reported: ms per round (median, min, max over the repetitions), the parent's spread, the host packing and the host column staging
+alone, whether the ingest way wins by more than that spread, and the column way's claim: it is below the record way by at least the
+packing time minus the staging time, both as measured in this run.
 
 usage: python tools/bench_seg_stream.py [--compute mixed,bf16 --windows 40 --warmup 8 --reps 3 --recurrent convlstm --streams 1,2,4,8
                                          [--active 1,2,4,6,8 [--buckets 1,2,4]] | --streams 8 --events 100000 --ingest]"""
@@ -247,10 +251,18 @@ def partly_active(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiStre
 
 
 def from_host_events(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, default_options):
-    from ess_amd.datasets.data_util import pack_event_records
+    from ess_amd.datasets.data_util import EventColumns, pack_event_records, stage_event_columns
     out['shape'] = f'S streams of {a.bins}x{a.height}x{a.width} K={a.classes}, rounds from host event arrays, graph replay'
     del out['ms_per_window']
     out['ms_per_round'], out['parent_spread_ms'], out['ingest_wins_by_more_than_parent_spread'] = {}, {}, {}
+    out['columns'] = {}
+    # the same events as a DSEC file delivers them: t int64 microseconds, x / y uint16, p uint8.  The rows' times become those
+    # microseconds (as float64) too, so that all three ways are fed the same events.
+    cols = []
+    for w in wins:
+        us = np.round(w[:, 0] * 1e6).astype(np.int64)
+        w[:, 0] = us
+        cols.append(EventColumns(us, w[:, 1].astype(np.uint16), w[:, 2].astype(np.uint16), w[:, 3].astype(np.uint8)))
 
     def models():
         torch.manual_seed(6)
@@ -273,14 +285,28 @@ def from_host_events(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiS
         try:
             for S in (int(v) for v in a.streams.split(',')):
                 segs = {'parent': MultiStreamSegmenter(*models(), a.height, a.width, default_options(), S, graph=True),
-                        'ingest': MultiStreamSegmenter(*models(), a.height, a.width, default_options(), S, graph=True, event_capacity=a.events)}
-                ways = {k: (lambda seg: lambda i: seg.update_from_events([wins[(i + s) % 4] for s in range(S)]))(seg) for k, seg in segs.items()}
+                        'ingest': MultiStreamSegmenter(*models(), a.height, a.width, default_options(), S, graph=True, event_capacity=a.events),
+                        'columns': MultiStreamSegmenter(*models(), a.height, a.width, default_options(), S, graph=True, event_capacity=a.events,
+                                                        event_layout='columns')}
+                ways = {k: (lambda seg, src: lambda i: seg.update_from_events([src[(i + s) % 4] for s in range(S)]))(seg, cols if k == 'columns' else wins)
+                        for k, seg in segs.items()}
+                same = [ways[k](0).labels.clone() for k in ('ingest', 'columns')]  # (both from a zero state: the same events, the same labels)
+                assert torch.equal(*same)
+                for seg in segs.values():
+                    seg.reset()
                 staging = np.zeros((S, a.events), dtype=hip.EVENT_RECORD)
 
                 def pack_only(i):
                     for s in range(S):
                         pack_event_records(wins[(i + s) % 4], staging[s])
                 ways['host_packing_alone'] = pack_only
+                stride = hip.event_column_stride(a.events)
+                col_staging = [np.zeros((S, stride), d) for d in (np.int64, np.int16, np.int16, np.uint8)]
+
+                def stage_only(i):
+                    for s in range(S):
+                        stage_event_columns(cols[(i + s) % 4], *(c[s] for c in col_staging))
+                ways['host_column_staging_alone'] = stage_only
                 ms = {k: [] for k in ways}
                 for _ in range(a.reps):  # alternating: drift of the box hits both ways alike
                     for k, fn in ways.items():
@@ -291,6 +317,12 @@ def from_host_events(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiS
                 spread = max(ms['parent']) - min(ms['parent'])
                 out['parent_spread_ms'][key] = round(spread, 4)
                 out['ingest_wins_by_more_than_parent_spread'][key] = bool(statistics.median(ms['parent']) - statistics.median(ms['ingest']) > spread)
+                m = {k: statistics.median(v) for k, v in ms.items()}
+                saved, owed = m['ingest'] - m['columns'], m['host_packing_alone'] - m['host_column_staging_alone']
+                out['columns'][key] = {'records_minus_columns_ms': round(saved, 4), 'packing_minus_staging_ms': round(owed, 4),
+                                       'below_records_by_at_least_packing_minus_staging': bool(saved >= owed),
+                                       'parent_minus_columns_ms': round(m['parent'] - m['columns'], 4),
+                                       'columns_wins_over_parent_by_more_than_parent_spread': bool(m['parent'] - m['columns'] > spread)}
                 assert all(seg.n_captures == 1 for seg in segs.values())
                 del segs, ways
                 torch.cuda.empty_cache()

@@ -7,7 +7,10 @@ the host cores for a bounded sample.  usage: python tools/bench_voxel.py [--slic
 --ingest measures the temporal flavour INSTEAD, two ways on the same events (device resident), alternating: hip.voxel_grid_temporal
 (memset + fp32 atomics, separate_pol=False) and hip.event_ingest (the scatter + finish pair: 64-bit integer atomics into int64 sums,
 then the conversion pass that also zeroes the sums again); an ingest with every count 0 gives the finish pass alone, the difference
-the scatter, and from it the chip-wide rate of 64-bit integer atomics with one lane per row that the pair implies.
+the scatter, and from it the chip-wide rate of 64-bit integer atomics with one lane per row that the pair implies.  Next to the
+record row, hip.event_ingest_columns (scatter + finish as well) on the same events held as DSEC's columns -- x / y uint16, p uint8, t
+once as float64 (the records' own times: the grids are compared as bits) and once as int64 microseconds (compared as bits with the
+record kernel on those times); reported with the record row's max - min over the repetitions as the run-to-run spread.
 usage: python tools/bench_voxel.py --ingest --slices 8 --events 100000 --bins 5"""
 import argparse
 import json
@@ -108,8 +111,18 @@ def ingest(a):
     t = torch.from_numpy(host['t'].ravel().copy()).to(dev)
     p = torch.from_numpy(host['p'].astype(np.float32).ravel()).to(dev)
     offs = torch.tensor([i * n for i in range(S + 1)])
+    # the same events as DSEC delivers them: 13 bytes per event in four columns, rows at the aligned stride
+    stride = hip.event_column_stride(n)
+    hcols = [np.zeros((S, stride), d) for d in (np.float64, np.int64, np.uint16, np.uint16, np.uint8)]
+    hcols[0][:, :n], hcols[2][:, :n], hcols[3][:, :n], hcols[4][:, :n] = host['t'], host['x'], host['y'], host['p'] == 1
+    hcols[1][:, :n] = np.round(host['t'] * 1e6)  # (int64 microseconds)
+    t_f64, t_i64, cx, cy, cp = (torch.from_numpy(c.view(np.int16) if c.dtype == np.uint16 else c).to(dev) for c in hcols)
+    fmt_f64 = torch.full((S,), hip.EVCOL_XY_U16, dtype=torch.int32, device=dev)
+    fmt_i64 = torch.full((S,), hip.EVCOL_XY_U16 | hip.EVCOL_T_I64, dtype=torch.int32, device=dev)
     ways = {'voxel_grid_temporal': lambda: hip.voxel_grid_temporal(x, y, t, p, offs, C, H, W, separate_pol=False),
             'event_ingest': lambda: hip.event_ingest(records, counts, out, acc=acc),
+            'event_ingest_columns_t_i64': lambda: hip.event_ingest_columns(t_i64, cx, cy, cp, counts, fmt_i64, out, acc=acc),
+            'event_ingest_columns_t_f64': lambda: hip.event_ingest_columns(t_f64, cx, cy, cp, counts, fmt_f64, out, acc=acc),
             'event_ingest_finish_only': lambda: hip.event_ingest(records, zero, out, acc=acc)}
     for fn in ways.values():  # warm-up: clocks, allocator
         for _ in range(50):
@@ -129,12 +142,25 @@ def ingest(a):
     got = hip.event_ingest(records, counts, out, acc=acc)
     err = (got - ref).abs().max().item()
     assert err <= 1e-5 * max(1.0, ref.abs().max().item()) and not bool(acc.any()), err
+    # the column source gives the record kernel's bits: float64 times against the records above, int64 microseconds against
+    # records that carry those times
+    got = got.clone()
+    assert torch.equal(hip.event_ingest_columns(t_f64, cx, cy, cp, counts, fmt_f64, out, acc=acc).view(torch.int32), got.view(torch.int32))
+    host['t'] = hcols[1][:, :n]
+    got = hip.event_ingest(torch.from_numpy(host.view(np.uint8).reshape(S, n, 16)).to(dev), counts, torch.empty_like(out), acc=acc)
+    assert torch.equal(hip.event_ingest_columns(t_i64, cx, cy, cp, counts, fmt_i64, out, acc=acc).view(torch.int32), got.view(torch.int32))
+    assert not bool(acc.any())
     med = {k: sorted(v)[1] for k, v in ms.items()}
+    spread = max(ms['event_ingest']) - min(ms['event_ingest'])
     scatter_ms = med['event_ingest'] - med['event_ingest_finish_only']
     print(json.dumps({
         'metric': 'events -> voxel grids (temporal, one signed grid per stream), ms per batch', 'unit': 'ms',
         'config': {'workload': f'{S} streams x {n} events -> [{S},{C},{H},{W}] fp32', 'reps': a.reps},
         'ms_per_batch': {k: {'median': round(med[k], 5), 'min': round(min(v), 5), 'max': round(max(v), 5)} for k, v in ms.items()},
+        'record_spread_ms': round(spread, 5),
+        'columns_minus_records_ms': {k[-5:]: round(med[k] - med['event_ingest'], 5) for k in med if 'columns' in k},
+        'columns_slower_than_records_by_more_than_the_spread': {k[-5:]: bool(med[k] - med['event_ingest'] > spread) for k in med if 'columns' in k},
+        'bytes_per_event': {'records': 16, 'columns': 13},
         'scatter_ms': round(scatter_ms, 5), 'atomics_per_batch': atomics,
         'int64_atomics_per_s': atomics / (scatter_ms * 1e-3) if scatter_ms > 0 else None,
         'fp32_atomics_per_s_of_voxel_grid_temporal_incl_memset': atomics / (med['voxel_grid_temporal'] * 1e-3),
