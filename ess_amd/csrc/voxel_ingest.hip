@@ -1,6 +1,7 @@
 // Event ingest for the captured multi-stream round: packed 16-byte event records (ess_event_ingest) or the raw event columns a
-// camera delivers (ess_event_ingest_columns) -> the round's voxel grids, with a sum that does not depend on the order the events
-// arrive in (include/ess_hip.h).  The two sources differ in how an event is LOADED; what an event adds is one function, scatter_event.
+// camera delivers, one window per row (ess_event_ingest_columns) or windows named inside per-stream rings (ess_event_ingest_ring)
+// -> the round's voxel grids, with a sum that does not depend on the order the events arrive in (include/ess_hip.h).  The sources
+// differ in how an event is LOADED; what an event adds is one function, scatter_event.
 //
 // voxel_temporal_kernel (voxel.hip) adds its fp32 contributions with fp32 global atomics: a voxel's value depends on which event
 // got there first, two builds of one window differ in the last bits.  Here every contribution is the SAME fp32 value (the same
@@ -139,6 +140,62 @@ __global__ __launch_bounds__(INGEST_THREADS) void event_scatter_columns_kernel(c
   }
 }
 
+// ---- the ring source: the same four columns, [n_rows][ring], as per-stream RINGS that packets are appended to as they arrive.  A
+// slot's window is counts[i] events of row rows[i] from position starts[i] on, modulo ring; all four words are device words.  A start
+// is no multiple of COLUMN_GROUP, so a lane walks the aligned groups from starts - starts % COLUMN_GROUP on and masks the head of the
+// first and the tail of the last: the loads stay 2 x 16 B, 8 B, 8 B, 4 B.  ring is a multiple of COLUMN_STRIDE_ALIGN, so no group
+// straddles the wrap and the wrap falls between two groups; a full ring from an unaligned start reads its first group twice, once
+// under each mask.
+__global__ __launch_bounds__(INGEST_THREADS) void event_scatter_ring_kernel(const long long* __restrict__ t, const unsigned short* __restrict__ x,
+                                                                            const unsigned short* __restrict__ y,
+                                                                            const unsigned char* __restrict__ p,
+                                                                            const int32_t* __restrict__ rows, const int32_t* __restrict__ starts,
+                                                                            const int32_t* __restrict__ counts,
+                                                                            const int32_t* __restrict__ formats, int64_t ring, int n_rows,
+                                                                            int nb, int H, int W, long long* __restrict__ acc) {
+#pragma clang fp contract(off)
+  const int s = blockIdx.y;
+  const int cnt = counts[s];
+  const int fmt = formats[s], r = rows[s], start = starts[s];  // (read beside the count: the four scalar loads issue together)
+  if (cnt <= 0) return;  // an empty window, or INGEST_KEEP: nothing is read for this slot
+  if ((fmt & ~(EVCOL_T_I64 | EVCOL_XY_U16)) != 0) return;  // an unknown format: as count 0
+  if (r < 0 || r >= n_rows || start < 0 || (int64_t)start >= ring) return;  // a row or a start outside the rings: as count 0
+  const bool t_i64 = (fmt & EVCOL_T_I64) != 0, xy_u16 = (fmt & EVCOL_XY_U16) != 0;
+  const int64_t n = (int64_t)cnt < ring ? (int64_t)cnt : ring;
+  const size_t row = (size_t)r * ring;
+  const long long* __restrict__ ts = t + row;
+  int64_t last_at = (int64_t)start + n - 1;  // (< 2 * ring)
+  if (last_at >= ring) last_at -= ring;
+  const double first = column_time(ts[start], t_i64);
+  double dT = column_time(ts[last_at], t_i64) - first;
+  if (dT == 0) dT = 1.0;
+  const size_t plane = (size_t)H * W;
+  long long* __restrict__ g = acc + (size_t)s * nb * plane;
+  const i64x2* __restrict__ t2 = (const i64x2*)ts;
+  const uint2* __restrict__ x4 = (const uint2*)(x + row);
+  const uint2* __restrict__ y4 = (const uint2*)(y + row);
+  const unsigned* __restrict__ p4 = (const unsigned*)(p + row);
+  const int64_t head = start % COLUMN_GROUP, group0 = start / COLUMN_GROUP, ring_groups = ring / COLUMN_GROUP;
+  const int64_t groups = (head + n + COLUMN_GROUP - 1) / COLUMN_GROUP;  // (<= ring_groups + 1)
+  for (int64_t q = (int64_t)blockIdx.x * INGEST_THREADS + threadIdx.x; q < groups; q += (int64_t)gridDim.x * INGEST_THREADS) {
+    int64_t at = group0 + q;  // (< 2 * ring_groups: one subtraction wraps it; every group lies inside the row)
+    if (at >= ring_groups) at -= ring_groups;
+    const i64x2 ta = t2[2 * at], tb = t2[2 * at + 1];
+    const uint2 xv = x4[at], yv = y4[at];
+    const unsigned pv = p4[at];
+    const long long tw[COLUMN_GROUP] = {ta[0], ta[1], tb[0], tb[1]};
+    const unsigned xh[COLUMN_GROUP] = {xv.x & 0xffffu, xv.x >> 16, xv.y & 0xffffu, xv.y >> 16};
+    const unsigned yh[COLUMN_GROUP] = {yv.x & 0xffffu, yv.x >> 16, yv.y & 0xffffu, yv.y >> 16};
+#pragma unroll
+    for (int j = 0; j < COLUMN_GROUP; ++j) {
+      const int64_t k = q * COLUMN_GROUP + j - head;  // the event's number inside the window
+      if (k < 0 || k >= n) continue;                  // (the head and the tail: loaded, inside the row, never summed)
+      scatter_event(column_time(tw[j], t_i64), column_coordinate(xh[j], xy_u16), column_coordinate(yh[j], xy_u16),
+                    (int)((pv >> (8 * j)) & 0xffu), first, dT, nb, H, W, plane, g);
+    }
+  }
+}
+
 __device__ __forceinline__ float dequantise(long long a) { return (float)a * INGEST_INV_SCALE; }
 
 // VEC: per_stream is a multiple of 4, so every stream's acc / out rows start 16-byte aligned
@@ -245,4 +302,34 @@ extern "C" int ess_event_ingest_columns(const void* t, const void* x, const void
   int rc = ess_launch_status("event_ingest_columns(scatter)");
   if (rc) return rc;
   return launch_finish(counts, n_streams, bins, height, width, acc, out, st, "event_ingest_columns(finish)");
+}
+
+extern "C" int ess_event_ingest_ring(const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
+                                     const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots,
+                                     int32_t bins, int32_t height, int32_t width, void* acc, size_t acc_bytes, float* out,
+                                     ess_stream_t stream) {
+  ESS_CHECK_ARG(t && x && y && p && rows && starts && counts && formats && acc && out,
+                "event_ingest_ring: null t, x, y, p, rows, starts, counts, formats, acc or out");
+  ESS_CHECK_ARG(n_slots >= 1 && n_slots <= 65535, "event_ingest_ring: n_slots=%d (1..65535)", (int)n_slots);
+  ESS_CHECK_ARG(n_rows >= 1, "event_ingest_ring: n_rows=%d must be positive", (int)n_rows);
+  ESS_CHECK_ARG(bins > 0 && height > 0 && width > 0, "event_ingest_ring: bins=%d height=%d width=%d must be positive", (int)bins,
+                (int)height, (int)width);
+  ESS_CHECK_ARG(ring >= 1 && ring <= INGEST_MAX_CAPACITY,
+                "event_ingest_ring: ring=%lld events per row (16..%lld: the int64 sums hold 2^22 contributions of magnitude 1 at scale 2^40)",
+                (long long)ring, (long long)INGEST_MAX_CAPACITY);
+  ESS_CHECK_ARG(ring % COLUMN_STRIDE_ALIGN == 0,
+                "event_ingest_ring: ring=%lld must be a multiple of %d (every row of every column starts 16-byte aligned, no group of %d "
+                "events straddles the wrap)",
+                (long long)ring, COLUMN_STRIDE_ALIGN, COLUMN_GROUP);
+  const size_t need = ess_event_ingest_workspace(n_slots, bins, height, width);
+  ESS_CHECK_ARG(acc_bytes >= need, "event_ingest_ring: acc has %zu bytes, %zu are needed", acc_bytes, need);
+  ESS_CHECK_ARG(((((uintptr_t)t) | ((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)p) | ((uintptr_t)acc) | ((uintptr_t)out)) & 15) == 0,
+                "event_ingest_ring: t, x, y, p, acc and out must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(event_scatter_ring_kernel, dim3(scatter_blocks(ring), (unsigned)n_slots), dim3(INGEST_THREADS), 0, st,
+                     (const long long*)t, (const unsigned short*)x, (const unsigned short*)y, (const unsigned char*)p, rows, starts, counts,
+                     formats, ring, n_rows, bins, height, width, (long long*)acc);
+  int rc = ess_launch_status("event_ingest_ring(scatter)");
+  if (rc) return rc;
+  return launch_finish(counts, n_slots, bins, height, width, acc, out, st, "event_ingest_ring(finish)");
 }

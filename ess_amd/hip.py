@@ -77,7 +77,7 @@ EXPORTS = [
     'ess_label_confusion', 'ess_augment_perspective_filter', 'ess_tuning_set', 'ess_tuning_get', 'ess_conv2d_s2d_preferred',
     'ess_to_f16_c8', 'ess_bf16_c8_to_f16_c8', 'ess_f16_c8_to_bf16_c8', 'ess_instnorm_forward_c8_mixed', 'ess_seg_head',
     'ess_event_normalize_samples', 'ess_state_carry_masked', 'ess_state_carry_indexed',
-    'ess_event_ingest_workspace', 'ess_event_ingest', 'ess_event_ingest_columns',
+    'ess_event_ingest_workspace', 'ess_event_ingest', 'ess_event_ingest_columns', 'ess_event_ingest_ring',
 ]
 
 
@@ -174,6 +174,7 @@ def lib():
             'ess_state_carry_indexed': [P, P, P, I, I, I, I, P, P, P],
             'ess_event_ingest': [P, P, I64, I, I, I, I, P, c_size_t, P, P],
             'ess_event_ingest_columns': [P, P, P, P, P, P, I64, I, I, I, I, P, c_size_t, P, P],
+            'ess_event_ingest_ring': [P, P, P, P, P, P, P, P, I64, I, I, I, I, I, P, c_size_t, P, P],
         }
         for name, argtypes in sig.items():
             fn = getattr(L, name)
@@ -922,6 +923,54 @@ def event_ingest_columns(t, x, y, p, counts, formats, out, acc=None):
                                       ptr(counts, torch.int32), ptr(formats, torch.int32), t.shape[1], S, bins, H, W,
                                       c_void_p(acc.data_ptr()), acc.numel() * 8, c_void_p(out.data_ptr()), stream()),
            'ess_event_ingest_columns')
+    return out
+
+
+def event_ingest_ring(t, x, y, p, rows, starts, counts, formats, out, acc=None):
+    """event_ingest_columns on windows named inside per-stream event RINGS: the same grids, bit for bit, as event_ingest_columns
+    gives on the same windows laid out from entry 0.  t, x, y, p: device [n_rows, ring] raw columns (dtypes as event_ingest_columns),
+    row r the ring stream r's packets are appended to; ring: a multiple of 16.  rows, starts, counts, formats: device int32
+    [n_slots], all read on the device -- slot i's window is the counts[i] events of row rows[i] at (starts[i] + k) mod ring; count 0:
+    an all-zero grid, INGEST_KEEP (< 0): out[i] is neither read nor written, a count above ring: ring; a row outside [0, n_rows), a
+    start outside [0, ring) or an unknown format bit: the slot counts as empty.  Two slots may name one row.  out: fp32
+    [n_slots, bins, H, W], returned; acc: as event_ingest, at least n_slots * bins * H * W elements."""
+    named = (('t', t), ('x', x), ('y', y), ('p', p), ('rows', rows), ('starts', starts), ('counts', counts), ('formats', formats),
+             ('out', out))
+    every = named + ((('acc', acc),) if acc is not None else ())
+    for name, v in every:
+        if not torch.is_tensor(v):
+            raise EssHipError(f'event_ingest_ring: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+    if out.dim() != 4 or out.dtype != torch.float32 or out.numel() == 0:
+        raise EssHipError(f'event_ingest_ring: out must be a non-empty fp32 [n_slots, bins, H, W] tensor, got {out.dtype}{tuple(out.shape)}')
+    n_slots, bins, H, W = out.shape
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise EssHipError(f'event_ingest_ring: t must be [n_rows, ring], got {tuple(t.shape)}')
+    for name, v in named[:4]:
+        if v.dtype not in _EVCOL_DTYPES[name] or v.shape != t.shape:
+            raise EssHipError(f'event_ingest_ring: {name} must be {" / ".join(str(d) for d in _EVCOL_DTYPES[name])} '
+                              f'{list(t.shape)}, got {v.dtype}{tuple(v.shape)}')
+    for name, v in named[4:8]:
+        if v.dtype != torch.int32 or tuple(v.shape) != (n_slots,):
+            raise EssHipError(f'event_ingest_ring: {name} must be int32 [{n_slots}], got {v.dtype}{tuple(v.shape)}')
+    if acc is not None and acc.dtype != torch.int64:
+        raise EssHipError(f'event_ingest_ring: acc must be int64, got {acc.dtype}')
+    n_rows, ring = t.shape
+    if ring % EVCOL_STRIDE_ALIGN or ring > INGEST_MAX_CAPACITY:
+        raise EssHipError(f'event_ingest_ring: ring={ring} must be a multiple of {EVCOL_STRIDE_ALIGN} in [{EVCOL_STRIDE_ALIGN}, '
+                          f'{INGEST_MAX_CAPACITY}] (event_column_stride rounds a capacity up)')
+    for name, v in every:  # (the device last: what is wrong with a tensor's form is said whatever memory it lies in)
+        if not v.is_cuda:
+            raise EssHipError(f'event_ingest_ring: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+        if not v.is_contiguous():
+            raise EssHipError(f'event_ingest_ring: {name} must be contiguous')
+    L = lib()
+    need = L.ess_event_ingest_workspace(n_slots, bins, H, W)
+    if acc is None:
+        acc = torch.zeros(need // 8, dtype=torch.int64, device=out.device)
+    _check(L.ess_event_ingest_ring(c_void_p(t.data_ptr()), c_void_p(x.data_ptr()), c_void_p(y.data_ptr()), c_void_p(p.data_ptr()),
+                                   ptr(rows, torch.int32), ptr(starts, torch.int32), ptr(counts, torch.int32), ptr(formats, torch.int32),
+                                   ring, n_rows, n_slots, bins, H, W, c_void_p(acc.data_ptr()), acc.numel() * 8,
+                                   c_void_p(out.data_ptr()), stream()), 'ess_event_ingest_ring')
     return out
 
 

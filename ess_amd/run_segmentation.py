@@ -39,6 +39,7 @@ along as before.
 """
 import collections
 
+import numpy as np
 import torch
 
 from . import hip
@@ -283,7 +284,7 @@ def _event_capacity(n, height, width):
     return n
 
 
-EVENT_LAYOUTS = ('records', 'columns')
+EVENT_LAYOUTS = ('records', 'columns', 'ring')
 
 
 def _event_layout(layout, event_capacity):
@@ -319,6 +320,26 @@ class _ColumnStage:
         self.cols, self.words, self.done, self.used = cols, words, done, ()
         self.cols_np = tuple(c.numpy() for c in cols)
         self.counts_np, self.formats_np = words.numpy()[0], words.numpy()[1]
+
+
+class _RingStage:
+    """one pinned staging set of the ring ingest: the words [4, S] (rows, starts, counts, formats) as torch (pinned) and as numpy
+    views, and the event recorded behind the set's last upload.  No event is staged: they went to the device ring when they arrived"""
+    __slots__ = ('words', 'rows_np', 'starts_np', 'counts_np', 'formats_np', 'done', 'used')
+
+    def __init__(self, words, done):
+        self.words, self.done, self.used = words, done, ()
+        self.rows_np, self.starts_np, self.counts_np, self.formats_np = words.numpy()
+
+
+class _Feed:
+    """one stream's side of the continuous feed: its window cutter (absolute event indices; position in the ring = index mod R), the
+    format word its dtypes give (None until the first packet), and the uploads out of the pinned mirror still to be waited for --
+    (the absolute index the packet began at, the event recorded behind its copies), oldest first"""
+    __slots__ = ('windows', 'format', 'dtypes', 'uploads')
+
+    def __init__(self, windows):
+        self.windows, self.format, self.dtypes, self.uploads = windows, None, None, collections.deque()
 
 
 class _IngestStage:
@@ -371,10 +392,20 @@ class MultiStreamSegmenter(GraphedWindowState):
     them -- or None, and the round starts with hip.event_ingest_columns.  The host does no arithmetic: staging is four copies per
     stream into pinned columns (13 bytes per event), then their used prefixes, the counts and the per-stream format words go to
     static device columns [S, stride].  The format is a device word like the count, so streams may change their dtypes from round
-    to round under the one capture.  Labels, colours and confidences equal the record path's on the same events bit for bit."""
+    to round under the one capture.  Labels, colours and confidences equal the record path's on the same events bit for bit.
+
+    event_layout='ring' (with event_capacity=N; ring_capacity=R, default 2 N, rounded up to a multiple of 16; window_events=N_w or
+    window_duration=D, window_stride= default the window): the continuous feed.  feed(stream, EventColumns) takes packets of any size
+    as they arrive and appends them to the stream's ring of R events in device memory, through a pinned mirror, at once; the host
+    cuts windows by event count or by duration, with an optional overlap, from the indices and times it holds
+    (datasets.event_feed.EventWindows).  update_from_feed(active=None) runs one round on the oldest pending window of every stream
+    that has one: its upload is the four words per slot -- row, start, count, format -- that hip.event_ingest_ring reads inside
+    the capture; an event crosses to the device once however many overlapping windows read it.  pending(stream), drop_feed(streams);
+    update_from_events raises.  Labels, colours and confidences equal the column path's on the same windows bit for bit."""
 
     def __init__(self, encoder, decoder, height, width, options, n_streams, device=None, graph=False, copy=True, palette=None,
-                 want_confidence=False, out_hw=None, compact=False, compact_buckets=None, event_capacity=None, event_layout='records'):
+                 want_confidence=False, out_hw=None, compact=False, compact_buckets=None, event_capacity=None, event_layout='records',
+                 ring_capacity=None, window_events=None, window_duration=None, window_stride=None):
         if not isinstance(n_streams, int) or isinstance(n_streams, bool) or n_streams < 1:
             raise hip.EssHipError(f'n_streams={n_streams!r}: a positive number of streams is needed')
         self.compact = bool(compact)
@@ -406,14 +437,18 @@ class MultiStreamSegmenter(GraphedWindowState):
         self._pending = [True] * S
         self.event_layout = _event_layout(event_layout, event_capacity)
         self.event_capacity = None if event_capacity is None else _event_capacity(event_capacity, height, width)
-        if self.event_capacity is not None:
+        if self.event_layout == 'ring':
+            self._build_ingest_ring(ring_capacity, window_events, window_duration, window_stride)
+        elif not (ring_capacity is None and window_events is None and window_duration is None and window_stride is None):
+            raise hip.EssHipError("ring_capacity, window_events, window_duration and window_stride belong to event_layout='ring'")
+        elif self.event_capacity is not None:
             self._build_ingest() if self.event_layout == 'records' else self._build_ingest_columns()
         self._build_state()
         if self.buckets:
             self._build_compact()
 
     # ---- event ingest (event_capacity=N): static record / count buffers the captured round reads, pinned staging in front of them
-    event_capacity = _records = _columns = _counts = _formats = _acc = None
+    event_capacity = ring_capacity = _records = _columns = _counts = _formats = _acc = _ring = None
 
     def _build_ingest(self):
         """Device records [S, N, 16], counts [S] and the int64 sums of hip.event_ingest (zeroed here, once), and two pinned staging
@@ -449,10 +484,133 @@ class MultiStreamSegmenter(GraphedWindowState):
             self._stage.append(_ColumnStage(tuple(torch.zeros(S, stride, dtype=d).pin_memory() for d in dtypes), words, torch.cuda.Event()))
         self._stage_next = 0
 
+    def _build_ingest_ring(self, ring_capacity, window_events, window_duration, window_stride):
+        """event_layout='ring': per stream a ring of R events in device memory -- the four raw columns [S, R] -- that feed() appends
+        packets to, a pinned mirror of the same shape the packets pass through, the device words [4, S] (rows, starts, counts,
+        formats: one upload a round) with two pinned staging sets under _next_stage's rule, the int64 sums of hip.event_ingest_ring,
+        and per stream the window cutter.  R: ring_capacity (default 2 N), at least N, rounded up to a multiple of 16."""
+        from .datasets.event_feed import EventWindows
+        S, N = self.n_streams, self.event_capacity
+        R = 2 * N if ring_capacity is None else ring_capacity
+        if not isinstance(R, int) or isinstance(R, bool) or R < N or hip.event_column_stride(R) > hip.INGEST_MAX_CAPACITY:
+            raise hip.EssHipError(f'ring_capacity={ring_capacity!r}: events per stream the ring holds, an int in [event_capacity={N}, '
+                                  f'{hip.INGEST_MAX_CAPACITY}] (default: 2 * event_capacity)')
+        self.ring_capacity = R = hip.event_column_stride(R)
+        self._window_args = dict(window_events=window_events, window_duration=window_duration, stride=window_stride, event_capacity=N,
+                                 ring_capacity=R)
+        self._feeds = [_Feed(EventWindows(**self._window_args)) for _ in range(S)]  # (refuses a bad window argument here)
+        dtypes = (torch.int64, torch.int16, torch.int16, torch.uint8)
+        self._ring = tuple(torch.zeros(S, R, dtype=d, device=self.device) for d in dtypes)
+        self._ring_host = tuple(torch.zeros(S, R, dtype=d).pin_memory() for d in dtypes)
+        self._ring_np = tuple(c.numpy() for c in self._ring_host)
+        self._words = torch.zeros(4, S, dtype=torch.int32, device=self.device)
+        self._counts, self._formats = self._words[2], self._words[3]
+        self._counts.fill_(hip.INGEST_KEEP)
+        self._acc = torch.zeros(S, self.num_bins, self.height, self.width, dtype=torch.int64, device=self.device)
+        self._stage = []
+        for _ in range(2):
+            words = torch.zeros(4, S, dtype=torch.int32).pin_memory()
+            words[2].fill_(hip.INGEST_KEEP)
+            self._stage.append(_RingStage(words, torch.cuda.Event()))
+        self._stage_next = 0
+
+    def _feed_of(self, stream, what):
+        if self._ring is None:
+            raise hip.EssHipError(f"{what} belongs to event_layout='ring' (this segmenter: {self.event_layout!r})")
+        if not isinstance(stream, (int, np.integer)) or isinstance(stream, bool) or not 0 <= stream < self.n_streams:
+            raise hip.EssHipError(f'{what}: stream {stream!r} of n_streams={self.n_streams}')
+        return self._feeds[int(stream)]
+
+    def feed(self, stream, cols):
+        """A packet of a stream's events as it arrives (datasets.data_util.EventColumns, any size up to the ring's room; the times
+        non-decreasing, also from packet to packet) -> the number of windows of that stream now pending.  The packet is copied as it
+        is into the pinned mirror at head mod R -- at most two segments per column where it wraps -- and those segments go to the
+        device ring on the current stream, non-blocking: each event crosses to the device once, when it arrives, however many
+        overlapping windows read it.  Refused before anything is written: another object than an EventColumns, other dtypes than the
+        stream's first packet had (drop_feed forgets them), a packet that goes back in time, a ring overrun (windows must be consumed
+        by update_from_feed first) and a cut window of more than event_capacity events."""
+        from .datasets.data_util import EventColumns
+        from .datasets.event_feed import copy_into_ring
+        f = self._feed_of(stream, 'feed')
+        s = int(stream)
+        if not isinstance(cols, EventColumns):
+            raise hip.EssHipError(f'feed: an EventColumns is needed, got {type(cols).__name__}: hand the columns over as they arrive, '
+                                  'EventColumns(t, x, y, p)')
+        if cols.n == 0:
+            return f.windows.pending
+        dtypes = (cols.t.dtype, cols.x.dtype)
+        if f.dtypes is not None and dtypes != f.dtypes:
+            raise hip.EssHipError(f'feed: stream {s} delivers t {f.dtypes[0]} and x / y {f.dtypes[1]} since its first packet, this packet has '
+                                  f'{dtypes[0]} and {dtypes[1]}: a ring holds one format (drop_feed([{s}]) starts afresh)')
+        head, R = f.windows.head, self.ring_capacity
+        f.windows.push(cols.n, cols.t)  # (refuses before anything changes)
+        f.dtypes, f.format = dtypes, cols.format
+        # the pinned entries about to be rewritten held the events [head - R, head + n - R): the uploads that read them must be over
+        # (a whole ring lies between two uses of an entry, so in practice this never waits; finished uploads are forgotten on the way)
+        while f.uploads and (f.uploads[0][0] < head + cols.n - R or f.uploads[0][1].query()):
+            f.uploads.popleft()[1].synchronize()
+        for at, _, m in copy_into_ring(cols, tuple(c[s] for c in self._ring_np), head, R):
+            for dev, host in zip(self._ring, self._ring_host):
+                dev[s, at:at + m].copy_(host[s, at:at + m], non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        f.uploads.append((head, done))
+        return f.windows.pending
+
+    def pending(self, stream):
+        """the number of complete windows of the stream that update_from_feed has not consumed yet"""
+        return self._feed_of(stream, 'pending').windows.pending
+
+    def drop_feed(self, streams=None):
+        """these streams (default: all) forget their ring contents, their pending windows, the origin of their windows and their
+        dtypes: the next packet is event 0 of a new sequence.  The recurrent state is reset()'s business, not this call's."""
+        from .datasets.event_feed import EventWindows
+        for s in (range(self.n_streams) if streams is None else streams):
+            f = self._feed_of(s, 'drop_feed')
+            for _, done in f.uploads:  # (the new sequence writes the mirror from entry 0 on)
+                done.synchronize()
+            self._feeds[int(s)] = _Feed(EventWindows(**self._window_args))
+
+    def _stage_ring(self, slots):
+        """slots: per slot (stream, or slot of a compact batch) None or (row, start, count, format) -> the staging set with the four
+        words written; a slot without a window and the slots behind the list: count 0"""
+        st = self._next_stage()
+        st.rows_np[:] = np.arange(self.n_streams)
+        st.starts_np[:] = 0
+        st.counts_np[:] = 0
+        st.formats_np[:] = 0
+        for i, w in enumerate(slots):
+            if w is not None:
+                st.rows_np[i], st.starts_np[i], st.counts_np[i], st.formats_np[i] = w
+        return st
+
+    def update_from_feed(self, active=None):
+        """One round from the fed events: every stream with a pending window -- and active[s] true, where active is given --
+        consumes its OLDEST window; the others ride along idle.  A window without events (a duration window in a pause) is consumed
+        and counts as idle: a pending restart stays pending, as with an empty window in update_from_events.  The round is one upload
+        of the words [4, S] and the replay: a ride-along round names rows 0 .. S - 1, a compacted round writes the active streams'
+        numbers into the rows in slot order and count 0 into a padded slot; no event moves."""
+        if self._ring is None:
+            raise hip.EssHipError(f"update_from_feed belongs to event_layout='ring' (this segmenter: {self.event_layout!r})")
+        allowed = check_active(active, self.n_streams)
+        self._check_compute()
+        R = self.ring_capacity
+        wins = []
+        for f, a in zip(self._feeds, allowed):
+            start, count = f.windows.pop() if a and f.windows.pending else (0, 0)
+            wins.append((start % R, count, f.format) if count else None)
+        on = [w is not None for w in wins]
+        plan = compact_plan(self._pending, on, self.buckets) if self.buckets else None
+        if plan is None:
+            return self._ride_along(None, on, self._stage_ring([None if w is None else (s,) + w for s, w in enumerate(wins)]))
+        return self._update_compact(plan, None, on, True, self._stage_ring([(s,) + wins[s] for s in plan.rows]))
+
     def _ingest(self, ev, b=None):
         """the round's first launches: the static event buffers (b: their first b slots) -> the grids ev, inside the capture"""
         cut = (lambda v: v) if b is None else (lambda v: v[:b])
-        if self._columns is not None:
+        if self._ring is not None:  # (every row of the rings stays in reach: a slot names its row)
+            hip.event_ingest_ring(*self._ring, *(cut(w) for w in self._words), ev, self._acc)
+        elif self._columns is not None:
             hip.event_ingest_columns(*(cut(c) for c in self._columns), cut(self._counts), cut(self._formats), ev, self._acc)
         else:
             hip.event_ingest(cut(self._records), cut(self._counts), ev, self._acc)
@@ -516,7 +674,9 @@ class MultiStreamSegmenter(GraphedWindowState):
     def _upload(self, st):
         """the staged counts (and formats) and the used prefix of every staged slot -> the static device buffers, on the current
         stream"""
-        if self._columns is not None:
+        if self._ring is not None:
+            self._words.copy_(st.words, non_blocking=True)
+        elif self._columns is not None:
             for i, n in st.used:
                 for dev, host in zip(self._columns, st.cols):
                     dev[i, :n].copy_(host[i, :n], non_blocking=True)
@@ -803,6 +963,9 @@ class MultiStreamSegmenter(GraphedWindowState):
         """events: S entries, [N, 4] rows (t, x, y, polarity) of the stream's window or None (idle).  All grids are built by ONE
         hip.voxel_grid_temporal call over the concatenated events; an idle stream is an empty slice (an all-zero grid).  A compacted
         round builds only its bucket's grids: the active streams' in slot order, a padded slot an empty slice."""
+        if self._ring is not None:
+            raise hip.EssHipError("update_from_events: event_layout='ring' cuts its windows itself: hand the packets to feed(stream, cols) "
+                                  'as they arrive and run the rounds with update_from_feed()')
         if self.event_capacity is not None:
             return self._update_from_events_ingest(events)
         evs, active = check_stream_events(events, self.n_streams)

@@ -436,6 +436,22 @@ enum { ESS_EVCOL_T_I64 = 1, ESS_EVCOL_XY_U16 = 2 };
 int ess_event_ingest_columns(const void* t, const void* x, const void* y, const void* p, const int32_t* counts, const int32_t* formats,
                              int64_t stride, int32_t n_streams, int32_t bins, int32_t height, int32_t width, void* acc,
                              size_t acc_bytes, float* out, ess_stream_t stream);
+/* The same ingest from per-stream event RINGS in device memory -- PURELY ADDITIVE to ABI 110 (ess_version() is unchanged; no existing
+ * entry point changes).  t, x, y, p (device, 16-byte aligned): [n_rows][ring] raw columns as above, row r the ring that stream r's
+ * packets are appended to as they arrive.  ring: a multiple of 16, 16..2^22 (so no aligned group of 4 events straddles the wrap).
+ * rows, starts, counts, formats (device, int32 [n_slots] each), all read by the kernels, so one captured launch serves every round:
+ * slot i's window is the counts[i] events of row rows[i] at the positions (starts[i] + k) mod ring, k = 0 .. counts[i] - 1; first /
+ * last = the times at starts[i] and at (starts[i] + counts[i] - 1) mod ring; formats[i] as above.  Two slots may name the same row
+ * (the columns are only read).
+ *   counts[i] == 0: an all-zero grid;  counts[i] < 0 (ESS_INGEST_KEEP): out[i] is neither read nor written;
+ *   counts[i] > ring counts as ring;
+ *   rows[i] outside [0, n_rows), starts[i] outside [0, ring) or an unknown format bit: the slot counts as empty (nothing of it is
+ *   read, an all-zero grid).
+ * Every per-event expression is that of ess_event_ingest_columns: the grids are bit-equal to its grids on the same windows.
+ * acc: int64 [n_slots][bins][height][width], all zero on entry and again behind the call; out: fp32 [n_slots][bins][height][width]. */
+int ess_event_ingest_ring(const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
+                          const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots, int32_t bins,
+                          int32_t height, int32_t width, void* acc, size_t acc_bytes, float* out, ess_stream_t stream);
 
 /* ---- image-branch augmentation on the device: the geometric + photometric core of the albumentations
  * pipeline of datasets/cityscapes_loader.py:39-74 (HorizontalFlip, ShiftScaleRotate with rotate 0 and a constant-0 border,

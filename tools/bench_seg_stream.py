@@ -40,8 +40,17 @@ Reported: ms per round (median, min, max over the repetitions), the parent's spr
 alone, whether the ingest way wins by more than that spread, and the column way's claim: it is below the record way by at least the
 packing time minus the staging time, both as measured in this run.
 
+--streams S[,S...] --feed measures rounds FROM A CONTINUOUS PACKET FEED INSTEAD: every stream delivers packets of a tenth of a window;
+per round the wall time from the hand-over of the packet that completes the window to synchronised labels, two ways, both replayed,
+alternating in the same process, once with windows back to back (stride = window) and once overlapping (stride = window / 4):
+
+  columns      MultiStreamSegmenter(event_capacity=N, event_layout='columns').update_from_events on the window the deployment's own
+               cutter has buffered and assembled (its assembly is NOT timed: the window is handed over as one contiguous EventColumns);
+  ring         MultiStreamSegmenter(event_capacity=N, event_layout='ring').feed of that last packet + update_from_feed(): the earlier
+               packets went to the device ring when they arrived, outside the timed region.
+
 usage: python tools/bench_seg_stream.py [--compute mixed,bf16 --windows 40 --warmup 8 --reps 3 --recurrent convlstm --streams 1,2,4,8
-                                         [--active 1,2,4,6,8 [--buckets 1,2,4]] | --streams 8 --events 100000 --ingest]"""
+                                         [--active 1,2,4,6,8 [--buckets 1,2,4]] | --streams 8 --events 100000 --ingest | --streams 8 --events 100000 --feed]"""
 import argparse
 import json
 import os
@@ -73,7 +82,11 @@ def main():
     ap.add_argument('--buckets', default=None, help="(with --active) the compacting segmenter's compact_buckets, comma-separated (default: its own)")
     ap.add_argument('--ingest', action='store_true', help='(with --streams) rounds from host event arrays: event_capacity=--events against '
                                                           'event_capacity=None')
+    ap.add_argument('--feed', action='store_true', help="(with --streams) rounds from a continuous packet feed: event_layout='ring' against "
+                                                        "'columns'")
     a = ap.parse_args()
+    if a.feed and (not a.streams or a.active or a.ingest):
+        ap.error('--feed needs --streams and excludes --active and --ingest')
     if a.active and not a.streams:
         ap.error('--active needs --streams')
     if a.ingest and (not a.streams or a.active):
@@ -107,6 +120,10 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / a.windows * 1e3
 
+    if a.feed:
+        from_packet_feed(a, hip, cfg, [w.cpu().numpy() for w in wins], out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, default_options)
+        print(json.dumps(out))
+        return
     if a.ingest:
         from_host_events(a, hip, cfg, [w.cpu().numpy() for w in wins], out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, default_options)
         print(json.dumps(out))
@@ -326,6 +343,96 @@ def from_host_events(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiS
                 assert all(seg.n_captures == 1 for seg in segs.values())
                 del segs, ways
                 torch.cuda.empty_cache()
+        finally:
+            hip.set_compute('fp32')
+
+
+def from_packet_feed(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, default_options):
+    from ess_amd.datasets.data_util import EventColumns
+    out['shape'] = f'S streams of {a.bins}x{a.height}x{a.width} K={a.classes}, rounds from a packet feed, graph replay'
+    del out['ms_per_window']
+    out['ms_per_round'], out['columns_minus_ring_ms'], out['ring_wins_by_more_than_columns_spread'] = {}, {}, {}
+    N = a.events
+    packet = max(N // 10, 1)
+    out['packet_events'] = packet
+    rounds = a.warmup + a.windows
+
+    def models():
+        torch.manual_seed(6)
+        return E2VIDRecurrent(dict(cfg)), SemSegE2VID(256, a.classes, skip_connect=True, skip_type='concat')
+
+    def source(total):
+        """one long sequence in DSEC's dtypes (t int64 microseconds, x / y uint16, p uint8): the four windows over and over, the times
+        running on"""
+        reps = -(-total // (4 * N))
+        base = np.concatenate(wins)
+        us = np.round(base[:, 0] * 1e6).astype(np.int64)
+        period = int(us[-1] - us[0]) + 1
+        t = np.concatenate([us + r * period for r in range(reps)])[:total]
+        x, y, p = (np.tile(base[:, k].astype(d), reps)[:total] for k, d in ((1, np.uint16), (2, np.uint16), (3, np.uint8)))
+        return t, x, y, p
+
+    def piece(src, lo, hi):
+        return EventColumns(*(np.ascontiguousarray(c[lo:hi]) for c in src))
+
+    for compute in a.compute.split(','):
+        hip.set_compute(compute)
+        try:
+            for S in (int(v) for v in a.streams.split(',')):
+                for M in (N, max(N // 4, 1)):
+                    shift = 1237  # (stream s reads the sequence from event s * shift on: the streams' windows differ)
+                    src = source(N + M * rounds + packet + S * shift)
+                    ring = MultiStreamSegmenter(*models(), a.height, a.width, default_options(), S, graph=True, event_capacity=N,
+                                                event_layout='ring', window_events=N, window_stride=M)
+                    cols = MultiStreamSegmenter(*models(), a.height, a.width, default_options(), S, graph=True, event_capacity=N,
+                                                event_layout='columns')
+                    ms = {'ring': [], 'columns': []}
+                    fed, k = 0, 0
+                    while k < rounds:
+                        last = fed + packet >= k * M + N  # this packet completes window k of every stream
+                        pk = [piece(src, s * shift + fed, s * shift + fed + packet) for s in range(S)]
+                        if not last:
+                            for s in range(S):
+                                ring.feed(s, pk[s])
+                            fed += packet
+                            torch.cuda.synchronize()  # (the packet arrived long before the next one: its upload is over)
+                            continue
+                        window = [piece(src, s * shift + k * M, s * shift + k * M + N) for s in range(S)]
+                        def by_ring():
+                            for s in range(S):
+                                ring.feed(s, pk[s])
+                            return ring.update_from_feed()
+
+                        def by_columns():
+                            return cols.update_from_events(window)
+                        res, took = {}, {}
+                        for way, fn in ((('ring', by_ring), ('columns', by_columns))[::1 if k % 2 == 0 else -1]):  # (who goes first alternates)
+                            torch.cuda.synchronize()
+                            t0 = time.perf_counter()
+                            res[way] = fn()
+                            torch.cuda.synchronize()
+                            took[way] = (time.perf_counter() - t0) * 1e3
+                        got, want = res['ring'], res['columns']
+                        fed += packet
+                        assert got.valid == want.valid == (True,) * S and ring.pending(0) == 0
+                        if k == 0:  # (both from a zero state: the same windows, the same labels)
+                            assert torch.equal(got.labels, want.labels)
+                        if k >= a.warmup:
+                            for way in ms:
+                                ms[way].append(took[way])
+                        k += 1
+                    key = f'{compute}/S={S}/stride={"window" if M == N else "window/4"}'
+                    for way, v in ms.items():
+                        out['ms_per_round'][f'{key}/{way}'] = {'median': round(statistics.median(v), 4), 'min': round(min(v), 4),
+                                                               'max': round(max(v), 4), 'p90': round(sorted(v)[int(0.9 * (len(v) - 1))], 4)}
+                    diff = statistics.median(ms['columns']) - statistics.median(ms['ring'])
+                    q = sorted(ms['columns'])
+                    spread = q[int(0.75 * (len(q) - 1))] - q[int(0.25 * (len(q) - 1))]
+                    out['columns_minus_ring_ms'][key] = round(diff, 4)
+                    out['ring_wins_by_more_than_columns_spread'][key] = bool(diff > spread)
+                    assert ring.n_captures == cols.n_captures == 1
+                    del ring, cols, src
+                    torch.cuda.empty_cache()
         finally:
             hip.set_compute('fp32')
 

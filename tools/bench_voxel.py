@@ -10,7 +10,10 @@ then the conversion pass that also zeroes the sums again); an ingest with every 
 the scatter, and from it the chip-wide rate of 64-bit integer atomics with one lane per row that the pair implies.  Next to the
 record row, hip.event_ingest_columns (scatter + finish as well) on the same events held as DSEC's columns -- x / y uint16, p uint8, t
 once as float64 (the records' own times: the grids are compared as bits) and once as int64 microseconds (compared as bits with the
-record kernel on those times); reported with the record row's max - min over the repetitions as the run-to-run spread.
+record kernel on those times); reported with the record row's max - min over the repetitions as the run-to-run spread.  And
+hip.event_ingest_ring on the int64 columns laid into rings of twice the stride, the window named by device words: from position 0
+(every group of four aligned and whole, as in the column kernel), from position 3 (head and tail masked) and from a position that
+puts the wrap into the middle of the window; each compared as bits with the column kernel, reported as its difference to it.
 usage: python tools/bench_voxel.py --ingest --slices 8 --events 100000 --bins 5"""
 import argparse
 import json
@@ -119,11 +122,28 @@ def ingest(a):
     t_f64, t_i64, cx, cy, cp = (torch.from_numpy(c.view(np.int16) if c.dtype == np.uint16 else c).to(dev) for c in hcols)
     fmt_f64 = torch.full((S,), hip.EVCOL_XY_U16, dtype=torch.int32, device=dev)
     fmt_i64 = torch.full((S,), hip.EVCOL_XY_U16 | hip.EVCOL_T_I64, dtype=torch.int32, device=dev)
+    # the int64 columns as rings of 2 * stride events: the window (n events from `start` on, modulo the ring) holds the same events
+    ring = 2 * stride
+    rows_w = torch.arange(S, dtype=torch.int32, device=dev)
+    ring_starts = {'start0': 0, 'start3': 3, 'wrapped': ring - (n // 2) // 4 * 4}
+    rings = {}
+    for k, start in ring_starts.items():
+        at = (start + np.arange(n)) % ring
+        hr = [np.zeros((S, ring), c.dtype) for c in (hcols[1], hcols[2], hcols[3], hcols[4])]
+        for dst, src in zip(hr, (hcols[1], hcols[2], hcols[3], hcols[4])):
+            dst[:, at] = src[:, :n]
+        rings[k] = tuple(torch.from_numpy(c.view(np.int16) if c.dtype == np.uint16 else c).to(dev) for c in hr) + \
+            (torch.full((S,), start, dtype=torch.int32, device=dev),)
+
+    def ring_way(k):
+        rt, rx, ry, rp, starts_w = rings[k]
+        return lambda: hip.event_ingest_ring(rt, rx, ry, rp, rows_w, starts_w, counts, fmt_i64, out, acc=acc)
     ways = {'voxel_grid_temporal': lambda: hip.voxel_grid_temporal(x, y, t, p, offs, C, H, W, separate_pol=False),
             'event_ingest': lambda: hip.event_ingest(records, counts, out, acc=acc),
             'event_ingest_columns_t_i64': lambda: hip.event_ingest_columns(t_i64, cx, cy, cp, counts, fmt_i64, out, acc=acc),
             'event_ingest_columns_t_f64': lambda: hip.event_ingest_columns(t_f64, cx, cy, cp, counts, fmt_f64, out, acc=acc),
             'event_ingest_finish_only': lambda: hip.event_ingest(records, zero, out, acc=acc)}
+    ways.update({f'event_ingest_ring_{k}': ring_way(k) for k in rings})
     for fn in ways.values():  # warm-up: clocks, allocator
         for _ in range(50):
             fn()
@@ -149,6 +169,9 @@ def ingest(a):
     host['t'] = hcols[1][:, :n]
     got = hip.event_ingest(torch.from_numpy(host.view(np.uint8).reshape(S, n, 16)).to(dev), counts, torch.empty_like(out), acc=acc)
     assert torch.equal(hip.event_ingest_columns(t_i64, cx, cy, cp, counts, fmt_i64, out, acc=acc).view(torch.int32), got.view(torch.int32))
+    by_columns = out.clone()
+    for k in rings:  # the ring source gives the column kernel's bits, wherever the window starts
+        assert torch.equal(ways[f'event_ingest_ring_{k}']().view(torch.int32), by_columns.view(torch.int32)), k
     assert not bool(acc.any())
     med = {k: sorted(v)[1] for k, v in ms.items()}
     spread = max(ms['event_ingest']) - min(ms['event_ingest'])
@@ -160,6 +183,10 @@ def ingest(a):
         'record_spread_ms': round(spread, 5),
         'columns_minus_records_ms': {k[-5:]: round(med[k] - med['event_ingest'], 5) for k in med if 'columns' in k},
         'columns_slower_than_records_by_more_than_the_spread': {k[-5:]: bool(med[k] - med['event_ingest'] > spread) for k in med if 'columns' in k},
+        'ring': {'events_per_row': ring, 'starts': ring_starts,
+                 'ring_minus_columns_t_i64_ms': {k: round(med[f'event_ingest_ring_{k}'] - med['event_ingest_columns_t_i64'], 5) for k in rings},
+                 'slower_than_columns_by_more_than_the_spread': {k: bool(med[f'event_ingest_ring_{k}'] - med['event_ingest_columns_t_i64'] > spread)
+                                                                 for k in rings}},
         'bytes_per_event': {'records': 16, 'columns': 13},
         'scatter_ms': round(scatter_ms, 5), 'atomics_per_batch': atomics,
         'int64_atomics_per_s': atomics / (scatter_ms * 1e-3) if scatter_ms > 0 else None,
