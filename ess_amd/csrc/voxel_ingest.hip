@@ -1,7 +1,9 @@
 // Event ingest for the captured multi-stream round: packed 16-byte event records (ess_event_ingest) or the raw event columns a
 // camera delivers, one window per row (ess_event_ingest_columns) or windows named inside per-stream rings (ess_event_ingest_ring)
 // -> the round's voxel grids, with a sum that does not depend on the order the events arrive in (include/ess_hip.h).  The sources
-// differ in how an event is LOADED; what an event adds is one function, scatter_event.
+// differ in how an event is LOADED; what an event adds is one function per FLAVOUR: scatter_event (temporal: integer pixels, bilinear
+// in time) for all three sources, scatter_event_trilinear (the DSEC grid: rectified float coordinates, eight corners) for the column
+// and the ring source, whose kernels are templates on the flavour -- the loading code is one piece of text per source.
 //
 // voxel_temporal_kernel (voxel.hip) adds its fp32 contributions with fp32 global atomics: a voxel's value depends on which event
 // got there first, two builds of one window differ in the last bits.  Here every contribution is the SAME fp32 value (the same
@@ -98,25 +100,134 @@ __device__ __forceinline__ double column_time(long long word, bool t_i64) { retu
 // a uint16 coordinate enters as its unsigned value (32768.. lie outside every grid: dropped, never wrapped)
 __device__ __forceinline__ int column_coordinate(unsigned half, bool xy_u16) { return xy_u16 ? (int)half : (int)(short)half; }
 
+// ---- the trilinear flavour: VoxelGrid.convert on coordinates that went through the camera's rectify map, as the DSEC loader builds
+// its grids (the reference's behaviour restated, not its code).  One event adds up to eight contributions c, each the fp32 value of
+// voxel_trilinear_kernel's expression sequence (voxel.hip) -- wx = value * (1 - |xl - xe|), wxy = wx * (1 - |yl - ye|),
+// c = wxy * (1 - |tb - tn|) -- added as llrint(c * 2^40) like the temporal halves.  Every factor has magnitude <= 1 (a corner lies
+// within 1 of its coordinate, but for a coordinate in (-2, -1], whose only corner in the grid is 0 or -0 away from -1: factor in
+// (-1, 0]), so |c| <= 1, and an event's eight corners are eight distinct voxels: an event adds to a voxel at most once, at most
+// 2^40 in magnitude, and capacity <= 2^22 events per stream keep |acc| <= 2^62 as above.
+//
+// The test in front of the conversions keeps exactly the events of which some corner can land in the grid under truncation toward
+// zero: x0 = (int)xe lies in [-1, W - 1] iff -2 < xe < W (coordinates in (-2, -1] still reach column 0, with a weight <= 0: the
+// reference's quirk, kept), and alike for ye and tn.  The comparisons are written so that NaN fails them: no NaN, infinity or value
+// beyond int reaches a float -> int conversion.
+__device__ __forceinline__ void scatter_event_trilinear(float xe, float ye, float tn, int p, int nb, int H, int W, size_t plane,
+                                                        long long* __restrict__ g) {
+#pragma clang fp contract(off)
+  if (!(xe > -2.f && xe < (float)W && ye > -2.f && ye < (float)H && tn > -2.f && tn < (float)nb)) return;
+  const float value = p == 1 ? 1.f : -1.f;  // 2 * pol - 1 with pol = (byte == 1)
+  const int x0 = (int)xe, y0 = (int)ye, t0 = (int)tn;
+#pragma unroll
+  for (int dx = 0; dx < 2; ++dx) {
+    const int xl = x0 + dx;
+    if (xl < 0 || xl >= W) continue;
+    const float wx = value * (1.f - fabsf((float)xl - xe));
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+      const int yl = y0 + dy;
+      if (yl < 0 || yl >= H) continue;
+      const float wxy = wx * (1.f - fabsf((float)yl - ye));
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt) {
+        const int tb = t0 + dt;
+        if (tb < 0 || tb >= nb) continue;
+        const long long q = quantise(wxy * (1.f - fabsf((float)tb - tn)));
+        if (q != 0) atomicAdd((unsigned long long*)(g + (size_t)tb * plane + (size_t)yl * W + xl), (unsigned long long)q);
+      }
+    }
+  }
+}
+
+// the rectify maps of a call: maps [n_maps][map_h][map_w] (x, y) pairs, map_of[slot] = the slot's map, RECTIFY_NONE or anything else
+struct Rectify {
+  const float2* maps;
+  const int32_t* map_of;
+  int n_maps, map_h, map_w;
+};
+constexpr int RECTIFY_NONE = -1;  // (ESS_RECTIFY_NONE of include/ess_hip.h)
+
+// What the two column loaders hand their events to.  open(): the slot's own words beyond count and format, false: the slot counts as
+// empty;  window(): the raw time words of the window's first and last event;  add(): one event's raw words.
+struct TemporalFlavour {
+  double first, dT;
+  __device__ __forceinline__ bool open(int) { return true; }
+  __device__ __forceinline__ void window(long long w_first, long long w_last, bool t_i64, int) {
+#pragma clang fp contract(off)
+    first = column_time(w_first, t_i64);
+    dT = column_time(w_last, t_i64) - first;
+    if (dT == 0) dT = 1.0;
+  }
+  __device__ __forceinline__ void add(long long tw, unsigned xh, unsigned yh, int p, bool t_i64, bool xy_u16, int nb, int H, int W,
+                                      size_t plane, long long* __restrict__ g) const {
+    scatter_event(column_time(tw, t_i64), column_coordinate(xh, xy_u16), column_coordinate(yh, xy_u16), p, first, dT, nb, H, W, plane, g);
+  }
+};
+
+struct TrilinearFlavour {
+  const float2* map;  // the slot's map, nullptr: RECTIFY_NONE
+  int map_h, map_w;
+  long long w_first;
+  float d_last, u_first, den, cm1;
+  __device__ __forceinline__ bool open(int s, const Rectify r) {
+    const int m = r.map_of[s];
+    map_h = r.map_h;
+    map_w = r.map_w;
+    map = m >= 0 && m < r.n_maps ? r.maps + (size_t)m * r.map_h * r.map_w : nullptr;
+    return m == RECTIFY_NONE || map != nullptr;  // any other map word: as an unknown format bit
+  }
+  // d = t - t_first in the column's own type (int64: the raw words, modulo 2^64; else fp64), rounded ONCE to fp32
+  __device__ __forceinline__ float since_first(long long tw, bool t_i64) const {
+#pragma clang fp contract(off)
+    return t_i64 ? (float)(long long)((unsigned long long)tw - (unsigned long long)w_first)
+                 : (float)(__longlong_as_double(tw) - __longlong_as_double(w_first));
+  }
+  // u = d / d_last, tn = ((C - 1) * (u - u_first)) / (u_last - u_first): a window whose last time equals its first gives 0 / 0 = NaN
+  // for every event and an all-zero grid (there is no dT = 1 rescue in this flavour)
+  __device__ __forceinline__ void window(long long first_word, long long last_word, bool t_i64, int nb) {
+#pragma clang fp contract(off)
+    w_first = first_word;
+    d_last = since_first(last_word, t_i64);
+    u_first = since_first(first_word, t_i64) / d_last;
+    den = d_last / d_last - u_first;
+    cm1 = (float)(nb - 1);
+  }
+  __device__ __forceinline__ void add(long long tw, unsigned xh, unsigned yh, int p, bool t_i64, bool xy_u16, int nb, int H, int W,
+                                      size_t plane, long long* __restrict__ g) const {
+#pragma clang fp contract(off)
+    const int x = column_coordinate(xh, xy_u16), y = column_coordinate(yh, xy_u16);
+    float xe = (float)x, ye = (float)y;
+    if (map != nullptr) {
+      if (x < 0 || x >= map_w || y < 0 || y >= map_h) return;  // a raw pixel outside the sensor the map was made for: dropped
+      const float2 v = map[(size_t)y * map_w + x];
+      xe = v.x;
+      ye = v.y;
+    }
+    const float tn = (cm1 * (since_first(tw, t_i64) / d_last - u_first)) / den;
+    scatter_event_trilinear(xe, ye, tn, p, nb, H, W, plane, g);
+  }
+};
+
+template <class Flavour, class... Extra>
 __global__ __launch_bounds__(INGEST_THREADS) void event_scatter_columns_kernel(const long long* __restrict__ t, const unsigned short* __restrict__ x,
                                                                                const unsigned short* __restrict__ y,
                                                                                const unsigned char* __restrict__ p,
                                                                                const int32_t* __restrict__ counts,
                                                                                const int32_t* __restrict__ formats, int64_t stride, int nb, int H,
-                                                                               int W, long long* __restrict__ acc) {
+                                                                               int W, long long* __restrict__ acc, const Extra... extra) {
 #pragma clang fp contract(off)
   const int s = blockIdx.y;
   const int cnt = counts[s];
   const int fmt = formats[s];  // (read beside the count, not behind the test on it: the two scalar loads issue together)
   if (cnt <= 0) return;  // an empty window, or INGEST_KEEP: nothing of this stream's columns is read
   if ((fmt & ~(EVCOL_T_I64 | EVCOL_XY_U16)) != 0) return;  // an unknown format: as count 0
+  Flavour f;
+  if (!f.open(s, extra...)) return;
   const bool t_i64 = (fmt & EVCOL_T_I64) != 0, xy_u16 = (fmt & EVCOL_XY_U16) != 0;
   const int64_t n = (int64_t)cnt < stride ? (int64_t)cnt : stride;
   const size_t row = (size_t)s * stride;
   const long long* __restrict__ ts = t + row;
-  const double first = column_time(ts[0], t_i64);
-  double dT = column_time(ts[n - 1], t_i64) - first;
-  if (dT == 0) dT = 1.0;
+  f.window(ts[0], ts[n - 1], t_i64, nb);
   const size_t plane = (size_t)H * W;
   long long* __restrict__ g = acc + (size_t)s * nb * plane;
   const i64x2* __restrict__ t2 = (const i64x2*)ts;               // two events
@@ -134,8 +245,7 @@ __global__ __launch_bounds__(INGEST_THREADS) void event_scatter_columns_kernel(c
 #pragma unroll
     for (int j = 0; j < COLUMN_GROUP; ++j) {
       if (q * COLUMN_GROUP + j >= n) break;  // (the tail: loaded, inside the stride, never summed)
-      scatter_event(column_time(tw[j], t_i64), column_coordinate(xh[j], xy_u16), column_coordinate(yh[j], xy_u16),
-                    (int)((pv >> (8 * j)) & 0xffu), first, dT, nb, H, W, plane, g);
+      f.add(tw[j], xh[j], yh[j], (int)((pv >> (8 * j)) & 0xffu), t_i64, xy_u16, nb, H, W, plane, g);
     }
   }
 }
@@ -146,13 +256,15 @@ __global__ __launch_bounds__(INGEST_THREADS) void event_scatter_columns_kernel(c
 // first and the tail of the last: the loads stay 2 x 16 B, 8 B, 8 B, 4 B.  ring is a multiple of COLUMN_STRIDE_ALIGN, so no group
 // straddles the wrap and the wrap falls between two groups; a full ring from an unaligned start reads its first group twice, once
 // under each mask.
+template <class Flavour, class... Extra>
 __global__ __launch_bounds__(INGEST_THREADS) void event_scatter_ring_kernel(const long long* __restrict__ t, const unsigned short* __restrict__ x,
                                                                             const unsigned short* __restrict__ y,
                                                                             const unsigned char* __restrict__ p,
                                                                             const int32_t* __restrict__ rows, const int32_t* __restrict__ starts,
                                                                             const int32_t* __restrict__ counts,
                                                                             const int32_t* __restrict__ formats, int64_t ring, int n_rows,
-                                                                            int nb, int H, int W, long long* __restrict__ acc) {
+                                                                            int nb, int H, int W, long long* __restrict__ acc,
+                                                                            const Extra... extra) {
 #pragma clang fp contract(off)
   const int s = blockIdx.y;
   const int cnt = counts[s];
@@ -160,15 +272,15 @@ __global__ __launch_bounds__(INGEST_THREADS) void event_scatter_ring_kernel(cons
   if (cnt <= 0) return;  // an empty window, or INGEST_KEEP: nothing is read for this slot
   if ((fmt & ~(EVCOL_T_I64 | EVCOL_XY_U16)) != 0) return;  // an unknown format: as count 0
   if (r < 0 || r >= n_rows || start < 0 || (int64_t)start >= ring) return;  // a row or a start outside the rings: as count 0
+  Flavour f;
+  if (!f.open(s, extra...)) return;
   const bool t_i64 = (fmt & EVCOL_T_I64) != 0, xy_u16 = (fmt & EVCOL_XY_U16) != 0;
   const int64_t n = (int64_t)cnt < ring ? (int64_t)cnt : ring;
   const size_t row = (size_t)r * ring;
   const long long* __restrict__ ts = t + row;
   int64_t last_at = (int64_t)start + n - 1;  // (< 2 * ring)
   if (last_at >= ring) last_at -= ring;
-  const double first = column_time(ts[start], t_i64);
-  double dT = column_time(ts[last_at], t_i64) - first;
-  if (dT == 0) dT = 1.0;
+  f.window(ts[start], ts[last_at], t_i64, nb);
   const size_t plane = (size_t)H * W;
   long long* __restrict__ g = acc + (size_t)s * nb * plane;
   const i64x2* __restrict__ t2 = (const i64x2*)ts;
@@ -190,8 +302,7 @@ __global__ __launch_bounds__(INGEST_THREADS) void event_scatter_ring_kernel(cons
     for (int j = 0; j < COLUMN_GROUP; ++j) {
       const int64_t k = q * COLUMN_GROUP + j - head;  // the event's number inside the window
       if (k < 0 || k >= n) continue;                  // (the head and the tail: loaded, inside the row, never summed)
-      scatter_event(column_time(tw[j], t_i64), column_coordinate(xh[j], xy_u16), column_coordinate(yh[j], xy_u16),
-                    (int)((pv >> (8 * j)) & 0xffu), first, dT, nb, H, W, plane, g);
+      f.add(tw[j], xh[j], yh[j], (int)((pv >> (8 * j)) & 0xffu), t_i64, xy_u16, nb, H, W, plane, g);
     }
   }
 }
@@ -249,6 +360,66 @@ int launch_finish(const int32_t* counts, int32_t n_streams, int32_t bins, int32_
   return ess_launch_status(what);
 }
 
+
+// the argument checks of the two column sources, shared by their flavours; `what` names the entry point in every message
+int check_columns(const char* what, const void* t, const void* x, const void* y, const void* p, const int32_t* counts,
+                  const int32_t* formats, int64_t stride, int32_t n_streams, int32_t bins, int32_t height, int32_t width, const void* acc,
+                  size_t acc_bytes, const float* out) {
+  ESS_CHECK_ARG(t && x && y && p && counts && formats && acc && out, "%s: null t, x, y, p, counts, formats, acc or out", what);
+  ESS_CHECK_ARG(n_streams >= 1 && n_streams <= 65535, "%s: n_streams=%d (1..65535)", what, (int)n_streams);
+  ESS_CHECK_ARG(bins > 0 && height > 0 && width > 0, "%s: bins=%d height=%d width=%d must be positive", what, (int)bins, (int)height,
+                (int)width);
+  ESS_CHECK_ARG(stride >= 1 && stride <= INGEST_MAX_CAPACITY,
+                "%s: stride=%lld events per stream (1..%lld: the int64 sums hold 2^22 contributions of magnitude 1 at scale 2^40)", what,
+                (long long)stride, (long long)INGEST_MAX_CAPACITY);
+  ESS_CHECK_ARG(stride % COLUMN_STRIDE_ALIGN == 0,
+                "%s: stride=%lld must be a multiple of %d (every stream's row of every column starts 16-byte aligned)", what,
+                (long long)stride, COLUMN_STRIDE_ALIGN);
+  const size_t need = ess_event_ingest_workspace(n_streams, bins, height, width);
+  ESS_CHECK_ARG(acc_bytes >= need, "%s: acc has %zu bytes, %zu are needed", what, acc_bytes, need);
+  ESS_CHECK_ARG(((((uintptr_t)t) | ((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)p) | ((uintptr_t)acc) | ((uintptr_t)out)) & 15) == 0,
+                "%s: t, x, y, p, acc and out must be 16-byte aligned", what);
+  return ESS_OK;
+}
+
+int check_ring(const char* what, const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
+               const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots, int32_t bins, int32_t height,
+               int32_t width, const void* acc, size_t acc_bytes, const float* out) {
+  ESS_CHECK_ARG(t && x && y && p && rows && starts && counts && formats && acc && out,
+                "%s: null t, x, y, p, rows, starts, counts, formats, acc or out", what);
+  ESS_CHECK_ARG(n_slots >= 1 && n_slots <= 65535, "%s: n_slots=%d (1..65535)", what, (int)n_slots);
+  ESS_CHECK_ARG(n_rows >= 1, "%s: n_rows=%d must be positive", what, (int)n_rows);
+  ESS_CHECK_ARG(bins > 0 && height > 0 && width > 0, "%s: bins=%d height=%d width=%d must be positive", what, (int)bins, (int)height,
+                (int)width);
+  ESS_CHECK_ARG(ring >= 1 && ring <= INGEST_MAX_CAPACITY,
+                "%s: ring=%lld events per row (16..%lld: the int64 sums hold 2^22 contributions of magnitude 1 at scale 2^40)", what,
+                (long long)ring, (long long)INGEST_MAX_CAPACITY);
+  ESS_CHECK_ARG(ring % COLUMN_STRIDE_ALIGN == 0,
+                "%s: ring=%lld must be a multiple of %d (every row of every column starts 16-byte aligned, no group of %d "
+                "events straddles the wrap)",
+                what, (long long)ring, COLUMN_STRIDE_ALIGN, COLUMN_GROUP);
+  const size_t need = ess_event_ingest_workspace(n_slots, bins, height, width);
+  ESS_CHECK_ARG(acc_bytes >= need, "%s: acc has %zu bytes, %zu are needed", what, acc_bytes, need);
+  ESS_CHECK_ARG(((((uintptr_t)t) | ((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)p) | ((uintptr_t)acc) | ((uintptr_t)out)) & 15) == 0,
+                "%s: t, x, y, p, acc and out must be 16-byte aligned", what);
+  return ESS_OK;
+}
+
+// the rectify arguments of the trilinear flavour -> the kernels' Rectify
+int check_rectify(const char* what, const float* maps, const int32_t* map_of, int32_t n_maps, int32_t map_height, int32_t map_width,
+                  Rectify& r) {
+  ESS_CHECK_ARG(map_of, "%s: null map_of", what);
+  ESS_CHECK_ARG(n_maps >= 0, "%s: n_maps=%d must not be negative", what, (int)n_maps);
+  ESS_CHECK_ARG((maps != nullptr) == (n_maps > 0), "%s: maps must be null with n_maps=0 and only then (n_maps=%d, maps %s)", what,
+                (int)n_maps, maps ? "given" : "null");
+  ESS_CHECK_ARG(map_height >= 1 && map_height <= 32768 && map_width >= 1 && map_width <= 32768,
+                "%s: map_height=%d map_width=%d (1..32768 each: the sensor's size, whatever the grid's)", what, (int)map_height,
+                (int)map_width);
+  ESS_CHECK_ARG((((uintptr_t)maps) & 15) == 0, "%s: maps must be 16-byte aligned", what);
+  r = Rectify{(const float2*)maps, map_of, n_maps, map_height, map_width};
+  return ESS_OK;
+}
+
 }  // namespace
 
 extern "C" size_t ess_event_ingest_workspace(int32_t n_streams, int32_t bins, int32_t height, int32_t width) {
@@ -280,56 +451,69 @@ extern "C" int ess_event_ingest(const void* records, const int32_t* counts, int6
 extern "C" int ess_event_ingest_columns(const void* t, const void* x, const void* y, const void* p, const int32_t* counts,
                                         const int32_t* formats, int64_t stride, int32_t n_streams, int32_t bins, int32_t height,
                                         int32_t width, void* acc, size_t acc_bytes, float* out, ess_stream_t stream) {
-  ESS_CHECK_ARG(t && x && y && p && counts && formats && acc && out,
-                "event_ingest_columns: null t, x, y, p, counts, formats, acc or out");
-  ESS_CHECK_ARG(n_streams >= 1 && n_streams <= 65535, "event_ingest_columns: n_streams=%d (1..65535)", (int)n_streams);
-  ESS_CHECK_ARG(bins > 0 && height > 0 && width > 0, "event_ingest_columns: bins=%d height=%d width=%d must be positive", (int)bins,
-                (int)height, (int)width);
-  ESS_CHECK_ARG(stride >= 1 && stride <= INGEST_MAX_CAPACITY,
-                "event_ingest_columns: stride=%lld events per stream (1..%lld: the int64 sums hold 2^22 contributions of magnitude 1 at scale 2^40)",
-                (long long)stride, (long long)INGEST_MAX_CAPACITY);
-  ESS_CHECK_ARG(stride % COLUMN_STRIDE_ALIGN == 0,
-                "event_ingest_columns: stride=%lld must be a multiple of %d (every stream's row of every column starts 16-byte aligned)",
-                (long long)stride, COLUMN_STRIDE_ALIGN);
-  const size_t need = ess_event_ingest_workspace(n_streams, bins, height, width);
-  ESS_CHECK_ARG(acc_bytes >= need, "event_ingest_columns: acc has %zu bytes, %zu are needed", acc_bytes, need);
-  ESS_CHECK_ARG(((((uintptr_t)t) | ((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)p) | ((uintptr_t)acc) | ((uintptr_t)out)) & 15) == 0,
-                "event_ingest_columns: t, x, y, p, acc and out must be 16-byte aligned");
+  int rc = check_columns("event_ingest_columns", t, x, y, p, counts, formats, stride, n_streams, bins, height, width, acc, acc_bytes, out);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(event_scatter_columns_kernel, dim3(scatter_blocks(stride), (unsigned)n_streams), dim3(INGEST_THREADS), 0, st,
-                     (const long long*)t, (const unsigned short*)x, (const unsigned short*)y, (const unsigned char*)p, counts, formats, stride,
-                     bins, height, width, (long long*)acc);
-  int rc = ess_launch_status("event_ingest_columns(scatter)");
+  hipLaunchKernelGGL((event_scatter_columns_kernel<TemporalFlavour>), dim3(scatter_blocks(stride), (unsigned)n_streams),
+                     dim3(INGEST_THREADS), 0, st, (const long long*)t, (const unsigned short*)x, (const unsigned short*)y,
+                     (const unsigned char*)p, counts, formats, stride, bins, height, width, (long long*)acc);
+  rc = ess_launch_status("event_ingest_columns(scatter)");
   if (rc) return rc;
   return launch_finish(counts, n_streams, bins, height, width, acc, out, st, "event_ingest_columns(finish)");
+}
+
+extern "C" int ess_event_ingest_columns_trilinear(const void* t, const void* x, const void* y, const void* p, const int32_t* counts,
+                                                  const int32_t* formats, int64_t stride, int32_t n_streams, int32_t bins,
+                                                  int32_t height, int32_t width, void* acc, size_t acc_bytes, float* out,
+                                                  const float* maps, const int32_t* map_of, int32_t n_maps, int32_t map_height,
+                                                  int32_t map_width, ess_stream_t stream) {
+  const char* what = "event_ingest_columns_trilinear";
+  int rc = check_columns(what, t, x, y, p, counts, formats, stride, n_streams, bins, height, width, acc, acc_bytes, out);
+  if (rc) return rc;
+  Rectify rect;
+  rc = check_rectify(what, maps, map_of, n_maps, map_height, map_width, rect);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((event_scatter_columns_kernel<TrilinearFlavour, Rectify>), dim3(scatter_blocks(stride), (unsigned)n_streams),
+                     dim3(INGEST_THREADS), 0, st, (const long long*)t, (const unsigned short*)x, (const unsigned short*)y,
+                     (const unsigned char*)p, counts, formats, stride, bins, height, width, (long long*)acc, rect);
+  rc = ess_launch_status("event_ingest_columns_trilinear(scatter)");
+  if (rc) return rc;
+  return launch_finish(counts, n_streams, bins, height, width, acc, out, st, "event_ingest_columns_trilinear(finish)");
 }
 
 extern "C" int ess_event_ingest_ring(const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
                                      const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots,
                                      int32_t bins, int32_t height, int32_t width, void* acc, size_t acc_bytes, float* out,
                                      ess_stream_t stream) {
-  ESS_CHECK_ARG(t && x && y && p && rows && starts && counts && formats && acc && out,
-                "event_ingest_ring: null t, x, y, p, rows, starts, counts, formats, acc or out");
-  ESS_CHECK_ARG(n_slots >= 1 && n_slots <= 65535, "event_ingest_ring: n_slots=%d (1..65535)", (int)n_slots);
-  ESS_CHECK_ARG(n_rows >= 1, "event_ingest_ring: n_rows=%d must be positive", (int)n_rows);
-  ESS_CHECK_ARG(bins > 0 && height > 0 && width > 0, "event_ingest_ring: bins=%d height=%d width=%d must be positive", (int)bins,
-                (int)height, (int)width);
-  ESS_CHECK_ARG(ring >= 1 && ring <= INGEST_MAX_CAPACITY,
-                "event_ingest_ring: ring=%lld events per row (16..%lld: the int64 sums hold 2^22 contributions of magnitude 1 at scale 2^40)",
-                (long long)ring, (long long)INGEST_MAX_CAPACITY);
-  ESS_CHECK_ARG(ring % COLUMN_STRIDE_ALIGN == 0,
-                "event_ingest_ring: ring=%lld must be a multiple of %d (every row of every column starts 16-byte aligned, no group of %d "
-                "events straddles the wrap)",
-                (long long)ring, COLUMN_STRIDE_ALIGN, COLUMN_GROUP);
-  const size_t need = ess_event_ingest_workspace(n_slots, bins, height, width);
-  ESS_CHECK_ARG(acc_bytes >= need, "event_ingest_ring: acc has %zu bytes, %zu are needed", acc_bytes, need);
-  ESS_CHECK_ARG(((((uintptr_t)t) | ((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)p) | ((uintptr_t)acc) | ((uintptr_t)out)) & 15) == 0,
-                "event_ingest_ring: t, x, y, p, acc and out must be 16-byte aligned");
+  int rc = check_ring("event_ingest_ring", t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, bins, height, width, acc,
+                      acc_bytes, out);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(event_scatter_ring_kernel, dim3(scatter_blocks(ring), (unsigned)n_slots), dim3(INGEST_THREADS), 0, st,
-                     (const long long*)t, (const unsigned short*)x, (const unsigned short*)y, (const unsigned char*)p, rows, starts, counts,
-                     formats, ring, n_rows, bins, height, width, (long long*)acc);
-  int rc = ess_launch_status("event_ingest_ring(scatter)");
+  hipLaunchKernelGGL((event_scatter_ring_kernel<TemporalFlavour>), dim3(scatter_blocks(ring), (unsigned)n_slots), dim3(INGEST_THREADS), 0,
+                     st, (const long long*)t, (const unsigned short*)x, (const unsigned short*)y, (const unsigned char*)p, rows, starts,
+                     counts, formats, ring, n_rows, bins, height, width, (long long*)acc);
+  rc = ess_launch_status("event_ingest_ring(scatter)");
   if (rc) return rc;
   return launch_finish(counts, n_slots, bins, height, width, acc, out, st, "event_ingest_ring(finish)");
+}
+
+extern "C" int ess_event_ingest_ring_trilinear(const void* t, const void* x, const void* y, const void* p, const int32_t* rows,
+                                               const int32_t* starts, const int32_t* counts, const int32_t* formats, int64_t ring,
+                                               int32_t n_rows, int32_t n_slots, int32_t bins, int32_t height, int32_t width, void* acc,
+                                               size_t acc_bytes, float* out, const float* maps, const int32_t* map_of, int32_t n_maps,
+                                               int32_t map_height, int32_t map_width, ess_stream_t stream) {
+  const char* what = "event_ingest_ring_trilinear";
+  int rc = check_ring(what, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, bins, height, width, acc, acc_bytes, out);
+  if (rc) return rc;
+  Rectify rect;
+  rc = check_rectify(what, maps, map_of, n_maps, map_height, map_width, rect);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((event_scatter_ring_kernel<TrilinearFlavour, Rectify>), dim3(scatter_blocks(ring), (unsigned)n_slots),
+                     dim3(INGEST_THREADS), 0, st, (const long long*)t, (const unsigned short*)x, (const unsigned short*)y,
+                     (const unsigned char*)p, rows, starts, counts, formats, ring, n_rows, bins, height, width, (long long*)acc, rect);
+  rc = ess_launch_status("event_ingest_ring_trilinear(scatter)");
+  if (rc) return rc;
+  return launch_finish(counts, n_slots, bins, height, width, acc, out, st, "event_ingest_ring_trilinear(finish)");
 }

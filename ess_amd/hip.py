@@ -78,6 +78,7 @@ EXPORTS = [
     'ess_to_f16_c8', 'ess_bf16_c8_to_f16_c8', 'ess_f16_c8_to_bf16_c8', 'ess_instnorm_forward_c8_mixed', 'ess_seg_head',
     'ess_event_normalize_samples', 'ess_state_carry_masked', 'ess_state_carry_indexed',
     'ess_event_ingest_workspace', 'ess_event_ingest', 'ess_event_ingest_columns', 'ess_event_ingest_ring',
+    'ess_event_ingest_columns_trilinear', 'ess_event_ingest_ring_trilinear',
 ]
 
 
@@ -175,6 +176,8 @@ def lib():
             'ess_event_ingest': [P, P, I64, I, I, I, I, P, c_size_t, P, P],
             'ess_event_ingest_columns': [P, P, P, P, P, P, I64, I, I, I, I, P, c_size_t, P, P],
             'ess_event_ingest_ring': [P, P, P, P, P, P, P, P, I64, I, I, I, I, I, P, c_size_t, P, P],
+            'ess_event_ingest_columns_trilinear': [P, P, P, P, P, P, I64, I, I, I, I, P, c_size_t, P, P, P, I, I, I, P],
+            'ess_event_ingest_ring_trilinear': [P, P, P, P, P, P, P, P, I64, I, I, I, I, I, P, c_size_t, P, P, P, I, I, I, P],
         }
         for name, argtypes in sig.items():
             fn = getattr(L, name)
@@ -895,35 +898,82 @@ def event_ingest_columns(t, x, y, p, counts, formats, out, acc=None):
     other bit: the stream counts as empty), a device int32 [S] read by the kernel like counts, so one captured call serves streams
     whose formats change from round to round.  p: +1 where the byte equals 1, -1 otherwise.  stride: a multiple of 16
     (event_column_stride).  counts, out, acc: as event_ingest."""
+    return _event_ingest_columns('event_ingest_columns', t, x, y, p, counts, formats, out, acc, None)
+
+
+def _event_ingest_columns(fn, t, x, y, p, counts, formats, out, acc, rectify):
+    """event_ingest_columns (rectify None) / event_ingest_columns_trilinear (rectify: (maps, map_of) as given): the checks and the call"""
     named = (('t', t), ('x', x), ('y', y), ('p', p), ('counts', counts), ('formats', formats), ('out', out))
     for name, v in named + ((('acc', acc),) if acc is not None else ()):
         if not torch.is_tensor(v) or not v.is_cuda:
-            raise EssHipError(f'event_ingest_columns: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
         if not v.is_contiguous():
-            raise EssHipError(f'event_ingest_columns: {name} must be contiguous')
+            raise EssHipError(f'{fn}: {name} must be contiguous')
     if out.dim() != 4 or out.dtype != torch.float32 or out.numel() == 0:
-        raise EssHipError(f'event_ingest_columns: out must be a non-empty fp32 [S, bins, H, W] tensor, got {out.dtype}{tuple(out.shape)}')
+        raise EssHipError(f'{fn}: out must be a non-empty fp32 [S, bins, H, W] tensor, got {out.dtype}{tuple(out.shape)}')
     S, bins, H, W = out.shape
     if t.dim() != 2 or t.shape[0] != S or t.shape[1] < 1:
-        raise EssHipError(f'event_ingest_columns: t must be [{S}, stride], got {tuple(t.shape)}')
+        raise EssHipError(f'{fn}: t must be [{S}, stride], got {tuple(t.shape)}')
     for name, v in named[:4]:
         if v.dtype not in _EVCOL_DTYPES[name] or v.shape != t.shape:
-            raise EssHipError(f'event_ingest_columns: {name} must be {" / ".join(str(d) for d in _EVCOL_DTYPES[name])} '
+            raise EssHipError(f'{fn}: {name} must be {" / ".join(str(d) for d in _EVCOL_DTYPES[name])} '
                               f'{list(t.shape)}, got {v.dtype}{tuple(v.shape)}')
     for name, v in named[4:6]:
         if v.dtype != torch.int32 or tuple(v.shape) != (S,):
-            raise EssHipError(f'event_ingest_columns: {name} must be int32 [{S}], got {v.dtype}{tuple(v.shape)}')
+            raise EssHipError(f'{fn}: {name} must be int32 [{S}], got {v.dtype}{tuple(v.shape)}')
     L = lib()
     need = L.ess_event_ingest_workspace(S, bins, H, W)
     if acc is None:
         acc = torch.zeros(need // 8, dtype=torch.int64, device=out.device)
     elif acc.dtype != torch.int64:
-        raise EssHipError(f'event_ingest_columns: acc must be int64, got {acc.dtype}')
-    _check(L.ess_event_ingest_columns(c_void_p(t.data_ptr()), c_void_p(x.data_ptr()), c_void_p(y.data_ptr()), c_void_p(p.data_ptr()),
-                                      ptr(counts, torch.int32), ptr(formats, torch.int32), t.shape[1], S, bins, H, W,
-                                      c_void_p(acc.data_ptr()), acc.numel() * 8, c_void_p(out.data_ptr()), stream()),
-           'ess_event_ingest_columns')
+        raise EssHipError(f'{fn}: acc must be int64, got {acc.dtype}')
+    tail = () if rectify is None else _rectify_args(fn, rectify[0], rectify[1], S, out.device)
+    _check(getattr(L, 'ess_' + fn)(c_void_p(t.data_ptr()), c_void_p(x.data_ptr()), c_void_p(y.data_ptr()), c_void_p(p.data_ptr()),
+                                   ptr(counts, torch.int32), ptr(formats, torch.int32), t.shape[1], S, bins, H, W,
+                                   c_void_p(acc.data_ptr()), acc.numel() * 8, c_void_p(out.data_ptr()), *tail, stream()), 'ess_' + fn)
     return out
+
+
+RECTIFY_NONE = -1  # ESS_RECTIFY_NONE: a map word for a stream whose raw pixels are its coordinates
+RECTIFY_MAX_SIDE = 32768
+
+
+def _rectify_args(fn, maps, map_of, n, device):
+    """maps: None or device fp32 [n_maps, map_h, map_w, 2]; map_of: None (RECTIFY_NONE for every slot) or device int32 [n] -> the
+    five rectify arguments of the trilinear entry points.  Without maps the map size is (1, 1): no word names a map."""
+    if maps is None:
+        n_maps, mh, mw = 0, 1, 1
+    else:
+        if not torch.is_tensor(maps) or maps.dtype != torch.float32 or maps.dim() != 4 or maps.shape[3] != 2 or maps.numel() == 0:
+            got = f'{maps.dtype}{tuple(maps.shape)}' if torch.is_tensor(maps) else type(maps).__name__
+            raise EssHipError(f'{fn}: maps must be a non-empty fp32 [n_maps, map_h, map_w, 2] tensor or None, got {got}')
+        n_maps, mh, mw = maps.shape[:3]
+        if mh > RECTIFY_MAX_SIDE or mw > RECTIFY_MAX_SIDE:
+            raise EssHipError(f'{fn}: maps of {mh} x {mw} pixels: a side is 1..{RECTIFY_MAX_SIDE}')
+    if map_of is None:
+        map_of = torch.full((n,), RECTIFY_NONE, dtype=torch.int32, device=device)
+    elif not torch.is_tensor(map_of) or map_of.dtype != torch.int32 or tuple(map_of.shape) != (n,):
+        got = f'{map_of.dtype}{tuple(map_of.shape)}' if torch.is_tensor(map_of) else type(map_of).__name__
+        raise EssHipError(f'{fn}: map_of must be int32 [{n}] or None, got {got}')
+    for name, v in (('maps', maps), ('map_of', map_of)):
+        if v is not None and not v.is_cuda:
+            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+        if v is not None and not v.is_contiguous():
+            raise EssHipError(f'{fn}: {name} must be contiguous')
+    return (c_void_p(0 if maps is None else maps.data_ptr()), ptr(map_of, torch.int32), n_maps, mh, mw)
+
+
+def event_ingest_columns_trilinear(t, x, y, p, counts, formats, out, maps=None, map_of=None, acc=None):
+    """event_ingest_columns in the TRILINEAR flavour, the grid the DSEC loader builds: each raw (x, y) goes through its stream's
+    rectify map, the float coordinates and the time -- normalised in fp32 as the loader does -- are spread over the up to eight
+    corners VoxelGrid.convert gives them (hip.voxel_grid_trilinear's per-event expressions), and the contributions are summed in
+    64-bit fixed point like the temporal flavour's: out is a pure function of the set of events.  maps: device fp32
+    [n_maps, map_h, map_w, 2], entry [y, x] = the rectified (x, y) -- the SENSOR's size, whatever the grid's -- or None; map_of:
+    device int32 [S], read on the device -- RECTIFY_NONE: the integer pixel is the coordinate, 0 .. n_maps - 1: that map (a raw
+    pixel outside it drops the event), anything else: the stream counts as empty -- or None: RECTIFY_NONE throughout.  A window
+    whose last time equals its first gives an all-zero grid.  VoxelGrid(normalize=True)'s own normalisation is not applied.
+    Everything else: as event_ingest_columns."""
+    return _event_ingest_columns('event_ingest_columns_trilinear', t, x, y, p, counts, formats, out, acc, (maps, map_of))
 
 
 def event_ingest_ring(t, x, y, p, rows, starts, counts, formats, out, acc=None):
@@ -934,44 +984,57 @@ def event_ingest_ring(t, x, y, p, rows, starts, counts, formats, out, acc=None):
     an all-zero grid, INGEST_KEEP (< 0): out[i] is neither read nor written, a count above ring: ring; a row outside [0, n_rows), a
     start outside [0, ring) or an unknown format bit: the slot counts as empty.  Two slots may name one row.  out: fp32
     [n_slots, bins, H, W], returned; acc: as event_ingest, at least n_slots * bins * H * W elements."""
+    return _event_ingest_ring('event_ingest_ring', t, x, y, p, rows, starts, counts, formats, out, acc, None)
+
+
+def _event_ingest_ring(fn, t, x, y, p, rows, starts, counts, formats, out, acc, rectify):
+    """event_ingest_ring (rectify None) / event_ingest_ring_trilinear (rectify: (maps, map_of) as given): the checks and the call"""
     named = (('t', t), ('x', x), ('y', y), ('p', p), ('rows', rows), ('starts', starts), ('counts', counts), ('formats', formats),
              ('out', out))
     every = named + ((('acc', acc),) if acc is not None else ())
     for name, v in every:
         if not torch.is_tensor(v):
-            raise EssHipError(f'event_ingest_ring: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
     if out.dim() != 4 or out.dtype != torch.float32 or out.numel() == 0:
-        raise EssHipError(f'event_ingest_ring: out must be a non-empty fp32 [n_slots, bins, H, W] tensor, got {out.dtype}{tuple(out.shape)}')
+        raise EssHipError(f'{fn}: out must be a non-empty fp32 [n_slots, bins, H, W] tensor, got {out.dtype}{tuple(out.shape)}')
     n_slots, bins, H, W = out.shape
     if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise EssHipError(f'event_ingest_ring: t must be [n_rows, ring], got {tuple(t.shape)}')
+        raise EssHipError(f'{fn}: t must be [n_rows, ring], got {tuple(t.shape)}')
     for name, v in named[:4]:
         if v.dtype not in _EVCOL_DTYPES[name] or v.shape != t.shape:
-            raise EssHipError(f'event_ingest_ring: {name} must be {" / ".join(str(d) for d in _EVCOL_DTYPES[name])} '
+            raise EssHipError(f'{fn}: {name} must be {" / ".join(str(d) for d in _EVCOL_DTYPES[name])} '
                               f'{list(t.shape)}, got {v.dtype}{tuple(v.shape)}')
     for name, v in named[4:8]:
         if v.dtype != torch.int32 or tuple(v.shape) != (n_slots,):
-            raise EssHipError(f'event_ingest_ring: {name} must be int32 [{n_slots}], got {v.dtype}{tuple(v.shape)}')
+            raise EssHipError(f'{fn}: {name} must be int32 [{n_slots}], got {v.dtype}{tuple(v.shape)}')
     if acc is not None and acc.dtype != torch.int64:
-        raise EssHipError(f'event_ingest_ring: acc must be int64, got {acc.dtype}')
+        raise EssHipError(f'{fn}: acc must be int64, got {acc.dtype}')
     n_rows, ring = t.shape
     if ring % EVCOL_STRIDE_ALIGN or ring > INGEST_MAX_CAPACITY:
-        raise EssHipError(f'event_ingest_ring: ring={ring} must be a multiple of {EVCOL_STRIDE_ALIGN} in [{EVCOL_STRIDE_ALIGN}, '
+        raise EssHipError(f'{fn}: ring={ring} must be a multiple of {EVCOL_STRIDE_ALIGN} in [{EVCOL_STRIDE_ALIGN}, '
                           f'{INGEST_MAX_CAPACITY}] (event_column_stride rounds a capacity up)')
     for name, v in every:  # (the device last: what is wrong with a tensor's form is said whatever memory it lies in)
         if not v.is_cuda:
-            raise EssHipError(f'event_ingest_ring: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
         if not v.is_contiguous():
-            raise EssHipError(f'event_ingest_ring: {name} must be contiguous')
+            raise EssHipError(f'{fn}: {name} must be contiguous')
     L = lib()
     need = L.ess_event_ingest_workspace(n_slots, bins, H, W)
     if acc is None:
         acc = torch.zeros(need // 8, dtype=torch.int64, device=out.device)
-    _check(L.ess_event_ingest_ring(c_void_p(t.data_ptr()), c_void_p(x.data_ptr()), c_void_p(y.data_ptr()), c_void_p(p.data_ptr()),
+    tail = () if rectify is None else _rectify_args(fn, rectify[0], rectify[1], n_slots, out.device)
+    _check(getattr(L, 'ess_' + fn)(c_void_p(t.data_ptr()), c_void_p(x.data_ptr()), c_void_p(y.data_ptr()), c_void_p(p.data_ptr()),
                                    ptr(rows, torch.int32), ptr(starts, torch.int32), ptr(counts, torch.int32), ptr(formats, torch.int32),
                                    ring, n_rows, n_slots, bins, H, W, c_void_p(acc.data_ptr()), acc.numel() * 8,
-                                   c_void_p(out.data_ptr()), stream()), 'ess_event_ingest_ring')
+                                   c_void_p(out.data_ptr()), *tail, stream()), 'ess_' + fn)
     return out
+
+
+def event_ingest_ring_trilinear(t, x, y, p, rows, starts, counts, formats, out, maps=None, map_of=None, acc=None):
+    """event_ingest_ring in the trilinear flavour: the same grids, bit for bit, as event_ingest_columns_trilinear gives on the same
+    windows laid out from entry 0.  maps, map_of (int32 [n_slots], slot i's map): as event_ingest_columns_trilinear; everything else:
+    as event_ingest_ring."""
+    return _event_ingest_ring('event_ingest_ring_trilinear', t, x, y, p, rows, starts, counts, formats, out, acc, (maps, map_of))
 
 
 def voxel_normalize_(grids, mode):

@@ -296,6 +296,55 @@ def _event_layout(layout, event_capacity):
     return layout
 
 
+VOXEL_FLAVOURS = ('temporal', 'trilinear')
+
+
+def _voxel_flavour(voxel, layout, event_capacity):
+    """MultiStreamSegmenter's voxel argument, checked against event_layout and event_capacity (the arguments as given) -> the flavour"""
+    if voxel not in VOXEL_FLAVOURS:
+        raise hip.EssHipError(f'voxel={voxel!r}: one of {VOXEL_FLAVOURS}')
+    if voxel == 'trilinear' and (event_capacity is None or layout == 'records'):
+        raise hip.EssHipError(f"voxel='trilinear' is built from raw event columns inside the round: pass event_capacity=N and "
+                              f"event_layout='columns' or 'ring' (got event_layout={layout!r}, event_capacity={event_capacity!r})")
+    return voxel
+
+
+def _rectify_maps(rectify_maps, voxel, n_streams):
+    """MultiStreamSegmenter's rectify_maps argument, checked -> (the distinct maps stacked, host fp32 [n_maps, map_h, map_w, 2], or
+    None where no stream has one; per stream its map's number or hip.RECTIFY_NONE).  Entries that are the same object share a map."""
+    none = [hip.RECTIFY_NONE] * n_streams
+    if rectify_maps is None:
+        return None, none
+    if voxel != 'trilinear':
+        raise hip.EssHipError(f"rectify_maps belongs to voxel='trilinear' (this segmenter: voxel={voxel!r}): the temporal grid takes the "
+                              'integer pixels as they are')
+    if not isinstance(rectify_maps, (list, tuple)) or len(rectify_maps) != n_streams:
+        n = len(rectify_maps) if isinstance(rectify_maps, (list, tuple)) else type(rectify_maps).__name__
+        raise hip.EssHipError(f'rectify_maps must be a list with one entry per stream (a map or None): got {n}, the segmenter serves '
+                              f'n_streams={n_streams}')
+    seen, maps, map_of = {}, [], []
+    for s, m in enumerate(rectify_maps):
+        if m is None:
+            map_of.append(hip.RECTIFY_NONE)
+            continue
+        if id(m) not in seen:
+            if not (torch.is_tensor(m) or isinstance(m, np.ndarray)):
+                raise hip.EssHipError(f'rectify_maps[{s}] must be a float32 array or tensor [map_h, map_w, 2] or None, got {type(m).__name__}')
+            v = torch.as_tensor(m)
+            if v.dtype != torch.float32:
+                raise hip.EssHipError(f'rectify_maps[{s}] must be float32 (the rectify map as the file holds it), got {v.dtype}')
+            if v.dim() != 3 or v.shape[2] != 2 or v.numel() == 0 or max(v.shape[:2]) > hip.RECTIFY_MAX_SIDE:
+                raise hip.EssHipError(f'rectify_maps[{s}] must be [map_h, map_w, 2] with sides in 1..{hip.RECTIFY_MAX_SIDE}: entry [y, x] = '
+                                      f'the rectified (x, y); got {tuple(v.shape)}')
+            if maps and v.shape != maps[0].shape:
+                raise hip.EssHipError(f'rectify_maps[{s}] is {tuple(v.shape)}, the maps before it {tuple(maps[0].shape)}: one call reads '
+                                      'maps of one sensor size')
+            seen[id(m)] = len(maps)
+            maps.append(v.detach().cpu())
+        map_of.append(seen[id(m)])
+    return (torch.stack(maps).contiguous() if maps else None), map_of
+
+
 def check_stream_columns(events, n_streams):
     """events: S entries, each a datasets.data_util.EventColumns or None / empty (idle) -> (list of EventColumns or None, active)"""
     from .datasets.data_util import EventColumns
@@ -312,24 +361,28 @@ def check_stream_columns(events, n_streams):
 
 
 class _ColumnStage:
-    """one pinned staging set of the column ingest: the four columns [S, stride] and the words [2, S] (counts, formats) as torch
-    (pinned) and as numpy views, the event recorded behind the set's last upload, and the (slot, events) pairs staged for the next"""
-    __slots__ = ('cols', 'words', 'cols_np', 'counts_np', 'formats_np', 'done', 'used')
+    """one pinned staging set of the column ingest: the four columns [S, stride] and the words [2, S] (counts, formats; voxel=
+    'trilinear': [3, S], the map words behind them) as torch (pinned) and as numpy views, the event recorded behind the set's last
+    upload, and the (slot, events) pairs staged for the next"""
+    __slots__ = ('cols', 'words', 'cols_np', 'counts_np', 'formats_np', 'maps_np', 'done', 'used')
 
     def __init__(self, cols, words, done):
         self.cols, self.words, self.done, self.used = cols, words, done, ()
         self.cols_np = tuple(c.numpy() for c in cols)
         self.counts_np, self.formats_np = words.numpy()[0], words.numpy()[1]
+        self.maps_np = words.numpy()[2] if words.shape[0] > 2 else None
 
 
 class _RingStage:
-    """one pinned staging set of the ring ingest: the words [4, S] (rows, starts, counts, formats) as torch (pinned) and as numpy
-    views, and the event recorded behind the set's last upload.  No event is staged: they went to the device ring when they arrived"""
-    __slots__ = ('words', 'rows_np', 'starts_np', 'counts_np', 'formats_np', 'done', 'used')
+    """one pinned staging set of the ring ingest: the words [4, S] (rows, starts, counts, formats; voxel='trilinear': [5, S], the map
+    words behind them) as torch (pinned) and as numpy views, and the event recorded behind the set's last upload.  No event is
+    staged: they went to the device ring when they arrived"""
+    __slots__ = ('words', 'rows_np', 'starts_np', 'counts_np', 'formats_np', 'maps_np', 'done', 'used')
 
     def __init__(self, words, done):
         self.words, self.done, self.used = words, done, ()
-        self.rows_np, self.starts_np, self.counts_np, self.formats_np = words.numpy()
+        self.rows_np, self.starts_np, self.counts_np, self.formats_np = words.numpy()[:4]
+        self.maps_np = words.numpy()[4] if words.shape[0] > 4 else None
 
 
 class _Feed:
@@ -401,11 +454,23 @@ class MultiStreamSegmenter(GraphedWindowState):
     (datasets.event_feed.EventWindows).  update_from_feed(active=None) runs one round on the oldest pending window of every stream
     that has one: its upload is the four words per slot -- row, start, count, format -- that hip.event_ingest_ring reads inside
     the capture; an event crosses to the device once however many overlapping windows read it.  pending(stream), drop_feed(streams);
-    update_from_events raises.  Labels, colours and confidences equal the column path's on the same windows bit for bit."""
+    update_from_events raises.  Labels, colours and confidences equal the column path's on the same windows bit for bit.
+
+    voxel='trilinear' (with event_layout='columns' or 'ring'; 'temporal', the default, is everything above, unchanged): the round
+    starts with hip.event_ingest_columns_trilinear / hip.event_ingest_ring_trilinear and builds the grid a DSEC-trained decoder
+    expects from the same raw columns -- each (x, y) through the stream's rectify map on the device, time normalised in fp32 as the
+    DSEC loader does, eight trilinear corners per event (VoxelGrid.convert), summed in 64-bit fixed point like the temporal grid.
+    rectify_maps: n_streams entries, None or a float32 [map_h, map_w, 2] array / tensor (entry [y, x] = the rectified (x, y); the
+    sensor's size, which may exceed the grid's: a 480-row map over height=440 cuts DSEC's 40 bottom rows), all of one shape,
+    uploaded once here; entries that are the SAME object share one device copy (a stereo rig: two maps; a farm replaying one
+    camera: one).  A stream without a map takes its integer pixels as coordinates.  The stream's map number is a device word that
+    travels with its count and format (the words grow by one row: [3, S] / [5, S]; still one upload a round), and a compacted round
+    writes it per slot.  Not reproduced from the DSEC loader: VoxelGrid(normalize=True)'s own per-grid normalisation in front of the
+    event preprocessor's -- the grid enters the round as the raw sums."""
 
     def __init__(self, encoder, decoder, height, width, options, n_streams, device=None, graph=False, copy=True, palette=None,
                  want_confidence=False, out_hw=None, compact=False, compact_buckets=None, event_capacity=None, event_layout='records',
-                 ring_capacity=None, window_events=None, window_duration=None, window_stride=None):
+                 ring_capacity=None, window_events=None, window_duration=None, window_stride=None, voxel='temporal', rectify_maps=None):
         if not isinstance(n_streams, int) or isinstance(n_streams, bool) or n_streams < 1:
             raise hip.EssHipError(f'n_streams={n_streams!r}: a positive number of streams is needed')
         self.compact = bool(compact)
@@ -437,6 +502,9 @@ class MultiStreamSegmenter(GraphedWindowState):
         self._pending = [True] * S
         self.event_layout = _event_layout(event_layout, event_capacity)
         self.event_capacity = None if event_capacity is None else _event_capacity(event_capacity, height, width)
+        self.voxel = _voxel_flavour(voxel, self.event_layout, event_capacity)
+        maps, self._map_of = _rectify_maps(rectify_maps, self.voxel, n_streams)
+        self._maps = None if maps is None else maps.to(self.device)  # (uploaded once, here)
         if self.event_layout == 'ring':
             self._build_ingest_ring(ring_capacity, window_events, window_duration, window_stride)
         elif not (ring_capacity is None and window_events is None and window_duration is None and window_stride is None):
@@ -448,7 +516,8 @@ class MultiStreamSegmenter(GraphedWindowState):
             self._build_compact()
 
     # ---- event ingest (event_capacity=N): static record / count buffers the captured round reads, pinned staging in front of them
-    event_capacity = ring_capacity = _records = _columns = _counts = _formats = _acc = _ring = None
+    event_capacity = ring_capacity = _records = _columns = _counts = _formats = _acc = _ring = _maps = None
+    voxel = 'temporal'
 
     def _build_ingest(self):
         """Device records [S, N, 16], counts [S] and the int64 sums of hip.event_ingest (zeroed here, once), and two pinned staging
@@ -473,14 +542,17 @@ class MultiStreamSegmenter(GraphedWindowState):
         S, stride = self.n_streams, hip.event_column_stride(self.event_capacity)
         dtypes = (torch.int64, torch.int16, torch.int16, torch.uint8)
         self._columns = tuple(torch.zeros(S, stride, dtype=d, device=self.device) for d in dtypes)
-        self._words = torch.zeros(2, S, dtype=torch.int32, device=self.device)
+        n_words = 3 if self.voxel == 'trilinear' else 2  # (the map words ride behind the counts and formats: still one upload)
+        self._words = torch.zeros(n_words, S, dtype=torch.int32, device=self.device)
         self._counts, self._formats = self._words[0], self._words[1]
         self._counts.fill_(hip.INGEST_KEEP)
+        self._words[2:].fill_(hip.RECTIFY_NONE)
         self._acc = torch.zeros(S, self.num_bins, self.height, self.width, dtype=torch.int64, device=self.device)
         self._stage = []
         for _ in range(2):
-            words = torch.zeros(2, S, dtype=torch.int32).pin_memory()
+            words = torch.zeros(n_words, S, dtype=torch.int32).pin_memory()
             words[0].fill_(hip.INGEST_KEEP)
+            words[2:].fill_(hip.RECTIFY_NONE)
             self._stage.append(_ColumnStage(tuple(torch.zeros(S, stride, dtype=d).pin_memory() for d in dtypes), words, torch.cuda.Event()))
         self._stage_next = 0
 
@@ -503,14 +575,17 @@ class MultiStreamSegmenter(GraphedWindowState):
         self._ring = tuple(torch.zeros(S, R, dtype=d, device=self.device) for d in dtypes)
         self._ring_host = tuple(torch.zeros(S, R, dtype=d).pin_memory() for d in dtypes)
         self._ring_np = tuple(c.numpy() for c in self._ring_host)
-        self._words = torch.zeros(4, S, dtype=torch.int32, device=self.device)
+        n_words = 5 if self.voxel == 'trilinear' else 4  # (the map words ride behind the four: still one upload)
+        self._words = torch.zeros(n_words, S, dtype=torch.int32, device=self.device)
         self._counts, self._formats = self._words[2], self._words[3]
         self._counts.fill_(hip.INGEST_KEEP)
+        self._words[4:].fill_(hip.RECTIFY_NONE)
         self._acc = torch.zeros(S, self.num_bins, self.height, self.width, dtype=torch.int64, device=self.device)
         self._stage = []
         for _ in range(2):
-            words = torch.zeros(4, S, dtype=torch.int32).pin_memory()
+            words = torch.zeros(n_words, S, dtype=torch.int32).pin_memory()
             words[2].fill_(hip.INGEST_KEEP)
+            words[4:].fill_(hip.RECTIFY_NONE)
             self._stage.append(_RingStage(words, torch.cuda.Event()))
         self._stage_next = 0
 
@@ -573,15 +648,20 @@ class MultiStreamSegmenter(GraphedWindowState):
 
     def _stage_ring(self, slots):
         """slots: per slot (stream, or slot of a compact batch) None or (row, start, count, format) -> the staging set with the four
-        words written; a slot without a window and the slots behind the list: count 0"""
+        words written; a slot without a window and the slots behind the list: count 0.  voxel='trilinear': the map word of the
+        stream whose row the slot names, RECTIFY_NONE in every other slot"""
         st = self._next_stage()
         st.rows_np[:] = np.arange(self.n_streams)
         st.starts_np[:] = 0
         st.counts_np[:] = 0
         st.formats_np[:] = 0
+        if st.maps_np is not None:
+            st.maps_np[:] = hip.RECTIFY_NONE
         for i, w in enumerate(slots):
             if w is not None:
                 st.rows_np[i], st.starts_np[i], st.counts_np[i], st.formats_np[i] = w
+                if st.maps_np is not None:
+                    st.maps_np[i] = self._map_of[w[0]]
         return st
 
     def update_from_feed(self, active=None):
@@ -608,10 +688,18 @@ class MultiStreamSegmenter(GraphedWindowState):
     def _ingest(self, ev, b=None):
         """the round's first launches: the static event buffers (b: their first b slots) -> the grids ev, inside the capture"""
         cut = (lambda v: v) if b is None else (lambda v: v[:b])
+        tri = self.voxel == 'trilinear'
         if self._ring is not None:  # (every row of the rings stays in reach: a slot names its row)
-            hip.event_ingest_ring(*self._ring, *(cut(w) for w in self._words), ev, self._acc)
+            if tri:
+                hip.event_ingest_ring_trilinear(*self._ring, *(cut(w) for w in self._words[:4]), ev, self._maps, cut(self._words[4]), self._acc)
+            else:
+                hip.event_ingest_ring(*self._ring, *(cut(w) for w in self._words), ev, self._acc)
         elif self._columns is not None:
-            hip.event_ingest_columns(*(cut(c) for c in self._columns), cut(self._counts), cut(self._formats), ev, self._acc)
+            if tri:
+                hip.event_ingest_columns_trilinear(*(cut(c) for c in self._columns), cut(self._counts), cut(self._formats), ev, self._maps,
+                                                   cut(self._words[2]), self._acc)
+            else:
+                hip.event_ingest_columns(*(cut(c) for c in self._columns), cut(self._counts), cut(self._formats), ev, self._acc)
         else:
             hip.event_ingest(cut(self._records), cut(self._counts), ev, self._acc)
 
@@ -652,9 +740,10 @@ class MultiStreamSegmenter(GraphedWindowState):
         st.used = tuple(used)
         return st
 
-    def _stage_columns(self, slots):
+    def _stage_columns(self, slots, streams=None):
         """_stage_events for event_layout='columns': slots hold EventColumns or None; per staged slot four copies into the pinned
-        columns (datasets.data_util.stage_event_columns), its count and its format word"""
+        columns (datasets.data_util.stage_event_columns), its count and its format word -- voxel='trilinear': and the map word of the
+        stream in the slot (streams[i]; None: stream i), RECTIFY_NONE in every other slot"""
         from .datasets.data_util import stage_event_columns
         for i, e in enumerate(slots):
             if e is not None and e.n > self.event_capacity:
@@ -662,11 +751,15 @@ class MultiStreamSegmenter(GraphedWindowState):
         st = self._next_stage()
         st.counts_np[:] = 0
         st.formats_np[:] = 0
+        if st.maps_np is not None:
+            st.maps_np[:] = hip.RECTIFY_NONE
         used = []
         for i, e in enumerate(slots):
             if e is not None:
                 st.counts_np[i] = stage_event_columns(e, *(c[i] for c in st.cols_np))
                 st.formats_np[i] = e.format
+                if st.maps_np is not None:
+                    st.maps_np[i] = self._map_of[i if streams is None else streams[i]]
                 used.append((i, e.n))
         st.used = tuple(used)
         return st
@@ -995,12 +1088,15 @@ class MultiStreamSegmenter(GraphedWindowState):
         hip.event_ingest_columns, inside the capture) build the grids: idle streams and padded slots have count 0, an all-zero grid.  The
         labels are a pure function of the events: the ingest's sums do not depend on arrival order."""
         if self._columns is not None:
-            (evs, active), stage = check_stream_columns(events, self.n_streams), self._stage_columns
+            evs, active = check_stream_columns(events, self.n_streams)
         else:
-            (evs, active), stage = check_stream_events(events, self.n_streams), self._stage_events
+            evs, active = check_stream_events(events, self.n_streams)
             evs = [None if e is None else e.detach().cpu().numpy() for e in evs]
         self._check_compute()
         plan = compact_plan(self._pending, active, self.buckets) if self.buckets else None
+        rows = None if plan is None else plan.rows  # (the stream in every slot; None: slot s holds stream s)
+        slots = evs if plan is None else [evs[s] for s in rows]
+        stage = self._stage_columns(slots, rows) if self._columns is not None else self._stage_events(slots)
         if plan is None:
-            return self._ride_along(None, active, stage(evs))
-        return self._update_compact(plan, None, active, True, stage([evs[s] for s in plan.rows]))
+            return self._ride_along(None, active, stage)
+        return self._update_compact(plan, None, active, True, stage)

@@ -452,6 +452,40 @@ int ess_event_ingest_columns(const void* t, const void* x, const void* y, const 
 int ess_event_ingest_ring(const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
                           const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots, int32_t bins,
                           int32_t height, int32_t width, void* acc, size_t acc_bytes, float* out, ess_stream_t stream);
+/* The TRILINEAR flavour of the column and the ring ingest -- PURELY ADDITIVE to ABI 110 (ess_version() is unchanged; no existing
+ * entry point changes): the grid the DSEC loader builds (the raw pixel through the camera's rectify map, then VoxelGrid.convert, the
+ * trilinear flavour above), from the same raw columns, with the same order-independent sum.  The arguments of ess_event_ingest_columns
+ * / ess_event_ingest_ring, and in front of the stream:
+ *   maps (device, 16-byte aligned): fp32 [n_maps][map_height][map_width][2], entry [y][x] = the rectified (x, y) of raw pixel (x, y);
+ *     null iff n_maps == 0.  n_maps >= 0; map_height, map_width in 1..32768: the SENSOR's size, whatever the grid's height and width
+ *     are (a 480-row map over a 440-row grid cuts the bottom 40 rows).
+ *   map_of (device, int32 [n_streams] / [n_slots]), read by the kernel like counts and formats:
+ *     ESS_RECTIFY_NONE (-1): xe = (float)x, ye = (float)y;
+ *     0 .. n_maps - 1: a raw (x, y) outside [0, map_width) x [0, map_height) drops the event, else (xe, ye) = maps[m][y][x];
+ *     any other word: the stream / slot counts as empty (nothing of it is read, an all-zero grid).
+ * Per event, every step in fp32 and without contraction unless said otherwise; first / last = the window's first and last event:
+ *   d = t - t_first in the column's own type (ESS_EVCOL_T_I64: int64 subtraction of the raw words, else fp64), rounded once to fp32;
+ *   u = d / d_last;  tn = ((float)(bins - 1) * (u - u_first)) / (u_last - u_first), u_first and u_last formed the same way.  A window
+ *   whose last time equals its first gives NaN for every event: an all-zero grid (there is no dT = 1 rescue in this flavour);
+ *   the event is dropped unless xe > -2 && xe < width && ye > -2 && ye < height && tn > -2 && tn < bins -- comparisons that NaN fails,
+ *   made in front of every float -> int conversion.  These are exactly the events of which some corner lands in the grid under
+ *   truncation toward zero (a coordinate in (-2, -1] still reaches index 0, with a weight <= 0: VoxelGrid.convert's quirk, kept);
+ *   value = +1 where the polarity byte equals 1, else -1;  x0 = (int)xe, y0 = (int)ye, t0 = (int)tn;  for the up to eight corners
+ *   (xl, yl, tb) in {x0, x0 + 1} x {y0, y0 + 1} x {t0, t0 + 1} inside the grid:  wx = value * (1 - |xl - xe|),
+ *   wxy = wx * (1 - |yl - ye|), c = wxy * (1 - |tb - tn|) -- ess_voxel_grid_trilinear's expressions -- added as llrint(c * 2^40).
+ * |c| <= 1 and an event's corners are distinct voxels: stride / ring <= 2^22 keeps every sum inside int64.  counts, formats, rows,
+ * starts, ESS_INGEST_KEEP, acc and out: as for the temporal flavour.  NOT applied: VoxelGrid(normalize=True)'s own per-grid
+ * normalisation (ess_voxel_normalize mode 0 does it).                                                                              */
+enum { ESS_RECTIFY_NONE = -1 };
+int ess_event_ingest_columns_trilinear(const void* t, const void* x, const void* y, const void* p, const int32_t* counts,
+                                       const int32_t* formats, int64_t stride, int32_t n_streams, int32_t bins, int32_t height,
+                                       int32_t width, void* acc, size_t acc_bytes, float* out, const float* maps, const int32_t* map_of,
+                                       int32_t n_maps, int32_t map_height, int32_t map_width, ess_stream_t stream);
+int ess_event_ingest_ring_trilinear(const void* t, const void* x, const void* y, const void* p, const int32_t* rows,
+                                    const int32_t* starts, const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows,
+                                    int32_t n_slots, int32_t bins, int32_t height, int32_t width, void* acc, size_t acc_bytes, float* out,
+                                    const float* maps, const int32_t* map_of, int32_t n_maps, int32_t map_height, int32_t map_width,
+                                    ess_stream_t stream);
 
 /* ---- image-branch augmentation on the device: the geometric + photometric core of the albumentations
  * pipeline of datasets/cityscapes_loader.py:39-74 (HorizontalFlip, ShiftScaleRotate with rotate 0 and a constant-0 border,

@@ -49,8 +49,15 @@ alternating in the same process, once with windows back to back (stride = window
   ring         MultiStreamSegmenter(event_capacity=N, event_layout='ring').feed of that last packet + update_from_feed(): the earlier
                packets went to the device ring when they arrived, outside the timed region.
 
+--feed --voxel trilinear builds both with voxel='trilinear' and two synthetic rectify maps shared by the streams in turn (a stereo
+rig's), and times two more ways beside them, alternating in the same process:
+
+  ring_temporal  the 'ring' way with voxel='temporal' on the same packets: what the flavour costs a round;
+  host           what the flavour replaces: per stream a numpy lookup of the window's pixels in its map and the loader's fp32 time
+                 normalisation, four float uploads, hip.voxel_grid_trilinear (binned), update(grids).
+
 usage: python tools/bench_seg_stream.py [--compute mixed,bf16 --windows 40 --warmup 8 --reps 3 --recurrent convlstm --streams 1,2,4,8
-                                         [--active 1,2,4,6,8 [--buckets 1,2,4]] | --streams 8 --events 100000 --ingest | --streams 8 --events 100000 --feed]"""
+                                         [--active 1,2,4,6,8 [--buckets 1,2,4]] | --streams 8 --events 100000 --ingest | --streams 8 --events 100000 --feed [--voxel trilinear]]"""
 import argparse
 import json
 import os
@@ -84,9 +91,14 @@ def main():
                                                           'event_capacity=None')
     ap.add_argument('--feed', action='store_true', help="(with --streams) rounds from a continuous packet feed: event_layout='ring' against "
                                                         "'columns'")
+    ap.add_argument('--voxel', default='temporal', choices=('temporal', 'trilinear'),
+                    help="(with --feed) the grid the fed rounds build; 'trilinear': through rectify maps, timed against the temporal feed "
+                         'and against the host alternative as well')
     a = ap.parse_args()
     if a.feed and (not a.streams or a.active or a.ingest):
         ap.error('--feed needs --streams and excludes --active and --ingest')
+    if a.voxel != 'temporal' and not a.feed:
+        ap.error('--voxel belongs to --feed')
     if a.active and not a.streams:
         ap.error('--active needs --streams')
     if a.ingest and (not a.streams or a.active):
@@ -356,6 +368,13 @@ def from_packet_feed(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiS
     packet = max(N // 10, 1)
     out['packet_events'] = packet
     rounds = a.warmup + a.windows
+    tri = a.voxel == 'trilinear'
+    out['voxel'] = a.voxel
+    if tri:  # two smooth distortions of the sensor by a few pixels (some events pushed over the border), as float32 [H, W, 2]
+        out['trilinear_ring_minus_temporal_ring_ms'], out['trilinear_ring_SLOWER_than_temporal_ring'] = {}, {}
+        out['host_minus_trilinear_ring_ms'], out['trilinear_ring_SLOWER_than_host'] = {}, {}
+        yy, xx = np.meshgrid(np.arange(a.height, dtype=np.float64), np.arange(a.width, dtype=np.float64), indexing='ij')
+        rectify = [np.stack([xx + amp * np.sin(yy / 40.0), yy + amp * np.cos(xx / 50.0)], -1).astype(np.float32) for amp in (3.0, -2.0)]
 
     def models():
         torch.manual_seed(6)
@@ -382,11 +401,19 @@ def from_packet_feed(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiS
                 for M in (N, max(N // 4, 1)):
                     shift = 1237  # (stream s reads the sequence from event s * shift on: the streams' windows differ)
                     src = source(N + M * rounds + packet + S * shift)
+                    rig = [rectify[s % 2] for s in range(S)] if tri else None
+                    flavour = dict(voxel='trilinear', rectify_maps=rig) if tri else {}
                     ring = MultiStreamSegmenter(*models(), a.height, a.width, default_options(), S, graph=True, event_capacity=N,
-                                                event_layout='ring', window_events=N, window_stride=M)
+                                                event_layout='ring', window_events=N, window_stride=M, **flavour)
                     cols = MultiStreamSegmenter(*models(), a.height, a.width, default_options(), S, graph=True, event_capacity=N,
-                                                event_layout='columns')
+                                                event_layout='columns', **flavour)
                     ms = {'ring': [], 'columns': []}
+                    if tri:
+                        ring_t = MultiStreamSegmenter(*models(), a.height, a.width, default_options(), S, graph=True, event_capacity=N,
+                                                      event_layout='ring', window_events=N, window_stride=M)
+                        host_seg = MultiStreamSegmenter(*models(), a.height, a.width, default_options(), S, graph=True)
+                        offs = [i * N for i in range(S + 1)]
+                        ms.update(ring_temporal=[], host=[])
                     fed, k = 0, 0
                     while k < rounds:
                         last = fed + packet >= k * M + N  # this packet completes window k of every stream
@@ -394,6 +421,8 @@ def from_packet_feed(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiS
                         if not last:
                             for s in range(S):
                                 ring.feed(s, pk[s])
+                                if tri:
+                                    ring_t.feed(s, pk[s])
                             fed += packet
                             torch.cuda.synchronize()  # (the packet arrived long before the next one: its upload is over)
                             continue
@@ -405,8 +434,25 @@ def from_packet_feed(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiS
 
                         def by_columns():
                             return cols.update_from_events(window)
+
+                        def by_ring_temporal():
+                            for s in range(S):
+                                ring_t.feed(s, pk[s])
+                            return ring_t.update_from_feed()
+
+                        def by_host():
+                            cols4 = [[], [], [], []]
+                            for s, w in enumerate(window):
+                                xy = rig[s][w.y, w.x]
+                                d = (w.t - w.t[0]).astype(np.float32)
+                                for c, v in zip(cols4, (xy[:, 0], xy[:, 1], w.p.astype(np.float32), d / d[-1])):
+                                    c.append(v)
+                            dev4 = [torch.from_numpy(np.concatenate(c)).cuda(non_blocking=True) for c in cols4]
+                            return host_seg.update(hip.voxel_grid_trilinear(*dev4, offs, a.bins, a.height, a.width))
                         res, took = {}, {}
-                        for way, fn in ((('ring', by_ring), ('columns', by_columns))[::1 if k % 2 == 0 else -1]):  # (who goes first alternates)
+                        order = [('ring', by_ring), ('columns', by_columns)] + ([('ring_temporal', by_ring_temporal), ('host', by_host)] if tri else [])
+                        order = order[::1 if k % 2 == 0 else -1]  # (who goes first alternates)
+                        for way, fn in order:
                             torch.cuda.synchronize()
                             t0 = time.perf_counter()
                             res[way] = fn()
@@ -430,6 +476,17 @@ def from_packet_feed(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiS
                     spread = q[int(0.75 * (len(q) - 1))] - q[int(0.25 * (len(q) - 1))]
                     out['columns_minus_ring_ms'][key] = round(diff, 4)
                     out['ring_wins_by_more_than_columns_spread'][key] = bool(diff > spread)
+                    if tri:
+                        spread_r = sorted(ms['ring'])
+                        spread_r = spread_r[int(0.75 * (len(spread_r) - 1))] - spread_r[int(0.25 * (len(spread_r) - 1))]
+                        d_t = statistics.median(ms['ring']) - statistics.median(ms['ring_temporal'])
+                        d_h = statistics.median(ms['host']) - statistics.median(ms['ring'])
+                        out['trilinear_ring_minus_temporal_ring_ms'][key] = round(d_t, 4)
+                        out['trilinear_ring_SLOWER_than_temporal_ring'][key] = bool(d_t > spread_r)
+                        out['host_minus_trilinear_ring_ms'][key] = round(d_h, 4)
+                        out['trilinear_ring_SLOWER_than_host'][key] = bool(-d_h > spread_r)
+                        assert ring_t.n_captures == host_seg.n_captures == 1
+                        del ring_t, host_seg
                     assert ring.n_captures == cols.n_captures == 1
                     del ring, cols, src
                     torch.cuda.empty_cache()

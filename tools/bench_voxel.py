@@ -14,6 +14,10 @@ record kernel on those times); reported with the record row's max - min over the
 hip.event_ingest_ring on the int64 columns laid into rings of twice the stride, the window named by device words: from position 0
 (every group of four aligned and whole, as in the column kernel), from position 3 (head and tail masked) and from a position that
 puts the wrap into the middle of the window; each compared as bits with the column kernel, reported as its difference to it.
+Beside them the TRILINEAR flavour on the same int64 columns, hip.event_ingest_columns_trilinear and hip.event_ingest_ring_trilinear
+(ring: from position 3), through an identity map and through a smooth synthetic distortion map of the sensor -- the ring's bits
+compared with the columns', the identity map's with no map at all -- and hip.voxel_grid_trilinear (binned) on the same events
+rectified and converted to floats on the host beforehand, compared within the fp32 sums' rounding.
 usage: python tools/bench_voxel.py --ingest --slices 8 --events 100000 --bins 5"""
 import argparse
 import json
@@ -144,6 +148,23 @@ def ingest(a):
             'event_ingest_columns_t_f64': lambda: hip.event_ingest_columns(t_f64, cx, cy, cp, counts, fmt_f64, out, acc=acc),
             'event_ingest_finish_only': lambda: hip.event_ingest(records, zero, out, acc=acc)}
     ways.update({f'event_ingest_ring_{k}': ring_way(k) for k in rings})
+    # the trilinear flavour: an identity map and a smooth distortion (a few pixels, some events pushed over the border) of the sensor
+    yy, xx = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing='ij')
+    hmaps = {'identity': np.stack([xx, yy], -1).astype(np.float32),
+             'distorted': np.stack([xx + 3.0 * np.sin(yy / 40.0), yy + 3.0 * np.cos(xx / 50.0)], -1).astype(np.float32)}
+    map0 = torch.zeros(S, dtype=torch.int32, device=dev)
+    rt, rx, ry, rp, starts3 = rings['start3']
+    tri_out = {}
+    for k, m in hmaps.items():
+        dm = torch.from_numpy(m[None]).to(dev)
+        ways[f'event_ingest_columns_trilinear_{k}'] = lambda dm=dm: hip.event_ingest_columns_trilinear(t_i64, cx, cy, cp, counts, fmt_i64, out, dm, map0, acc=acc)
+        ways[f'event_ingest_ring_trilinear_{k}'] = lambda dm=dm: hip.event_ingest_ring_trilinear(rt, rx, ry, rp, rows_w, starts3, counts, fmt_i64, out, dm,
+                                                                                                  map0, acc=acc)
+        # the host alternative's input: the map looked up and the time normalised as the DSEC loader does, floats on the device
+        xy = m[hcols[3][:, :n].astype(np.int64), hcols[2][:, :n].astype(np.int64)]
+        d = (hcols[1][:, :n] - hcols[1][:, :1]).astype(np.float32)
+        fl = [torch.from_numpy(np.ascontiguousarray(v).ravel()).to(dev) for v in (xy[..., 0], xy[..., 1], hcols[4][:, :n].astype(np.float32), d / d[:, -1:])]
+        ways[f'voxel_grid_trilinear_binned_{k}'] = lambda fl=fl: hip.voxel_grid_trilinear(*fl, offs, C, H, W)
     for fn in ways.values():  # warm-up: clocks, allocator
         for _ in range(50):
             fn()
@@ -172,6 +193,16 @@ def ingest(a):
     by_columns = out.clone()
     for k in rings:  # the ring source gives the column kernel's bits, wherever the window starts
         assert torch.equal(ways[f'event_ingest_ring_{k}']().view(torch.int32), by_columns.view(torch.int32)), k
+    # the trilinear flavour: the ring kernel gives the column kernel's bits, the identity map those of no map at all, and both the
+    # grid hip.voxel_grid_trilinear sums in fp32 from the same rectified events
+    for k in hmaps:
+        tri_out[k] = ways[f'event_ingest_columns_trilinear_{k}']().clone()
+        assert torch.equal(ways[f'event_ingest_ring_trilinear_{k}']().view(torch.int32), tri_out[k].view(torch.int32)), k
+        ref = ways[f'voxel_grid_trilinear_binned_{k}']()
+        tri_err = (tri_out[k] - ref).abs().max().item()
+        assert tri_err <= 1e-5 * max(1.0, ref.abs().max().item()) and bool(ref.any()), (k, tri_err)
+    no_map = hip.event_ingest_columns_trilinear(t_i64, cx, cy, cp, counts, fmt_i64, torch.empty_like(out), acc=acc)
+    assert torch.equal(no_map.view(torch.int32), tri_out['identity'].view(torch.int32))
     assert not bool(acc.any())
     med = {k: sorted(v)[1] for k, v in ms.items()}
     spread = max(ms['event_ingest']) - min(ms['event_ingest'])
@@ -181,12 +212,18 @@ def ingest(a):
         'config': {'workload': f'{S} streams x {n} events -> [{S},{C},{H},{W}] fp32', 'reps': a.reps},
         'ms_per_batch': {k: {'median': round(med[k], 5), 'min': round(min(v), 5), 'max': round(max(v), 5)} for k, v in ms.items()},
         'record_spread_ms': round(spread, 5),
-        'columns_minus_records_ms': {k[-5:]: round(med[k] - med['event_ingest'], 5) for k in med if 'columns' in k},
-        'columns_slower_than_records_by_more_than_the_spread': {k[-5:]: bool(med[k] - med['event_ingest'] > spread) for k in med if 'columns' in k},
+        'columns_minus_records_ms': {k[-5:]: round(med[k] - med['event_ingest'], 5) for k in med if 'columns_t_' in k},
+        'columns_slower_than_records_by_more_than_the_spread': {k[-5:]: bool(med[k] - med['event_ingest'] > spread) for k in med if 'columns_t_' in k},
         'ring': {'events_per_row': ring, 'starts': ring_starts,
                  'ring_minus_columns_t_i64_ms': {k: round(med[f'event_ingest_ring_{k}'] - med['event_ingest_columns_t_i64'], 5) for k in rings},
                  'slower_than_columns_by_more_than_the_spread': {k: bool(med[f'event_ingest_ring_{k}'] - med['event_ingest_columns_t_i64'] > spread)
                                                                  for k in rings}},
+        'trilinear': {k: {'columns_over_temporal_columns': round(med[f'event_ingest_columns_trilinear_{k}'] / med['event_ingest_columns_t_i64'], 3),
+                          'ring_over_temporal_ring': round(med[f'event_ingest_ring_trilinear_{k}'] / med['event_ingest_ring_start3'], 3),
+                          'ring_over_voxel_grid_trilinear_binned': round(med[f'event_ingest_ring_trilinear_{k}'] / med[f'voxel_grid_trilinear_binned_{k}'], 3),
+                          'slower_than_temporal_ring': bool(med[f'event_ingest_ring_trilinear_{k}'] - med['event_ingest_ring_start3'] > spread),
+                          'slower_than_voxel_grid_trilinear_binned':
+                              bool(med[f'event_ingest_ring_trilinear_{k}'] - med[f'voxel_grid_trilinear_binned_{k}'] > spread)} for k in hmaps},
         'bytes_per_event': {'records': 16, 'columns': 13},
         'scatter_ms': round(scatter_ms, 5), 'atomics_per_batch': atomics,
         'int64_atomics_per_s': atomics / (scatter_ms * 1e-3) if scatter_ms > 0 else None,
