@@ -168,3 +168,56 @@ class EventWindows:
         if not self._pending:
             raise hip.EssHipError('EventWindows.pop: no window is pending')
         return self._pending.popleft()
+
+
+# ------------------------------------------------------------------------------- sequence rounds (run_sequence_segmentation.py)
+def sequence_windows(end, available_from, T, n_per_window):
+    """The DSEC loader's cut of one validation sample (reference DSEC/dataset/sequence.py:255-279), in absolute event indices: the
+    last T * n_per_window events before `end` (the index get_events_fixed_num's t_end maps to), clamped at available_from (the
+    loader: the start of the file; a ring: its oldest kept event), split into T equal windows.
+        start = max(available_from, end - T * n_per_window);  loaded = end - start;  n = loaded // T
+        window i = [start + i n, start + (i + 1) n);  the loaded - T n events at the END are not used (generate_event_tensor)
+    -> a list of T pairs (start, count), or None where n == 0: no sequence"""
+    end, available_from, T, n_per_window = int(end), int(available_from), int(T), int(n_per_window)
+    if T < 1 or n_per_window < 1 or available_from < 0 or end < available_from:
+        raise hip.EssHipError(f'sequence_windows: end={end} available_from={available_from} T={T} n_per_window={n_per_window}')
+    start = max(available_from, end - T * n_per_window)
+    n = (end - start) // T
+    if n == 0:
+        return None
+    return [(start + i * n, n) for i in range(T)]
+
+
+def ring_end_index(t_ring, head, ring, t_end, need=0):
+    """The absolute index of the first fed event with t >= t_end (head where there is none): the index the reference's
+    get_time_indices_offsets gives get_events_fixed_num (DSEC/utils/eventslicer.py:116, 223-228: time_array[idx_end] >= time_end_us,
+    time_array[idx_end - 1] < time_end_us).  t_ring: the ring's time column on the host, `ring` entries in the stream's own dtype
+    (int64 or float64; entry k mod ring holds event k), head: the events fed so far.  The kept events [max(0, head - ring), head)
+    are at most two sorted segments of t_ring, each searched with np.searchsorted in t's own arithmetic.
+    Refused: a t_end at or before the oldest kept event's time once older events have been overwritten (the index lies, or may lie,
+    among them), and -- need: the events the caller's sequence reads before the index -- an index whose `need` predecessors (as far
+    as the stream has any) are no longer all in the ring."""
+    head, ring, need = int(head), int(ring), int(need)
+    if not isinstance(t_ring, np.ndarray) or t_ring.ndim != 1 or len(t_ring) != ring or t_ring.dtype not in (np.int64, np.float64):
+        raise hip.EssHipError(f'ring_end_index: t_ring must be the ring\'s {ring} times as a 1-D int64 or float64 array')
+    if head < 0 or ring < 1 or need < 0:
+        raise hip.EssHipError(f'ring_end_index: head={head} ring={ring} need={need}')
+    oldest = max(0, head - ring)
+    if isinstance(t_end, (float, np.floating)) and t_end != t_end:
+        raise hip.EssHipError('ring_end_index: t_end is NaN')
+    if t_ring.dtype == np.int64 and int(t_end) != t_end:
+        t_end = int(np.ceil(t_end))  # (integer times: t >= t_end and t >= ceil(t_end) are one condition)
+    t_end = t_ring.dtype.type(t_end)
+    if oldest > 0 and t_end <= t_ring[oldest % ring]:
+        raise hip.EssHipError(f'ring_end_index: t_end={t_end!r} is not after the oldest kept event (index {oldest}, '
+                              f't={t_ring[oldest % ring]!r}): the events before it have been overwritten (ring of {ring})')
+    end = oldest
+    for at, _, m in ring_segments(oldest, head - oldest, ring):
+        k = int(np.searchsorted(t_ring[at:at + m], t_end, side='left'))
+        end += k
+        if k < m:
+            break
+    if max(0, end - need) < oldest:
+        raise hip.EssHipError(f'ring_end_index: the {need} events before index {end} (t_end={t_end!r}) reach back to event '
+                              f'{max(0, end - need)}, the ring of {ring} keeps events from {oldest} on: feed a larger ring_capacity')
+    return end

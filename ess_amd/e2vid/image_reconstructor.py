@@ -76,7 +76,8 @@ class ImageReconstructor:
             out = flat.view(b, 1, h, w)
         return out, states, latent
 
-    def update_reconstruction_sequence(self, event_tensor, T, need_image=True, time_batched_prefix=None, final_lean=False):
+    def update_reconstruction_sequence(self, event_tensor, T, need_image=True, time_batched_prefix=None, final_lean=False,
+                                       slices=None):
         """The trainers' hot loop as one call (reference training/ess_trainer.py:277-280, ess_supervised_trainer.py:128-130):
             for i in range(T): out, states, latent = update_reconstruction(event_tensor[:, i*C:(i+1)*C])
         -> (out, states, latent) of the LAST step (out is None unless need_image).  Same per-slice arithmetic; what changes is the
@@ -85,8 +86,12 @@ class ImageReconstructor:
         to the per-slice path when the preprocessor has hot pixels / flipping or the size needs reflection padding.
         final_lean (the trainers, which reset the state with every batch): the LAST step's recurrent blocks run their lean form too
         (hidden states as BF16_C8 copies only, on the wide-tile gate kernel) -- the returned image and latents are bit-identical,
-        the returned states carry no fp32 hidden tensors (round 5: the non-lean last step cost 1.0 ms of the 23.4 ms step)."""
+        the returned states carry no fp32 hidden tensors (round 5: the non-lean last step cost 1.0 ms of the 23.4 ms step).
+        slices (default None: everything above): the caller's own normalised, padded, contiguous slices [T, B, C, H, W] (the sequence
+        round's, normalised per SAMPLE); event_tensor is then not read and the steps run on slices[i] as they are."""
         from .. import hip
+        if slices is not None:
+            return self._run_slices(slices, T, need_image, final_lean)
         with torch.no_grad():
             events = event_tensor.to(self.device)
             if events.shape[1] % T:
@@ -125,3 +130,22 @@ class ImageReconstructor:
                     if unet is not None:
                         unet.steps_left = None
             return res
+
+    def _run_slices(self, slices, T, need_image, final_lean):
+        """update_reconstruction_sequence's step loop on slices handed over ready: lean steps, the steps_left pair rule, the last
+        step as there"""
+        if slices.dim() != 5 or slices.shape[0] != T or not slices.is_contiguous():
+            raise ValueError(f'update_reconstruction_sequence: slices must be contiguous [T={T}, B, C, H, W], got {tuple(slices.shape)}')
+        unet = getattr(self.model, 'unetrecurrent', None)
+        res = (None, None, None)
+        with torch.no_grad():
+            for i in range(T):
+                last = i == T - 1
+                if unet is not None:
+                    unet.steps_left = T - 1 - i
+                try:
+                    res = self._step(slices[i], need_image and last, not last, final_lean=final_lean and last)
+                finally:
+                    if unet is not None:
+                        unet.steps_left = None
+        return res

@@ -78,7 +78,7 @@ EXPORTS = [
     'ess_to_f16_c8', 'ess_bf16_c8_to_f16_c8', 'ess_f16_c8_to_bf16_c8', 'ess_instnorm_forward_c8_mixed', 'ess_seg_head',
     'ess_event_normalize_samples', 'ess_state_carry_masked', 'ess_state_carry_indexed',
     'ess_event_ingest_workspace', 'ess_event_ingest', 'ess_event_ingest_columns', 'ess_event_ingest_ring',
-    'ess_event_ingest_columns_trilinear', 'ess_event_ingest_ring_trilinear',
+    'ess_event_ingest_columns_trilinear', 'ess_event_ingest_ring_trilinear', 'ess_seg_head_eval',
 ]
 
 
@@ -170,6 +170,7 @@ def lib():
             'ess_upsample_bilinear2x_add_c8': [P, P, P, I, I, I, I, P],
             'ess_upsample_bilinear2x_add_c8_from_c8': [P, P, P, I, I, I, I, P],
             'ess_seg_head': [P, I, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
+            'ess_seg_head_eval': [P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P],
             'ess_event_normalize_samples': [P, P, I, I64, P, P, P],
             'ess_state_carry_masked': [P, P, P, I, I, P, P],
             'ess_state_carry_indexed': [P, P, P, I, I, I, I, P, P, P],
@@ -1184,6 +1185,52 @@ def argmax_confusion(logits, labels=None, conf=None, ignore_index=255, want_pred
 SEG_HEAD_MAX_K = 64
 
 
+def _seg_head_args(who, x, C, weight, bias, out_hw, window, palette):
+    """the argument checks hip.seg_head and hip.seg_head_eval share -> (fmt, weight [K, C], N, K, H, W, (y0, x0, h, w), (Ho, Wo))"""
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise EssHipError(f'{who}: x must be a CUDA(HIP) tensor; there is no CPU path')
+    if x.dim() == 5 and x.shape[-1] == 8 and x.dtype in (torch.bfloat16, torch.float16):
+        fmt = FMT_F16_C8 if (x.dtype == torch.float16 or is_f16_c8(x)) else FMT_BF16_C8
+        N, nb, H, W, _ = x.shape
+        if not 0 < C <= nb * 8:
+            raise EssHipError(f'{who}: C={C} channels do not fit the source\'s {nb} blocks of 8')
+        if nb != (C + 7) // 8:
+            raise EssHipError(f'{who}: C={C} channels need {(C + 7) // 8} blocks of 8, x has {nb}')
+    elif x.dim() == 4 and x.dtype == torch.float32:
+        fmt = FMT_F32_NCHW
+        N, Cx, H, W = x.shape
+        if Cx != C:
+            raise EssHipError(f'{who}: C={C} but x has {Cx} channels')
+    else:
+        raise EssHipError(f'{who}: x must be fp32 NCHW, BF16_C8 or F16_C8, got {x.dtype}{tuple(x.shape)}')
+    if weight.dim() == 4 and weight.shape[2:] == (1, 1):
+        weight = weight.view(weight.shape[0], weight.shape[1])
+    if weight.dim() != 2 or weight.shape[1] != C:
+        raise EssHipError(f'{who}: weight must be [K, C={C}], got {tuple(weight.shape)}')
+    K = weight.shape[0]
+    if not 0 < K <= SEG_HEAD_MAX_K:
+        raise EssHipError(f'{who}: weight has K={K} classes, at most {SEG_HEAD_MAX_K} are supported')
+    if bias is None or tuple(bias.shape) != (K,):
+        raise EssHipError(f'{who}: bias must be [K={K}], got {None if bias is None else tuple(bias.shape)}')
+    if palette is not None and (not torch.is_tensor(palette) or palette.dtype != torch.uint8 or tuple(palette.shape) != (K, 3)):
+        got = f'{palette.dtype}{tuple(palette.shape)}' if torch.is_tensor(palette) else type(palette).__name__
+        raise EssHipError(f'{who}: palette must be a uint8 [K={K}, 3] tensor, got {got}')
+    y0, x0, h, w = (0, 0, H, W) if window is None else (int(v) for v in window)
+    if y0 < 0 or x0 < 0 or h <= 0 or w <= 0 or y0 + h > H or x0 + w > W:
+        raise EssHipError(f'{who}: window {(y0, x0, h, w)} leaves the {H} x {W} source plane')
+    Ho, Wo = (h, w) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+    if Ho <= 0 or Wo <= 0:
+        raise EssHipError(f'{who}: out_hw {(Ho, Wo)} is empty')
+    return fmt, weight, N, K, H, W, (y0, x0, h, w), (Ho, Wo)
+
+
+def _seg_head_outputs(N, Ho, Wo, palette, want_confidence, dev):
+    labels = torch.empty(N, Ho, Wo, dtype=torch.uint8, device=dev)
+    colour = torch.empty(N, Ho, Wo, 3, dtype=torch.uint8, device=dev) if palette is not None else None
+    conf = torch.empty(N, Ho, Wo, dtype=torch.float32, device=dev) if want_confidence else None
+    return labels, colour, conf
+
+
 def seg_head(x, C, weight, bias, out_hw=None, window=None, palette=None, want_confidence=False):
     """Fused class head at inference (ess_seg_head): labels = first argmax_k (bias[k] + sum_c weight[k, c] x[c]) per output pixel,
     without the scores ever being written -> (labels uint8 [N, H_out, W_out], colour uint8 [N, H_out, W_out, 3] or None, confidence
@@ -1195,47 +1242,30 @@ def seg_head(x, C, weight, bias, out_hw=None, window=None, palette=None, want_co
     (default: the window's) -- source pixels by hip.resize_nearest's index rule inside the window, so labels equal
     argmax(resize_nearest(scores)).  palette: uint8 [K, 3] on the device -> colour = palette[labels].  want_confidence: the softmax
     probability of the winning class."""
-    if not torch.is_tensor(x) or not x.is_cuda:
-        raise EssHipError('seg_head: x must be a CUDA(HIP) tensor; there is no CPU path')
-    if x.dim() == 5 and x.shape[-1] == 8 and x.dtype in (torch.bfloat16, torch.float16):
-        fmt = FMT_F16_C8 if (x.dtype == torch.float16 or is_f16_c8(x)) else FMT_BF16_C8
-        N, nb, H, W, _ = x.shape
-        if not 0 < C <= nb * 8:
-            raise EssHipError(f'seg_head: C={C} channels do not fit the source\'s {nb} blocks of 8')
-        if nb != (C + 7) // 8:
-            raise EssHipError(f'seg_head: C={C} channels need {(C + 7) // 8} blocks of 8, x has {nb}')
-    elif x.dim() == 4 and x.dtype == torch.float32:
-        fmt = FMT_F32_NCHW
-        N, Cx, H, W = x.shape
-        if Cx != C:
-            raise EssHipError(f'seg_head: C={C} but x has {Cx} channels')
-    else:
-        raise EssHipError(f'seg_head: x must be fp32 NCHW, BF16_C8 or F16_C8, got {x.dtype}{tuple(x.shape)}')
-    if weight.dim() == 4 and weight.shape[2:] == (1, 1):
-        weight = weight.view(weight.shape[0], weight.shape[1])
-    if weight.dim() != 2 or weight.shape[1] != C:
-        raise EssHipError(f'seg_head: weight must be [K, C={C}], got {tuple(weight.shape)}')
-    K = weight.shape[0]
-    if not 0 < K <= SEG_HEAD_MAX_K:
-        raise EssHipError(f'seg_head: weight has K={K} classes, at most {SEG_HEAD_MAX_K} are supported')
-    if bias is None or tuple(bias.shape) != (K,):
-        raise EssHipError(f'seg_head: bias must be [K={K}], got {None if bias is None else tuple(bias.shape)}')
-    if palette is not None and (not torch.is_tensor(palette) or palette.dtype != torch.uint8 or tuple(palette.shape) != (K, 3)):
-        got = f'{palette.dtype}{tuple(palette.shape)}' if torch.is_tensor(palette) else type(palette).__name__
-        raise EssHipError(f'seg_head: palette must be a uint8 [K={K}, 3] tensor, got {got}')
-    y0, x0, h, w = (0, 0, H, W) if window is None else (int(v) for v in window)
-    if y0 < 0 or x0 < 0 or h <= 0 or w <= 0 or y0 + h > H or x0 + w > W:
-        raise EssHipError(f'seg_head: window {(y0, x0, h, w)} leaves the {H} x {W} source plane')
-    Ho, Wo = (h, w) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
-    if Ho <= 0 or Wo <= 0:
-        raise EssHipError(f'seg_head: out_hw {(Ho, Wo)} is empty')
-    dev = x.device
-    labels = torch.empty(N, Ho, Wo, dtype=torch.uint8, device=dev)
-    colour = torch.empty(N, Ho, Wo, 3, dtype=torch.uint8, device=dev) if palette is not None else None
-    conf = torch.empty(N, Ho, Wo, dtype=torch.float32, device=dev) if want_confidence else None
+    fmt, weight, N, K, H, W, (y0, x0, h, w), (Ho, Wo) = _seg_head_args('seg_head', x, C, weight, bias, out_hw, window, palette)
+    labels, colour, conf = _seg_head_outputs(N, Ho, Wo, palette, want_confidence, x.device)
     _check(lib().ess_seg_head(ptr(x, x.dtype, allow_none=False), fmt, ptr(weight.detach(), allow_none=False), ptr(bias.detach(), allow_none=False),
                               ptr(palette, torch.uint8), ptr(labels, torch.uint8), ptr(colour, torch.uint8), ptr(conf), N, C, K, H, W,
                               y0, x0, h, w, Ho, Wo, stream()), 'ess_seg_head')
+    return labels, colour, conf
+
+
+def seg_head_eval(x, C, weight, bias, gt, confusion, ignore_index=255, out_hw=None, window=None, palette=None, want_confidence=False):
+    """hip.seg_head that scores itself (ess_seg_head_eval): the same (labels, colour, confidence), bit for bit, and per sample
+    confusion[n, gt, label] += 1 over the output pixels with gt != ignore_index and gt < K.  gt: uint8 [N, H_out, W_out]; confusion:
+    int64 [N, K, K], both contiguous on the device; confusion is ADDED to (integer sums: order-independent), never zeroed."""
+    fmt, weight, N, K, H, W, (y0, x0, h, w), (Ho, Wo) = _seg_head_args('seg_head_eval', x, C, weight, bias, out_hw, window, palette)
+    if gt is None or confusion is None:
+        raise EssHipError('seg_head_eval: gt and confusion come together (hip.seg_head is the head without scoring)')
+    for name, t, dtype, shape in (('gt', gt, torch.uint8, (N, Ho, Wo)), ('confusion', confusion, torch.int64, (N, K, K))):
+        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+            got = f'{t.dtype}{tuple(t.shape)}' if torch.is_tensor(t) else type(t).__name__
+            raise EssHipError(f'seg_head_eval: {name} must be a contiguous {dtype} {list(shape)} tensor on the device, got {got}')
+    labels, colour, conf = _seg_head_outputs(N, Ho, Wo, palette, want_confidence, x.device)
+    _check(lib().ess_seg_head_eval(ptr(x, x.dtype, allow_none=False), fmt, ptr(weight.detach(), allow_none=False),
+                                   ptr(bias.detach(), allow_none=False), ptr(palette, torch.uint8), ptr(labels, torch.uint8),
+                                   ptr(colour, torch.uint8), ptr(conf), ptr(gt, torch.uint8), ptr(confusion, torch.int64),
+                                   int(ignore_index), N, C, K, H, W, y0, x0, h, w, Ho, Wo, stream()), 'ess_seg_head_eval')
     return labels, colour, conf
 
 

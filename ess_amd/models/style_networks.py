@@ -160,14 +160,19 @@ class SemSegE2VID(nn.Module):
             x = self.decoder_scale_4[1].forward_fused(x, None, up=True)
         return x
 
-    def predict(self, input_dict, out_hw=None, window=None, palette=None, want_confidence=False):
+    def predict(self, input_dict, out_hw=None, window=None, palette=None, want_confidence=False, gt=None, confusion=None,
+                ignore_index=255):
         """Forward-only labels from latents {1, 2, 4, 8}: forward's layers up to decoder_scale_4, then the fused class head
         (hip.seg_head: 1x1 convolution with decoder_scale_5's weight and bias, nearest resize, first argmax) instead of the logits ->
         (labels uint8 [N, H_out, W_out], colour uint8 [N, H_out, W_out, 3] or None, confidence fp32 [N, H_out, W_out] or None);
         window / out_hw / palette / want_confidence: see hip.seg_head.  Runs under torch.no_grad(), in train or eval mode alike
         (InstanceNorm keeps no running statistics), reads the packed weights forward reads; the head contracts the operands
         forward's last convolution contracts in each configuration (the half copy in 'mixed', the BF16_C8 tensor in 'bf16', fp32
-        otherwise; 'bf16x3' runs it in plain fp32 where forward uses split operands without the lo x lo products)."""
+        otherwise; 'bf16x3' runs it in plain fp32 where forward uses split operands without the lo x lo products).
+        gt (uint8 [N, H_out, W_out]) and confusion (int64 [N, K, K]), both or neither: the head scores itself (hip.seg_head_eval:
+        the same outputs, and confusion[n, gt, label] += 1 over the pixels whose gt is neither ignore_index nor >= K)."""
+        if (gt is None) != (confusion is None):
+            raise hip.EssHipError('SemSegE2VID.predict: gt and confusion come together')
         with torch.no_grad():
             x = self._trunk(input_dict, None, input_dict[1].shape[3])
             c5 = self.decoder_scale_5[0]
@@ -180,6 +185,9 @@ class SemSegE2VID(nn.Module):
                     x = h
             else:
                 C = x.shape[1]
+            if gt is not None:
+                return hip.seg_head_eval(x.contiguous(), C, c5.weight, c5.bias, gt, confusion, ignore_index=ignore_index, out_hw=out_hw, window=window,
+                                         palette=palette, want_confidence=want_confidence)
             return hip.seg_head(x.contiguous(), C, c5.weight, c5.bias, out_hw=out_hw, window=window, palette=palette,
                                 want_confidence=want_confidence)
 

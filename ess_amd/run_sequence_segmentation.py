@@ -1,0 +1,378 @@
+"""
+Sequence rounds: the validation protocol of the DSEC trainers, served from a continuous event feed and scored on the device.
+
+The reference never carries recurrent state across labels.  Its DSEC loader (DSEC/dataset/sequence.py:255-279) takes, for a label
+at time t, the last nr_events_data x nr_events_window events before t (20 x 100 000 in settings_DSEC.yaml), splits them into
+nr_events_data equal chunks and voxelises each; the trainer's validation (training/ess_trainer.py:424-493) resets the encoder's
+state, runs the T chunks from zero, resizes the logits, takes the argmax and adds to a confusion matrix.  MultiStreamSegmenter
+(run_segmentation.py) carries one state for the life of a stream instead, so its labels are not those validation would give on
+the same events, and nothing in it can score itself.
+
+SequenceSegmenter does the protocol: at a label time each stream's last T x N_w fed events are cut as the loader cuts them
+(datasets.event_feed.sequence_windows), voxelised inside the round from the stream's device ring (T x S slots, slot t S + s naming
+row s), normalised per sample, run through T encoder steps from a ZERO state (ImageReconstructor.update_reconstruction_sequence:
+lean steps, the last one final-lean, in 'mixed' the [hi | lo] operand pair only where steps_left says so) and decoded by
+SemSegE2VID.predict with the class head that scores itself (hip.seg_head_eval): labels, colours, confidences and a per-stream
+confusion matrix against the ground truth, all on the device, in one captured graph.
+"""
+import collections
+
+import numpy as np
+import torch
+
+from . import hip
+from .e2vid.image_reconstructor import ImageReconstructor
+from .evaluation.metrics import semseg_accum_confusion_to_acc, semseg_accum_confusion_to_iou
+from .run_segmentation import (VOXEL_FLAVOURS, MultiSegmentationResult, _event_capacity, _models_from_checkpoints, _rectify_maps,
+                               _RingStage)
+
+
+class _SequenceStage(_RingStage):
+    """one pinned staging set of a sequence round: _RingStage's words, [4 or 5, T S], and the ground-truth rows [S, H_out, W_out]"""
+    __slots__ = ('gt', 'gt_np')
+
+    def __init__(self, words, gt, done):
+        super().__init__(words, done)
+        self.gt, self.gt_np = gt, gt.numpy()
+
+
+class _SequenceFeed:
+    """one stream's side of the feed: the events fed so far (absolute index of the next one; position in the ring = index mod R),
+    the last time fed, the dtypes of its first packet with the format word they give, and the uploads out of the pinned mirror
+    still to be waited for -- (the absolute index the packet began at, the event recorded behind its copies), oldest first"""
+    __slots__ = ('head', 'last_t', 'dtypes', 'format', 'uploads')
+
+    def __init__(self):
+        self.head, self.last_t, self.dtypes, self.format, self.uploads = 0, None, None, None, collections.deque()
+
+
+class SequenceSegmenter:
+    """n_streams event streams, one SEQUENCE ROUND at a time: segment_at(t_end=[...]) or segment_at(end=[...]) cuts, per stream, the
+    last sequence_steps x window_events events before the given time (or absolute event index) into sequence_steps equal windows
+    -- the DSEC loader's rule, remainder dropped at the end, fewer events than that: what there is, none: no sequence -- and runs
+    them from a zero recurrent state -> MultiSegmentationResult (valid[s]: a sequence ran; the rows of the other streams are
+    unspecified).  labels=[...]: per stream None or a uint8 [H_out, W_out] ground truth (array or tensor); the round adds
+    confusion[s, gt, label] over the pixels whose gt is neither ignore_index nor >= K.  A stream that is idle or has no label this
+    round has its ground-truth row filled with ignore_index in front of the round, so its row of `confusion` does not move.
+
+    feed(stream, EventColumns): packets of any size as they arrive, through a pinned mirror into the stream's ring of ring_capacity
+    events in device memory (default 2 T N_w, in [T N_w, 2^22], rounded up to a multiple of 16).  No window is pending here and
+    nothing is refused for room: old events are overwritten, and segment_at refuses a sequence that reaches behind the ring.
+    voxel / rectify_maps: as MultiStreamSegmenter(event_layout='ring').  graph=True: the round's device work -- ring ingest over
+    the T S slots, normalisation, T encoder steps, decoder, scoring head -- is captured once (n_captures stays 1); a round is then
+    one upload of the slot words, the ground-truth rows that were given, and one replay.  copy, palette, want_confidence, out_hw:
+    as StreamingSegmenter.  Each stream's results are those it gets alone (n_streams=1) under the two process-wide batch-size
+    switches MultiStreamSegmenter's docstring names.
+
+    confusion: int64 [S, K, K] on the device, accumulated over the rounds; metrics(streams=None) -> {'mean_iou', 'acc', 'cm'} of the
+    summed rows (evaluation.metrics' formulas); reset_metrics(streams=None) zeroes rows; drop_feed(streams=None) forgets rings.
+
+    Memory: the T S grids of a round are static buffers -- fp32 [T S, num_bins, H, W] plus the ingest's int64 sums of the same
+    shape: at T = 20, S = 8, 5 x 440 x 640 about 0.9 GB + 1.8 GB -- and the rings take 13 bytes per event on the device and again in
+    pinned host memory (T = 20, N_w = 100 000, S = 8: 0.42 GB each).
+    Not covered: fixed_duration sequences (delta_t_per_data windows by TIME, the DDD17 loader's rule and the DSEC loader's other
+    branch, sequence.py:224-253); VoxelGrid(normalize=True)'s own per-grid normalisation, as in MultiStreamSegmenter; the loader's
+    optional bilinear resize of the grids."""
+
+    def __init__(self, encoder, decoder, height, width, options, n_streams, sequence_steps=None, window_events=None, ring_capacity=None,
+                 voxel='temporal', rectify_maps=None, graph=False, copy=True, palette=None, want_confidence=False, out_hw=None,
+                 ignore_index=255, device=None):
+        if not isinstance(n_streams, int) or isinstance(n_streams, bool) or n_streams < 1:
+            raise hip.EssHipError(f'n_streams={n_streams!r}: a positive number of streams is needed')
+        T = sequence_steps
+        if not isinstance(T, int) or isinstance(T, bool) or T < 1:
+            raise hip.EssHipError(f'sequence_steps={T!r}: the number of windows of a sequence, a positive int (DSEC: nr_events_data = 20)')
+        if window_events is None:
+            raise hip.EssHipError('window_events is needed: the events per window (DSEC: nr_events_window = 100000)')
+        N_w = _event_capacity(window_events, height, width)
+        if voxel not in VOXEL_FLAVOURS:
+            raise hip.EssHipError(f'voxel={voxel!r}: one of {VOXEL_FLAVOURS}')
+        if not isinstance(ignore_index, int) or isinstance(ignore_index, bool) or not 0 <= ignore_index <= 255:
+            raise hip.EssHipError(f'ignore_index={ignore_index!r}: a value of the uint8 ground truth is needed')
+        R = 2 * T * N_w if ring_capacity is None else ring_capacity
+        if not isinstance(R, int) or isinstance(R, bool) or R < T * N_w or hip.event_column_stride(R) > hip.INGEST_MAX_CAPACITY:
+            raise hip.EssHipError(f'ring_capacity={R!r}: events per stream the ring holds, an int in [sequence_steps * window_events = '
+                                  f'{T * N_w}, {hip.INGEST_MAX_CAPACITY}] (default: twice the lower bound)')
+        self.n_streams, self.sequence_steps, self.window_events = n_streams, T, N_w
+        self.ring_capacity = R = hip.event_column_stride(R)
+        self.voxel, self.ignore_index = voxel, ignore_index
+        self.copy_outputs = bool(copy)
+        self.device = device if device is not None else torch.device('cuda:0')
+        self.model = encoder.to(self.device).eval()
+        self.decoder = decoder.to(self.device).eval()
+        self.rec = ImageReconstructor(self.model, height, width, encoder.num_bins, self.device, options)
+        if self.rec.no_recurrent:
+            raise hip.EssHipError('SequenceSegmenter: options.no_recurrent leaves no sequence to run')
+        if self.rec.event_preprocessor.no_normalize:
+            raise hip.EssHipError('SequenceSegmenter: options.no_normalize is not supported')
+        self.height, self.width, self.num_bins = height, width, encoder.num_bins
+        crop = self.rec.crop
+        self.window = (crop.iy0, crop.ix0, crop.iy1 - crop.iy0, crop.ix1 - crop.ix0)
+        self.out_hw = (height, width) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+        self.palette = None if palette is None else torch.as_tensor(palette).to(self.device).contiguous()
+        self.want_confidence = bool(want_confidence)
+        self.use_graph = graph
+        self.n_rounds = 0
+        self.n_captures = 0
+        self.compute = hip.compute_name()
+        self.num_classes = K = int(self.decoder.decoder_scale_5[0].weight.shape[0])
+        maps, self._map_of = _rectify_maps(rectify_maps, voxel, n_streams)
+        self._maps = None if maps is None else maps.to(self.device)  # (uploaded once, here)
+        S, dev = n_streams, self.device
+        dtypes = (torch.int64, torch.int16, torch.int16, torch.uint8)
+        self._feeds = [_SequenceFeed() for _ in range(S)]
+        self._ring = tuple(torch.zeros(S, R, dtype=d, device=dev) for d in dtypes)
+        self._ring_host = tuple(torch.zeros(S, R, dtype=d).pin_memory() for d in dtypes)
+        self._ring_np = tuple(c.numpy() for c in self._ring_host)
+        n_words = 5 if voxel == 'trilinear' else 4  # (rows, starts, counts, formats; the map words behind them)
+        self._words = torch.zeros(n_words, T * S, dtype=torch.int32, device=dev)
+        self._words[4:].fill_(hip.RECTIFY_NONE)
+        self._in = torch.zeros(T * S, self.num_bins, height, width, dtype=torch.float32, device=dev)
+        self._acc = torch.zeros(T * S, self.num_bins, height, width, dtype=torch.int64, device=dev)
+        self._gt = torch.full((S,) + self.out_hw, ignore_index, dtype=torch.uint8, device=dev)
+        self._gt_live = [False] * S  # (host: the stream's row of _gt holds a ground truth, not the ignore fill)
+        self.confusion = torch.zeros(S, K, K, dtype=torch.int64, device=dev)
+        self._stage = []
+        for _ in range(2):
+            words = torch.zeros(n_words, T * S, dtype=torch.int32).pin_memory()
+            words[4:].fill_(hip.RECTIFY_NONE)
+            self._stage.append(_SequenceStage(words, torch.zeros((S,) + self.out_hw, dtype=torch.uint8).pin_memory(), torch.cuda.Event()))
+        self._stage_next = 0
+        self._g = self._outputs = None
+
+    @classmethod
+    def from_checkpoints(cls, e2vid_path, ess_checkpoint_path, settings_or_kwargs, n_streams, **kw):
+        """as StreamingSegmenter.from_checkpoints, plus the number of streams; sequence_steps, window_events and the rest: keywords"""
+        encoder, decoder, height, width, options, palette = _models_from_checkpoints(e2vid_path, ess_checkpoint_path, settings_or_kwargs)
+        kw.setdefault('palette', palette)
+        return cls(encoder, decoder, height, width, options, n_streams, **kw)
+
+    # ---- the feed
+    def _stream(self, stream, what):
+        if not isinstance(stream, (int, np.integer)) or isinstance(stream, bool) or not 0 <= stream < self.n_streams:
+            raise hip.EssHipError(f'{what}: stream {stream!r} of n_streams={self.n_streams}')
+        return int(stream)
+
+    def feed(self, stream, cols):
+        """A packet of a stream's events as it arrives (datasets.data_util.EventColumns; the times non-decreasing, also from packet to
+        packet) -> the number of events the stream has been fed.  The packet is copied as it is into the pinned mirror at head mod R --
+        at most two segments per column -- and those segments go to the device ring on the current stream, non-blocking; of a packet
+        larger than the ring only its last R events are kept.  Refused before anything is written: another object than an
+        EventColumns, other dtypes than the stream's first packet had (drop_feed forgets them), a packet that goes back in time."""
+        from .datasets.data_util import EventColumns
+        from .datasets.event_feed import copy_into_ring
+        s = self._stream(stream, 'feed')
+        f = self._feeds[s]
+        if not isinstance(cols, EventColumns):
+            raise hip.EssHipError(f'feed: an EventColumns is needed, got {type(cols).__name__}: hand the columns over as they arrive, '
+                                  'EventColumns(t, x, y, p)')
+        if cols.n == 0:
+            return f.head
+        dtypes = (cols.t.dtype, cols.x.dtype)
+        if f.dtypes is not None and dtypes != f.dtypes:
+            raise hip.EssHipError(f'feed: stream {s} delivers t {f.dtypes[0]} and x / y {f.dtypes[1]} since its first packet, this packet has '
+                                  f'{dtypes[0]} and {dtypes[1]}: a ring holds one format (drop_feed([{s}]) starts afresh)')
+        first = cols.t[0].item()
+        if f.last_t is not None and first < f.last_t:
+            raise hip.EssHipError(f'feed: the packet starts at t={first!r}, before the previous packet\'s last time {f.last_t!r}: packets must '
+                                  'be non-decreasing in t')
+        R, head, last = self.ring_capacity, f.head, cols.t[-1].item()
+        if cols.n > R:  # (the ring keeps the last R events anyway)
+            head += cols.n - R
+            cols = EventColumns(cols.t[-R:], cols.x[-R:], cols.y[-R:], cols.p[-R:])
+        f.dtypes, f.format = dtypes, cols.format
+        # the pinned entries about to be rewritten held the events [head - R, head + n - R): the uploads that read them must be over
+        while f.uploads and (f.uploads[0][0] < head + cols.n - R or f.uploads[0][1].query()):
+            f.uploads.popleft()[1].synchronize()
+        for at, _, m in copy_into_ring(cols, tuple(c[s] for c in self._ring_np), head, R):
+            for dev, host in zip(self._ring, self._ring_host):
+                dev[s, at:at + m].copy_(host[s, at:at + m], non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        f.uploads.append((head, done))
+        f.head, f.last_t = head + cols.n, last
+        return f.head
+
+    def fed(self, stream):
+        """the number of events the stream has been fed (the absolute index of its next event)"""
+        return self._feeds[self._stream(stream, 'fed')].head
+
+    def drop_feed(self, streams=None):
+        """these streams (default: all) forget their ring contents and their dtypes: the next packet is event 0 of a new recording.
+        The confusion rows are reset_metrics' business, not this call's."""
+        for s in (range(self.n_streams) if streams is None else streams):
+            s = self._stream(s, 'drop_feed')
+            for _, done in self._feeds[s].uploads:  # (the new recording writes the mirror from entry 0 on)
+                done.synchronize()
+            self._feeds[s] = _SequenceFeed()
+
+    # ---- metrics
+    def _rows(self, streams, what):
+        return list(range(self.n_streams)) if streams is None else [self._stream(s, what) for s in streams]
+
+    def metrics(self, streams=None):
+        """-> {'mean_iou', 'acc', 'iou_per_class', 'cm'} of these streams' (default: all) summed confusion rows: one host read, the
+        formulas of evaluation.metrics (MetricsSemseg.get_metrics_summary's)"""
+        rows = self._rows(streams, 'metrics')
+        cm = self.confusion[rows].sum(dim=0).cpu()
+        mean_iou, per_class = semseg_accum_confusion_to_iou(cm)
+        return {'mean_iou': mean_iou, 'acc': semseg_accum_confusion_to_acc(cm), 'iou_per_class': per_class, 'cm': cm}
+
+    def reset_metrics(self, streams=None):
+        """these streams' (default: all) rows of `confusion` start again from zero"""
+        if streams is None:
+            self.confusion.zero_()
+        else:
+            for s in self._rows(streams, 'reset_metrics'):
+                self.confusion[s].zero_()
+
+    # ---- one round
+    def _round(self):
+        """the device work of one sequence round on the static rings, words and ground truth -> (labels, colour, confidence)"""
+        rec, pre = self.rec, self.rec.event_preprocessor
+        T, S = self.sequence_steps, self.n_streams
+        with torch.no_grad():
+            ev = self._in
+            if self.voxel == 'trilinear':
+                hip.event_ingest_ring_trilinear(*self._ring, *self._words[:4], ev, self._maps, self._words[4], self._acc)
+            else:
+                hip.event_ingest_ring(*self._ring, *self._words, ev, self._acc)
+            for x, y in pre.hot_pixel_locations:
+                ev[:, :, y, x] = 0
+            if pre.flip:
+                ev = torch.flip(ev, dims=[2, 3]).contiguous()
+            ev = rec.crop.pad(hip.event_normalize_samples(ev))  # (per slot: a window's statistics are its own; an idle slot: zeros)
+            if not ev.is_contiguous():
+                ev = ev.contiguous()
+            rec.last_states_for_each_channel = {'grayscale': None}  # every sequence runs from a zero state
+            try:
+                _, _, latent = rec.update_reconstruction_sequence(None, T, need_image=False, final_lean=True,
+                                                                  slices=ev.view(T, S, *ev.shape[1:]))
+            finally:
+                rec.last_states_for_each_channel = {'grayscale': None}
+            return self.decoder.predict(latent, out_hw=self.out_hw, window=self.window, palette=self.palette,
+                                        want_confidence=self.want_confidence, gt=self._gt, confusion=self.confusion,
+                                        ignore_index=self.ignore_index)
+
+    def _capture(self):
+        """one eager run on a side stream, then the recording on the current stream.  The warm-up run must not score: every slot is
+        empty and every ground-truth row holds the ignore fill during it."""
+        self._words[2].zero_()
+        self._gt.fill_(self.ignore_index)
+        self._gt_live = [False] * self.n_streams
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._round()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self._g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._g):
+            self._outputs = self._round()
+        self.n_captures += 1
+
+    def _next_stage(self):
+        """the staging set of this round, free to be rewritten: its last upload has completed"""
+        st = self._stage[self._stage_next]
+        self._stage_next ^= 1
+        st.done.synchronize()
+        return st
+
+    def _check_labels(self, labels):
+        """labels: None or S entries, each None or a uint8 [H_out, W_out] array / tensor -> list of S (None | numpy | device tensor)"""
+        S = self.n_streams
+        if labels is None:
+            return [None] * S
+        if not isinstance(labels, (list, tuple)) or len(labels) != S:
+            n = len(labels) if isinstance(labels, (list, tuple)) else type(labels).__name__
+            raise hip.EssHipError(f'labels must be a list with one entry per stream (a ground truth or None): got {n}, n_streams={S}')
+        out = []
+        for s, g in enumerate(labels):
+            if g is not None:
+                if not (torch.is_tensor(g) or isinstance(g, np.ndarray)):
+                    raise hip.EssHipError(f'labels[{s}] must be a uint8 {list(self.out_hw)} array or tensor or None, got {type(g).__name__}')
+                if g.dtype != (torch.uint8 if torch.is_tensor(g) else np.uint8) or tuple(g.shape) != self.out_hw:
+                    raise hip.EssHipError(f'labels[{s}] must be uint8 {list(self.out_hw)} (the output size), got {g.dtype}{tuple(g.shape)}')
+                if torch.is_tensor(g) and not g.is_cuda:
+                    g = g.numpy()
+            out.append(g)
+        return out
+
+    def _ends(self, t_end, end):
+        """the round's request -> per stream None (idle) or the absolute index its sequence ends in front of"""
+        from .datasets.event_feed import ring_end_index
+        S, R, need = self.n_streams, self.ring_capacity, self.sequence_steps * self.window_events
+        if (t_end is None) == (end is None):
+            raise hip.EssHipError('segment_at: give t_end=[...] (times) or end=[...] (absolute event indices), one of the two')
+        req, what = (t_end, 't_end') if end is None else (end, 'end')
+        if not isinstance(req, (list, tuple)) or len(req) != S:
+            n = len(req) if isinstance(req, (list, tuple)) else type(req).__name__
+            raise hip.EssHipError(f'{what} must be a list with one entry per stream (None: idle): got {n}, n_streams={S}')
+        out = []
+        for s, (v, f) in enumerate(zip(req, self._feeds)):
+            if v is None or f.head == 0:
+                out.append(None)
+            elif end is None:
+                out.append(ring_end_index(self._ring_np[0][s].view(f.dtypes[0]), f.head, R, v, need=need))
+            else:
+                if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= v <= f.head:
+                    raise hip.EssHipError(f'end[{s}]={v!r}: an absolute event index in [0, {f.head}] (the events fed) is needed')
+                if max(0, int(v) - need) < f.head - R:
+                    raise hip.EssHipError(f'end[{s}]={v}: the sequence reaches back to event {max(0, int(v) - need)}, the ring of {R} keeps '
+                                          f'events from {f.head - R} on')
+                out.append(int(v))
+        return out
+
+    def _check_compute(self):
+        if hip.compute_name() != self.compute:
+            raise hip.EssHipError(f"SequenceSegmenter: built in the '{self.compute}' configuration, called in '{hip.compute_name()}'")
+
+    def segment_at(self, t_end=None, end=None, labels=None):
+        """One sequence round.  t_end / end: S entries -- a time (the sequence ends in front of the first event with t >= t_end, as
+        the reference's get_events_fixed_num) / an absolute event index, or None for an idle stream; exactly one of the two lists.
+        labels: None or S entries, each None or the stream's uint8 [H_out, W_out] ground truth.  Everything is checked before
+        anything is written.  -> MultiSegmentationResult"""
+        from .datasets.event_feed import sequence_windows
+        self._check_compute()
+        ends = self._ends(t_end, end)
+        gts = self._check_labels(labels)
+        T, S, R = self.sequence_steps, self.n_streams, self.ring_capacity
+        wins = [None if e is None else sequence_windows(e, 0, T, self.window_events) for e in ends]
+        on = [w is not None for w in wins]
+        if self.use_graph and self._g is None:
+            self._capture()
+        st = self._next_stage()
+        st.rows_np[:] = np.tile(np.arange(S, dtype=np.int32), T)
+        st.starts_np[:] = 0
+        st.counts_np[:] = 0
+        st.formats_np[:] = 0
+        if st.maps_np is not None:
+            st.maps_np[:] = hip.RECTIFY_NONE
+        for s, w in enumerate(wins):
+            if w is not None:
+                for i, (start, count) in enumerate(w):
+                    k = i * S + s
+                    st.starts_np[k], st.counts_np[k], st.formats_np[k] = start % R, count, self._feeds[s].format
+                    if st.maps_np is not None:
+                        st.maps_np[k] = self._map_of[s]
+        self._words.copy_(st.words, non_blocking=True)
+        for s, g in enumerate(gts):
+            if g is not None and on[s]:
+                if torch.is_tensor(g):
+                    self._gt[s].copy_(g, non_blocking=True)
+                else:
+                    np.copyto(st.gt_np[s], g)
+                    self._gt[s].copy_(st.gt[s], non_blocking=True)
+                self._gt_live[s] = True
+            elif self._gt_live[s]:  # (idle, or no label this round: the row must not score)
+                self._gt[s].fill_(self.ignore_index)
+                self._gt_live[s] = False
+        st.done.record()
+        if self.use_graph:
+            self._g.replay()
+            out = self._outputs
+        else:
+            out = self._round()
+        self.n_rounds += 1
+        res = MultiSegmentationResult(*out, valid=on)
+        return res.clone() if (self.use_graph and self.copy_outputs) else res

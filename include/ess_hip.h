@@ -574,6 +574,17 @@ int ess_seg_head(const void* x, int32_t fmt, const float* weight, const float* b
                  uint8_t* colour, float* confidence, int32_t N, int32_t C, int32_t K, int32_t H, int32_t W, int32_t win_y0,
                  int32_t win_x0, int32_t win_h, int32_t win_w, int32_t H_out, int32_t W_out, ess_stream_t stream);
 
+/* The class head that scores itself -- PURELY ADDITIVE to ABI 110: ess_seg_head (the same per-pixel code, so labels, colour and
+ * confidence are its bits) plus, per sample, confusion[n][gt][label] += 1 over the output pixels whose ground truth is neither
+ * ignore_index nor >= K (the rule of ess_label_confusion).  gt: uint8 [N][H_out][W_out]; confusion: int64 [N][K][K], ACCUMULATED
+ * (the caller zeroes it): integer sums, so the result does not depend on the order of the additions.  One grid row per sample, a
+ * K x K histogram in LDS per workgroup, one 64-bit atomic per non-zero cell.  Both gt and confusion are required (ess_seg_head is the
+ * head without them); the K x K x 4 bytes of counts come on top of the weights in the 64 KiB of LDS; N <= 65535.                */
+int ess_seg_head_eval(const void* x, int32_t fmt, const float* weight, const float* bias, const uint8_t* palette, uint8_t* labels,
+                      uint8_t* colour, float* confidence, const uint8_t* gt, int64_t* confusion, int32_t ignore_index, int32_t N,
+                      int32_t C, int32_t K, int32_t H, int32_t W, int32_t win_y0, int32_t win_x0, int32_t win_h, int32_t win_w,
+                      int32_t H_out, int32_t W_out, ess_stream_t stream);
+
 /* confusion-matrix accumulation from GIVEN predictions (evaluation/metrics.py:4-24, semseg_compute_confusion): pred_lbl,
  * labels int64 [total]; conf int64 [K][K] accumulated (conf[label][pred]) over labels != ignore_index.          */
 int ess_label_confusion(const int64_t* pred_lbl, const int64_t* labels, int64_t* conf, int64_t total, int32_t K,

@@ -56,8 +56,21 @@ rig's), and times two more ways beside them, alternating in the same process:
   host           what the flavour replaces: per stream a numpy lookup of the window's pixels in its map and the loader's fp32 time
                  normalisation, four float uploads, hip.voxel_grid_trilinear (binned), update(grids).
 
+--streams S[,S...] --sequence T measures SEQUENCE ROUNDS INSTEAD (the DSEC validation protocol: at a label time the last T windows of
+--events events run from a zero state and are scored against a ground truth): every stream has been fed its T x --events events
+before the clock starts; per round the wall time from the request to synchronised labels and confusion rows, two ways, both
+replayed, alternating in the same process:
+
+  sequence     ess_amd.run_sequence_segmentation.SequenceSegmenter.segment_at(end=, labels=): one upload, one replay;
+  composed     what the older public pieces give: MultiStreamSegmenter(event_layout='ring').reset() + T x update_from_feed(), then
+               hip.label_confusion of every stream's last labels against its ground truth.
+
+and, beside them, the class head alone (device time over 50 launches): hip.seg_head_eval against hip.seg_head followed by S
+hip.label_confusion calls on int64 copies of the labels.  SLOWER is reported wherever that is the result.
+
 usage: python tools/bench_seg_stream.py [--compute mixed,bf16 --windows 40 --warmup 8 --reps 3 --recurrent convlstm --streams 1,2,4,8
-                                         [--active 1,2,4,6,8 [--buckets 1,2,4]] | --streams 8 --events 100000 --ingest | --streams 8 --events 100000 --feed [--voxel trilinear]]"""
+                                         [--active 1,2,4,6,8 [--buckets 1,2,4]] | --streams 8 --events 100000 --ingest | --streams 8 --events 100000 --feed [--voxel trilinear]
+                                         | --streams 8 --events 100000 --sequence 20 --height 440 --windows 6 --warmup 2]"""
 import argparse
 import json
 import os
@@ -94,7 +107,11 @@ def main():
     ap.add_argument('--voxel', default='temporal', choices=('temporal', 'trilinear'),
                     help="(with --feed) the grid the fed rounds build; 'trilinear': through rectify maps, timed against the temporal feed "
                          'and against the host alternative as well')
+    ap.add_argument('--sequence', type=int, default=None, help='(with --streams) sequence rounds of this many windows: SequenceSegmenter '
+                                                               'against reset() + T x update_from_feed() + label_confusion')
     a = ap.parse_args()
+    if a.sequence is not None and (not a.streams or a.active or a.ingest or a.feed or a.sequence < 1):
+        ap.error('--sequence T (T >= 1) needs --streams and excludes --active, --ingest and --feed')
     if a.feed and (not a.streams or a.active or a.ingest):
         ap.error('--feed needs --streams and excludes --active and --ingest')
     if a.voxel != 'temporal' and not a.feed:
@@ -132,6 +149,10 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / a.windows * 1e3
 
+    if a.sequence is not None:
+        sequence_rounds(a, hip, cfg, [w.cpu().numpy() for w in wins], out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, default_options)
+        print(json.dumps(out))
+        return
     if a.feed:
         from_packet_feed(a, hip, cfg, [w.cpu().numpy() for w in wins], out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, default_options)
         print(json.dumps(out))
@@ -490,6 +511,118 @@ def from_packet_feed(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiS
                     assert ring.n_captures == cols.n_captures == 1
                     del ring, cols, src
                     torch.cuda.empty_cache()
+        finally:
+            hip.set_compute('fp32')
+
+
+def sequence_rounds(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, default_options):
+    from ess_amd.datasets.data_util import EventColumns
+    from ess_amd.run_sequence_segmentation import SequenceSegmenter
+    T, N, K = a.sequence, a.events, a.classes
+    out['shape'] = f'S streams of {a.bins}x{a.height}x{a.width} K={K}, sequence rounds of T={T} windows, graph replay'
+    del out['ms_per_window']
+    out['ms_per_round'], out['composed_minus_sequence_ms'], out['sequence_SLOWER_than_composed'] = {}, {}, {}
+    out['head_ms'], out['head_eval_SLOWER_than_head_plus_label_confusion'] = {}, {}
+    rounds = a.warmup + a.windows
+    dev = torch.device('cuda:0')
+
+    def models():
+        torch.manual_seed(6)
+        return E2VIDRecurrent(dict(cfg)), SemSegE2VID(256, K, skip_connect=True, skip_type='concat')
+
+    base = np.concatenate(wins)
+    us = np.round(base[:, 0] * 1e6).astype(np.int64)
+    period = int(us[-1] - us[0]) + 1
+
+    def piece(lo, hi):
+        """events [lo, hi) of the endless sequence made of the four windows over and over, in DSEC's dtypes"""
+        idx = np.arange(lo, hi)
+        r, k = idx // len(us), idx % len(us)
+        return EventColumns(us[k] + r * period, base[k, 1].astype(np.uint16), base[k, 2].astype(np.uint16), base[k, 3].astype(np.uint8))
+
+    for compute in a.compute.split(','):
+        hip.set_compute(compute)
+        try:
+            for S in (int(v) for v in a.streams.split(',')):
+                seq = SequenceSegmenter(*models(), a.height, a.width, default_options(), S, sequence_steps=T, window_events=N, graph=True)
+                R = seq.ring_capacity
+                multi = MultiStreamSegmenter(*models(), a.height, a.width, default_options(), S, graph=True, event_capacity=N,
+                                             event_layout='ring', window_events=N, ring_capacity=R)
+                g = torch.Generator().manual_seed(1)
+                gt = torch.randint(0, K, (S, a.height, a.width), generator=g, dtype=torch.uint8).to(dev)
+                gt64 = gt.long()
+                conf = torch.zeros(S, K, K, dtype=torch.int64, device=dev)
+                shift, ms, fed = 1237, {'sequence': [], 'composed': []}, 0
+                for k in range(rounds):
+                    for s in range(S):  # the T windows of this round arrive: outside the clock, as in a replay farm
+                        for lo in range(fed, fed + T * N, N):
+                            pk = piece(s * shift + lo, s * shift + lo + N)
+                            seq.feed(s, pk)
+                            multi.feed(s, pk)
+                    fed += T * N
+                    torch.cuda.synchronize()
+
+                    def by_sequence():
+                        return seq.segment_at(end=[fed] * S, labels=list(gt)).labels
+
+                    def by_composed():
+                        multi.reset()
+                        for _ in range(T):
+                            res = multi.update_from_feed()
+                        lab = res.labels.long()
+                        for s in range(S):
+                            hip.label_confusion(lab[s], gt64[s], conf[s])
+                        return res.labels
+                    took, res = {}, {}
+                    for way, fn in [('sequence', by_sequence), ('composed', by_composed)][::1 if k % 2 == 0 else -1]:
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        res[way] = fn()
+                        torch.cuda.synchronize()
+                        took[way] = (time.perf_counter() - t0) * 1e3
+                    assert multi.pending(0) == 0
+                    if k >= a.warmup:
+                        for way in ms:
+                            ms[way].append(took[way])
+                key = f'{compute}/S={S}/T={T}'
+                for way, v in ms.items():
+                    out['ms_per_round'][f'{key}/{way}'] = {'median': round(statistics.median(v), 4), 'min': round(min(v), 4), 'max': round(max(v), 4)}
+                q = sorted(ms['composed'])
+                spread = q[-1] - q[0]
+                diff = statistics.median(ms['composed']) - statistics.median(ms['sequence'])
+                out['composed_minus_sequence_ms'][key] = round(diff, 4)
+                out['sequence_SLOWER_than_composed'][key] = bool(diff < 0)
+                out.setdefault('composed_spread_ms', {})[key] = round(spread, 4)
+                assert seq.n_captures == multi.n_captures == 1
+                # the class head alone, on an activation of the decoder's last width in the configuration's operand format
+                C = seq.decoder.decoder_scale_5[0].weight.shape[1]
+                c5 = seq.decoder.decoder_scale_5[0]
+                x = torch.randn(S, C, a.height, a.width, device=dev).relu()
+                x = hip.to_f16_c8(x) if compute == 'mixed' else hip.to_bf16_c8(x) if compute == 'bf16' else x
+                cm = torch.zeros(S, K, K, dtype=torch.int64, device=dev)
+
+                def head_eval():
+                    hip.seg_head_eval(x, C, c5.weight, c5.bias, gt, cm)
+
+                def head_then_confusion():
+                    lab = hip.seg_head(x, C, c5.weight, c5.bias)[0].long()
+                    for s in range(S):
+                        hip.label_confusion(lab[s], gt64[s], conf[s])
+                hm = {}
+                for way, fn in (('seg_head_eval', head_eval), ('seg_head+label_confusion', head_then_confusion)) * 2:
+                    for _ in range(5):
+                        fn()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(50):
+                        fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    hm.setdefault(way, []).append(e0.elapsed_time(e1) / 50)
+                out['head_ms'][f'{compute}/S={S}'] = {way: [round(v, 4) for v in vs] for way, vs in hm.items()}
+                out['head_eval_SLOWER_than_head_plus_label_confusion'][f'{compute}/S={S}'] = bool(min(hm['seg_head_eval']) > min(hm['seg_head+label_confusion']))
+                del seq, multi
+                torch.cuda.empty_cache()
         finally:
             hip.set_compute('fp32')
 
