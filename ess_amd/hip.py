@@ -437,6 +437,12 @@ def _wgrad_call(spec, src0, dy):
     return desc, sdt, ddt, workspace(nbytes, dy.device, 'wgrad')
 
 
+def wgrad_workspace(spec, src0, dy):
+    """The cached buffer a weight-gradient call of `spec` on these tensors takes its split-K slabs (and split-operand copies) from.
+    Every call writes what it reads of it; the tests fill it with NaN bytes before a launch to prove that."""
+    return _wgrad_call(spec, src0, dy)[3]
+
+
 def conv_wgrad(spec, src0, src1, dy, dw, db=None, accumulate=False):
     """dw (+)= the weight gradient of `spec` from the sources and dy (fp32 NCHW or BF16_C8 tensors), db (+)= the bias gradient."""
     desc, sdt, ddt, ws = _wgrad_call(spec, src0, dy)

@@ -10,6 +10,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from wgrad_ref import poison_workspace
+
 pytestmark = pytest.mark.gpu
 
 
@@ -434,7 +436,9 @@ def test_conv_wgrad_c8(H, case):
             assert ((db.cpu() - b.grad).abs().max() / b.grad.abs().max()).item() < 2e-5
         # accumulate form
         dw2 = dw.clone()
-        H.conv_wgrad(spec, c8(H, x0), None if x1 is None else c8(H, x1), c8(H, dy), dw2, None, accumulate=True)
+        x8, dy8 = c8(H, x0), c8(H, dy)
+        poison_workspace(H, spec, x8, dy8)  # (the slabs still hold the first launch's values: NaN bytes instead)
+        H.conv_wgrad(spec, x8, None if x1 is None else c8(H, x1), dy8, dw2, None, accumulate=True)
         assert ((dw2.cpu() - 2 * w.grad).abs().max() / w.grad.abs().max()).item() < 4e-5
     finally:
         H.set_compute('fp32')
@@ -471,6 +475,7 @@ def test_conv_wgrad_sets_c8(H, case):
         if bias:
             assert ((db.cpu() - bsum).abs().max() / bsum.abs().max()).item() < 2e-5
         dw2 = dw.clone()
+        poison_workspace(H, spec, sets[0][0], sets[0][2])  # (the slabs still hold the first launch's values: NaN bytes instead)
         H.conv_wgrad_sets(spec, sets, dw2, None, accumulate=True)
         assert ((dw2.cpu() - 2 * wsum).abs().max() / wsum.abs().max()).item() < 4e-5
         # one set through the same entry == the plain call, bit for bit
