@@ -87,12 +87,21 @@ template <> __device__ __forceinline__ uint2 ess_cvt4<true>(float v0, float v1, 
   h[0] = ess_f16_sat(v0); h[1] = ess_f16_sat(v1); h[2] = ess_f16_sat(v2); h[3] = ess_f16_sat(v3);
   return __builtin_bit_cast(uint2, h);
 }
-// the lo parts of a [hi | lo] half pair: half(v - float(half(v)))  (|v| <= 65504: exact difference, ~22 significant bits in the pair)
+// the lo part of a [hi | lo] half pair: half(clamp(v - float(hi), +-65504)), hi = ess_f16_sat(v).  |v| <= 65504: the difference is exact
+// and at most 16 in magnitude (the clamp is the identity), ~22 significant bits in the pair.  Above it hi is +-65504 and the
+// difference grows with |v|: a plain cast turns it into +-inf from |v| = 131024 on (the pair 65504 + inf: NaN statistics, inf
+// products -- what the saturating hi exists to prevent), so lo saturates as well and the pair holds clamp(v, +-131008) to lo's
+// half rounding.  A NaN v needs no branch: hi keeps it, so hi + lo is NaN whatever the clamp makes of the NaN difference.
+// The clamp is taken on the halves (rounding is monotone and 65504 is a half: half(clamp(d)) == clamp(half(d))), two packed
+// instructions per two elements: a v_med3_f32 on the fp32 difference costs the same by count, but it stands between the subtraction
+// and the conversion, which the compiler otherwise fuses (v_fma_mixlo_f16 / v_fma_mixhi_f16 in the tile epilogues).
 __device__ __forceinline__ uint2 ess_cvt4_lo(float v0, float v1, float v2, float v3) {
   typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
   f16x4 h;
   h[0] = (_Float16)(v0 - (float)ess_f16_sat(v0)); h[1] = (_Float16)(v1 - (float)ess_f16_sat(v1));
   h[2] = (_Float16)(v2 - (float)ess_f16_sat(v2)); h[3] = (_Float16)(v3 - (float)ess_f16_sat(v3));
+  const f16x4 m = {(_Float16)65504.f, (_Float16)65504.f, (_Float16)65504.f, (_Float16)65504.f};
+  h = __builtin_elementwise_min(__builtin_elementwise_max(h, -m), m);
   return __builtin_bit_cast(uint2, h);
 }
 template <> __device__ __forceinline__ void ess_up4<false>(uint2 r, float (&f)[4]) {

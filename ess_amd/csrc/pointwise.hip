@@ -686,7 +686,7 @@ __device__ __forceinline__ _Float16 half_sat(float v) {  // (saturating at +-655
   const float c = __builtin_amdgcn_fmed3f(v, -65504.f, 65504.f);
   return (_Float16)(v != v ? v : c);
 }
-// fp32 NCHW -> F16_C8, or (hilo) the [hi | lo] pair [N][2 nblk][hw][8]: hi = half(v), lo = half(v - hi)
+// fp32 NCHW -> F16_C8, or (hilo) the [hi | lo] pair [N][2 nblk][hw][8]: hi = half(v), lo = half(v - hi), both saturating at +-65504
 __global__ __launch_bounds__(256) void to_f16_c8_kernel(const float* __restrict__ x, uint4* __restrict__ y, int C, int64_t hw,
                                                         int64_t total, int hilo) {
   typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -701,7 +701,8 @@ __global__ __launch_bounds__(256) void to_f16_c8_kernel(const float* __restrict_
     for (int j = 0; j < 8; ++j) {
       const float v = blk * 8 + j < C ? p[(size_t)j * hw] : 0.f;
       h[j] = half_sat(v);
-      l[j] = (_Float16)(v - (float)h[j]);
+      // (lo saturates like hi: above 65504 the difference would cast to +-inf from |v| = 131024 on -- conv_common.h ess_cvt4_lo)
+      l[j] = (_Float16)__builtin_amdgcn_fmed3f(v - (float)h[j], -65504.f, 65504.f);
     }
     if (hilo) {
       y[((size_t)n * 2 * nblk + blk) * hw + pix] = __builtin_bit_cast(uint4, h);

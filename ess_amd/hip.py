@@ -573,8 +573,16 @@ def batchnorm_train_backward_c8(x, C, y, dy, gamma, stats, relu, need_dx=True, n
 
 
 # ------------------------------------------------------------------------------------------ glue
+def _same_shape(what, name, t, shape):
+    """Refuse a second operand / destination of another shape before any pointer is taken: the kernels index it with the first
+    operand's extents, so a smaller one would be read or written past its end."""
+    if t is not None and tuple(t.shape) != tuple(shape):
+        raise EssHipError(f'{what}: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}')
+
+
 def upsample_bilinear2x_add(a, b=None):
     N, C, H, W = a.shape
+    _same_shape('upsample_bilinear2x_add', 'b', b, a.shape)
     y = torch.empty(N, C, 2 * H, 2 * W, dtype=torch.float32, device=a.device)
     _check(lib().ess_upsample_bilinear2x_add(ptr(a), ptr(b), ptr(y), N * C, H, W, stream()), 'ess_upsample_bilinear2x_add')
     return y
@@ -583,6 +591,7 @@ def upsample_bilinear2x_add(a, b=None):
 def upsample_bilinear2x_add_c8(a, b=None):
     """bilinear_x2(a + b) written as a BF16_C8 tensor (the staging form of a following bf16 convolution)."""
     N, C, H, W = a.shape
+    _same_shape('upsample_bilinear2x_add_c8', 'b', b, a.shape)
     y = bf16_c8_empty(N, C, 2 * H, 2 * W, a.device)
     _check(lib().ess_upsample_bilinear2x_add_c8(ptr(a), ptr(b), ptr(y, torch.bfloat16), N, C, H, W, stream()),
            'ess_upsample_bilinear2x_add_c8')
@@ -592,6 +601,7 @@ def upsample_bilinear2x_add_c8(a, b=None):
 def upsample_bilinear2x_add_c8_from_c8(a8, b8=None):
     """bilinear_x2(a + b) from BF16_C8 sources to a BF16_C8 tensor."""
     N, CB, H, W, _ = a8.shape
+    _same_shape('upsample_bilinear2x_add_c8_from_c8', 'b8', b8, a8.shape)
     y = torch.empty(N, CB, 2 * H, 2 * W, 8, dtype=torch.bfloat16, device=a8.device)
     _check(lib().ess_upsample_bilinear2x_add_c8_from_c8(ptr(a8, torch.bfloat16), ptr(b8, torch.bfloat16), ptr(y, torch.bfloat16), N,
                                                         CB * 8, H, W, stream()), 'ess_upsample_bilinear2x_add_c8_from_c8')
@@ -600,6 +610,9 @@ def upsample_bilinear2x_add_c8_from_c8(a8, b8=None):
 
 def sumpool2x2(x, out=None, accumulate=False):
     N, C, H, W = x.shape
+    if H % 2 or W % 2:  # (the kernels stride the input by 2 W_out: an odd W would pool the wrong pixels, an odd H drop a row)
+        raise EssHipError(f'sumpool2x2: input extents {H} x {W} must both be even')
+    _same_shape('sumpool2x2', 'out', out, (N, C, H // 2, W // 2))
     if out is None:
         out = torch.empty(N, C, H // 2, W // 2, dtype=torch.float32, device=x.device)
     _check(lib().ess_sumpool2x2(ptr(x), ptr(out), N * C, H // 2, W // 2, int(accumulate), stream()), 'ess_sumpool2x2')
@@ -607,6 +620,8 @@ def sumpool2x2(x, out=None, accumulate=False):
 
 
 def add(a, b, out=None):
+    _same_shape('add', 'b', b, a.shape)
+    _same_shape('add', 'out', out, a.shape)
     if out is None:
         out = torch.empty_like(a)
     _check(lib().ess_add(ptr(a), ptr(b), ptr(out), a.numel(), stream()), 'ess_add')

@@ -77,7 +77,8 @@ enum { ESS_COMPUTE_FP32 = 0, ESS_COMPUTE_BF16 = 1,
  * kernel reads (x of ess_instnorm_* / ess_batchnorm_train_*_c8 with x_f16 = 1): pre-normalisation tensors keep 11 significant bits. */
 /* ESS_COMPUTE_F16 convolutions read and write F16_C8 tensors throughout.  ESS_FMT_F16_C8_HILO (fmt_out of such a LINEAR convolution; act in
  * {none, relu}, no residual, no out_split, C_out % 64 == 0): the output is [N][2 ceil(C/8)][H][W][8] halfs -- blocks [0, CB) hold
- * hi = half(v), blocks [CB, 2 CB) lo = half(v - hi), ~22 significant bits in the pair.  A consumer reads it as a plain F16_C8 source of 2 C
+ * hi = half(v), blocks [CB, 2 CB) lo = half(v - hi), ~22 significant bits in the pair; both parts saturate at +-65504 (the pair holds
+ * clamp(v, +-131008), never an inf; NaN is kept in hi).  A consumer reads it as a plain F16_C8 source of 2 C
  * channels against a weight whose input columns are repeated ([w | w]): w (hi + lo) on the half matrix cores.  Used where an
  * activation's mean is large against its spread: the encoder convolution in front of a recurrent block, the event latents.   */
 enum { ESS_FMT_F32_NCHW = 0, ESS_FMT_BF16_C8 = 1, ESS_FMT_F16_C8 = 3, ESS_FMT_F16_C8_HILO = 4,
