@@ -16,7 +16,9 @@ __global__ __launch_bounds__(NT) void instnorm_fwd_kernel(const float* __restric
   double s = 0, ss = 0;
   // small planes (<= 3 x 16 bytes per thread): x is read once and stays in registers between the reduction and the map
   constexpr int MAXV = 3;
-  if ((hw & 3) == 0 && hw <= NT * 4 * MAXV && ((((uintptr_t)x) | ((uintptr_t)res) | ((uintptr_t)y)) & 15) == 0) {
+  // 16-byte accesses need planes of whole vectors AND 16-byte aligned tensors (every plane start is then aligned too)
+  const bool vec = (hw & 3) == 0 && ((((uintptr_t)x) | ((uintptr_t)res) | ((uintptr_t)y)) & 15) == 0;
+  if (vec && hw <= NT * 4 * MAXV) {
     f32x4 xv[MAXV];
 #pragma unroll
     for (int k = 0; k < MAXV; ++k) {
@@ -56,7 +58,7 @@ __global__ __launch_bounds__(NT) void instnorm_fwd_kernel(const float* __restric
     }
     return;
   }
-  if ((hw & 3) == 0) {
+  if (vec) {
     for (int i = threadIdx.x * 4; i < hw; i += NT * 4) {
       const f32x4 v = *(const f32x4*)(xp + i);
       s += (double)v[0] + (double)v[1] + (double)v[2] + (double)v[3];
@@ -75,7 +77,7 @@ __global__ __launch_bounds__(NT) void instnorm_fwd_kernel(const float* __restric
   if (threadIdx.x == 0) { stats[2 * blockIdx.x] = mean; stats[2 * blockIdx.x + 1] = rstd; }
   float* yp = y + base;
   const float* rp = res ? res + base : nullptr;
-  if ((hw & 3) == 0) {
+  if (vec) {
     for (int i = threadIdx.x * 4; i < hw; i += NT * 4) {
       f32x4 v = *(const f32x4*)(xp + i);
 #pragma unroll
@@ -162,82 +164,6 @@ __global__ __launch_bounds__(NT) void instnorm_bwd_kernel(const float* __restric
     float g = gp[i];
     if (relu && xh <= 0.f) g = 0.f;
     op[i] = rstd * (g - m1 - xh * m2);
-  }
-}
-
-__global__ __launch_bounds__(NT) void bn_train_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res,
-                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                          float* running_mean, float* running_var, float momentum, float eps,
-                                                          float* __restrict__ y, float* __restrict__ stats, int N, int C,
-                                                          int hw, int relu) {
-  __shared__ double red[16];
-  const int c = blockIdx.x;
-  double s = 0, ss = 0;
-  for (int n = 0; n < N; ++n) {
-    const float* xp = x + ((size_t)n * C + c) * hw;
-    for (int i = threadIdx.x; i < hw; i += NT) { const double v = xp[i]; s += v; ss += v * v; }
-  }
-  s = block_sum_d(s, red);
-  ss = block_sum_d(ss, red);
-  const double cnt = (double)N * hw;
-  const double mean_d = s / cnt;
-  double var = ss / cnt - mean_d * mean_d;
-  if (var < 0) var = 0;
-  const float mean = (float)mean_d, rstd = (float)(1.0 / sqrt(var + (double)eps));
-  if (threadIdx.x == 0) {
-    stats[2 * c] = mean; stats[2 * c + 1] = rstd;
-    if (running_mean) {
-      const double unb = cnt > 1 ? var * cnt / (cnt - 1) : var;
-      running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
-      running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
-    }
-  }
-  const float g = gamma[c], b = beta[c];
-  for (int n = 0; n < N; ++n) {
-    const size_t base = ((size_t)n * C + c) * hw;
-    for (int i = threadIdx.x; i < hw; i += NT) {
-      float t = (x[base + i] - mean) * rstd * g + b;
-      if (res) t += res[base + i];
-      if (relu) t = fmaxf(t, 0.f);
-      y[base + i] = t;
-    }
-  }
-}
-
-__global__ __launch_bounds__(NT) void bn_train_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                          const float* __restrict__ dy, const float* __restrict__ gamma,
-                                                          const float* __restrict__ stats, float* __restrict__ dx,
-                                                          float* __restrict__ dres, float* dgamma, float* dbeta,
-                                                          int accumulate, int N, int C, int hw, int relu) {
-  __shared__ double red[16];
-  const int c = blockIdx.x;
-  const float mean = stats[2 * c], rstd = stats[2 * c + 1];
-  double s1 = 0, s2 = 0;
-  for (int n = 0; n < N; ++n) {
-    const size_t base = ((size_t)n * C + c) * hw;
-    for (int i = threadIdx.x; i < hw; i += NT) {
-      float g = dy[base + i];
-      if (relu && y[base + i] <= 0.f) g = 0.f;
-      s1 += g;
-      s2 += (double)g * ((x[base + i] - mean) * rstd);
-    }
-  }
-  s1 = block_sum_d(s1, red);
-  s2 = block_sum_d(s2, red);
-  if (threadIdx.x == 0) {
-    if (dbeta) dbeta[c] = accumulate ? dbeta[c] + (float)s1 : (float)s1;
-    if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)s2 : (float)s2;
-  }
-  const double cnt = (double)N * hw;
-  const float m1 = (float)(s1 / cnt), m2 = (float)(s2 / cnt), gr = gamma[c] * rstd;
-  for (int n = 0; n < N; ++n) {
-    const size_t base = ((size_t)n * C + c) * hw;
-    for (int i = threadIdx.x; i < hw; i += NT) {
-      float g = dy[base + i];
-      if (relu && y[base + i] <= 0.f) g = 0.f;
-      if (dres) dres[base + i] = g;
-      if (dx) dx[base + i] = gr * (g - m1 - (x[base + i] - mean) * rstd * m2);
-    }
   }
 }
 

@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from norm_ref import _bwd_check, _channels, _check_stats
+
 pytestmark = pytest.mark.gpu
 
 NAN = float('nan')
@@ -425,33 +427,7 @@ def test_conv_gru_f16_edges(H, case):
 
 
 # ---------------------------------------------------------------------------------------------------------------- norm statistics
-def _channels(N, C, Hh, W, g, sd=0.7):
-    """x with channel means of 0, 6, 17 and 30 standard deviations (cycling), a near-constant channel (sigma^2 << eps) and an exactly
-    constant one (the last two channels)"""
-    ratios = torch.tensor([0.0, 6.0, 17.0, 30.0]).repeat((C + 3) // 4)[:C]
-    sign = torch.where(torch.arange(C) % 3 == 1, -1.0, 1.0)
-    x = torch.randn(N, C, Hh, W, generator=g) * sd + (ratios * sd * sign).view(1, C, 1, 1)
-    x[:, C - 2] = 3.0 + 1e-4 * torch.randn(N, Hh, W, generator=g)
-    x[:, C - 1] = 5.0
-    return x
-
-
-def _check_stats(stats, xv, dims, eps, what):
-    """mean and rstd of the kernel against fp64 over the stored values.  rstd: 1e-5 relative at every mean ratio (the bound
-    test_instance_norm_c8 applies to benign data).  mean: the fp32 value of a sum taken in fp32 partials, |dm| <= 2^-20 mean|x| + 1e-7
-    (at most ~16 rounding steps of 2^-24 on a running magnitude <= the sum of |x|)."""
-    m = xv.mean(dims).reshape(-1)
-    var = ((xv - xv.mean(dims, keepdim=True)) ** 2).mean(dims).reshape(-1)
-    rstd = 1.0 / torch.sqrt(var + eps)
-    am = xv.abs().mean(dims).reshape(-1)
-    gm, gr = stats[:, 0].cpu().double(), stats[:, 1].cpu().double()
-    dm = (gm - m).abs()
-    assert (dm <= 2 ** -20 * am + 1e-7).all(), (what, 'mean', dm.max().item(), int((dm > 2 ** -20 * am + 1e-7).sum()))
-    rel = ((gr - rstd) / rstd).abs()
-    assert rel.max().item() < 1e-5, (what, 'rstd', rel.max().item(), int(rel.argmax()))
-    return rel.max().item()
-
-
+# (_channels, _check_stats and _bwd_check live in tests/norm_ref.py, shared with tests/test_hip_norm_edges.py)
 NORM_SHAPES = [
     # N, C, H, W
     (2, 20, 60, 80),      # fused single-plane kernels (4800 pixels), C % 8 != 0
@@ -491,23 +467,6 @@ def test_instance_norm_mixed_statistics(H, shape, x_fmt):
     torch.cuda.synchronize()
     xr = unblock(xs[:, :xs.shape[1] // 2], C).double() if x_fmt == 2 else xv
     _bwd_check(H.from_bf16_c8(dx, C).cpu().double(), xr, dy.to(torch.bfloat16).double(), stats, (2, 3), ('IN mixed bwd', shape, x_fmt))
-
-
-def _bwd_check(got, xr, dyq, stats, dims, what, gamma=None):
-    """dx = g rstd (dy - mean(dy) - xhat mean(dy xhat)) in fp64 from the kernel's (mean, rstd) over the stored x and dy; bound: the bf16
-    rounding of dx (2^-8 |dx|) plus 2^-12 rstd |dy|max per element for the fp32 xhat the kernel forms"""
-    N, C = xr.shape[0], xr.shape[1]
-    shp = (N, C, 1, 1) if dims == (2, 3) else (1, C, 1, 1)
-    m = stats[:, 0].cpu().double().view(shp)
-    r = stats[:, 1].cpu().double().view(shp)
-    xh = (xr - m) * r
-    s1 = dyq.mean(dims, keepdim=True)
-    s2 = (dyq * xh).mean(dims, keepdim=True)
-    gr = r * (gamma.double().view(1, -1, 1, 1) if gamma is not None else 1.0)
-    ref = gr * (dyq - s1 - xh * s2)
-    tol = 2 ** -8 * ref.abs() + 2 ** -12 * gr.abs() * dyq.abs().amax(dims, keepdim=True)
-    assert not torch.isnan(got).any()
-    assert ((got - ref).abs() - tol).max().item() <= 0, (what, (got - ref).abs().max().item())
 
 
 IN_STAT_CASES = [((2, 20, 60, 80), 256), ((2, 20, 60, 80), 512), ((2, 20, 60, 80), 1024),  # fused, each in_small_threads value
