@@ -360,6 +360,268 @@ int launch_finish(const int32_t* counts, int32_t n_streams, int32_t bins, int32_
   return ess_launch_status(what);
 }
 
+// ---- the loader finish (ess_event_grid_finish): what the reference loaders do to a grid between voxelising it and handing it to
+// the network -- normalise it over its non-zero voxels, cut rows, resize bilinearly, cut rows again -- from the int64 sums, so that
+// the grid stays a pure function of the set of events.  Up to four launches, all shaped by the sizes alone:
+//   grid_stats_kernel (when normalising): GRID_STATS_BLOCKS(src_per) workgroups a slot, each leaves {count, sum, sum of squares} of its
+//     share of the slot's non-zero voxels in the workspace.  Count and sum are EXACT: f = (float)acc is an integer-valued float, so it
+//     is summed as an int64 -- sum |f| <= (1 + 2^-24) sum |acc|, and sum |acc| <= 2^22 events x (sum |c| of an event <= 1: the two
+//     temporal halves, the eight trilinear corners) x 2^40 = 2^62: inside int64.  The squares v * v of v = f * 2^-40 are exact in
+//     fp64 (48 bits); their sum is rounded, in an order that the launch shape fixes: a thread's voxels in index order, the wave
+//     butterfly, the waves in order.
+//   grid_stats_finalize_kernel: a slot's partials added IN WORKGROUP ORDER (the scheme of loss.hip's mean losses: plain stores, no
+//     atomic, no memset in front) -> the slot's GridStat: voxel_apply_kernel's (voxel.hip) case analysis and fp32 expressions.
+//   grid_map_kernel: every output voxel reads its <= 4 taps of acc, dequantises and normalises each, blends.  Several outputs read
+//     one sum, so the sums are cleared behind it by grid_clear_kernel -- but for the identity geometry, where each sum has one
+//     reader: grid_identity_kernel maps and clears like event_finish_kernel, and gives its bits where nothing is normalised.
+constexpr int GRID_NORM_NONE = 0, GRID_NORM_UNBIASED = 1, GRID_NORM_POPULATION = 2;  // (ESS_GRID_NORM_* of include/ess_hip.h)
+constexpr int GRID_STATS_MAX_BLOCKS = 64;
+constexpr int GRID_STATS_PER_THREAD = 16;  // voxels a thread of the statistics pass walks before the block cap widens it
+
+struct GridStat {  // 16 bytes a slot, at the head of the workspace
+  float fm, fs;
+  int32_t divide;  // (v - fm) / fs, else v - fm
+  int32_t active;  // 0: the slot has no non-zero voxel (or nothing is normalised): v stays
+};
+
+// workgroups a slot in the statistics pass: from the slot's size alone, so a slot's partials -- and its bits -- are the same
+// however many slots the call has
+int grid_stats_blocks(int64_t src_per) {
+  const int64_t bx = ceil_div64(src_per, (int64_t)INGEST_THREADS * GRID_STATS_PER_THREAD);
+  return (int)(bx > GRID_STATS_MAX_BLOCKS ? GRID_STATS_MAX_BLOCKS : bx);
+}
+
+__device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v, unsigned long long* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) red[w] = v;
+  __syncthreads();
+  unsigned long long t = 0;
+  for (int i = 0; i < INGEST_THREADS / 64; ++i) t += red[i];
+  return t;
+}
+
+// partials: [n_slots][blocks][3] 8-byte words {count, sum of (float)acc as int64, sum of squares as fp64 bits}
+// VEC: src_per is even, so every slot's acc starts 16-byte aligned
+template <bool VEC>
+__global__ __launch_bounds__(INGEST_THREADS) void grid_stats_kernel(const int32_t* __restrict__ counts, int64_t src_per,
+                                                                    const long long* __restrict__ acc,
+                                                                    unsigned long long* __restrict__ partials) {
+  __shared__ double red[16];
+  __shared__ unsigned long long redu[INGEST_THREADS / 64];
+  const int s = blockIdx.y;
+  if (counts[s] < 0) return;  // INGEST_KEEP: no statistics are read for this slot
+  const long long* __restrict__ a = acc + (size_t)s * src_per;
+  unsigned long long n = 0, sum = 0;  // (unsigned: a sum outside the stated bound wraps, it is not undefined)
+  double sq = 0;
+  auto add = [&](long long q) {
+    if (q == 0) return;
+    const float f = (float)q;
+    const double v = (double)(f * INGEST_INV_SCALE);
+    n += 1;
+    sum += (unsigned long long)(long long)f;
+    sq += v * v;
+  };
+  const int64_t stride = (int64_t)gridDim.x * INGEST_THREADS;
+  const int64_t i0 = (int64_t)blockIdx.x * INGEST_THREADS + threadIdx.x;
+  if constexpr (VEC) {
+    const i64x2* __restrict__ a2 = (const i64x2*)a;
+    for (int64_t i = i0; i < (src_per >> 1); i += stride) {
+      const i64x2 q = a2[i];
+      add(q[0]);
+      add(q[1]);
+    }
+  } else {
+    for (int64_t i = i0; i < src_per; i += stride) add(a[i]);
+  }
+  n = block_sum_u64(n, redu);
+  sum = block_sum_u64(sum, redu);
+  sq = block_sum_d(sq, red);
+  if (threadIdx.x == 0) {
+    unsigned long long* __restrict__ w = partials + ((size_t)s * gridDim.x + blockIdx.x) * 3;
+    w[0] = n;
+    w[1] = sum;
+    w[2] = (unsigned long long)__double_as_longlong(sq);
+  }
+}
+
+// one thread a slot: the partials in workgroup order -> GridStat.  The expressions below are voxel_apply_kernel's, on exact n and sum,
+// evaluated WITHOUT fused multiply-add: a slot whose non-zero voxels are all equal (one voxel, say) then has E[v^2] and mean^2 rounded
+// alike and a population std of exactly 0, as the loader's own fp32 arithmetic gives it -- not the rounding residual of v^2.
+__global__ __launch_bounds__(64) void grid_stats_finalize_kernel(const int32_t* __restrict__ counts, int n_slots, int blocks, int mode,
+                                                                 const unsigned long long* __restrict__ partials,
+                                                                 GridStat* __restrict__ stats) {
+#pragma clang fp contract(off)
+  const int s = blockIdx.x * 64 + threadIdx.x;
+  if (s >= n_slots || counts[s] < 0) return;
+  unsigned long long cnt = 0, isum = 0;
+  double sq = 0;
+  for (int b = 0; b < blocks; ++b) {
+    const unsigned long long* __restrict__ w = partials + ((size_t)s * blocks + b) * 3;
+    cnt += w[0];
+    isum += w[1];
+    sq += __longlong_as_double((long long)w[2]);
+  }
+  GridStat r = {0.f, 1.f, 0, 0};
+  if (cnt > 0) {
+    const double n = (double)cnt;
+    const double mean = ((double)(long long)isum * 0x1p-40) / n;
+    float fm, fs;
+    bool divide = true;
+    if (mode == GRID_NORM_UNBIASED) {
+      // torch.std(): sqrt(sum((v-mean)^2) / (n-1)); one non-zero voxel -> NaN -> "std > 0" is false -> subtract only
+      const double var = n > 1 ? (sq - n * mean * mean) / (n - 1) : -1.0;
+      const double sd = var > 0 ? sqrt(var) : 0.0;
+      divide = sd > 0;
+      fm = (float)mean;
+      fs = (float)sd;
+    } else {
+      fm = (float)mean;
+      fs = sqrtf((float)(sq / n) - fm * fm);
+    }
+    r = GridStat{fm, fs, divide ? 1 : 0, 1};
+  }
+  stats[s] = r;
+}
+
+// one tap: the dequantised sum, normalised where it is not zero
+__device__ __forceinline__ float grid_tap(long long q, const GridStat st) {
+#pragma clang fp contract(off)
+  const float v = dequantise(q);
+  if (st.active == 0 || v == 0.f) return v;
+  return st.divide ? (v - st.fm) / st.fs : v - st.fm;
+}
+
+struct GridGeometry {
+  int bins, src_h, src_w;  // the slot's sums
+  int in_h;                // rows [0, in_h) of them enter the resize
+  int rh, rw;              // the resized grid
+  int out_rows;            // rows [0, out_rows) of it are stored
+  float scale_y, scale_x;  // (in - 1) / (out - 1), 0 where out == 1: fp32 divisions, as torch's area_pixel_compute_scale
+};
+
+// torch's align_corners=True source index and weights of output index d (fp32, no contraction); i0 is clamped into the source
+// (the product can exceed in - 1 by an ulp, never by one: the clamp changes no value, it only bounds the index)
+__device__ __forceinline__ void grid_source(float scale, int d, int in, int& i0, int& i1, float& l0, float& l1) {
+#pragma clang fp contract(off)
+  const float src = scale * (float)d;
+  i0 = (int)src;
+  if (i0 > in - 1) i0 = in - 1;
+  i1 = i0 + (i0 < in - 1 ? 1 : 0);
+  l1 = src - (float)i0;
+  l0 = 1.f - l1;
+}
+
+// VEC: rw is a multiple of 4, so every row of out starts 16-byte aligned and a thread stores four neighbours at once
+template <bool VEC>
+__global__ __launch_bounds__(INGEST_THREADS) void grid_map_kernel(const int32_t* __restrict__ counts, const GridGeometry g,
+                                                                  const long long* __restrict__ acc, const GridStat* __restrict__ stats,
+                                                                  float* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int s = blockIdx.y;
+  if (counts[s] < 0) return;  // INGEST_KEEP
+  const GridStat st = stats != nullptr ? stats[s] : GridStat{0.f, 1.f, 0, 0};
+  const size_t src_plane = (size_t)g.src_h * g.src_w;
+  const long long* __restrict__ a = acc + (size_t)s * g.bins * src_plane;
+  float* __restrict__ o = out + (size_t)s * g.bins * g.out_rows * g.rw;
+  constexpr int PER = VEC ? 4 : 1;
+  const int64_t row_items = g.rw / PER;
+  const int64_t items = (int64_t)g.bins * g.out_rows * row_items;
+  for (int64_t i = (int64_t)blockIdx.x * INGEST_THREADS + threadIdx.x; i < items; i += (int64_t)gridDim.x * INGEST_THREADS) {
+    const int xq = (int)(i % row_items);
+    const int64_t br = i / row_items;  // bin * out_rows + row
+    const int oy = (int)(br % g.out_rows), b = (int)(br / g.out_rows);
+    int y0, y1;
+    float ly0, ly1;
+    grid_source(g.scale_y, oy, g.in_h, y0, y1, ly0, ly1);
+    const long long* __restrict__ r0 = a + (size_t)b * src_plane + (size_t)y0 * g.src_w;
+    const long long* __restrict__ r1 = a + (size_t)b * src_plane + (size_t)y1 * g.src_w;
+    float v[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      int x0, x1;
+      float lx0, lx1;
+      grid_source(g.scale_x, xq * PER + j, g.src_w, x0, x1, lx0, lx1);
+      const float v00 = grid_tap(r0[x0], st), v01 = grid_tap(r0[x1], st), v10 = grid_tap(r1[x0], st), v11 = grid_tap(r1[x1], st);
+      v[j] = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
+    }
+    if constexpr (VEC) {
+      f32x4 w;
+      w[0] = v[0]; w[1] = v[1]; w[2] = v[2]; w[3] = v[3];
+      ((f32x4*)o)[i] = w;  // (item i of the slot is its i-th group of four floats)
+    } else {
+      o[i] = v[0];
+    }
+  }
+}
+
+// zeros where a sum was; VEC: src_per is even
+template <bool VEC>
+__global__ __launch_bounds__(INGEST_THREADS) void grid_clear_kernel(const int32_t* __restrict__ counts, int64_t src_per,
+                                                                    long long* __restrict__ acc) {
+  const int s = blockIdx.y;
+  if (counts[s] < 0) return;  // INGEST_KEEP: acc of this slot is zero and stays so
+  long long* __restrict__ a = acc + (size_t)s * src_per;
+  const int64_t stride = (int64_t)gridDim.x * INGEST_THREADS;
+  const int64_t i0 = (int64_t)blockIdx.x * INGEST_THREADS + threadIdx.x;
+  if constexpr (VEC) {
+    i64x2* __restrict__ a2 = (i64x2*)a;
+    const i64x2 z = {0, 0};
+    for (int64_t i = i0; i < (src_per >> 1); i += stride) {
+      const i64x2 q = a2[i];
+      if ((q[0] | q[1]) != 0) a2[i] = z;
+    }
+  } else {
+    for (int64_t i = i0; i < src_per; i += stride)
+      if (a[i] != 0) a[i] = 0;
+  }
+}
+
+// the identity geometry: event_finish_kernel with a tap in place of the plain dequantisation (the same bits where st.active == 0)
+template <bool VEC>
+__global__ __launch_bounds__(INGEST_THREADS) void grid_identity_kernel(const int32_t* __restrict__ counts, int64_t per_stream,
+                                                                       long long* __restrict__ acc, const GridStat* __restrict__ stats,
+                                                                       float* __restrict__ out) {
+  const int s = blockIdx.y;
+  if (counts[s] < 0) return;  // INGEST_KEEP
+  const GridStat st = stats != nullptr ? stats[s] : GridStat{0.f, 1.f, 0, 0};
+  long long* __restrict__ a = acc + (size_t)s * per_stream;
+  float* __restrict__ o = out + (size_t)s * per_stream;
+  const int64_t stride = (int64_t)gridDim.x * INGEST_THREADS;
+  const int64_t i0 = (int64_t)blockIdx.x * INGEST_THREADS + threadIdx.x;
+  if constexpr (VEC) {
+    i64x2* __restrict__ a2 = (i64x2*)a;
+    f32x4* __restrict__ o4 = (f32x4*)o;
+    const i64x2 z = {0, 0};
+    for (int64_t i = i0; i < (per_stream >> 2); i += stride) {
+      const i64x2 lo = a2[2 * i], hi = a2[2 * i + 1];
+      f32x4 v;
+      v[0] = grid_tap(lo[0], st); v[1] = grid_tap(lo[1], st); v[2] = grid_tap(hi[0], st); v[3] = grid_tap(hi[1], st);
+      o4[i] = v;
+      if ((lo[0] | lo[1]) != 0) a2[2 * i] = z;
+      if ((hi[0] | hi[1]) != 0) a2[2 * i + 1] = z;
+    }
+  } else {
+    for (int64_t i = i0; i < per_stream; i += stride) {
+      const long long q = a[i];
+      o[i] = grid_tap(q, st);
+      if (q != 0) a[i] = 0;
+    }
+  }
+}
+
+// the grid of a pass over `items` items a slot, INGEST_QUADS_PER_THREAD a thread before the block cap widens it
+dim3 grid_pass(int64_t items, int32_t n_slots) {
+  int64_t bx = ceil_div64(items, (int64_t)INGEST_THREADS * INGEST_QUADS_PER_THREAD);
+  if (bx > INGEST_MAX_BLOCKS_X) bx = INGEST_MAX_BLOCKS_X;
+  return dim3((unsigned)bx, (unsigned)n_slots);
+}
+
+// torch's area_pixel_compute_scale<float>(in, out, align_corners=true)
+float grid_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
+
 
 // the argument checks of the two column sources, shared by their flavours; `what` names the entry point in every message
 int check_columns(const char* what, const void* t, const void* x, const void* y, const void* p, const int32_t* counts,
@@ -384,9 +646,10 @@ int check_columns(const char* what, const void* t, const void* x, const void* y,
 
 int check_ring(const char* what, const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
                const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots, int32_t bins, int32_t height,
-               int32_t width, const void* acc, size_t acc_bytes, const float* out) {
-  ESS_CHECK_ARG(t && x && y && p && rows && starts && counts && formats && acc && out,
-                "%s: null t, x, y, p, rows, starts, counts, formats, acc or out", what);
+               int32_t width, const void* acc, size_t acc_bytes, const float* out, bool with_out = true) {
+  // (with_out false: the scatter-only entry points, which have no out)
+  ESS_CHECK_ARG(t && x && y && p && rows && starts && counts && formats && acc && (out || !with_out),
+                "%s: null t, x, y, p, rows, starts, counts, formats%s", what, with_out ? ", acc or out" : " or acc");
   ESS_CHECK_ARG(n_slots >= 1 && n_slots <= 65535, "%s: n_slots=%d (1..65535)", what, (int)n_slots);
   ESS_CHECK_ARG(n_rows >= 1, "%s: n_rows=%d must be positive", what, (int)n_rows);
   ESS_CHECK_ARG(bins > 0 && height > 0 && width > 0, "%s: bins=%d height=%d width=%d must be positive", what, (int)bins, (int)height,
@@ -401,7 +664,7 @@ int check_ring(const char* what, const void* t, const void* x, const void* y, co
   const size_t need = ess_event_ingest_workspace(n_slots, bins, height, width);
   ESS_CHECK_ARG(acc_bytes >= need, "%s: acc has %zu bytes, %zu are needed", what, acc_bytes, need);
   ESS_CHECK_ARG(((((uintptr_t)t) | ((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)p) | ((uintptr_t)acc) | ((uintptr_t)out)) & 15) == 0,
-                "%s: t, x, y, p, acc and out must be 16-byte aligned", what);
+                "%s: t, x, y, p, acc%s must be 16-byte aligned", what, with_out ? " and out" : "");
   return ESS_OK;
 }
 
@@ -516,4 +779,117 @@ extern "C" int ess_event_ingest_ring_trilinear(const void* t, const void* x, con
   rc = ess_launch_status("event_ingest_ring_trilinear(scatter)");
   if (rc) return rc;
   return launch_finish(counts, n_slots, bins, height, width, acc, out, st, "event_ingest_ring_trilinear(finish)");
+}
+
+// ---- the ring ingest in two halves: scatter alone (acc keeps the sums), and the loader finish that turns sums into the loader's grid
+extern "C" int ess_event_scatter_ring(const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
+                                      const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots,
+                                      int32_t bins, int32_t height, int32_t width, void* acc, size_t acc_bytes, ess_stream_t stream) {
+  int rc = check_ring("event_scatter_ring", t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, bins, height, width, acc,
+                      acc_bytes, nullptr, false);
+  if (rc) return rc;
+  hipLaunchKernelGGL((event_scatter_ring_kernel<TemporalFlavour>), dim3(scatter_blocks(ring), (unsigned)n_slots), dim3(INGEST_THREADS), 0,
+                     (hipStream_t)stream, (const long long*)t, (const unsigned short*)x, (const unsigned short*)y,
+                     (const unsigned char*)p, rows, starts, counts, formats, ring, n_rows, bins, height, width, (long long*)acc);
+  return ess_launch_status("event_scatter_ring");
+}
+
+extern "C" int ess_event_scatter_ring_trilinear(const void* t, const void* x, const void* y, const void* p, const int32_t* rows,
+                                                const int32_t* starts, const int32_t* counts, const int32_t* formats, int64_t ring,
+                                                int32_t n_rows, int32_t n_slots, int32_t bins, int32_t height, int32_t width, void* acc,
+                                                size_t acc_bytes, const float* maps, const int32_t* map_of, int32_t n_maps,
+                                                int32_t map_height, int32_t map_width, ess_stream_t stream) {
+  const char* what = "event_scatter_ring_trilinear";
+  int rc = check_ring(what, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, bins, height, width, acc, acc_bytes, nullptr,
+                      false);
+  if (rc) return rc;
+  Rectify rect;
+  rc = check_rectify(what, maps, map_of, n_maps, map_height, map_width, rect);
+  if (rc) return rc;
+  hipLaunchKernelGGL((event_scatter_ring_kernel<TrilinearFlavour, Rectify>), dim3(scatter_blocks(ring), (unsigned)n_slots),
+                     dim3(INGEST_THREADS), 0, (hipStream_t)stream, (const long long*)t, (const unsigned short*)x,
+                     (const unsigned short*)y, (const unsigned char*)p, rows, starts, counts, formats, ring, n_rows, bins, height, width,
+                     (long long*)acc, rect);
+  return ess_launch_status(what);
+}
+
+// workspace: [n_slots] GridStat, then [n_slots][grid_stats_blocks][3] 8-byte partials
+extern "C" size_t ess_event_grid_finish_workspace(int32_t n_slots, int32_t bins, int32_t src_height, int32_t src_width) {
+  if (n_slots <= 0 || bins <= 0 || src_height <= 0 || src_width <= 0) return 0;
+  const int64_t src_per = (int64_t)bins * src_height * src_width;
+  return (size_t)n_slots * (sizeof(GridStat) + (size_t)grid_stats_blocks(src_per) * 3 * sizeof(unsigned long long));
+}
+
+extern "C" int ess_event_grid_finish(const int32_t* counts, int32_t n_slots, int32_t bins, int32_t src_height, int32_t src_width, void* acc,
+                                     size_t acc_bytes, int32_t crop_rows, int32_t resize_height, int32_t resize_width, int32_t out_rows,
+                                     int32_t normalize, float* out, void* workspace, size_t workspace_bytes, ess_stream_t stream) {
+  ESS_CHECK_ARG(counts && acc && out && workspace, "event_grid_finish: null counts, acc, out or workspace");
+  ESS_CHECK_ARG(n_slots >= 1 && n_slots <= 65535, "event_grid_finish: n_slots=%d (1..65535)", (int)n_slots);
+  ESS_CHECK_ARG(bins > 0 && src_height > 0 && src_width > 0, "event_grid_finish: bins=%d src_height=%d src_width=%d must be positive",
+                (int)bins, (int)src_height, (int)src_width);
+  ESS_CHECK_ARG(resize_height > 0 && resize_width > 0, "event_grid_finish: resize_height=%d resize_width=%d must be positive",
+                (int)resize_height, (int)resize_width);
+  ESS_CHECK_ARG(crop_rows >= 1 && crop_rows <= src_height, "event_grid_finish: crop_rows=%d (1..src_height=%d)", (int)crop_rows,
+                (int)src_height);
+  ESS_CHECK_ARG(out_rows >= 1 && out_rows <= resize_height, "event_grid_finish: out_rows=%d (1..resize_height=%d)", (int)out_rows,
+                (int)resize_height);
+  ESS_CHECK_ARG(normalize == GRID_NORM_NONE || normalize == GRID_NORM_UNBIASED || normalize == GRID_NORM_POPULATION,
+                "event_grid_finish: normalize=%d (0 none, 1 unbiased, 2 population)", (int)normalize);
+  const size_t need = ess_event_ingest_workspace(n_slots, bins, src_height, src_width);
+  ESS_CHECK_ARG(acc_bytes >= need, "event_grid_finish: acc has %zu bytes, %zu are needed", acc_bytes, need);
+  const size_t ws_need = ess_event_grid_finish_workspace(n_slots, bins, src_height, src_width);
+  ESS_CHECK_ARG(workspace_bytes >= ws_need, "event_grid_finish: workspace has %zu bytes, %zu are needed", workspace_bytes, ws_need);
+  ESS_CHECK_ARG(((((uintptr_t)acc) | ((uintptr_t)out) | ((uintptr_t)workspace)) & 15) == 0,
+                "event_grid_finish: acc, out and workspace must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t src_per = (int64_t)bins * src_height * src_width;
+  GridStat* stats = nullptr;
+  int rc;
+  if (normalize != GRID_NORM_NONE) {
+    stats = (GridStat*)workspace;
+    unsigned long long* partials = (unsigned long long*)(stats + n_slots);
+    const int blocks = grid_stats_blocks(src_per);
+    const dim3 sgrid((unsigned)blocks, (unsigned)n_slots);
+    if ((src_per & 1) == 0)
+      hipLaunchKernelGGL(grid_stats_kernel<true>, sgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (const long long*)acc, partials);
+    else
+      hipLaunchKernelGGL(grid_stats_kernel<false>, sgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (const long long*)acc, partials);
+    rc = ess_launch_status("event_grid_finish(statistics)");
+    if (rc) return rc;
+    hipLaunchKernelGGL(grid_stats_finalize_kernel, dim3((unsigned)ceil_div(n_slots, 64)), dim3(64), 0, st, counts, (int)n_slots, blocks,
+                       (int)normalize, (const unsigned long long*)partials, stats);
+    rc = ess_launch_status("event_grid_finish(finalize)");
+    if (rc) return rc;
+  }
+  if (crop_rows == src_height && resize_height == src_height && out_rows == src_height && resize_width == src_width) {
+    // each sum has one reader: map and clear in one kernel
+    const bool vec = (src_per & 3) == 0;
+    const dim3 grid = grid_pass(vec ? src_per >> 2 : src_per, n_slots);
+    if (vec)
+      hipLaunchKernelGGL(grid_identity_kernel<true>, grid, dim3(INGEST_THREADS), 0, st, counts, src_per, (long long*)acc,
+                         (const GridStat*)stats, out);
+    else
+      hipLaunchKernelGGL(grid_identity_kernel<false>, grid, dim3(INGEST_THREADS), 0, st, counts, src_per, (long long*)acc,
+                         (const GridStat*)stats, out);
+    return ess_launch_status("event_grid_finish(identity)");
+  }
+  const GridGeometry g = {bins,         src_height, src_width, crop_rows, resize_height, resize_width, out_rows,
+                          grid_scale(crop_rows, resize_height), grid_scale(src_width, resize_width)};
+  const bool vec = (resize_width & 3) == 0;
+  const int64_t items = (int64_t)bins * out_rows * (vec ? resize_width >> 2 : resize_width);
+  if (vec)
+    hipLaunchKernelGGL(grid_map_kernel<true>, grid_pass(items, n_slots), dim3(INGEST_THREADS), 0, st, counts, g, (const long long*)acc,
+                       (const GridStat*)stats, out);
+  else
+    hipLaunchKernelGGL(grid_map_kernel<false>, grid_pass(items, n_slots), dim3(INGEST_THREADS), 0, st, counts, g, (const long long*)acc,
+                       (const GridStat*)stats, out);
+  rc = ess_launch_status("event_grid_finish(map)");
+  if (rc) return rc;
+  const bool cvec = (src_per & 1) == 0;
+  const dim3 cgrid = grid_pass(cvec ? src_per >> 1 : src_per, n_slots);
+  if (cvec)
+    hipLaunchKernelGGL(grid_clear_kernel<true>, cgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (long long*)acc);
+  else
+    hipLaunchKernelGGL(grid_clear_kernel<false>, cgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (long long*)acc);
+  return ess_launch_status("event_grid_finish(clear)");
 }

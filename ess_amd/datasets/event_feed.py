@@ -221,3 +221,71 @@ def ring_end_index(t_ring, head, ring, t_end, need=0):
         raise hip.EssHipError(f'ring_end_index: the {need} events before index {end} (t_end={t_end!r}) reach back to event '
                               f'{max(0, end - need)}, the ring of {ring} keeps events from {oldest} on: feed a larger ring_capacity')
     return end
+
+
+def _first_at_or_after(t_ring, oldest, head, ring, bound):
+    """the absolute index of the first kept event [oldest, head) with t >= bound (head where there is none); for int64 times the
+    bound is raised to the next integer first: t >= b and t >= ceil(b) are one condition"""
+    if t_ring.dtype == np.int64 and int(bound) != bound:
+        bound = int(np.ceil(bound))
+    bound = t_ring.dtype.type(bound)
+    at_abs = oldest
+    for at, _, m in ring_segments(oldest, head - oldest, ring):
+        k = int(np.searchsorted(t_ring[at:at + m], bound, side='left'))
+        at_abs += k
+        if k < m:
+            break
+    return at_abs
+
+
+def sequence_windows_fixed_duration(t_ring, head, ring, t_end, T, window_duration):
+    """The DSEC loader's fixed_duration cut of one sample (reference DSEC/dataset/sequence.py:224-231), in absolute event indices:
+        ts_start = t_end - T d;  per = (T d) / T (the loader's delta_t_us / nr_events_data: a TRUE division, a float)
+        window i = the events with ts_start + i per <= t < ts_start + (i + 1) per
+    both bounds of a window found as "the first event with t >= bound" (EventSlicer.get_time_indices_offsets).  t_ring, head, ring: as
+    ring_end_index.  -> T pairs (start, count); a count of 0 is a window without events (an all-zero grid).  Refused: a first bound at
+    or before the oldest kept event's time once older events have been overwritten (the window's start lies, or may lie, among them)."""
+    head, ring, T = int(head), int(ring), int(T)
+    if not isinstance(t_ring, np.ndarray) or t_ring.ndim != 1 or len(t_ring) != ring or t_ring.dtype not in (np.int64, np.float64):
+        raise hip.EssHipError(f'sequence_windows_fixed_duration: t_ring must be the ring\'s {ring} times as a 1-D int64 or float64 array')
+    if head < 0 or ring < 1 or T < 1:
+        raise hip.EssHipError(f'sequence_windows_fixed_duration: head={head} ring={ring} T={T}')
+    d = window_duration
+    if isinstance(d, bool) or not isinstance(d, (int, float, np.integer, np.floating)) or not d > 0 or d == float('inf'):
+        raise hip.EssHipError(f'sequence_windows_fixed_duration: window_duration={d!r} must be a positive number')
+    if isinstance(t_end, bool) or not isinstance(t_end, (int, float, np.integer, np.floating)) or not np.isfinite(t_end):
+        raise hip.EssHipError(f'sequence_windows_fixed_duration: t_end={t_end!r} must be a finite time')
+    delta_t = T * d
+    ts_start = t_end - delta_t
+    per = delta_t / T
+    bounds = [ts_start + i * per for i in range(T + 1)]
+    oldest = max(0, head - ring)
+    if oldest > 0 and bounds[0] <= t_ring[oldest % ring]:
+        raise hip.EssHipError(f'sequence_windows_fixed_duration: the sequence starts at t={bounds[0]!r}, not after the oldest kept event '
+                              f'(index {oldest}, t={t_ring[oldest % ring]!r}): the events before it have been overwritten (ring of {ring})')
+    idx = [_first_at_or_after(t_ring, oldest, head, ring, b) for b in bounds]
+    # (window i is [first t >= bound i, first t >= bound i + 1), the two searches the loader makes per window)
+    return [(idx[i], idx[i + 1] - idx[i]) for i in range(T)]
+
+
+def sequence_windows_by_time(t, begin, end, T):
+    """The DDD17 loader's cut of one sample by time (reference datasets/ddd17_events_loader.py:134-149) on the events [begin, end)
+    of a recording's sorted time column t (entry k: event k's time), in absolute event indices:
+        delta = int((t[end - 1] - t[begin]) / T);  id_end_i = searchsorted(t[begin:end], t[begin] + (i + 1) delta), at most end - begin
+        window 0 starts at begin, window i at id_end_(i-1)
+    -> T pairs (start, count).  The events behind id_end_(T-1) are not used; delta == 0 (a span shorter than T time units) gives T
+    empty windows, as the loader's searchsorted does."""
+    begin, end, T = int(begin), int(end), int(T)
+    if not isinstance(t, np.ndarray) or t.ndim != 1:
+        raise hip.EssHipError('sequence_windows_by_time: t must be a 1-D array of times')
+    if T < 1 or not 0 <= begin < end <= len(t):
+        raise hip.EssHipError(f'sequence_windows_by_time: begin={begin} end={end} T={T} on {len(t)} events (a non-empty range is needed)')
+    ts = t[begin:end]
+    n = len(ts)
+    delta = int((ts[-1] - ts[0]) / T)
+    out, id_end = [], 0
+    for i in range(T):
+        id_start = id_end
+        id_end = min(int(np.searchsorted(ts, ts[0] + (i + 1) * delta)), n)
+        out.append((begin + id_start, id_end - id_start))
+    return out

@@ -79,6 +79,7 @@ EXPORTS = [
     'ess_event_normalize_samples', 'ess_state_carry_masked', 'ess_state_carry_indexed',
     'ess_event_ingest_workspace', 'ess_event_ingest', 'ess_event_ingest_columns', 'ess_event_ingest_ring',
     'ess_event_ingest_columns_trilinear', 'ess_event_ingest_ring_trilinear', 'ess_seg_head_eval',
+    'ess_event_scatter_ring', 'ess_event_scatter_ring_trilinear', 'ess_event_grid_finish_workspace', 'ess_event_grid_finish',
 ]
 
 
@@ -123,6 +124,8 @@ def lib():
         L.ess_voxel_grid_trilinear_workspace.argtypes = [c_int64, c_int32, c_int32, c_int32]
         L.ess_event_ingest_workspace.restype = c_size_t
         L.ess_event_ingest_workspace.argtypes = [c_int32, c_int32, c_int32, c_int32]
+        L.ess_event_grid_finish_workspace.restype = c_size_t
+        L.ess_event_grid_finish_workspace.argtypes = [c_int32, c_int32, c_int32, c_int32]
         P, F, I, I64 = c_void_p, c_float, c_int32, c_int64
         D = POINTER(EssConvDesc)
         sig = {
@@ -179,6 +182,9 @@ def lib():
             'ess_event_ingest_ring': [P, P, P, P, P, P, P, P, I64, I, I, I, I, I, P, c_size_t, P, P],
             'ess_event_ingest_columns_trilinear': [P, P, P, P, P, P, I64, I, I, I, I, P, c_size_t, P, P, P, I, I, I, P],
             'ess_event_ingest_ring_trilinear': [P, P, P, P, P, P, P, P, I64, I, I, I, I, I, P, c_size_t, P, P, P, I, I, I, P],
+            'ess_event_scatter_ring': [P, P, P, P, P, P, P, P, I64, I, I, I, I, I, P, c_size_t, P],
+            'ess_event_scatter_ring_trilinear': [P, P, P, P, P, P, P, P, I64, I, I, I, I, I, P, c_size_t, P, P, I, I, I, P],
+            'ess_event_grid_finish': [P, I, I, I, I, P, c_size_t, I, I, I, I, I, P, P, c_size_t, P],
         }
         for name, argtypes in sig.items():
             fn = getattr(L, name)
@@ -1057,6 +1063,114 @@ def event_ingest_ring_trilinear(t, x, y, p, rows, starts, counts, formats, out, 
     windows laid out from entry 0.  maps, map_of (int32 [n_slots], slot i's map): as event_ingest_columns_trilinear; everything else:
     as event_ingest_ring."""
     return _event_ingest_ring('event_ingest_ring_trilinear', t, x, y, p, rows, starts, counts, formats, out, acc, (maps, map_of))
+
+
+# The ring ingest in its two halves (ess_event_scatter_ring* / ess_event_grid_finish): the LOADER's grid -- normalised over its
+# non-zero voxels, rows cut, resized bilinearly -- from the same order-independent sums.
+GRID_NORM_NONE = 0        # ESS_GRID_NORM_NONE
+GRID_NORM_UNBIASED = 1    # ESS_GRID_NORM_UNBIASED: VoxelGrid(normalize=True)
+GRID_NORM_POPULATION = 2  # ESS_GRID_NORM_POPULATION: normalize_voxel_grid
+
+
+def event_scatter_ring(t, x, y, p, rows, starts, counts, formats, acc):
+    """The first half of event_ingest_ring: the windows' events are added into acc and nothing else happens.  acc: device int64
+    [n_slots, bins, H, W] -- the grid's geometry is read from it -- ALL ZERO before the call; behind it it holds the sums at scale 2^40
+    that event_grid_finish turns into grids (and zeroes again).  t .. formats: as event_ingest_ring.  -> acc"""
+    return _event_scatter_ring('event_scatter_ring', t, x, y, p, rows, starts, counts, formats, acc, None)
+
+
+def event_scatter_ring_trilinear(t, x, y, p, rows, starts, counts, formats, acc, maps=None, map_of=None):
+    """event_scatter_ring in the trilinear flavour: the first half of event_ingest_ring_trilinear; maps, map_of: as there."""
+    return _event_scatter_ring('event_scatter_ring_trilinear', t, x, y, p, rows, starts, counts, formats, acc, (maps, map_of))
+
+
+def _event_scatter_ring(fn, t, x, y, p, rows, starts, counts, formats, acc, rectify):
+    named = (('t', t), ('x', x), ('y', y), ('p', p), ('rows', rows), ('starts', starts), ('counts', counts), ('formats', formats),
+             ('acc', acc))
+    for name, v in named:
+        if not torch.is_tensor(v):
+            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+    if acc.dim() != 4 or acc.dtype != torch.int64 or acc.numel() == 0:
+        raise EssHipError(f'{fn}: acc must be a non-empty int64 [n_slots, bins, H, W] tensor, got {acc.dtype}{tuple(acc.shape)}')
+    n_slots, bins, H, W = acc.shape
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise EssHipError(f'{fn}: t must be [n_rows, ring], got {tuple(t.shape)}')
+    for name, v in named[:4]:
+        if v.dtype not in _EVCOL_DTYPES[name] or v.shape != t.shape:
+            raise EssHipError(f'{fn}: {name} must be {" / ".join(str(d) for d in _EVCOL_DTYPES[name])} '
+                              f'{list(t.shape)}, got {v.dtype}{tuple(v.shape)}')
+    for name, v in named[4:8]:
+        if v.dtype != torch.int32 or tuple(v.shape) != (n_slots,):
+            raise EssHipError(f'{fn}: {name} must be int32 [{n_slots}], got {v.dtype}{tuple(v.shape)}')
+    n_rows, ring = t.shape
+    if ring % EVCOL_STRIDE_ALIGN or ring > INGEST_MAX_CAPACITY:
+        raise EssHipError(f'{fn}: ring={ring} must be a multiple of {EVCOL_STRIDE_ALIGN} in [{EVCOL_STRIDE_ALIGN}, '
+                          f'{INGEST_MAX_CAPACITY}] (event_column_stride rounds a capacity up)')
+    for name, v in named:  # (the device last: what is wrong with a tensor's form is said whatever memory it lies in)
+        if not v.is_cuda:
+            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+        if not v.is_contiguous():
+            raise EssHipError(f'{fn}: {name} must be contiguous')
+    tail = () if rectify is None else _rectify_args(fn, rectify[0], rectify[1], n_slots, acc.device)
+    _check(getattr(lib(), 'ess_' + fn)(c_void_p(t.data_ptr()), c_void_p(x.data_ptr()), c_void_p(y.data_ptr()), c_void_p(p.data_ptr()),
+                                       ptr(rows, torch.int32), ptr(starts, torch.int32), ptr(counts, torch.int32),
+                                       ptr(formats, torch.int32), ring, n_rows, n_slots, bins, H, W, c_void_p(acc.data_ptr()),
+                                       acc.numel() * 8, *tail, stream()), 'ess_' + fn)
+    return acc
+
+
+def event_grid_finish(counts, acc, out, crop_rows=None, resize=None, normalize=GRID_NORM_NONE):
+    """The second half: acc (device int64 [n_slots, bins, Hs, Ws], the sums event_scatter_ring* left) -> out (fp32
+    [n_slots, bins, out_rows, Wr], returned), the grid a reference LOADER hands the network.  Per slot, in this order: the sums are
+    dequantised; normalize (GRID_NORM_NONE / GRID_NORM_UNBIASED: VoxelGrid(normalize=True) / GRID_NORM_POPULATION:
+    normalize_voxel_grid) over the non-zero voxels of ALL Hs rows, with exact integer count and sum and an fp64 sum of squares in a
+    fixed order; rows [0, crop_rows) are kept (None: Hs); they are resized bilinearly (align_corners=True, torch's fp32 coordinates)
+    to resize=(Hr, Wr) (None: (crop_rows, Ws)); rows [0, out_rows) of that are stored -- out's shape names out_rows <= Hr and Wr.
+    counts: device int32 [n_slots] -- INGEST_KEEP (< 0): out[i] is neither read nor written.  acc is ALL ZERO behind the call.  out is
+    a pure function of the sums: the same bits run to run, for a slot alone or among others; with no crop, no resize and no
+    normalisation they are event_ingest_ring's bits.  No memset, no synchronisation: capturable."""
+    fn = 'event_grid_finish'
+    named = (('counts', counts), ('acc', acc), ('out', out))
+    for name, v in named:
+        if not torch.is_tensor(v):
+            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+    if acc.dim() != 4 or acc.dtype != torch.int64 or acc.numel() == 0:
+        raise EssHipError(f'{fn}: acc must be a non-empty int64 [n_slots, bins, Hs, Ws] tensor, got {acc.dtype}{tuple(acc.shape)}')
+    n_slots, bins, Hs, Ws = acc.shape
+    crop_rows = Hs if crop_rows is None else crop_rows
+    if isinstance(crop_rows, bool) or not isinstance(crop_rows, int) or not 1 <= crop_rows <= Hs:
+        raise EssHipError(f'{fn}: crop_rows={crop_rows!r} must be an int in [1, {Hs}]')
+    if resize is None:
+        resize = (crop_rows, Ws)
+    if not isinstance(resize, (tuple, list)) or len(resize) != 2 or \
+            any(isinstance(v, bool) or not isinstance(v, int) or v < 1 or v > 1 << 24 for v in resize):
+        raise EssHipError(f'{fn}: resize={resize!r} must be a pair of positive ints (Hr, Wr)')
+    Hr, Wr = resize
+    if out.dim() != 4 or out.dtype != torch.float32 or out.numel() == 0 or out.shape[0] != n_slots or out.shape[1] != bins \
+            or out.shape[2] > Hr or out.shape[3] != Wr:
+        raise EssHipError(f'{fn}: out must be fp32 [{n_slots}, {bins}, rows <= {Hr}, {Wr}], got {out.dtype}{tuple(out.shape)}')
+    if normalize not in (GRID_NORM_NONE, GRID_NORM_UNBIASED, GRID_NORM_POPULATION) or isinstance(normalize, bool):
+        raise EssHipError(f'{fn}: normalize={normalize!r} must be GRID_NORM_NONE, GRID_NORM_UNBIASED or GRID_NORM_POPULATION')
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (n_slots,):
+        raise EssHipError(f'{fn}: counts must be int32 [{n_slots}], got {counts.dtype}{tuple(counts.shape)}')
+    for name, v in named:
+        if not v.is_cuda:
+            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+        if not v.is_contiguous():
+            raise EssHipError(f'{fn}: {name} must be contiguous')
+    L = lib()
+    nbytes = L.ess_event_grid_finish_workspace(n_slots, bins, Hs, Ws)
+    ws = workspace(nbytes, out.device, 'grid_finish')
+    _check(L.ess_event_grid_finish(ptr(counts, torch.int32), n_slots, bins, Hs, Ws, c_void_p(acc.data_ptr()), acc.numel() * 8, crop_rows,
+                                   Hr, Wr, out.shape[2], int(normalize), c_void_p(out.data_ptr()), c_void_p(ws.data_ptr()), ws.numel(),
+                                   stream()), 'ess_event_grid_finish')
+    return out
+
+
+def grid_finish_workspace(n_slots, bins, Hs, Ws, device):
+    """The cached buffer event_grid_finish takes its statistics from.  Every call writes what it reads of it; the tests fill it with
+    0xFF bytes before a launch to prove that."""
+    return workspace(lib().ess_event_grid_finish_workspace(n_slots, bins, Hs, Ws), device, 'grid_finish')
 
 
 def voxel_normalize_(grids, mode):

@@ -70,30 +70,59 @@ class SequenceSegmenter:
     Memory: the T S grids of a round are static buffers -- fp32 [T S, num_bins, H, W] plus the ingest's int64 sums of the same
     shape: at T = 20, S = 8, 5 x 440 x 640 about 0.9 GB + 1.8 GB -- and the rings take 13 bytes per event on the device and again in
     pinned host memory (T = 20, N_w = 100 000, S = 8: 0.42 GB each).
-    Not covered: fixed_duration sequences (delta_t_per_data windows by TIME, the DDD17 loader's rule and the DSEC loader's other
-    branch, sequence.py:224-253); VoxelGrid(normalize=True)'s own per-grid normalisation, as in MultiStreamSegmenter; the loader's
-    optional bilinear resize of the grids."""
+
+    The LOADER's grid (all opt-in; with none of these keywords a round goes through hip.event_ingest_ring* as before).  The reference
+    loaders do not voxelise at the network's size: they voxelise at the sensor's, normalise the grid over its non-zero voxels, cut
+    rows and resize bilinearly.  grid_hw=(Hs, Ws): the size the events are voxelised at (a rectify map stays the sensor's size
+    whatever it is); grid_normalize=None | 'unbiased' (VoxelGrid(normalize=True)) | 'population' (normalize_voxel_grid): over all Hs
+    rows, in front of the event preprocessor's own normalisation; grid_rows: the top rows kept (default Hs); grid_resize=(Hr, Wr):
+    their bilinear resize, align_corners=True (default: none); the top `height` rows of that are the network's input, so Wr == width
+    and height <= Hr.  The round then starts with hip.event_scatter_ring* and hip.event_grid_finish: the grids stay a pure function
+    of the events.  The two presets:
+        DDD17 (ddd17_events_loader.py:162-173): grid_hw=(260, 346), grid_resize=(260, 352), height=200, width=352, voxel='temporal'
+        DSEC resize=True (sequence.py:281-287): grid_hw=(480, 640), grid_rows=440, grid_resize=(448, 640), height=448, width=640
+    window_duration=d in place of window_events (ring_capacity must then be given): segment_at(t_end=[...]) cuts the DSEC loader's
+    fixed_duration windows (datasets.event_feed.sequence_windows_fixed_duration): T windows of d time units ending at t_end.
+    segment_at(windows=[...]): per stream None or T explicit (start, count) pairs in absolute event indices -- any other rule, such as
+    the DDD17 loader's datasets.event_feed.sequence_windows_by_time."""
 
     def __init__(self, encoder, decoder, height, width, options, n_streams, sequence_steps=None, window_events=None, ring_capacity=None,
                  voxel='temporal', rectify_maps=None, graph=False, copy=True, palette=None, want_confidence=False, out_hw=None,
-                 ignore_index=255, device=None):
+                 ignore_index=255, device=None, window_duration=None, grid_hw=None, grid_rows=None, grid_resize=None,
+                 grid_normalize=None):
         if not isinstance(n_streams, int) or isinstance(n_streams, bool) or n_streams < 1:
             raise hip.EssHipError(f'n_streams={n_streams!r}: a positive number of streams is needed')
         T = sequence_steps
         if not isinstance(T, int) or isinstance(T, bool) or T < 1:
             raise hip.EssHipError(f'sequence_steps={T!r}: the number of windows of a sequence, a positive int (DSEC: nr_events_data = 20)')
-        if window_events is None:
+        if window_events is not None and window_duration is not None:
+            raise hip.EssHipError('give window_events=N or window_duration=d, not both: a sequence is cut by count or by time')
+        if window_events is None and window_duration is None:
             raise hip.EssHipError('window_events is needed: the events per window (DSEC: nr_events_window = 100000)')
-        N_w = _event_capacity(window_events, height, width)
+        self._loader_grid = any(v is not None for v in (grid_hw, grid_rows, grid_resize, grid_normalize))
+        Hs, Ws, self._grid = height, width, None
+        if self._loader_grid:
+            Hs, Ws = self._grid_geometry(height, width, grid_hw, grid_rows, grid_resize, grid_normalize)
+        if window_duration is not None:
+            d = window_duration
+            if isinstance(d, bool) or not isinstance(d, (int, float, np.integer, np.floating)) or not d > 0 or d == float('inf'):
+                raise hip.EssHipError(f'window_duration={d!r}: the duration of one window in the unit of t, a positive number')
+            if ring_capacity is None:
+                raise hip.EssHipError('window_duration needs ring_capacity: no event count follows from a duration')
+            N_w = 0
+            _event_capacity(1, Hs, Ws)  # (the coordinates must fit the columns)
+        else:
+            N_w = _event_capacity(window_events, Hs, Ws)
+        self.window_duration = window_duration
         if voxel not in VOXEL_FLAVOURS:
             raise hip.EssHipError(f'voxel={voxel!r}: one of {VOXEL_FLAVOURS}')
         if not isinstance(ignore_index, int) or isinstance(ignore_index, bool) or not 0 <= ignore_index <= 255:
             raise hip.EssHipError(f'ignore_index={ignore_index!r}: a value of the uint8 ground truth is needed')
         R = 2 * T * N_w if ring_capacity is None else ring_capacity
-        if not isinstance(R, int) or isinstance(R, bool) or R < T * N_w or hip.event_column_stride(R) > hip.INGEST_MAX_CAPACITY:
+        if not isinstance(R, int) or isinstance(R, bool) or R < max(1, T * N_w) or hip.event_column_stride(R) > hip.INGEST_MAX_CAPACITY:
             raise hip.EssHipError(f'ring_capacity={R!r}: events per stream the ring holds, an int in [sequence_steps * window_events = '
                                   f'{T * N_w}, {hip.INGEST_MAX_CAPACITY}] (default: twice the lower bound)')
-        self.n_streams, self.sequence_steps, self.window_events = n_streams, T, N_w
+        self.n_streams, self.sequence_steps, self.window_events = n_streams, T, (N_w if window_duration is None else None)
         self.ring_capacity = R = hip.event_column_stride(R)
         self.voxel, self.ignore_index = voxel, ignore_index
         self.copy_outputs = bool(copy)
@@ -128,7 +157,7 @@ class SequenceSegmenter:
         self._words = torch.zeros(n_words, T * S, dtype=torch.int32, device=dev)
         self._words[4:].fill_(hip.RECTIFY_NONE)
         self._in = torch.zeros(T * S, self.num_bins, height, width, dtype=torch.float32, device=dev)
-        self._acc = torch.zeros(T * S, self.num_bins, height, width, dtype=torch.int64, device=dev)
+        self._acc = torch.zeros(T * S, self.num_bins, Hs, Ws, dtype=torch.int64, device=dev)  # (the size the events are voxelised at)
         self._gt = torch.full((S,) + self.out_hw, ignore_index, dtype=torch.uint8, device=dev)
         self._gt_live = [False] * S  # (host: the stream's row of _gt holds a ground truth, not the ignore fill)
         self.confusion = torch.zeros(S, K, K, dtype=torch.int64, device=dev)
@@ -139,6 +168,27 @@ class SequenceSegmenter:
             self._stage.append(_SequenceStage(words, torch.zeros((S,) + self.out_hw, dtype=torch.uint8).pin_memory(), torch.cuda.Event()))
         self._stage_next = 0
         self._g = self._outputs = None
+
+    def _grid_geometry(self, height, width, grid_hw, grid_rows, grid_resize, grid_normalize):
+        """the loader-grid keywords, checked -> (Hs, Ws); self._grid = (crop_rows, (Hr, Wr), hip.GRID_NORM_*)"""
+        def pair(name, v):
+            if not isinstance(v, (tuple, list)) or len(v) != 2 or any(isinstance(a, bool) or not isinstance(a, int) or a < 1 for a in v):
+                raise hip.EssHipError(f'{name}={v!r}: a pair of positive ints (rows, columns) is needed')
+            return int(v[0]), int(v[1])
+        Hs, Ws = (height, width) if grid_hw is None else pair('grid_hw', grid_hw)
+        rows = Hs if grid_rows is None else grid_rows
+        if isinstance(rows, bool) or not isinstance(rows, int) or not 1 <= rows <= Hs:
+            raise hip.EssHipError(f'grid_rows={rows!r}: the top rows of the {Hs} x {Ws} grid that are kept, an int in [1, {Hs}]')
+        Hr, Wr = (rows, Ws) if grid_resize is None else pair('grid_resize', grid_resize)
+        if Wr != width or height > Hr:
+            raise hip.EssHipError(f'the loader grid ends as {Hr} x {Wr} (grid_resize, or grid_rows x the grid\'s width), the network reads its '
+                                  f'top {height} rows of {width} columns: the widths must agree and height <= {Hr}')
+        norms = {None: hip.GRID_NORM_NONE, 'unbiased': hip.GRID_NORM_UNBIASED, 'population': hip.GRID_NORM_POPULATION}
+        if not isinstance(grid_normalize, (str, type(None))) or grid_normalize not in norms:
+            raise hip.EssHipError(f"grid_normalize={grid_normalize!r}: None, 'unbiased' (VoxelGrid(normalize=True)) or 'population' "
+                                  '(normalize_voxel_grid)')
+        self._grid = (rows, (Hr, Wr), norms[grid_normalize])
+        return Hs, Ws
 
     @classmethod
     def from_checkpoints(cls, e2vid_path, ess_checkpoint_path, settings_or_kwargs, n_streams, **kw):
@@ -229,14 +279,27 @@ class SequenceSegmenter:
     # ---- one round
     def _round(self):
         """the device work of one sequence round on the static rings, words and ground truth -> (labels, colour, confidence)"""
-        rec, pre = self.rec, self.rec.event_preprocessor
-        T, S = self.sequence_steps, self.n_streams
         with torch.no_grad():
             ev = self._in
-            if self.voxel == 'trilinear':
+            if self._loader_grid:  # the loader's grid: the sums at the size the loader voxelises at, then its normalise / cut / resize
+                if self.voxel == 'trilinear':
+                    hip.event_scatter_ring_trilinear(*self._ring, *self._words[:4], self._acc, self._maps, self._words[4])
+                else:
+                    hip.event_scatter_ring(*self._ring, *self._words, self._acc)
+                crop_rows, resize, normalize = self._grid
+                hip.event_grid_finish(self._words[2], self._acc, ev, crop_rows=crop_rows, resize=resize, normalize=normalize)
+            elif self.voxel == 'trilinear':
                 hip.event_ingest_ring_trilinear(*self._ring, *self._words[:4], ev, self._maps, self._words[4], self._acc)
             else:
                 hip.event_ingest_ring(*self._ring, *self._words, ev, self._acc)
+            return self._round_from(ev)
+
+    def _round_from(self, ev):
+        """the round behind its grids: ev fp32 [T S, num_bins, height, width] (the round's own buffer, or -- tools/bench_seg_stream.py --
+        grids put together another way) -> (labels, colour, confidence)"""
+        rec, pre = self.rec, self.rec.event_preprocessor
+        T, S = self.sequence_steps, self.n_streams
+        with torch.no_grad():
             for x, y in pre.hot_pixel_locations:
                 ev[:, :, y, x] = 0
             if pre.flip:
@@ -327,17 +390,68 @@ class SequenceSegmenter:
         if hip.compute_name() != self.compute:
             raise hip.EssHipError(f"SequenceSegmenter: built in the '{self.compute}' configuration, called in '{hip.compute_name()}'")
 
-    def segment_at(self, t_end=None, end=None, labels=None):
+    def _explicit_windows(self, windows):
+        """segment_at's windows=[...] -> per stream None or T pairs (start, count), every one checked against the events the ring keeps"""
+        T, S, R = self.sequence_steps, self.n_streams, self.ring_capacity
+        if not isinstance(windows, (list, tuple)) or len(windows) != S:
+            n = len(windows) if isinstance(windows, (list, tuple)) else type(windows).__name__
+            raise hip.EssHipError(f'windows must be a list with one entry per stream (None: idle): got {n}, n_streams={S}')
+        out = []
+        for s, (w, f) in enumerate(zip(windows, self._feeds)):
+            if w is None:
+                out.append(None)
+                continue
+            if not isinstance(w, (list, tuple)) or len(w) != T:
+                n = len(w) if isinstance(w, (list, tuple)) else type(w).__name__
+                raise hip.EssHipError(f'windows[{s}] must hold sequence_steps={T} pairs (start, count): got {n}')
+            pairs = []
+            for i, v in enumerate(w):
+                if not isinstance(v, (list, tuple)) or len(v) != 2 or \
+                        any(isinstance(a, bool) or not isinstance(a, (int, np.integer)) for a in v):
+                    raise hip.EssHipError(f'windows[{s}][{i}]={v!r}: a pair of ints (start, count) in absolute event indices is needed')
+                start, count = int(v[0]), int(v[1])
+                if start < 0 or count < 0 or start + count > f.head:
+                    raise hip.EssHipError(f'windows[{s}][{i}]=({start}, {count}): the events [{start}, {start + count}) are not all among the '
+                                          f'{f.head} events fed')
+                if count > 0 and start < f.head - R:
+                    raise hip.EssHipError(f'windows[{s}][{i}]=({start}, {count}): the window reaches back to event {start}, the ring of {R} '
+                                          f'keeps events from {f.head - R} on')
+                pairs.append((start, count))
+            out.append(pairs)
+        return out
+
+    def _duration_windows(self, t_end):
+        """segment_at's t_end=[...] of a window_duration segmenter -> per stream None (idle) or the loader's fixed_duration windows"""
+        from .datasets.event_feed import sequence_windows_fixed_duration
+        S, R = self.n_streams, self.ring_capacity
+        if not isinstance(t_end, (list, tuple)) or len(t_end) != S:
+            n = len(t_end) if isinstance(t_end, (list, tuple)) else type(t_end).__name__
+            raise hip.EssHipError(f't_end must be a list with one entry per stream (None: idle): got {n}, n_streams={S}')
+        return [None if v is None or f.head == 0 else
+                sequence_windows_fixed_duration(self._ring_np[0][s].view(f.dtypes[0]), f.head, R, v, self.sequence_steps, self.window_duration)
+                for s, (v, f) in enumerate(zip(t_end, self._feeds))]
+
+    def segment_at(self, t_end=None, end=None, labels=None, windows=None):
         """One sequence round.  t_end / end: S entries -- a time (the sequence ends in front of the first event with t >= t_end, as
-        the reference's get_events_fixed_num) / an absolute event index, or None for an idle stream; exactly one of the two lists.
+        the reference's get_events_fixed_num; with window_duration: the T windows of that duration in front of t_end) / an absolute
+        event index, or None for an idle stream; windows: S entries, each None or sequence_steps pairs (start, count) in absolute
+        event indices, a count of 0 being a window without events; exactly one of the three lists.
         labels: None or S entries, each None or the stream's uint8 [H_out, W_out] ground truth.  Everything is checked before
         anything is written.  -> MultiSegmentationResult"""
         from .datasets.event_feed import sequence_windows
         self._check_compute()
-        ends = self._ends(t_end, end)
-        gts = self._check_labels(labels)
         T, S, R = self.sequence_steps, self.n_streams, self.ring_capacity
-        wins = [None if e is None else sequence_windows(e, 0, T, self.window_events) for e in ends]
+        if windows is not None:
+            if t_end is not None or end is not None:
+                raise hip.EssHipError('segment_at: windows=[...] names the windows themselves: give it without t_end and end')
+            wins = self._explicit_windows(windows)
+        elif self.window_duration is not None:
+            if end is not None or t_end is None:
+                raise hip.EssHipError('segment_at: a window_duration segmenter cuts by time: give t_end=[...] (or windows=[...])')
+            wins = self._duration_windows(t_end)
+        else:
+            wins = [None if e is None else sequence_windows(e, 0, T, self.window_events) for e in self._ends(t_end, end)]
+        gts = self._check_labels(labels)
         on = [w is not None for w in wins]
         if self.use_graph and self._g is None:
             self._capture()
@@ -352,7 +466,8 @@ class SequenceSegmenter:
             if w is not None:
                 for i, (start, count) in enumerate(w):
                     k = i * S + s
-                    st.starts_np[k], st.counts_np[k], st.formats_np[k] = start % R, count, self._feeds[s].format
+                    # (a stream that was never fed can only name empty windows: its format word is not read)
+                    st.starts_np[k], st.counts_np[k], st.formats_np[k] = start % R, count, self._feeds[s].format or 0
                     if st.maps_np is not None:
                         st.maps_np[k] = self._map_of[s]
         self._words.copy_(st.words, non_blocking=True)

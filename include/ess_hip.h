@@ -488,6 +488,51 @@ int ess_event_ingest_ring_trilinear(const void* t, const void* x, const void* y,
                                     const float* maps, const int32_t* map_of, int32_t n_maps, int32_t map_height, int32_t map_width,
                                     ess_stream_t stream);
 
+/* The LOADER's grid from the ring ingest -- PURELY ADDITIVE to ABI 110 (ess_version() is unchanged; no existing entry point changes).
+ * The reference loaders do not hand the network the grid they voxelise: DSEC's VoxelGrid(normalize=True) normalises it over its
+ * non-zero voxels, both loaders cut rows and resize bilinearly (DSEC resize=True: 480 rows -> the top 440 -> 448 x 640; DDD17: 260 x 346
+ * -> 260 x 352 -> the top 200 rows).  All of that sits between the ingest's int64 sums and the fp32 grid, so the ingest is offered in
+ * its two halves:
+ *
+ * ess_event_scatter_ring / ess_event_scatter_ring_trilinear: the arguments of ess_event_ingest_ring / _trilinear without `out`, the
+ * same scatter launch, and nothing behind it: acc (all zero before, [n_slots][bins][height][width]) keeps the sums.
+ *
+ * ess_event_grid_finish: acc [n_slots][bins][src_height][src_width] -> out fp32 [n_slots][bins][out_rows][resize_width].  Per slot,
+ * in this order:
+ *   1. v = (float)acc * 2^-40 (what ess_event_ingest_ring stores);
+ *   2. normalize, over ALL src_height rows of the slot's grid (the loader takes its statistics before it cuts rows):
+ *        ESS_GRID_NORM_NONE;
+ *        ESS_GRID_NORM_UNBIASED   VoxelGrid(normalize=True): mean and n - 1 std of the non-zero voxels, a non-zero v becomes
+ *                                 (v - mean) / std where std > 0, else v - mean (one non-zero voxel: NaN std, the else branch);
+ *        ESS_GRID_NORM_POPULATION normalize_voxel_grid: std = sqrt(E[v^2] - mean^2), a non-zero v becomes (v - mean) / std, unguarded;
+ *      the case analysis and the fp32 expressions are ess_voxel_normalize's (mode 0 / mode 1), evaluated without fused multiply-add
+ *      (equal non-zero voxels give a population std of exactly 0).  Zeros stay zero.  The statistics are exact: count and
+ *      sum of the integer-valued (float)acc as int64, sum of squares in fp64 in a FIXED order (per-workgroup partials in `workspace`,
+ *      the number of workgroups a function of the slot's size alone, added in workgroup order) -- no atomics, no memset;
+ *   3. rows [0, crop_rows) are kept;
+ *   4. bilinear resize [crop_rows, src_width] -> [resize_height, resize_width], align_corners=True, torch's fp32 coordinates:
+ *      scale = (in - 1) / (out - 1) (0 where out == 1), src = scale * dst, i0 = (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0,
+ *      l0 = 1 - l1;  value = l0y * (l0x * v00 + l1x * v01) + l1y * (l0x * v10 + l1x * v11), no fused multiply-add;
+ *   5. rows [0, out_rows) of the resized grid are stored.
+ * counts[i] < 0 (ESS_INGEST_KEEP): out[i] is neither read nor written;  counts[i] == 0: acc is zero, so is the grid.  acc is ALL ZERO
+ * behind the call.  A slot's grid is a pure function of its sums: the same bits run to run, alone or among other slots.  With
+ * crop_rows == src_height == resize_height == out_rows, resize_width == src_width and ESS_GRID_NORM_NONE the grid has the bits of
+ * ess_event_ingest_ring's.  Launches shaped by the sizes alone, counts read on the device, no synchronisation: capturable.
+ * workspace: ess_event_grid_finish_workspace() bytes, 16-byte aligned, written before it is read (needs no initial value).       */
+enum { ESS_GRID_NORM_NONE = 0, ESS_GRID_NORM_UNBIASED = 1, ESS_GRID_NORM_POPULATION = 2 };
+int ess_event_scatter_ring(const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
+                           const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots, int32_t bins,
+                           int32_t height, int32_t width, void* acc, size_t acc_bytes, ess_stream_t stream);
+int ess_event_scatter_ring_trilinear(const void* t, const void* x, const void* y, const void* p, const int32_t* rows,
+                                     const int32_t* starts, const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows,
+                                     int32_t n_slots, int32_t bins, int32_t height, int32_t width, void* acc, size_t acc_bytes,
+                                     const float* maps, const int32_t* map_of, int32_t n_maps, int32_t map_height, int32_t map_width,
+                                     ess_stream_t stream);
+size_t ess_event_grid_finish_workspace(int32_t n_slots, int32_t bins, int32_t src_height, int32_t src_width);
+int ess_event_grid_finish(const int32_t* counts, int32_t n_slots, int32_t bins, int32_t src_height, int32_t src_width, void* acc,
+                          size_t acc_bytes, int32_t crop_rows, int32_t resize_height, int32_t resize_width, int32_t out_rows,
+                          int32_t normalize, float* out, void* workspace, size_t workspace_bytes, ess_stream_t stream);
+
 /* ---- image-branch augmentation on the device: the geometric + photometric core of the albumentations
  * pipeline of datasets/cityscapes_loader.py:39-74 (HorizontalFlip, ShiftScaleRotate with rotate 0 and a constant-0 border,
  * centred PadIfNeeded, RandomCrop, GaussNoise, RandomBrightnessContrast), uint8 quantisation, ToTensor (/255), and for the label

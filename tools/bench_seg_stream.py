@@ -68,9 +68,19 @@ replayed, alternating in the same process:
 and, beside them, the class head alone (device time over 50 launches): hip.seg_head_eval against hip.seg_head followed by S
 hip.label_confusion calls on int64 copies of the labels.  SLOWER is reported wherever that is the result.
 
+--sequence T --loader-grid ddd17|dsec measures the sequence round on the LOADER's grid instead (the preset sets the sensor's size, the
+network's size and the classes: DDD17 260 x 346 -> 200 x 352, K = 6, temporal, normalize_voxel_grid; DSEC 480 x 640 -> 448 x 640,
+K = 11, trilinear, VoxelGrid(normalize=True)), two ways on ONE segmenter's rings, slot words and models, both replayed, alternating:
+
+  loader_grid  SequenceSegmenter(grid_hw=, grid_rows=, grid_resize=, grid_normalize=).segment_at(end=, labels=);
+  composed     the same round with its grids put together from the older pieces: hip.event_ingest_ring* at the sensor's size,
+               hip.voxel_normalize_, torch's F.interpolate on the device, a slice made contiguous, then the round behind its grids
+               (one captured graph as well; it reads the slot words the other way uploaded, so it pays no upload of its own).
+
 usage: python tools/bench_seg_stream.py [--compute mixed,bf16 --windows 40 --warmup 8 --reps 3 --recurrent convlstm --streams 1,2,4,8
                                          [--active 1,2,4,6,8 [--buckets 1,2,4]] | --streams 8 --events 100000 --ingest | --streams 8 --events 100000 --feed [--voxel trilinear]
-                                         | --streams 8 --events 100000 --sequence 20 --height 440 --windows 6 --warmup 2]"""
+                                         | --streams 8 --events 100000 --sequence 20 --height 440 --windows 6 --warmup 2
+                                         | --streams 8 --events 100000 --sequence 20 --loader-grid dsec --windows 6 --warmup 2]"""
 import argparse
 import json
 import os
@@ -109,7 +119,14 @@ def main():
                          'and against the host alternative as well')
     ap.add_argument('--sequence', type=int, default=None, help='(with --streams) sequence rounds of this many windows: SequenceSegmenter '
                                                                'against reset() + T x update_from_feed() + label_confusion')
+    ap.add_argument('--loader-grid', default=None, choices=tuple(LOADER_PRESETS),
+                    help="(with --sequence) the round on a reference loader's grid against the composition of the older pieces; sets "
+                         '--height, --width (the sensor) and --classes')
     a = ap.parse_args()
+    if a.loader_grid and a.sequence is None:
+        ap.error('--loader-grid belongs to --sequence')
+    if a.loader_grid:
+        (a.height, a.width), a.classes = LOADER_PRESETS[a.loader_grid]['sensor'], LOADER_PRESETS[a.loader_grid]['classes']
     if a.sequence is not None and (not a.streams or a.active or a.ingest or a.feed or a.sequence < 1):
         ap.error('--sequence T (T >= 1) needs --streams and excludes --active, --ingest and --feed')
     if a.feed and (not a.streams or a.active or a.ingest):
@@ -149,6 +166,10 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / a.windows * 1e3
 
+    if a.sequence is not None and a.loader_grid:
+        sequence_loader_grid(a, hip, cfg, [w.cpu().numpy() for w in wins], out, E2VIDRecurrent, SemSegE2VID, default_options)
+        print(json.dumps(out))
+        return
     if a.sequence is not None:
         sequence_rounds(a, hip, cfg, [w.cpu().numpy() for w in wins], out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, default_options)
         print(json.dumps(out))
@@ -511,6 +532,112 @@ def from_packet_feed(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiS
                     assert ring.n_captures == cols.n_captures == 1
                     del ring, cols, src
                     torch.cuda.empty_cache()
+        finally:
+            hip.set_compute('fp32')
+
+
+# the reference loaders' grids (SequenceSegmenter's docstring): the sensor's size, the network's, the classes, the keywords
+LOADER_PRESETS = {
+    'ddd17': dict(sensor=(260, 346), net=(200, 352), classes=6,
+                  kw=dict(voxel='temporal', grid_hw=(260, 346), grid_resize=(260, 352), grid_normalize='population')),
+    'dsec': dict(sensor=(480, 640), net=(448, 640), classes=11,
+                 kw=dict(voxel='trilinear', grid_hw=(480, 640), grid_rows=440, grid_resize=(448, 640), grid_normalize='unbiased')),
+}
+
+
+def sequence_loader_grid(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, default_options):
+    import torch.nn.functional as F
+    from ess_amd.datasets.data_util import EventColumns
+    from ess_amd.run_sequence_segmentation import SequenceSegmenter
+    preset = LOADER_PRESETS[a.loader_grid]
+    (Hs, Ws), (Hn, Wn), T, N, K = preset['sensor'], preset['net'], a.sequence, a.events, a.classes
+    out['shape'] = f'S streams, events voxelised at {a.bins}x{Hs}x{Ws} -> the loader grid {a.bins}x{Hn}x{Wn} ({a.loader_grid}) K={K}, ' \
+                   f'sequence rounds of T={T} windows, graph replay'
+    del out['ms_per_window']
+    out['ms_per_round'], out['composed_minus_loader_grid_ms'], out['loader_grid_SLOWER_than_composed'] = {}, {}, {}
+    out['labels_equal_fraction'] = {}
+    rounds = a.warmup + a.windows
+    dev = torch.device('cuda:0')
+    base = np.concatenate(wins)
+    us = np.round(base[:, 0] * 1e6).astype(np.int64)
+    period = int(us[-1] - us[0]) + 1
+
+    def piece(lo, hi):
+        idx = np.arange(lo, hi)
+        r, k = idx // len(us), idx % len(us)
+        return EventColumns(us[k] + r * period, base[k, 1].astype(np.uint16), base[k, 2].astype(np.uint16), base[k, 3].astype(np.uint8))
+
+    for compute in a.compute.split(','):
+        hip.set_compute(compute)
+        try:
+            for S in (int(v) for v in a.streams.split(',')):
+                torch.manual_seed(6)
+                seq = SequenceSegmenter(E2VIDRecurrent(dict(cfg)), SemSegE2VID(256, K, skip_connect=True, skip_type='concat'), Hn, Wn,
+                                        default_options(), S, sequence_steps=T, window_events=N, graph=True, **preset['kw'])
+                crop_rows, (Hr, Wr), norm = seq._grid
+                big = torch.empty(T * S, a.bins, Hs, Ws, device=dev)
+                acc_big = torch.zeros(T * S, a.bins, Hs, Ws, dtype=torch.int64, device=dev)
+
+                def composed_round():
+                    if seq.voxel == 'trilinear':
+                        hip.event_ingest_ring_trilinear(*seq._ring, *seq._words[:4], big, seq._maps, seq._words[4], acc_big)
+                    else:
+                        hip.event_ingest_ring(*seq._ring, *seq._words, big, acc_big)
+                    hip.voxel_normalize_(big, 0 if norm == hip.GRID_NORM_UNBIASED else 1)
+                    ev = F.interpolate(big[:, :, :crop_rows], size=(Hr, Wr), mode='bilinear', align_corners=True)[:, :, :Hn].contiguous()
+                    return seq._round_from(ev)
+                g = torch.Generator().manual_seed(1)
+                gt = torch.randint(0, K, (S, Hn, Wn), generator=g, dtype=torch.uint8).to(dev)
+                shift, ms, fed, same = 1237, {'loader_grid': [], 'composed': []}, 0, []
+                graph = None
+                for k in range(rounds):
+                    for s in range(S):  # the T windows of this round arrive: outside the clock
+                        for lo in range(fed, fed + T * N, N):
+                            seq.feed(s, piece(s * shift + lo, s * shift + lo + N))
+                    fed += T * N
+                    torch.cuda.synchronize()
+                    if graph is None:  # a priming round captures the segmenter's graph and leaves slot words for the composed capture
+                        seq.segment_at(end=[fed] * S, labels=list(gt))
+                        side = torch.cuda.Stream()
+                        side.wait_stream(torch.cuda.current_stream())
+                        with torch.cuda.stream(side):
+                            composed_round()
+                        torch.cuda.current_stream().wait_stream(side)
+                        torch.cuda.synchronize()
+                        graph = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(graph):
+                            composed_out = composed_round()
+
+                    def by_loader_grid():
+                        return seq.segment_at(end=[fed] * S, labels=list(gt)).labels
+
+                    def by_composed():
+                        graph.replay()
+                        return composed_out[0].clone()
+                    took, res = {}, {}
+                    for way, fn in [('loader_grid', by_loader_grid), ('composed', by_composed)][::1 if k % 2 == 0 else -1]:
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        res[way] = fn()
+                        torch.cuda.synchronize()
+                        took[way] = (time.perf_counter() - t0) * 1e3
+                    if k >= a.warmup:
+                        for way in ms:
+                            ms[way].append(took[way])
+                        if k % 2 == 0:  # (the composed way read this round's slot words)
+                            same.append(float((res['loader_grid'] == res['composed']).float().mean()))
+                key = f'{compute}/S={S}/T={T}'
+                for way, v in ms.items():
+                    out['ms_per_round'][f'{key}/{way}'] = {'median': round(statistics.median(v), 4), 'min': round(min(v), 4), 'max': round(max(v), 4)}
+                spread = max(max(v) - min(v) for v in ms.values())
+                diff = statistics.median(ms['composed']) - statistics.median(ms['loader_grid'])
+                out['composed_minus_loader_grid_ms'][key] = round(diff, 4)
+                out['loader_grid_SLOWER_than_composed'][key] = bool(diff < 0)
+                out.setdefault('spread_ms', {})[key] = round(spread, 4)
+                out['labels_equal_fraction'][key] = round(min(same), 6) if same else None
+                assert seq.n_captures == 1 and not bool(seq._acc.any()) and not bool(acc_big.any())
+                del seq, big, acc_big, graph
+                torch.cuda.empty_cache()
         finally:
             hip.set_compute('fp32')
 

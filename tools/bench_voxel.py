@@ -18,7 +18,14 @@ Beside them the TRILINEAR flavour on the same int64 columns, hip.event_ingest_co
 (ring: from position 3), through an identity map and through a smooth synthetic distortion map of the sensor -- the ring's bits
 compared with the columns', the identity map's with no map at all -- and hip.voxel_grid_trilinear (binned) on the same events
 rectified and converted to floats on the host beforehand, compared within the fp32 sums' rounding.
-usage: python tools/bench_voxel.py --ingest --slices 8 --events 100000 --bins 5"""
+Behind them the LOADER FINISH at the two reference presets (their own sensor sizes, whatever --height / --width say): per preset
+the ring ingest as it is (hip.event_ingest_ring*: the grid at the sensor's size), the loader's grid from the same sums
+(hip.event_scatter_ring* + hip.event_grid_finish: normalised over its non-zero voxels, rows cut, resized, rows cut) and the
+composition the older pieces allow (the ring ingest, hip.voxel_normalize_, torch's F.interpolate on the device, a slice made
+contiguous), alternating.  --loader-finish-only skips everything in front of these rows.
+
+usage: python tools/bench_voxel.py --ingest --slices 8 --events 100000 --bins 5
+       python tools/bench_voxel.py --ingest --loader-finish-only --slices 160 --events 100000 --bins 5 --reps 20"""
 import argparse
 import json
 import os
@@ -40,6 +47,7 @@ def main():
     ap.add_argument('--reps', type=int, default=200)
     ap.add_argument('--normalize', action='store_true')
     ap.add_argument('--ingest', action='store_true', help='hip.event_ingest against hip.voxel_grid_temporal (see above)')
+    ap.add_argument('--loader-finish-only', action='store_true', help='(with --ingest) only the loader-finish rows')
     a = ap.parse_args()
     if a.ingest:
         return ingest(a)
@@ -91,11 +99,89 @@ def main():
     }))
 
 
+# the reference loaders' grids: DDD17 (datasets/ddd17_events_loader.py: 260 x 346 -> 260 x 352, the top 200 rows; temporal) and DSEC
+# with resize=True (DSEC/dataset/sequence.py: 480 rows -> the top 440 -> 448 x 640; trilinear, VoxelGrid(normalize=True))
+LOADER_PRESETS = {'ddd17': dict(flavour='temporal', src=(260, 346), crop_rows=260, resize=(260, 352), out_rows=200, normalize='population'),
+                  'dsec': dict(flavour='trilinear', src=(480, 640), crop_rows=440, resize=(448, 640), out_rows=448, normalize='unbiased')}
+
+
+def loader_finish(a):
+    """-> {preset: row}: ms per batch of the three ways above, alternating, 3 x --reps launches each"""
+    import numpy as np
+    import torch.nn.functional as F
+    from ess_amd import hip
+    S, n, C = a.slices, a.events, a.bins
+    dev = torch.device('cuda:0')
+    rows_out = {}
+    for name, ps in LOADER_PRESETS.items():
+        (Hs, Ws), (Hr, Wr), crop, rows = ps['src'], ps['resize'], ps['crop_rows'], ps['out_rows']
+        g = np.random.default_rng(1)
+        ring = hip.event_column_stride(n)
+        t = np.sort(g.integers(0, 30_000, (S, ring)), axis=1).astype(np.int64) + 1_600_000_000_000_000
+        cols = (t, g.integers(0, Ws, (S, ring)).astype(np.int16), g.integers(0, Hs, (S, ring)).astype(np.int16),
+                g.integers(0, 2, (S, ring)).astype(np.uint8))
+        dcols = tuple(torch.from_numpy(c).to(dev) for c in cols)
+        words = (torch.arange(S, dtype=torch.int32, device=dev), torch.zeros(S, dtype=torch.int32, device=dev),
+                 torch.full((S,), n, dtype=torch.int32, device=dev), torch.full((S,), hip.EVCOL_T_I64, dtype=torch.int32, device=dev))
+        acc = torch.zeros(S, C, Hs, Ws, dtype=torch.int64, device=dev)
+        big, net = torch.empty(S, C, Hs, Ws, device=dev), torch.empty(S, C, rows, Wr, device=dev)
+        tri = ps['flavour'] == 'trilinear'
+        ingest_fn, scatter_fn = (hip.event_ingest_ring_trilinear, hip.event_scatter_ring_trilinear) if tri else \
+            (hip.event_ingest_ring, hip.event_scatter_ring)
+        norm = hip.GRID_NORM_UNBIASED if ps['normalize'] == 'unbiased' else hip.GRID_NORM_POPULATION
+
+        def plain():
+            return ingest_fn(*dcols, *words, big, acc=acc)
+
+        def finish():
+            scatter_fn(*dcols, *words, acc)
+            return hip.event_grid_finish(words[2], acc, net, crop_rows=crop, resize=(Hr, Wr), normalize=norm)
+
+        def composed():
+            plain()
+            hip.voxel_normalize_(big, 0 if norm == hip.GRID_NORM_UNBIASED else 1)
+            return F.interpolate(big[:, :, :crop], size=(Hr, Wr), mode='bilinear', align_corners=True)[:, :, :rows].contiguous()
+        ways = {'ingest_ring_at_sensor_size': plain, 'scatter_plus_grid_finish': finish, 'ingest_normalize_interpolate_slice': composed}
+        for fn in ways.values():
+            for _ in range(5):
+                fn()
+        torch.cuda.synchronize()
+        diff = (finish() - composed()).abs().max().item()
+        assert diff <= 1e-3 and not bool(acc.any()) and bool(net.any()), (name, diff)
+        ms = {k: [] for k in ways}
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(3):
+            for k, fn in ways.items():
+                e0.record()
+                for _ in range(a.reps):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                ms[k].append(e0.elapsed_time(e1) / a.reps)
+        med = {k: sorted(v)[1] for k, v in ms.items()}
+        spread = max(max(v) - min(v) for v in ms.values())
+        rows_out[name] = {
+            'workload': f'{S} slots x {n} events, {ps["flavour"]}, [{S},{C},{Hs},{Ws}] sums -> [{S},{C},{rows},{Wr}] fp32, {ps["normalize"]}',
+            'ms_per_batch': {k: {'median': round(med[k], 5), 'min': round(min(v), 5), 'max': round(max(v), 5)} for k, v in ms.items()},
+            'finish_minus_plain_ingest_ms': round(med['scatter_plus_grid_finish'] - med['ingest_ring_at_sensor_size'], 5),
+            'finish_SLOWER_than_plain_ingest': bool(med['scatter_plus_grid_finish'] - med['ingest_ring_at_sensor_size'] > spread),
+            'composed_over_finish': round(med['ingest_normalize_interpolate_slice'] / med['scatter_plus_grid_finish'], 3),
+            'finish_SLOWER_than_composed': bool(med['scatter_plus_grid_finish'] - med['ingest_normalize_interpolate_slice'] > spread),
+            'spread_ms': round(spread, 5), 'max_abs_diff_finish_vs_composed': diff}
+        del acc, big, net, dcols
+        torch.cuda.empty_cache()
+    return rows_out
+
+
 def ingest(a):
     import numpy as np
     from ess_amd import hip
     from ess_amd.datasets.data_util import pack_event_records
     hip.lib()
+    if a.loader_finish_only:
+        print(json.dumps({'metric': 'ring events -> the loader\'s grids, ms per batch', 'unit': 'ms', 'reps': a.reps,
+                          'loader_finish': loader_finish(a), 'data': 'synthetic'}))
+        return
     S, n, C, H, W = a.slices, a.events, a.bins, a.height, a.width
     g = np.random.default_rng(0)
     host = np.zeros((S, n), dtype=hip.EVENT_RECORD)
@@ -229,7 +315,7 @@ def ingest(a):
         'int64_atomics_per_s': atomics / (scatter_ms * 1e-3) if scatter_ms > 0 else None,
         'fp32_atomics_per_s_of_voxel_grid_temporal_incl_memset': atomics / (med['voxel_grid_temporal'] * 1e-3),
         'finish_GBps': S * C * H * W * 12 / (med['event_ingest_finish_only'] * 1e-3) / 1e9,
-        'max_abs_diff_ingest_vs_temporal': err, 'data': 'synthetic'}))
+        'max_abs_diff_ingest_vs_temporal': err, 'loader_finish': loader_finish(a), 'data': 'synthetic'}))
 
 
 if __name__ == '__main__':
