@@ -622,6 +622,96 @@ dim3 grid_pass(int64_t items, int32_t n_slots) {
 // torch's area_pixel_compute_scale<float>(in, out, align_corners=true)
 float grid_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
 
+// ---- the training window (ess_event_grid_finish_window, ess_label_window): the loaders' horizontal flip and random crop, applied
+// where the grid (and its label) is written.  One row of `words` = (flip, y0, x0, reserved) serves a group of slots (the T windows
+// of a sample) and the sample's label; the device clamps it, so no word reads or writes outside a slot.
+struct Window {
+  int y0, x0;  // the window's first row and column in the FLIPPED grid
+  bool flip;
+};
+
+__device__ __forceinline__ Window window_of(const int32_t* __restrict__ words, int group, int grid_h, int grid_w, int win_h, int win_w) {
+  const int32_t* __restrict__ w = words + (size_t)group * 4;
+  int y0 = w[1], x0 = w[2];
+  y0 = y0 < 0 ? 0 : (y0 > grid_h - win_h ? grid_h - win_h : y0);
+  x0 = x0 < 0 ? 0 : (x0 > grid_w - win_w ? grid_w - win_w : x0);
+  return Window{y0, x0, w[0] != 0};
+}
+
+// out[b][y][x] = g[b][y0 + y][flip ? rw - 1 - (x0 + x) : x0 + x] of the grid g that grid_map_kernel (IDENTITY: grid_identity_kernel)
+// stores: their expressions, evaluated for the window's voxels alone.  The sums stay; grid_clear_kernel runs behind it.
+// VEC: win_w is a multiple of 4, so every row of out starts 16-byte aligned and a thread stores four neighbours at once
+template <bool VEC, bool IDENTITY>
+__global__ __launch_bounds__(INGEST_THREADS) void grid_window_kernel(const int32_t* __restrict__ counts, const GridGeometry g,
+                                                                     const int32_t* __restrict__ words, int slots_per_group, int win_h,
+                                                                     int win_w, const long long* __restrict__ acc,
+                                                                     const GridStat* __restrict__ stats, float* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int s = blockIdx.y;
+  if (counts[s] < 0) return;  // INGEST_KEEP
+  const GridStat st = stats != nullptr ? stats[s] : GridStat{0.f, 1.f, 0, 0};
+  const Window win = window_of(words, s / slots_per_group, g.out_rows, g.rw, win_h, win_w);
+  const size_t src_plane = (size_t)g.src_h * g.src_w;
+  const long long* __restrict__ a = acc + (size_t)s * g.bins * src_plane;
+  float* __restrict__ o = out + (size_t)s * g.bins * win_h * win_w;
+  constexpr int PER = VEC ? 4 : 1;
+  const int64_t row_items = win_w / PER;
+  const int64_t items = (int64_t)g.bins * win_h * row_items;
+  for (int64_t i = (int64_t)blockIdx.x * INGEST_THREADS + threadIdx.x; i < items; i += (int64_t)gridDim.x * INGEST_THREADS) {
+    const int xq = (int)(i % row_items);
+    const int64_t br = i / row_items;  // bin * win_h + row
+    const int oy = win.y0 + (int)(br % win_h), b = (int)(br / win_h);
+    int y0 = oy, y1 = oy;
+    float ly0 = 1.f, ly1 = 0.f;
+    if constexpr (!IDENTITY) grid_source(g.scale_y, oy, g.in_h, y0, y1, ly0, ly1);
+    const long long* __restrict__ r0 = a + (size_t)b * src_plane + (size_t)y0 * g.src_w;
+    const long long* __restrict__ r1 = a + (size_t)b * src_plane + (size_t)y1 * g.src_w;
+    float v[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      const int wx = win.x0 + xq * PER + j;
+      const int ox = win.flip ? g.rw - 1 - wx : wx;  // (four neighbours of a flipped row: the same four of the grid, reversed)
+      if constexpr (IDENTITY) {
+        v[j] = grid_tap(r0[ox], st);
+      } else {
+        int x0, x1;
+        float lx0, lx1;
+        grid_source(g.scale_x, ox, g.src_w, x0, x1, lx0, lx1);
+        const float v00 = grid_tap(r0[x0], st), v01 = grid_tap(r0[x1], st), v10 = grid_tap(r1[x0], st), v11 = grid_tap(r1[x1], st);
+        v[j] = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
+      }
+    }
+    if constexpr (VEC) {
+      f32x4 w;
+      w[0] = v[0]; w[1] = v[1]; w[2] = v[2]; w[3] = v[3];
+      ((f32x4*)o)[i] = w;  // (item i of the slot is its i-th group of four floats)
+    } else {
+      o[i] = v[0];
+    }
+  }
+}
+
+// the label's side: nearest resize [hs][ws] -> [rh][rw] by the integer rule s = min(d * in / out, in - 1), then the same flip and
+// window; one int64 a thread
+__global__ __launch_bounds__(INGEST_THREADS) void label_window_kernel(const unsigned char* __restrict__ src, int hs, int ws, int rh, int rw,
+                                                                      const int32_t* __restrict__ words, int win_h, int win_w,
+                                                                      long long* __restrict__ out) {
+  const int s = blockIdx.y;
+  const Window win = window_of(words, s, rh, rw, win_h, win_w);
+  const unsigned char* __restrict__ a = src + (size_t)s * hs * ws;
+  long long* __restrict__ o = out + (size_t)s * win_h * win_w;
+  const int64_t items = (int64_t)win_h * win_w;
+  for (int64_t i = (int64_t)blockIdx.x * INGEST_THREADS + threadIdx.x; i < items; i += (int64_t)gridDim.x * INGEST_THREADS) {
+    const int dy = win.y0 + (int)(i / win_w);
+    const int wx = win.x0 + (int)(i % win_w);
+    const int dx = win.flip ? rw - 1 - wx : wx;
+    int64_t sy = (int64_t)dy * hs / rh, sx = (int64_t)dx * ws / rw;
+    if (sy > hs - 1) sy = hs - 1;
+    if (sx > ws - 1) sx = ws - 1;
+    o[i] = (long long)a[sy * ws + sx];
+  }
+}
+
 
 // the argument checks of the two column sources, shared by their flavours; `what` names the entry point in every message
 int check_columns(const char* what, const void* t, const void* x, const void* y, const void* p, const int32_t* counts,
@@ -892,4 +982,97 @@ extern "C" int ess_event_grid_finish(const int32_t* counts, int32_t n_slots, int
   else
     hipLaunchKernelGGL(grid_clear_kernel<false>, cgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (long long*)acc);
   return ess_launch_status("event_grid_finish(clear)");
+}
+
+// ess_event_grid_finish with the training window fused into its map pass.  The statistics launches are ess_event_grid_finish's; the
+// map computes the window's voxels alone, so some sums may have no reader: the clear always runs as a pass of its own.
+extern "C" int ess_event_grid_finish_window(const int32_t* counts, int32_t n_slots, int32_t bins, int32_t src_height, int32_t src_width,
+                                            void* acc, size_t acc_bytes, int32_t crop_rows, int32_t resize_height, int32_t resize_width,
+                                            int32_t out_rows, int32_t normalize, const int32_t* words, int32_t slots_per_group,
+                                            int32_t win_height, int32_t win_width, float* out, void* workspace, size_t workspace_bytes,
+                                            ess_stream_t stream) {
+  const char* what = "event_grid_finish_window";
+  ESS_CHECK_ARG(counts && acc && out && workspace && words, "%s: null counts, acc, out, workspace or words", what);
+  ESS_CHECK_ARG(n_slots >= 1 && n_slots <= 65535, "%s: n_slots=%d (1..65535)", what, (int)n_slots);
+  ESS_CHECK_ARG(bins > 0 && src_height > 0 && src_width > 0, "%s: bins=%d src_height=%d src_width=%d must be positive", what, (int)bins,
+                (int)src_height, (int)src_width);
+  ESS_CHECK_ARG(resize_height > 0 && resize_width > 0, "%s: resize_height=%d resize_width=%d must be positive", what, (int)resize_height,
+                (int)resize_width);
+  ESS_CHECK_ARG(crop_rows >= 1 && crop_rows <= src_height, "%s: crop_rows=%d (1..src_height=%d)", what, (int)crop_rows, (int)src_height);
+  ESS_CHECK_ARG(out_rows >= 1 && out_rows <= resize_height, "%s: out_rows=%d (1..resize_height=%d)", what, (int)out_rows,
+                (int)resize_height);
+  ESS_CHECK_ARG(normalize == GRID_NORM_NONE || normalize == GRID_NORM_UNBIASED || normalize == GRID_NORM_POPULATION,
+                "%s: normalize=%d (0 none, 1 unbiased, 2 population)", what, (int)normalize);
+  ESS_CHECK_ARG(slots_per_group >= 1, "%s: slots_per_group=%d must be positive", what, (int)slots_per_group);
+  ESS_CHECK_ARG(win_height >= 1 && win_height <= out_rows, "%s: win_height=%d (1..out_rows=%d)", what, (int)win_height, (int)out_rows);
+  ESS_CHECK_ARG(win_width >= 1 && win_width <= resize_width, "%s: win_width=%d (1..resize_width=%d)", what, (int)win_width,
+                (int)resize_width);
+  const size_t need = ess_event_ingest_workspace(n_slots, bins, src_height, src_width);
+  ESS_CHECK_ARG(acc_bytes >= need, "%s: acc has %zu bytes, %zu are needed", what, acc_bytes, need);
+  const size_t ws_need = ess_event_grid_finish_workspace(n_slots, bins, src_height, src_width);
+  ESS_CHECK_ARG(workspace_bytes >= ws_need, "%s: workspace has %zu bytes, %zu are needed", what, workspace_bytes, ws_need);
+  ESS_CHECK_ARG(((((uintptr_t)acc) | ((uintptr_t)out) | ((uintptr_t)workspace)) & 15) == 0,
+                "%s: acc, out and workspace must be 16-byte aligned", what);
+  ESS_CHECK_ARG((((uintptr_t)words) & 3) == 0, "%s: words must be 4-byte aligned", what);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t src_per = (int64_t)bins * src_height * src_width;
+  GridStat* stats = nullptr;
+  int rc;
+  if (normalize != GRID_NORM_NONE) {
+    stats = (GridStat*)workspace;
+    unsigned long long* partials = (unsigned long long*)(stats + n_slots);
+    const int blocks = grid_stats_blocks(src_per);
+    const dim3 sgrid((unsigned)blocks, (unsigned)n_slots);
+    if ((src_per & 1) == 0)
+      hipLaunchKernelGGL(grid_stats_kernel<true>, sgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (const long long*)acc, partials);
+    else
+      hipLaunchKernelGGL(grid_stats_kernel<false>, sgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (const long long*)acc, partials);
+    rc = ess_launch_status("event_grid_finish_window(statistics)");
+    if (rc) return rc;
+    hipLaunchKernelGGL(grid_stats_finalize_kernel, dim3((unsigned)ceil_div(n_slots, 64)), dim3(64), 0, st, counts, (int)n_slots, blocks,
+                       (int)normalize, (const unsigned long long*)partials, stats);
+    rc = ess_launch_status("event_grid_finish_window(finalize)");
+    if (rc) return rc;
+  }
+  const bool identity = crop_rows == src_height && resize_height == src_height && out_rows == src_height && resize_width == src_width;
+  const GridGeometry g = {bins,         src_height, src_width, crop_rows, resize_height, resize_width, out_rows,
+                          grid_scale(crop_rows, resize_height), grid_scale(src_width, resize_width)};
+  const bool vec = (win_width & 3) == 0;
+  const dim3 grid = grid_pass((int64_t)bins * win_height * (vec ? win_width >> 2 : win_width), n_slots);
+#define ESS_LAUNCH_WINDOW(VEC, IDENTITY)                                                                                          \
+  hipLaunchKernelGGL((grid_window_kernel<VEC, IDENTITY>), grid, dim3(INGEST_THREADS), 0, st, counts, g, words, (int)slots_per_group, \
+                     (int)win_height, (int)win_width, (const long long*)acc, (const GridStat*)stats, out)
+  if (vec && identity) ESS_LAUNCH_WINDOW(true, true);
+  else if (vec) ESS_LAUNCH_WINDOW(true, false);
+  else if (identity) ESS_LAUNCH_WINDOW(false, true);
+  else ESS_LAUNCH_WINDOW(false, false);
+#undef ESS_LAUNCH_WINDOW
+  rc = ess_launch_status("event_grid_finish_window(map)");
+  if (rc) return rc;
+  const bool cvec = (src_per & 1) == 0;
+  const dim3 cgrid = grid_pass(cvec ? src_per >> 1 : src_per, n_slots);
+  if (cvec)
+    hipLaunchKernelGGL(grid_clear_kernel<true>, cgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (long long*)acc);
+  else
+    hipLaunchKernelGGL(grid_clear_kernel<false>, cgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (long long*)acc);
+  return ess_launch_status("event_grid_finish_window(clear)");
+}
+
+extern "C" int ess_label_window(const uint8_t* src, int32_t n, int32_t src_height, int32_t src_width, int32_t resize_height,
+                                int32_t resize_width, const int32_t* words, int32_t win_height, int32_t win_width, int64_t* out,
+                                ess_stream_t stream) {
+  ESS_CHECK_ARG(src && words && out, "label_window: null src, words or out");
+  ESS_CHECK_ARG(n >= 1 && n <= 65535, "label_window: n=%d (1..65535)", (int)n);
+  ESS_CHECK_ARG(src_height > 0 && src_width > 0 && resize_height > 0 && resize_width > 0,
+                "label_window: src_height=%d src_width=%d resize_height=%d resize_width=%d must be positive", (int)src_height,
+                (int)src_width, (int)resize_height, (int)resize_width);
+  ESS_CHECK_ARG(win_height >= 1 && win_height <= resize_height, "label_window: win_height=%d (1..resize_height=%d)", (int)win_height,
+                (int)resize_height);
+  ESS_CHECK_ARG(win_width >= 1 && win_width <= resize_width, "label_window: win_width=%d (1..resize_width=%d)", (int)win_width,
+                (int)resize_width);
+  ESS_CHECK_ARG(((((uintptr_t)words) & 3) | (((uintptr_t)out) & 7)) == 0, "label_window: words must be 4-byte, out 8-byte aligned");
+  hipLaunchKernelGGL(label_window_kernel, grid_pass((int64_t)win_height * win_width, n), dim3(INGEST_THREADS), 0, (hipStream_t)stream,
+                     (const unsigned char*)src, (int)src_height, (int)src_width, (int)resize_height, (int)resize_width, words,
+                     (int)win_height, (int)win_width, (long long*)out);
+  return ess_launch_status("label_window");
 }

@@ -80,6 +80,7 @@ EXPORTS = [
     'ess_event_ingest_workspace', 'ess_event_ingest', 'ess_event_ingest_columns', 'ess_event_ingest_ring',
     'ess_event_ingest_columns_trilinear', 'ess_event_ingest_ring_trilinear', 'ess_seg_head_eval',
     'ess_event_scatter_ring', 'ess_event_scatter_ring_trilinear', 'ess_event_grid_finish_workspace', 'ess_event_grid_finish',
+    'ess_event_grid_finish_window', 'ess_label_window',
 ]
 
 
@@ -185,6 +186,8 @@ def lib():
             'ess_event_scatter_ring': [P, P, P, P, P, P, P, P, I64, I, I, I, I, I, P, c_size_t, P],
             'ess_event_scatter_ring_trilinear': [P, P, P, P, P, P, P, P, I64, I, I, I, I, I, P, c_size_t, P, P, I, I, I, P],
             'ess_event_grid_finish': [P, I, I, I, I, P, c_size_t, I, I, I, I, I, P, P, c_size_t, P],
+            'ess_event_grid_finish_window': [P, I, I, I, I, P, c_size_t, I, I, I, I, I, P, I, I, I, P, P, c_size_t, P],
+            'ess_label_window': [P, I, I, I, I, I, P, I, I, P, P],
         }
         for name, argtypes in sig.items():
             fn = getattr(L, name)
@@ -1171,6 +1174,101 @@ def grid_finish_workspace(n_slots, bins, Hs, Ws, device):
     """The cached buffer event_grid_finish takes its statistics from.  Every call writes what it reads of it; the tests fill it with
     0xFF bytes before a launch to prove that."""
     return workspace(lib().ess_event_grid_finish_workspace(n_slots, bins, Hs, Ws), device, 'grid_finish')
+
+
+def _window_words(fn, words, n_groups):
+    """the (flip, y0, x0, reserved) table of the training window: int32 [n_groups, 4]"""
+    if not torch.is_tensor(words):
+        raise EssHipError(f'{fn}: words must be a CUDA(HIP) tensor; there is no CPU path')
+    if words.dtype != torch.int32 or tuple(words.shape) != (n_groups, 4):
+        raise EssHipError(f'{fn}: words must be int32 [{n_groups}, 4] rows of (flip, y0, x0, reserved), got {words.dtype}{tuple(words.shape)}')
+
+
+def event_grid_finish_window(counts, acc, out, words, slots_per_group, crop_rows=None, resize=None, normalize=GRID_NORM_NONE):
+    """event_grid_finish with the loaders' training augmentation fused into its map pass: counts, acc, crop_rows, resize, normalize as
+    there; call the grid it would store g [n_slots, bins, rows, Wr] -- rows = Hr here: out's shape names the WINDOW.  out: fp32
+    [n_slots, bins, h <= Hr, w <= Wr] (returned); words: device int32 [ceil(n_slots / slots_per_group), 4] rows of (flip, y0, x0,
+    reserved), slot i reads row i // slots_per_group (the T windows of a sample share one row, and so does label_window):
+        out[i, b, y, x] = g[i, b, y0 + y, Wr - 1 - (x0 + x) if flip else x0 + x]
+    the flip first, then the crop (albumentations' order); only the window's voxels are computed.  The device reads flip as != 0 and
+    clamps y0 into [0, Hr - h] and x0 into [0, Wr - w].  The bits are event_grid_finish's followed by torch.flip and slicing; acc is
+    ALL ZERO behind the call, the sums no output read included.  No memset, no synchronisation: capturable."""
+    fn = 'event_grid_finish_window'
+    named = (('counts', counts), ('acc', acc), ('out', out), ('words', words))
+    for name, v in named:
+        if not torch.is_tensor(v):
+            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+    if acc.dim() != 4 or acc.dtype != torch.int64 or acc.numel() == 0:
+        raise EssHipError(f'{fn}: acc must be a non-empty int64 [n_slots, bins, Hs, Ws] tensor, got {acc.dtype}{tuple(acc.shape)}')
+    n_slots, bins, Hs, Ws = acc.shape
+    crop_rows = Hs if crop_rows is None else crop_rows
+    if isinstance(crop_rows, bool) or not isinstance(crop_rows, int) or not 1 <= crop_rows <= Hs:
+        raise EssHipError(f'{fn}: crop_rows={crop_rows!r} must be an int in [1, {Hs}]')
+    if resize is None:
+        resize = (crop_rows, Ws)
+    if not isinstance(resize, (tuple, list)) or len(resize) != 2 or \
+            any(isinstance(v, bool) or not isinstance(v, int) or v < 1 or v > 1 << 24 for v in resize):
+        raise EssHipError(f'{fn}: resize={resize!r} must be a pair of positive ints (Hr, Wr)')
+    Hr, Wr = resize
+    if out.dim() != 4 or out.dtype != torch.float32 or out.numel() == 0 or out.shape[0] != n_slots or out.shape[1] != bins \
+            or out.shape[2] > Hr or out.shape[3] > Wr:
+        raise EssHipError(f'{fn}: out must be fp32 [{n_slots}, {bins}, h <= {Hr}, w <= {Wr}] (the window inside the {Hr} x {Wr} grid), '
+                          f'got {out.dtype}{tuple(out.shape)}')
+    if normalize not in (GRID_NORM_NONE, GRID_NORM_UNBIASED, GRID_NORM_POPULATION) or isinstance(normalize, bool):
+        raise EssHipError(f'{fn}: normalize={normalize!r} must be GRID_NORM_NONE, GRID_NORM_UNBIASED or GRID_NORM_POPULATION')
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (n_slots,):
+        raise EssHipError(f'{fn}: counts must be int32 [{n_slots}], got {counts.dtype}{tuple(counts.shape)}')
+    if isinstance(slots_per_group, bool) or not isinstance(slots_per_group, int) or slots_per_group < 1:
+        raise EssHipError(f'{fn}: slots_per_group={slots_per_group!r} must be a positive int')
+    _window_words(fn, words, -(-n_slots // slots_per_group))
+    for name, v in named:
+        if not v.is_cuda:
+            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+        if not v.is_contiguous():
+            raise EssHipError(f'{fn}: {name} must be contiguous')
+    L = lib()
+    nbytes = L.ess_event_grid_finish_workspace(n_slots, bins, Hs, Ws)
+    ws = workspace(nbytes, out.device, 'grid_finish')
+    _check(L.ess_event_grid_finish_window(ptr(counts, torch.int32), n_slots, bins, Hs, Ws, c_void_p(acc.data_ptr()), acc.numel() * 8,
+                                          crop_rows, Hr, Wr, Hr, int(normalize), ptr(words, torch.int32), slots_per_group, out.shape[2],
+                                          out.shape[3], c_void_p(out.data_ptr()), c_void_p(ws.data_ptr()), ws.numel(), stream()),
+           'ess_event_grid_finish_window')
+    return out
+
+
+def label_window(src, out, words, resize=None):
+    """The label's side of event_grid_finish_window.  src: device uint8 [n, Hs, Ws]; resize=(Hr, Wr) (None: (Hs, Ws)): nearest resize
+    by the exact integer rule sy = min(dy * Hs // Hr, Hs - 1), sx alike; then the flip and the window of sample i's row words[i]
+    (device int32 [n, 4] = (flip, y0, x0, reserved), clamped on the device as there) -> out int64 [n, h <= Hr, w <= Wr] (returned).
+    Values pass unchanged: 255 stays 255.  The loaders resize labels with cv2.resize(INTER_NEAREST), which computes
+    floor(d * (1 / (dst / src))) in doubles; the two rules agree for every d at 440 -> 448, 640 -> 640, 346 -> 352 and 480 -> 448,
+    but parity with cv2 itself is UNPINNED (cv2 is not a dependency), as datasets/augment.py says of albumentations."""
+    fn = 'label_window'
+    named = (('src', src), ('out', out), ('words', words))
+    for name, v in named:
+        if not torch.is_tensor(v):
+            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+    if src.dim() != 3 or src.dtype != torch.uint8 or src.numel() == 0 or src.shape[0] > 65535:
+        raise EssHipError(f'{fn}: src must be a non-empty uint8 [n <= 65535, Hs, Ws] tensor, got {src.dtype}{tuple(src.shape)}')
+    n, Hs, Ws = src.shape
+    if resize is None:
+        resize = (Hs, Ws)
+    if not isinstance(resize, (tuple, list)) or len(resize) != 2 or \
+            any(isinstance(v, bool) or not isinstance(v, int) or v < 1 or v > 1 << 24 for v in resize):
+        raise EssHipError(f'{fn}: resize={resize!r} must be a pair of positive ints (Hr, Wr)')
+    Hr, Wr = resize
+    if out.dim() != 3 or out.dtype != torch.int64 or out.numel() == 0 or out.shape[0] != n or out.shape[1] > Hr or out.shape[2] > Wr:
+        raise EssHipError(f'{fn}: out must be int64 [{n}, h <= {Hr}, w <= {Wr}] (the window inside the {Hr} x {Wr} label), '
+                          f'got {out.dtype}{tuple(out.shape)}')
+    _window_words(fn, words, n)
+    for name, v in named:
+        if not v.is_cuda:
+            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+        if not v.is_contiguous():
+            raise EssHipError(f'{fn}: {name} must be contiguous')
+    _check(lib().ess_label_window(ptr(src, torch.uint8), n, Hs, Ws, Hr, Wr, ptr(words, torch.int32), out.shape[1], out.shape[2],
+                                  ptr(out, torch.int64), stream()), 'ess_label_window')
+    return out
 
 
 def voxel_normalize_(grids, mode):

@@ -533,6 +533,33 @@ int ess_event_grid_finish(const int32_t* counts, int32_t n_slots, int32_t bins, 
                           size_t acc_bytes, int32_t crop_rows, int32_t resize_height, int32_t resize_width, int32_t out_rows,
                           int32_t normalize, float* out, void* workspace, size_t workspace_bytes, ess_stream_t stream);
 
+/* Training batches from events: the loaders' augmentation where the grid is written -- PURELY ADDITIVE to ABI 110.
+ * DSEC flips horizontally with p = 0.5 (DSEC/dataset/sequence.py:291-295); DDD17 flips, then crops 120 x 216 at random inside the
+ * bottom 120 rows (datasets/ddd17_events_loader.py:87-96, 173-183).  Both are index permutations of the finished grid and of its
+ * label, driven by one table:  words: device int32 [n_groups][4] = (flip, y0, x0, reserved), drawn by the host.
+ *
+ * ess_event_grid_finish_window: ess_event_grid_finish with a sixth step.  Steps 1-5 are its own, word for word (statistics over ALL
+ * source rows, the row cuts, the fp32 align-corners blend without fused multiply-add); call the grid they store
+ * g[bins][out_rows][resize_width].  Per slot i, with (flip, y0, x0) = words[i / slots_per_group]:
+ *   6. out[b][y][x] = g[b][y0 + y][flip ? resize_width - 1 - (x0 + x) : x0 + x]      -- the flip first, then the crop --
+ * out: fp32 [n_slots][bins][win_height][win_width], 1 <= win_height <= out_rows, 1 <= win_width <= resize_width (else ESS_EINVAL).
+ * The device reads flip as != 0 and clamps y0 into [0, out_rows - win_height], x0 into [0, resize_width - win_width]: no word reads
+ * or writes outside a slot.  Only the window's voxels are computed (four neighbours a thread, one 16-byte store, where win_width is
+ * a multiple of 4).  Everything else is ess_event_grid_finish's contract: counts[i] < 0 keeps out[i] untouched, counts[i] == 0 gives
+ * zeros, acc is ALL ZERO behind the call (the sums no output read included: the clear is a pass of its own in every geometry), a
+ * slot's output is a pure function of its sums and its words, launches shaped by the sizes alone, words and counts read on the device,
+ * no synchronisation: capturable.  workspace: ess_event_grid_finish_workspace() bytes.
+ *
+ * ess_label_window: src uint8 [n][src_height][src_width] -> out int64 [n][win_height][win_width]: nearest resize to
+ * [resize_height][resize_width] by the integer rule sy = min(floor(dy * src_height / resize_height), src_height - 1) (x alike), then
+ * step 6 with sample i's row words[i] and the same clamps.  Values pass unchanged (255 stays 255).                              */
+int ess_event_grid_finish_window(const int32_t* counts, int32_t n_slots, int32_t bins, int32_t src_height, int32_t src_width, void* acc,
+                                 size_t acc_bytes, int32_t crop_rows, int32_t resize_height, int32_t resize_width, int32_t out_rows,
+                                 int32_t normalize, const int32_t* words, int32_t slots_per_group, int32_t win_height, int32_t win_width,
+                                 float* out, void* workspace, size_t workspace_bytes, ess_stream_t stream);
+int ess_label_window(const uint8_t* src, int32_t n, int32_t src_height, int32_t src_width, int32_t resize_height, int32_t resize_width,
+                     const int32_t* words, int32_t win_height, int32_t win_width, int64_t* out, ess_stream_t stream);
+
 /* ---- image-branch augmentation on the device: the geometric + photometric core of the albumentations
  * pipeline of datasets/cityscapes_loader.py:39-74 (HorizontalFlip, ShiftScaleRotate with rotate 0 and a constant-0 border,
  * centred PadIfNeeded, RandomCrop, GaussNoise, RandomBrightnessContrast), uint8 quantisation, ToTensor (/255), and for the label
