@@ -3,7 +3,13 @@
 // -> the round's voxel grids, with a sum that does not depend on the order the events arrive in (include/ess_hip.h).  The sources
 // differ in how an event is LOADED; what an event adds is one function per FLAVOUR: scatter_event (temporal: integer pixels, bilinear
 // in time) for all three sources, scatter_event_trilinear (the DSEC grid: rectified float coordinates, eight corners) for the column
-// and the ring source, whose kernels are templates on the flavour -- the loading code is one piece of text per source.
+// and the ring source, which share ONE loader, event_scatter_columns_kernel<Flavour, RING>: a template on the flavour and on whether
+// a window lies at the head of its row or anywhere inside a ring.
+//
+// Behind the scatter, one kernel per job: event_finish_kernel<VEC, TAP> turns sums into a grid and zeroes them where each sum has
+// one reader -- the plain ingest (TAP false) and the loader finish at the identity geometry (TAP true); grid_map_kernel<VEC,
+// IDENTITY, WINDOW> is the loader finish's crop / resize pass, with or without the training window.  One routine checks the
+// arguments of every source's entry points (check_source), one drives both loader finishes (grid_finish).
 //
 // voxel_temporal_kernel (voxel.hip) adds its fp32 contributions with fp32 global atomics: a voxel's value depends on which event
 // got there first, two builds of one window differ in the last bits.  Here every contribution is the SAME fp32 value (the same
@@ -208,70 +214,36 @@ struct TrilinearFlavour {
   }
 };
 
-template <class Flavour, class... Extra>
+// ---- the ring source (RING): the same four columns, [n_rows][ring], as per-stream RINGS that packets are appended to as they
+// arrive.  A slot's window is counts[i] events of row rows[i] from position starts[i] on, modulo ring; all four words are device
+// words.  A start is no multiple of COLUMN_GROUP, so a lane walks the aligned groups from starts - starts % COLUMN_GROUP on and masks
+// the head of the first and the tail of the last: the loads stay 2 x 16 B, 8 B, 8 B, 4 B.  ring is a multiple of
+// COLUMN_STRIDE_ALIGN, so no group straddles the wrap and the wrap falls between two groups; a full ring from an unaligned start
+// reads its first group twice, once under each mask.
+// The column source is the ring source with slot s's window at the head of row s -- rows, starts and n_rows are not read, nothing
+// wraps, no head is masked -- and `ring` its stride: one loader serves both.
+template <class Flavour, bool RING, class... Extra>
 __global__ __launch_bounds__(INGEST_THREADS) void event_scatter_columns_kernel(const long long* __restrict__ t, const unsigned short* __restrict__ x,
                                                                                const unsigned short* __restrict__ y,
                                                                                const unsigned char* __restrict__ p,
+                                                                               const int32_t* __restrict__ rows, const int32_t* __restrict__ starts,
                                                                                const int32_t* __restrict__ counts,
-                                                                               const int32_t* __restrict__ formats, int64_t stride, int nb, int H,
-                                                                               int W, long long* __restrict__ acc, const Extra... extra) {
+                                                                               const int32_t* __restrict__ formats, int64_t ring, int n_rows,
+                                                                               int nb, int H, int W, long long* __restrict__ acc,
+                                                                               const Extra... extra) {
 #pragma clang fp contract(off)
   const int s = blockIdx.y;
   const int cnt = counts[s];
-  const int fmt = formats[s];  // (read beside the count, not behind the test on it: the two scalar loads issue together)
-  if (cnt <= 0) return;  // an empty window, or INGEST_KEEP: nothing of this stream's columns is read
-  if ((fmt & ~(EVCOL_T_I64 | EVCOL_XY_U16)) != 0) return;  // an unknown format: as count 0
-  Flavour f;
-  if (!f.open(s, extra...)) return;
-  const bool t_i64 = (fmt & EVCOL_T_I64) != 0, xy_u16 = (fmt & EVCOL_XY_U16) != 0;
-  const int64_t n = (int64_t)cnt < stride ? (int64_t)cnt : stride;
-  const size_t row = (size_t)s * stride;
-  const long long* __restrict__ ts = t + row;
-  f.window(ts[0], ts[n - 1], t_i64, nb);
-  const size_t plane = (size_t)H * W;
-  long long* __restrict__ g = acc + (size_t)s * nb * plane;
-  const i64x2* __restrict__ t2 = (const i64x2*)ts;               // two events
-  const uint2* __restrict__ x4 = (const uint2*)(x + row);        // COLUMN_GROUP events
-  const uint2* __restrict__ y4 = (const uint2*)(y + row);
-  const unsigned* __restrict__ p4 = (const unsigned*)(p + row);
-  const int64_t groups = (n + COLUMN_GROUP - 1) / COLUMN_GROUP;  // (the last one may be partial: 4 * q + 3 < stride all the same)
-  for (int64_t q = (int64_t)blockIdx.x * INGEST_THREADS + threadIdx.x; q < groups; q += (int64_t)gridDim.x * INGEST_THREADS) {
-    const i64x2 ta = t2[2 * q], tb = t2[2 * q + 1];
-    const uint2 xv = x4[q], yv = y4[q];
-    const unsigned pv = p4[q];
-    const long long tw[COLUMN_GROUP] = {ta[0], ta[1], tb[0], tb[1]};
-    const unsigned xh[COLUMN_GROUP] = {xv.x & 0xffffu, xv.x >> 16, xv.y & 0xffffu, xv.y >> 16};
-    const unsigned yh[COLUMN_GROUP] = {yv.x & 0xffffu, yv.x >> 16, yv.y & 0xffffu, yv.y >> 16};
-#pragma unroll
-    for (int j = 0; j < COLUMN_GROUP; ++j) {
-      if (q * COLUMN_GROUP + j >= n) break;  // (the tail: loaded, inside the stride, never summed)
-      f.add(tw[j], xh[j], yh[j], (int)((pv >> (8 * j)) & 0xffu), t_i64, xy_u16, nb, H, W, plane, g);
-    }
+  const int fmt = formats[s];  // (read beside the count, not behind the test on it, like rows and starts: the scalar loads issue together)
+  int r = s, start = 0;
+  if constexpr (RING) {
+    r = rows[s];
+    start = starts[s];
   }
-}
-
-// ---- the ring source: the same four columns, [n_rows][ring], as per-stream RINGS that packets are appended to as they arrive.  A
-// slot's window is counts[i] events of row rows[i] from position starts[i] on, modulo ring; all four words are device words.  A start
-// is no multiple of COLUMN_GROUP, so a lane walks the aligned groups from starts - starts % COLUMN_GROUP on and masks the head of the
-// first and the tail of the last: the loads stay 2 x 16 B, 8 B, 8 B, 4 B.  ring is a multiple of COLUMN_STRIDE_ALIGN, so no group
-// straddles the wrap and the wrap falls between two groups; a full ring from an unaligned start reads its first group twice, once
-// under each mask.
-template <class Flavour, class... Extra>
-__global__ __launch_bounds__(INGEST_THREADS) void event_scatter_ring_kernel(const long long* __restrict__ t, const unsigned short* __restrict__ x,
-                                                                            const unsigned short* __restrict__ y,
-                                                                            const unsigned char* __restrict__ p,
-                                                                            const int32_t* __restrict__ rows, const int32_t* __restrict__ starts,
-                                                                            const int32_t* __restrict__ counts,
-                                                                            const int32_t* __restrict__ formats, int64_t ring, int n_rows,
-                                                                            int nb, int H, int W, long long* __restrict__ acc,
-                                                                            const Extra... extra) {
-#pragma clang fp contract(off)
-  const int s = blockIdx.y;
-  const int cnt = counts[s];
-  const int fmt = formats[s], r = rows[s], start = starts[s];  // (read beside the count: the four scalar loads issue together)
   if (cnt <= 0) return;  // an empty window, or INGEST_KEEP: nothing is read for this slot
   if ((fmt & ~(EVCOL_T_I64 | EVCOL_XY_U16)) != 0) return;  // an unknown format: as count 0
-  if (r < 0 || r >= n_rows || start < 0 || (int64_t)start >= ring) return;  // a row or a start outside the rings: as count 0
+  if constexpr (RING)
+    if (r < 0 || r >= n_rows || start < 0 || (int64_t)start >= ring) return;  // a row or a start outside the rings: as count 0
   Flavour f;
   if (!f.open(s, extra...)) return;
   const bool t_i64 = (fmt & EVCOL_T_I64) != 0, xy_u16 = (fmt & EVCOL_XY_U16) != 0;
@@ -279,19 +251,21 @@ __global__ __launch_bounds__(INGEST_THREADS) void event_scatter_ring_kernel(cons
   const size_t row = (size_t)r * ring;
   const long long* __restrict__ ts = t + row;
   int64_t last_at = (int64_t)start + n - 1;  // (< 2 * ring)
-  if (last_at >= ring) last_at -= ring;
+  if constexpr (RING)
+    if (last_at >= ring) last_at -= ring;
   f.window(ts[start], ts[last_at], t_i64, nb);
   const size_t plane = (size_t)H * W;
   long long* __restrict__ g = acc + (size_t)s * nb * plane;
-  const i64x2* __restrict__ t2 = (const i64x2*)ts;
-  const uint2* __restrict__ x4 = (const uint2*)(x + row);
+  const i64x2* __restrict__ t2 = (const i64x2*)ts;               // two events
+  const uint2* __restrict__ x4 = (const uint2*)(x + row);        // COLUMN_GROUP events
   const uint2* __restrict__ y4 = (const uint2*)(y + row);
   const unsigned* __restrict__ p4 = (const unsigned*)(p + row);
   const int64_t head = start % COLUMN_GROUP, group0 = start / COLUMN_GROUP, ring_groups = ring / COLUMN_GROUP;
-  const int64_t groups = (head + n + COLUMN_GROUP - 1) / COLUMN_GROUP;  // (<= ring_groups + 1)
+  const int64_t groups = (head + n + COLUMN_GROUP - 1) / COLUMN_GROUP;  // (<= ring_groups + 1; the last one may be partial)
   for (int64_t q = (int64_t)blockIdx.x * INGEST_THREADS + threadIdx.x; q < groups; q += (int64_t)gridDim.x * INGEST_THREADS) {
     int64_t at = group0 + q;  // (< 2 * ring_groups: one subtraction wraps it; every group lies inside the row)
-    if (at >= ring_groups) at -= ring_groups;
+    if constexpr (RING)
+      if (at >= ring_groups) at -= ring_groups;
     const i64x2 ta = t2[2 * at], tb = t2[2 * at + 1];
     const uint2 xv = x4[at], yv = y4[at];
     const unsigned pv = p4[at];
@@ -309,55 +283,22 @@ __global__ __launch_bounds__(INGEST_THREADS) void event_scatter_ring_kernel(cons
 
 __device__ __forceinline__ float dequantise(long long a) { return (float)a * INGEST_INV_SCALE; }
 
-// VEC: per_stream is a multiple of 4, so every stream's acc / out rows start 16-byte aligned
-template <bool VEC>
-__global__ __launch_bounds__(INGEST_THREADS) void event_finish_kernel(const int32_t* __restrict__ counts, int64_t per_stream,
-                                                                      long long* __restrict__ acc, float* __restrict__ out) {
-  const int s = blockIdx.y;
-  if (counts[s] < 0) return;  // INGEST_KEEP: the grid already in `out` is the caller's; acc of this stream is zero and stays so
-  long long* __restrict__ a = acc + (size_t)s * per_stream;
-  float* __restrict__ o = out + (size_t)s * per_stream;
-  const int64_t stride = (int64_t)gridDim.x * INGEST_THREADS;
-  const int64_t i0 = (int64_t)blockIdx.x * INGEST_THREADS + threadIdx.x;
-  if constexpr (VEC) {
-    i64x2* __restrict__ a2 = (i64x2*)a;
-    f32x4* __restrict__ o4 = (f32x4*)o;
-    const i64x2 z = {0, 0};
-    for (int64_t i = i0; i < (per_stream >> 2); i += stride) {
-      const i64x2 lo = a2[2 * i], hi = a2[2 * i + 1];
-      f32x4 v;
-      v[0] = dequantise(lo[0]); v[1] = dequantise(lo[1]); v[2] = dequantise(hi[0]); v[3] = dequantise(hi[1]);
-      o4[i] = v;
-      if ((lo[0] | lo[1]) != 0) a2[2 * i] = z;
-      if ((hi[0] | hi[1]) != 0) a2[2 * i + 1] = z;
-    }
-  } else {
-    for (int64_t i = i0; i < per_stream; i += stride) {
-      const long long v = a[i];
-      o[i] = dequantise(v);
-      if (v != 0) a[i] = 0;
-    }
-  }
-}
-
 // the scatter grid: from the capacity alone (a captured launch), INGEST_EVENTS_PER_THREAD events a thread at full capacity
 unsigned scatter_blocks(int64_t capacity) {
   const int64_t bx = ceil_div64(capacity, (int64_t)INGEST_THREADS * INGEST_EVENTS_PER_THREAD);
   return (unsigned)(bx > INGEST_MAX_BLOCKS_X ? INGEST_MAX_BLOCKS_X : bx);
 }
 
-int launch_finish(const int32_t* counts, int32_t n_streams, int32_t bins, int32_t height, int32_t width, void* acc, float* out, hipStream_t st,
-                  const char* what) {
-  const int64_t per = (int64_t)bins * height * width;
-  const bool vec = (per & 3) == 0;
-  int64_t fx = ceil_div64(vec ? per >> 2 : per, (int64_t)INGEST_THREADS * INGEST_QUADS_PER_THREAD);
-  if (fx > INGEST_MAX_BLOCKS_X) fx = INGEST_MAX_BLOCKS_X;
-  const dim3 fgrid((unsigned)fx, (unsigned)n_streams);
-  if (vec)
-    hipLaunchKernelGGL(event_finish_kernel<true>, fgrid, dim3(INGEST_THREADS), 0, st, counts, per, (long long*)acc, out);
-  else
-    hipLaunchKernelGGL(event_finish_kernel<false>, fgrid, dim3(INGEST_THREADS), 0, st, counts, per, (long long*)acc, out);
-  return ess_launch_status(what);
+// one launch for the column (RING false: rows, starts null, n_rows unused) and the ring source, in either flavour
+template <class Flavour, bool RING, class... Extra>
+int launch_scatter(const char* status, const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
+                   const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots, int32_t bins, int32_t height,
+                   int32_t width, void* acc, hipStream_t st, const Extra... extra) {
+  hipLaunchKernelGGL((event_scatter_columns_kernel<Flavour, RING, Extra...>), dim3(scatter_blocks(ring), (unsigned)n_slots),
+                     dim3(INGEST_THREADS), 0, st, (const long long*)t, (const unsigned short*)x, (const unsigned short*)y,
+                     (const unsigned char*)p, rows, starts, counts, formats, ring, (int)n_rows, (int)bins, (int)height, (int)width,
+                     (long long*)acc, extra...);
+  return ess_launch_status(status);
 }
 
 // ---- the loader finish (ess_event_grid_finish): what the reference loaders do to a grid between voxelising it and handing it to
@@ -373,7 +314,8 @@ int launch_finish(const int32_t* counts, int32_t n_streams, int32_t bins, int32_
 //     atomic, no memset in front) -> the slot's GridStat: voxel_apply_kernel's (voxel.hip) case analysis and fp32 expressions.
 //   grid_map_kernel: every output voxel reads its <= 4 taps of acc, dequantises and normalises each, blends.  Several outputs read
 //     one sum, so the sums are cleared behind it by grid_clear_kernel -- but for the identity geometry, where each sum has one
-//     reader: grid_identity_kernel maps and clears like event_finish_kernel, and gives its bits where nothing is normalised.
+//     reader: event_finish_kernel<VEC, TAP = true> maps and clears in one pass, with a tap where the plain ingest (TAP = false)
+//     dequantises, and gives the plain ingest's bits where nothing is normalised.
 constexpr int GRID_NORM_NONE = 0, GRID_NORM_UNBIASED = 1, GRID_NORM_POPULATION = 2;  // (ESS_GRID_NORM_* of include/ess_hip.h)
 constexpr int GRID_STATS_MAX_BLOCKS = 64;
 constexpr int GRID_STATS_PER_THREAD = 16;  // voxels a thread of the statistics pass walks before the block cap widens it
@@ -514,49 +456,6 @@ __device__ __forceinline__ void grid_source(float scale, int d, int in, int& i0,
   l0 = 1.f - l1;
 }
 
-// VEC: rw is a multiple of 4, so every row of out starts 16-byte aligned and a thread stores four neighbours at once
-template <bool VEC>
-__global__ __launch_bounds__(INGEST_THREADS) void grid_map_kernel(const int32_t* __restrict__ counts, const GridGeometry g,
-                                                                  const long long* __restrict__ acc, const GridStat* __restrict__ stats,
-                                                                  float* __restrict__ out) {
-#pragma clang fp contract(off)
-  const int s = blockIdx.y;
-  if (counts[s] < 0) return;  // INGEST_KEEP
-  const GridStat st = stats != nullptr ? stats[s] : GridStat{0.f, 1.f, 0, 0};
-  const size_t src_plane = (size_t)g.src_h * g.src_w;
-  const long long* __restrict__ a = acc + (size_t)s * g.bins * src_plane;
-  float* __restrict__ o = out + (size_t)s * g.bins * g.out_rows * g.rw;
-  constexpr int PER = VEC ? 4 : 1;
-  const int64_t row_items = g.rw / PER;
-  const int64_t items = (int64_t)g.bins * g.out_rows * row_items;
-  for (int64_t i = (int64_t)blockIdx.x * INGEST_THREADS + threadIdx.x; i < items; i += (int64_t)gridDim.x * INGEST_THREADS) {
-    const int xq = (int)(i % row_items);
-    const int64_t br = i / row_items;  // bin * out_rows + row
-    const int oy = (int)(br % g.out_rows), b = (int)(br / g.out_rows);
-    int y0, y1;
-    float ly0, ly1;
-    grid_source(g.scale_y, oy, g.in_h, y0, y1, ly0, ly1);
-    const long long* __restrict__ r0 = a + (size_t)b * src_plane + (size_t)y0 * g.src_w;
-    const long long* __restrict__ r1 = a + (size_t)b * src_plane + (size_t)y1 * g.src_w;
-    float v[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      int x0, x1;
-      float lx0, lx1;
-      grid_source(g.scale_x, xq * PER + j, g.src_w, x0, x1, lx0, lx1);
-      const float v00 = grid_tap(r0[x0], st), v01 = grid_tap(r0[x1], st), v10 = grid_tap(r1[x0], st), v11 = grid_tap(r1[x1], st);
-      v[j] = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
-    }
-    if constexpr (VEC) {
-      f32x4 w;
-      w[0] = v[0]; w[1] = v[1]; w[2] = v[2]; w[3] = v[3];
-      ((f32x4*)o)[i] = w;  // (item i of the slot is its i-th group of four floats)
-    } else {
-      o[i] = v[0];
-    }
-  }
-}
-
 // zeros where a sum was; VEC: src_per is even
 template <bool VEC>
 __global__ __launch_bounds__(INGEST_THREADS) void grid_clear_kernel(const int32_t* __restrict__ counts, int64_t src_per,
@@ -579,14 +478,20 @@ __global__ __launch_bounds__(INGEST_THREADS) void grid_clear_kernel(const int32_
   }
 }
 
-// the identity geometry: event_finish_kernel with a tap in place of the plain dequantisation (the same bits where st.active == 0)
-template <bool VEC>
-__global__ __launch_bounds__(INGEST_THREADS) void grid_identity_kernel(const int32_t* __restrict__ counts, int64_t per_stream,
-                                                                       long long* __restrict__ acc, const GridStat* __restrict__ stats,
-                                                                       float* __restrict__ out) {
+// The finish of a slot whose every sum has one reader: out = the sum dequantised (the plain ingest) or, TAP, tapped (the loader
+// finish at the identity geometry: the same bits where st.active == 0), and zeros stored back where a sum was.  stats is read only
+// under TAP.  VEC: per_stream is a multiple of 4, so every stream's acc / out rows start 16-byte aligned
+template <bool VEC, bool TAP>
+__global__ __launch_bounds__(INGEST_THREADS) void event_finish_kernel(const int32_t* __restrict__ counts, int64_t per_stream,
+                                                                      long long* __restrict__ acc, float* __restrict__ out,
+                                                                      const GridStat* __restrict__ stats) {
   const int s = blockIdx.y;
-  if (counts[s] < 0) return;  // INGEST_KEEP
-  const GridStat st = stats != nullptr ? stats[s] : GridStat{0.f, 1.f, 0, 0};
+  if (counts[s] < 0) return;  // INGEST_KEEP: the grid already in `out` is the caller's; acc of this stream is zero and stays so
+  const GridStat st = TAP && stats != nullptr ? stats[s] : GridStat{0.f, 1.f, 0, 0};
+  auto value = [&](long long q) {
+    if constexpr (TAP) return grid_tap(q, st);
+    else return dequantise(q);
+  };
   long long* __restrict__ a = acc + (size_t)s * per_stream;
   float* __restrict__ o = out + (size_t)s * per_stream;
   const int64_t stride = (int64_t)gridDim.x * INGEST_THREADS;
@@ -598,7 +503,7 @@ __global__ __launch_bounds__(INGEST_THREADS) void grid_identity_kernel(const int
     for (int64_t i = i0; i < (per_stream >> 2); i += stride) {
       const i64x2 lo = a2[2 * i], hi = a2[2 * i + 1];
       f32x4 v;
-      v[0] = grid_tap(lo[0], st); v[1] = grid_tap(lo[1], st); v[2] = grid_tap(hi[0], st); v[3] = grid_tap(hi[1], st);
+      v[0] = value(lo[0]); v[1] = value(lo[1]); v[2] = value(hi[0]); v[3] = value(hi[1]);
       o4[i] = v;
       if ((lo[0] | lo[1]) != 0) a2[2 * i] = z;
       if ((hi[0] | hi[1]) != 0) a2[2 * i + 1] = z;
@@ -606,7 +511,7 @@ __global__ __launch_bounds__(INGEST_THREADS) void grid_identity_kernel(const int
   } else {
     for (int64_t i = i0; i < per_stream; i += stride) {
       const long long q = a[i];
-      o[i] = grid_tap(q, st);
+      o[i] = value(q);
       if (q != 0) a[i] = 0;
     }
   }
@@ -617,6 +522,25 @@ dim3 grid_pass(int64_t items, int32_t n_slots) {
   int64_t bx = ceil_div64(items, (int64_t)INGEST_THREADS * INGEST_QUADS_PER_THREAD);
   if (bx > INGEST_MAX_BLOCKS_X) bx = INGEST_MAX_BLOCKS_X;
   return dim3((unsigned)bx, (unsigned)n_slots);
+}
+
+// the status of the launch in front, named "<entry point>(<stage>)" (the name is put together only for a launch that failed)
+int stage_status(const char* what, const char* stage) {
+  if (hipPeekAtLastError() == hipSuccess) return ESS_OK;
+  char name[64];
+  snprintf(name, sizeof name, "%s(%s)", what, stage);
+  return ess_launch_status(name);
+}
+
+// TAP false: the plain ingest's finish (stats unused);  true: the loader finish at the identity geometry (stats null: nothing normalised)
+template <bool TAP>
+void launch_finish(const int32_t* counts, int32_t n_slots, int64_t per, void* acc, const GridStat* stats, float* out, hipStream_t st) {
+  const bool vec = (per & 3) == 0;
+  const dim3 grid = grid_pass(vec ? per >> 2 : per, n_slots);
+  if (vec)
+    hipLaunchKernelGGL((event_finish_kernel<true, TAP>), grid, dim3(INGEST_THREADS), 0, st, counts, per, (long long*)acc, out, stats);
+  else
+    hipLaunchKernelGGL((event_finish_kernel<false, TAP>), grid, dim3(INGEST_THREADS), 0, st, counts, per, (long long*)acc, out, stats);
 }
 
 // torch's area_pixel_compute_scale<float>(in, out, align_corners=true)
@@ -638,19 +562,29 @@ __device__ __forceinline__ Window window_of(const int32_t* __restrict__ words, i
   return Window{y0, x0, w[0] != 0};
 }
 
-// out[b][y][x] = g[b][y0 + y][flip ? rw - 1 - (x0 + x) : x0 + x] of the grid g that grid_map_kernel (IDENTITY: grid_identity_kernel)
-// stores: their expressions, evaluated for the window's voxels alone.  The sums stay; grid_clear_kernel runs behind it.
+// The map pass of the loader finish.  Call g [bins][out_rows][rw] the loader's grid: every voxel reads its <= 4 taps of acc (IDENTITY,
+// no crop and no resize: its one sum), dequantises and normalises each, blends.  WINDOW: out[b][y][x] =
+// g[b][y0 + y][flip ? rw - 1 - (x0 + x) : x0 + x], the same expressions evaluated for the window's voxels alone; else the window is
+// the whole grid, unflipped, and words .. win_width are not read (the identity geometry then goes to event_finish_kernel: each sum
+// has one reader).  The sums stay; grid_clear_kernel runs behind it.
 // VEC: win_w is a multiple of 4, so every row of out starts 16-byte aligned and a thread stores four neighbours at once
-template <bool VEC, bool IDENTITY>
-__global__ __launch_bounds__(INGEST_THREADS) void grid_window_kernel(const int32_t* __restrict__ counts, const GridGeometry g,
-                                                                     const int32_t* __restrict__ words, int slots_per_group, int win_h,
-                                                                     int win_w, const long long* __restrict__ acc,
-                                                                     const GridStat* __restrict__ stats, float* __restrict__ out) {
+template <bool VEC, bool IDENTITY, bool WINDOW>
+__global__ __launch_bounds__(INGEST_THREADS) void grid_map_kernel(const int32_t* __restrict__ counts, const GridGeometry g,
+                                                                  const int32_t* __restrict__ words, int slots_per_group, int win_height,
+                                                                  int win_width, const long long* __restrict__ acc,
+                                                                  const GridStat* __restrict__ stats, float* __restrict__ out) {
 #pragma clang fp contract(off)
+  static_assert(WINDOW || !IDENTITY, "the identity geometry without a window is event_finish_kernel's");
   const int s = blockIdx.y;
   if (counts[s] < 0) return;  // INGEST_KEEP
   const GridStat st = stats != nullptr ? stats[s] : GridStat{0.f, 1.f, 0, 0};
-  const Window win = window_of(words, s / slots_per_group, g.out_rows, g.rw, win_h, win_w);
+  int win_h = g.out_rows, win_w = g.rw;
+  Window win = {0, 0, false};
+  if constexpr (WINDOW) {
+    win_h = win_height;
+    win_w = win_width;
+    win = window_of(words, s / slots_per_group, g.out_rows, g.rw, win_h, win_w);
+  }
   const size_t src_plane = (size_t)g.src_h * g.src_w;
   const long long* __restrict__ a = acc + (size_t)s * g.bins * src_plane;
   float* __restrict__ o = out + (size_t)s * g.bins * win_h * win_w;
@@ -713,49 +647,58 @@ __global__ __launch_bounds__(INGEST_THREADS) void label_window_kernel(const unsi
 }
 
 
-// the argument checks of the two column sources, shared by their flavours; `what` names the entry point in every message
+// ---- the argument checks.  The three sources' entry points check one list; SourceNames holds the words their messages differ in,
+// `what` names the entry point in every message.
+struct SourceNames {
+  const char* pointers;      // the source's own pointers, as the null message lists them
+  const char* aligned;       // those of them that must be 16-byte aligned
+  const char* n_name;        // how many grids the call fills
+  const char* span_name;     // the events a row holds ...
+  const char* span_unit;     // ... per what ...
+  int span_low;              // ... and the least value the message names
+  const char* multiple_why;  // why the span is a multiple of COLUMN_STRIDE_ALIGN; nullptr: it need not be
+};
+static_assert(COLUMN_STRIDE_ALIGN == 16 && COLUMN_GROUP == 4, "the texts below name them");
+constexpr SourceNames SOURCE_RECORDS = {"records, counts", "records", "n_streams", "capacity", "stream", 1, nullptr};
+constexpr SourceNames SOURCE_COLUMNS = {"t, x, y, p, counts, formats", "t, x, y, p", "n_streams", "stride", "stream", 1,
+                                        "every stream's row of every column starts 16-byte aligned"};
+constexpr SourceNames SOURCE_RING = {"t, x, y, p, rows, starts, counts, formats", "t, x, y, p", "n_slots", "ring", "row", 16,
+                                     "every row of every column starts 16-byte aligned, no group of 4 events straddles the wrap"};
+
+// given: none of the source's own pointers is null;  addresses: those that must be aligned, or-ed;  n_rows: 1 but for the rings;
+// with_out false: the scatter-only entry points, which have no out
+int check_source(const char* what, const SourceNames& k, bool given, uintptr_t addresses, int64_t span, int32_t n_rows, int32_t n,
+                 int32_t bins, int32_t height, int32_t width, const void* acc, size_t acc_bytes, const float* out, bool with_out = true) {
+  ESS_CHECK_ARG(given && acc && (out || !with_out), "%s: null %s%s", what, k.pointers, with_out ? ", acc or out" : " or acc");
+  ESS_CHECK_ARG(n >= 1 && n <= 65535, "%s: %s=%d (1..65535)", what, k.n_name, (int)n);
+  ESS_CHECK_ARG(n_rows >= 1, "%s: n_rows=%d must be positive", what, (int)n_rows);
+  ESS_CHECK_ARG(bins > 0 && height > 0 && width > 0, "%s: bins=%d height=%d width=%d must be positive", what, (int)bins, (int)height,
+                (int)width);
+  ESS_CHECK_ARG(span >= 1 && span <= INGEST_MAX_CAPACITY,
+                "%s: %s=%lld events per %s (%d..%lld: the int64 sums hold 2^22 contributions of magnitude 1 at scale 2^40)", what,
+                k.span_name, (long long)span, k.span_unit, k.span_low, (long long)INGEST_MAX_CAPACITY);
+  ESS_CHECK_ARG(k.multiple_why == nullptr || span % COLUMN_STRIDE_ALIGN == 0, "%s: %s=%lld must be a multiple of %d (%s)", what,
+                k.span_name, (long long)span, COLUMN_STRIDE_ALIGN, k.multiple_why);
+  const size_t need = ess_event_ingest_workspace(n, bins, height, width);
+  ESS_CHECK_ARG(acc_bytes >= need, "%s: acc has %zu bytes, %zu are needed", what, acc_bytes, need);
+  ESS_CHECK_ARG(((addresses | (uintptr_t)acc | (uintptr_t)out) & 15) == 0, "%s: %s, acc%s must be 16-byte aligned", what, k.aligned,
+                with_out ? " and out" : "");
+  return ESS_OK;
+}
+
 int check_columns(const char* what, const void* t, const void* x, const void* y, const void* p, const int32_t* counts,
                   const int32_t* formats, int64_t stride, int32_t n_streams, int32_t bins, int32_t height, int32_t width, const void* acc,
                   size_t acc_bytes, const float* out) {
-  ESS_CHECK_ARG(t && x && y && p && counts && formats && acc && out, "%s: null t, x, y, p, counts, formats, acc or out", what);
-  ESS_CHECK_ARG(n_streams >= 1 && n_streams <= 65535, "%s: n_streams=%d (1..65535)", what, (int)n_streams);
-  ESS_CHECK_ARG(bins > 0 && height > 0 && width > 0, "%s: bins=%d height=%d width=%d must be positive", what, (int)bins, (int)height,
-                (int)width);
-  ESS_CHECK_ARG(stride >= 1 && stride <= INGEST_MAX_CAPACITY,
-                "%s: stride=%lld events per stream (1..%lld: the int64 sums hold 2^22 contributions of magnitude 1 at scale 2^40)", what,
-                (long long)stride, (long long)INGEST_MAX_CAPACITY);
-  ESS_CHECK_ARG(stride % COLUMN_STRIDE_ALIGN == 0,
-                "%s: stride=%lld must be a multiple of %d (every stream's row of every column starts 16-byte aligned)", what,
-                (long long)stride, COLUMN_STRIDE_ALIGN);
-  const size_t need = ess_event_ingest_workspace(n_streams, bins, height, width);
-  ESS_CHECK_ARG(acc_bytes >= need, "%s: acc has %zu bytes, %zu are needed", what, acc_bytes, need);
-  ESS_CHECK_ARG(((((uintptr_t)t) | ((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)p) | ((uintptr_t)acc) | ((uintptr_t)out)) & 15) == 0,
-                "%s: t, x, y, p, acc and out must be 16-byte aligned", what);
-  return ESS_OK;
+  return check_source(what, SOURCE_COLUMNS, t && x && y && p && counts && formats, (uintptr_t)t | (uintptr_t)x | (uintptr_t)y | (uintptr_t)p,
+                      stride, 1, n_streams, bins, height, width, acc, acc_bytes, out);
 }
 
 int check_ring(const char* what, const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
                const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots, int32_t bins, int32_t height,
                int32_t width, const void* acc, size_t acc_bytes, const float* out, bool with_out = true) {
-  // (with_out false: the scatter-only entry points, which have no out)
-  ESS_CHECK_ARG(t && x && y && p && rows && starts && counts && formats && acc && (out || !with_out),
-                "%s: null t, x, y, p, rows, starts, counts, formats%s", what, with_out ? ", acc or out" : " or acc");
-  ESS_CHECK_ARG(n_slots >= 1 && n_slots <= 65535, "%s: n_slots=%d (1..65535)", what, (int)n_slots);
-  ESS_CHECK_ARG(n_rows >= 1, "%s: n_rows=%d must be positive", what, (int)n_rows);
-  ESS_CHECK_ARG(bins > 0 && height > 0 && width > 0, "%s: bins=%d height=%d width=%d must be positive", what, (int)bins, (int)height,
-                (int)width);
-  ESS_CHECK_ARG(ring >= 1 && ring <= INGEST_MAX_CAPACITY,
-                "%s: ring=%lld events per row (16..%lld: the int64 sums hold 2^22 contributions of magnitude 1 at scale 2^40)", what,
-                (long long)ring, (long long)INGEST_MAX_CAPACITY);
-  ESS_CHECK_ARG(ring % COLUMN_STRIDE_ALIGN == 0,
-                "%s: ring=%lld must be a multiple of %d (every row of every column starts 16-byte aligned, no group of %d "
-                "events straddles the wrap)",
-                what, (long long)ring, COLUMN_STRIDE_ALIGN, COLUMN_GROUP);
-  const size_t need = ess_event_ingest_workspace(n_slots, bins, height, width);
-  ESS_CHECK_ARG(acc_bytes >= need, "%s: acc has %zu bytes, %zu are needed", what, acc_bytes, need);
-  ESS_CHECK_ARG(((((uintptr_t)t) | ((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)p) | ((uintptr_t)acc) | ((uintptr_t)out)) & 15) == 0,
-                "%s: t, x, y, p, acc%s must be 16-byte aligned", what, with_out ? " and out" : "");
-  return ESS_OK;
+  return check_source(what, SOURCE_RING, t && x && y && p && rows && starts && counts && formats,
+                      (uintptr_t)t | (uintptr_t)x | (uintptr_t)y | (uintptr_t)p, ring, n_rows, n_slots, bins, height, width, acc, acc_bytes,
+                      out, with_out);
 }
 
 // the rectify arguments of the trilinear flavour -> the kernels' Rectify
@@ -773,6 +716,94 @@ int check_rectify(const char* what, const float* maps, const int32_t* map_of, in
   return ESS_OK;
 }
 
+// the training window's arguments of ess_event_grid_finish_window
+struct WindowArgs {
+  const int32_t* words;
+  int32_t slots_per_group, win_height, win_width;
+};
+
+// The loader finish behind ess_event_grid_finish (win null) and ess_event_grid_finish_window: the checks, the statistics, the map --
+// event_finish_kernel where every sum has one reader, else grid_map_kernel and the clear as a pass of its own.  With a window the
+// map computes the window's voxels alone, so some sums may have no reader: the clear always runs.
+int grid_finish(const char* what, const int32_t* counts, int32_t n_slots, int32_t bins, int32_t src_height, int32_t src_width, void* acc,
+                size_t acc_bytes, int32_t crop_rows, int32_t resize_height, int32_t resize_width, int32_t out_rows, int32_t normalize,
+                const WindowArgs* win, float* out, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  ESS_CHECK_ARG(counts && acc && out && workspace && (!win || win->words), "%s: null counts, acc, out%s", what,
+                win ? ", workspace or words" : " or workspace");
+  ESS_CHECK_ARG(n_slots >= 1 && n_slots <= 65535, "%s: n_slots=%d (1..65535)", what, (int)n_slots);
+  ESS_CHECK_ARG(bins > 0 && src_height > 0 && src_width > 0, "%s: bins=%d src_height=%d src_width=%d must be positive", what, (int)bins,
+                (int)src_height, (int)src_width);
+  ESS_CHECK_ARG(resize_height > 0 && resize_width > 0, "%s: resize_height=%d resize_width=%d must be positive", what, (int)resize_height,
+                (int)resize_width);
+  ESS_CHECK_ARG(crop_rows >= 1 && crop_rows <= src_height, "%s: crop_rows=%d (1..src_height=%d)", what, (int)crop_rows, (int)src_height);
+  ESS_CHECK_ARG(out_rows >= 1 && out_rows <= resize_height, "%s: out_rows=%d (1..resize_height=%d)", what, (int)out_rows,
+                (int)resize_height);
+  ESS_CHECK_ARG(normalize == GRID_NORM_NONE || normalize == GRID_NORM_UNBIASED || normalize == GRID_NORM_POPULATION,
+                "%s: normalize=%d (0 none, 1 unbiased, 2 population)", what, (int)normalize);
+  if (win) {
+    ESS_CHECK_ARG(win->slots_per_group >= 1, "%s: slots_per_group=%d must be positive", what, (int)win->slots_per_group);
+    ESS_CHECK_ARG(win->win_height >= 1 && win->win_height <= out_rows, "%s: win_height=%d (1..out_rows=%d)", what, (int)win->win_height,
+                  (int)out_rows);
+    ESS_CHECK_ARG(win->win_width >= 1 && win->win_width <= resize_width, "%s: win_width=%d (1..resize_width=%d)", what,
+                  (int)win->win_width, (int)resize_width);
+  }
+  const size_t need = ess_event_ingest_workspace(n_slots, bins, src_height, src_width);
+  ESS_CHECK_ARG(acc_bytes >= need, "%s: acc has %zu bytes, %zu are needed", what, acc_bytes, need);
+  const size_t ws_need = ess_event_grid_finish_workspace(n_slots, bins, src_height, src_width);
+  ESS_CHECK_ARG(workspace_bytes >= ws_need, "%s: workspace has %zu bytes, %zu are needed", what, workspace_bytes, ws_need);
+  ESS_CHECK_ARG(((((uintptr_t)acc) | ((uintptr_t)out) | ((uintptr_t)workspace)) & 15) == 0,
+                "%s: acc, out and workspace must be 16-byte aligned", what);
+  ESS_CHECK_ARG(!win || (((uintptr_t)win->words) & 3) == 0, "%s: words must be 4-byte aligned", what);
+  const int64_t src_per = (int64_t)bins * src_height * src_width;
+  GridStat* stats = nullptr;
+  int rc;
+  if (normalize != GRID_NORM_NONE) {
+    stats = (GridStat*)workspace;
+    unsigned long long* partials = (unsigned long long*)(stats + n_slots);
+    const int blocks = grid_stats_blocks(src_per);
+    const dim3 sgrid((unsigned)blocks, (unsigned)n_slots);
+    if ((src_per & 1) == 0)
+      hipLaunchKernelGGL(grid_stats_kernel<true>, sgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (const long long*)acc, partials);
+    else
+      hipLaunchKernelGGL(grid_stats_kernel<false>, sgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (const long long*)acc, partials);
+    rc = stage_status(what, "statistics");
+    if (rc) return rc;
+    hipLaunchKernelGGL(grid_stats_finalize_kernel, dim3((unsigned)ceil_div(n_slots, 64)), dim3(64), 0, st, counts, (int)n_slots, blocks,
+                       (int)normalize, (const unsigned long long*)partials, stats);
+    rc = stage_status(what, "finalize");
+    if (rc) return rc;
+  }
+  const bool identity = crop_rows == src_height && resize_height == src_height && out_rows == src_height && resize_width == src_width;
+  if (identity && !win) {  // each sum has one reader: map and clear in one kernel
+    launch_finish<true>(counts, n_slots, src_per, acc, stats, out, st);
+    return stage_status(what, "identity");
+  }
+  const GridGeometry g = {bins,         src_height, src_width, crop_rows, resize_height, resize_width, out_rows,
+                          grid_scale(crop_rows, resize_height), grid_scale(src_width, resize_width)};
+  const WindowArgs w = win ? *win : WindowArgs{nullptr, 1, out_rows, resize_width};
+  const bool vec = (w.win_width & 3) == 0;
+  const dim3 grid = grid_pass((int64_t)bins * w.win_height * (vec ? w.win_width >> 2 : w.win_width), n_slots);
+#define ESS_LAUNCH_MAP(VEC, IDENTITY, WINDOW)                                                                                   \
+  hipLaunchKernelGGL((grid_map_kernel<VEC, IDENTITY, WINDOW>), grid, dim3(INGEST_THREADS), 0, st, counts, g, w.words,              \
+                     (int)w.slots_per_group, (int)w.win_height, (int)w.win_width, (const long long*)acc, (const GridStat*)stats, out)
+  if (!win && vec) ESS_LAUNCH_MAP(true, false, false);
+  else if (!win) ESS_LAUNCH_MAP(false, false, false);
+  else if (vec && identity) ESS_LAUNCH_MAP(true, true, true);
+  else if (vec) ESS_LAUNCH_MAP(true, false, true);
+  else if (identity) ESS_LAUNCH_MAP(false, true, true);
+  else ESS_LAUNCH_MAP(false, false, true);
+#undef ESS_LAUNCH_MAP
+  rc = stage_status(what, "map");
+  if (rc) return rc;
+  const bool cvec = (src_per & 1) == 0;
+  const dim3 cgrid = grid_pass(cvec ? src_per >> 1 : src_per, n_slots);
+  if (cvec)
+    hipLaunchKernelGGL(grid_clear_kernel<true>, cgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (long long*)acc);
+  else
+    hipLaunchKernelGGL(grid_clear_kernel<false>, cgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (long long*)acc);
+  return stage_status(what, "clear");
+}
+
 }  // namespace
 
 extern "C" size_t ess_event_ingest_workspace(int32_t n_streams, int32_t bins, int32_t height, int32_t width) {
@@ -782,23 +813,16 @@ extern "C" size_t ess_event_ingest_workspace(int32_t n_streams, int32_t bins, in
 
 extern "C" int ess_event_ingest(const void* records, const int32_t* counts, int64_t capacity, int32_t n_streams, int32_t bins,
                                 int32_t height, int32_t width, void* acc, size_t acc_bytes, float* out, ess_stream_t stream) {
-  ESS_CHECK_ARG(records && counts && acc && out, "event_ingest: null records, counts, acc or out");
-  ESS_CHECK_ARG(n_streams >= 1 && n_streams <= 65535, "event_ingest: n_streams=%d (1..65535)", (int)n_streams);
-  ESS_CHECK_ARG(bins > 0 && height > 0 && width > 0, "event_ingest: bins=%d height=%d width=%d must be positive", (int)bins, (int)height,
-                (int)width);
-  ESS_CHECK_ARG(capacity >= 1 && capacity <= INGEST_MAX_CAPACITY,
-                "event_ingest: capacity=%lld events per stream (1..%lld: the int64 sums hold 2^22 contributions of magnitude 1 at scale 2^40)",
-                (long long)capacity, (long long)INGEST_MAX_CAPACITY);
-  const size_t need = ess_event_ingest_workspace(n_streams, bins, height, width);
-  ESS_CHECK_ARG(acc_bytes >= need, "event_ingest: acc has %zu bytes, %zu are needed", acc_bytes, need);
-  ESS_CHECK_ARG((((uintptr_t)records) & 15) == 0 && (((uintptr_t)acc) & 15) == 0 && (((uintptr_t)out) & 15) == 0,
-                "event_ingest: records, acc and out must be 16-byte aligned");
+  int rc = check_source("event_ingest", SOURCE_RECORDS, records && counts, (uintptr_t)records, capacity, 1, n_streams, bins, height, width,
+                        acc, acc_bytes, out);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(event_scatter_kernel, dim3(scatter_blocks(capacity), (unsigned)n_streams), dim3(INGEST_THREADS), 0, st,
                      (const uint4*)records, counts, capacity, bins, height, width, (long long*)acc);
-  int rc = ess_launch_status("event_ingest(scatter)");
+  rc = ess_launch_status("event_ingest(scatter)");
   if (rc) return rc;
-  return launch_finish(counts, n_streams, bins, height, width, acc, out, st, "event_ingest(finish)");
+  launch_finish<false>(counts, n_streams, (int64_t)bins * height * width, acc, nullptr, out, st);
+  return ess_launch_status("event_ingest(finish)");
 }
 
 extern "C" int ess_event_ingest_columns(const void* t, const void* x, const void* y, const void* p, const int32_t* counts,
@@ -807,12 +831,11 @@ extern "C" int ess_event_ingest_columns(const void* t, const void* x, const void
   int rc = check_columns("event_ingest_columns", t, x, y, p, counts, formats, stride, n_streams, bins, height, width, acc, acc_bytes, out);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL((event_scatter_columns_kernel<TemporalFlavour>), dim3(scatter_blocks(stride), (unsigned)n_streams),
-                     dim3(INGEST_THREADS), 0, st, (const long long*)t, (const unsigned short*)x, (const unsigned short*)y,
-                     (const unsigned char*)p, counts, formats, stride, bins, height, width, (long long*)acc);
-  rc = ess_launch_status("event_ingest_columns(scatter)");
+  rc = launch_scatter<TemporalFlavour, false>("event_ingest_columns(scatter)", t, x, y, p, nullptr, nullptr, counts, formats, stride, 1,
+                                              n_streams, bins, height, width, acc, st);
   if (rc) return rc;
-  return launch_finish(counts, n_streams, bins, height, width, acc, out, st, "event_ingest_columns(finish)");
+  launch_finish<false>(counts, n_streams, (int64_t)bins * height * width, acc, nullptr, out, st);
+  return ess_launch_status("event_ingest_columns(finish)");
 }
 
 extern "C" int ess_event_ingest_columns_trilinear(const void* t, const void* x, const void* y, const void* p, const int32_t* counts,
@@ -827,12 +850,11 @@ extern "C" int ess_event_ingest_columns_trilinear(const void* t, const void* x, 
   rc = check_rectify(what, maps, map_of, n_maps, map_height, map_width, rect);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL((event_scatter_columns_kernel<TrilinearFlavour, Rectify>), dim3(scatter_blocks(stride), (unsigned)n_streams),
-                     dim3(INGEST_THREADS), 0, st, (const long long*)t, (const unsigned short*)x, (const unsigned short*)y,
-                     (const unsigned char*)p, counts, formats, stride, bins, height, width, (long long*)acc, rect);
-  rc = ess_launch_status("event_ingest_columns_trilinear(scatter)");
+  rc = launch_scatter<TrilinearFlavour, false>("event_ingest_columns_trilinear(scatter)", t, x, y, p, nullptr, nullptr, counts, formats,
+                                               stride, 1, n_streams, bins, height, width, acc, st, rect);
   if (rc) return rc;
-  return launch_finish(counts, n_streams, bins, height, width, acc, out, st, "event_ingest_columns_trilinear(finish)");
+  launch_finish<false>(counts, n_streams, (int64_t)bins * height * width, acc, nullptr, out, st);
+  return ess_launch_status("event_ingest_columns_trilinear(finish)");
 }
 
 extern "C" int ess_event_ingest_ring(const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
@@ -843,12 +865,11 @@ extern "C" int ess_event_ingest_ring(const void* t, const void* x, const void* y
                       acc_bytes, out);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL((event_scatter_ring_kernel<TemporalFlavour>), dim3(scatter_blocks(ring), (unsigned)n_slots), dim3(INGEST_THREADS), 0,
-                     st, (const long long*)t, (const unsigned short*)x, (const unsigned short*)y, (const unsigned char*)p, rows, starts,
-                     counts, formats, ring, n_rows, bins, height, width, (long long*)acc);
-  rc = ess_launch_status("event_ingest_ring(scatter)");
+  rc = launch_scatter<TemporalFlavour, true>("event_ingest_ring(scatter)", t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots,
+                                             bins, height, width, acc, st);
   if (rc) return rc;
-  return launch_finish(counts, n_slots, bins, height, width, acc, out, st, "event_ingest_ring(finish)");
+  launch_finish<false>(counts, n_slots, (int64_t)bins * height * width, acc, nullptr, out, st);
+  return ess_launch_status("event_ingest_ring(finish)");
 }
 
 extern "C" int ess_event_ingest_ring_trilinear(const void* t, const void* x, const void* y, const void* p, const int32_t* rows,
@@ -863,12 +884,11 @@ extern "C" int ess_event_ingest_ring_trilinear(const void* t, const void* x, con
   rc = check_rectify(what, maps, map_of, n_maps, map_height, map_width, rect);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL((event_scatter_ring_kernel<TrilinearFlavour, Rectify>), dim3(scatter_blocks(ring), (unsigned)n_slots),
-                     dim3(INGEST_THREADS), 0, st, (const long long*)t, (const unsigned short*)x, (const unsigned short*)y,
-                     (const unsigned char*)p, rows, starts, counts, formats, ring, n_rows, bins, height, width, (long long*)acc, rect);
-  rc = ess_launch_status("event_ingest_ring_trilinear(scatter)");
+  rc = launch_scatter<TrilinearFlavour, true>("event_ingest_ring_trilinear(scatter)", t, x, y, p, rows, starts, counts, formats, ring, n_rows,
+                                              n_slots, bins, height, width, acc, st, rect);
   if (rc) return rc;
-  return launch_finish(counts, n_slots, bins, height, width, acc, out, st, "event_ingest_ring_trilinear(finish)");
+  launch_finish<false>(counts, n_slots, (int64_t)bins * height * width, acc, nullptr, out, st);
+  return ess_launch_status("event_ingest_ring_trilinear(finish)");
 }
 
 // ---- the ring ingest in two halves: scatter alone (acc keeps the sums), and the loader finish that turns sums into the loader's grid
@@ -878,10 +898,8 @@ extern "C" int ess_event_scatter_ring(const void* t, const void* x, const void* 
   int rc = check_ring("event_scatter_ring", t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, bins, height, width, acc,
                       acc_bytes, nullptr, false);
   if (rc) return rc;
-  hipLaunchKernelGGL((event_scatter_ring_kernel<TemporalFlavour>), dim3(scatter_blocks(ring), (unsigned)n_slots), dim3(INGEST_THREADS), 0,
-                     (hipStream_t)stream, (const long long*)t, (const unsigned short*)x, (const unsigned short*)y,
-                     (const unsigned char*)p, rows, starts, counts, formats, ring, n_rows, bins, height, width, (long long*)acc);
-  return ess_launch_status("event_scatter_ring");
+  return launch_scatter<TemporalFlavour, true>("event_scatter_ring", t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, bins,
+                                               height, width, acc, (hipStream_t)stream);
 }
 
 extern "C" int ess_event_scatter_ring_trilinear(const void* t, const void* x, const void* y, const void* p, const int32_t* rows,
@@ -896,11 +914,8 @@ extern "C" int ess_event_scatter_ring_trilinear(const void* t, const void* x, co
   Rectify rect;
   rc = check_rectify(what, maps, map_of, n_maps, map_height, map_width, rect);
   if (rc) return rc;
-  hipLaunchKernelGGL((event_scatter_ring_kernel<TrilinearFlavour, Rectify>), dim3(scatter_blocks(ring), (unsigned)n_slots),
-                     dim3(INGEST_THREADS), 0, (hipStream_t)stream, (const long long*)t, (const unsigned short*)x,
-                     (const unsigned short*)y, (const unsigned char*)p, rows, starts, counts, formats, ring, n_rows, bins, height, width,
-                     (long long*)acc, rect);
-  return ess_launch_status(what);
+  return launch_scatter<TrilinearFlavour, true>(what, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, bins, height, width,
+                                                acc, (hipStream_t)stream, rect);
 }
 
 // workspace: [n_slots] GridStat, then [n_slots][grid_stats_blocks][3] 8-byte partials
@@ -913,149 +928,19 @@ extern "C" size_t ess_event_grid_finish_workspace(int32_t n_slots, int32_t bins,
 extern "C" int ess_event_grid_finish(const int32_t* counts, int32_t n_slots, int32_t bins, int32_t src_height, int32_t src_width, void* acc,
                                      size_t acc_bytes, int32_t crop_rows, int32_t resize_height, int32_t resize_width, int32_t out_rows,
                                      int32_t normalize, float* out, void* workspace, size_t workspace_bytes, ess_stream_t stream) {
-  ESS_CHECK_ARG(counts && acc && out && workspace, "event_grid_finish: null counts, acc, out or workspace");
-  ESS_CHECK_ARG(n_slots >= 1 && n_slots <= 65535, "event_grid_finish: n_slots=%d (1..65535)", (int)n_slots);
-  ESS_CHECK_ARG(bins > 0 && src_height > 0 && src_width > 0, "event_grid_finish: bins=%d src_height=%d src_width=%d must be positive",
-                (int)bins, (int)src_height, (int)src_width);
-  ESS_CHECK_ARG(resize_height > 0 && resize_width > 0, "event_grid_finish: resize_height=%d resize_width=%d must be positive",
-                (int)resize_height, (int)resize_width);
-  ESS_CHECK_ARG(crop_rows >= 1 && crop_rows <= src_height, "event_grid_finish: crop_rows=%d (1..src_height=%d)", (int)crop_rows,
-                (int)src_height);
-  ESS_CHECK_ARG(out_rows >= 1 && out_rows <= resize_height, "event_grid_finish: out_rows=%d (1..resize_height=%d)", (int)out_rows,
-                (int)resize_height);
-  ESS_CHECK_ARG(normalize == GRID_NORM_NONE || normalize == GRID_NORM_UNBIASED || normalize == GRID_NORM_POPULATION,
-                "event_grid_finish: normalize=%d (0 none, 1 unbiased, 2 population)", (int)normalize);
-  const size_t need = ess_event_ingest_workspace(n_slots, bins, src_height, src_width);
-  ESS_CHECK_ARG(acc_bytes >= need, "event_grid_finish: acc has %zu bytes, %zu are needed", acc_bytes, need);
-  const size_t ws_need = ess_event_grid_finish_workspace(n_slots, bins, src_height, src_width);
-  ESS_CHECK_ARG(workspace_bytes >= ws_need, "event_grid_finish: workspace has %zu bytes, %zu are needed", workspace_bytes, ws_need);
-  ESS_CHECK_ARG(((((uintptr_t)acc) | ((uintptr_t)out) | ((uintptr_t)workspace)) & 15) == 0,
-                "event_grid_finish: acc, out and workspace must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t src_per = (int64_t)bins * src_height * src_width;
-  GridStat* stats = nullptr;
-  int rc;
-  if (normalize != GRID_NORM_NONE) {
-    stats = (GridStat*)workspace;
-    unsigned long long* partials = (unsigned long long*)(stats + n_slots);
-    const int blocks = grid_stats_blocks(src_per);
-    const dim3 sgrid((unsigned)blocks, (unsigned)n_slots);
-    if ((src_per & 1) == 0)
-      hipLaunchKernelGGL(grid_stats_kernel<true>, sgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (const long long*)acc, partials);
-    else
-      hipLaunchKernelGGL(grid_stats_kernel<false>, sgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (const long long*)acc, partials);
-    rc = ess_launch_status("event_grid_finish(statistics)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(grid_stats_finalize_kernel, dim3((unsigned)ceil_div(n_slots, 64)), dim3(64), 0, st, counts, (int)n_slots, blocks,
-                       (int)normalize, (const unsigned long long*)partials, stats);
-    rc = ess_launch_status("event_grid_finish(finalize)");
-    if (rc) return rc;
-  }
-  if (crop_rows == src_height && resize_height == src_height && out_rows == src_height && resize_width == src_width) {
-    // each sum has one reader: map and clear in one kernel
-    const bool vec = (src_per & 3) == 0;
-    const dim3 grid = grid_pass(vec ? src_per >> 2 : src_per, n_slots);
-    if (vec)
-      hipLaunchKernelGGL(grid_identity_kernel<true>, grid, dim3(INGEST_THREADS), 0, st, counts, src_per, (long long*)acc,
-                         (const GridStat*)stats, out);
-    else
-      hipLaunchKernelGGL(grid_identity_kernel<false>, grid, dim3(INGEST_THREADS), 0, st, counts, src_per, (long long*)acc,
-                         (const GridStat*)stats, out);
-    return ess_launch_status("event_grid_finish(identity)");
-  }
-  const GridGeometry g = {bins,         src_height, src_width, crop_rows, resize_height, resize_width, out_rows,
-                          grid_scale(crop_rows, resize_height), grid_scale(src_width, resize_width)};
-  const bool vec = (resize_width & 3) == 0;
-  const int64_t items = (int64_t)bins * out_rows * (vec ? resize_width >> 2 : resize_width);
-  if (vec)
-    hipLaunchKernelGGL(grid_map_kernel<true>, grid_pass(items, n_slots), dim3(INGEST_THREADS), 0, st, counts, g, (const long long*)acc,
-                       (const GridStat*)stats, out);
-  else
-    hipLaunchKernelGGL(grid_map_kernel<false>, grid_pass(items, n_slots), dim3(INGEST_THREADS), 0, st, counts, g, (const long long*)acc,
-                       (const GridStat*)stats, out);
-  rc = ess_launch_status("event_grid_finish(map)");
-  if (rc) return rc;
-  const bool cvec = (src_per & 1) == 0;
-  const dim3 cgrid = grid_pass(cvec ? src_per >> 1 : src_per, n_slots);
-  if (cvec)
-    hipLaunchKernelGGL(grid_clear_kernel<true>, cgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (long long*)acc);
-  else
-    hipLaunchKernelGGL(grid_clear_kernel<false>, cgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (long long*)acc);
-  return ess_launch_status("event_grid_finish(clear)");
+  return grid_finish("event_grid_finish", counts, n_slots, bins, src_height, src_width, acc, acc_bytes, crop_rows, resize_height,
+                     resize_width, out_rows, normalize, nullptr, out, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
-// ess_event_grid_finish with the training window fused into its map pass.  The statistics launches are ess_event_grid_finish's; the
-// map computes the window's voxels alone, so some sums may have no reader: the clear always runs as a pass of its own.
+// ess_event_grid_finish with the training window fused into its map pass
 extern "C" int ess_event_grid_finish_window(const int32_t* counts, int32_t n_slots, int32_t bins, int32_t src_height, int32_t src_width,
                                             void* acc, size_t acc_bytes, int32_t crop_rows, int32_t resize_height, int32_t resize_width,
                                             int32_t out_rows, int32_t normalize, const int32_t* words, int32_t slots_per_group,
                                             int32_t win_height, int32_t win_width, float* out, void* workspace, size_t workspace_bytes,
                                             ess_stream_t stream) {
-  const char* what = "event_grid_finish_window";
-  ESS_CHECK_ARG(counts && acc && out && workspace && words, "%s: null counts, acc, out, workspace or words", what);
-  ESS_CHECK_ARG(n_slots >= 1 && n_slots <= 65535, "%s: n_slots=%d (1..65535)", what, (int)n_slots);
-  ESS_CHECK_ARG(bins > 0 && src_height > 0 && src_width > 0, "%s: bins=%d src_height=%d src_width=%d must be positive", what, (int)bins,
-                (int)src_height, (int)src_width);
-  ESS_CHECK_ARG(resize_height > 0 && resize_width > 0, "%s: resize_height=%d resize_width=%d must be positive", what, (int)resize_height,
-                (int)resize_width);
-  ESS_CHECK_ARG(crop_rows >= 1 && crop_rows <= src_height, "%s: crop_rows=%d (1..src_height=%d)", what, (int)crop_rows, (int)src_height);
-  ESS_CHECK_ARG(out_rows >= 1 && out_rows <= resize_height, "%s: out_rows=%d (1..resize_height=%d)", what, (int)out_rows,
-                (int)resize_height);
-  ESS_CHECK_ARG(normalize == GRID_NORM_NONE || normalize == GRID_NORM_UNBIASED || normalize == GRID_NORM_POPULATION,
-                "%s: normalize=%d (0 none, 1 unbiased, 2 population)", what, (int)normalize);
-  ESS_CHECK_ARG(slots_per_group >= 1, "%s: slots_per_group=%d must be positive", what, (int)slots_per_group);
-  ESS_CHECK_ARG(win_height >= 1 && win_height <= out_rows, "%s: win_height=%d (1..out_rows=%d)", what, (int)win_height, (int)out_rows);
-  ESS_CHECK_ARG(win_width >= 1 && win_width <= resize_width, "%s: win_width=%d (1..resize_width=%d)", what, (int)win_width,
-                (int)resize_width);
-  const size_t need = ess_event_ingest_workspace(n_slots, bins, src_height, src_width);
-  ESS_CHECK_ARG(acc_bytes >= need, "%s: acc has %zu bytes, %zu are needed", what, acc_bytes, need);
-  const size_t ws_need = ess_event_grid_finish_workspace(n_slots, bins, src_height, src_width);
-  ESS_CHECK_ARG(workspace_bytes >= ws_need, "%s: workspace has %zu bytes, %zu are needed", what, workspace_bytes, ws_need);
-  ESS_CHECK_ARG(((((uintptr_t)acc) | ((uintptr_t)out) | ((uintptr_t)workspace)) & 15) == 0,
-                "%s: acc, out and workspace must be 16-byte aligned", what);
-  ESS_CHECK_ARG((((uintptr_t)words) & 3) == 0, "%s: words must be 4-byte aligned", what);
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t src_per = (int64_t)bins * src_height * src_width;
-  GridStat* stats = nullptr;
-  int rc;
-  if (normalize != GRID_NORM_NONE) {
-    stats = (GridStat*)workspace;
-    unsigned long long* partials = (unsigned long long*)(stats + n_slots);
-    const int blocks = grid_stats_blocks(src_per);
-    const dim3 sgrid((unsigned)blocks, (unsigned)n_slots);
-    if ((src_per & 1) == 0)
-      hipLaunchKernelGGL(grid_stats_kernel<true>, sgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (const long long*)acc, partials);
-    else
-      hipLaunchKernelGGL(grid_stats_kernel<false>, sgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (const long long*)acc, partials);
-    rc = ess_launch_status("event_grid_finish_window(statistics)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(grid_stats_finalize_kernel, dim3((unsigned)ceil_div(n_slots, 64)), dim3(64), 0, st, counts, (int)n_slots, blocks,
-                       (int)normalize, (const unsigned long long*)partials, stats);
-    rc = ess_launch_status("event_grid_finish_window(finalize)");
-    if (rc) return rc;
-  }
-  const bool identity = crop_rows == src_height && resize_height == src_height && out_rows == src_height && resize_width == src_width;
-  const GridGeometry g = {bins,         src_height, src_width, crop_rows, resize_height, resize_width, out_rows,
-                          grid_scale(crop_rows, resize_height), grid_scale(src_width, resize_width)};
-  const bool vec = (win_width & 3) == 0;
-  const dim3 grid = grid_pass((int64_t)bins * win_height * (vec ? win_width >> 2 : win_width), n_slots);
-#define ESS_LAUNCH_WINDOW(VEC, IDENTITY)                                                                                          \
-  hipLaunchKernelGGL((grid_window_kernel<VEC, IDENTITY>), grid, dim3(INGEST_THREADS), 0, st, counts, g, words, (int)slots_per_group, \
-                     (int)win_height, (int)win_width, (const long long*)acc, (const GridStat*)stats, out)
-  if (vec && identity) ESS_LAUNCH_WINDOW(true, true);
-  else if (vec) ESS_LAUNCH_WINDOW(true, false);
-  else if (identity) ESS_LAUNCH_WINDOW(false, true);
-  else ESS_LAUNCH_WINDOW(false, false);
-#undef ESS_LAUNCH_WINDOW
-  rc = ess_launch_status("event_grid_finish_window(map)");
-  if (rc) return rc;
-  const bool cvec = (src_per & 1) == 0;
-  const dim3 cgrid = grid_pass(cvec ? src_per >> 1 : src_per, n_slots);
-  if (cvec)
-    hipLaunchKernelGGL(grid_clear_kernel<true>, cgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (long long*)acc);
-  else
-    hipLaunchKernelGGL(grid_clear_kernel<false>, cgrid, dim3(INGEST_THREADS), 0, st, counts, src_per, (long long*)acc);
-  return ess_launch_status("event_grid_finish_window(clear)");
+  const WindowArgs win = {words, slots_per_group, win_height, win_width};
+  return grid_finish("event_grid_finish_window", counts, n_slots, bins, src_height, src_width, acc, acc_bytes, crop_rows, resize_height,
+                     resize_width, out_rows, normalize, &win, out, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int ess_label_window(const uint8_t* src, int32_t n, int32_t src_height, int32_t src_width, int32_t resize_height,

@@ -873,6 +873,38 @@ INGEST_KEEP = -1  # ESS_INGEST_KEEP: a count word that leaves the stream's grid 
 INGEST_MAX_CAPACITY = 1 << 22
 
 
+def _are_tensors(fn, named):
+    for name, v in named:
+        if not torch.is_tensor(v):
+            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+
+
+def _on_device(fn, named):
+    """the last check of a binding: what is wrong with a tensor's form is said whatever memory it lies in"""
+    for name, v in named:
+        if not v.is_cuda:
+            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+        if not v.is_contiguous():
+            raise EssHipError(f'{fn}: {name} must be contiguous')
+
+
+def _ingest_out(fn, out, n_name):
+    """the grids an ingest fills -> (n, bins, H, W)"""
+    if out.dim() != 4 or out.dtype != torch.float32 or out.numel() == 0:
+        raise EssHipError(f'{fn}: out must be a non-empty fp32 [{n_name}, bins, H, W] tensor, got {out.dtype}{tuple(out.shape)}')
+    return out.shape
+
+
+def _ingest_acc(fn, named, acc, out):
+    """the last checks of an ingest binding -- acc's dtype, then _on_device -- and the all-zero sums of a call that gave none"""
+    if acc is not None and acc.dtype != torch.int64:
+        raise EssHipError(f'{fn}: acc must be int64, got {acc.dtype}')
+    _on_device(fn, named)
+    if acc is None:
+        acc = torch.zeros(out.numel(), dtype=torch.int64, device=out.device)
+    return acc
+
+
 def event_ingest(records, counts, out, acc=None):
     """Packed event records -> one signed temporal voxel grid per stream, ORDER-INDEPENDENT: each contribution is the fp32 value
     voxel_grid_temporal(separate_pol=False) adds, summed as a 64-bit integer at scale 2^40, so out is a pure function of the set of
@@ -932,36 +964,41 @@ def event_ingest_columns(t, x, y, p, counts, formats, out, acc=None):
     return _event_ingest_columns('event_ingest_columns', t, x, y, p, counts, formats, out, acc, None)
 
 
-def _event_ingest_columns(fn, t, x, y, p, counts, formats, out, acc, rectify):
-    """event_ingest_columns (rectify None) / event_ingest_columns_trilinear (rectify: (maps, map_of) as given): the checks and the call"""
-    named = (('t', t), ('x', x), ('y', y), ('p', p), ('counts', counts), ('formats', formats), ('out', out))
-    for name, v in named + ((('acc', acc),) if acc is not None else ()):
-        if not torch.is_tensor(v) or not v.is_cuda:
-            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
-        if not v.is_contiguous():
-            raise EssHipError(f'{fn}: {name} must be contiguous')
-    if out.dim() != 4 or out.dtype != torch.float32 or out.numel() == 0:
-        raise EssHipError(f'{fn}: out must be a non-empty fp32 [S, bins, H, W] tensor, got {out.dtype}{tuple(out.shape)}')
-    S, bins, H, W = out.shape
-    if t.dim() != 2 or t.shape[0] != S or t.shape[1] < 1:
-        raise EssHipError(f'{fn}: t must be [{S}, stride], got {tuple(t.shape)}')
+def _event_columns(fn, named, n, ring):
+    """The tensors a column-source call reads.  named[:4]: the raw columns t, x, y, p -- [n, stride] each, or (ring) [n_rows, ring]
+    with ring a multiple of 16 inside the capacity (a stride is the library's to check); named[4:]: the device words, int32 [n]."""
+    t = named[0][1]
+    if t.dim() != 2 or t.shape[1] < 1 or (t.shape[0] < 1 if ring else t.shape[0] != n):
+        form = 'n_rows, ring' if ring else f'{n}, stride'
+        raise EssHipError(f'{fn}: t must be [{form}], got {tuple(t.shape)}')
     for name, v in named[:4]:
         if v.dtype not in _EVCOL_DTYPES[name] or v.shape != t.shape:
             raise EssHipError(f'{fn}: {name} must be {" / ".join(str(d) for d in _EVCOL_DTYPES[name])} '
                               f'{list(t.shape)}, got {v.dtype}{tuple(v.shape)}')
-    for name, v in named[4:6]:
-        if v.dtype != torch.int32 or tuple(v.shape) != (S,):
-            raise EssHipError(f'{fn}: {name} must be int32 [{S}], got {v.dtype}{tuple(v.shape)}')
-    L = lib()
-    need = L.ess_event_ingest_workspace(S, bins, H, W)
-    if acc is None:
-        acc = torch.zeros(need // 8, dtype=torch.int64, device=out.device)
-    elif acc.dtype != torch.int64:
-        raise EssHipError(f'{fn}: acc must be int64, got {acc.dtype}')
+    for name, v in named[4:]:
+        if v.dtype != torch.int32 or tuple(v.shape) != (n,):
+            raise EssHipError(f'{fn}: {name} must be int32 [{n}], got {v.dtype}{tuple(v.shape)}')
+    if ring and (t.shape[1] % EVCOL_STRIDE_ALIGN or t.shape[1] > INGEST_MAX_CAPACITY):
+        raise EssHipError(f'{fn}: ring={t.shape[1]} must be a multiple of {EVCOL_STRIDE_ALIGN} in [{EVCOL_STRIDE_ALIGN}, '
+                          f'{INGEST_MAX_CAPACITY}] (event_column_stride rounds a capacity up)')
+
+
+def _column_pointers(named):
+    """t, x, y, p as untyped pointers, the int32 words behind them"""
+    return [c_void_p(v.data_ptr()) for _, v in named[:4]] + [ptr(v, torch.int32) for _, v in named[4:]]
+
+
+def _event_ingest_columns(fn, t, x, y, p, counts, formats, out, acc, rectify):
+    """event_ingest_columns (rectify None) / event_ingest_columns_trilinear (rectify: (maps, map_of) as given): the checks and the call"""
+    words = (('t', t), ('x', x), ('y', y), ('p', p), ('counts', counts), ('formats', formats))
+    named = words + (('out', out),) + ((('acc', acc),) if acc is not None else ())
+    _are_tensors(fn, named)
+    S, bins, H, W = _ingest_out(fn, out, 'S')
+    _event_columns(fn, words, S, ring=False)
+    acc = _ingest_acc(fn, named, acc, out)
     tail = () if rectify is None else _rectify_args(fn, rectify[0], rectify[1], S, out.device)
-    _check(getattr(L, 'ess_' + fn)(c_void_p(t.data_ptr()), c_void_p(x.data_ptr()), c_void_p(y.data_ptr()), c_void_p(p.data_ptr()),
-                                   ptr(counts, torch.int32), ptr(formats, torch.int32), t.shape[1], S, bins, H, W,
-                                   c_void_p(acc.data_ptr()), acc.numel() * 8, c_void_p(out.data_ptr()), *tail, stream()), 'ess_' + fn)
+    _check(getattr(lib(), 'ess_' + fn)(*_column_pointers(words), t.shape[1], S, bins, H, W, c_void_p(acc.data_ptr()), acc.numel() * 8,
+                                       c_void_p(out.data_ptr()), *tail, stream()), 'ess_' + fn)
     return out
 
 
@@ -1020,44 +1057,16 @@ def event_ingest_ring(t, x, y, p, rows, starts, counts, formats, out, acc=None):
 
 def _event_ingest_ring(fn, t, x, y, p, rows, starts, counts, formats, out, acc, rectify):
     """event_ingest_ring (rectify None) / event_ingest_ring_trilinear (rectify: (maps, map_of) as given): the checks and the call"""
-    named = (('t', t), ('x', x), ('y', y), ('p', p), ('rows', rows), ('starts', starts), ('counts', counts), ('formats', formats),
-             ('out', out))
-    every = named + ((('acc', acc),) if acc is not None else ())
-    for name, v in every:
-        if not torch.is_tensor(v):
-            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
-    if out.dim() != 4 or out.dtype != torch.float32 or out.numel() == 0:
-        raise EssHipError(f'{fn}: out must be a non-empty fp32 [n_slots, bins, H, W] tensor, got {out.dtype}{tuple(out.shape)}')
-    n_slots, bins, H, W = out.shape
-    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise EssHipError(f'{fn}: t must be [n_rows, ring], got {tuple(t.shape)}')
-    for name, v in named[:4]:
-        if v.dtype not in _EVCOL_DTYPES[name] or v.shape != t.shape:
-            raise EssHipError(f'{fn}: {name} must be {" / ".join(str(d) for d in _EVCOL_DTYPES[name])} '
-                              f'{list(t.shape)}, got {v.dtype}{tuple(v.shape)}')
-    for name, v in named[4:8]:
-        if v.dtype != torch.int32 or tuple(v.shape) != (n_slots,):
-            raise EssHipError(f'{fn}: {name} must be int32 [{n_slots}], got {v.dtype}{tuple(v.shape)}')
-    if acc is not None and acc.dtype != torch.int64:
-        raise EssHipError(f'{fn}: acc must be int64, got {acc.dtype}')
+    words = (('t', t), ('x', x), ('y', y), ('p', p), ('rows', rows), ('starts', starts), ('counts', counts), ('formats', formats))
+    named = words + (('out', out),) + ((('acc', acc),) if acc is not None else ())
+    _are_tensors(fn, named)
+    n_slots, bins, H, W = _ingest_out(fn, out, 'n_slots')
+    _event_columns(fn, words, n_slots, ring=True)
+    acc = _ingest_acc(fn, named, acc, out)
     n_rows, ring = t.shape
-    if ring % EVCOL_STRIDE_ALIGN or ring > INGEST_MAX_CAPACITY:
-        raise EssHipError(f'{fn}: ring={ring} must be a multiple of {EVCOL_STRIDE_ALIGN} in [{EVCOL_STRIDE_ALIGN}, '
-                          f'{INGEST_MAX_CAPACITY}] (event_column_stride rounds a capacity up)')
-    for name, v in every:  # (the device last: what is wrong with a tensor's form is said whatever memory it lies in)
-        if not v.is_cuda:
-            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
-        if not v.is_contiguous():
-            raise EssHipError(f'{fn}: {name} must be contiguous')
-    L = lib()
-    need = L.ess_event_ingest_workspace(n_slots, bins, H, W)
-    if acc is None:
-        acc = torch.zeros(need // 8, dtype=torch.int64, device=out.device)
     tail = () if rectify is None else _rectify_args(fn, rectify[0], rectify[1], n_slots, out.device)
-    _check(getattr(L, 'ess_' + fn)(c_void_p(t.data_ptr()), c_void_p(x.data_ptr()), c_void_p(y.data_ptr()), c_void_p(p.data_ptr()),
-                                   ptr(rows, torch.int32), ptr(starts, torch.int32), ptr(counts, torch.int32), ptr(formats, torch.int32),
-                                   ring, n_rows, n_slots, bins, H, W, c_void_p(acc.data_ptr()), acc.numel() * 8,
-                                   c_void_p(out.data_ptr()), *tail, stream()), 'ess_' + fn)
+    _check(getattr(lib(), 'ess_' + fn)(*_column_pointers(words), ring, n_rows, n_slots, bins, H, W, c_void_p(acc.data_ptr()),
+                                       acc.numel() * 8, c_void_p(out.data_ptr()), *tail, stream()), 'ess_' + fn)
     return out
 
 
@@ -1087,37 +1096,23 @@ def event_scatter_ring_trilinear(t, x, y, p, rows, starts, counts, formats, acc,
     return _event_scatter_ring('event_scatter_ring_trilinear', t, x, y, p, rows, starts, counts, formats, acc, (maps, map_of))
 
 
-def _event_scatter_ring(fn, t, x, y, p, rows, starts, counts, formats, acc, rectify):
-    named = (('t', t), ('x', x), ('y', y), ('p', p), ('rows', rows), ('starts', starts), ('counts', counts), ('formats', formats),
-             ('acc', acc))
-    for name, v in named:
-        if not torch.is_tensor(v):
-            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+def _finish_acc(fn, acc, dims):
+    """the sums a scatter leaves and a loader finish reads -> (n_slots, bins, Hs, Ws)"""
     if acc.dim() != 4 or acc.dtype != torch.int64 or acc.numel() == 0:
-        raise EssHipError(f'{fn}: acc must be a non-empty int64 [n_slots, bins, H, W] tensor, got {acc.dtype}{tuple(acc.shape)}')
-    n_slots, bins, H, W = acc.shape
-    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise EssHipError(f'{fn}: t must be [n_rows, ring], got {tuple(t.shape)}')
-    for name, v in named[:4]:
-        if v.dtype not in _EVCOL_DTYPES[name] or v.shape != t.shape:
-            raise EssHipError(f'{fn}: {name} must be {" / ".join(str(d) for d in _EVCOL_DTYPES[name])} '
-                              f'{list(t.shape)}, got {v.dtype}{tuple(v.shape)}')
-    for name, v in named[4:8]:
-        if v.dtype != torch.int32 or tuple(v.shape) != (n_slots,):
-            raise EssHipError(f'{fn}: {name} must be int32 [{n_slots}], got {v.dtype}{tuple(v.shape)}')
+        raise EssHipError(f'{fn}: acc must be a non-empty int64 [n_slots, bins, {dims}] tensor, got {acc.dtype}{tuple(acc.shape)}')
+    return acc.shape
+
+
+def _event_scatter_ring(fn, t, x, y, p, rows, starts, counts, formats, acc, rectify):
+    words = (('t', t), ('x', x), ('y', y), ('p', p), ('rows', rows), ('starts', starts), ('counts', counts), ('formats', formats))
+    named = words + (('acc', acc),)
+    _are_tensors(fn, named)
+    n_slots, bins, H, W = _finish_acc(fn, acc, 'H, W')
+    _event_columns(fn, words, n_slots, ring=True)
+    _on_device(fn, named)
     n_rows, ring = t.shape
-    if ring % EVCOL_STRIDE_ALIGN or ring > INGEST_MAX_CAPACITY:
-        raise EssHipError(f'{fn}: ring={ring} must be a multiple of {EVCOL_STRIDE_ALIGN} in [{EVCOL_STRIDE_ALIGN}, '
-                          f'{INGEST_MAX_CAPACITY}] (event_column_stride rounds a capacity up)')
-    for name, v in named:  # (the device last: what is wrong with a tensor's form is said whatever memory it lies in)
-        if not v.is_cuda:
-            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
-        if not v.is_contiguous():
-            raise EssHipError(f'{fn}: {name} must be contiguous')
     tail = () if rectify is None else _rectify_args(fn, rectify[0], rectify[1], n_slots, acc.device)
-    _check(getattr(lib(), 'ess_' + fn)(c_void_p(t.data_ptr()), c_void_p(x.data_ptr()), c_void_p(y.data_ptr()), c_void_p(p.data_ptr()),
-                                       ptr(rows, torch.int32), ptr(starts, torch.int32), ptr(counts, torch.int32),
-                                       ptr(formats, torch.int32), ring, n_rows, n_slots, bins, H, W, c_void_p(acc.data_ptr()),
+    _check(getattr(lib(), 'ess_' + fn)(*_column_pointers(words), ring, n_rows, n_slots, bins, H, W, c_void_p(acc.data_ptr()),
                                        acc.numel() * 8, *tail, stream()), 'ess_' + fn)
     return acc
 
@@ -1134,40 +1129,40 @@ def event_grid_finish(counts, acc, out, crop_rows=None, resize=None, normalize=G
     normalisation they are event_ingest_ring's bits.  No memset, no synchronisation: capturable."""
     fn = 'event_grid_finish'
     named = (('counts', counts), ('acc', acc), ('out', out))
-    for name, v in named:
-        if not torch.is_tensor(v):
-            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
-    if acc.dim() != 4 or acc.dtype != torch.int64 or acc.numel() == 0:
-        raise EssHipError(f'{fn}: acc must be a non-empty int64 [n_slots, bins, Hs, Ws] tensor, got {acc.dtype}{tuple(acc.shape)}')
-    n_slots, bins, Hs, Ws = acc.shape
-    crop_rows = Hs if crop_rows is None else crop_rows
-    if isinstance(crop_rows, bool) or not isinstance(crop_rows, int) or not 1 <= crop_rows <= Hs:
-        raise EssHipError(f'{fn}: crop_rows={crop_rows!r} must be an int in [1, {Hs}]')
-    if resize is None:
-        resize = (crop_rows, Ws)
+    _are_tensors(fn, named)
+    n_slots, bins, Hs, Ws, crop_rows, Hr, Wr = _finish_geometry(fn, counts, acc, out, crop_rows, resize, normalize, window=False)
+    _on_device(fn, named)
+    ws = grid_finish_workspace(n_slots, bins, Hs, Ws, out.device)
+    _check(lib().ess_event_grid_finish(ptr(counts, torch.int32), n_slots, bins, Hs, Ws, c_void_p(acc.data_ptr()), acc.numel() * 8,
+                                       crop_rows, Hr, Wr, out.shape[2], int(normalize), c_void_p(out.data_ptr()),
+                                       c_void_p(ws.data_ptr()), ws.numel(), stream()), 'ess_event_grid_finish')
+    return out
+
+
+def _resize_pair(fn, resize):
     if not isinstance(resize, (tuple, list)) or len(resize) != 2 or \
             any(isinstance(v, bool) or not isinstance(v, int) or v < 1 or v > 1 << 24 for v in resize):
         raise EssHipError(f'{fn}: resize={resize!r} must be a pair of positive ints (Hr, Wr)')
-    Hr, Wr = resize
+    return resize
+
+
+def _finish_geometry(fn, counts, acc, out, crop_rows, resize, normalize, window):
+    """What the two loader finishes check of acc, crop_rows, resize, out, normalize and counts, in this order -> (n_slots, bins, Hs,
+    Ws, crop_rows, Hr, Wr) with the defaults filled in.  window: out is a window inside the Hr x Wr grid, else its rows <= Hr."""
+    n_slots, bins, Hs, Ws = _finish_acc(fn, acc, 'Hs, Ws')
+    crop_rows = Hs if crop_rows is None else crop_rows
+    if isinstance(crop_rows, bool) or not isinstance(crop_rows, int) or not 1 <= crop_rows <= Hs:
+        raise EssHipError(f'{fn}: crop_rows={crop_rows!r} must be an int in [1, {Hs}]')
+    Hr, Wr = _resize_pair(fn, (crop_rows, Ws) if resize is None else resize)
     if out.dim() != 4 or out.dtype != torch.float32 or out.numel() == 0 or out.shape[0] != n_slots or out.shape[1] != bins \
-            or out.shape[2] > Hr or out.shape[3] != Wr:
-        raise EssHipError(f'{fn}: out must be fp32 [{n_slots}, {bins}, rows <= {Hr}, {Wr}], got {out.dtype}{tuple(out.shape)}')
+            or out.shape[2] > Hr or (out.shape[3] > Wr if window else out.shape[3] != Wr):
+        form = f'h <= {Hr}, w <= {Wr}] (the window inside the {Hr} x {Wr} grid)' if window else f'rows <= {Hr}, {Wr}]'
+        raise EssHipError(f'{fn}: out must be fp32 [{n_slots}, {bins}, {form}, got {out.dtype}{tuple(out.shape)}')
     if normalize not in (GRID_NORM_NONE, GRID_NORM_UNBIASED, GRID_NORM_POPULATION) or isinstance(normalize, bool):
         raise EssHipError(f'{fn}: normalize={normalize!r} must be GRID_NORM_NONE, GRID_NORM_UNBIASED or GRID_NORM_POPULATION')
     if counts.dtype != torch.int32 or tuple(counts.shape) != (n_slots,):
         raise EssHipError(f'{fn}: counts must be int32 [{n_slots}], got {counts.dtype}{tuple(counts.shape)}')
-    for name, v in named:
-        if not v.is_cuda:
-            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
-        if not v.is_contiguous():
-            raise EssHipError(f'{fn}: {name} must be contiguous')
-    L = lib()
-    nbytes = L.ess_event_grid_finish_workspace(n_slots, bins, Hs, Ws)
-    ws = workspace(nbytes, out.device, 'grid_finish')
-    _check(L.ess_event_grid_finish(ptr(counts, torch.int32), n_slots, bins, Hs, Ws, c_void_p(acc.data_ptr()), acc.numel() * 8, crop_rows,
-                                   Hr, Wr, out.shape[2], int(normalize), c_void_p(out.data_ptr()), c_void_p(ws.data_ptr()), ws.numel(),
-                                   stream()), 'ess_event_grid_finish')
-    return out
+    return n_slots, bins, Hs, Ws, crop_rows, Hr, Wr
 
 
 def grid_finish_workspace(n_slots, bins, Hs, Ws, device):
@@ -1178,8 +1173,6 @@ def grid_finish_workspace(n_slots, bins, Hs, Ws, device):
 
 def _window_words(fn, words, n_groups):
     """the (flip, y0, x0, reserved) table of the training window: int32 [n_groups, 4]"""
-    if not torch.is_tensor(words):
-        raise EssHipError(f'{fn}: words must be a CUDA(HIP) tensor; there is no CPU path')
     if words.dtype != torch.int32 or tuple(words.shape) != (n_groups, 4):
         raise EssHipError(f'{fn}: words must be int32 [{n_groups}, 4] rows of (flip, y0, x0, reserved), got {words.dtype}{tuple(words.shape)}')
 
@@ -1195,44 +1188,17 @@ def event_grid_finish_window(counts, acc, out, words, slots_per_group, crop_rows
     ALL ZERO behind the call, the sums no output read included.  No memset, no synchronisation: capturable."""
     fn = 'event_grid_finish_window'
     named = (('counts', counts), ('acc', acc), ('out', out), ('words', words))
-    for name, v in named:
-        if not torch.is_tensor(v):
-            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
-    if acc.dim() != 4 or acc.dtype != torch.int64 or acc.numel() == 0:
-        raise EssHipError(f'{fn}: acc must be a non-empty int64 [n_slots, bins, Hs, Ws] tensor, got {acc.dtype}{tuple(acc.shape)}')
-    n_slots, bins, Hs, Ws = acc.shape
-    crop_rows = Hs if crop_rows is None else crop_rows
-    if isinstance(crop_rows, bool) or not isinstance(crop_rows, int) or not 1 <= crop_rows <= Hs:
-        raise EssHipError(f'{fn}: crop_rows={crop_rows!r} must be an int in [1, {Hs}]')
-    if resize is None:
-        resize = (crop_rows, Ws)
-    if not isinstance(resize, (tuple, list)) or len(resize) != 2 or \
-            any(isinstance(v, bool) or not isinstance(v, int) or v < 1 or v > 1 << 24 for v in resize):
-        raise EssHipError(f'{fn}: resize={resize!r} must be a pair of positive ints (Hr, Wr)')
-    Hr, Wr = resize
-    if out.dim() != 4 or out.dtype != torch.float32 or out.numel() == 0 or out.shape[0] != n_slots or out.shape[1] != bins \
-            or out.shape[2] > Hr or out.shape[3] > Wr:
-        raise EssHipError(f'{fn}: out must be fp32 [{n_slots}, {bins}, h <= {Hr}, w <= {Wr}] (the window inside the {Hr} x {Wr} grid), '
-                          f'got {out.dtype}{tuple(out.shape)}')
-    if normalize not in (GRID_NORM_NONE, GRID_NORM_UNBIASED, GRID_NORM_POPULATION) or isinstance(normalize, bool):
-        raise EssHipError(f'{fn}: normalize={normalize!r} must be GRID_NORM_NONE, GRID_NORM_UNBIASED or GRID_NORM_POPULATION')
-    if counts.dtype != torch.int32 or tuple(counts.shape) != (n_slots,):
-        raise EssHipError(f'{fn}: counts must be int32 [{n_slots}], got {counts.dtype}{tuple(counts.shape)}')
+    _are_tensors(fn, named)
+    n_slots, bins, Hs, Ws, crop_rows, Hr, Wr = _finish_geometry(fn, counts, acc, out, crop_rows, resize, normalize, window=True)
     if isinstance(slots_per_group, bool) or not isinstance(slots_per_group, int) or slots_per_group < 1:
         raise EssHipError(f'{fn}: slots_per_group={slots_per_group!r} must be a positive int')
     _window_words(fn, words, -(-n_slots // slots_per_group))
-    for name, v in named:
-        if not v.is_cuda:
-            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
-        if not v.is_contiguous():
-            raise EssHipError(f'{fn}: {name} must be contiguous')
-    L = lib()
-    nbytes = L.ess_event_grid_finish_workspace(n_slots, bins, Hs, Ws)
-    ws = workspace(nbytes, out.device, 'grid_finish')
-    _check(L.ess_event_grid_finish_window(ptr(counts, torch.int32), n_slots, bins, Hs, Ws, c_void_p(acc.data_ptr()), acc.numel() * 8,
-                                          crop_rows, Hr, Wr, Hr, int(normalize), ptr(words, torch.int32), slots_per_group, out.shape[2],
-                                          out.shape[3], c_void_p(out.data_ptr()), c_void_p(ws.data_ptr()), ws.numel(), stream()),
-           'ess_event_grid_finish_window')
+    _on_device(fn, named)
+    ws = grid_finish_workspace(n_slots, bins, Hs, Ws, out.device)
+    _check(lib().ess_event_grid_finish_window(ptr(counts, torch.int32), n_slots, bins, Hs, Ws, c_void_p(acc.data_ptr()), acc.numel() * 8,
+                                              crop_rows, Hr, Wr, Hr, int(normalize), ptr(words, torch.int32), slots_per_group,
+                                              out.shape[2], out.shape[3], c_void_p(out.data_ptr()), c_void_p(ws.data_ptr()), ws.numel(),
+                                              stream()), 'ess_event_grid_finish_window')
     return out
 
 
@@ -1245,27 +1211,16 @@ def label_window(src, out, words, resize=None):
     but parity with cv2 itself is UNPINNED (cv2 is not a dependency), as datasets/augment.py says of albumentations."""
     fn = 'label_window'
     named = (('src', src), ('out', out), ('words', words))
-    for name, v in named:
-        if not torch.is_tensor(v):
-            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+    _are_tensors(fn, named)
     if src.dim() != 3 or src.dtype != torch.uint8 or src.numel() == 0 or src.shape[0] > 65535:
         raise EssHipError(f'{fn}: src must be a non-empty uint8 [n <= 65535, Hs, Ws] tensor, got {src.dtype}{tuple(src.shape)}')
     n, Hs, Ws = src.shape
-    if resize is None:
-        resize = (Hs, Ws)
-    if not isinstance(resize, (tuple, list)) or len(resize) != 2 or \
-            any(isinstance(v, bool) or not isinstance(v, int) or v < 1 or v > 1 << 24 for v in resize):
-        raise EssHipError(f'{fn}: resize={resize!r} must be a pair of positive ints (Hr, Wr)')
-    Hr, Wr = resize
+    Hr, Wr = _resize_pair(fn, (Hs, Ws) if resize is None else resize)
     if out.dim() != 3 or out.dtype != torch.int64 or out.numel() == 0 or out.shape[0] != n or out.shape[1] > Hr or out.shape[2] > Wr:
         raise EssHipError(f'{fn}: out must be int64 [{n}, h <= {Hr}, w <= {Wr}] (the window inside the {Hr} x {Wr} label), '
                           f'got {out.dtype}{tuple(out.shape)}')
     _window_words(fn, words, n)
-    for name, v in named:
-        if not v.is_cuda:
-            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
-        if not v.is_contiguous():
-            raise EssHipError(f'{fn}: {name} must be contiguous')
+    _on_device(fn, named)
     _check(lib().ess_label_window(ptr(src, torch.uint8), n, Hs, Ws, Hr, Wr, ptr(words, torch.int32), out.shape[1], out.shape[2],
                                   ptr(out, torch.int64), stream()), 'ess_label_window')
     return out

@@ -1,66 +1,221 @@
-// Stand-alone host program: the argument checks of ess_event_ingest_ring, which all come in front of any launch, so no device is
-// needed.  Meant to be built with the host sanitizers and run on its own (a library loaded into python is out of their reach):
+// Stand-alone host program: the argument checks of every entry point of voxel_ingest.hip -- the ingest from records, columns and
+// rings in both flavours, the scatter-only ring calls, the two loader finishes and the label window.  The checks all come in front
+// of any launch, so no device is needed.  Meant to be built with the host sanitizers and run on its own (a library loaded into python
+// is out of their reach):
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Iinclude -Xarch_host -fsanitize=address,undefined \
 //         -x hip ess_amd/csrc/voxel_ingest.hip tools/host_checks/event_ring_args_main.cpp \
 //         -x none ess_amd/libess_hip.so -Wl,-rpath,$PWD/ess_amd -o event_ring_args
-//   ./event_ring_args
+//   ./event_ring_args            (--texts: print every refusal's text as well, one a line, to compare two builds)
 //
 // voxel_ingest.hip -- the code under test -- is compiled into the program with the sanitizers; the built library only supplies the
-// error text (api.cpp), and the program's own ess_event_ingest_ring takes precedence over the library's.
+// error text (api.cpp), and the program's own entry points take precedence over the library's.
 // Every refused call must return ESS_EINVAL and leave a text in ess_last_error(); the pointers handed over are never dereferenced.
+// Each entry point is refused at least once for a null pointer, a count out of range, a short acc (or workspace) and a misalignment.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 
 #include "ess_hip.h"
 
 namespace {
-int failures = 0;
+int failures = 0, refusals = 0;
+bool texts = false;
 
-void expect_refused(int rc, const char* needle, const char* what) {
+void expect_refused(int rc, const char* needle, const char* entry, const char* what) {
   const char* msg = ess_last_error();
-  if (rc != -22 || !msg || !std::strstr(msg, needle)) {
-    std::printf("FAIL %s: rc=%d, message '%s' (wanted -22 and '%s')\n", what, rc, msg ? msg : "(null)", needle);
+  ++refusals;
+  if (rc != -22 || !msg || !std::strstr(msg, needle) || !std::strstr(msg, entry)) {
+    std::printf("FAIL %s, %s: rc=%d, message '%s' (wanted -22, '%s' and '%s')\n", entry, what, rc, msg ? msg : "(null)", entry, needle);
     ++failures;
+  } else if (texts) {
+    std::printf("%s | %s | %s\n", entry, what, msg);
   }
+}
+
+alignas(16) unsigned char block[64];
+void* const a = block;  // 16-byte aligned, never read
+const int32_t* const w = (const int32_t*)block;
+const int32_t NB = 5, H = 24, W = 40;
+
+// what a refusal changes of an otherwise good call: one pointer of each kind, the span (capacity / stride / ring), the count
+// (n_streams / n_slots), acc's size, out
+struct Args {
+  const void* t = a;         // the source's first pointer (records / t)
+  const void* p = a;         // its last column (the polarity bytes)
+  const int32_t* words = w;  // its last device word (formats; the ring's rows too)
+  int64_t span = 32;
+  int32_t n_rows = 1, n = 1;
+  void* acc = a;
+  size_t acc_bytes = (size_t)NB * H * W * 8;
+  void* out = a;
+  const float* maps = nullptr;  // (n_maps = 0: maps must be null)
+  const int32_t* map_of = w;
+};
+
+struct Source {
+  const char* entry;
+  const char* span;  // the span's name in the messages
+  const char* n;     // the count's
+  bool ring, with_out, rectify;
+  int (*call)(const Args&);
+};
+
+const Source SOURCES[] = {
+    {"event_ingest:", "capacity=", "n_streams=", false, true, false,
+     [](const Args& g) { return ess_event_ingest(g.t, g.words, g.span, g.n, NB, H, W, g.acc, g.acc_bytes, (float*)g.out, nullptr); }},
+    {"event_ingest_columns:", "stride=", "n_streams=", false, true, false,
+     [](const Args& g) {
+       return ess_event_ingest_columns(g.t, a, a, g.p, w, g.words, g.span, g.n, NB, H, W, g.acc, g.acc_bytes, (float*)g.out, nullptr);
+     }},
+    {"event_ingest_columns_trilinear:", "stride=", "n_streams=", false, true, true,
+     [](const Args& g) {
+       return ess_event_ingest_columns_trilinear(g.t, a, a, g.p, w, g.words, g.span, g.n, NB, H, W, g.acc, g.acc_bytes, (float*)g.out,
+                                                 g.maps, g.map_of, 0, 28, 44, nullptr);
+     }},
+    {"event_ingest_ring:", "ring=", "n_slots=", true, true, false,
+     [](const Args& g) {
+       return ess_event_ingest_ring(g.t, a, a, g.p, g.words, w, w, g.words, g.span, g.n_rows, g.n, NB, H, W, g.acc, g.acc_bytes,
+                                    (float*)g.out, nullptr);
+     }},
+    {"event_ingest_ring_trilinear:", "ring=", "n_slots=", true, true, true,
+     [](const Args& g) {
+       return ess_event_ingest_ring_trilinear(g.t, a, a, g.p, g.words, w, w, g.words, g.span, g.n_rows, g.n, NB, H, W, g.acc, g.acc_bytes,
+                                              (float*)g.out, g.maps, g.map_of, 0, 28, 44, nullptr);
+     }},
+    {"event_scatter_ring:", "ring=", "n_slots=", true, false, false,
+     [](const Args& g) {
+       return ess_event_scatter_ring(g.t, a, a, g.p, g.words, w, w, g.words, g.span, g.n_rows, g.n, NB, H, W, g.acc, g.acc_bytes, nullptr);
+     }},
+    {"event_scatter_ring_trilinear:", "ring=", "n_slots=", true, false, true,
+     [](const Args& g) {
+       return ess_event_scatter_ring_trilinear(g.t, a, a, g.p, g.words, w, w, g.words, g.span, g.n_rows, g.n, NB, H, W, g.acc, g.acc_bytes,
+                                               g.maps, g.map_of, 0, 28, 44, nullptr);
+     }},
+};
+
+template <class F>
+Args with(F&& change) {
+  Args g;
+  change(g);
+  return g;
+}
+
+void check_source(const Source& s) {
+  auto refused = [&](const Args& g, const char* needle, const char* what) { expect_refused(s.call(g), needle, s.entry, what); };
+  refused(with([](Args& g) { g.t = nullptr; }), "null", "a null first pointer");
+  refused(with([](Args& g) { g.words = nullptr; }), "null", "a null device word");
+  refused(with([](Args& g) { g.acc = nullptr; }), "null", "a null acc");
+  if (s.with_out) refused(with([](Args& g) { g.out = nullptr; }), "null", "a null out");
+  for (int32_t n : {0, -1, 65536}) refused(with([&](Args& g) { g.n = n; }), s.n, "a count out of range");
+  const int64_t bad_spans[] = {0, -16, ((int64_t)1 << 22) + 16, INT64_MAX, INT64_MIN};
+  for (int64_t span : bad_spans) refused(with([&](Args& g) { g.span = span; }), s.span, "a span out of range");
+  if (std::strcmp(s.span, "capacity=") != 0)
+    for (int64_t span : {8, 24, 1003}) refused(with([&](Args& g) { g.span = span; }), "multiple of 16", "a span that misaligns the rows");
+  if (s.ring) refused(with([](Args& g) { g.n_rows = 0; }), "n_rows=0", "n_rows 0");
+  refused(with([](Args& g) { g.acc_bytes -= 8; }), "acc has", "a short acc");
+  refused(with([](Args& g) { g.n = 2; }), "acc has", "acc sized for one grid of two");
+  refused(with([](Args& g) { g.t = block + 8; }), "16-byte aligned", "a misaligned first pointer");
+  if (std::strcmp(s.span, "capacity=") != 0) refused(with([](Args& g) { g.p = block + 1; }), "16-byte aligned", "a misaligned p");
+  refused(with([](Args& g) { g.acc = block + 8; }), "16-byte aligned", "a misaligned acc");
+  if (s.with_out) refused(with([](Args& g) { g.out = block + 4; }), "16-byte aligned", "a misaligned out");
+  if (s.rectify) {
+    refused(with([](Args& g) { g.map_of = nullptr; }), "null map_of", "a null map_of");
+    refused(with([](Args& g) { g.maps = (const float*)block; }), "maps must be null", "maps with n_maps 0");
+  }
+}
+
+// the two loader finishes: window false -> ess_event_grid_finish
+struct Finish {
+  const int32_t* counts = w;
+  int32_t n_slots = 1, crop_rows = 20, resize_height = 26, resize_width = 44, out_rows = 22, normalize = 1;
+  void* acc = a;
+  size_t acc_bytes = (size_t)NB * H * W * 8;
+  const int32_t* words = w;
+  int32_t slots_per_group = 1, win_height = 12, win_width = 20;
+  void* out = a;
+  void* workspace = a;
+  size_t workspace_bytes = ess_event_grid_finish_workspace(1, NB, H, W);
+};
+
+int finish(bool window, const Finish& f) {
+  if (window)
+    return ess_event_grid_finish_window(f.counts, f.n_slots, NB, H, W, f.acc, f.acc_bytes, f.crop_rows, f.resize_height, f.resize_width,
+                                        f.out_rows, f.normalize, f.words, f.slots_per_group, f.win_height, f.win_width, (float*)f.out,
+                                        f.workspace, f.workspace_bytes, nullptr);
+  return ess_event_grid_finish(f.counts, f.n_slots, NB, H, W, f.acc, f.acc_bytes, f.crop_rows, f.resize_height, f.resize_width, f.out_rows,
+                               f.normalize, (float*)f.out, f.workspace, f.workspace_bytes, nullptr);
+}
+
+void check_finish(bool window) {
+  const char* entry = window ? "event_grid_finish_window:" : "event_grid_finish:";
+  auto refused = [&](auto&& change, const char* needle, const char* what) {
+    Finish f;
+    change(f);
+    expect_refused(finish(window, f), needle, entry, what);
+  };
+  refused([](Finish& f) { f.counts = nullptr; }, "null", "null counts");
+  refused([](Finish& f) { f.acc = nullptr; }, "null", "a null acc");
+  refused([](Finish& f) { f.out = nullptr; }, "null", "a null out");
+  refused([](Finish& f) { f.workspace = nullptr; }, "null", "a null workspace");
+  for (int32_t n : {0, 65536}) refused([&](Finish& f) { f.n_slots = n; }, "n_slots=", "a count out of range");
+  for (int32_t v : {0, H + 1}) refused([&](Finish& f) { f.crop_rows = v; }, "crop_rows=", "crop_rows out of range");
+  refused([](Finish& f) { f.resize_width = 0; }, "resize_width=0", "resize_width 0");
+  for (int32_t v : {0, 27}) refused([&](Finish& f) { f.out_rows = v; }, "out_rows=", "out_rows out of range");
+  for (int32_t v : {-1, 3}) refused([&](Finish& f) { f.normalize = v; }, "normalize=", "an unknown normalisation");
+  refused([](Finish& f) { f.acc_bytes -= 8; }, "acc has", "a short acc");
+  refused([](Finish& f) { f.n_slots = 2; }, "acc has", "acc sized for one slot of two");
+  refused([](Finish& f) { f.workspace_bytes -= 1; }, "workspace has", "a short workspace");
+  refused([](Finish& f) { f.acc = block + 8; }, "16-byte aligned", "a misaligned acc");
+  refused([](Finish& f) { f.out = block + 4; }, "16-byte aligned", "a misaligned out");
+  refused([](Finish& f) { f.workspace = block + 8; }, "16-byte aligned", "a misaligned workspace");
+  if (!window) return;
+  refused([](Finish& f) { f.words = nullptr; }, "null", "null words");
+  refused([](Finish& f) { f.slots_per_group = 0; }, "slots_per_group=0", "slots_per_group 0");
+  for (int32_t v : {0, 23}) refused([&](Finish& f) { f.win_height = v; }, "win_height=", "win_height out of range");
+  for (int32_t v : {0, 45}) refused([&](Finish& f) { f.win_width = v; }, "win_width=", "win_width out of range");
+  refused([](Finish& f) { f.words = (const int32_t*)(block + 2); }, "4-byte aligned", "misaligned words");
+}
+
+void check_label() {
+  struct Label {
+    const uint8_t* src = block;
+    int32_t n = 2, src_height = 7, resize_height = 5, win_height = 4, win_width = 6;
+    const int32_t* words = w;
+    int64_t* out = (int64_t*)block;
+  };
+  auto refused = [&](auto&& change, const char* needle, const char* what) {
+    Label l;
+    change(l);
+    expect_refused(ess_label_window(l.src, l.n, l.src_height, 5, l.resize_height, 9, l.words, l.win_height, l.win_width, l.out, nullptr),
+                   needle, "label_window:", what);
+  };
+  refused([](Label& l) { l.src = nullptr; }, "null", "a null src");
+  refused([](Label& l) { l.words = nullptr; }, "null", "null words");
+  refused([](Label& l) { l.out = nullptr; }, "null", "a null out");
+  for (int32_t n : {0, 65536}) refused([&](Label& l) { l.n = n; }, "n=", "a count out of range");
+  refused([](Label& l) { l.src_height = 0; }, "must be positive", "src_height 0");
+  refused([](Label& l) { l.resize_height = 0; }, "must be positive", "resize_height 0");
+  for (int32_t v : {0, 6}) refused([&](Label& l) { l.win_height = v; }, "win_height=", "win_height out of range");
+  for (int32_t v : {0, 10}) refused([&](Label& l) { l.win_width = v; }, "win_width=", "win_width out of range");
+  refused([](Label& l) { l.words = (const int32_t*)(block + 2); }, "4-byte", "misaligned words");
+  refused([](Label& l) { l.out = (int64_t*)(block + 4); }, "8-byte aligned", "a misaligned out");
 }
 }  // namespace
 
-int main() {
-  alignas(16) static unsigned char block[64];
-  void* a = block;  // 16-byte aligned, never read
-  const int32_t* w = (const int32_t*)block;
-  const int32_t NB = 5, H = 24, W = 40;
+int main(int argc, char** argv) {
+  texts = argc > 1 && std::strcmp(argv[1], "--texts") == 0;
   const size_t need = ess_event_ingest_workspace(1, NB, H, W);
-  if (need != (size_t)NB * H * W * 8) {
+  if (need != (size_t)NB * H * W * 8 || ess_event_grid_finish_workspace(1, NB, H, W) == 0 || ess_event_ingest_workspace(0, NB, H, W) != 0) {
     std::printf("FAIL workspace: %zu\n", need);
     ++failures;
   }
-  // one null pointer at a time
-  for (int k = 0; k < 10; ++k) {
-    const void* p[10] = {a, a, a, a, w, w, w, w, a, a};
-    p[k] = nullptr;
-    const int rc = ess_event_ingest_ring(p[0], p[1], p[2], p[3], (const int32_t*)p[4], (const int32_t*)p[5], (const int32_t*)p[6],
-                                         (const int32_t*)p[7], 32, 1, 1, NB, H, W, (void*)p[8], need, (float*)p[9], nullptr);
-    char what[32];
-    std::snprintf(what, sizeof what, "null pointer %d", k);
-    expect_refused(rc, "null", what);
-  }
-  auto call = [&](int64_t ring, int32_t n_rows, int32_t n_slots, size_t acc_bytes, const void* p, void* out) {
-    return ess_event_ingest_ring(a, a, a, p, w, w, w, w, ring, n_rows, n_slots, NB, H, W, a, acc_bytes, (float*)out, nullptr);
-  };
-  const int64_t bad_rings[] = {0, -16, 8, 24, 1003, ((int64_t)1 << 22) + 16, INT64_MAX, INT64_MIN};
-  for (int64_t ring : bad_rings) expect_refused(call(ring, 1, 1, need, a, a), "ring=", "a bad ring");
-  expect_refused(call(24, 1, 1, need, a, a), "multiple of 16", "ring 24");
-  expect_refused(call(32, 0, 1, need, a, a), "n_rows", "n_rows 0");
-  expect_refused(call(32, 1, 0, need, a, a), "n_slots", "n_slots 0");
-  expect_refused(call(32, 1, 65536, need, a, a), "n_slots", "n_slots 65536");
-  expect_refused(call(32, 1, 1, need - 8, a, a), "acc has", "a short acc");
-  expect_refused(call(32, 1, 2, need, a, a), "acc has", "acc sized for one slot of two");
-  expect_refused(call(32, 1, 1, need, block + 1, a), "16-byte aligned", "a misaligned p");
-  expect_refused(call(32, 1, 1, need, a, block + 4), "16-byte aligned", "a misaligned out");
+  for (const Source& s : SOURCES) check_source(s);
+  check_finish(false);
+  check_finish(true);
+  check_label();
   if (failures) return 1;
-  std::printf("event_ring_args: every refusal as expected\n");
+  std::printf("event_ring_args: every refusal as expected (%d refusals)\n", refusals);
   return 0;
 }
