@@ -4,7 +4,9 @@
 // differ in how an event is LOADED; what an event adds is one function per FLAVOUR: scatter_event (temporal: integer pixels, bilinear
 // in time) for all three sources, scatter_event_trilinear (the DSEC grid: rectified float coordinates, eight corners) for the column
 // and the ring source, which share ONE loader, event_scatter_columns_kernel<Flavour, RING>: a template on the flavour and on whether
-// a window lies at the head of its row or anywhere inside a ring.
+// a window lies at the head of its row or anywhere inside a ring.  Two more flavours of that loader fill the reference loaders' other
+// event representations (ess_event_*_rep): SeparateFlavour (2 * bins planes, the polarities kept apart) and HistogramFlavour (two
+// planes of per-pixel counts, the time column not read); the finish kernels take a plane count, not a meaning.
 //
 // Behind the scatter, one kernel per job: event_finish_kernel<VEC, TAP> turns sums into a grid and zeroes them where each sum has
 // one reader -- the plain ingest (TAP false) and the loader finish at the identity geometry (TAP true); grid_map_kernel<VEC,
@@ -154,8 +156,10 @@ struct Rectify {
 constexpr int RECTIFY_NONE = -1;  // (ESS_RECTIFY_NONE of include/ess_hip.h)
 
 // What the two column loaders hand their events to.  open(): the slot's own words beyond count and format, false: the slot counts as
-// empty;  window(): the raw time words of the window's first and last event;  add(): one event's raw words.
+// empty;  window(): the raw time words of the window's first and last event;  add(): one event's raw words.  READS_TIME false: the
+// loader issues no load of the time column -- neither window()'s two words nor the groups' 2 x 16 B -- and hands add() a zero word.
 struct TemporalFlavour {
+  static constexpr bool READS_TIME = true;
   double first, dT;
   __device__ __forceinline__ bool open(int) { return true; }
   __device__ __forceinline__ void window(long long w_first, long long w_last, bool t_i64, int) {
@@ -170,7 +174,59 @@ struct TemporalFlavour {
   }
 };
 
+// ---- the two further event representations of the reference's loaders (generate_voxel_grid(separate_pol=True),
+// generate_event_histogram; the behaviour restated, not the code).  The kernel's plane count nb is the representation's C.
+//
+// Separate polarity, C = 2 * bins planes [positive bins; negative bins]: scatter_event's window, validity test, bin and weights --
+// left = fp32(1 - dts), right = fp32(dts) -- with NO sign (the reference adds |pol| * weight): a positive event (word == 1) adds to
+// planes ti and ti + 1, any other to planes bins + ti and bins + ti + 1, the right half only where ti + 1 < bins.  An event adds to
+// a voxel at most once (its two halves go to two planes), at most 2^40 in magnitude, and left + right = 1 up to rounding as for the
+// signed grid: check_source's 2^22-event bound (|acc| <= 2^62) and the statistics pass's sum |acc| <= 2^62 hold as they stand.
+struct SeparateFlavour {
+  static constexpr bool READS_TIME = true;
+  double first, dT;
+  __device__ __forceinline__ bool open(int) { return true; }
+  __device__ __forceinline__ void window(long long w_first, long long w_last, bool t_i64, int) {
+#pragma clang fp contract(off)
+    first = column_time(w_first, t_i64);
+    dT = column_time(w_last, t_i64) - first;
+    if (dT == 0) dT = 1.0;
+  }
+  __device__ __forceinline__ void add(long long tw, unsigned xh, unsigned yh, int p, bool t_i64, bool xy_u16, int nb, int H, int W,
+                                      size_t plane, long long* __restrict__ g) const {
+#pragma clang fp contract(off)
+    const int bins = nb >> 1;  // (nb is even: the entry points refuse any other)
+    const int xs = column_coordinate(xh, xy_u16), ys = column_coordinate(yh, xy_u16);
+    const double ts = ((double)(bins - 1) * (column_time(tw, t_i64) - first)) / dT;
+    if (!(xs < W && xs >= 0 && ys < H && ys >= 0 && ts >= 0 && ts < bins)) return;  // (a NaN time fails both comparisons)
+    const int ti = (int)ts;
+    const double dts = ts - ti;
+    const float left = (float)(1.0 - dts), right = (float)dts;
+    long long* gp = g + (size_t)(p == 1 ? ti : bins + ti) * plane + (size_t)ys * W + xs;
+    const long long ql = quantise(left), qr = quantise(right);
+    // (ti < bins holds: both planes lie inside the event's own half; a zero adds nothing)
+    if (ql != 0) atomicAdd((unsigned long long*)gp, (unsigned long long)ql);
+    if (ti + 1 < bins && qr != 0) atomicAdd((unsigned long long*)(gp + plane), (unsigned long long)qr);
+  }
+};
+
+// The histogram, C = 2 planes [negative counts, positive counts]: every event inside [0, W) x [0, H) adds 2^40 -- one count -- to
+// plane 1 where its polarity word equals 1, else to plane 0, whatever its time is (the time column is never loaded: 5 bytes an
+// event instead of 13).  One add of exactly 2^40 per event: 2^22 events keep |acc| <= 2^62.  A coordinate outside the grid drops the
+// event; the reference's x + width * y would wrap it into a neighbouring row or raise: not reproduced.
+struct HistogramFlavour {
+  static constexpr bool READS_TIME = false;
+  __device__ __forceinline__ bool open(int) { return true; }
+  __device__ __forceinline__ void add(long long, unsigned xh, unsigned yh, int p, bool, bool xy_u16, int, int H, int W, size_t plane,
+                                      long long* __restrict__ g) const {
+    const int xs = column_coordinate(xh, xy_u16), ys = column_coordinate(yh, xy_u16);
+    if (!(xs < W && xs >= 0 && ys < H && ys >= 0)) return;
+    atomicAdd((unsigned long long*)(g + (p == 1 ? plane : (size_t)0) + (size_t)ys * W + xs), (unsigned long long)INGEST_SCALE);
+  }
+};
+
 struct TrilinearFlavour {
+  static constexpr bool READS_TIME = true;
   const float2* map;  // the slot's map, nullptr: RECTIFY_NONE
   int map_h, map_w;
   long long w_first;
@@ -253,7 +309,7 @@ __global__ __launch_bounds__(INGEST_THREADS) void event_scatter_columns_kernel(c
   int64_t last_at = (int64_t)start + n - 1;  // (< 2 * ring)
   if constexpr (RING)
     if (last_at >= ring) last_at -= ring;
-  f.window(ts[start], ts[last_at], t_i64, nb);
+  if constexpr (Flavour::READS_TIME) f.window(ts[start], ts[last_at], t_i64, nb);
   const size_t plane = (size_t)H * W;
   long long* __restrict__ g = acc + (size_t)s * nb * plane;
   const i64x2* __restrict__ t2 = (const i64x2*)ts;               // two events
@@ -266,7 +322,11 @@ __global__ __launch_bounds__(INGEST_THREADS) void event_scatter_columns_kernel(c
     int64_t at = group0 + q;  // (< 2 * ring_groups: one subtraction wraps it; every group lies inside the row)
     if constexpr (RING)
       if (at >= ring_groups) at -= ring_groups;
-    const i64x2 ta = t2[2 * at], tb = t2[2 * at + 1];
+    i64x2 ta = {0, 0}, tb = {0, 0};
+    if constexpr (Flavour::READS_TIME) {
+      ta = t2[2 * at];
+      tb = t2[2 * at + 1];
+    }
     const uint2 xv = x4[at], yv = y4[at];
     const unsigned pv = p4[at];
     const long long tw[COLUMN_GROUP] = {ta[0], ta[1], tb[0], tb[1]};
@@ -916,6 +976,88 @@ extern "C" int ess_event_scatter_ring_trilinear(const void* t, const void* x, co
   if (rc) return rc;
   return launch_scatter<TrilinearFlavour, true>(what, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, bins, height, width,
                                                 acc, (hipStream_t)stream, rect);
+}
+
+// ---- the event representations: the column / ring ingest and the ring scatter with `channels` planes a slot and a representation
+// word that picks the loader's flavour.  ESS_EVENT_REP_SIGNED launches the very kernel of the entry points above.
+namespace {
+
+constexpr int EVENT_REP_SIGNED = 0, EVENT_REP_SEPARATE = 1, EVENT_REP_HISTOGRAM = 2;  // (ESS_EVENT_REP_* of include/ess_hip.h)
+
+// (in front of check_source, which sizes the workspace from `channels` where the signed entry points pass bins)
+int check_representation(const char* what, int32_t representation, int32_t channels) {
+  ESS_CHECK_ARG(channels > 0, "%s: channels=%d must be positive", what, (int)channels);
+  ESS_CHECK_ARG(representation == EVENT_REP_SIGNED || representation == EVENT_REP_SEPARATE || representation == EVENT_REP_HISTOGRAM,
+                "%s: representation=%d (0 signed, 1 separate polarity, 2 histogram)", what, (int)representation);
+  ESS_CHECK_ARG(representation != EVENT_REP_SEPARATE || channels % 2 == 0,
+                "%s: channels=%d must be even with representation=1 (separate polarity: 2 * bins planes)", what, (int)channels);
+  ESS_CHECK_ARG(representation != EVENT_REP_HISTOGRAM || channels == 2,
+                "%s: channels=%d must be 2 with representation=2 (histogram: negative counts, positive counts)", what, (int)channels);
+  return ESS_OK;
+}
+
+template <bool RING>
+int launch_scatter_rep(const char* status, int32_t representation, const void* t, const void* x, const void* y, const void* p,
+                       const int32_t* rows, const int32_t* starts, const int32_t* counts, const int32_t* formats, int64_t ring,
+                       int32_t n_rows, int32_t n_slots, int32_t channels, int32_t height, int32_t width, void* acc, hipStream_t st) {
+  if (representation == EVENT_REP_SEPARATE)
+    return launch_scatter<SeparateFlavour, RING>(status, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels, height,
+                                                 width, acc, st);
+  if (representation == EVENT_REP_HISTOGRAM)
+    return launch_scatter<HistogramFlavour, RING>(status, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels, height,
+                                                  width, acc, st);
+  return launch_scatter<TemporalFlavour, RING>(status, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels, height,
+                                               width, acc, st);
+}
+
+}  // namespace
+
+extern "C" int ess_event_scatter_ring_rep(const void* t, const void* x, const void* y, const void* p, const int32_t* rows,
+                                          const int32_t* starts, const int32_t* counts, const int32_t* formats, int64_t ring,
+                                          int32_t n_rows, int32_t n_slots, int32_t channels, int32_t height, int32_t width, void* acc,
+                                          size_t acc_bytes, int32_t representation, ess_stream_t stream) {
+  const char* what = "event_scatter_ring_rep";
+  int rc = check_representation(what, representation, channels);
+  if (rc) return rc;
+  rc = check_ring(what, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels, height, width, acc, acc_bytes, nullptr,
+                  false);
+  if (rc) return rc;
+  return launch_scatter_rep<true>(what, representation, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels, height,
+                                  width, acc, (hipStream_t)stream);
+}
+
+extern "C" int ess_event_ingest_ring_rep(const void* t, const void* x, const void* y, const void* p, const int32_t* rows,
+                                         const int32_t* starts, const int32_t* counts, const int32_t* formats, int64_t ring,
+                                         int32_t n_rows, int32_t n_slots, int32_t channels, int32_t height, int32_t width, void* acc,
+                                         size_t acc_bytes, float* out, int32_t representation, ess_stream_t stream) {
+  const char* what = "event_ingest_ring_rep";
+  int rc = check_representation(what, representation, channels);
+  if (rc) return rc;
+  rc = check_ring(what, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels, height, width, acc, acc_bytes, out);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  rc = launch_scatter_rep<true>("event_ingest_ring_rep(scatter)", representation, t, x, y, p, rows, starts, counts, formats, ring, n_rows,
+                                n_slots, channels, height, width, acc, st);
+  if (rc) return rc;
+  launch_finish<false>(counts, n_slots, (int64_t)channels * height * width, acc, nullptr, out, st);
+  return ess_launch_status("event_ingest_ring_rep(finish)");
+}
+
+extern "C" int ess_event_ingest_columns_rep(const void* t, const void* x, const void* y, const void* p, const int32_t* counts,
+                                            const int32_t* formats, int64_t stride, int32_t n_streams, int32_t channels, int32_t height,
+                                            int32_t width, void* acc, size_t acc_bytes, float* out, int32_t representation,
+                                            ess_stream_t stream) {
+  const char* what = "event_ingest_columns_rep";
+  int rc = check_representation(what, representation, channels);
+  if (rc) return rc;
+  rc = check_columns(what, t, x, y, p, counts, formats, stride, n_streams, channels, height, width, acc, acc_bytes, out);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  rc = launch_scatter_rep<false>("event_ingest_columns_rep(scatter)", representation, t, x, y, p, nullptr, nullptr, counts, formats, stride,
+                                 1, n_streams, channels, height, width, acc, st);
+  if (rc) return rc;
+  launch_finish<false>(counts, n_streams, (int64_t)channels * height * width, acc, nullptr, out, st);
+  return ess_launch_status("event_ingest_columns_rep(finish)");
 }
 
 // workspace: [n_slots] GridStat, then [n_slots][grid_stats_blocks][3] 8-byte partials

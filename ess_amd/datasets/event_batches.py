@@ -102,7 +102,7 @@ class _BatchStage:
 
 
 class EventBatchBuilder:
-    """build(samples) -> (events fp32 [B, T * bins, h, w], labels int64 [B, h, w] or None): the [data, label] batch a train step of
+    """build(samples) -> (events fp32 [B, T * C, h, w], labels int64 [B, h, w] or None): the [data, label] batch a train step of
     ESSSupervisedModel takes (the layout SyntheticPairedLoader(events_only=True) yields), from B samples of raw events.
 
     samples: B entries (EventColumns, label[, map index]) -- label: a uint8 [label_hw] array / CPU tensor, or None for EVERY sample of
@@ -111,7 +111,10 @@ class EventBatchBuilder:
     n // T events per window, window i = [i (n // T), (i + 1) (n // T)), the remainder at the end unused; n < T: an all-zero sample.
 
     Geometry (SequenceSegmenter's keywords): the events are voxelised at grid_hw=(Hs, Ws) with `bins` bins (voxel='temporal' |
-    'trilinear'), normalised over their non-zero voxels (grid_normalize=None | 'unbiased' | 'population'), the top grid_rows are
+    'trilinear') into C = `channels` planes a window -- representation=None: the signed grid, C = bins; 'separate_pol': C = 2 bins,
+    [positive bins; negative bins]; 'histogram': C = 2, [negative counts, positive counts], bins unused (hip.event_scatter_ring_rep;
+    both need voxel='temporal' and no rectify_maps) --, normalised over the non-zero voxels of all C planes, as the DDD17 loader
+    normalises the concatenated representation (grid_normalize=None | 'unbiased' | 'population'), the top grid_rows are
     resized bilinearly to grid_resize=(Hr, Wr), and the top `height` rows of `width` = Wr columns are the loader's grid.  The
     augmentation cuts a crop_hw=(h, w) window (default: the whole height x width) out of its horizontally flipped (p = 0.5) self, at a
     random place inside the rows crop_band=(first_row, n_rows) (default: all).  The label, label_hw=(Hl, Wl), is resized (nearest)
@@ -128,13 +131,14 @@ class EventBatchBuilder:
     graph=True: those launches are captured once per output set and replayed.  The returned tensors stay valid until the build after
     the next one: two output sets alternate.
 
-    Static device memory (allocated at the first batch): B T int64 sum grids [bins, Hs, Ws] + two fp32 output sets [B T, bins, h, w]
-    + 13 bytes per event of capacity -- DSEC, B = 8, T = 20, bins = 5: 1.97 GB + 2 x 0.92 GB; DDD17, B = 8, T = 20, bins = 5:
-    0.58 GB + 2 x 0.08 GB -- and the staging sets in pinned host memory: 2 x 13 bytes x B x event_capacity."""
+    Static device memory (allocated at the first batch): B T int64 sum grids [C, Hs, Ws] + two fp32 output sets [B T, C, h, w]
+    + 13 bytes per event of capacity -- DSEC, B = 8, T = 20, C = bins = 5: 1.97 GB + 2 x 0.92 GB; DDD17, B = 8, T = 20, C = bins = 5:
+    0.58 GB + 2 x 0.08 GB; 'separate_pol' doubles both terms (C = 10), 'histogram' takes 2 / 5 of them -- and the staging sets in
+    pinned host memory: 2 x 13 bytes x B x event_capacity."""
 
     def __init__(self, batch_size, sequence_steps, bins, event_capacity, grid_hw, height, width, label_hw, grid_rows=None,
                  grid_resize=None, grid_normalize=None, crop_hw=None, crop_band=None, voxel='temporal', rectify_maps=None,
-                 augmentation=True, seed=0, device=None, graph=False):
+                 augmentation=True, seed=0, device=None, graph=False, representation=None):
         for name, v in (('batch_size', batch_size), ('sequence_steps', sequence_steps), ('bins', bins)):
             if isinstance(v, bool) or not isinstance(v, int) or v < 1:
                 raise hip.EssHipError(f'{name}={v!r}: a positive int is needed')
@@ -160,6 +164,8 @@ class EventBatchBuilder:
                                   '(normalize_voxel_grid)')
         if voxel not in VOXEL_FLAVOURS:
             raise hip.EssHipError(f'voxel={voxel!r}: one of {VOXEL_FLAVOURS}')
+        self._rep = hip.event_representation(representation, voxel, rectify_maps)
+        self.representation, self.channels = representation, hip.event_rep_channels(self._rep, bins)
         self.augmentation = bool(augmentation)
         if crop_hw is None:
             if crop_band is not None:
@@ -259,8 +265,8 @@ class EventBatchBuilder:
             'words': torch.zeros(n_words, B * T, dtype=torch.int32, device=dev),
             'params': torch.zeros(B, 4, dtype=torch.int32, device=dev),
             'labels': torch.zeros((B,) + self.label_hw, dtype=torch.uint8, device=dev),
-            'acc': torch.zeros(B * T, self.bins, *self.grid_hw, dtype=torch.int64, device=dev),
-            'out': [(torch.zeros(B * T, self.bins, h, w, dtype=torch.float32, device=dev),
+            'acc': torch.zeros(B * T, self.channels, *self.grid_hw, dtype=torch.int64, device=dev),
+            'out': [(torch.zeros(B * T, self.channels, h, w, dtype=torch.float32, device=dev),
                      torch.zeros(B, h, w, dtype=torch.int64, device=dev)) for _ in range(2)],
             'maps': None if self.maps is None else self.maps.to(dev),
             'stage': [_BatchStage(B, T, cap, n_words, self.label_hw) for _ in range(2)],
@@ -276,6 +282,8 @@ class EventBatchBuilder:
         words = st['words']
         if self.voxel == 'trilinear':
             hip.event_scatter_ring_trilinear(*st['cols'], *words[:4], st['acc'], st['maps'], words[4])
+        elif self._rep != hip.EVENT_REP_SIGNED:
+            hip.event_scatter_ring_rep(*st['cols'], *words, st['acc'], self._rep)
         else:
             hip.event_scatter_ring(*st['cols'], *words, st['acc'])
         hip.event_grid_finish_window(words[2], st['acc'], ev, st['params'], self.sequence_steps, crop_rows=self.grid_rows,
@@ -338,7 +346,7 @@ class EventBatchBuilder:
         self.last_params = p
         ev, lab = st['out'][k]
         h, wd = self.crop_hw
-        return ev.view(B, T * self.bins, h, wd), (lab if labels is not None else None)
+        return ev.view(B, T * self.channels, h, wd), (lab if labels is not None else None)
 
 
 class EventBatchLoader:

@@ -81,6 +81,7 @@ EXPORTS = [
     'ess_event_ingest_columns_trilinear', 'ess_event_ingest_ring_trilinear', 'ess_seg_head_eval',
     'ess_event_scatter_ring', 'ess_event_scatter_ring_trilinear', 'ess_event_grid_finish_workspace', 'ess_event_grid_finish',
     'ess_event_grid_finish_window', 'ess_label_window',
+    'ess_event_scatter_ring_rep', 'ess_event_ingest_ring_rep', 'ess_event_ingest_columns_rep',
 ]
 
 
@@ -188,6 +189,9 @@ def lib():
             'ess_event_grid_finish': [P, I, I, I, I, P, c_size_t, I, I, I, I, I, P, P, c_size_t, P],
             'ess_event_grid_finish_window': [P, I, I, I, I, P, c_size_t, I, I, I, I, I, P, I, I, I, P, P, c_size_t, P],
             'ess_label_window': [P, I, I, I, I, I, P, I, I, P, P],
+            'ess_event_scatter_ring_rep': [P, P, P, P, P, P, P, P, I64, I, I, I, I, I, P, c_size_t, I, P],
+            'ess_event_ingest_ring_rep': [P, P, P, P, P, P, P, P, I64, I, I, I, I, I, P, c_size_t, P, I, P],
+            'ess_event_ingest_columns_rep': [P, P, P, P, P, P, I64, I, I, I, I, P, c_size_t, P, I, P],
         }
         for name, argtypes in sig.items():
             fn = getattr(L, name)
@@ -1094,6 +1098,117 @@ def event_scatter_ring(t, x, y, p, rows, starts, counts, formats, acc):
 def event_scatter_ring_trilinear(t, x, y, p, rows, starts, counts, formats, acc, maps=None, map_of=None):
     """event_scatter_ring in the trilinear flavour: the first half of event_ingest_ring_trilinear; maps, map_of: as there."""
     return _event_scatter_ring('event_scatter_ring_trilinear', t, x, y, p, rows, starts, counts, formats, acc, (maps, map_of))
+
+
+# The event REPRESENTATIONS of the column / ring ingest (ess_event_*_rep): what the reference's loaders hand the network
+# (datasets/data_util.py:6-126 there, `event_representation` and `separate_pol` in its settings).
+EVENT_REP_SIGNED = 0     # ESS_EVENT_REP_SIGNED: the signed temporal voxel grid, `bins` planes (event_ingest_columns' own grid)
+EVENT_REP_SEPARATE = 1   # ESS_EVENT_REP_SEPARATE: 2 * bins planes [positive bins; negative bins], both halves non-negative
+EVENT_REP_HISTOGRAM = 2  # ESS_EVENT_REP_HISTOGRAM: 2 planes [negative counts, positive counts]; the time column is not read
+_EVENT_REPS = (EVENT_REP_SIGNED, EVENT_REP_SEPARATE, EVENT_REP_HISTOGRAM)
+
+
+def _event_rep(fn, representation):
+    if isinstance(representation, bool) or not isinstance(representation, int) or representation not in _EVENT_REPS:
+        raise EssHipError(f'{fn}: representation={representation!r} must be EVENT_REP_SIGNED, EVENT_REP_SEPARATE or EVENT_REP_HISTOGRAM')
+    return representation
+
+
+def event_rep_channels(representation, bins):
+    """the planes C of one grid: bins (EVENT_REP_SIGNED), 2 * bins (EVENT_REP_SEPARATE), 2 whatever bins is (EVENT_REP_HISTOGRAM)"""
+    rep = _event_rep('event_rep_channels', representation)
+    if isinstance(bins, bool) or not isinstance(bins, int) or bins < 1:
+        raise EssHipError(f'event_rep_channels: bins={bins!r} must be a positive int')
+    return (bins, 2 * bins, 2)[rep]
+
+
+def _event_rep_of(fn, representation, channels, where):
+    """the representation word, checked against the planes of the grid it fills (`where` names the tensor they were read from)"""
+    rep = _event_rep(fn, representation)
+    if rep == EVENT_REP_SEPARATE and channels % 2:
+        raise EssHipError(f'{fn}: representation=EVENT_REP_SEPARATE fills 2 * bins planes [positive; negative], {where} has channels={channels}')
+    if rep == EVENT_REP_HISTOGRAM and channels != 2:
+        raise EssHipError(f'{fn}: representation=EVENT_REP_HISTOGRAM fills 2 planes [negative, positive], {where} has channels={channels}')
+    return rep
+
+
+EVENT_REPRESENTATIONS = {None: EVENT_REP_SIGNED, 'separate_pol': EVENT_REP_SEPARATE, 'histogram': EVENT_REP_HISTOGRAM}
+
+
+def event_representation(representation, voxel, rectify_maps):
+    """The representation= keyword of EventBatchBuilder and the segmenters, checked against their voxel= and rectify_maps= -> the
+    EVENT_REP_* word.  None: the signed grid, whatever the flavour.  'separate_pol' / 'histogram' are built by the temporal
+    loader on integer pixels: the reference's DSEC voxel_grid path ignores separate_pol too, and a rectified histogram is no grid
+    the reference builds."""
+    if not isinstance(representation, (str, type(None))) or representation not in EVENT_REPRESENTATIONS:
+        raise EssHipError(f"representation={representation!r}: None (the signed grid), 'separate_pol' or 'histogram'")
+    if representation is not None and (voxel != 'temporal' or rectify_maps is not None):
+        raise EssHipError(f"representation={representation!r} is built from integer pixels by the temporal loader: it needs "
+                          f"voxel='temporal' and rectify_maps=None (got voxel={voxel!r}, rectify_maps "
+                          f"{'given' if rectify_maps is not None else 'None'})")
+    return EVENT_REPRESENTATIONS[representation]
+
+
+def event_scatter_ring_rep(t, x, y, p, rows, starts, counts, formats, acc, representation):
+    """event_scatter_ring in one of the three event representations.  acc: device int64 [n_slots, C, H, W], ALL ZERO before the
+    call; representation (a host int, fixed per call):
+        EVENT_REP_SIGNED:    C = bins; event_scatter_ring's own sums, bit for bit;
+        EVENT_REP_SEPARATE:  C = 2 * bins (even).  Window, validity test, bin and the two weights left = fp32(1 - dts), right =
+                             fp32(dts) are event_scatter_ring's; NO sign is applied (the reference adds |pol| * weight): a positive
+                             event (byte == 1) adds to planes ti and ti + 1, any other to planes bins + ti and bins + ti + 1, the
+                             right half dropped where ti + 1 == bins.  sums[b] - sums[bins + b] is the signed grid's sum, exactly;
+        EVENT_REP_HISTOGRAM: C = 2.  Plane 0 counts the events of pixel (x, y) whose polarity byte is not 1, plane 1 those whose
+                             byte is 1, 2^40 each.  The time column is NOT READ (t still gives the rings' shape): an event counts
+                             whatever its time is, a NaN included.  Coordinates outside [0, W) x [0, H) are DROPPED; the reference
+                             neither checks nor drops them (x + width * y wraps into a neighbouring row, or raises): not reproduced.
+    Counts, rows, starts, format words and INGEST_KEEP: as event_ingest_ring.  The sums stay a pure function of the SET of events;
+    event_grid_finish* turn them into grids over all C planes of a slot.  -> acc"""
+    fn = 'event_scatter_ring_rep'
+    words = (('t', t), ('x', x), ('y', y), ('p', p), ('rows', rows), ('starts', starts), ('counts', counts), ('formats', formats))
+    named = words + (('acc', acc),)
+    _are_tensors(fn, named)
+    n_slots, C, H, W = _finish_acc(fn, acc, 'H, W')
+    rep = _event_rep_of(fn, representation, C, 'acc')
+    _event_columns(fn, words, n_slots, ring=True)
+    _on_device(fn, named)
+    n_rows, ring = t.shape
+    _check(lib().ess_event_scatter_ring_rep(*_column_pointers(words), ring, n_rows, n_slots, C, H, W, c_void_p(acc.data_ptr()),
+                                            acc.numel() * 8, rep, stream()), 'ess_' + fn)
+    return acc
+
+
+def event_ingest_ring_rep(t, x, y, p, rows, starts, counts, formats, out, representation, acc=None):
+    """event_ingest_ring in one of the three event representations (event_scatter_ring_rep names them): the scatter and the plain
+    finish, out fp32 [n_slots, C, H, W] = (float)sums * 2^-40, returned.  EVENT_REP_SIGNED gives event_ingest_ring's bits.
+    Everything else: as event_ingest_ring; acc: at least n_slots * C * H * W elements."""
+    fn = 'event_ingest_ring_rep'
+    words = (('t', t), ('x', x), ('y', y), ('p', p), ('rows', rows), ('starts', starts), ('counts', counts), ('formats', formats))
+    named = words + (('out', out),) + ((('acc', acc),) if acc is not None else ())
+    _are_tensors(fn, named)
+    n_slots, C, H, W = _ingest_out(fn, out, 'n_slots')
+    rep = _event_rep_of(fn, representation, C, 'out')
+    _event_columns(fn, words, n_slots, ring=True)
+    acc = _ingest_acc(fn, named, acc, out)
+    n_rows, ring = t.shape
+    _check(lib().ess_event_ingest_ring_rep(*_column_pointers(words), ring, n_rows, n_slots, C, H, W, c_void_p(acc.data_ptr()),
+                                           acc.numel() * 8, c_void_p(out.data_ptr()), rep, stream()), 'ess_' + fn)
+    return out
+
+
+def event_ingest_columns_rep(t, x, y, p, counts, formats, out, representation, acc=None):
+    """event_ingest_columns in one of the three event representations (event_scatter_ring_rep names them): out fp32 [S, C, H, W],
+    returned.  EVENT_REP_SIGNED gives event_ingest_columns' bits.  Everything else: as event_ingest_columns."""
+    fn = 'event_ingest_columns_rep'
+    words = (('t', t), ('x', x), ('y', y), ('p', p), ('counts', counts), ('formats', formats))
+    named = words + (('out', out),) + ((('acc', acc),) if acc is not None else ())
+    _are_tensors(fn, named)
+    S, C, H, W = _ingest_out(fn, out, 'S')
+    rep = _event_rep_of(fn, representation, C, 'out')
+    _event_columns(fn, words, S, ring=False)
+    acc = _ingest_acc(fn, named, acc, out)
+    _check(lib().ess_event_ingest_columns_rep(*_column_pointers(words), t.shape[1], S, C, H, W, c_void_p(acc.data_ptr()),
+                                              acc.numel() * 8, c_void_p(out.data_ptr()), rep, stream()), 'ess_' + fn)
+    return out
 
 
 def _finish_acc(fn, acc, dims):

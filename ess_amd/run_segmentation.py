@@ -309,6 +309,19 @@ def _voxel_flavour(voxel, layout, event_capacity):
     return voxel
 
 
+def _event_representation(representation, voxel, rectify_maps, num_bins):
+    """The segmenters' representation argument, checked against voxel, rectify_maps (hip.event_representation) and the planes
+    C = encoder.num_bins the network reads -> the hip.EVENT_REP_* word"""
+    rep = hip.event_representation(representation, voxel, rectify_maps)
+    if rep == hip.EVENT_REP_SEPARATE and num_bins % 2:
+        raise hip.EssHipError(f"representation='separate_pol' fills 2 * bins planes [positive bins; negative bins]: the encoder's "
+                              f'num_bins={num_bins} must be even')
+    if rep == hip.EVENT_REP_HISTOGRAM and num_bins != 2:
+        raise hip.EssHipError(f"representation='histogram' fills 2 planes [negative counts, positive counts]: the encoder's "
+                              f'num_bins={num_bins} must be 2')
+    return rep
+
+
 def _rectify_maps(rectify_maps, voxel, n_streams):
     """MultiStreamSegmenter's rectify_maps argument, checked -> (the distinct maps stacked, host fp32 [n_maps, map_h, map_w, 2], or
     None where no stream has one; per stream its map's number or hip.RECTIFY_NONE).  Entries that are the same object share a map."""
@@ -466,13 +479,28 @@ class MultiStreamSegmenter(GraphedWindowState):
     camera: one).  A stream without a map takes its integer pixels as coordinates.  The stream's map number is a device word that
     travels with its count and format (the words grow by one row: [3, S] / [5, S]; still one upload a round), and a compacted round
     writes it per slot.  Not reproduced from the DSEC loader: VoxelGrid(normalize=True)'s own per-grid normalisation in front of the
-    event preprocessor's -- the grid enters the round as the raw sums."""
+    event preprocessor's -- the grid enters the round as the raw sums.
+
+    representation='separate_pol' | 'histogram' (with event_layout='columns' or 'ring', voxel='temporal' and no rectify_maps; None,
+    the default, is the signed grid of everything above): the round starts with hip.event_ingest_columns_rep /
+    hip.event_ingest_ring_rep and fills the C = encoder.num_bins planes the network reads with the reference loaders' other two
+    event representations -- 'separate_pol': C even, [C / 2 positive bins; C / 2 negative bins], both non-negative; 'histogram':
+    C == 2, [negative counts, positive counts], the time column not read -- summed in 64-bit fixed point like the signed grid.  The
+    static grids and int64 sums are sized by C as before: 5 bins kept apart are C = 10, twice the signed grid's memory."""
 
     def __init__(self, encoder, decoder, height, width, options, n_streams, device=None, graph=False, copy=True, palette=None,
                  want_confidence=False, out_hw=None, compact=False, compact_buckets=None, event_capacity=None, event_layout='records',
-                 ring_capacity=None, window_events=None, window_duration=None, window_stride=None, voxel='temporal', rectify_maps=None):
+                 ring_capacity=None, window_events=None, window_duration=None, window_stride=None, voxel='temporal', rectify_maps=None,
+                 representation=None):
         if not isinstance(n_streams, int) or isinstance(n_streams, bool) or n_streams < 1:
             raise hip.EssHipError(f'n_streams={n_streams!r}: a positive number of streams is needed')
+        self.representation = representation
+        if representation is not None:  # (refused before the models reach the device)
+            self._rep = _event_representation(representation, voxel, rectify_maps, encoder.num_bins)
+            if event_capacity is None or event_layout not in ('columns', 'ring'):
+                raise hip.EssHipError(f"representation={representation!r} is built from raw event columns inside the round: pass "
+                                      f"event_capacity=N and event_layout='columns' or 'ring' (got event_layout={event_layout!r}, "
+                                      f'event_capacity={event_capacity!r})')
         self.compact = bool(compact)
         self.buckets = _compact_buckets(n_streams, compact_buckets) if self.compact else ()
         self.n_streams = n_streams
@@ -518,6 +546,7 @@ class MultiStreamSegmenter(GraphedWindowState):
     # ---- event ingest (event_capacity=N): static record / count buffers the captured round reads, pinned staging in front of them
     event_capacity = ring_capacity = _records = _columns = _counts = _formats = _acc = _ring = _maps = None
     voxel = 'temporal'
+    representation, _rep = None, hip.EVENT_REP_SIGNED
 
     def _build_ingest(self):
         """Device records [S, N, 16], counts [S] and the int64 sums of hip.event_ingest (zeroed here, once), and two pinned staging
@@ -688,16 +717,20 @@ class MultiStreamSegmenter(GraphedWindowState):
     def _ingest(self, ev, b=None):
         """the round's first launches: the static event buffers (b: their first b slots) -> the grids ev, inside the capture"""
         cut = (lambda v: v) if b is None else (lambda v: v[:b])
-        tri = self.voxel == 'trilinear'
+        tri, rep = self.voxel == 'trilinear', self._rep
         if self._ring is not None:  # (every row of the rings stays in reach: a slot names its row)
             if tri:
                 hip.event_ingest_ring_trilinear(*self._ring, *(cut(w) for w in self._words[:4]), ev, self._maps, cut(self._words[4]), self._acc)
+            elif rep != hip.EVENT_REP_SIGNED:
+                hip.event_ingest_ring_rep(*self._ring, *(cut(w) for w in self._words), ev, rep, self._acc)
             else:
                 hip.event_ingest_ring(*self._ring, *(cut(w) for w in self._words), ev, self._acc)
         elif self._columns is not None:
             if tri:
                 hip.event_ingest_columns_trilinear(*(cut(c) for c in self._columns), cut(self._counts), cut(self._formats), ev, self._maps,
                                                    cut(self._words[2]), self._acc)
+            elif rep != hip.EVENT_REP_SIGNED:
+                hip.event_ingest_columns_rep(*(cut(c) for c in self._columns), cut(self._counts), cut(self._formats), ev, rep, self._acc)
             else:
                 hip.event_ingest_columns(*(cut(c) for c in self._columns), cut(self._counts), cut(self._formats), ev, self._acc)
         else:

@@ -23,8 +23,8 @@ import torch
 from . import hip
 from .e2vid.image_reconstructor import ImageReconstructor
 from .evaluation.metrics import semseg_accum_confusion_to_acc, semseg_accum_confusion_to_iou
-from .run_segmentation import (VOXEL_FLAVOURS, MultiSegmentationResult, _event_capacity, _models_from_checkpoints, _rectify_maps,
-                               _RingStage)
+from .run_segmentation import (VOXEL_FLAVOURS, MultiSegmentationResult, _event_capacity, _event_representation,
+                               _models_from_checkpoints, _rectify_maps, _RingStage)
 
 
 class _SequenceStage(_RingStage):
@@ -58,7 +58,7 @@ class SequenceSegmenter:
     feed(stream, EventColumns): packets of any size as they arrive, through a pinned mirror into the stream's ring of ring_capacity
     events in device memory (default 2 T N_w, in [T N_w, 2^22], rounded up to a multiple of 16).  No window is pending here and
     nothing is refused for room: old events are overwritten, and segment_at refuses a sequence that reaches behind the ring.
-    voxel / rectify_maps: as MultiStreamSegmenter(event_layout='ring').  graph=True: the round's device work -- ring ingest over
+    voxel / rectify_maps / representation: as MultiStreamSegmenter(event_layout='ring').  graph=True: the round's device work -- ring ingest over
     the T S slots, normalisation, T encoder steps, decoder, scoring head -- is captured once (n_captures stays 1); a round is then
     one upload of the slot words, the ground-truth rows that were given, and one replay.  copy, palette, want_confidence, out_hw:
     as StreamingSegmenter.  Each stream's results are those it gets alone (n_streams=1) under the two process-wide batch-size
@@ -68,7 +68,7 @@ class SequenceSegmenter:
     summed rows (evaluation.metrics' formulas); reset_metrics(streams=None) zeroes rows; drop_feed(streams=None) forgets rings.
 
     Memory: the T S grids of a round are static buffers -- fp32 [T S, num_bins, H, W] plus the ingest's int64 sums of the same
-    shape: at T = 20, S = 8, 5 x 440 x 640 about 0.9 GB + 1.8 GB -- and the rings take 13 bytes per event on the device and again in
+    shape: at T = 20, S = 8, 5 x 440 x 640 about 0.9 GB + 1.8 GB (num_bins = 10, 'separate_pol' of 5 bins: twice that) -- and the rings take 13 bytes per event on the device and again in
     pinned host memory (T = 20, N_w = 100 000, S = 8: 0.42 GB each).
 
     The LOADER's grid (all opt-in; with none of these keywords a round goes through hip.event_ingest_ring* as before).  The reference
@@ -89,7 +89,7 @@ class SequenceSegmenter:
     def __init__(self, encoder, decoder, height, width, options, n_streams, sequence_steps=None, window_events=None, ring_capacity=None,
                  voxel='temporal', rectify_maps=None, graph=False, copy=True, palette=None, want_confidence=False, out_hw=None,
                  ignore_index=255, device=None, window_duration=None, grid_hw=None, grid_rows=None, grid_resize=None,
-                 grid_normalize=None):
+                 grid_normalize=None, representation=None):
         if not isinstance(n_streams, int) or isinstance(n_streams, bool) or n_streams < 1:
             raise hip.EssHipError(f'n_streams={n_streams!r}: a positive number of streams is needed')
         T = sequence_steps
@@ -125,6 +125,8 @@ class SequenceSegmenter:
         self.n_streams, self.sequence_steps, self.window_events = n_streams, T, (N_w if window_duration is None else None)
         self.ring_capacity = R = hip.event_column_stride(R)
         self.voxel, self.ignore_index = voxel, ignore_index
+        self.representation = representation
+        self._rep = _event_representation(representation, voxel, rectify_maps, encoder.num_bins)  # (the last refusal before the device)
         self.copy_outputs = bool(copy)
         self.device = device if device is not None else torch.device('cuda:0')
         self.model = encoder.to(self.device).eval()
@@ -284,12 +286,16 @@ class SequenceSegmenter:
             if self._loader_grid:  # the loader's grid: the sums at the size the loader voxelises at, then its normalise / cut / resize
                 if self.voxel == 'trilinear':
                     hip.event_scatter_ring_trilinear(*self._ring, *self._words[:4], self._acc, self._maps, self._words[4])
+                elif self._rep != hip.EVENT_REP_SIGNED:
+                    hip.event_scatter_ring_rep(*self._ring, *self._words, self._acc, self._rep)
                 else:
                     hip.event_scatter_ring(*self._ring, *self._words, self._acc)
                 crop_rows, resize, normalize = self._grid
                 hip.event_grid_finish(self._words[2], self._acc, ev, crop_rows=crop_rows, resize=resize, normalize=normalize)
             elif self.voxel == 'trilinear':
                 hip.event_ingest_ring_trilinear(*self._ring, *self._words[:4], ev, self._maps, self._words[4], self._acc)
+            elif self._rep != hip.EVENT_REP_SIGNED:
+                hip.event_ingest_ring_rep(*self._ring, *self._words, ev, self._rep, self._acc)
             else:
                 hip.event_ingest_ring(*self._ring, *self._words, ev, self._acc)
             return self._round_from(ev)

@@ -533,6 +533,42 @@ int ess_event_grid_finish(const int32_t* counts, int32_t n_slots, int32_t bins, 
                           size_t acc_bytes, int32_t crop_rows, int32_t resize_height, int32_t resize_width, int32_t out_rows,
                           int32_t normalize, float* out, void* workspace, size_t workspace_bytes, ess_stream_t stream);
 
+/* The event REPRESENTATIONS of the column / ring ingest -- PURELY ADDITIVE to ABI 110 (ess_version() is unchanged; no existing entry
+ * point changes).  The reference's loaders hand the network one of three representations of a window's events; the entry points
+ * above build the first.  These three take the arguments of ess_event_scatter_ring, ess_event_ingest_ring and
+ * ess_event_ingest_columns with `channels` -- the planes C of one grid, acc [n][channels][height][width] -- where those take `bins`,
+ * and, in front of the stream, a representation word (host side, fixed per call):
+ *   ESS_EVENT_REP_SIGNED (0):    C = bins.  The signed temporal grid: the very kernel, and the bits, of the entry points above.
+ *   ESS_EVENT_REP_SEPARATE (1):  C = 2 * bins, [positive bins; negative bins] (generate_voxel_grid(separate_pol=True)); channels
+ *     must be even.  first, dT (dT == 0 -> 1), ts = ((bins - 1) * (t - first)) / dT, the validity test, ti = (int)ts, dts = ts - ti,
+ *     left = (float)(1 - dts), right = (float)dts are ess_event_ingest_columns' own; no sign is applied.  A positive event (polarity
+ *     byte == 1) adds llrint(left * 2^40) to plane ti and llrint(right * 2^40) to plane ti + 1 if ti + 1 < bins; any other polarity
+ *     adds them to planes bins + ti and bins + ti + 1 under the same test.  Both halves are non-negative, and
+ *     acc[b] - acc[bins + b] equals the signed grid's sum exactly.
+ *   ESS_EVENT_REP_HISTOGRAM (2): C = 2, [negative counts, positive counts] (generate_event_histogram); channels must be 2.  Every
+ *     event whose (x, y) lies in [0, width) x [0, height) adds 2^40 to plane 1 where its polarity byte == 1, else to plane 0.  The
+ *     time column is NOT READ (t must still be a valid 16-byte aligned pointer): 5 instead of 13 bytes an event, and an event counts
+ *     whatever its time is, a NaN included.  A coordinate outside the grid drops the event; the reference neither checks nor drops
+ *     (x + width * y wraps into a neighbouring row, or raises): that is not reproduced.
+ * An event adds to a voxel at most once, at most 2^40 in magnitude: ring / stride <= 2^22 keep the sums inside int64 as above, and
+ * acc stays a pure function of the SET of events.  Counts, rows, starts, format words, ESS_INGEST_KEEP, alignment, acc (all zero
+ * before; all zero again behind the two ingest calls, the sums behind the scatter) and out: as for the entry points above.
+ * ess_event_grid_finish / _window take acc with bins = channels: they normalise over all C planes of a slot, as the DDD17 loader
+ * normalises the concatenated representation.  Any other representation word, an odd channels with 1, channels != 2 with 2:
+ * ESS_EINVAL.                                                                                                                   */
+enum { ESS_EVENT_REP_SIGNED = 0, ESS_EVENT_REP_SEPARATE = 1, ESS_EVENT_REP_HISTOGRAM = 2 };
+int ess_event_scatter_ring_rep(const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
+                               const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots,
+                               int32_t channels, int32_t height, int32_t width, void* acc, size_t acc_bytes, int32_t representation,
+                               ess_stream_t stream);
+int ess_event_ingest_ring_rep(const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
+                              const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots,
+                              int32_t channels, int32_t height, int32_t width, void* acc, size_t acc_bytes, float* out,
+                              int32_t representation, ess_stream_t stream);
+int ess_event_ingest_columns_rep(const void* t, const void* x, const void* y, const void* p, const int32_t* counts,
+                                 const int32_t* formats, int64_t stride, int32_t n_streams, int32_t channels, int32_t height,
+                                 int32_t width, void* acc, size_t acc_bytes, float* out, int32_t representation, ess_stream_t stream);
+
 /* Training batches from events: the loaders' augmentation where the grid is written -- PURELY ADDITIVE to ABI 110.
  * DSEC flips horizontally with p = 0.5 (DSEC/dataset/sequence.py:291-295); DDD17 flips, then crops 120 x 216 at random inside the
  * bottom 120 rows (datasets/ddd17_events_loader.py:87-96, 173-183).  Both are index permutations of the finished grid and of its

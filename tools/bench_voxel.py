@@ -24,7 +24,11 @@ the ring ingest as it is (hip.event_ingest_ring*: the grid at the sensor's size)
 composition the older pieces allow (the ring ingest, hip.voxel_normalize_, torch's F.interpolate on the device, a slice made
 contiguous), alternating.  --loader-finish-only skips everything in front of these rows.
 
+And the event REPRESENTATIONS (representations()): the signed ring ingest against hip.event_ingest_ring_rep's separate-polarity and
+histogram flavours on the same rings, at 480 x 640 and 260 x 346.
+
 usage: python tools/bench_voxel.py --ingest --slices 8 --events 100000 --bins 5
+       python tools/bench_voxel.py --ingest --representations-only --slices 8 --events 100000 --bins 5
        python tools/bench_voxel.py --ingest --loader-finish-only --slices 160 --events 100000 --bins 5 --reps 20"""
 import argparse
 import json
@@ -48,6 +52,7 @@ def main():
     ap.add_argument('--normalize', action='store_true')
     ap.add_argument('--ingest', action='store_true', help='hip.event_ingest against hip.voxel_grid_temporal (see above)')
     ap.add_argument('--loader-finish-only', action='store_true', help='(with --ingest) only the loader-finish rows')
+    ap.add_argument('--representations-only', action='store_true', help='(with --ingest) only the event-representation rows')
     a = ap.parse_args()
     if a.ingest:
         return ingest(a)
@@ -173,11 +178,78 @@ def loader_finish(a):
     return rows_out
 
 
+def representations(a):
+    """The event representations beside the signed grid: hip.event_ingest_ring (scatter + finish, `bins` planes) against
+    hip.event_ingest_ring_rep in the separate-polarity (2 * bins planes) and the histogram (2 planes, no time loads) flavour, on
+    the same int64 / uint16 rings read from an unaligned start, at the DSEC and the DDD17 sensor size; three alternating rounds of
+    a.reps calls each.  A library without the _rep entry points (an older build) gets the signed row alone.  -> rows for the JSON"""
+    import numpy as np
+    from ess_amd import hip
+    S, n, bins = a.slices, a.events, a.bins
+    dev = torch.device('cuda:0')
+    have = hasattr(hip, 'event_ingest_ring_rep')
+    stride = hip.event_column_stride(n)
+    ring, start = 2 * stride, 3
+    rows = {}
+    for H, W in ((480, 640), (260, 346)):
+        g = np.random.default_rng(1)
+        at = (start + np.arange(n)) % ring
+        cols = [np.zeros((S, ring), d) for d in (np.int64, np.uint16, np.uint16, np.uint8)]
+        cols[0][:, at] = np.sort(g.integers(0, 30_000, (S, n)), axis=1)
+        cols[1][:, at], cols[2][:, at], cols[3][:, at] = g.integers(0, W, (S, n)), g.integers(0, H, (S, n)), g.integers(0, 2, (S, n))
+        dcols = tuple(torch.from_numpy(c.view(np.int16) if c.dtype == np.uint16 else c).to(dev) for c in cols)
+        words = (torch.arange(S, dtype=torch.int32, device=dev), torch.full((S,), start, dtype=torch.int32, device=dev),
+                 torch.full((S,), n, dtype=torch.int32, device=dev),
+                 torch.full((S,), hip.EVCOL_XY_U16 | hip.EVCOL_T_I64, dtype=torch.int32, device=dev))
+        buffers = lambda C: (torch.empty(S, C, H, W, device=dev), torch.zeros(S, C, H, W, dtype=torch.int64, device=dev))  # noqa: E731
+        out_s, acc_s = buffers(bins)
+        ways = {'signed_event_ingest_ring': lambda: hip.event_ingest_ring(*dcols, *words, out_s, acc=acc_s)}
+        if have:
+            out_p, acc_p = buffers(2 * bins)
+            out_h, acc_h = buffers(2)
+            ways['signed_event_ingest_ring_rep'] = lambda: hip.event_ingest_ring_rep(*dcols, *words, out_s, hip.EVENT_REP_SIGNED, acc=acc_s)
+            ways['separate_pol'] = lambda: hip.event_ingest_ring_rep(*dcols, *words, out_p, hip.EVENT_REP_SEPARATE, acc=acc_p)
+            ways['histogram'] = lambda: hip.event_ingest_ring_rep(*dcols, *words, out_h, hip.EVENT_REP_HISTOGRAM, acc=acc_h)
+        for fn in ways.values():  # warm-up: clocks, allocator
+            for _ in range(50):
+                fn()
+        torch.cuda.synchronize()
+        ms = {k: [] for k in ways}
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(3):
+            for k, fn in ways.items():
+                e0.record()
+                for _ in range(a.reps):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                ms[k].append(e0.elapsed_time(e1) / a.reps)
+        med = {k: sorted(v)[1] for k, v in ms.items()}
+        spread = max(ms['signed_event_ingest_ring']) - min(ms['signed_event_ingest_ring'])
+        row = {'ms_per_batch': {k: {'median': round(med[k], 5), 'min': round(min(v), 5), 'max': round(max(v), 5)} for k, v in ms.items()},
+               'signed_spread_ms': round(spread, 5)}
+        if have:
+            # what is timed is what the representations are: positive - negative = the signed grid, the counts add up to the events
+            signed = ways['signed_event_ingest_ring']().clone()
+            sep, hist = ways['separate_pol'](), ways['histogram']()
+            assert float((sep[:, :bins] - sep[:, bins:] - signed).abs().max()) <= 1e-5 * max(1.0, float(signed.abs().max()))
+            assert float(hist.sum()) == S * n and bool((sep >= 0).all()) and not bool(acc_p.any()) and not bool(acc_h.any())
+            for k in ('separate_pol', 'histogram', 'signed_event_ingest_ring_rep'):
+                row[f'{k}_over_signed'] = round(med[k] / med['signed_event_ingest_ring'], 3)
+                row[f'{k}_SLOWER_than_signed'] = bool(med[k] - med['signed_event_ingest_ring'] > spread)
+        rows[f'{H}x{W}'] = row
+    return {'workload': f'{S} streams x {n} events, bins={bins}, ring of {ring} from start {start}', 'reps': a.reps, 'rows': rows}
+
+
 def ingest(a):
     import numpy as np
     from ess_amd import hip
     from ess_amd.datasets.data_util import pack_event_records
     hip.lib()
+    if a.representations_only:
+        print(json.dumps({'metric': 'ring events -> grids in the three event representations, ms per batch', 'unit': 'ms',
+                          'representations': representations(a), 'data': 'synthetic'}))
+        return
     if a.loader_finish_only:
         print(json.dumps({'metric': 'ring events -> the loader\'s grids, ms per batch', 'unit': 'ms', 'reps': a.reps,
                           'loader_finish': loader_finish(a), 'data': 'synthetic'}))
@@ -315,7 +387,8 @@ def ingest(a):
         'int64_atomics_per_s': atomics / (scatter_ms * 1e-3) if scatter_ms > 0 else None,
         'fp32_atomics_per_s_of_voxel_grid_temporal_incl_memset': atomics / (med['voxel_grid_temporal'] * 1e-3),
         'finish_GBps': S * C * H * W * 12 / (med['event_ingest_finish_only'] * 1e-3) / 1e9,
-        'max_abs_diff_ingest_vs_temporal': err, 'loader_finish': loader_finish(a), 'data': 'synthetic'}))
+        'max_abs_diff_ingest_vs_temporal': err, 'loader_finish': loader_finish(a), 'representations': representations(a),
+        'data': 'synthetic'}))
 
 
 if __name__ == '__main__':

@@ -1,5 +1,5 @@
 // Stand-alone host program: the argument checks of every entry point of voxel_ingest.hip -- the ingest from records, columns and
-// rings in both flavours, the scatter-only ring calls, the two loader finishes and the label window.  The checks all come in front
+// rings in both flavours, the scatter-only ring calls, the three representation calls, the two loader finishes and the label window.  The checks all come in front
 // of any launch, so no device is needed.  Meant to be built with the host sanitizers and run on its own (a library loaded into python
 // is out of their reach):
 //
@@ -52,6 +52,7 @@ struct Args {
   void* out = a;
   const float* maps = nullptr;  // (n_maps = 0: maps must be null)
   const int32_t* map_of = w;
+  int32_t channels = NB, representation = 0;  // (the _rep entry points: the signed grid of NB planes)
 };
 
 struct Source {
@@ -60,6 +61,7 @@ struct Source {
   const char* n;     // the count's
   bool ring, with_out, rectify;
   int (*call)(const Args&);
+  bool rep = false;  // takes channels and a representation word
 };
 
 const Source SOURCES[] = {
@@ -93,6 +95,24 @@ const Source SOURCES[] = {
        return ess_event_scatter_ring_trilinear(g.t, a, a, g.p, g.words, w, w, g.words, g.span, g.n_rows, g.n, NB, H, W, g.acc, g.acc_bytes,
                                                g.maps, g.map_of, 0, 28, 44, nullptr);
      }},
+    {"event_scatter_ring_rep:", "ring=", "n_slots=", true, false, false,
+     [](const Args& g) {
+       return ess_event_scatter_ring_rep(g.t, a, a, g.p, g.words, w, w, g.words, g.span, g.n_rows, g.n, g.channels, H, W, g.acc, g.acc_bytes,
+                                         g.representation, nullptr);
+     },
+     true},
+    {"event_ingest_ring_rep:", "ring=", "n_slots=", true, true, false,
+     [](const Args& g) {
+       return ess_event_ingest_ring_rep(g.t, a, a, g.p, g.words, w, w, g.words, g.span, g.n_rows, g.n, g.channels, H, W, g.acc, g.acc_bytes,
+                                        (float*)g.out, g.representation, nullptr);
+     },
+     true},
+    {"event_ingest_columns_rep:", "stride=", "n_streams=", false, true, false,
+     [](const Args& g) {
+       return ess_event_ingest_columns_rep(g.t, a, a, g.p, w, g.words, g.span, g.n, g.channels, H, W, g.acc, g.acc_bytes, (float*)g.out,
+                                           g.representation, nullptr);
+     },
+     true},
 };
 
 template <class F>
@@ -123,6 +143,14 @@ void check_source(const Source& s) {
   if (s.rectify) {
     refused(with([](Args& g) { g.map_of = nullptr; }), "null map_of", "a null map_of");
     refused(with([](Args& g) { g.maps = (const float*)block; }), "maps must be null", "maps with n_maps 0");
+  }
+  if (s.rep) {
+    for (int32_t r : {-1, 3, 1 << 20}) refused(with([&](Args& g) { g.representation = r; }), "representation=", "an unknown representation");
+    refused(with([](Args& g) { g.representation = 1; }), "channels=5 must be even", "separate polarity with an odd channels");
+    for (int32_t c : {1, 4}) refused(with([&](Args& g) { g.representation = 2; g.channels = c; }), "must be 2", "a histogram of other than 2 planes");
+    refused(with([](Args& g) { g.channels = 0; }), "channels=0 must be positive", "channels 0");
+    // the workspace follows from channels: acc sized for 5 planes does not hold 6
+    refused(with([](Args& g) { g.representation = 1; g.channels = 6; }), "acc has", "acc sized for fewer planes");
   }
 }
 
