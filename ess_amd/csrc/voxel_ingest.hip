@@ -6,7 +6,9 @@
 // and the ring source, which share ONE loader, event_scatter_columns_kernel<Flavour, RING>: a template on the flavour and on whether
 // a window lies at the head of its row or anywhere inside a ring.  Two more flavours of that loader fill the reference loaders' other
 // event representations (ess_event_*_rep): SeparateFlavour (2 * bins planes, the polarities kept apart) and HistogramFlavour (two
-// planes of per-pixel counts, the time column not read); the finish kernels take a plane count, not a meaning.
+// planes of per-pixel counts, the time column not read); the finish kernels take a plane count, not a meaning.  Masked<Flavour>
+// puts a per-sensor hot-pixel bit mask in front of any of the four (ess_event_ingest_masked: an event on a masked raw pixel never
+// reaches the flavour); hot_pixel_mask_kernel turns the histogram's counts into such masks (ess_event_hot_pixel_mask).
 //
 // Behind the scatter, one kernel per job: event_finish_kernel<VEC, TAP> turns sums into a grid and zeroes them where each sum has
 // one reader -- the plain ingest (TAP false) and the loader finish at the identity geometry (TAP true); grid_map_kernel<VEC,
@@ -269,6 +271,80 @@ struct TrilinearFlavour {
     scatter_event_trilinear(xe, ye, tn, p, nb, H, W, plane, g);
   }
 };
+
+// ---- hot-pixel masks: one more per-slot table, in FRONT of the flavour.  masks [n_masks][mask_h][mask_words] 32-bit words,
+// mask_words = ceil(mask_w / 32), pixel (x, y) = bit x & 31 of word x >> 5 of row y, set: hot;  mask_of[slot] = the slot's mask,
+// MASK_NONE or anything else (the slot counts as empty, as for an unknown map word).  mask_h x mask_w is the SENSOR's size.
+struct Masks {
+  const uint32_t* masks;
+  const int32_t* mask_of;
+  int n_masks, mask_h, mask_w;
+};
+constexpr int MASK_NONE = -1;  // (ESS_MASK_NONE of include/ess_hip.h)
+
+// Any flavour behind a mask: an event whose RAW pixel lies inside the mask's rectangle with its bit set never reaches the flavour's
+// add(); every other event reaches it with its words unchanged (one outside the rectangle is the flavour's to judge).  window() is
+// the flavour's own: the time base comes from the window's first and last event whether they are hot or not -- the reference
+// voxelises first and zeroes the pixel afterwards, so its time base counts hot events too.  A type of its own: the four flavours
+// and their instantiations stay what they are.
+template <class Flavour>
+struct Masked {
+  static constexpr bool READS_TIME = Flavour::READS_TIME;
+  Flavour f;
+  const uint32_t* mask;  // the slot's mask, nullptr: MASK_NONE
+  int mask_h, mask_w, mask_words;
+  template <class... Extra>
+  __device__ __forceinline__ bool open(int s, const Masks m, const Extra... extra) {
+    const int k = m.mask_of[s];
+    mask_h = m.mask_h;
+    mask_w = m.mask_w;
+    mask_words = (m.mask_w + 31) >> 5;
+    mask = k >= 0 && k < m.n_masks ? m.masks + (size_t)k * m.mask_h * mask_words : nullptr;
+    if (!(k == MASK_NONE || mask != nullptr)) return false;
+    return f.open(s, extra...);
+  }
+  __device__ __forceinline__ void window(long long w_first, long long w_last, bool t_i64, int nb) { f.window(w_first, w_last, t_i64, nb); }
+  __device__ __forceinline__ void add(long long tw, unsigned xh, unsigned yh, int p, bool t_i64, bool xy_u16, int nb, int H, int W,
+                                      size_t plane, long long* __restrict__ g) const {
+    if (mask != nullptr) {
+      const int x = column_coordinate(xh, xy_u16), y = column_coordinate(yh, xy_u16);
+      if (x >= 0 && x < mask_w && y >= 0 && y < mask_h && ((mask[(size_t)y * mask_words + (x >> 5)] >> (x & 31)) & 1u) != 0) return;
+    }
+    f.add(tw, xh, yh, p, t_i64, xy_u16, nb, H, W, plane, g);
+  }
+};
+
+// ---- counts -> mask (ess_event_hot_pixel_mask): a wave takes 64 consecutive x of one row of one sensor, every lane compares its
+// pixel's count with the sensor's threshold, one wave-wide ballot packs the 64 answers into the row's two words, lanes 0 and 1
+// store them with plain stores (the second only where the row has that word).  A lane at x >= W votes 0: REPLACE writes the tail
+// bits as 0, OR leaves them.  No atomics, no memset; the launch follows from the sizes alone.
+constexpr int MASK_REPLACE = 0, MASK_OR = 1;  // (ESS_MASK_REPLACE, ESS_MASK_OR of include/ess_hip.h)
+constexpr int MASK_WAVES = INGEST_THREADS / 64;
+
+template <bool OR>
+__global__ __launch_bounds__(INGEST_THREADS) void hot_pixel_mask_kernel(const long long* __restrict__ sums, const long long* __restrict__ thresholds,
+                                                                        int H, int W, uint32_t* __restrict__ masks) {
+  const int i = blockIdx.y;
+  const long long thr = thresholds[i];
+  if (thr < 0) return;  // this sensor's mask is neither read nor written
+  const int chunks = (W + 63) >> 6, mask_words = (W + 31) >> 5;
+  const int64_t c = (int64_t)blockIdx.x * MASK_WAVES + (threadIdx.x >> 6);  // (the same for a whole wave)
+  if (c >= (int64_t)H * chunks) return;
+  const int y = (int)(c / chunks), lane = threadIdx.x & 63;
+  const int x0 = (int)(c % chunks) << 6, x = x0 + lane;
+  const size_t plane = (size_t)H * W;
+  const long long* __restrict__ s = sums + (size_t)i * 2 * plane + (size_t)y * W;
+  bool hot = false;
+  if (x < W) hot = ((s[x] + s[plane + x]) >> 40) > thr;
+  const unsigned long long votes = __ballot(hot);
+  const int word = (x0 >> 5) + lane;
+  if (lane < 2 && word < mask_words) {
+    uint32_t* __restrict__ m = masks + ((size_t)i * H + y) * mask_words + word;
+    const uint32_t bits = (uint32_t)(votes >> (32 * lane));
+    if constexpr (OR) *m |= bits;
+    else *m = bits;
+  }
+}
 
 // ---- the ring source (RING): the same four columns, [n_rows][ring], as per-stream RINGS that packets are appended to as they
 // arrive.  A slot's window is counts[i] events of row rows[i] from position starts[i] on, modulo ring; all four words are device
@@ -1058,6 +1134,108 @@ extern "C" int ess_event_ingest_columns_rep(const void* t, const void* x, const 
   if (rc) return rc;
   launch_finish<false>(counts, n_streams, (int64_t)channels * height * width, acc, nullptr, out, st);
   return ess_launch_status("event_ingest_columns_rep(finish)");
+}
+
+// ---- hot-pixel masks: ONE entry point for both sources, all four flavours and both halves (ess_event_ingest_masked), every one a
+// Masked<Flavour> instantiation of the loader; and the kernel that turns the histogram flavour's counts into masks.
+namespace {
+
+constexpr int MASK_MAX_SIDE = 32768;
+
+// the mask arguments -> the kernels' Masks
+int check_masks(const char* what, const uint32_t* masks, const int32_t* mask_of, int32_t n_masks, int32_t mask_height, int32_t mask_width,
+                Masks& m) {
+  ESS_CHECK_ARG(mask_of, "%s: null mask_of", what);
+  ESS_CHECK_ARG(n_masks >= 0, "%s: n_masks=%d must not be negative", what, (int)n_masks);
+  ESS_CHECK_ARG((masks != nullptr) == (n_masks > 0), "%s: masks must be null with n_masks=0 and only then (n_masks=%d, masks %s)", what,
+                (int)n_masks, masks ? "given" : "null");
+  ESS_CHECK_ARG(mask_height >= 1 && mask_height <= MASK_MAX_SIDE && mask_width >= 1 && mask_width <= MASK_MAX_SIDE,
+                "%s: mask_height=%d mask_width=%d (1..32768 each: the sensor's size, whatever the grid's)", what, (int)mask_height,
+                (int)mask_width);
+  ESS_CHECK_ARG((((uintptr_t)masks) & 15) == 0, "%s: masks must be 16-byte aligned", what);
+  m = Masks{masks, mask_of, n_masks, mask_height, mask_width};
+  return ESS_OK;
+}
+
+template <bool RING>
+int launch_scatter_masked(const char* status, int32_t representation, bool trilinear, const void* t, const void* x, const void* y,
+                          const void* p, const int32_t* rows, const int32_t* starts, const int32_t* counts, const int32_t* formats,
+                          int64_t ring, int32_t n_rows, int32_t n_slots, int32_t channels, int32_t height, int32_t width, void* acc,
+                          hipStream_t st, const Masks m, const Rectify r) {
+  if (trilinear)
+    return launch_scatter<Masked<TrilinearFlavour>, RING>(status, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels,
+                                                          height, width, acc, st, m, r);
+  if (representation == EVENT_REP_SEPARATE)
+    return launch_scatter<Masked<SeparateFlavour>, RING>(status, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels,
+                                                         height, width, acc, st, m);
+  if (representation == EVENT_REP_HISTOGRAM)
+    return launch_scatter<Masked<HistogramFlavour>, RING>(status, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels,
+                                                          height, width, acc, st, m);
+  return launch_scatter<Masked<TemporalFlavour>, RING>(status, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels,
+                                                       height, width, acc, st, m);
+}
+
+}  // namespace
+
+extern "C" int ess_event_ingest_masked(const void* t, const void* x, const void* y, const void* p, const int32_t* rows,
+                                       const int32_t* starts, const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows,
+                                       int32_t n_slots, int32_t channels, int32_t height, int32_t width, void* acc, size_t acc_bytes,
+                                       float* out, int32_t representation, int32_t trilinear, const float* maps, const int32_t* map_of,
+                                       int32_t n_maps, int32_t map_height, int32_t map_width, const uint32_t* masks,
+                                       const int32_t* mask_of, int32_t n_masks, int32_t mask_height, int32_t mask_width,
+                                       ess_stream_t stream) {
+  const char* what = "event_ingest_masked";
+  int rc = check_representation(what, representation, channels);
+  if (rc) return rc;
+  ESS_CHECK_ARG(trilinear == 0 || trilinear == 1, "%s: trilinear=%d (0 integer pixels, 1 the trilinear flavour)", what, (int)trilinear);
+  ESS_CHECK_ARG(!trilinear || representation == EVENT_REP_SIGNED,
+                "%s: trilinear=1 builds the signed grid alone: representation=%d must be 0", what, (int)representation);
+  ESS_CHECK_ARG((rows == nullptr) == (starts == nullptr),
+                "%s: rows and starts are both given (the ring source) or both null (the column source): rows %s, starts %s", what,
+                rows ? "given" : "null", starts ? "given" : "null");
+  const bool is_ring = rows != nullptr;
+  const uintptr_t addresses = (uintptr_t)t | (uintptr_t)x | (uintptr_t)y | (uintptr_t)p;
+  rc = check_source(what, is_ring ? SOURCE_RING : SOURCE_COLUMNS, t && x && y && p && counts && formats, addresses, ring,
+                    is_ring ? n_rows : 1, n_slots, channels, height, width, acc, acc_bytes, out, out != nullptr);
+  if (rc) return rc;
+  Rectify rect = {nullptr, nullptr, 0, 1, 1};
+  if (trilinear) {
+    rc = check_rectify(what, maps, map_of, n_maps, map_height, map_width, rect);
+    if (rc) return rc;
+  }
+  Masks m;
+  rc = check_masks(what, masks, mask_of, n_masks, mask_height, mask_width, m);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const char* status = out ? "event_ingest_masked(scatter)" : what;
+  rc = is_ring ? launch_scatter_masked<true>(status, representation, trilinear != 0, t, x, y, p, rows, starts, counts, formats, ring, n_rows,
+                                             n_slots, channels, height, width, acc, st, m, rect)
+               : launch_scatter_masked<false>(status, representation, trilinear != 0, t, x, y, p, nullptr, nullptr, counts, formats, ring, 1,
+                                              n_slots, channels, height, width, acc, st, m, rect);
+  if (rc || !out) return rc;
+  launch_finish<false>(counts, n_slots, (int64_t)channels * height * width, acc, nullptr, out, st);
+  return ess_launch_status("event_ingest_masked(finish)");
+}
+
+extern "C" int ess_event_hot_pixel_mask(const int64_t* sums, int32_t n, int32_t height, int32_t width, const int64_t* thresholds,
+                                        uint32_t* masks, int32_t mode, ess_stream_t stream) {
+  ESS_CHECK_ARG(sums && thresholds && masks, "event_hot_pixel_mask: null sums, thresholds or masks");
+  ESS_CHECK_ARG(n >= 1 && n <= 65535, "event_hot_pixel_mask: n=%d (1..65535)", (int)n);
+  ESS_CHECK_ARG(height >= 1 && height <= MASK_MAX_SIDE && width >= 1 && width <= MASK_MAX_SIDE,
+                "event_hot_pixel_mask: height=%d width=%d (1..32768 each: the sensor's size)", (int)height, (int)width);
+  ESS_CHECK_ARG(mode == MASK_REPLACE || mode == MASK_OR, "event_hot_pixel_mask: mode=%d (0 replace, 1 or)", (int)mode);
+  ESS_CHECK_ARG(((((uintptr_t)sums) | ((uintptr_t)masks)) & 15) == 0 && (((uintptr_t)thresholds) & 7) == 0,
+                "event_hot_pixel_mask: sums and masks must be 16-byte, thresholds 8-byte aligned");
+  const int64_t chunks = (int64_t)height * ((width + 63) >> 6);  // (<= 2^24)
+  const dim3 grid((unsigned)ceil_div64(chunks, (int64_t)MASK_WAVES), (unsigned)n);
+  hipStream_t st = (hipStream_t)stream;
+  if (mode == MASK_OR)
+    hipLaunchKernelGGL(hot_pixel_mask_kernel<true>, grid, dim3(INGEST_THREADS), 0, st, (const long long*)sums, (const long long*)thresholds,
+                       (int)height, (int)width, masks);
+  else
+    hipLaunchKernelGGL(hot_pixel_mask_kernel<false>, grid, dim3(INGEST_THREADS), 0, st, (const long long*)sums, (const long long*)thresholds,
+                       (int)height, (int)width, masks);
+  return ess_launch_status("event_hot_pixel_mask");
 }
 
 // workspace: [n_slots] GridStat, then [n_slots][grid_stats_blocks][3] 8-byte partials

@@ -82,6 +82,7 @@ EXPORTS = [
     'ess_event_scatter_ring', 'ess_event_scatter_ring_trilinear', 'ess_event_grid_finish_workspace', 'ess_event_grid_finish',
     'ess_event_grid_finish_window', 'ess_label_window',
     'ess_event_scatter_ring_rep', 'ess_event_ingest_ring_rep', 'ess_event_ingest_columns_rep',
+    'ess_event_ingest_masked', 'ess_event_hot_pixel_mask',
 ]
 
 
@@ -192,6 +193,8 @@ def lib():
             'ess_event_scatter_ring_rep': [P, P, P, P, P, P, P, P, I64, I, I, I, I, I, P, c_size_t, I, P],
             'ess_event_ingest_ring_rep': [P, P, P, P, P, P, P, P, I64, I, I, I, I, I, P, c_size_t, P, I, P],
             'ess_event_ingest_columns_rep': [P, P, P, P, P, P, I64, I, I, I, I, P, c_size_t, P, I, P],
+            'ess_event_ingest_masked': [P, P, P, P, P, P, P, P, I64, I, I, I, I, I, P, c_size_t, P, I, I, P, P, I, I, I, P, P, I, I, I, P],
+            'ess_event_hot_pixel_mask': [P, I, I, I, P, P, I, P],
         }
         for name, argtypes in sig.items():
             fn = getattr(L, name)
@@ -1209,6 +1212,143 @@ def event_ingest_columns_rep(t, x, y, p, counts, formats, out, representation, a
     _check(lib().ess_event_ingest_columns_rep(*_column_pointers(words), t.shape[1], S, C, H, W, c_void_p(acc.data_ptr()),
                                               acc.numel() * 8, c_void_p(out.data_ptr()), rep, stream()), 'ess_' + fn)
     return out
+
+
+# Hot-pixel masks (ess_event_ingest_masked / ess_event_hot_pixel_mask): per-sensor bit masks applied to the RAW events
+MASK_NONE = -1     # ESS_MASK_NONE: a mask word for a slot without a mask
+MASK_REPLACE = 0   # ESS_MASK_REPLACE: event_hot_pixel_mask writes whole words, the tail bits of a row as 0
+MASK_OR = 1        # ESS_MASK_OR: ... or-s the new bits onto the words that are there
+MASK_MAX_SIDE = 32768
+_MASK_DTYPES = (torch.int32,) + ((torch.uint32,) if hasattr(torch, 'uint32') else ())
+
+
+def mask_words(width):
+    """32-bit words in one row of a hot-pixel mask of `width` pixels"""
+    return (int(width) + 31) // 32
+
+
+def _mask_tensor(fn, masks, size, lead):
+    """masks: device int32 / uint32 [n, h, ceil(w / 32)] with size = (h, w) -> (n, h, w); what is wrong with its form is said here"""
+    if not isinstance(size, (tuple, list)) or len(size) != 2 or \
+            any(isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= MASK_MAX_SIDE for v in size):
+        raise EssHipError(f'{fn}: mask_size={size!r} must be (mask_h, mask_w), the sensor\'s size, 1..{MASK_MAX_SIDE} each')
+    h, w = size
+    if not torch.is_tensor(masks) or masks.dtype not in _MASK_DTYPES or masks.dim() != 3 or masks.numel() == 0 \
+            or tuple(masks.shape[1:]) != (h, mask_words(w)):
+        got = f'{masks.dtype}{tuple(masks.shape)}' if torch.is_tensor(masks) else type(masks).__name__
+        raise EssHipError(f'{fn}: masks must be a non-empty int32 / uint32 [{lead}, {h}, {mask_words(w)}] tensor '
+                          f'(bit x & 31 of word x >> 5 of row y: pixel (x, y) of a {h} x {w} sensor), got {got}')
+    return masks.shape[0], h, w
+
+
+def _mask_form(fn, masks, mask_of, mask_size, n):
+    """the form of masks (None or int32 / uint32 [n_masks, mask_h, ceil(mask_w / 32)] with mask_size = (mask_h, mask_w)) and of mask_of
+    (None or int32 [n]), whatever memory they lie in -> (n_masks, mask_h, mask_w)"""
+    if masks is None:
+        if mask_size is not None:
+            raise EssHipError(f'{fn}: mask_size={mask_size!r} without masks')
+        n_masks, mh, mw = 0, 1, 1
+    else:
+        n_masks, mh, mw = _mask_tensor(fn, masks, mask_size, 'n_masks')
+    if mask_of is not None and (not torch.is_tensor(mask_of) or mask_of.dtype != torch.int32 or tuple(mask_of.shape) != (n,)):
+        got = f'{mask_of.dtype}{tuple(mask_of.shape)}' if torch.is_tensor(mask_of) else type(mask_of).__name__
+        raise EssHipError(f'{fn}: mask_of must be int32 [{n}] or None, got {got}')
+    return n_masks, mh, mw
+
+
+def _mask_args(fn, masks, mask_of, form, n, device):
+    """the checked masks / mask_of (None: MASK_NONE for every slot) and _mask_form's answer -> the five mask arguments of
+    event_ingest_masked"""
+    n_masks, mh, mw = form
+    if mask_of is None:
+        mask_of = torch.full((n,), MASK_NONE, dtype=torch.int32, device=device)
+    for name, v in (('masks', masks), ('mask_of', mask_of)):
+        if v is not None and not v.is_cuda:
+            raise EssHipError(f'{fn}: {name} must be a CUDA(HIP) tensor; there is no CPU path')
+        if v is not None and not v.is_contiguous():
+            raise EssHipError(f'{fn}: {name} must be contiguous')
+    return (c_void_p(0 if masks is None else masks.data_ptr()), ptr(mask_of, torch.int32), n_masks, mh, mw)
+
+
+def event_ingest_masked(t, x, y, p, rows, starts, counts, formats, out, masks=None, mask_of=None, mask_size=None,
+                        representation=EVENT_REP_SIGNED, trilinear=False, maps=None, map_of=None, acc=None):
+    """The column / ring ingest behind per-sensor HOT-PIXEL MASKS, applied to the raw events: one call for both sources, every
+    flavour and both halves.  rows, starts: device int32 [n_slots] (the ring source, t .. p [n_rows, ring]) or both None (the column
+    source, t .. p [n_slots, stride], slot s's window at the head of row s).  out: fp32 [n_slots, C, H, W], returned -- or None:
+    scatter only, acc (then required: int64 [n_slots, C, H, W], all zero before) keeps the sums for event_grid_finish*, and is
+    returned.  representation: EVENT_REP_*; trilinear=True: the trilinear flavour with maps / map_of as
+    event_ingest_ring_trilinear takes them (representation must be EVENT_REP_SIGNED).
+    masks: device int32 / uint32 [n_masks, mask_h, ceil(mask_w / 32)], pixel (x, y) = bit x & 31 of word x >> 5 of row y, set: hot
+    (datasets.hot_pixels.HotPixelMask.words), with mask_size=(mask_h, mask_w) the SENSOR's size whatever the grid's -- or None;
+    mask_of: device int32 [n_slots], read on the device -- MASK_NONE: no mask, 0 .. n_masks - 1: that mask, anything else: the slot
+    counts as empty -- or None: MASK_NONE throughout.  An event whose raw (x, y) lies inside the mask with its bit set is dropped
+    BEFORE the flavour sees it (before a rectify map moves it); every other event is handled as the unmasked entry points handle
+    it.  The window's time base comes from its first and last event whether they are masked or not (the reference voxelises
+    first and zeroes afterwards).  Everything else: as event_ingest_ring_rep / event_ingest_columns_rep."""
+    fn = 'event_ingest_masked'
+    if (rows is None) != (starts is None):
+        raise EssHipError(f'{fn}: rows and starts are both given (the ring source) or both None (the column source)')
+    ring = rows is not None
+    words = (('t', t), ('x', x), ('y', y), ('p', p)) + ((('rows', rows), ('starts', starts)) if ring else ()) + \
+        (('counts', counts), ('formats', formats))
+    if out is None and acc is None:
+        raise EssHipError(f'{fn}: out=None (scatter only) needs acc, the int64 [n_slots, C, H, W] sums it leaves')
+    named = words + ((('out', out),) if out is not None else ()) + ((('acc', acc),) if acc is not None else ())
+    _are_tensors(fn, named)
+    n_slots, C, H, W = _ingest_out(fn, out, 'n_slots') if out is not None else _finish_acc(fn, acc, 'H, W')
+    rep = _event_rep_of(fn, representation, C, 'out' if out is not None else 'acc')
+    if not isinstance(trilinear, (bool, int)) or trilinear not in (0, 1):
+        raise EssHipError(f'{fn}: trilinear={trilinear!r} must be False or True')
+    if trilinear and rep != EVENT_REP_SIGNED:
+        raise EssHipError(f'{fn}: trilinear=True builds the signed grid alone, representation={representation!r} must be EVENT_REP_SIGNED')
+    if not trilinear and (maps is not None or map_of is not None):
+        raise EssHipError(f'{fn}: maps / map_of are read by the trilinear flavour alone (trilinear=False)')
+    _event_columns(fn, words, n_slots, ring=ring)
+    form = _mask_form(fn, masks, mask_of, mask_size, n_slots)
+    if out is not None:
+        acc = _ingest_acc(fn, named, acc, out)
+    else:
+        _on_device(fn, named)
+    dev = acc.device
+    rect = _rectify_args(fn, maps, map_of, n_slots, dev) if trilinear else (c_void_p(0), c_void_p(0), 0, 1, 1)
+    mask = _mask_args(fn, masks, mask_of, form, n_slots, dev)
+    cols = _column_pointers(words)
+    if not ring:
+        cols = cols[:4] + [c_void_p(0), c_void_p(0)] + cols[4:]
+    n_rows, span = t.shape
+    _check(lib().ess_event_ingest_masked(*cols, span, n_rows, n_slots, C, H, W, c_void_p(acc.data_ptr()), acc.numel() * 8,
+                                         c_void_p(0 if out is None else out.data_ptr()), rep, int(trilinear), *rect, *mask, stream()),
+           'ess_' + fn)
+    return out if out is not None else acc
+
+
+def event_hot_pixel_mask(sums, thresholds, masks, mode=MASK_REPLACE):
+    """Per-pixel event counts -> hot-pixel masks.  sums: device int64 [n, 2, H, W], what event_scatter_ring_rep(EVENT_REP_HISTOGRAM)
+    leaves (2^40 per event; read only -- the sums of several scatters onto one acc may be thresholded, as long as no pixel
+    collects more than 2^22 events).  thresholds: device int64 [n], in EVENTS, read on the device: >= 0 -- bit (y, x) of masks[i] is
+    set iff the pixel's events of both polarities together number MORE than thresholds[i]; < 0 -- masks[i] is neither read nor
+    written.  masks: device int32 / uint32 [n, H, ceil(W / 32)] (the layout event_ingest_masked reads), returned.  mode:
+    MASK_REPLACE -- whole words are written, the bits at x >= W of a row's last word as 0; MASK_OR -- the new bits are or-ed onto what
+    is there, the tail bits stay.  One launch shaped by the sizes alone, no atomics, no memset: capturable."""
+    fn = 'event_hot_pixel_mask'
+    named = (('sums', sums), ('thresholds', thresholds), ('masks', masks))
+    _are_tensors(fn, named)
+    if sums.dim() != 4 or sums.dtype != torch.int64 or sums.numel() == 0 or sums.shape[1] != 2:
+        raise EssHipError(f'{fn}: sums must be a non-empty int64 [n, 2, H, W] tensor (the histogram flavour\'s sums), '
+                          f'got {sums.dtype}{tuple(sums.shape)}')
+    n, _, H, W = sums.shape
+    if H > MASK_MAX_SIDE or W > MASK_MAX_SIDE:
+        raise EssHipError(f'{fn}: sums of {H} x {W} pixels: a side is 1..{MASK_MAX_SIDE}')
+    if thresholds.dtype != torch.int64 or tuple(thresholds.shape) != (n,):
+        raise EssHipError(f'{fn}: thresholds must be int64 [{n}], got {thresholds.dtype}{tuple(thresholds.shape)}')
+    if _mask_tensor(fn, masks, (H, W), n)[0] != n:
+        raise EssHipError(f'{fn}: masks must hold {n} masks, one per sensor of sums, got {tuple(masks.shape)}')
+    if isinstance(mode, bool) or mode not in (MASK_REPLACE, MASK_OR):
+        raise EssHipError(f'{fn}: mode={mode!r} must be MASK_REPLACE or MASK_OR')
+    _on_device(fn, named)
+    _check(lib().ess_event_hot_pixel_mask(c_void_p(sums.data_ptr()), n, H, W, c_void_p(thresholds.data_ptr()), c_void_p(masks.data_ptr()),
+                                          int(mode), stream()), 'ess_' + fn)
+    return masks
 
 
 def _finish_acc(fn, acc, dims):

@@ -358,6 +358,79 @@ def _rectify_maps(rectify_maps, voxel, n_streams):
     return (torch.stack(maps).contiguous() if maps else None), map_of
 
 
+def _check_hot_pixel_masks(masks, n_streams, size):
+    """The segmenters' hot_pixel_masks argument: n_streams entries, each None or a datasets.hot_pixels.HotPixelMask, all of one sensor
+    size (size: (h, w) they must have, or None) -> that size, None where every entry is None"""
+    from .datasets.hot_pixels import HotPixelMask
+    if not isinstance(masks, (list, tuple)) or len(masks) != n_streams:
+        n = len(masks) if isinstance(masks, (list, tuple)) else type(masks).__name__
+        raise hip.EssHipError(f'hot_pixel_masks must be a list with one entry per stream (a HotPixelMask or None): got {n}, the segmenter '
+                              f'serves n_streams={n_streams}')
+    for s, m in enumerate(masks):
+        if m is None:
+            continue
+        if not isinstance(m, HotPixelMask):
+            raise hip.EssHipError(f'hot_pixel_masks[{s}] must be a datasets.hot_pixels.HotPixelMask or None, got {type(m).__name__}')
+        if size is not None and (m.height, m.width) != tuple(size):
+            raise hip.EssHipError(f'hot_pixel_masks[{s}] is {m.height} x {m.width}, the masks of this segmenter {size[0]} x {size[1]}: one '
+                                  'call reads masks of one sensor size')
+        size = (m.height, m.width)
+    return size
+
+
+class _HotPixelSlots:
+    """The hot-pixel masks of a segmenter: ONE static device buffer words int32 [S, mask_h, ceil(mask_w / 32)] -- a slot per stream,
+    so that set_hot_pixels and calibrate_hot_pixels never run out of room under a capture that has the buffer's address and size --
+    and the host's books: which HotPixelMask each slot holds (entries that are the same object share a slot) and mask_of, per STREAM
+    its slot or hip.MASK_NONE, which the staging writes into the round's words."""
+
+    def __init__(self, masks, n_streams, default_size, device):
+        self.size = _check_hot_pixel_masks(masks, n_streams, None) or (int(default_size[0]), int(default_size[1]))
+        mh, mw = self.size
+        self.n_streams, self.device = n_streams, device
+        self.words = torch.zeros(n_streams, mh, hip.mask_words(mw), dtype=torch.int32, device=device)
+        self.held = [None] * n_streams
+        self.mask_of = [hip.MASK_NONE] * n_streams
+        self.scratch = None  # (calibration: the histogram sums, made when first needed)
+        for s, m in enumerate(masks):
+            self.assign(s, m)
+
+    def free_slot(self):
+        """a slot no stream names (there is always one for a stream that has just let go of its own)"""
+        return next(k for k in range(self.n_streams) if k not in self.mask_of)
+
+    def assign(self, s, m):
+        """stream s reads mask m (None: none) from its next round on; a mask no slot holds is uploaded, outside any capture"""
+        self.mask_of[s] = hip.MASK_NONE
+        if m is None:
+            return
+        _check_hot_pixel_masks([m], 1, self.size)
+        for k, o in enumerate(self.held):
+            if o is m:
+                self.mask_of[s] = k
+                return
+        k = self.free_slot()
+        self.words[k].copy_(torch.from_numpy(m.words.view(np.int32).copy()))
+        self.held[k] = m
+        self.mask_of[s] = k
+
+    def own_slot(self, s, keep):
+        """a slot that stream s alone names, for a calibration to write; keep: with the bits of the stream's mask so far"""
+        k = self.mask_of[s]
+        if k != hip.MASK_NONE and self.mask_of.count(k) == 1:
+            self.held[k] = None
+            return k
+        self.mask_of[s] = hip.MASK_NONE
+        j = self.free_slot()
+        if keep and k != hip.MASK_NONE:
+            self.words[j].copy_(self.words[k])
+        elif keep:
+            self.words[j].zero_()
+        self.held[j] = None
+        self.mask_of[s] = j
+        return j
+
+
 def check_stream_columns(events, n_streams):
     """events: S entries, each a datasets.data_util.EventColumns or None / empty (idle) -> (list of EventColumns or None, active)"""
     from .datasets.data_util import EventColumns
@@ -377,25 +450,27 @@ class _ColumnStage:
     """one pinned staging set of the column ingest: the four columns [S, stride] and the words [2, S] (counts, formats; voxel=
     'trilinear': [3, S], the map words behind them) as torch (pinned) and as numpy views, the event recorded behind the set's last
     upload, and the (slot, events) pairs staged for the next"""
-    __slots__ = ('cols', 'words', 'cols_np', 'counts_np', 'formats_np', 'maps_np', 'done', 'used')
+    __slots__ = ('cols', 'words', 'cols_np', 'counts_np', 'formats_np', 'maps_np', 'masks_np', 'done', 'used')
 
     def __init__(self, cols, words, done):
         self.cols, self.words, self.done, self.used = cols, words, done, ()
         self.cols_np = tuple(c.numpy() for c in cols)
         self.counts_np, self.formats_np = words.numpy()[0], words.numpy()[1]
         self.maps_np = words.numpy()[2] if words.shape[0] > 2 else None
+        self.masks_np = words.numpy()[3] if words.shape[0] > 3 else None  # (hot_pixel_masks: [4, S], the map words always there)
 
 
 class _RingStage:
     """one pinned staging set of the ring ingest: the words [4, S] (rows, starts, counts, formats; voxel='trilinear': [5, S], the map
     words behind them) as torch (pinned) and as numpy views, and the event recorded behind the set's last upload.  No event is
     staged: they went to the device ring when they arrived"""
-    __slots__ = ('words', 'rows_np', 'starts_np', 'counts_np', 'formats_np', 'maps_np', 'done', 'used')
+    __slots__ = ('words', 'rows_np', 'starts_np', 'counts_np', 'formats_np', 'maps_np', 'masks_np', 'done', 'used')
 
     def __init__(self, words, done):
         self.words, self.done, self.used = words, done, ()
         self.rows_np, self.starts_np, self.counts_np, self.formats_np = words.numpy()[:4]
         self.maps_np = words.numpy()[4] if words.shape[0] > 4 else None
+        self.masks_np = words.numpy()[5] if words.shape[0] > 5 else None  # (hot_pixel_masks: [6, S], the map words always there)
 
 
 class _Feed:
@@ -486,14 +561,31 @@ class MultiStreamSegmenter(GraphedWindowState):
     hip.event_ingest_ring_rep and fills the C = encoder.num_bins planes the network reads with the reference loaders' other two
     event representations -- 'separate_pol': C even, [C / 2 positive bins; C / 2 negative bins], both non-negative; 'histogram':
     C == 2, [negative counts, positive counts], the time column not read -- summed in 64-bit fixed point like the signed grid.  The
-    static grids and int64 sums are sized by C as before: 5 bins kept apart are C = 10, twice the signed grid's memory."""
+    static grids and int64 sums are sized by C as before: 5 bins kept apart are C = 10, twice the signed grid's memory.
+
+    hot_pixel_masks=[...] (with event_layout='columns' or 'ring', any voxel / representation; None, the default, is everything
+    above, unchanged): n_streams entries, None or a datasets.hot_pixels.HotPixelMask of the SENSOR's size (all of one size; with
+    every entry None: the rectify maps' size, else height x width), and the round starts with hip.event_ingest_masked: a hot
+    pixel's events are dropped as RAW events, before a rectify map moves them, where the event preprocessor's hot_pixels_file loop
+    (kept as it is) zeroes grid pixels afterwards.  Hot pixels belong to a sensor: each stream has its own mask; entries that are
+    the same object share one device copy.  The masks live in one static buffer of n_streams slots; a stream's mask word travels
+    with its count and format (the words grow to [4, S] / [6, S], the map words always among them), and a compacted round writes
+    it per slot.  set_hot_pixels(stream, mask | None) and calibrate_hot_pixels(...) change masks between rounds without a
+    re-capture.  The window's time base still counts the hot events, as the reference's does."""
 
     def __init__(self, encoder, decoder, height, width, options, n_streams, device=None, graph=False, copy=True, palette=None,
                  want_confidence=False, out_hw=None, compact=False, compact_buckets=None, event_capacity=None, event_layout='records',
                  ring_capacity=None, window_events=None, window_duration=None, window_stride=None, voxel='temporal', rectify_maps=None,
-                 representation=None):
+                 representation=None, hot_pixel_masks=None):
         if not isinstance(n_streams, int) or isinstance(n_streams, bool) or n_streams < 1:
             raise hip.EssHipError(f'n_streams={n_streams!r}: a positive number of streams is needed')
+        if hot_pixel_masks is not None:  # (refused before the models reach the device)
+            if event_capacity is None or event_layout not in ('columns', 'ring'):
+                raise hip.EssHipError(f"hot_pixel_masks are applied to raw events, where (x, y) is still the sensor's pixel: that needs the "
+                                      f"raw event columns inside the round, event_capacity=N and event_layout='columns' or 'ring' (got "
+                                      f'event_layout={event_layout!r}, event_capacity={event_capacity!r}; the record layout and grids handed '
+                                      'to update() keep the hot_pixels_file loop of the event preprocessor)')
+            _check_hot_pixel_masks(hot_pixel_masks, n_streams, None)
         self.representation = representation
         if representation is not None:  # (refused before the models reach the device)
             self._rep = _event_representation(representation, voxel, rectify_maps, encoder.num_bins)
@@ -533,6 +625,9 @@ class MultiStreamSegmenter(GraphedWindowState):
         self.voxel = _voxel_flavour(voxel, self.event_layout, event_capacity)
         maps, self._map_of = _rectify_maps(rectify_maps, self.voxel, n_streams)
         self._maps = None if maps is None else maps.to(self.device)  # (uploaded once, here)
+        if hot_pixel_masks is not None:
+            default = tuple(maps.shape[1:3]) if maps is not None else (height, width)
+            self._hot = _HotPixelSlots(hot_pixel_masks, n_streams, default, self.device)
         if self.event_layout == 'ring':
             self._build_ingest_ring(ring_capacity, window_events, window_duration, window_stride)
         elif not (ring_capacity is None and window_events is None and window_duration is None and window_stride is None):
@@ -544,7 +639,7 @@ class MultiStreamSegmenter(GraphedWindowState):
             self._build_compact()
 
     # ---- event ingest (event_capacity=N): static record / count buffers the captured round reads, pinned staging in front of them
-    event_capacity = ring_capacity = _records = _columns = _counts = _formats = _acc = _ring = _maps = None
+    event_capacity = ring_capacity = _records = _columns = _counts = _formats = _acc = _ring = _maps = _hot = None
     voxel = 'temporal'
     representation, _rep = None, hip.EVENT_REP_SIGNED
 
@@ -572,6 +667,8 @@ class MultiStreamSegmenter(GraphedWindowState):
         dtypes = (torch.int64, torch.int16, torch.int16, torch.uint8)
         self._columns = tuple(torch.zeros(S, stride, dtype=d, device=self.device) for d in dtypes)
         n_words = 3 if self.voxel == 'trilinear' else 2  # (the map words ride behind the counts and formats: still one upload)
+        if self._hot is not None:
+            n_words = 4  # (... and the mask words behind the map words, which are then always there: -1 is NONE for both)
         self._words = torch.zeros(n_words, S, dtype=torch.int32, device=self.device)
         self._counts, self._formats = self._words[0], self._words[1]
         self._counts.fill_(hip.INGEST_KEEP)
@@ -605,6 +702,8 @@ class MultiStreamSegmenter(GraphedWindowState):
         self._ring_host = tuple(torch.zeros(S, R, dtype=d).pin_memory() for d in dtypes)
         self._ring_np = tuple(c.numpy() for c in self._ring_host)
         n_words = 5 if self.voxel == 'trilinear' else 4  # (the map words ride behind the four: still one upload)
+        if self._hot is not None:
+            n_words = 6  # (... and the mask words behind the map words, which are then always there: -1 is NONE for both)
         self._words = torch.zeros(n_words, S, dtype=torch.int32, device=self.device)
         self._counts, self._formats = self._words[2], self._words[3]
         self._counts.fill_(hip.INGEST_KEEP)
@@ -686,11 +785,15 @@ class MultiStreamSegmenter(GraphedWindowState):
         st.formats_np[:] = 0
         if st.maps_np is not None:
             st.maps_np[:] = hip.RECTIFY_NONE
+        if st.masks_np is not None:
+            st.masks_np[:] = hip.MASK_NONE
         for i, w in enumerate(slots):
             if w is not None:
                 st.rows_np[i], st.starts_np[i], st.counts_np[i], st.formats_np[i] = w
                 if st.maps_np is not None:
                     st.maps_np[i] = self._map_of[w[0]]
+                if st.masks_np is not None:  # (a compacted round's slot carries the mask of the stream it holds)
+                    st.masks_np[i] = self._hot.mask_of[w[0]]
         return st
 
     def update_from_feed(self, active=None):
@@ -718,7 +821,15 @@ class MultiStreamSegmenter(GraphedWindowState):
         """the round's first launches: the static event buffers (b: their first b slots) -> the grids ev, inside the capture"""
         cut = (lambda v: v) if b is None else (lambda v: v[:b])
         tri, rep = self.voxel == 'trilinear', self._rep
-        if self._ring is not None:  # (every row of the rings stays in reach: a slot names its row)
+        if self._hot is not None:  # (hot_pixel_masks: one entry point for both sources and every flavour)
+            w = [cut(v) for v in self._words]
+            if self._ring is not None:
+                cols, (rows, starts, counts, formats, map_of, mask_of) = self._ring, w
+            else:
+                cols, rows, starts, (counts, formats, map_of, mask_of) = tuple(cut(c) for c in self._columns), None, None, w
+            hip.event_ingest_masked(*cols, rows, starts, counts, formats, ev, self._hot.words, mask_of, self._hot.size, representation=rep,
+                                    trilinear=tri, maps=self._maps if tri else None, map_of=map_of if tri else None, acc=self._acc)
+        elif self._ring is not None:  # (every row of the rings stays in reach: a slot names its row)
             if tri:
                 hip.event_ingest_ring_trilinear(*self._ring, *(cut(w) for w in self._words[:4]), ev, self._maps, cut(self._words[4]), self._acc)
             elif rep != hip.EVENT_REP_SIGNED:
@@ -735,6 +846,88 @@ class MultiStreamSegmenter(GraphedWindowState):
                 hip.event_ingest_columns(*(cut(c) for c in self._columns), cut(self._counts), cut(self._formats), ev, self._acc)
         else:
             hip.event_ingest(cut(self._records), cut(self._counts), ev, self._acc)
+
+    # ---- hot-pixel masks (hot_pixel_masks=[...]): per-sensor bit masks the ingest applies to the raw events
+    def _hot_slots(self, what):
+        if self._hot is None:
+            raise hip.EssHipError(f'{what}: this segmenter was built without hot_pixel_masks, so no mask buffer exists under its captures: '
+                                  'pass hot_pixel_masks=[...] (a list of None will do)')
+        return self._hot
+
+    def set_hot_pixels(self, stream, mask):
+        """stream reads `mask` (a HotPixelMask of the segmenter's sensor size, or None: no mask) from its next round on.  The words
+        go into the static mask buffer here, outside any capture; the stream's mask word travels with its next round's words: no
+        re-capture, n_captures does not move."""
+        hot = self._hot_slots('set_hot_pixels')
+        if not isinstance(stream, (int, np.integer)) or isinstance(stream, bool) or not 0 <= stream < self.n_streams:
+            raise hip.EssHipError(f'set_hot_pixels: stream {stream!r} of n_streams={self.n_streams}')
+        hot.assign(int(stream), mask)
+
+    def hot_pixels(self, stream):
+        """the HotPixelMask the stream reads, or None"""
+        hot = self._hot_slots('hot_pixels')
+        k = hot.mask_of[int(stream)]
+        return None if k == hip.MASK_NONE else hot.held[k]
+
+    def calibrate_hot_pixels(self, streams=None, max_events_per_pixel=None, max_rate_hz=None, mode='replace'):
+        """event_layout='ring': per named stream (default: all) a mask from the events its ring holds NOW -> the list of their
+        HotPixelMask objects, in the order of `streams` (one download), which the streams read from their next round on.  A pixel
+        is hot when it fired MORE than the limit: max_events_per_pixel=k events, or max_rate_hz=r: floor(r * (t_last - t_first))
+        events, from the first and last time the ring holds, t taken in seconds -- exactly one of the two.  mode='replace': the
+        stream's mask becomes the calibrated one; 'or': its bits are added to the mask the stream has.  On the device: the UNMASKED
+        histogram scatter (hip.event_scatter_ring_rep) of the rings into scratch sums of the sensor's size, then
+        hip.event_hot_pixel_mask into the stream's slot of the static buffer, then the scratch is zeroed.  Outside the captured
+        round: recurrent state, pending windows and rings are not touched, nothing is captured again."""
+        from .datasets.hot_pixels import HotPixelMask
+        what = 'calibrate_hot_pixels'
+        if self._ring is None:
+            raise hip.EssHipError(f"{what} reads the streams' device rings: event_layout='ring' (this segmenter: {self.event_layout!r})")
+        hot = self._hot_slots(what)
+        if (max_events_per_pixel is None) == (max_rate_hz is None):
+            raise hip.EssHipError(f'{what}: give max_events_per_pixel=k or max_rate_hz=r, exactly one of the two')
+        limit = max_events_per_pixel if max_rate_hz is None else max_rate_hz
+        ok = isinstance(limit, (int, np.integer)) if max_rate_hz is None else isinstance(limit, (int, float, np.integer, np.floating))
+        if isinstance(limit, bool) or not ok or not 0 <= limit < float('inf'):
+            raise hip.EssHipError(f'{what}: the limit {limit!r} must be a non-negative ' + ('int' if max_rate_hz is None else 'number'))
+        if mode not in ('replace', 'or'):
+            raise hip.EssHipError(f"{what}: mode={mode!r}: 'replace' or 'or'")
+        streams = list(range(self.n_streams)) if streams is None else list(streams)
+        for s in streams:
+            self._feed_of(s, what)
+        if len(set(int(s) for s in streams)) != len(streams):
+            raise hip.EssHipError(f'{what}: streams={streams!r} names a stream twice')
+        S, R = self.n_streams, self.ring_capacity
+        mh, mw = hot.size
+        words = np.zeros((4, S), dtype=np.int32)
+        words[0] = np.arange(S)
+        thresholds = np.full(S, -1, dtype=np.int64)
+        slots = []
+        for s in (int(s) for s in streams):
+            f = self._feeds[s]
+            head = f.windows.head
+            n = min(head, R)
+            k = hot.own_slot(s, keep=mode == 'or')
+            slots.append(k)
+            words[:, k] = (s, (head - n) % R, n, f.format or 0)
+            if max_rate_hz is None:
+                thresholds[k] = int(limit)
+            else:
+                t = self._ring_np[0][s].view(f.dtypes[0]) if n else np.zeros(1)
+                span = float(t[(head - 1) % R]) - float(t[(head - n) % R]) if n else 0.0
+                thresholds[k] = int(np.floor(float(limit) * span))
+        if hot.scratch is None:
+            hot.scratch = torch.zeros(S, 2, mh, mw, dtype=torch.int64, device=self.device)
+        w = torch.from_numpy(words).to(self.device)
+        hip.event_scatter_ring_rep(*self._ring, w[0], w[1], w[2], w[3], hot.scratch, hip.EVENT_REP_HISTOGRAM)
+        hip.event_hot_pixel_mask(hot.scratch, torch.from_numpy(thresholds).to(self.device), hot.words,
+                                 hip.MASK_OR if mode == 'or' else hip.MASK_REPLACE)
+        hot.scratch.zero_()
+        host = hot.words.cpu().numpy().view(np.uint32)
+        out = []
+        for k in slots:
+            hot.held[k] = HotPixelMask.from_words(host[k], mh, mw)
+            out.append(hot.held[k])
+        return out
 
     def _next_stage(self):
         """the staging set of this round, free to be rewritten: its last upload has completed (in practice long ago -- a whole
@@ -786,6 +979,8 @@ class MultiStreamSegmenter(GraphedWindowState):
         st.formats_np[:] = 0
         if st.maps_np is not None:
             st.maps_np[:] = hip.RECTIFY_NONE
+        if st.masks_np is not None:
+            st.masks_np[:] = hip.MASK_NONE
         used = []
         for i, e in enumerate(slots):
             if e is not None:
@@ -793,6 +988,8 @@ class MultiStreamSegmenter(GraphedWindowState):
                 st.formats_np[i] = e.format
                 if st.maps_np is not None:
                     st.maps_np[i] = self._map_of[i if streams is None else streams[i]]
+                if st.masks_np is not None:
+                    st.masks_np[i] = self._hot.mask_of[i if streams is None else streams[i]]
                 used.append((i, e.n))
         st.used = tuple(used)
         return st

@@ -23,8 +23,8 @@ import torch
 from . import hip
 from .e2vid.image_reconstructor import ImageReconstructor
 from .evaluation.metrics import semseg_accum_confusion_to_acc, semseg_accum_confusion_to_iou
-from .run_segmentation import (VOXEL_FLAVOURS, MultiSegmentationResult, _event_capacity, _event_representation,
-                               _models_from_checkpoints, _rectify_maps, _RingStage)
+from .run_segmentation import (VOXEL_FLAVOURS, MultiSegmentationResult, _check_hot_pixel_masks, _event_capacity,
+                               _event_representation, _HotPixelSlots, _models_from_checkpoints, _rectify_maps, _RingStage)
 
 
 class _SequenceStage(_RingStage):
@@ -84,12 +84,17 @@ class SequenceSegmenter:
     window_duration=d in place of window_events (ring_capacity must then be given): segment_at(t_end=[...]) cuts the DSEC loader's
     fixed_duration windows (datasets.event_feed.sequence_windows_fixed_duration): T windows of d time units ending at t_end.
     segment_at(windows=[...]): per stream None or T explicit (start, count) pairs in absolute event indices -- any other rule, such as
-    the DDD17 loader's datasets.event_feed.sequence_windows_by_time."""
+    the DDD17 loader's datasets.event_feed.sequence_windows_by_time.
+
+    hot_pixel_masks=[...]: as MultiStreamSegmenter's -- per stream None or a HotPixelMask of the sensor's size (with every entry
+    None: the rectify maps' size, else the size the events are voxelised at), applied to the raw events by hip.event_ingest_masked
+    on both ingest heads (with a loader grid: its scatter half, out=None, in front of hip.event_grid_finish); every one of a
+    stream's T windows reads that stream's mask.  set_hot_pixels(stream, mask | None) changes it between rounds."""
 
     def __init__(self, encoder, decoder, height, width, options, n_streams, sequence_steps=None, window_events=None, ring_capacity=None,
                  voxel='temporal', rectify_maps=None, graph=False, copy=True, palette=None, want_confidence=False, out_hw=None,
                  ignore_index=255, device=None, window_duration=None, grid_hw=None, grid_rows=None, grid_resize=None,
-                 grid_normalize=None, representation=None):
+                 grid_normalize=None, representation=None, hot_pixel_masks=None):
         if not isinstance(n_streams, int) or isinstance(n_streams, bool) or n_streams < 1:
             raise hip.EssHipError(f'n_streams={n_streams!r}: a positive number of streams is needed')
         T = sequence_steps
@@ -126,7 +131,9 @@ class SequenceSegmenter:
         self.ring_capacity = R = hip.event_column_stride(R)
         self.voxel, self.ignore_index = voxel, ignore_index
         self.representation = representation
-        self._rep = _event_representation(representation, voxel, rectify_maps, encoder.num_bins)  # (the last refusal before the device)
+        self._rep = _event_representation(representation, voxel, rectify_maps, encoder.num_bins)
+        if hot_pixel_masks is not None:
+            _check_hot_pixel_masks(hot_pixel_masks, n_streams, None)  # (the last refusal before the device)
         self.copy_outputs = bool(copy)
         self.device = device if device is not None else torch.device('cuda:0')
         self.model = encoder.to(self.device).eval()
@@ -156,6 +163,10 @@ class SequenceSegmenter:
         self._ring_host = tuple(torch.zeros(S, R, dtype=d).pin_memory() for d in dtypes)
         self._ring_np = tuple(c.numpy() for c in self._ring_host)
         n_words = 5 if voxel == 'trilinear' else 4  # (rows, starts, counts, formats; the map words behind them)
+        self._hot = None
+        if hot_pixel_masks is not None:  # (the mask words behind the map words, which are then always there: -1 is NONE for both)
+            n_words = 6
+            self._hot = _HotPixelSlots(hot_pixel_masks, n_streams, tuple(maps.shape[1:3]) if maps is not None else (Hs, Ws), dev)
         self._words = torch.zeros(n_words, T * S, dtype=torch.int32, device=dev)
         self._words[4:].fill_(hip.RECTIFY_NONE)
         self._in = torch.zeros(T * S, self.num_bins, height, width, dtype=torch.float32, device=dev)
@@ -258,6 +269,15 @@ class SequenceSegmenter:
                 done.synchronize()
             self._feeds[s] = _SequenceFeed()
 
+    # ---- hot-pixel masks
+    def set_hot_pixels(self, stream, mask):
+        """stream reads `mask` (a datasets.hot_pixels.HotPixelMask of the segmenter's sensor size, or None) in every one of its T
+        windows from the next round on: the words go into the static mask buffer here, outside the capture; no re-capture"""
+        if self._hot is None:
+            raise hip.EssHipError('set_hot_pixels: this segmenter was built without hot_pixel_masks, so no mask buffer exists under its '
+                                  'capture: pass hot_pixel_masks=[...] (a list of None will do)')
+        self._hot.assign(self._stream(stream, 'set_hot_pixels'), mask)
+
     # ---- metrics
     def _rows(self, streams, what):
         return list(range(self.n_streams)) if streams is None else [self._stream(s, what) for s in streams]
@@ -283,7 +303,15 @@ class SequenceSegmenter:
         """the device work of one sequence round on the static rings, words and ground truth -> (labels, colour, confidence)"""
         with torch.no_grad():
             ev = self._in
-            if self._loader_grid:  # the loader's grid: the sums at the size the loader voxelises at, then its normalise / cut / resize
+            if self._hot is not None:  # hot_pixel_masks: both heads through the one masked entry point
+                tri, w = self.voxel == 'trilinear', self._words
+                out = None if self._loader_grid else ev
+                hip.event_ingest_masked(*self._ring, *w[:4], out, self._hot.words, w[5], self._hot.size, representation=self._rep,
+                                        trilinear=tri, maps=self._maps if tri else None, map_of=w[4] if tri else None, acc=self._acc)
+                if self._loader_grid:
+                    crop_rows, resize, normalize = self._grid
+                    hip.event_grid_finish(w[2], self._acc, ev, crop_rows=crop_rows, resize=resize, normalize=normalize)
+            elif self._loader_grid:  # the loader's grid: the sums at the size the loader voxelises at, then its normalise / cut / resize
                 if self.voxel == 'trilinear':
                     hip.event_scatter_ring_trilinear(*self._ring, *self._words[:4], self._acc, self._maps, self._words[4])
                 elif self._rep != hip.EVENT_REP_SIGNED:
@@ -468,6 +496,8 @@ class SequenceSegmenter:
         st.formats_np[:] = 0
         if st.maps_np is not None:
             st.maps_np[:] = hip.RECTIFY_NONE
+        if st.masks_np is not None:
+            st.masks_np[:] = hip.MASK_NONE
         for s, w in enumerate(wins):
             if w is not None:
                 for i, (start, count) in enumerate(w):
@@ -476,6 +506,8 @@ class SequenceSegmenter:
                     st.starts_np[k], st.counts_np[k], st.formats_np[k] = start % R, count, self._feeds[s].format or 0
                     if st.maps_np is not None:
                         st.maps_np[k] = self._map_of[s]
+                    if st.masks_np is not None:  # (every one of a stream's T windows reads that stream's mask)
+                        st.masks_np[k] = self._hot.mask_of[s]
         self._words.copy_(st.words, non_blocking=True)
         for s, g in enumerate(gts):
             if g is not None and on[s]:

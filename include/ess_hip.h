@@ -569,6 +569,59 @@ int ess_event_ingest_columns_rep(const void* t, const void* x, const void* y, co
                                  const int32_t* formats, int64_t stride, int32_t n_streams, int32_t channels, int32_t height,
                                  int32_t width, void* acc, size_t acc_bytes, float* out, int32_t representation, ess_stream_t stream);
 
+/* HOT-PIXEL MASKS in the column / ring ingest -- PURELY ADDITIVE to ABI 110 (ess_version() is unchanged; no existing entry point
+ * changes, and the unmasked entry points launch the kernels they launched before).  The reference removes hot pixels from the
+ * finished grid (events[:, :, y, x] = 0 for every line of hot_pixels_file).  Here a hot pixel's events are dropped where (x, y) is
+ * still the RAW sensor coordinate, before a rectify map moves them or a resize blends them: one mask per sensor, picked per slot.
+ *   masks (device, 16-byte aligned): uint32 [n_masks][mask_height][mask_words], mask_words = ceil(mask_width / 32); pixel (x, y) is
+ *     bit x & 31 of word x >> 5 of row y, a set bit means hot.  null iff n_masks == 0.  mask_height, mask_width in 1..32768: the
+ *     SENSOR's size, whatever the grid's, as for the rectify maps.
+ *   mask_of (device, int32 [n_slots]), read by the kernel like counts and formats:
+ *     ESS_MASK_NONE (-1): no mask;   0 .. n_masks - 1: that mask;
+ *     any other word: the slot counts as empty (nothing of it is read, an all-zero grid), as an unknown map word does.
+ * Per event: x, y are decoded from the raw words as the format says; the event is DROPPED when it lies inside
+ * [0, mask_width) x [0, mask_height) and its bit is set; every other event -- one outside the mask's rectangle included -- goes
+ * through the flavour with its words unchanged, and the flavour decides about it as in the unmasked entry points.  The window's
+ * time base (first / last, d_last) is taken from the window's first and last event WHETHER THEY ARE MASKED OR NOT: the
+ * reference voxelises first and zeroes the pixel afterwards, so its time base counts hot events too.  A masked call therefore gives,
+ * bit for bit, what the unmasked entry point gives on columns in which every masked event's x was replaced by a value outside
+ * every grid and map (-1, or 65535 under ESS_EVCOL_XY_U16); for the integer-pixel flavours with a mask of the grid's size that is
+ * the unmasked grid followed by the reference's zeroing.
+ *
+ * ess_event_ingest_masked: one entry point for both sources, every flavour and both halves.  t .. acc_bytes: the arguments of
+ * ess_event_ingest_ring_rep (`channels` planes a slot).  rows == starts == NULL selects the COLUMN source: slot s's window lies at
+ * the head of row s, `ring` is the stride (a multiple of 16), n_rows is not read -- ess_event_ingest_columns*'s launch.  Only one of
+ * the two null: ESS_EINVAL.  representation: ESS_EVENT_REP_*.  trilinear: 0, or 1: the trilinear flavour, maps .. map_width are
+ * read as by ess_event_ingest_ring_trilinear and representation must be ESS_EVENT_REP_SIGNED (with 0 they are not read).  out:
+ * nullable.  NULL: scatter only, acc keeps the sums for ess_event_grid_finish / _finish_window, as behind ess_event_scatter_ring*;
+ * else the plain finish follows as in ess_event_ingest_*, and acc is all zero again.  Counts, ESS_INGEST_KEEP, format words, rows,
+ * starts, alignment and the 2^22 bound: as they stand -- a mask only removes contributions.  NOT reproduced: a mask applied to
+ * the packed-record source (ess_event_ingest); rectified histograms.
+ *
+ * ess_event_hot_pixel_mask: per-pixel event counts -> masks.  sums (device, 16-byte aligned, READ ONLY): int64
+ * [n][2][height][width], the sums the histogram flavour leaves behind a scatter (ESS_EVENT_REP_HISTOGRAM: exact multiples of
+ * 2^40, one per event).  thresholds (device, int64 [n], in EVENTS), read by the kernel:
+ *   thresholds[i] >= 0: bit (y, x) of masks[i] is set iff (sums[i][0][y][x] + sums[i][1][y][x]) >> 40 > thresholds[i] -- exact
+ *     integer arithmetic, both polarities counted together;
+ *   thresholds[i] <  0: masks[i] is neither read nor written.
+ * masks (device, 16-byte aligned): uint32 [n][height][ceil(width / 32)], the layout above.  mode:
+ *   ESS_MASK_REPLACE (0): whole words are written; the bits at x >= width of a row's last word are written as 0;
+ *   ESS_MASK_OR (1):      the new bits are or-ed onto the words that are there; the tail bits stay as they were.
+ * A wave packs 64 consecutive x of a row with one ballot; plain stores, no atomics, no memset, one launch shaped by n, height and
+ * width alone: capturable.  The sums of SEVERAL scatters onto one acc (acc not finished in between) may be thresholded as long
+ * as no pixel of a slot collects more than 2^22 events (the int64 bound above).  height, width in 1..32768, n in 1..65535; any
+ * other mode: ESS_EINVAL.  NOT provided: a mean + k * sigma rule -- thresholds are the caller's, in events.                      */
+enum { ESS_MASK_NONE = -1 };
+enum { ESS_MASK_REPLACE = 0, ESS_MASK_OR = 1 };
+int ess_event_ingest_masked(const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
+                            const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots,
+                            int32_t channels, int32_t height, int32_t width, void* acc, size_t acc_bytes, float* out,
+                            int32_t representation, int32_t trilinear, const float* maps, const int32_t* map_of, int32_t n_maps,
+                            int32_t map_height, int32_t map_width, const uint32_t* masks, const int32_t* mask_of, int32_t n_masks,
+                            int32_t mask_height, int32_t mask_width, ess_stream_t stream);
+int ess_event_hot_pixel_mask(const int64_t* sums, int32_t n, int32_t height, int32_t width, const int64_t* thresholds, uint32_t* masks,
+                             int32_t mode, ess_stream_t stream);
+
 /* Training batches from events: the loaders' augmentation where the grid is written -- PURELY ADDITIVE to ABI 110.
  * DSEC flips horizontally with p = 0.5 (DSEC/dataset/sequence.py:291-295); DDD17 flips, then crops 120 x 216 at random inside the
  * bottom 120 rows (datasets/ddd17_events_loader.py:87-96, 173-183).  Both are index permutations of the finished grid and of its

@@ -27,7 +27,12 @@ contiguous), alternating.  --loader-finish-only skips everything in front of the
 And the event REPRESENTATIONS (representations()): the signed ring ingest against hip.event_ingest_ring_rep's separate-polarity and
 histogram flavours on the same rings, at 480 x 640 and 260 x 346.
 
+And the HOT-PIXEL MASKS (masked(), --masked: these rows alone): the ring source, signed temporal and trilinear through the distortion
+map, three ways in ONE run -- the unmasked kernel, hip.event_ingest_masked under an all-zero mask, and under a mask of 100 hot pixels
+that carry 5 % of the events -- and hip.event_hot_pixel_mask on one histogram a stream.
+
 usage: python tools/bench_voxel.py --ingest --slices 8 --events 100000 --bins 5
+       python tools/bench_voxel.py --ingest --masked --slices 8 --events 100000 --bins 5
        python tools/bench_voxel.py --ingest --representations-only --slices 8 --events 100000 --bins 5
        python tools/bench_voxel.py --ingest --loader-finish-only --slices 160 --events 100000 --bins 5 --reps 20"""
 import argparse
@@ -53,6 +58,7 @@ def main():
     ap.add_argument('--ingest', action='store_true', help='hip.event_ingest against hip.voxel_grid_temporal (see above)')
     ap.add_argument('--loader-finish-only', action='store_true', help='(with --ingest) only the loader-finish rows')
     ap.add_argument('--representations-only', action='store_true', help='(with --ingest) only the event-representation rows')
+    ap.add_argument('--masked', action='store_true', help='(with --ingest) only the hot-pixel mask rows')
     a = ap.parse_args()
     if a.ingest:
         return ingest(a)
@@ -241,11 +247,99 @@ def representations(a):
     return {'workload': f'{S} streams x {n} events, bins={bins}, ring of {ring} from start {start}', 'reps': a.reps, 'rows': rows}
 
 
+def masked(a):
+    """The hot-pixel masks beside the kernels they wrap, on int64 / uint16 rings read from start 3 (S streams x n events, 5 % of them
+    on 100 pixels of the sensor): per flavour -- signed temporal, trilinear through the synthetic distortion map -- the unmasked
+    entry point, hip.event_ingest_masked with an all-zero mask (the added load and test, no event dropped) and with the 100 pixels
+    masked (5 % fewer events reach the flavour); three alternating rounds of a.reps calls each.  And hip.event_hot_pixel_mask on
+    [S, 2, H, W] histogram sums.  -> rows for the JSON"""
+    import numpy as np
+    from ess_amd import hip
+    from ess_amd.datasets.hot_pixels import HotPixelMask
+    S, n, C, H, W = a.slices, a.events, a.bins, a.height, a.width
+    dev = torch.device('cuda:0')
+    g = np.random.default_rng(2)
+    stride = hip.event_column_stride(n)
+    ring, start = 2 * stride, 3
+    at = (start + np.arange(n)) % ring
+    hot = g.permutation(H * W)[:100]
+    x, y = g.integers(0, W, (S, n)), g.integers(0, H, (S, n))
+    on_hot = g.random((S, n)) < 0.05
+    pick = hot[g.integers(0, len(hot), (S, n))]
+    x, y = np.where(on_hot, pick % W, x), np.where(on_hot, pick // W, y)
+    cols = [np.zeros((S, ring), d) for d in (np.int64, np.uint16, np.uint16, np.uint8)]
+    cols[0][:, at] = np.sort(g.integers(0, 30_000, (S, n)), axis=1)
+    cols[1][:, at], cols[2][:, at], cols[3][:, at] = x, y, g.integers(0, 2, (S, n))
+    dcols = tuple(torch.from_numpy(c.view(np.int16) if c.dtype == np.uint16 else c).to(dev) for c in cols)
+    words = (torch.arange(S, dtype=torch.int32, device=dev), torch.full((S,), start, dtype=torch.int32, device=dev),
+             torch.full((S,), n, dtype=torch.int32, device=dev), torch.full((S,), hip.EVCOL_XY_U16 | hip.EVCOL_T_I64, dtype=torch.int32, device=dev))
+    mask = HotPixelMask.from_locations(np.stack([hot % W, hot // W], 1), H, W)
+    dmasks = torch.from_numpy(np.stack([np.zeros_like(mask.words), mask.words]).view(np.int32)).to(dev)  # mask 0: empty, mask 1: the 100
+    of = {'all_zero_mask': torch.zeros(S, dtype=torch.int32, device=dev), 'hot_100_pixels': torch.ones(S, dtype=torch.int32, device=dev)}
+    yy, xx = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing='ij')
+    dmap = torch.from_numpy(np.stack([xx + 3.0 * np.sin(yy / 40.0), yy + 3.0 * np.cos(xx / 50.0)], -1).astype(np.float32)[None]).to(dev)
+    map0 = torch.zeros(S, dtype=torch.int32, device=dev)
+    out, acc = torch.empty(S, C, H, W, device=dev), torch.zeros(S, C, H, W, dtype=torch.int64, device=dev)
+    ways = {'temporal_unmasked': lambda: hip.event_ingest_ring(*dcols, *words, out, acc=acc),
+            'trilinear_unmasked': lambda: hip.event_ingest_ring_trilinear(*dcols, *words, out, dmap, map0, acc=acc)}
+    for k, w in of.items():
+        ways[f'temporal_{k}'] = lambda w=w: hip.event_ingest_masked(*dcols, *words, out, dmasks, w, (H, W), acc=acc)
+        ways[f'trilinear_{k}'] = lambda w=w: hip.event_ingest_masked(*dcols, *words, out, dmasks, w, (H, W), trilinear=True, maps=dmap,
+                                                                     map_of=map0, acc=acc)
+    sums = hip.event_scatter_ring_rep(*dcols, *words, torch.zeros(S, 2, H, W, dtype=torch.int64, device=dev), hip.EVENT_REP_HISTOGRAM)
+    thresholds = torch.full((S,), 20, dtype=torch.int64, device=dev)
+    found = torch.zeros(S, H, hip.mask_words(W), dtype=torch.int32, device=dev)
+    ways['event_hot_pixel_mask'] = lambda: hip.event_hot_pixel_mask(sums, thresholds, found)
+    for fn in ways.values():  # warm-up: clocks, allocator
+        for _ in range(50):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in ways}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(3):  # alternating: drift of the box hits every way alike
+        for k, fn in ways.items():
+            e0.record()
+            for _ in range(a.reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / a.reps)
+    # what is timed is what it says: an all-zero mask gives the unmasked bits, the 100 pixels remove their events and only those,
+    # and the calibration finds exactly the 100 (5 % of n over 100 pixels: ~ n / 2000 events each, against ~ n / (H W) elsewhere)
+    for f in ('temporal', 'trilinear'):
+        plain = ways[f'{f}_unmasked']().clone()
+        assert torch.equal(ways[f'{f}_all_zero_mask']().view(torch.int32), plain.view(torch.int32)), f
+        assert not torch.equal(ways[f'{f}_hot_100_pixels']().view(torch.int32), plain.view(torch.int32)), f
+    cut = ways['temporal_hot_100_pixels']()
+    assert not bool(cut[:, :, torch.from_numpy(hot // W).to(dev), torch.from_numpy(hot % W).to(dev)].any()) and not bool(acc.any())
+    ways['event_hot_pixel_mask']()
+    host = found.cpu().numpy().view(np.uint32)
+    expect = n * 0.05 / 100 > 2 * 20
+    if expect:
+        assert all(np.array_equal(host[s], mask.words) for s in range(S)), 'the calibration does not return the 100 pixels'
+    med = {k: sorted(v)[1] for k, v in ms.items()}
+    row = {'ms_per_batch': {k: {'median': round(med[k], 5), 'min': round(min(v), 5), 'max': round(max(v), 5)} for k, v in ms.items()}}
+    for f in ('temporal', 'trilinear'):
+        spread = max(ms[f'{f}_unmasked']) - min(ms[f'{f}_unmasked'])
+        row[f'{f}_unmasked_spread_ms'] = round(spread, 5)
+        for k in of:
+            d = med[f'{f}_{k}'] - med[f'{f}_unmasked']
+            row[f'{f}_{k}_minus_unmasked_ms'] = round(d, 5)
+            row[f'{f}_{k}_over_unmasked'] = round(med[f'{f}_{k}'] / med[f'{f}_unmasked'], 3)
+            row[f'{f}_{k}_SLOWER_than_unmasked'] = bool(d > spread)
+    return {'workload': f'{S} streams x {n} events, bins={C}, {H} x {W}, ring of {ring} from start {start}; 100 hot pixels carry 5 % of '
+                        f'the events; event_hot_pixel_mask at {S} x {H} x {W}', 'reps': a.reps, 'mask_bytes': int(mask.words.nbytes), 'rows': row}
+
+
 def ingest(a):
     import numpy as np
     from ess_amd import hip
     from ess_amd.datasets.data_util import pack_event_records
     hip.lib()
+    if a.masked:
+        print(json.dumps({'metric': 'ring events -> grids under hot-pixel masks, ms per batch', 'unit': 'ms', 'masked': masked(a),
+                          'data': 'synthetic'}))
+        return
     if a.representations_only:
         print(json.dumps({'metric': 'ring events -> grids in the three event representations, ms per batch', 'unit': 'ms',
                           'representations': representations(a), 'data': 'synthetic'}))
