@@ -6,12 +6,16 @@ Same constructor and `update_reconstruction(event_tensor) -> (out, states, laten
 not change results: no CudaTimer device synchronisations inside the hot loop (the reference syncs >= 5 times
 per time step, e2vid/utils/timers.py:23-26), and an extra keyword `need_image=False` that lets the trainers
 skip the decoder half of the UNet for all but the last time step.
+
+`PostProcessor` (reference :166-185) turns the model's output into a displayable frame: unsharp mask, intensity rescale to 8 bit
+(fixed or auto-HDR bounds), image filter -- here two or three HIP launches with all state in device memory, so that a streaming
+driver can capture them at the end of its window.
 """
 import os
 
 import torch
 
-from .utils.inference_utils import CropParameters, EventPreprocessor
+from .utils.inference_utils import CropParameters, EventPreprocessor, ImageFilter, IntensityRescaler, UnsharpMaskFilter
 
 
 _LEAN = os.environ.get('ESS_LEAN', '1') != '0'  # diagnostic switch: materialise every fp32 state
@@ -149,3 +153,41 @@ class ImageReconstructor:
                     if unet is not None:
                         unet.steps_left = None
         return res
+
+
+class PostProcessor:
+    """Unsharp mask -> intensity rescale -> image filter (reference :166-185), for frames of `n` samples.
+
+    process(frame) -> fp32 [n, 1, H, W], the reference's result (float(uint8) / 255);  process_u8(frame) -> uint8 [n, H, W], the frame
+    itself.  Both are capture-safe: no synchronisation, no host state -- the reference fetches min / max with .item() and keeps its
+    auto-HDR history in a deque.  Each call advances the auto-HDR history (one per sample: the one extension; n = 1 is the reference).
+    crop: a CropParameters -- or a window (y0, x0, H, W) -- when the frame comes at the model's reflection-padded size: the unsharp
+    mask and the auto-HDR min / max see the whole padded frame (as the reference's, which filters before it crops), only the
+    sensor's window is written.  bilateral_filter_sigma > 0 is refused (ImageFilter)."""
+
+    def __init__(self, device, options, n=1, crop=None):
+        self.device = device
+        self.unsharp_mask_filter = UnsharpMaskFilter(options, device=self.device)
+        self.intensity_rescaler = IntensityRescaler(options, n=n, device=self.device)
+        self.image_filter = ImageFilter(options)
+        if isinstance(crop, CropParameters):
+            crop = None if crop.is_identity else (crop.iy0, crop.ix0, crop.height, crop.width)
+        self.window = None if crop is None else tuple(int(v) for v in crop)
+
+    def reset(self, samples=None):
+        self.intensity_rescaler.reset(samples)
+
+    def state_tensors(self):
+        return self.intensity_rescaler.state_tensors()
+
+    def _run(self, frame, want_u8, want_f32):
+        f = self.unsharp_mask_filter
+        with torch.no_grad():
+            return self.intensity_rescaler.rescale(frame, f.weights, f.unsharp_mask_amount, window=self.window, want_u8=want_u8,
+                                                   want_f32=want_f32)
+
+    def process(self, new_predicted_frame):
+        return self.image_filter(self._run(new_predicted_frame, False, True)[1])
+
+    def process_u8(self, new_predicted_frame):
+        return self._run(new_predicted_frame, True, False)[0]

@@ -1,5 +1,6 @@
 """E2VID inference option defaults (reference: e2vid/options/inference_options.py).  Only the flags the ESS
-training path consumes through ImageReconstructor / EventPreprocessor are kept."""
+training path consumes through ImageReconstructor / EventPreprocessor are kept, and those of the frame post-processing
+(Imin, Imax, auto_hdr*, unsharp_mask_*, bilateral_filter_sigma: image_reconstructor.PostProcessor)."""
 import argparse
 
 

@@ -22,7 +22,7 @@ data handling, outside the hot path: `iter_windows_fixed_size` covers the in-mem
 import torch
 
 from .. import copies, hip
-from .image_reconstructor import ImageReconstructor
+from .image_reconstructor import ImageReconstructor, PostProcessor
 
 
 def events_to_voxel_grid_device(events, num_bins, width, height, device):
@@ -126,13 +126,17 @@ class GraphedWindowState:
 class StreamingReconstructor(GraphedWindowState):
     """One sequence, one window at a time; the recurrent state persists between calls (reference run_reconstruction.py:84-112).
 
-    update(event_tensor [1, num_bins, H, W] or [num_bins, H, W]) -> (image [1, 1, H, W], latent dict) ; reset() drops the state."""
+    update(event_tensor [1, num_bins, H, W] or [num_bins, H, W]) -> (image [1, 1, H, W], latent dict) ; reset() drops the state.
+    postprocess=True: update() -> (image, latent, frame uint8 [H, W]) -- the displayable frame of image_reconstructor.PostProcessor
+    (unsharp mask, fixed or auto-HDR rescale, 8 bit; cropped to the sensor's size where the model runs on a padded one).  Its launches
+    are part of the captured window in graph mode; the eager first window and the replays share the one auto-HDR history in device
+    memory, which reset() empties."""
 
-    def __init__(self, model, height, width, options, device=None, graph=False, copy=True):
+    def __init__(self, model, height, width, options, device=None, graph=False, copy=True, postprocess=False):
         """copy (graph mode): update() returns CLONES of the captured graph's static output buffers, like the eager path's fresh
         tensors -- a caller that keeps frames across windows (the reference script's writer / display queue) must not see them
         overwritten by the next replay.  copy=False hands out the static buffers themselves (70 KB - 1 MB less traffic per
-        window; valid until the next update())."""
+        window; valid until the next update()).  It governs the post-processed frame as it governs the image."""
         self.copy_outputs = bool(copy)
         self.device = device if device is not None else torch.device('cuda:0')
         self.model = model.to(self.device).eval()
@@ -141,9 +145,12 @@ class StreamingReconstructor(GraphedWindowState):
         self.use_graph = graph
         self._g = None
         self.n_windows = 0
+        self.post = PostProcessor(self.device, options, n=1, crop=self.rec.crop) if postprocess else None
 
     def reset(self):
         self.rec.last_states_for_each_channel = {'grayscale': None}
+        if self.post is not None:
+            self.post.reset()
         self.n_windows = 0  # (the captured graph stays valid: it reads the static state buffers, which the next first step rewrites)
 
     def update_from_events(self, events):
@@ -159,29 +166,38 @@ class StreamingReconstructor(GraphedWindowState):
         first = self.rec.last_states_for_each_channel['grayscale'] is None
         if not self.use_graph or first:
             # the first window of a sequence runs eagerly: no previous state (x-only gate convolutions), different launches
-            img, states, latent = self.rec.update_reconstruction(ev)
+            outputs, states = self._window(ev)
             if self.use_graph:
                 self._adopt_state(states)
             self.n_windows += 1
-            return img, latent
+            return outputs
         if self._g is None:
             self._capture(ev)
         self._in.copy_(ev, non_blocking=True)
         self._g.replay()
         self.n_windows += 1
         if not self.copy_outputs:
-            return self._out_img, self._out_latent
+            return self._outputs
         lat = self._out_latent
         if isinstance(lat, dict):
             lat = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in lat.items()}
         elif torch.is_tensor(lat):
             lat = lat.clone()
-        return self._out_img.clone(), lat
+        return (self._out_img.clone(), lat) + tuple(t.clone() for t in self._outputs[2:])
 
     # ---- hipGraph mode: static input, static state buffers; one recorded window = step + state carry (GraphedWindowState)
     def _window(self, ev):
         img, states, latent = self.rec.update_reconstruction(ev)
-        return (img, latent), states
+        if self.post is None:
+            return (img, latent), states
+        return (img, latent, self.post.process_u8(img)[0]), states
+
+    def _capture(self, example):
+        """the warm-up window in front of the recording must not leave an entry in the auto-HDR history either"""
+        saved = [t.clone() for t in self.post.state_tensors()] if self.post is not None else []
+        super()._capture(example)
+        for t, sv in zip(self.post.state_tensors() if saved else [], saved):
+            t.copy_(sv)
 
     @property
     def _out_img(self):

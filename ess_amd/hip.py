@@ -83,6 +83,7 @@ EXPORTS = [
     'ess_event_grid_finish_window', 'ess_label_window',
     'ess_event_scatter_ring_rep', 'ess_event_ingest_ring_rep', 'ess_event_ingest_columns_rep',
     'ess_event_ingest_masked', 'ess_event_hot_pixel_mask',
+    'ess_recon_post_frame', 'ess_recon_post_bounds', 'ess_event_preview',
 ]
 
 
@@ -195,6 +196,9 @@ def lib():
             'ess_event_ingest_columns_rep': [P, P, P, P, P, P, I64, I, I, I, I, P, c_size_t, P, I, P],
             'ess_event_ingest_masked': [P, P, P, P, P, P, P, P, I64, I, I, I, I, I, P, c_size_t, P, I, I, P, P, I, I, I, P, P, I, I, I, P],
             'ess_event_hot_pixel_mask': [P, I, I, I, P, P, I, P],
+            'ess_recon_post_frame': [P, P, F, F, P, P, P, I, I, I, I, I, I, I, P],
+            'ess_recon_post_bounds': [P, P, F, F, I, I, I, P, c_size_t, P, P, I, P, P],
+            'ess_event_preview': [P, P, I, I, I, I, I, I, P],
         }
         for name, argtypes in sig.items():
             fn = getattr(L, name)
@@ -1710,6 +1714,118 @@ def seg_head_eval(x, C, weight, bias, gt, confusion, ignore_index=255, out_hw=No
                                    ptr(colour, torch.uint8), ptr(conf), ptr(gt, torch.uint8), ptr(confusion, torch.int64),
                                    int(ignore_index), N, C, K, H, W, y0, x0, h, w, Ho, Wo, stream()), 'ess_seg_head_eval')
     return labels, colour, conf
+
+
+# ------------------------------------------------------------------------------------------ reconstruction post-processing
+RECON_POST_PARTIALS = 256   # ESS_RECON_POST_PARTIALS: min / max partial pairs per sample in recon_post_bounds' workspace
+RECON_POST_MAX_FILTER = 63  # ESS_RECON_POST_MAX_FILTER: the largest auto_hdr_median_filter_size (a history of 64 entries: one wave)
+PREVIEW_MODES = {'red-blue': 0, 'grayscale': 1}  # ESS_PREVIEW_RED_BLUE, ESS_PREVIEW_GRAYSCALE
+
+
+def _formed(fn, name, t, dtype, shape):
+    """`t` is a contiguous `dtype` tensor of `shape`, or the call is refused (where it lies is _on_device's question, asked last)"""
+    if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        got = f'{t.dtype}{tuple(t.shape)}' if torch.is_tensor(t) else type(t).__name__
+        raise EssHipError(f'{fn}: {name} must be a contiguous {dtype} {list(shape)} tensor, got {got}')
+    return t
+
+
+def _recon_post_image(fn, img, weights, amount):
+    """-> (N, Hs, Ws, the 25 weights as a ctypes array or None, c1, amount)"""
+    if not torch.is_tensor(img) or img.dtype != torch.float32 or img.dim() != 4 or img.shape[1] != 1 or img.numel() == 0 or not img.is_contiguous():
+        got = f'{img.dtype}{tuple(img.shape)}' if torch.is_tensor(img) else type(img).__name__
+        raise EssHipError(f'{fn}: img must be a non-empty contiguous fp32 [N, 1, Hs, Ws] tensor, got {got}')
+    amount = float(amount)
+    if amount != amount:
+        raise EssHipError(f'{fn}: amount is NaN')
+    w = None
+    if amount > 0:
+        if weights is None:
+            raise EssHipError(f'{fn}: amount={amount} > 0 needs the 5 x 5 weights')
+        flat = np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights, dtype=np.float32).reshape(-1)
+        if flat.size != 25 or not np.isfinite(flat).all():
+            raise EssHipError(f'{fn}: weights must be 25 finite values (5 x 5), got {flat.size}')
+        w = (c_float * 25)(*flat.tolist())
+    c1 = float(np.float32(1 + amount))  # (1 + amount) in double, rounded to fp32 once: the reference's `(1 + amount) * img`
+    return img.shape[0], img.shape[2], img.shape[3], w, c1, float(np.float32(amount))
+
+
+def recon_post_frame(img, weights, amount, bounds, window=None, out_u8=None, out_f32=None, want_u8=True, want_f32=False):
+    """Unsharp mask + intensity rescale + 8-bit quantisation in one pass (ess_recon_post_frame) -> (frame_u8 [N, H, W] uint8 or None,
+    frame_f32 [N, 1, H, W] = float(u8) / 255 or None).  img: fp32 [N, 1, Hs, Ws]; weights: the 5 x 5 Gaussian (host values; unused for
+    amount <= 0, which skips the stencil); bounds: fp32 [N, 2] ON THE DEVICE = (Imin, Imax - Imin) per sample; window (y0, x0, H, W): the
+    part of the source that is written (default: all) -- the stencil still sees the whole source, zero beyond its borders.  out_u8 /
+    out_f32: the caller's output tensors.  Per pixel, in fp32 without fused operations: blur = sum of w * v in row-major tap order,
+    s = c1 v - amount blur, q = (255 (s - Imin)) / range, clamped to [0, 255] and truncated.  A NaN pixel gives 0."""
+    fn = 'recon_post_frame'
+    N, Hs, Ws, w, c1, amount = _recon_post_image(fn, img, weights, amount)
+    y0, x0, H, W = (0, 0, Hs, Ws) if window is None else (int(v) for v in window)
+    if y0 < 0 or x0 < 0 or H <= 0 or W <= 0 or y0 + H > Hs or x0 + W > Ws:
+        raise EssHipError(f'{fn}: window {(y0, x0, H, W)} leaves the {Hs} x {Ws} source')
+    if out_u8 is None and out_f32 is None and not want_u8 and not want_f32:
+        raise EssHipError(f'{fn}: neither frame_u8 nor frame_f32 is asked for')
+    _formed(fn, 'bounds', bounds, torch.float32, (N, 2))
+    if out_u8 is not None:
+        _formed(fn, 'out_u8', out_u8, torch.uint8, (N, H, W))
+    if out_f32 is not None:
+        _formed(fn, 'out_f32', out_f32, torch.float32, (N, 1, H, W))
+    _on_device(fn, [(k, v) for k, v in (('img', img), ('bounds', bounds), ('out_u8', out_u8), ('out_f32', out_f32)) if v is not None])
+    if out_u8 is None and want_u8:
+        out_u8 = torch.empty(N, H, W, dtype=torch.uint8, device=img.device)
+    if out_f32 is None and want_f32:
+        out_f32 = torch.empty(N, 1, H, W, dtype=torch.float32, device=img.device)
+    _check(lib().ess_recon_post_frame(ptr(img), w, c1, amount, ptr(bounds), ptr(out_u8, torch.uint8), ptr(out_f32), N, Hs, Ws, y0, x0, H, W,
+                                      stream()), 'ess_recon_post_frame')
+    return out_u8, out_f32
+
+
+def recon_post_bounds(img, weights, amount, workspace, ring, ring_state, filter_size, bounds):
+    """The auto-HDR step of IntensityRescaler with its history on the device (ess_recon_post_bounds; two launches, no
+    synchronisation): min / max of the SHARPENED source per sample -> clip to [0, 0.45] / [0.55, 1] in fp64 -> push into the sample's
+    history (ring fp64 [N, filter_size + 1, 2], ring_state int32 [N, 2] = (head, count); zeros = empty) -> bounds[n] = (median of the
+    held mins, median of the held maxs minus it), np.median's rule.  workspace: fp32 [N, RECON_POST_PARTIALS, 2], fully rewritten.
+    Deviation: NaN pixels are skipped by the min / max (torch.min / max would hand NaN on)."""
+    fn = 'recon_post_bounds'
+    N, Hs, Ws, w, c1, amount = _recon_post_image(fn, img, weights, amount)
+    if isinstance(filter_size, bool) or int(filter_size) != filter_size or not 0 <= filter_size <= RECON_POST_MAX_FILTER:
+        raise EssHipError(f'{fn}: filter_size={filter_size} outside 0..{RECON_POST_MAX_FILTER}')
+    filter_size = int(filter_size)
+    if N > 65535:
+        raise EssHipError(f'{fn}: N={N} samples, at most 65535')
+    for name, t, dtype, shape in (('workspace', workspace, torch.float32, (N, RECON_POST_PARTIALS, 2)),
+                                  ('ring', ring, torch.float64, (N, filter_size + 1, 2)),
+                                  ('ring_state', ring_state, torch.int32, (N, 2)), ('bounds', bounds, torch.float32, (N, 2))):
+        _formed(fn, name, t, dtype, shape)
+    _on_device(fn, (('img', img), ('workspace', workspace), ('ring', ring), ('ring_state', ring_state), ('bounds', bounds)))
+    _check(lib().ess_recon_post_bounds(ptr(img), w, c1, amount, N, Hs, Ws, ptr(workspace), c_size_t(workspace.numel() * 4),
+                                       ptr(ring, torch.float64), ptr(ring_state, torch.int32), filter_size, ptr(bounds), stream()),
+           'ess_recon_post_bounds')
+    return bounds
+
+
+def event_preview(grids, mode='red-blue', num_bins_to_show=-1, out=None):
+    """make_event_preview for every sample of fp32 [N, C, H, W] grids (ess_event_preview) -> uint8 [N, H, W, 3] in BGR order
+    ('red-blue': blue 255 where the bin sum is > 0, red 255 where it is < 0) or uint8 [N, H, W] ('grayscale': 255 (s + 10) / 20).
+    The last num_bins_to_show planes are summed in plane order (< 0: all).  Deviation: the grey value is clamped to [0, 255] BEFORE the
+    cast; the reference casts first and lets values outside the range wrap."""
+    fn = 'event_preview'
+    if mode not in PREVIEW_MODES:
+        raise EssHipError(f"{fn}: mode must be 'red-blue' or 'grayscale', got {mode!r}")
+    if not torch.is_tensor(grids) or grids.dtype != torch.float32 or grids.dim() != 4 or grids.numel() == 0 or not grids.is_contiguous():
+        got = f'{grids.dtype}{tuple(grids.shape)}' if torch.is_tensor(grids) else type(grids).__name__
+        raise EssHipError(f'{fn}: grids must be a non-empty contiguous fp32 [N, C, H, W] tensor, got {got}')
+    if isinstance(num_bins_to_show, bool) or int(num_bins_to_show) != num_bins_to_show:
+        raise EssHipError(f'{fn}: num_bins_to_show={num_bins_to_show!r} is no whole number')
+    N, C, H, W = grids.shape
+    shape = (N, H, W, 3) if mode == 'red-blue' else (N, H, W)
+    if out is not None:
+        _formed(fn, 'out', out, torch.uint8, shape)
+    _on_device(fn, [('grids', grids)] + ([('out', out)] if out is not None else []))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=grids.device)
+    _check(lib().ess_event_preview(ptr(grids), ptr(out, torch.uint8), N, C, H, W, max(-1, min(int(num_bins_to_show), C)), PREVIEW_MODES[mode], stream()),
+           'ess_event_preview')
+    return out
 
 
 # ------------------------------------------------------------------------------------------ 'mixed' configuration (ESS_COMPUTE_F16)

@@ -747,6 +747,48 @@ int ess_seg_head_eval(const void* x, int32_t fmt, const float* weight, const flo
                       int32_t C, int32_t K, int32_t H, int32_t W, int32_t win_y0, int32_t win_x0, int32_t win_h, int32_t win_w,
                       int32_t H_out, int32_t W_out, ess_stream_t stream);
 
+/* ---- Post-processing of an E2VID reconstruction (e2vid/image_reconstructor.py:166-185 PostProcessor; e2vid/utils/inference_utils.py
+ * :18-53 make_event_preview, :112-153 IntensityRescaler, :261-279 UnsharpMaskFilter) -- PURELY ADDITIVE to ABI 110.  All three are
+ * capture-safe: no allocation, copy or synchronisation; the only workspace is the caller's.
+ *
+ * The pixel arithmetic is fixed: fp32 multiply, add and IEEE divide, each rounded once, never fused, in this order:
+ *   blur = sum_ky sum_kx weights[ky * 5 + kx] * v(y + ky - 2, x + kx - 2)   from 0.f, row-major taps; a tap outside the SOURCE plane
+ *                                                                            contributes weights * 0.f (F.conv2d(padding=2))
+ *   s    = c1 * v - amount * blur                                            c1 = (float)(1 + amount), rounded by the caller
+ *   q    = (255.f * (s - Imin)) / range;   u8 = (uint8)min(max(q, 0), 255)   truncation; a NaN gives 0
+ * amount <= 0 skips the stencil (s = v, the reference's `if amount > 0`), and `weights` may then be null.
+ * weights: 25 floats in HOST memory, read during the call and passed to the kernel by value (a captured launch keeps its copy).
+ *
+ * ess_recon_post_frame: img fp32 [N][1][Hs][Ws] (the model's output, possibly at the reflection-padded size); bounds fp32 [N][2] in
+ * DEVICE memory = (Imin, Imax - Imin) per sample; the stencil runs over the whole source, only the window (win_y0, win_x0, win_h, win_w)
+ * is written: frame_u8 uint8 [N][win_h][win_w] and / or frame_f32 fp32 [N][1][win_h][win_w] = (float)u8 / 255.f (what IntensityRescaler
+ * returns); each nullable, not both.  One 4-byte / 16-byte store per 4 pixels when win_w % 4 == 0 and the pointer is aligned so.   */
+int ess_recon_post_frame(const float* img, const float* weights, float c1, float amount, const float* bounds, uint8_t* frame_u8,
+                         float* frame_f32, int32_t N, int32_t Hs, int32_t Ws, int32_t win_y0, int32_t win_x0, int32_t win_h,
+                         int32_t win_w, ess_stream_t stream);
+
+/* The auto-HDR step of IntensityRescaler with its state in device memory, two launches:
+ * (a) min / max of s over the WHOLE source plane of each sample (NaN pixels skipped -- fminf / fmaxf; torch.min / max would return
+ *     NaN), one partial pair per workgroup: workspace fp32 [N][ESS_RECON_POST_PARTIALS][2], every slot written on every call;
+ * (b) per sample, in fp64: Imin = clip(min, 0, 0.45), Imax = clip(max, 0.55, 1); the pair is pushed into the sample's history -- ring
+ *     fp64 [N][filter_size + 1][2], ring_state int32 [N][2] = (head, count): the reference pops only when the history is LONGER than
+ *     filter_size, so it settles at filter_size + 1 entries --; bounds[n] = ((float)median(mins), (float)(median(maxs) - median(mins)))
+ *     with np.median's rule (mean of the two middle values for an even count).  ring_state all zero = empty histories.
+ * 0 <= filter_size <= ESS_RECON_POST_MAX_FILTER; N <= 65535.  Per-sample histories are this library's extension (N = 1: the reference). */
+#define ESS_RECON_POST_PARTIALS 256
+#define ESS_RECON_POST_MAX_FILTER 63
+int ess_recon_post_bounds(const float* img, const float* weights, float c1, float amount, int32_t N, int32_t Hs, int32_t Ws,
+                          float* workspace, size_t workspace_bytes, double* ring, int32_t* ring_state, int32_t filter_size,
+                          float* bounds, ess_stream_t stream);
+
+/* make_event_preview for every sample: s = sum of the last num_bins_to_show planes of grids fp32 [N][C][H][W] in plane order (fp32;
+ * num_bins_to_show < 0, 0 or >= C: all planes, as the reference's slice).  ESS_PREVIEW_RED_BLUE: out uint8 [N][H][W][3] in BGR order,
+ * blue = 255 where s > 0, red = 255 where s < 0.  ESS_PREVIEW_GRAYSCALE: out uint8 [N][H][W] = (255.f * (s + 10.f)) / 20.f clamped
+ * to [0, 255], THEN truncated (the reference casts first and lets values outside the range wrap).                                   */
+enum { ESS_PREVIEW_RED_BLUE = 0, ESS_PREVIEW_GRAYSCALE = 1 };
+int ess_event_preview(const float* grids, uint8_t* out, int32_t N, int32_t C, int32_t H, int32_t W, int32_t num_bins_to_show,
+                      int32_t mode, ess_stream_t stream);
+
 /* confusion-matrix accumulation from GIVEN predictions (evaluation/metrics.py:4-24, semseg_compute_confusion): pred_lbl,
  * labels int64 [total]; conf int64 [K][K] accumulated (conf[label][pred]) over labels != ignore_index.          */
 int ess_label_confusion(const int64_t* pred_lbl, const int64_t* labels, int64_t* conf, int64_t total, int32_t K,
