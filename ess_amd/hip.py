@@ -84,6 +84,7 @@ EXPORTS = [
     'ess_event_scatter_ring_rep', 'ess_event_ingest_ring_rep', 'ess_event_ingest_columns_rep',
     'ess_event_ingest_masked', 'ess_event_hot_pixel_mask',
     'ess_recon_post_frame', 'ess_recon_post_bounds', 'ess_event_preview',
+    'ess_viz_semseg', 'ess_viz_events', 'ess_viz_overlay',
 ]
 
 
@@ -96,6 +97,11 @@ class EssConvDesc(Structure):
 class EssConvPlan(Structure):
     _fields_ = [('cout_tile', c_int32), ('ck', c_int32), ('n_chunks', c_int32), ('n_cout_tiles', c_int32),
                 ('packed_elems', c_int64), ('packed_bytes', c_int64), ('rows_padded', c_int32), ('lds_bytes', c_int32)]
+
+
+class EssVizDst(Structure):
+    _fields_ = [('plane_stride', c_int64), ('row_stride', c_int64), ('tile_stride_y', c_int64), ('tile_stride_x', c_int64),
+                ('tile0', c_int32), ('tiles_per_row', c_int32)]
 
 
 class EssHipError(RuntimeError):
@@ -199,6 +205,9 @@ def lib():
             'ess_recon_post_frame': [P, P, F, F, P, P, P, I, I, I, I, I, I, I, P],
             'ess_recon_post_bounds': [P, P, F, F, I, I, I, P, c_size_t, P, P, I, P, P],
             'ess_event_preview': [P, P, I, I, I, I, I, I, P],
+            'ess_viz_semseg': [P, I, P, P, c_size_t, POINTER(EssVizDst), I, I, I, I, I, P],
+            'ess_viz_events': [P, P, c_size_t, POINTER(EssVizDst), I, I, I, I, I, I, P],
+            'ess_viz_overlay': [P, P, P, P, I, I, I, I, F, P],
         }
         for name, argtypes in sig.items():
             fn = getattr(L, name)
@@ -1825,6 +1834,150 @@ def event_preview(grids, mode='red-blue', num_bins_to_show=-1, out=None):
         out = torch.empty(shape, dtype=torch.uint8, device=grids.device)
     _check(lib().ess_event_preview(ptr(grids), ptr(out, torch.uint8), N, C, H, W, max(-1, min(int(num_bins_to_show), C)), PREVIEW_MODES[mode], stream()),
            'ess_event_preview')
+    return out
+
+
+# ------------------------------------------------------------------------------------------ segmentation display
+VIZ_EVENT_MODES = {'histogram': 0, 'separate_pol': 1, 'signed': 2}  # ESS_VIZ_HISTOGRAM, ESS_VIZ_SEPARATE_POL, ESS_VIZ_SIGNED
+GRID_PADDING = 2  # make_grid's default
+
+
+def grid_geometry(n, H, W, nrow=8, padding=GRID_PADDING):
+    """make_grid's layout of n tiles of H x W -> (xmaps, ymaps, Hg, Wg): xmaps = min(nrow, n) tiles per grid row, ymaps = ceil(n / xmaps)
+    grid rows; tile k at rows (k // xmaps) (H + padding) + padding, columns (k % xmaps) (W + padding) + padding."""
+    xmaps = min(int(nrow), n)
+    ymaps = -(-n // xmaps)
+    return xmaps, ymaps, ymaps * (H + padding) + padding, xmaps * (W + padding) + padding
+
+
+def _viz_dst(fn, out, dst, N, H, W, ref):
+    """where a tile writer writes -> (the tensor returned, pointer, elements owned from it on, EssVizDst).  out: a contiguous fp32
+    [N, 3, H, W] tensor (None: a new one); dst = (panel fp32 [3, Hg, Wg], tile0, xmaps, padding): the N tiles go to slots tile0 ..
+    tile0 + N - 1 of the panel's grid."""
+    if dst is not None:
+        if out is not None:
+            raise EssHipError(f'{fn}: out and dst exclude each other')
+        panel, tile0, xmaps, padding = dst
+        tile0, xmaps, padding = int(tile0), int(xmaps), int(padding)
+        if not torch.is_tensor(panel) or panel.dtype != torch.float32 or panel.dim() != 3 or panel.shape[0] != 3 or not panel.is_contiguous():
+            got = f'{panel.dtype}{tuple(panel.shape)}' if torch.is_tensor(panel) else type(panel).__name__
+            raise EssHipError(f'{fn}: the panel must be a contiguous fp32 [3, Hg, Wg] tensor, got {got}')
+        Hg, Wg = panel.shape[1:]
+        if tile0 < 0 or xmaps < 1 or padding < 0 or xmaps * (W + padding) + padding > Wg or \
+                ((tile0 + N - 1) // xmaps + 1) * (H + padding) + padding > Hg:
+            raise EssHipError(f'{fn}: tiles {tile0}..{tile0 + N - 1} of {H} x {W} ({xmaps} per row, padding {padding}) leave the {Hg} x {Wg} panel')
+        _on_device(fn, [('panel', panel), ref])
+        off = padding * Wg + padding
+        d = EssVizDst(Hg * Wg, Wg, (H + padding) * Wg, W + padding, tile0, xmaps)
+        return panel, c_void_p(panel.data_ptr() + 4 * off), c_size_t(panel.numel() - off), d
+    if out is not None:
+        _formed(fn, 'out', out, torch.float32, (N, 3, H, W))
+    _on_device(fn, [ref] + ([('out', out)] if out is not None else []))
+    if out is None:
+        out = torch.empty(N, 3, H, W, dtype=torch.float32, device=ref[1].device)
+    return out, c_void_p(out.data_ptr()), c_size_t(out.numel()), EssVizDst(H * W, W, 3 * H * W, 0, 0, 1)
+
+
+_colour_tables = {}
+
+
+def viz_colour_table(color_map, device):
+    """prepare_semseg's colour table: fp32 [K, 3] on `device`, divided by 255 (in fp32) if its maximum exceeds 128.  A host colour map
+    (list / numpy) is scaled on the host and uploaded once per content; a device tensor is scaled without a synchronisation."""
+    if torch.is_tensor(color_map) and color_map.is_cuda:
+        c = color_map.to(torch.float32)
+        if c.dim() != 2 or c.shape[1] != 3 or c.shape[0] == 0:
+            raise EssHipError(f'viz_colour_table: the colour map must be [K, 3], got {tuple(c.shape)}')
+        # (tensor / tensor: a division by a Python scalar is a multiplication with its reciprocal on the device, another last bit)
+        return torch.where(c.max() > 128, c / torch.full_like(c, 255), c).contiguous()
+    c = np.ascontiguousarray(np.asarray(color_map.cpu() if torch.is_tensor(color_map) else color_map, dtype=np.float32))
+    if c.ndim != 2 or c.shape[1] != 3 or c.shape[0] == 0:
+        raise EssHipError(f'viz_colour_table: the colour map must be [K, 3], got {c.shape}')
+    key = (c.tobytes(), c.shape[0], str(device))
+    t = _colour_tables.get(key)
+    if t is None:
+        if c.max() > 128:
+            c = c / np.float32(255)
+        if len(_colour_tables) >= 16:
+            _colour_tables.clear()
+        t = _colour_tables[key] = torch.from_numpy(c).to(device)
+    return t
+
+
+def viz_semseg(labels, colours, ignore_label=255, out=None, dst=None):
+    """prepare_semseg on the device (ess_viz_semseg): labels uint8 or int64 [N, H, W] + colours fp32 [K, 3] on the 0..1 scale
+    (viz_colour_table) -> fp32 [N, 3, H, W] (out, or a new tensor), or the N tiles written into their slots of a panel (dst = (panel,
+    tile0, xmaps, padding), see grid_geometry).  The ignore label shows create_checkerboard's pattern.  Deviation: so does any other
+    label outside [0, K), where the reference asserts on the host."""
+    fn = 'viz_semseg'
+    if not torch.is_tensor(labels) or labels.dtype not in (torch.uint8, torch.int64) or labels.dim() != 3 or labels.numel() == 0 \
+            or not labels.is_contiguous():
+        got = f'{labels.dtype}{tuple(labels.shape)}' if torch.is_tensor(labels) else type(labels).__name__
+        raise EssHipError(f'{fn}: labels must be a non-empty contiguous uint8 or int64 [N, H, W] tensor, got {got}')
+    if not torch.is_tensor(colours) or colours.dtype != torch.float32 or colours.dim() != 2 or colours.shape[1] != 3 or colours.shape[0] == 0 \
+            or not colours.is_contiguous():
+        got = f'{colours.dtype}{tuple(colours.shape)}' if torch.is_tensor(colours) else type(colours).__name__
+        raise EssHipError(f'{fn}: colours must be a contiguous fp32 [K, 3] tensor, got {got}')
+    if isinstance(ignore_label, bool) or int(ignore_label) != ignore_label or not -2 ** 31 <= ignore_label < 2 ** 31:
+        raise EssHipError(f'{fn}: ignore_label={ignore_label!r} is no 32-bit whole number')
+    N, H, W = labels.shape
+    ret, p_out, elems, d = _viz_dst(fn, out, dst, N, H, W, ('labels', labels))
+    _on_device(fn, [('colours', colours)])
+    _check(lib().ess_viz_semseg(c_void_p(labels.data_ptr()), 0 if labels.dtype == torch.uint8 else 1, ptr(colours), p_out, elems,
+                                ctypes.byref(d), N, colours.shape[0], H, W, int(ignore_label), stream()), 'ess_viz_semseg')
+    return ret
+
+
+def viz_events(x, mode, unit=False, out=None, dst=None):
+    """An event tensor's RGB tile (ess_viz_events): x fp32 [N, C, H, W] -> fp32 [N, 3, H, W] or panel slots (dst, as viz_semseg).
+    'histogram' (C = 2): (clamp(x0), clamp(x1), 0).  'separate_pol' (C even, >= 4): (clamp(neg), clamp(pos), 0) with pos / neg the
+    sums over a polarity's half of x[c] * ((c + 1) / half), ascending c, fp32.  'signed' (C > 3): 255 -- 1 with unit=True -- in plane 0
+    where the channel sum is > 0 and in plane 2 where it is < 0."""
+    fn = 'viz_events'
+    if mode not in VIZ_EVENT_MODES:
+        raise EssHipError(f"{fn}: mode must be 'histogram', 'separate_pol' or 'signed', got {mode!r}")
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 4 or x.numel() == 0 or not x.is_contiguous():
+        got = f'{x.dtype}{tuple(x.shape)}' if torch.is_tensor(x) else type(x).__name__
+        raise EssHipError(f'{fn}: x must be a non-empty contiguous fp32 [N, C, H, W] tensor, got {got}')
+    N, C, H, W = x.shape
+    if mode == 'histogram' and C != 2:
+        raise EssHipError(f'{fn}: the histogram tile needs C = 2 channels, got {C}')
+    if mode == 'separate_pol' and (C < 4 or C % 2):
+        raise EssHipError(f'{fn}: the separate_pol tile needs an even C >= 4 (a polarity per half), got {C}')
+    if mode == 'signed' and C <= 3:
+        raise EssHipError(f'{fn}: the signed tile needs C > 3 channels, got {C}')
+    ret, p_out, elems, d = _viz_dst(fn, out, dst, N, H, W, ('x', x))
+    _check(lib().ess_viz_events(ptr(x), p_out, elems, ctypes.byref(d), N, C, H, W, VIZ_EVENT_MODES[mode], int(bool(unit)), stream()),
+           'ess_viz_events')
+    return ret
+
+
+def viz_overlay(labels, gray, palette, alpha, out=None):
+    """Label colours over a gray frame (ess_viz_overlay): labels, gray uint8 [N, H, W]; palette uint8 [K, 3]; 0 <= alpha <= 1 ->
+    uint8 [N, H, W, 3] = (uint8) min((1 - alpha) gray + alpha palette[label] + 0.5, 255) in fp32 (two products, one sum; the palette's
+    channel order).  A label >= K shows the gray value.  The arithmetic is this package's own, not the reference's."""
+    fn = 'viz_overlay'
+    for name, t in (('labels', labels), ('gray', gray)):
+        if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 3 or t.numel() == 0 or not t.is_contiguous():
+            got = f'{t.dtype}{tuple(t.shape)}' if torch.is_tensor(t) else type(t).__name__
+            raise EssHipError(f'{fn}: {name} must be a non-empty contiguous uint8 [N, H, W] tensor, got {got}')
+    if tuple(labels.shape) != tuple(gray.shape):
+        raise EssHipError(f'{fn}: labels {tuple(labels.shape)} and the frame {tuple(gray.shape)} differ in size')
+    if not torch.is_tensor(palette) or palette.dtype != torch.uint8 or palette.dim() != 2 or palette.shape[1] != 3 \
+            or not 1 <= palette.shape[0] <= 256 or not palette.is_contiguous():
+        got = f'{palette.dtype}{tuple(palette.shape)}' if torch.is_tensor(palette) else type(palette).__name__
+        raise EssHipError(f'{fn}: palette must be a contiguous uint8 [K, 3] tensor with K <= 256, got {got}')
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise EssHipError(f'{fn}: alpha={alpha} outside [0, 1]')
+    N, H, W = labels.shape
+    if out is not None:
+        _formed(fn, 'out', out, torch.uint8, (N, H, W, 3))
+    _on_device(fn, [('labels', labels), ('gray', gray), ('palette', palette)] + ([('out', out)] if out is not None else []))
+    if out is None:
+        out = torch.empty(N, H, W, 3, dtype=torch.uint8, device=labels.device)
+    _check(lib().ess_viz_overlay(ptr(labels, torch.uint8), ptr(gray, torch.uint8), ptr(palette, torch.uint8), ptr(out, torch.uint8), N,
+                                 palette.shape[0], H, W, alpha, stream()), 'ess_viz_overlay')
     return out
 
 

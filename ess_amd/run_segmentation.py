@@ -43,19 +43,24 @@ import numpy as np
 import torch
 
 from . import hip
-from .e2vid.image_reconstructor import ImageReconstructor
+from .e2vid.image_reconstructor import ImageReconstructor, PostProcessor
 from .e2vid.run_reconstruction import _PARTS, GraphedWindowState, events_to_voxel_grid_device
 
 
 class SegmentationResult:
-    """labels uint8 [1, H, W]; colour uint8 [1, H, W, 3] or None (no palette); confidence fp32 [1, H, W] or None."""
-    __slots__ = ('labels', 'colour', 'confidence')
+    """labels uint8 [1, H, W]; colour uint8 [1, H, W, 3] or None (no palette); confidence fp32 [1, H, W] or None; with
+    StreamingSegmenter(reconstruct=True): image fp32 [1, 1, Hs, Ws], the E2VID reconstruction as StreamingReconstructor returns it;
+    (postprocess=True): frame uint8 [1, H, W], the displayable frame; (overlay=alpha): overlay uint8 [1, H, W, 3], the label colours
+    over the frame -- each None where it was not asked for."""
+    __slots__ = ('labels', 'colour', 'confidence', 'image', 'frame', 'overlay')
 
-    def __init__(self, labels, colour=None, confidence=None):
+    def __init__(self, labels, colour=None, confidence=None, image=None, frame=None, overlay=None):
         self.labels, self.colour, self.confidence = labels, colour, confidence
+        self.image, self.frame, self.overlay = image, frame, overlay
 
     def clone(self):
-        return SegmentationResult(*(None if t is None else t.clone() for t in (self.labels, self.colour, self.confidence)))
+        return SegmentationResult(*(None if t is None else t.clone() for t in (self.labels, self.colour, self.confidence, self.image,
+                                                                                self.frame, self.overlay)))
 
 
 def _models_from_checkpoints(e2vid_path, ess_checkpoint_path, settings_or_kwargs):
@@ -93,10 +98,30 @@ class StreamingSegmenter(GraphedWindowState):
     update_from_events builds the grid with hip.voxel_grid_temporal in front of the window (fp32 atomics: the last bits follow
     arrival order).  The order-independent event ingest inside the captured round (event_capacity=) is MultiStreamSegmenter's: this
     driver's first window runs eagerly outside the capture; MultiStreamSegmenter(n_streams=1, event_capacity=N) is the
-    single-stream form, at +0.02 ms per window."""
+    single-stream form, at +0.02 ms per window.
+
+    The display (all off by default; the results then are what they were without these keywords):
+    reconstruct=True   the window's recurrent step is the FULL one (need_image=True: residual blocks, E2VID decoders, prediction layer) in
+                       place of the encoder-only one, on the same encoder pass; the result carries `image`.  Labels, colours and
+                       confidence stay bit-identical to the plain segmenter's: the latents of the two steps are.
+    postprocess=True   (needs reconstruct) `frame`: PostProcessor.process_u8 of the image, cropped to the sensor -- StreamingReconstructor(
+                       postprocess=True)'s frame, bit for bit; part of the captured window; one auto-HDR history in device memory shared
+                       by the eager first window and the replays, untouched by the capture's warm-up run, emptied by reset().
+    overlay=alpha      (needs postprocess and a palette; labels at the frame's size) `overlay`: hip.viz_overlay(labels, frame, palette,
+                       alpha), uint8 [1, H, W, 3]."""
 
     def __init__(self, encoder, decoder, height, width, options, device=None, graph=False, copy=True, palette=None,
-                 want_confidence=False, out_hw=None):
+                 want_confidence=False, out_hw=None, reconstruct=False, postprocess=False, overlay=None):
+        if postprocess and not reconstruct:
+            raise hip.EssHipError('StreamingSegmenter: postprocess=True needs reconstruct=True (the frame is made from the image)')
+        if overlay is not None:
+            if not postprocess or palette is None:
+                raise hip.EssHipError('StreamingSegmenter: overlay= needs postprocess=True (the frame) and a palette (the colours)')
+            if not 0.0 <= float(overlay) <= 1.0:
+                raise hip.EssHipError(f'StreamingSegmenter: overlay={overlay} outside [0, 1]')
+            if out_hw is not None and (int(out_hw[0]), int(out_hw[1])) != (height, width):
+                raise hip.EssHipError(f'StreamingSegmenter: overlay= needs labels at the frame\'s size {(height, width)}, out_hw is '
+                                      f'{tuple(out_hw)}')
         self.copy_outputs = bool(copy)
         self.device = device if device is not None else torch.device('cuda:0')
         self.model = encoder.to(self.device).eval()
@@ -112,6 +137,9 @@ class StreamingSegmenter(GraphedWindowState):
         self.use_graph = graph
         self.n_windows = 0
         self.last_latent = None  # (eager windows: the latents handed to decoder.predict, for inspection)
+        self.reconstruct = bool(reconstruct)
+        self.post = PostProcessor(self.device, options, n=1, crop=crop) if postprocess else None
+        self.overlay_alpha = None if overlay is None else float(overlay)
 
     @classmethod
     def from_checkpoints(cls, e2vid_path, ess_checkpoint_path, settings_or_kwargs, **kw):
@@ -126,23 +154,37 @@ class StreamingSegmenter(GraphedWindowState):
 
     def reset(self):
         self.rec.last_states_for_each_channel = {'grayscale': None}
+        if self.post is not None:
+            self.post.reset()
         self.n_windows = 0  # (the captured graph stays valid: it reads the static state buffers, which the next first step rewrites)
 
     def update_from_events(self, events):
         return self.update(events_to_voxel_grid_device(events, self.num_bins, self.width, self.height, self.device))
 
+    def _capture(self, example):
+        """the warm-up window in front of the recording must not leave an entry in the auto-HDR history either"""
+        saved = [t.clone() for t in self.post.state_tensors()] if self.post is not None else []
+        super()._capture(example)
+        for t, sv in zip(self.post.state_tensors() if saved else [], saved):
+            t.copy_(sv)
+
     def _window(self, ev):
-        """one window's device work -> ((labels, colour, confidence), new states)"""
+        """one window's device work -> ((labels, colour, confidence, image, frame, overlay), new states)"""
         rec = self.rec
         with torch.no_grad():
             ev = rec.crop.pad(rec.event_preprocessor(ev))
             if not ev.is_contiguous():
                 ev = ev.contiguous()
             # encoder-only step whose latents ARE consumed; final_lean: the lean state form where the configuration has one
-            _, states, latent = rec._step(ev, False, False, final_lean=not hip.mixed())
+            # (reconstruct: the full step on the same encoder pass -- its image is the reconstruction, its latents are the same bits)
+            img, states, latent = rec._step(ev, self.reconstruct, False, final_lean=not hip.mixed())
             self.last_latent = latent
             out = self.decoder.predict(latent, out_hw=self.out_hw, window=self.window, palette=self.palette,
                                        want_confidence=self.want_confidence)
+            if self.reconstruct:
+                frame = None if self.post is None else self.post.process_u8(img)
+                over = None if self.overlay_alpha is None else hip.viz_overlay(out[0], frame, self.palette, self.overlay_alpha)
+                out = tuple(out) + (img, frame, over)
         return out, states
 
     def update(self, event_tensor):

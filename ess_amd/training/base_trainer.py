@@ -1,7 +1,8 @@
 """
 Trainer base: construction order, epoch loop, validation cadence, checkpoint cadence, LR schedule
-(reference: training/base_trainer.py:21-66,361-453).  Dataset factories and visualisation helpers of the
-reference (:72-359,455-609) are out of scope; loaders come from `createDataLoaders`,
+(reference: training/base_trainer.py:21-66,361-453), and the validation panels (:455-458, :551-554; opt-in through
+`vis_panels`, built on the device by utils/viz_utils.panel).  Dataset factories and the other visualisation helpers of the
+reference (:72-359,488-609) are out of scope; loaders come from `createDataLoaders`,
 which provides the seeded synthetic loaders when `settings.synthetic` is set and otherwise expects a subclass
 / caller to assign `train_loader` / `val_loader_sensor_b`.
 """
@@ -41,6 +42,9 @@ class BaseTrainer(object):
         torch.cuda.set_device(self.device)
         self.do_val_training_epoch = True
         self.grad_reducer = D.GradAllReducer()
+        # validation panels (events | reconstruction | prediction | ... | ground truth as one image per chosen batch): opt-in
+        self.vis_panels = bool(getattr(settings, 'vis_panels', False))
+        self.last_val_panels = {}  # tag -> the last panel under it, fp32 [3, Hg, Wg] on the device
 
         self.init_fn()  # models are built ON the device, then the optimisers flatten their parameters
         self.createDataLoaders()
@@ -261,7 +265,43 @@ class BaseTrainer(object):
         pass
 
     def visualize_epoch(self):
-        return False  # tensorboard image dumps (reference :488-490 and the vis* helpers) are out of scope
+        return False  # the train-step panels (reference :488-490, visTaskStep / visCycleStep) stay out: the captured step keeps no logits
+
+    # ------------------------------------------------------------------ validation panels (reference :455-458, :551-554)
+    def vis_reconstr_index(self, i_batch, data_loader):
+        """the panel index of validation batch i_batch, or -1: with vis_panels on, the reference's three panels per loader
+        (nr_reconstr_vis = 3, one every max(len // 3, 1) batches); off (the default), none"""
+        if not self.vis_panels:
+            return -1
+        vis_step_size = max(len(data_loader) // 3, 1)
+        return i_batch // vis_step_size if (i_batch % vis_step_size) == vis_step_size - 1 else -1
+
+    def img_summaries(self, tag, img, step=None):
+        """a validation panel fp32 [3, Hg, Wg] on the device: kept in last_val_panels[tag] (for a caller without tensorboard),
+        handed to the summary writer under the reference's tag"""
+        s = self.settings
+        tag = tag.replace('sensor_a', str(getattr(s, 'sensor_a_name', 'sensor_a'))).replace('sensor_b', str(getattr(s, 'sensor_b_name', 'sensor_b')))
+        self.last_val_panels[tag] = img
+        if not isinstance(self.summary_writer, _NullWriter):
+            self.summary_writer.add_image(tag, img, step)  # (the writer's own .cpu(): the one host read of a panel)
+
+    def _val_panel(self, rows, sensor, vis_reconstr_idx):
+        """rows of (kind, tensor) -> viz_utils.panel (nrow = 4, the reference's) -> img_summaries under the reference's tag"""
+        from ..utils import viz_utils
+        s = self.settings
+        grid = viz_utils.panel(rows, nrow=4, color_map=s.semseg_color_map, ignore_label=s.semseg_ignore_label)
+        self.img_summaries('val_' + sensor + '/reconst_input_' + sensor + '_' + str(vis_reconstr_idx), grid, self.epoch_count)
+
+    def _event_row(self, data):
+        """the event row of a sensor-b panel: createRGBImage(data, separate_pol=separate_pol_b).clamp(0, 1)"""
+        return ('events' if getattr(self.settings, 'separate_pol_b', False) else 'events_signed', data)
+
+    def _gt_row(self, labels, size):
+        """ground-truth labels at the prediction's size (the reference resizes them with the nearest rule, :571-572)"""
+        from .. import hip
+        if tuple(labels.shape[-2:]) != tuple(size):
+            labels = hip.resize_nearest(labels.float().unsqueeze(1).contiguous(), tuple(size)).squeeze(1).long()
+        return ('semseg', labels)
 
     def train_summaries(self, losses):
         """Running means over 50 steps written as scalars (reference :525-541), without forcing a device sync

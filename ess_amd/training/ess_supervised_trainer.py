@@ -109,7 +109,7 @@ class ESSSupervisedModel(base_trainer.BaseTrainer):
     def validationEpoch(self, data_loader, sensor_name):
         cumulative_losses, n = {}, 0
         for i_batch, batch in enumerate(data_loader):
-            losses, _ = self.val_step([t.to(self.device) for t in batch], sensor_name, i_batch, -1)
+            losses, _ = self.val_step([t.to(self.device) for t in batch], sensor_name, i_batch, self.vis_reconstr_index(i_batch, data_loader))
             for k, v in losses.items():
                 cumulative_losses[k] = cumulative_losses[k] + v if k in cumulative_losses else v
             n += 1
@@ -125,26 +125,49 @@ class ESSSupervisedModel(base_trainer.BaseTrainer):
         self.last_val_metrics, self.last_val_summary = m, summary
 
     def val_step(self, input_batch, sensor, i_batch=0, vis_reconstr_idx=-1):
-        """-> (losses, None) as the reference (:235-277); events only (this trainer has no front_sensor_a)."""
+        """-> (losses, None) as the reference (:235-277); events only (this trainer has no front_sensor_a).  vis_reconstr_idx != -1: the
+        batch's validation panel goes to img_summaries (visualizeSensorB); only such a batch runs the image half of the last step (its
+        latents are the same bits either way)."""
         if sensor != 'sensor_b':
             raise KeyError('front_' + sensor)  # the reference fails the same way on models_dict (:255)
         s = self.settings
         data = input_batch[0]
+        paired_data = None
         if getattr(s, 'require_paired_data_val_b', False):
+            paired_data = input_batch[1]
             labels = input_batch[3] if s.dataset_name_b == 'DDD17_events' else input_batch[2]
         else:
             labels = input_batch[1]
         losses = {}
+        vis = vis_reconstr_idx != -1
         with torch.no_grad():
             self.reconstructor.last_states_for_each_channel = {'grayscale': None}
             T, C = s.nr_events_data_b, s.input_channels_b
-            _, _, latent = self.reconstructor.update_reconstruction_sequence(data, T, need_image=False, final_lean=True)
-            self.valTaskStep(latent, labels, losses, sensor)
+            img_fake, _, latent = self.reconstructor.update_reconstruction_sequence(data, T, need_image=vis, final_lean=True)
+            logits = self.valTaskStep(latent, labels, losses, sensor)
+            if vis:
+                self.visualizeSensorB(data[:, -C:], logits, labels, img_fake, paired_data, vis_reconstr_idx, sensor)
         return losses, None
 
     def valTaskStep(self, content_first_sensor, labels, losses, sensor):
-        """decoder -> nearest resize to img_size_b -> argmax + confusion, task loss (unweighted, reference :279-292)."""
-        pred = self.models_dict['back_end'](content_first_sensor)[1]
-        pred = hip.resize_nearest(pred, tuple(self.settings.img_size_b))
+        """decoder -> nearest resize to img_size_b -> argmax + confusion, task loss (unweighted, reference :279-292) -> the decoder's
+        logits at the model's size (for the validation panel)"""
+        logits = self.models_dict['back_end'](content_first_sensor)[1]
+        pred = hip.resize_nearest(logits, tuple(self.settings.img_size_b))
         self.metrics_semseg_b.update_batch_logits(pred, labels)
         losses['semseg_' + sensor + '_loss'] = self.task_loss(pred, target=labels)
+        return logits
+
+    def visualizeSensorA(self, data, labels, logits, vis_reconstr_idx, sensor):
+        """reference :294-310: data | prediction | ground truth (this trainer validates events only: for a caller with its own images)"""
+        self._val_panel([('gray' if data.shape[1] == 1 else 'rgb', data), ('semseg', logits.argmax(dim=1)), ('semseg', labels)], sensor,
+                        vis_reconstr_idx)
+
+    def visualizeSensorB(self, data, logits, labels, img_fake, paired_data, vis_reconstr_idx, sensor):
+        """reference :312-333: events (the last slice) | prediction | ground truth (resized to the prediction's size) | img_fake | paired
+        data if given (the reference fails without it).  The decoder is not run a second time: these are valTaskStep's logits."""
+        pred_lbl = logits.argmax(dim=1)
+        rows = [self._event_row(data), ('semseg', pred_lbl), self._gt_row(labels, pred_lbl.shape[-2:]), ('gray', img_fake)]
+        if paired_data is not None:
+            rows.append(('gray' if paired_data.shape[1] == 1 else 'rgb', paired_data))
+        self._val_panel(rows, sensor, vis_reconstr_idx)

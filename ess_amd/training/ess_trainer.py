@@ -365,7 +365,7 @@ class ESSModel(base_trainer.BaseTrainer):
         """Loss sums stay on the device; the metric summaries are the only host reads of the epoch."""
         cumulative_losses, n = {}, 0
         for i_batch, batch in enumerate(data_loader):
-            losses, _ = self.val_step([t.to(self.device) for t in batch], sensor_name, i_batch, -1)
+            losses, _ = self.val_step([t.to(self.device) for t in batch], sensor_name, i_batch, self.vis_reconstr_index(i_batch, data_loader))
             for k, v in losses.items():
                 cumulative_losses[k] = cumulative_losses[k] + v if k in cumulative_losses else v
             n += 1
@@ -390,28 +390,54 @@ class ESSModel(base_trainer.BaseTrainer):
 
     def val_step(self, input_batch, sensor, i_batch=0, vis_reconstr_idx=-1):
         """-> (losses, None) as the reference (:424-474); runs under no_grad with the modules in eval mode
-        (validationEpochs).  The tensorboard image dumps behind vis_reconstr_idx are out of scope."""
+        (validationEpochs).  vis_reconstr_idx != -1: the batch's validation panel goes to img_summaries (visualizeSensorA / B)."""
         s = self.settings
         data = input_batch[0]
+        paired_data = None
         if sensor == 'sensor_a':
-            labels = input_batch[2] if getattr(s, 'require_paired_data_val_a', False) else input_batch[1]
-        elif getattr(s, 'require_paired_data_val_b', False):
-            labels = input_batch[3] if s.dataset_name_b == 'DDD17_events' else input_batch[2]
+            paired = getattr(s, 'require_paired_data_val_a', False)
+            labels = input_batch[2] if paired else input_batch[1]
         else:
-            labels = input_batch[1]
+            paired = getattr(s, 'require_paired_data_val_b', False)
+            if paired:
+                labels = input_batch[3] if s.dataset_name_b == 'DDD17_events' else input_batch[2]
+            else:
+                labels = input_batch[1]
+        if paired:
+            paired_data = input_batch[1]
         losses = {}
         with torch.no_grad():
             if sensor == 'sensor_a':
                 content = self.models_dict['front_sensor_a'](data)
-                self.valTaskStep(content, labels, losses, sensor)
+                preds = self.valTaskStep(content, labels, losses, sensor)
+                if vis_reconstr_idx != -1:
+                    self.visualizeSensorA(data, labels, preds, vis_reconstr_idx, sensor)
                 return losses, None
             rec = self.reconstructor_valid
             rec.last_states_for_each_channel = {'grayscale': None}
             T, C = s.nr_events_data_b, s.input_channels_b
             img_fake, _, content = rec.update_reconstruction_sequence(data, T, need_image=True, final_lean=True)  # (only the last slice's image and latents are consumed)
             preds = self.valTaskStep(content, labels, losses, sensor)
-            self.valCycleStep(content, img_fake, labels, losses, sensor, 'sensor_a', preds)
+            preds_cycle = self.valCycleStep(content, img_fake, labels, losses, sensor, 'sensor_a', preds)
+            if vis_reconstr_idx != -1:
+                self.visualizeSensorB(data[:, -C:], preds, preds_cycle, labels, img_fake, paired_data, vis_reconstr_idx, sensor)
         return losses, None
+
+    def visualizeSensorA(self, data, labels, preds_first_sensor, vis_reconstr_idx, sensor):
+        """reference :546-561: data | prediction | ground truth.  (argmax over the logits through torch: the cold path.)"""
+        pred_lbl = preds_first_sensor[1].argmax(dim=1)
+        self._val_panel([('gray' if data.shape[1] == 1 else 'rgb', data), ('semseg', pred_lbl), ('semseg', labels)], sensor, vis_reconstr_idx)
+
+    def visualizeSensorB(self, data, preds_first_sensor, preds_second_sensor, labels, img_fake, paired_data, vis_reconstr_idx, sensor):
+        """reference :563-603: events (the last slice) | img_fake | prediction | cycle prediction | ground truth when semseg_label_val_b
+        (resized to the prediction's size) | paired data if given.  The predictions are those of the model's size, not of img_size_b."""
+        pred_lbl = preds_first_sensor[1].argmax(dim=1)
+        rows = [self._event_row(data), ('gray', img_fake), ('semseg', pred_lbl), ('semseg', preds_second_sensor[1].argmax(dim=1))]
+        if self.settings.semseg_label_val_b:
+            rows.append(self._gt_row(labels, pred_lbl.shape[-2:]))
+        if paired_data is not None:
+            rows.append(('gray' if paired_data.shape[1] == 1 else 'rgb', paired_data))
+        self._val_panel(rows, sensor, vis_reconstr_idx)
 
     def _val_label_scores(self, pred, labels, metrics):
         """nearest resize to img_size_b + argmax + confusion + task loss (reference :482-492, :523-530)."""

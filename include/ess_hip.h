@@ -789,6 +789,49 @@ enum { ESS_PREVIEW_RED_BLUE = 0, ESS_PREVIEW_GRAYSCALE = 1 };
 int ess_event_preview(const float* grids, uint8_t* out, int32_t N, int32_t C, int32_t H, int32_t W, int32_t num_bins_to_show,
                       int32_t mode, ess_stream_t stream);
 
+/* ---- Segmentation display (utils/viz_utils.py:19-73 createRGBImage / visualizeHistogram / visualizeVoxelGrid, :105-145
+ * create_checkerboard / prepare_semseg; the overlay is this library's own) -- PURELY ADDITIVE to ABI 110 (ess_version() is unchanged; no
+ * existing entry point changes).  All three are capture-safe: explicit stream, no allocation, copy or synchronisation, no host state;
+ * every argument is checked before the launch.  fp32 arithmetic, each operation rounded once, never fused, sums in ascending channel
+ * order from 0.f: a numpy float32 restatement defines the bits.
+ *
+ * The two TILE WRITERS write sample n as an RGB tile of three planes: element (c, y, x) of sample n goes to
+ *   out[ ((tile0 + n) / tiles_per_row) * tile_stride_y + ((tile0 + n) % tiles_per_row) * tile_stride_x
+ *        + c * plane_stride + y * row_stride + x ]                                              (all strides in ELEMENTS)
+ * A contiguous [N][3][H][W] tensor: plane_stride = H * W, row_stride = W, tiles_per_row = 1, tile_stride_y = 3 * H * W.  A make_grid
+ * panel [3][Hg][Wg] with `padding` and xmaps tiles per grid row: out = panel + padding * Wg + padding, plane_stride = Hg * Wg,
+ * row_stride = Wg, tiles_per_row = xmaps, tile_stride_y = (H + padding) * Wg, tile_stride_x = W + padding.
+ * out_elems: the elements the caller owns from `out` on; a call whose tiles would reach beyond is refused.  16-byte stores are used
+ * only where `out`, every stride and W are multiples of 4 elements; single elements otherwise (a panel's row stride is odd in general). */
+typedef struct EssVizDst {
+  int64_t plane_stride, row_stride, tile_stride_y, tile_stride_x;
+  int32_t tile0, tiles_per_row;
+} EssVizDst;
+
+/* prepare_semseg: labels uint8 or int64 [N][H][W]; colours fp32 [K][3] ALREADY on the 0..1 scale (the caller applies the reference's
+ * "divide by 255 if the maximum exceeds 128").  A pixel whose label is ignore_label shows create_checkerboard's value: with
+ * cell = max(min(H, W) / 32, 1), 0.75f where (y / cell + x / cell) is even, else 0.25f, in all three planes.  DEVIATION: a label
+ * outside [0, K) that is not ignore_label shows the checkerboard as well (the reference asserts on the host).                    */
+enum { ESS_VIZ_LABELS_U8 = 0, ESS_VIZ_LABELS_I64 = 1 };
+int ess_viz_semseg(const void* labels, int32_t label_type, const float* colours, float* out, size_t out_elems, const EssVizDst* dst,
+                   int32_t N, int32_t K, int32_t H, int32_t W, int32_t ignore_label, ess_stream_t stream);
+
+/* x fp32 [N][C][H][W] -> RGB tiles.  clamp(v) = v < 0 ? 0 : v > 1 ? 1 : v (a NaN stays).
+ * ESS_VIZ_HISTOGRAM (C == 2): (clamp(x0), clamp(x1), 0).
+ * ESS_VIZ_SEPARATE_POL (C even, >= 4; half = C / 2): pos = sum_{c < half} x[c] * ((float)(c + 1) / (float)half),
+ *   neg = sum_{c < half} x[half + c] * (same scale); tile = (clamp(neg), clamp(pos), 0).
+ * ESS_VIZ_SIGNED (C > 3; the reference's separate_pol = False branch): s = sum_c x[c]; plane 0 = 255 where s > 0, plane 2 = 255 where
+ *   s < 0, else 0; unit != 0 writes 1 in place of 255 (the .clamp(0, 1) the trainers apply to the event row).                  */
+enum { ESS_VIZ_HISTOGRAM = 0, ESS_VIZ_SEPARATE_POL = 1, ESS_VIZ_SIGNED = 2 };
+int ess_viz_events(const float* x, float* out, size_t out_elems, const EssVizDst* dst, int32_t N, int32_t C, int32_t H, int32_t W,
+                   int32_t mode, int32_t unit, ess_stream_t stream);
+
+/* Label colours over a gray frame: labels, gray uint8 [N][H][W]; palette uint8 [K][3], K <= 256; 0 <= alpha <= 1;
+ * out uint8 [N][H][W][3] in the palette's channel order (as ess_seg_head's colour): v = (1.0f - alpha) * g + alpha * palette[label][c]
+ * (two products, one sum), out = (uint8)min(v + 0.5f, 255.f).  A label >= K shows g in all three channels.                      */
+int ess_viz_overlay(const uint8_t* labels, const uint8_t* gray, const uint8_t* palette, uint8_t* out, int32_t N, int32_t K, int32_t H,
+                    int32_t W, float alpha, ess_stream_t stream);
+
 /* confusion-matrix accumulation from GIVEN predictions (evaluation/metrics.py:4-24, semseg_compute_confusion): pred_lbl,
  * labels int64 [total]; conf int64 [K][K] accumulated (conf[label][pred]) over labels != ignore_index.          */
 int ess_label_confusion(const int64_t* pred_lbl, const int64_t* labels, int64_t* conf, int64_t total, int32_t K,
