@@ -8,7 +8,9 @@
 // event representations (ess_event_*_rep): SeparateFlavour (2 * bins planes, the polarities kept apart) and HistogramFlavour (two
 // planes of per-pixel counts, the time column not read); the finish kernels take a plane count, not a meaning.  Masked<Flavour>
 // puts a per-sensor hot-pixel bit mask in front of any of the four (ess_event_ingest_masked: an event on a masked raw pixel never
-// reaches the flavour); hot_pixel_mask_kernel turns the histogram's counts into such masks (ess_event_hot_pixel_mask).
+// reaches the flavour); hot_pixel_mask_kernel turns the histogram's counts into such masks (ess_event_hot_pixel_mask).  A third
+// source, the device event store (ess_event_scatter_store: windows at absolute 64-bit indices of one flat set of columns), hands
+// the same four flavours its events through event_scatter_store_kernel, the ring loader's walk without a row or a wrap.
 //
 // Behind the scatter, one kernel per job: event_finish_kernel<VEC, TAP> turns sums into a grid and zeroes them where each sum has
 // one reader -- the plain ingest (TAP false) and the loader finish at the identity geometry (TAP true); grid_map_kernel<VEC,
@@ -434,6 +436,79 @@ int launch_scatter(const char* status, const void* t, const void* x, const void*
                      dim3(INGEST_THREADS), 0, st, (const long long*)t, (const unsigned short*)x, (const unsigned short*)y,
                      (const unsigned char*)p, rows, starts, counts, formats, ring, (int)n_rows, (int)bins, (int)height, (int)width,
                      (long long*)acc, extra...);
+  return ess_launch_status(status);
+}
+
+// ---- the store source (ess_event_scatter_store): the same four columns as ONE flat set of `capacity` events, recordings laid one
+// behind the other (a training split uploaded once).  A slot's window is counts[s] events from ABSOLUTE event index starts[s], an
+// int64 device word; nothing wraps and there is no row.  The walk is the ring source's -- aligned groups of COLUMN_GROUP from
+// starts - starts % COLUMN_GROUP on, the head of the first and the tail of the last masked, loads of 2 x 16 B, 8 B, 8 B, 4 B -- with
+// every index, group number and offset 64-bit: total and capacity reach 2^40 events.  capacity is a multiple of COLUMN_STRIDE_ALIGN,
+// so the last group of a window that ends on event total - 1 lies inside the columns.  A start < 0, start + count > total,
+// count > window_capacity or an unknown format: as count 0.  A kernel of its own, not a third value of RING: the column and the ring
+// instantiations of the loader above stay what they are.
+constexpr int64_t STORE_MAX_CAPACITY = (int64_t)1 << 40;
+
+template <class Flavour, class... Extra>
+__global__ __launch_bounds__(INGEST_THREADS) void event_scatter_store_kernel(const long long* __restrict__ t, const unsigned short* __restrict__ x,
+                                                                             const unsigned short* __restrict__ y,
+                                                                             const unsigned char* __restrict__ p,
+                                                                             const long long* __restrict__ starts,
+                                                                             const int32_t* __restrict__ counts,
+                                                                             const int32_t* __restrict__ formats, int64_t total,
+                                                                             int64_t window_capacity, int nb, int H, int W,
+                                                                             long long* __restrict__ acc, const Extra... extra) {
+#pragma clang fp contract(off)
+  const int s = blockIdx.y;
+  const int cnt = counts[s];
+  const int fmt = formats[s];
+  const int64_t start = starts[s];
+  if (cnt <= 0) return;  // an empty window: nothing is read for this slot
+  if ((fmt & ~(EVCOL_T_I64 | EVCOL_XY_U16)) != 0) return;  // an unknown format: as count 0
+  const int64_t n = cnt;
+  if (start < 0 || n > window_capacity || start > total - n) return;  // a window outside the store or above the capacity: as count 0
+  Flavour f;
+  if (!f.open(s, extra...)) return;
+  const bool t_i64 = (fmt & EVCOL_T_I64) != 0, xy_u16 = (fmt & EVCOL_XY_U16) != 0;
+  if constexpr (Flavour::READS_TIME) f.window(t[start], t[start + n - 1], t_i64, nb);
+  const size_t plane = (size_t)H * W;
+  long long* __restrict__ g = acc + (size_t)s * nb * plane;
+  const i64x2* __restrict__ t2 = (const i64x2*)t;         // two events
+  const uint2* __restrict__ x4 = (const uint2*)x;         // COLUMN_GROUP events
+  const uint2* __restrict__ y4 = (const uint2*)y;
+  const unsigned* __restrict__ p4 = (const unsigned*)p;
+  const int64_t head = start % COLUMN_GROUP, group0 = start / COLUMN_GROUP;
+  const int64_t groups = (head + n + COLUMN_GROUP - 1) / COLUMN_GROUP;  // (the last one may be partial; it ends below capacity)
+  for (int64_t q = (int64_t)blockIdx.x * INGEST_THREADS + threadIdx.x; q < groups; q += (int64_t)gridDim.x * INGEST_THREADS) {
+    const int64_t at = group0 + q;
+    i64x2 ta = {0, 0}, tb = {0, 0};
+    if constexpr (Flavour::READS_TIME) {
+      ta = t2[2 * at];
+      tb = t2[2 * at + 1];
+    }
+    const uint2 xv = x4[at], yv = y4[at];
+    const unsigned pv = p4[at];
+    const long long tw[COLUMN_GROUP] = {ta[0], ta[1], tb[0], tb[1]};
+    const unsigned xh[COLUMN_GROUP] = {xv.x & 0xffffu, xv.x >> 16, xv.y & 0xffffu, xv.y >> 16};
+    const unsigned yh[COLUMN_GROUP] = {yv.x & 0xffffu, yv.x >> 16, yv.y & 0xffffu, yv.y >> 16};
+#pragma unroll
+    for (int j = 0; j < COLUMN_GROUP; ++j) {
+      const int64_t k = q * COLUMN_GROUP + j - head;  // the event's number inside the window
+      if (k < 0 || k >= n) continue;                  // (the head and the tail: loaded, inside the columns, never summed)
+      f.add(tw[j], xh[j], yh[j], (int)((pv >> (8 * j)) & 0xffu), t_i64, xy_u16, nb, H, W, plane, g);
+    }
+  }
+}
+
+// the grid follows window_capacity, not the store's size
+template <class Flavour, class... Extra>
+int launch_scatter_store(const char* status, const void* t, const void* x, const void* y, const void* p, const int64_t* starts,
+                         const int32_t* counts, const int32_t* formats, int64_t total, int64_t window_capacity, int32_t n_slots,
+                         int32_t channels, int32_t height, int32_t width, void* acc, hipStream_t st, const Extra... extra) {
+  hipLaunchKernelGGL((event_scatter_store_kernel<Flavour, Extra...>), dim3(scatter_blocks(window_capacity), (unsigned)n_slots),
+                     dim3(INGEST_THREADS), 0, st, (const long long*)t, (const unsigned short*)x, (const unsigned short*)y,
+                     (const unsigned char*)p, (const long long*)starts, counts, formats, total, window_capacity, (int)channels,
+                     (int)height, (int)width, (long long*)acc, extra...);
   return ess_launch_status(status);
 }
 
@@ -1215,6 +1290,56 @@ extern "C" int ess_event_ingest_masked(const void* t, const void* x, const void*
   if (rc || !out) return rc;
   launch_finish<false>(counts, n_slots, (int64_t)channels * height * width, acc, nullptr, out, st);
   return ess_launch_status("event_ingest_masked(finish)");
+}
+
+// ---- the store source: ONE entry point for the four flavours, scatter only (acc keeps the sums for ess_event_grid_finish*)
+namespace {
+constexpr int STORE_SIGNED = 0, STORE_SEPARATE = 1, STORE_HISTOGRAM = 2, STORE_TRILINEAR = 3;  // (ESS_EVENT_STORE_* of include/ess_hip.h)
+static_assert(STORE_SIGNED == EVENT_REP_SIGNED && STORE_SEPARATE == EVENT_REP_SEPARATE && STORE_HISTOGRAM == EVENT_REP_HISTOGRAM,
+              "the first three flavour words are the representation words");
+}  // namespace
+
+extern "C" int ess_event_scatter_store(const void* t, const void* x, const void* y, const void* p, const int64_t* starts,
+                                       const int32_t* counts, const int32_t* formats, int64_t capacity, int64_t total,
+                                       int64_t window_capacity, int32_t n_slots, int32_t channels, int32_t height, int32_t width,
+                                       void* acc, size_t acc_bytes, int32_t flavour, const float* maps, const int32_t* map_of,
+                                       int32_t n_maps, int32_t map_height, int32_t map_width, ess_stream_t stream) {
+  const char* what = "event_scatter_store";
+  ESS_CHECK_ARG(flavour >= STORE_SIGNED && flavour <= STORE_TRILINEAR,
+                "%s: flavour=%d (0 signed, 1 separate polarity, 2 histogram, 3 trilinear)", what, (int)flavour);
+  int rc = check_representation(what, flavour == STORE_TRILINEAR ? EVENT_REP_SIGNED : flavour, channels);
+  if (rc) return rc;
+  ESS_CHECK_ARG(t && x && y && p && starts && counts && formats && acc, "%s: null t, x, y, p, starts, counts, formats or acc", what);
+  ESS_CHECK_ARG(n_slots >= 1 && n_slots <= 65535, "%s: n_slots=%d (1..65535)", what, (int)n_slots);
+  ESS_CHECK_ARG(height > 0 && width > 0, "%s: height=%d width=%d must be positive", what, (int)height, (int)width);
+  ESS_CHECK_ARG(window_capacity >= 1 && window_capacity <= INGEST_MAX_CAPACITY,
+                "%s: window_capacity=%lld events per window (1..%lld: the int64 sums hold 2^22 contributions of magnitude 1 at scale 2^40)",
+                what, (long long)window_capacity, (long long)INGEST_MAX_CAPACITY);
+  ESS_CHECK_ARG(capacity >= COLUMN_STRIDE_ALIGN && capacity <= STORE_MAX_CAPACITY && capacity % COLUMN_STRIDE_ALIGN == 0,
+                "%s: capacity=%lld events must be a multiple of %d in [%d, 2^40] (a window's last group of 4 events stays inside the columns)",
+                what, (long long)capacity, COLUMN_STRIDE_ALIGN, COLUMN_STRIDE_ALIGN);
+  ESS_CHECK_ARG(total >= 0 && total <= capacity, "%s: total=%lld events (0..capacity=%lld)", what, (long long)total, (long long)capacity);
+  const size_t need = ess_event_ingest_workspace(n_slots, channels, height, width);
+  ESS_CHECK_ARG(acc_bytes >= need, "%s: acc has %zu bytes, %zu are needed", what, acc_bytes, need);
+  ESS_CHECK_ARG((((uintptr_t)t | (uintptr_t)x | (uintptr_t)y | (uintptr_t)p | (uintptr_t)acc) & 15) == 0 && (((uintptr_t)starts) & 7) == 0 &&
+                    ((((uintptr_t)counts) | ((uintptr_t)formats)) & 3) == 0,
+                "%s: t, x, y, p and acc must be 16-byte, starts 8-byte, counts and formats 4-byte aligned", what);
+  hipStream_t st = (hipStream_t)stream;
+  if (flavour == STORE_TRILINEAR) {
+    Rectify rect;
+    rc = check_rectify(what, maps, map_of, n_maps, map_height, map_width, rect);
+    if (rc) return rc;
+    return launch_scatter_store<TrilinearFlavour>(what, t, x, y, p, starts, counts, formats, total, window_capacity, n_slots, channels, height,
+                                                  width, acc, st, rect);
+  }
+  if (flavour == STORE_SEPARATE)
+    return launch_scatter_store<SeparateFlavour>(what, t, x, y, p, starts, counts, formats, total, window_capacity, n_slots, channels, height,
+                                                 width, acc, st);
+  if (flavour == STORE_HISTOGRAM)
+    return launch_scatter_store<HistogramFlavour>(what, t, x, y, p, starts, counts, formats, total, window_capacity, n_slots, channels, height,
+                                                  width, acc, st);
+  return launch_scatter_store<TemporalFlavour>(what, t, x, y, p, starts, counts, formats, total, window_capacity, n_slots, channels, height,
+                                               width, acc, st);
 }
 
 extern "C" int ess_event_hot_pixel_mask(const int64_t* sums, int32_t n, int32_t height, int32_t width, const int64_t* thresholds,

@@ -19,6 +19,7 @@ import torch
 
 from .. import hip
 from .data_util import EventColumns, stage_event_columns
+from .event_store import EventStore, StoreSample, duration_bounds, time_bound
 
 VOXEL_FLAVOURS = ('temporal', 'trilinear')
 _NORMS = {None: hip.GRID_NORM_NONE, 'unbiased': hip.GRID_NORM_UNBIASED, 'population': hip.GRID_NORM_POPULATION}
@@ -134,18 +135,34 @@ class EventBatchBuilder:
     Static device memory (allocated at the first batch): B T int64 sum grids [C, Hs, Ws] + two fp32 output sets [B T, C, h, w]
     + 13 bytes per event of capacity -- DSEC, B = 8, T = 20, C = bins = 5: 1.97 GB + 2 x 0.92 GB; DDD17, B = 8, T = 20, C = bins = 5:
     0.58 GB + 2 x 0.08 GB; 'separate_pol' doubles both terms (C = 10), 'histogram' takes 2 / 5 of them -- and the staging sets in
-    pinned host memory: 2 x 13 bytes x B x event_capacity."""
+    pinned host memory: 2 x 13 bytes x B x event_capacity.
+
+    store=EventStore (datasets/event_store.py): the samples are StoreSamples of recordings that lie in device memory already, and
+    event_capacity is not read (pass None): neither the static columns nor the pinned column staging exist.  window_events=N: a sample
+    is the last T N events before its end -- t_end: the first event of the recording with t >= t_end - t_offset, as
+    EventSlicer.get_events_fixed_num finds it, or end: an event index of the recording --, clamped at the recording's first event and
+    split into T equal windows (datasets.event_feed.sequence_windows); window_duration=D: T windows of D time units that end at t_end
+    (sequence_windows_fixed_duration), with window_capacity= the most events one may hold.  One of the two; one rule per batch.  A
+    batch uploads ONE pinned table of 8 (T + 1 | 1) + 32 bytes a sample; then hip.event_store_windows, hip.event_scatter_store,
+    hip.event_grid_finish_window, a torch.index_select of the store's labels and hip.label_window, all inside the captured graph with
+    graph=True (one capture per output set, kind of batch and rule).  last_flags: the device int32 [B] flag words of the batch just
+    built (hip.EVENT_STORE_FLAG_*; a flagged sample is all zero, as a sample with n < T is); reading them is the caller's
+    synchronisation."""
 
     def __init__(self, batch_size, sequence_steps, bins, event_capacity, grid_hw, height, width, label_hw, grid_rows=None,
                  grid_resize=None, grid_normalize=None, crop_hw=None, crop_band=None, voxel='temporal', rectify_maps=None,
-                 augmentation=True, seed=0, device=None, graph=False, representation=None):
+                 augmentation=True, seed=0, device=None, graph=False, representation=None, store=None, window_events=None,
+                 window_duration=None, window_capacity=None):
         for name, v in (('batch_size', batch_size), ('sequence_steps', sequence_steps), ('bins', bins)):
             if isinstance(v, bool) or not isinstance(v, int) or v < 1:
                 raise hip.EssHipError(f'{name}={v!r}: a positive int is needed')
         if batch_size * sequence_steps > 65535:
             raise hip.EssHipError(f'batch_size * sequence_steps = {batch_size * sequence_steps}: one launch serves at most 65535 windows')
         Hs, Ws = _pair('grid_hw', grid_hw)
-        if isinstance(event_capacity, bool) or not isinstance(event_capacity, int) or event_capacity < 1 or \
+        self._check_store(store, window_events, window_duration, window_capacity, device)
+        if store is not None:
+            event_capacity = None  # (no static columns: the windows are read where the store keeps them)
+        elif isinstance(event_capacity, bool) or not isinstance(event_capacity, int) or event_capacity < 1 or \
                 event_capacity % hip.EVCOL_STRIDE_ALIGN or event_capacity > hip.INGEST_MAX_CAPACITY:
             raise hip.EssHipError(f'event_capacity={event_capacity!r}: events per sample, a multiple of {hip.EVCOL_STRIDE_ALIGN} in '
                                   f'[{hip.EVCOL_STRIDE_ALIGN}, {hip.INGEST_MAX_CAPACITY}] (hip.event_column_stride rounds up)')
@@ -179,8 +196,9 @@ class EventBatchBuilder:
         self.batch_size, self.sequence_steps, self.bins, self.event_capacity = batch_size, sequence_steps, bins, event_capacity
         self.grid_hw, self.grid_rows, self.grid_resize, self.grid_normalize = (Hs, Ws), rows, (Hr, Wr), _NORMS[grid_normalize]
         self.height, self.width, self.crop_hw, self.crop_band, self.voxel = height, width, (h, w), (first, n_rows), voxel
-        self.device = device if device is not None else torch.device('cuda:0')
+        self.device = device if device is not None else (store.device if store is not None else torch.device('cuda:0'))
         self.use_graph = bool(graph)
+        self.last_flags = None
         self.generator = torch.Generator().manual_seed(int(seed))
         self.last_params = None
         self.n_batches = self.n_captures = 0
@@ -199,6 +217,82 @@ class EventBatchBuilder:
         geo = dict(grid_hw=(260, 346), grid_resize=(260, 352), height=200, width=352, label_hw=(200, 346), crop_hw=(120, 216),
                    crop_band=(80, 120))
         return cls(batch_size, sequence_steps, bins, event_capacity, **{**geo, **kw})
+
+    def _check_store(self, store, window_events, window_duration, window_capacity, device):
+        """store=, window_events=, window_duration=, window_capacity= -> self.store, self.store_rule_by_count, self.window,
+        self.window_capacity (the events a window may hold: it shapes the scatter's launch)"""
+        self.store = store
+        if store is None:
+            if window_events is not None or window_duration is not None or window_capacity is not None:
+                raise hip.EssHipError('window_events / window_duration / window_capacity cut samples out of an EventStore: they need store=')
+            return
+        if not isinstance(store, EventStore):
+            raise hip.EssHipError(f'store must be an EventStore, got {type(store).__name__}')
+        if device is not None and torch.device(device) != torch.device(store.device):
+            raise hip.EssHipError(f'device={device!r}: the batch is built where the store lies ({store.device})')
+        if (window_events is None) == (window_duration is None):
+            raise hip.EssHipError('give window_events=N (the events of a window) or window_duration=D (its time span), one of the two')
+        self.store_by_count = window_events is not None
+        if self.store_by_count:
+            if isinstance(window_events, bool) or not isinstance(window_events, int) or not 1 <= window_events <= hip.INGEST_MAX_CAPACITY:
+                raise hip.EssHipError(f'window_events={window_events!r}: an int in [1, {hip.INGEST_MAX_CAPACITY}]')
+            self.window = window_events
+            window_capacity = window_events if window_capacity is None else window_capacity
+        else:
+            d = window_duration
+            if isinstance(d, bool) or not isinstance(d, (int, float)) or not d > 0 or d == float('inf'):
+                raise hip.EssHipError(f'window_duration={d!r} must be a positive number')
+            if window_capacity is None:
+                raise hip.EssHipError('window_duration needs window_capacity=: the most events a window may hold (a larger one flags its sample)')
+            self.window = d
+        if isinstance(window_capacity, bool) or not isinstance(window_capacity, int) or \
+                not (self.window if self.store_by_count else 1) <= window_capacity <= hip.INGEST_MAX_CAPACITY:
+            raise hip.EssHipError(f'window_capacity={window_capacity!r}: an int in [window_events or 1, {hip.INGEST_MAX_CAPACITY}]')
+        self.window_capacity = window_capacity
+
+    def _check_store_samples(self, samples, params):
+        """the checks of one store batch: nothing is written -> (rule, bound words [B][n_bounds], label indices or None, map words, params)"""
+        B, T, store = self.batch_size, self.sequence_steps, self.store
+        if not isinstance(samples, (list, tuple)) or len(samples) != B or any(not isinstance(s, StoreSample) for s in samples):
+            raise hip.EssHipError(f'samples must be a list of batch_size={B} StoreSamples')
+        by_time = samples[0].t_end is not None
+        if any((s.t_end is not None) != by_time for s in samples):
+            raise hip.EssHipError('samples: t_end for every sample of the batch, or end for every one (one rule per launch)')
+        if not by_time and not self.store_by_count:
+            raise hip.EssHipError('window_duration cuts by time: its samples need t_end, not end')
+        rule = hip.EVENT_STORE_RULE_DURATION if not self.store_by_count else \
+            (hip.EVENT_STORE_RULE_COUNT_TIME if by_time else hip.EVENT_STORE_RULE_COUNT_INDEX)
+        bounds = []
+        n_maps =0 if self.maps is None else self.maps.shape[0]
+        for b, s in enumerate(samples):
+            if s.recording >= store.n_recordings:
+                raise hip.EssHipError(f'samples[{b}] names recording {s.recording}, the store holds {store.n_recordings}')
+            if s.label is not None and s.label >= store.n_labels:
+                raise hip.EssHipError(f'samples[{b}]: label index {s.label} of the store\'s {store.n_labels} labels')
+            if s.map is not None and s.map >= n_maps:
+                raise hip.EssHipError(f'samples[{b}]: map index {s.map!r} of the builder\'s {n_maps} rectify_maps')
+            begin, end = store.extent(s.recording)
+            if not by_time:
+                if s.end > end - begin:
+                    raise hip.EssHipError(f'samples[{b}]: end={s.end} of recording {s.recording}\'s {end - begin} events')
+                bounds.append([s.end])
+                continue
+            t_i64 = bool(store.format_of(s.recording) & hip.EVCOL_T_I64)
+            t_end = s.t_end - store.t_offset(s.recording)
+            times = [t_end] if self.store_by_count else duration_bounds(t_end, T, self.window)
+            bounds.append([time_bound(v, t_i64) for v in times])
+        map_of =[hip.RECTIFY_NONE if s.map is None else s.map for s in samples]
+        labelled = [s.label is not None for s in samples]
+        if any(labelled) and not all(labelled):
+            raise hip.EssHipError('samples: a label for every sample of the batch, or for none')
+        if all(labelled) and (store.label_hw != self.label_hw):
+            raise hip.EssHipError(f'the store keeps labels of {store.label_hw}, the builder takes label_hw={self.label_hw}')
+        grid, win = (self.height, self.width), self.crop_hw
+        if params is None:
+            p = draw_window_params(B, grid, win, self.crop_band, self.generator, self.augmentation)  # (the last check: it cannot fail)
+        else:
+            p = check_window_params(params, B, grid, win, self.crop_band)
+        return rule, bounds, ([s.label for s in samples] if all(labelled) else None), map_of, p
 
     @staticmethod
     def _check_maps(rectify_maps, voxel):
@@ -291,26 +385,118 @@ class EventBatchBuilder:
         if with_labels:
             hip.label_window(st['labels'], lab, st['params'], resize=(self.height, self.width))
 
-    def _replay(self, k, with_labels):
+    def _replay(self, k, with_labels, rule=None):
+        """rule: the store's window rule of the batch (a captured launch holds it), None for host columns"""
         st = self._static
-        key = (k, with_labels)
+        launch = (lambda: self._launch(k, with_labels)) if rule is None else (lambda: self._launch_store(k, with_labels, rule))
+        kind = with_labels if rule is None else (with_labels, rule)
         graphs = st['graphs'][k] = st['graphs'][k] or {}
-        if with_labels not in graphs:
+        if kind not in graphs:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                self._launch(*key)
+                launch()
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._launch(*key)
-            graphs[with_labels] = g
+                launch()
+            graphs[kind] = g
             self.n_captures += 1
-        graphs[with_labels].replay()
+        graphs[kind].replay()
+
+    # ---- the store source: no static columns, no column staging; one small table a batch
+    def _store_layout(self):
+        """the per-batch table, in bytes: name -> (offset, dtype, shape); every section starts 16-byte aligned"""
+        B, T = self.batch_size, self.sequence_steps
+        n_bounds = T + 1 if not self.store_by_count else 1
+        at, out = 0, {}
+        for name, dtype, shape in (('bounds', torch.int64, (B, n_bounds)), ('label_of', torch.int64, (B,)),
+                                   ('recording', torch.int32, (B,)), ('sample_map', torch.int32, (B,)), ('params', torch.int32, (B, 4))):
+            out[name] = (at, dtype, shape)
+            at += -(-int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size() // 16) * 16
+        return out, at
+
+    def _allocate_store(self):
+        B, T, dev = self.batch_size, self.sequence_steps, self.device
+        h, w = self.crop_hw
+        layout, nbytes = self._store_layout()
+        views = lambda buf: {name: buf[at:at + int(np.prod(shape)) * torch.empty(0, dtype=d).element_size()].view(d).view(shape)  # noqa: E731
+                             for name, (at, d, shape) in layout.items()}
+        table = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        stage = []
+        for _ in range(2):
+            host = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+            stage.append({'buf': host, 'np': {n: v.numpy() for n, v in views(host).items()}, 'done': torch.cuda.Event()})
+        self._static = {
+            'table': table, 'in': views(table), 'stage': stage,
+            'starts': torch.zeros(B * T, dtype=torch.int64, device=dev),
+            'words': torch.zeros(3, B * T, dtype=torch.int32, device=dev),  # counts, formats, map words
+            'flags': [torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2)],
+            'labels': torch.zeros((B,) + self.label_hw, dtype=torch.uint8, device=dev),
+            'acc': torch.zeros(B * T, self.channels, *self.grid_hw, dtype=torch.int64, device=dev),
+            'out': [(torch.zeros(B * T, self.channels, h, w, dtype=torch.float32, device=dev),
+                     torch.zeros(B, h, w, dtype=torch.int64, device=dev)) for _ in range(2)],
+            'maps': None if self.maps is None else self.maps.to(dev),
+            'graphs': [None, None],
+        }
+
+    def _launch_store(self, k, with_labels, rule):
+        """the launches of one store batch into output set k: the window search, the scatter, the finish, the labels' gather and window"""
+        st, store, T = self._static, self.store, self.sequence_steps
+        ev, lab = st['out'][k]
+        tin, (counts, formats, map_of) = st['in'], st['words']
+        t = store.columns[0]
+        # (total = the capacity: the search keeps every window inside its recording's table row, and a replayed graph serves
+        # recordings that were added after its capture)
+        hip.event_store_windows(t, store.table, tin['recording'], tin['bounds'], rule, T, st['starts'], counts, formats, st['flags'][k],
+                                store.capacity, self.window_capacity, n_per_window=self.window if self.store_by_count else None,
+                                sample_map=tin['sample_map'], map_of=map_of)
+        if self.voxel == 'trilinear':
+            hip.event_scatter_store(*store.columns, st['starts'], counts, formats, st['acc'], hip.EVENT_STORE_TRILINEAR, store.capacity,
+                                    self.window_capacity, st['maps'], map_of)
+        else:
+            hip.event_scatter_store(*store.columns, st['starts'], counts, formats, st['acc'], self._rep, store.capacity, self.window_capacity)
+        hip.event_grid_finish_window(counts, st['acc'], ev, tin['params'], T, crop_rows=self.grid_rows, resize=self.grid_resize,
+                                     normalize=self.grid_normalize)
+        if with_labels:
+            torch.index_select(store.labels, 0, tin['label_of'], out=st['labels'])
+            hip.label_window(st['labels'], lab, tin['params'], resize=(self.height, self.width))
+
+    def _build_store(self, samples, params):
+        rule, bounds, label_of, map_of, p = self._check_store_samples(samples, params)
+        if self.store.n_recordings == 0:
+            raise hip.EssHipError('the store holds no recording')
+        if self._static is None:
+            self._allocate_store()
+        st, B, T = self._static, self.batch_size, self.sequence_steps
+        k = self.n_batches & 1
+        stage = st['stage'][k]
+        stage['done'].synchronize()  # (the set's last upload has completed: it is free to be rewritten)
+        w = stage['np']
+        w['bounds'][:] = 0
+        for b, row in enumerate(bounds):
+            w['bounds'][b, :len(row)] = row
+        w['label_of'][:] = 0 if label_of is None else label_of
+        w['recording'][:] = [s.recording for s in samples]
+        w['sample_map'][:] = map_of
+        w['params'][:] = p.numpy()
+        st['table'].copy_(stage['buf'], non_blocking=True)
+        stage['done'].record()
+        if self.use_graph:
+            self._replay(k, label_of is not None, rule)
+        else:
+            self._launch_store(k, label_of is not None, rule)
+        self.n_batches += 1
+        self.last_params, self.last_flags = p, st['flags'][k]
+        ev, lab = st['out'][k]
+        h, wd = self.crop_hw
+        return ev.view(B, T * self.channels, h, wd), (lab if label_of is not None else None)
 
     def build(self, samples, params=None):
         """-> (events fp32 [B, T * bins, h, w], labels int64 [B, h, w] or None) on the device, valid until the build after the next"""
+        if self.store is not None:
+            return self._build_store(samples, params)
         cols, labels, map_of, p = self._check(samples, params)
         if self._static is None:
             self._allocate()

@@ -83,6 +83,7 @@ EXPORTS = [
     'ess_event_grid_finish_window', 'ess_label_window',
     'ess_event_scatter_ring_rep', 'ess_event_ingest_ring_rep', 'ess_event_ingest_columns_rep',
     'ess_event_ingest_masked', 'ess_event_hot_pixel_mask',
+    'ess_event_scatter_store', 'ess_event_store_windows',
     'ess_recon_post_frame', 'ess_recon_post_bounds', 'ess_event_preview',
     'ess_viz_semseg', 'ess_viz_events', 'ess_viz_overlay',
 ]
@@ -202,6 +203,8 @@ def lib():
             'ess_event_ingest_columns_rep': [P, P, P, P, P, P, I64, I, I, I, I, P, c_size_t, P, I, P],
             'ess_event_ingest_masked': [P, P, P, P, P, P, P, P, I64, I, I, I, I, I, P, c_size_t, P, I, I, P, P, I, I, I, P, P, I, I, I, P],
             'ess_event_hot_pixel_mask': [P, I, I, I, P, P, I, P],
+            'ess_event_scatter_store': [P, P, P, P, P, P, P, I64, I64, I64, I, I, I, I, P, c_size_t, I, P, P, I, I, I, P],
+            'ess_event_store_windows': [P, I64, I64, P, I, P, P, P, I, I, I, I64, I64, P, P, P, P, P, P],
             'ess_recon_post_frame': [P, P, F, F, P, P, P, I, I, I, I, I, I, I, P],
             'ess_recon_post_bounds': [P, P, F, F, I, I, I, P, c_size_t, P, P, I, P, P],
             'ess_event_preview': [P, P, I, I, I, I, I, I, P],
@@ -1383,6 +1386,134 @@ def _event_scatter_ring(fn, t, x, y, p, rows, starts, counts, formats, acc, rect
     _check(getattr(lib(), 'ess_' + fn)(*_column_pointers(words), ring, n_rows, n_slots, bins, H, W, c_void_p(acc.data_ptr()),
                                        acc.numel() * 8, *tail, stream()), 'ess_' + fn)
     return acc
+
+
+# The device event store (ess_event_scatter_store / ess_event_store_windows): windows cut on the device out of recordings that were
+# uploaded once (datasets.event_store.EventStore owns the columns and the recording table).
+EVENT_STORE_SIGNED = 0      # ESS_EVENT_STORE_SIGNED: EVENT_REP_SIGNED's grid
+EVENT_STORE_SEPARATE = 1    # ESS_EVENT_STORE_SEPARATE: EVENT_REP_SEPARATE's
+EVENT_STORE_HISTOGRAM = 2   # ESS_EVENT_STORE_HISTOGRAM: EVENT_REP_HISTOGRAM's
+EVENT_STORE_TRILINEAR = 3   # ESS_EVENT_STORE_TRILINEAR: event_scatter_ring_trilinear's grid, with maps / map_of
+EVENT_STORE_RULE_COUNT_TIME = 0   # ESS_EVENT_STORE_RULE_COUNT_TIME: T * n events before the first event with t >= bound
+EVENT_STORE_RULE_COUNT_INDEX = 1  # ESS_EVENT_STORE_RULE_COUNT_INDEX: ... before the given index of the recording
+EVENT_STORE_RULE_DURATION = 2     # ESS_EVENT_STORE_RULE_DURATION: T windows between T + 1 time bounds
+EVENT_STORE_FLAG_EMPTY = 1     # ESS_EVENT_STORE_FLAG_EMPTY: no event in any window of the sample
+EVENT_STORE_FLAG_OVERFLOW = 2  # ESS_EVENT_STORE_FLAG_OVERFLOW: a window above window_capacity; all T counts are 0
+EVENT_STORE_FLAG_RANGE = 4     # ESS_EVENT_STORE_FLAG_RANGE: the recording or the end index lies outside the table / the recording
+EVENT_STORE_MAX_CAPACITY = 1 << 40
+EVENT_STORE_TABLE_WORDS = 4    # a recording's row: begin, end, format, reserved
+_EVENT_STORE_FLAVOURS = (EVENT_STORE_SIGNED, EVENT_STORE_SEPARATE, EVENT_STORE_HISTOGRAM, EVENT_STORE_TRILINEAR)
+_EVENT_STORE_RULES = (EVENT_STORE_RULE_COUNT_TIME, EVENT_STORE_RULE_COUNT_INDEX, EVENT_STORE_RULE_DURATION)
+
+
+def _int_in(fn, name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+        raise EssHipError(f'{fn}: {name}={v!r} must be an int in [{lo}, {hi}]')
+    return int(v)
+
+
+def _store_columns(fn, named, total):
+    """the store's flat columns t, x, y, p [capacity] -> (capacity, total)"""
+    t = named[0][1]
+    if t.dim() != 1 or t.shape[0] < EVCOL_STRIDE_ALIGN or t.shape[0] % EVCOL_STRIDE_ALIGN or t.shape[0] > EVENT_STORE_MAX_CAPACITY:
+        raise EssHipError(f'{fn}: t must be [capacity], capacity a multiple of {EVCOL_STRIDE_ALIGN} in [{EVCOL_STRIDE_ALIGN}, 2^40], '
+                          f'got {tuple(t.shape)}')
+    for name, v in named[:4]:
+        if v.dtype not in _EVCOL_DTYPES[name] or v.shape != t.shape:
+            raise EssHipError(f'{fn}: {name} must be {" / ".join(str(d) for d in _EVCOL_DTYPES[name])} '
+                              f'{list(t.shape)}, got {v.dtype}{tuple(v.shape)}')
+    return t.shape[0], _int_in(fn, 'total', total, 0, t.shape[0])
+
+
+def _formed_words(fn, named, dtype, shape):
+    for name, v in named:
+        if v.dtype != dtype or tuple(v.shape) != tuple(shape):
+            raise EssHipError(f'{fn}: {name} must be {str(dtype).replace("torch.", "")} {list(shape)}, got {v.dtype}{tuple(v.shape)}')
+
+
+def event_scatter_store(t, x, y, p, starts, counts, formats, acc, flavour, total, window_capacity, maps=None, map_of=None):
+    """event_scatter_ring* on the device event store: the same sums, bit for bit, as the ring source leaves for the same events.
+    t, x, y, p: device [capacity] flat columns (dtypes as event_ingest_columns; capacity a multiple of 16 up to 2^40), the first
+    `total` events filled, recordings one behind the other.  starts: device int64 [n_slots], ABSOLUTE event indices; counts, formats:
+    device int32 [n_slots] -- slot i's window is the counts[i] events from starts[i] on, nothing wraps.  A negative start,
+    start + count > total, count > window_capacity, an unknown format bit (or map word): the slot counts as empty, its planes of
+    acc stay as they are.  window_capacity (1 .. 2^22) shapes the launch, not the store's size.  acc: device int64 [n_slots, C, H, W],
+    the sums are added to it.  flavour: EVENT_STORE_SIGNED / _SEPARATE / _HISTOGRAM (the EVENT_REP_* rules for C) or
+    EVENT_STORE_TRILINEAR with maps, map_of as event_scatter_ring_trilinear takes them (refused with any other flavour).  -> acc"""
+    fn = 'event_scatter_store'
+    cols = (('t', t), ('x', x), ('y', y), ('p', p))
+    words = (('starts', starts), ('counts', counts), ('formats', formats))
+    named = cols + words + (('acc', acc),)
+    _are_tensors(fn, named)
+    n_slots, C, H, W = _finish_acc(fn, acc, 'H, W')
+    if isinstance(flavour, bool) or flavour not in _EVENT_STORE_FLAVOURS:
+        raise EssHipError(f'{fn}: flavour={flavour!r} must be EVENT_STORE_SIGNED, _SEPARATE, _HISTOGRAM or _TRILINEAR')
+    if flavour != EVENT_STORE_TRILINEAR:
+        _event_rep_of(fn, int(flavour), C, 'acc')
+        if maps is not None or map_of is not None:
+            raise EssHipError(f'{fn}: maps / map_of belong to flavour=EVENT_STORE_TRILINEAR')
+    capacity, total = _store_columns(fn, cols, total)
+    window_capacity = _int_in(fn, 'window_capacity', window_capacity, 1, INGEST_MAX_CAPACITY)
+    _formed_words(fn, words[:1], torch.int64, (n_slots,))
+    _formed_words(fn, words[1:], torch.int32, (n_slots,))
+    _on_device(fn, named)
+    tail = _rectify_args(fn, maps, map_of, n_slots, acc.device) if flavour == EVENT_STORE_TRILINEAR else (c_void_p(0), c_void_p(0), 0, 1, 1)
+    _check(lib().ess_event_scatter_store(*(c_void_p(v.data_ptr()) for _, v in cols), ptr(starts, torch.int64), ptr(counts, torch.int32),
+                                         ptr(formats, torch.int32), capacity, total, window_capacity, n_slots, C, H, W,
+                                         c_void_p(acc.data_ptr()), acc.numel() * 8, int(flavour), *tail, stream()), 'ess_' + fn)
+    return acc
+
+
+def event_store_windows(t, table, recording, bounds, rule, sequence_steps, starts, counts, formats, flags, total, window_capacity,
+                        n_per_window=None, sample_map=None, map_of=None):
+    """A batch's sample table -> the B * T slot words event_scatter_store and event_grid_finish_window read, in one launch.
+    t: the store's time column, device [capacity] int64 or float64; table: device int64 [n_recordings, 4] rows (begin, end, format,
+    reserved), a negative format marks an unused row; recording: device int32 [B], the samples' rows; bounds: device int64 or
+    float64 [B, 1] ([B, T + 1] under EVENT_STORE_RULE_DURATION), 8-byte words READ IN THE RECORDING'S OWN TIME TYPE (a recording of
+    the other type than the tensor's dtype gets its words through .view()), prepared by the host as datasets.event_feed's rules
+    prepare them; under EVENT_STORE_RULE_COUNT_INDEX bounds[b, 0] is the int64 end index relative to the recording.  rule,
+    n_per_window, the three flag bits: as include/ess_hip.h states them.  starts (int64 [B T]), counts, formats (int32 [B T]) and flags
+    (int32 [B]) are written for every sample; sample_map (int32 [B]) and map_of (int32 [B T]): both or neither.  -> flags"""
+    fn = 'event_store_windows'
+    T = _int_in(fn, 'sequence_steps', sequence_steps, 1, 65535)
+    if isinstance(rule, bool) or rule not in _EVENT_STORE_RULES:
+        raise EssHipError(f'{fn}: rule={rule!r} must be EVENT_STORE_RULE_COUNT_TIME, _COUNT_INDEX or _DURATION')
+    if (sample_map is None) != (map_of is None):
+        raise EssHipError(f'{fn}: sample_map and map_of are given together (the map words are passed through) or not at all')
+    maps = () if map_of is None else (('sample_map', sample_map), ('map_of', map_of))
+    named = (('t', t), ('table', table), ('recording', recording), ('bounds', bounds), ('starts', starts), ('counts', counts),
+             ('formats', formats), ('flags', flags)) + maps
+    _are_tensors(fn, named)
+    if t.dim() != 1 or t.dtype not in _EVCOL_DTYPES['t'] or t.shape[0] < EVCOL_STRIDE_ALIGN or t.shape[0] % EVCOL_STRIDE_ALIGN or \
+            t.shape[0] > EVENT_STORE_MAX_CAPACITY:
+        raise EssHipError(f'{fn}: t must be int64 / float64 [capacity], capacity a multiple of {EVCOL_STRIDE_ALIGN} in '
+                          f'[{EVCOL_STRIDE_ALIGN}, 2^40], got {t.dtype}{tuple(t.shape)}')
+    total = _int_in(fn, 'total', total, 0, t.shape[0])
+    window_capacity = _int_in(fn, 'window_capacity', window_capacity, 1, INGEST_MAX_CAPACITY)
+    if rule == EVENT_STORE_RULE_DURATION:
+        if n_per_window is not None:
+            raise EssHipError(f'{fn}: n_per_window belongs to the count rules')
+        n_per_window = 0
+    else:
+        n_per_window = _int_in(fn, 'n_per_window', n_per_window, 1, window_capacity)
+    if table.dim() != 2 or table.dtype != torch.int64 or table.shape[0] < 1 or table.shape[1] != EVENT_STORE_TABLE_WORDS:
+        raise EssHipError(f'{fn}: table must be int64 [n_recordings, {EVENT_STORE_TABLE_WORDS}] rows of (begin, end, format, reserved), '
+                          f'got {table.dtype}{tuple(table.shape)}')
+    if recording.dim() != 1 or recording.dtype != torch.int32 or not 1 <= recording.shape[0] * T <= 65535:
+        raise EssHipError(f'{fn}: recording must be int32 [B] with B * sequence_steps in 1..65535, got {recording.dtype}{tuple(recording.shape)}')
+    B = recording.shape[0]
+    n_bounds = T + 1 if rule == EVENT_STORE_RULE_DURATION else 1
+    if bounds.dtype not in (torch.int64, torch.float64) or tuple(bounds.shape) != (B, n_bounds):
+        raise EssHipError(f'{fn}: bounds must be int64 / float64 [{B}, {n_bounds}], got {bounds.dtype}{tuple(bounds.shape)}')
+    _formed_words(fn, (('starts', starts),), torch.int64, (B * T,))
+    _formed_words(fn, (('counts', counts), ('formats', formats)) + maps[1:], torch.int32, (B * T,))
+    _formed_words(fn, (('flags', flags),) + maps[:1], torch.int32, (B,))
+    _on_device(fn, named)
+    P = lambda v: c_void_p(0 if v is None else v.data_ptr())  # noqa: E731
+    _check(lib().ess_event_store_windows(P(t), t.shape[0], total, P(table), table.shape[0], P(recording), P(bounds), P(sample_map), B, T,
+                                         int(rule), n_per_window, window_capacity, P(starts), P(counts), P(formats), P(map_of), P(flags),
+                                         stream()), 'ess_' + fn)
+    return flags
 
 
 def event_grid_finish(counts, acc, out, crop_rows=None, resize=None, normalize=GRID_NORM_NONE):

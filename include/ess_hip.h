@@ -649,6 +649,49 @@ int ess_event_grid_finish_window(const int32_t* counts, int32_t n_slots, int32_t
 int ess_label_window(const uint8_t* src, int32_t n, int32_t src_height, int32_t src_width, int32_t resize_height, int32_t resize_width,
                      const int32_t* words, int32_t win_height, int32_t win_width, int64_t* out, ess_stream_t stream);
 
+/* DEVICE EVENT STORE: training windows cut on the device out of recordings uploaded once -- PURELY ADDITIVE to ABI 110.
+ * The store is ONE flat set of the four columns in device memory (t 8 bytes, x / y 2, p 1 per event, each 16-byte aligned):
+ * `capacity` events, a multiple of 16 up to 2^40, of which the first `total` are filled, recordings laid one behind the other.
+ *
+ * ess_event_scatter_store: the scatter half of the ingest (ess_event_scatter_ring*) on the store.  Slot s's window is counts[s]
+ * events from ABSOLUTE event index starts[s] (int64, device), read under formats[s] (ESS_EVCOL_*); nothing wraps.  Counted as
+ * count 0 (the slot's planes of acc stay as they are): starts[s] < 0, starts[s] + counts[s] > total, counts[s] > window_capacity,
+ * an unknown format bit, and under ESS_EVENT_STORE_TRILINEAR an unknown map word.  window_capacity (1 .. 2^22, the int64 sums'
+ * bound) shapes the launch, NOT the store's size; every index on the path is 64-bit.  flavour: ESS_EVENT_STORE_SIGNED, _SEPARATE,
+ * _HISTOGRAM (the ESS_EVENT_REP_* words and their rules for `channels`) or _TRILINEAR (maps .. map_width as for
+ * ess_event_scatter_ring_trilinear; with any other flavour they are not read).  The sums are, bit for bit, what the ring source
+ * leaves for the same events.  Hot-pixel masks are not offered on this source.
+ *
+ * ess_event_store_windows: a batch's sample table -> the n_samples * T slot words.  table (device, int64 [n_recordings][4]):
+ * (begin, end, format, reserved) per recording, absolute indices with 0 <= begin <= end <= total; a negative format word marks an
+ * unused row.  recording (int32 [n_samples]): the sample's row.  bounds (8-byte words, [n_samples][1], or [n_samples][T + 1] under
+ * ESS_EVENT_STORE_RULE_DURATION): time bounds in the recording's OWN time type (int64, or fp64 bits), prepared by the host; the
+ * device finds "the first index in [begin, end) with t >= bound, end where there is none".  rule:
+ *   ESS_EVENT_STORE_RULE_COUNT_TIME (0):  e = that index for bounds[b][0];  start = max(begin, e - T * n_per_window);
+ *                                         n = (e - start) / T;  window i = (start + i n, n); the remainder at the END is unused
+ *   ESS_EVENT_STORE_RULE_COUNT_INDEX (1): the same with e = begin + bounds[b][0], an int64 index relative to the recording; no search
+ *   ESS_EVENT_STORE_RULE_DURATION (2):    idx_j = that index for bounds[b][j];  window i = (idx_i, idx_(i+1) - idx_i)
+ * starts (int64), counts, formats (int32 [n_samples * T]) and flags (int32 [n_samples]) are WRITTEN for every sample; sample_map
+ * (int32 [n_samples]) and map_of (int32 [n_samples * T]) are both given -- map_of[b T + i] = sample_map[b] -- or both null.  flags:
+ *   ESS_EVENT_STORE_FLAG_EMPTY (1):    n == 0, or every window is empty;
+ *   ESS_EVENT_STORE_FLAG_OVERFLOW (2): a window holds more than window_capacity events: ALL T counts of the sample are 0;
+ *   ESS_EVENT_STORE_FLAG_RANGE (4):    the recording number is outside the table (or names an unused or malformed row), e is outside
+ *                                      the recording: starts, counts and formats are 0; or the bounds descend: the counts are 0.
+ * One workgroup a sample, one wave a bound (a 64-ary search: <= 7 dependent loads over 2^40 events); no synchronisation, nothing
+ * read back: capturable.  n_samples * T in 1..65535, n_per_window in 1..window_capacity under the count rules.               */
+enum { ESS_EVENT_STORE_SIGNED = 0, ESS_EVENT_STORE_SEPARATE = 1, ESS_EVENT_STORE_HISTOGRAM = 2, ESS_EVENT_STORE_TRILINEAR = 3 };
+enum { ESS_EVENT_STORE_RULE_COUNT_TIME = 0, ESS_EVENT_STORE_RULE_COUNT_INDEX = 1, ESS_EVENT_STORE_RULE_DURATION = 2 };
+enum { ESS_EVENT_STORE_FLAG_EMPTY = 1, ESS_EVENT_STORE_FLAG_OVERFLOW = 2, ESS_EVENT_STORE_FLAG_RANGE = 4 };
+int ess_event_scatter_store(const void* t, const void* x, const void* y, const void* p, const int64_t* starts, const int32_t* counts,
+                            const int32_t* formats, int64_t capacity, int64_t total, int64_t window_capacity, int32_t n_slots,
+                            int32_t channels, int32_t height, int32_t width, void* acc, size_t acc_bytes, int32_t flavour,
+                            const float* maps, const int32_t* map_of, int32_t n_maps, int32_t map_height, int32_t map_width,
+                            ess_stream_t stream);
+int ess_event_store_windows(const void* t, int64_t capacity, int64_t total, const int64_t* table, int32_t n_recordings,
+                            const int32_t* recording, const int64_t* bounds, const int32_t* sample_map, int32_t n_samples, int32_t T,
+                            int32_t rule, int64_t n_per_window, int64_t window_capacity, int64_t* starts, int32_t* counts,
+                            int32_t* formats, int32_t* map_of, int32_t* flags, ess_stream_t stream);
+
 /* ---- image-branch augmentation on the device: the geometric + photometric core of the albumentations
  * pipeline of datasets/cityscapes_loader.py:39-74 (HorizontalFlip, ShiftScaleRotate with rotate 0 and a constant-0 border,
  * centred PadIfNeeded, RandomCrop, GaussNoise, RandomBrightnessContrast), uint8 quantisation, ToTensor (/255), and for the label

@@ -9,7 +9,9 @@ scatter + finish + flip / slice (the scatter refills the sums every finish clear
 The ways alternate, --rounds times; every figure is ms per batch, median (min - max) over the rounds.  The two ways' batches are
 compared bit for bit at the timed size before anything is timed.  One JSON line per figure.
 
-    python tools/bench_train_batch.py --preset dsec|ddd17 --batch 8 --steps 20 --events 100000 [--graph]"""
+    python tools/bench_train_batch.py --preset dsec|ddd17 --batch 8 --steps 20 --events 100000 [--graph]
+    python tools/bench_train_batch.py --store --preset dsec|ddd17 --batch 8 --steps 20 --events 100000 [--graph]
+        (a batch cut out of a device EventStore against the same batch from host columns: main_store)"""
 import argparse
 import json
 import os
@@ -99,8 +101,72 @@ def device_ms(fn, reps):
     return a.elapsed_time(b) / reps
 
 
+def main_store(a):
+    """--store: a batch from a device EventStore against the same batch from host columns, build() to synchronised tensors.
+    A synthetic store of --recordings recordings of 3 samples' worth of events each; a sample is the T * events events before an end
+    index, the ends half a sample apart (consecutive samples overlap by 50 %); the host-column way gets the same events as slices of
+    the recordings' host arrays.  Both ways get the same window rows, their batches are compared bit for bit before anything is
+    timed; they alternate, --rounds times.  Also: the one-off upload, ms per million events."""
+    from ess_amd.datasets.event_store import EventStore, StoreSample
+    make, kw, classes = PRESETS[a.preset]
+    B, T, n = a.batch, a.steps, a.events
+    per = T * n
+    probe = make(B, T, a.bins, hip.event_column_stride(per), **kw)
+    Hs, Ws = probe.grid_hw
+    g = np.random.default_rng(0)
+    store = EventStore(a.recordings * 3 * per, label_hw=probe.label_hw, label_capacity=a.recordings * 5)
+    recs, upload = [], []
+    for r in range(a.recordings):
+        m = 3 * per
+        t = np.sort(g.integers(0, 50_000 * 3 * T, m)).astype(np.int64) + 1_600_000_000_000_000
+        cols = EventColumns(t, g.integers(0, Ws, m).astype(np.uint16), g.integers(0, Hs, m).astype(np.uint16), g.integers(0, 2, m).astype(np.uint8))
+        labels = g.integers(0, classes, (5,) + probe.label_hw).astype(np.uint8)
+        upload.append(host_ms(lambda: store.add_recording(cols, labels=labels)) / (m / 1e6))
+        recs.append((cols, labels))
+    pool = [(r, per + k * per // 2, 5 * r + k) for r in range(a.recordings) for k in range(5)]  # (recording, end index, label)
+    order = np.random.default_rng(1).permutation(len(pool))
+    batches = [[pool[i] for i in order[(j * B + np.arange(B)) % len(pool)]] for j in range(2)]
+    new = make(B, T, a.bins, None, store=store, window_events=n, graph=a.graph, **kw)
+    old = make(B, T, a.bins, hip.event_column_stride(per), graph=a.graph, **kw)
+    s_store = [[StoreSample(r, end=e, label=lab) for r, e, lab in batch] for batch in batches]
+    s_cols = [[(EventColumns(*(c[e - per:e] for c in (recs[r][0].t, recs[r][0].x, recs[r][0].y, recs[r][0].p))), recs[r][1][lab - 5 * r])
+               for r, e, lab in batch] for batch in batches]
+    from ess_amd.datasets.event_batches import draw_window_params
+    gen = torch.Generator().manual_seed(1)
+    params = [draw_window_params(B, (new.height, new.width), new.crop_hw, new.crop_band, gen) for _ in range(2)]
+    same = True
+    for k in range(2):  # (also the warm-up, and the captures)
+        for _ in range(2):
+            ev, lab = new.build(s_store[k], params=params[k])
+            wev, wlab = old.build(s_cols[k], params=params[k])
+            same = same and torch.equal(ev.view(torch.int32), wev.view(torch.int32)) and torch.equal(lab, wlab)
+    same = same and not bool(new.last_flags.any())
+    print(json.dumps(dict(preset=a.preset, batch=B, steps=T, events=n, bins=a.bins, graph=a.graph, store_events=store.n_events,
+                          store_bytes=store.bytes(), same_bits=bool(same),
+                          upload_ms_per_million_events=dict(median=round(statistics.median(upload), 3), min=round(min(upload), 3),
+                                                            max=round(max(upload), 3)))), flush=True)
+    if not same:
+        raise SystemExit('the two ways do not give the same batch: nothing is timed')
+    ways = {'store': lambda: statistics.mean(host_ms(lambda k=k: new.build(s_store[k & 1], params=params[k & 1])) for k in range(a.batches)),
+            'host_columns': lambda: statistics.mean(host_ms(lambda k=k: old.build(s_cols[k & 1], params=params[k & 1])) for k in range(a.batches)),
+            'store_launches_alone': lambda: device_ms(lambda: new._launch_store(0, True, hip.EVENT_STORE_RULE_COUNT_INDEX), a.reps)}
+    times = {k: [] for k in ways}
+    for _ in range(a.rounds):
+        for k, fn in ways.items():
+            times[k].append(fn())
+    med = {k: statistics.median(v) for k, v in times.items()}
+    for k, v in times.items():
+        print(json.dumps(dict(way=k, ms_median=round(med[k], 3), ms_min=round(min(v), 3), ms_max=round(max(v), 3),
+                              clock=f'device events, {a.reps} launches' if 'alone' in k else 'host, to a device synchronise')), flush=True)
+    spread = max(times['host_columns']) - min(times['host_columns'])
+    print(json.dumps(dict(store_minus_host_columns_ms=round(med['store'] - med['host_columns'], 3), host_columns_spread_ms=round(spread, 3),
+                          store_SLOWER_than_host_columns=bool(med['store'] - med['host_columns'] > spread))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--store', action='store_true', help='a device EventStore against host columns (see main_store)')
+    ap.add_argument('--recordings', type=int, default=3, help='(with --store) recordings of 3 samples\' worth of events each')
     ap.add_argument('--preset', choices=sorted(PRESETS), default='ddd17')
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--steps', type=int, default=20, help='windows per sample (T)')
@@ -113,6 +179,8 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_train_batch needs an MI355X: there is no CPU path and no figure without one')
+    if a.store:
+        return main_store(a)
     make, kw, classes = PRESETS[a.preset]
     cap = hip.event_column_stride(a.steps * a.events)
     new = make(a.batch, a.steps, a.bins, cap, graph=a.graph, **kw)

@@ -31,10 +31,14 @@ And the HOT-PIXEL MASKS (masked(), --masked: these rows alone): the ring source,
 map, three ways in ONE run -- the unmasked kernel, hip.event_ingest_masked under an all-zero mask, and under a mask of 100 hot pixels
 that carry 5 % of the events -- and hip.event_hot_pixel_mask on one histogram a stream.
 
+And the DEVICE EVENT STORE (store(), --store: these rows alone): hip.event_scatter_store against hip.event_scatter_ring on the same
+events from start residues 0 and 3, and hip.event_store_windows alone on a time column of --store-events events.
+
 usage: python tools/bench_voxel.py --ingest --slices 8 --events 100000 --bins 5
        python tools/bench_voxel.py --ingest --masked --slices 8 --events 100000 --bins 5
        python tools/bench_voxel.py --ingest --representations-only --slices 8 --events 100000 --bins 5
-       python tools/bench_voxel.py --ingest --loader-finish-only --slices 160 --events 100000 --bins 5 --reps 20"""
+       python tools/bench_voxel.py --ingest --loader-finish-only --slices 160 --events 100000 --bins 5 --reps 20
+       python tools/bench_voxel.py --ingest --store --slices 8 --events 100000 --bins 5"""
 import argparse
 import json
 import os
@@ -59,6 +63,8 @@ def main():
     ap.add_argument('--loader-finish-only', action='store_true', help='(with --ingest) only the loader-finish rows')
     ap.add_argument('--representations-only', action='store_true', help='(with --ingest) only the event-representation rows')
     ap.add_argument('--masked', action='store_true', help='(with --ingest) only the hot-pixel mask rows')
+    ap.add_argument('--store', action='store_true', help='(with --ingest) only the device event store rows')
+    ap.add_argument('--store-events', type=int, default=100_000_000, help='(with --store) events of the column the window search runs on')
     a = ap.parse_args()
     if a.ingest:
         return ingest(a)
@@ -331,11 +337,114 @@ def masked(a):
                         f'the events; event_hot_pixel_mask at {S} x {H} x {W}', 'reps': a.reps, 'mask_bytes': int(mask.words.nbytes), 'rows': row}
 
 
+def store(a):
+    """The device event store beside the ring: hip.event_scatter_store against hip.event_scatter_ring on the SAME events (S windows
+    of n int64 / uint16 events), from start residues 0 and 3, alternating in one run -- every way scatters into one all-zero acc that
+    an untimed torch zero_() clears outside the events (a scatter alone never clears its sums); and hip.event_store_windows alone on a
+    time column of --store-events events made on the device, B = 8 samples x T = 20, by the count rule (one search a sample) and by
+    the duration rule (21 searches a sample).  -> rows for the JSON"""
+    import numpy as np
+    from ess_amd import hip
+    S, n, C, H, W = a.slices, a.events, a.bins, a.height, a.width
+    dev = torch.device('cuda:0')
+    stride = hip.event_column_stride(n)
+    ring = 2 * stride
+    g = np.random.default_rng(1)
+    ev = [np.sort(g.integers(0, 30_000, (S, n)), axis=1).astype(np.int64), g.integers(0, W, (S, n)).astype(np.uint16),
+          g.integers(0, H, (S, n)).astype(np.uint16), g.integers(0, 2, (S, n)).astype(np.uint8)]
+    i32 = lambda v: torch.as_tensor(v, dtype=torch.int32, device=dev)  # noqa: E731
+    fmt = i32([hip.EVCOL_XY_U16 | hip.EVCOL_T_I64] * S)
+    counts = i32([n] * S)
+    acc = torch.zeros(S, C, H, W, dtype=torch.int64, device=dev)
+    ways, sums = {}, {}
+    for start in (0, 3):
+        rcols = [np.zeros((S, ring), c.dtype) for c in ev]
+        flat = [np.zeros(S * ring, c.dtype) for c in ev]  # (window s lies at s * ring + start of the flat store: the ring's own bytes)
+        for r, f, c in zip(rcols, flat, ev):
+            r[:, start:start + n] = c
+            f[:] = r.reshape(-1)
+        dr = tuple(torch.from_numpy(c.view(np.int16) if c.dtype == np.uint16 else c).to(dev) for c in rcols)
+        df = tuple(torch.from_numpy(c.view(np.int16) if c.dtype == np.uint16 else c).to(dev) for c in flat)
+        rwords = (i32(list(range(S))), i32([start] * S), counts, fmt)
+        starts = torch.as_tensor([s * ring + start for s in range(S)], dtype=torch.int64, device=dev)
+        ways[f'scatter_ring_start{start}'] = lambda dr=dr, rwords=rwords: hip.event_scatter_ring(*dr, *rwords, acc)
+        ways[f'scatter_store_start{start}'] = lambda df=df, starts=starts: hip.event_scatter_store(*df, starts, counts, fmt, acc, hip.EVENT_STORE_SIGNED,
+                                                                                                  S * ring, stride)
+    for k, fn in ways.items():  # (what is timed gives the same sums) + warm-up
+        acc.zero_()
+        fn()
+        sums[k] = acc.clone()
+        for _ in range(20):
+            fn()
+    same = all(torch.equal(sums[f'scatter_ring_start{s}'], sums[f'scatter_store_start{s}']) for s in (0, 3))
+    torch.cuda.synchronize()
+    ms = {k: [] for k in ways}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(3):
+        for k, fn in ways.items():
+            total = 0.0
+            for _ in range(a.reps):
+                acc.zero_()
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                total += e0.elapsed_time(e1)
+            ms[k].append(total / a.reps)
+    med = {k: sorted(v)[1] for k, v in ms.items()}
+    spread = max(max(v) - min(v) for k, v in ms.items() if 'ring' in k)
+    rows = {'ms_per_batch': {k: {'median': round(med[k], 5), 'min': round(min(v), 5), 'max': round(max(v), 5)} for k, v in ms.items()},
+            'same_sums': bool(same), 'ring_spread_ms': round(spread, 5)}
+    for s in (0, 3):
+        d = med[f'scatter_store_start{s}'] - med[f'scatter_ring_start{s}']
+        rows[f'store_minus_ring_start{s}_ms'] = round(d, 5)
+        rows[f'store_SLOWER_than_ring_start{s}'] = bool(d > spread)
+    # -- the window search alone
+    N = hip.event_column_stride(a.store_events)
+    t = torch.cumsum(torch.randint(0, 3, (N,), device=dev, dtype=torch.int64), 0)
+    B, T = 8, 20
+    table = torch.tensor([[0, N, hip.EVCOL_T_I64, 0]], dtype=torch.int64, device=dev)
+    rec = torch.zeros(B, dtype=torch.int32, device=dev)
+    last = int(t[-1])
+    ends = torch.linspace(0.1, 0.95, B, dtype=torch.float64) * last
+    b_count = ends.to(torch.int64).view(B, 1).to(dev)
+    d = 50_000
+    b_dur = (ends.to(torch.int64).view(B, 1) - T * d + d * torch.arange(T + 1, dtype=torch.int64).view(1, T + 1)).to(dev)
+    out = (torch.zeros(B * T, dtype=torch.int64, device=dev), torch.zeros(B * T, dtype=torch.int32, device=dev),
+           torch.zeros(B * T, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.int32, device=dev))
+    search = {'count_rule': lambda: hip.event_store_windows(t, table, rec, b_count, hip.EVENT_STORE_RULE_COUNT_TIME, T, *out, N, 1 << 22,
+                                                            n_per_window=n),
+              'duration_rule': lambda: hip.event_store_windows(t, table, rec, b_dur, hip.EVENT_STORE_RULE_DURATION, T, *out, N, 1 << 22)}
+    sms = {k: [] for k in search}
+    for fn in search.values():
+        for _ in range(20):
+            fn()
+    torch.cuda.synchronize()
+    for _ in range(3):
+        for k, fn in search.items():
+            e0.record()
+            for _ in range(a.reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            sms[k].append(e0.elapsed_time(e1) / a.reps)
+    flags_ok = not bool(out[3].any())
+    rows['event_store_windows'] = {'events': N, 'samples': B, 'T': T, 'flags_all_zero': flags_ok,
+                                   'us_per_launch': {k: {'median': round(sorted(v)[1] * 1e3, 2), 'min': round(min(v) * 1e3, 2),
+                                                         'max': round(max(v) * 1e3, 2)} for k, v in sms.items()},
+                                   'clock': f'device events around {a.reps} back-to-back launches (launch overhead included)'}
+    return {'workload': f'{S} windows x {n} events, bins={C}, {H} x {W}; ring of {ring} / a flat store of {S * ring}', 'reps': a.reps, 'rows': rows}
+
+
 def ingest(a):
     import numpy as np
     from ess_amd import hip
     from ess_amd.datasets.data_util import pack_event_records
     hip.lib()
+    if a.store:
+        print(json.dumps({'metric': 'store events -> sums beside the ring scatter; the window search alone', 'unit': 'ms', 'store': store(a),
+                          'data': 'synthetic'}))
+        return
     if a.masked:
         print(json.dumps({'metric': 'ring events -> grids under hot-pixel masks, ms per batch', 'unit': 'ms', 'masked': masked(a),
                           'data': 'synthetic'}))
