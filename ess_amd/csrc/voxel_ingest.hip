@@ -323,7 +323,9 @@ struct Masked {
 constexpr int MASK_REPLACE = 0, MASK_OR = 1;  // (ESS_MASK_REPLACE, ESS_MASK_OR of include/ess_hip.h)
 constexpr int MASK_WAVES = INGEST_THREADS / 64;
 
-template <bool OR>
+// PLAIN: sums are plain counts, one plane a sensor (ess_event_count_mask: what ess_event_store_pixel_counts leaves), compared as they
+// stand; else the histogram flavour's two planes at scale 2^40.
+template <bool OR, bool PLAIN>
 __global__ __launch_bounds__(INGEST_THREADS) void hot_pixel_mask_kernel(const long long* __restrict__ sums, const long long* __restrict__ thresholds,
                                                                         int H, int W, uint32_t* __restrict__ masks) {
   const int i = blockIdx.y;
@@ -335,9 +337,13 @@ __global__ __launch_bounds__(INGEST_THREADS) void hot_pixel_mask_kernel(const lo
   const int y = (int)(c / chunks), lane = threadIdx.x & 63;
   const int x0 = (int)(c % chunks) << 6, x = x0 + lane;
   const size_t plane = (size_t)H * W;
-  const long long* __restrict__ s = sums + (size_t)i * 2 * plane + (size_t)y * W;
+  const long long* __restrict__ s = sums + (size_t)i * (PLAIN ? 1 : 2) * plane + (size_t)y * W;
   bool hot = false;
-  if (x < W) hot = ((s[x] + s[plane + x]) >> 40) > thr;
+  if constexpr (PLAIN) {
+    if (x < W) hot = s[x] > thr;
+  } else {
+    if (x < W) hot = ((s[x] + s[plane + x]) >> 40) > thr;
+  }
   const unsigned long long votes = __ballot(hot);
   const int word = (x0 >> 5) + lane;
   if (lane < 2 && word < mask_words) {
@@ -510,6 +516,45 @@ int launch_scatter_store(const char* status, const void* t, const void* x, const
                      (const unsigned char*)p, (const long long*)starts, counts, formats, total, window_capacity, (int)channels,
                      (int)height, (int)width, (long long*)acc, extra...);
   return ess_launch_status(status);
+}
+
+// ---- plain per-pixel counts of an index range of the store (ess_event_store_pixel_counts): job j counts the events begins[j] ..
+// ends[j] - 1 (absolute int64 indices, device words; a range as long as the store, not a window: no 2^22 bound) into counts[j], int64
+// [H][W], ONE per event whatever its polarity -- a whole recording's counts for a hot-pixel rule, which the histogram flavour's sums
+// (2^40 an event) cannot hold beyond 2^22 events a pixel.  Only x and y are loaded, 4 bytes an event; the walk is
+// event_scatter_store_kernel's -- aligned groups of COLUMN_GROUP, the head and the tail masked, every index 64-bit -- strided by the
+// grid over the range.  A range outside [0, total], begin > end or an unknown format bit: the job counts nothing.
+__global__ __launch_bounds__(INGEST_THREADS) void event_store_pixel_counts_kernel(const unsigned short* __restrict__ x,
+                                                                                  const unsigned short* __restrict__ y,
+                                                                                  const long long* __restrict__ begins,
+                                                                                  const long long* __restrict__ ends,
+                                                                                  const int32_t* __restrict__ formats, int64_t total, int H,
+                                                                                  int W, long long* __restrict__ counts) {
+  const int job = blockIdx.y;
+  const int64_t begin = begins[job], end = ends[job];
+  const int fmt = formats[job];
+  if ((fmt & ~(EVCOL_T_I64 | EVCOL_XY_U16)) != 0) return;
+  if (begin < 0 || begin >= end || end > total) return;  // (begin == end: nothing to count)
+  const bool xy_u16 = (fmt & EVCOL_XY_U16) != 0;
+  const int64_t n = end - begin;
+  long long* __restrict__ c = counts + (size_t)job * H * W;
+  const uint2* __restrict__ x4 = (const uint2*)x;  // COLUMN_GROUP events
+  const uint2* __restrict__ y4 = (const uint2*)y;
+  const int64_t head = begin % COLUMN_GROUP, group0 = begin / COLUMN_GROUP;
+  const int64_t groups = (head + n + COLUMN_GROUP - 1) / COLUMN_GROUP;  // (the last one may be partial; it ends below capacity)
+  for (int64_t q = (int64_t)blockIdx.x * INGEST_THREADS + threadIdx.x; q < groups; q += (int64_t)gridDim.x * INGEST_THREADS) {
+    const uint2 xv = x4[group0 + q], yv = y4[group0 + q];
+    const unsigned xh[COLUMN_GROUP] = {xv.x & 0xffffu, xv.x >> 16, xv.y & 0xffffu, xv.y >> 16};
+    const unsigned yh[COLUMN_GROUP] = {yv.x & 0xffffu, yv.x >> 16, yv.y & 0xffffu, yv.y >> 16};
+#pragma unroll
+    for (int j = 0; j < COLUMN_GROUP; ++j) {
+      const int64_t k = q * COLUMN_GROUP + j - head;  // the event's number inside the range
+      if (k < 0 || k >= n) continue;
+      const int xs = column_coordinate(xh[j], xy_u16), ys = column_coordinate(yh[j], xy_u16);
+      if (!(xs < W && xs >= 0 && ys < H && ys >= 0)) continue;
+      atomicAdd((unsigned long long*)(c + (size_t)ys * W + xs), 1ull);
+    }
+  }
 }
 
 // ---- the loader finish (ess_event_grid_finish): what the reference loaders do to a grid between voxelising it and handing it to
@@ -1292,19 +1337,26 @@ extern "C" int ess_event_ingest_masked(const void* t, const void* x, const void*
   return ess_launch_status("event_ingest_masked(finish)");
 }
 
-// ---- the store source: ONE entry point for the four flavours, scatter only (acc keeps the sums for ess_event_grid_finish*)
+// ---- the store source: ONE entry point for the four flavours, scatter only (acc keeps the sums for ess_event_grid_finish*), and its
+// masked counterpart with both halves (ess_event_ingest_store); one routine checks the arguments of both (check_store)
 namespace {
 constexpr int STORE_SIGNED = 0, STORE_SEPARATE = 1, STORE_HISTOGRAM = 2, STORE_TRILINEAR = 3;  // (ESS_EVENT_STORE_* of include/ess_hip.h)
 static_assert(STORE_SIGNED == EVENT_REP_SIGNED && STORE_SEPARATE == EVENT_REP_SEPARATE && STORE_HISTOGRAM == EVENT_REP_HISTOGRAM,
               "the first three flavour words are the representation words");
-}  // namespace
 
-extern "C" int ess_event_scatter_store(const void* t, const void* x, const void* y, const void* p, const int64_t* starts,
-                                       const int32_t* counts, const int32_t* formats, int64_t capacity, int64_t total,
-                                       int64_t window_capacity, int32_t n_slots, int32_t channels, int32_t height, int32_t width,
-                                       void* acc, size_t acc_bytes, int32_t flavour, const float* maps, const int32_t* map_of,
-                                       int32_t n_maps, int32_t map_height, int32_t map_width, ess_stream_t stream) {
-  const char* what = "event_scatter_store";
+// the store's own sizes, as every entry point that reads its columns takes them
+int check_store_extent(const char* what, int64_t capacity, int64_t total) {
+  ESS_CHECK_ARG(capacity >= COLUMN_STRIDE_ALIGN && capacity <= STORE_MAX_CAPACITY && capacity % COLUMN_STRIDE_ALIGN == 0,
+                "%s: capacity=%lld events must be a multiple of %d in [%d, 2^40] (a window's last group of 4 events stays inside the columns)",
+                what, (long long)capacity, COLUMN_STRIDE_ALIGN, COLUMN_STRIDE_ALIGN);
+  ESS_CHECK_ARG(total >= 0 && total <= capacity, "%s: total=%lld events (0..capacity=%lld)", what, (long long)total, (long long)capacity);
+  return ESS_OK;
+}
+
+// with_out false: the scatter-only entry point, which has no out;  else out is nullable (NULL: scatter only)
+int check_store(const char* what, const void* t, const void* x, const void* y, const void* p, const int64_t* starts, const int32_t* counts,
+                const int32_t* formats, int64_t capacity, int64_t total, int64_t window_capacity, int32_t n_slots, int32_t channels,
+                int32_t height, int32_t width, const void* acc, size_t acc_bytes, const float* out, bool with_out, int32_t flavour) {
   ESS_CHECK_ARG(flavour >= STORE_SIGNED && flavour <= STORE_TRILINEAR,
                 "%s: flavour=%d (0 signed, 1 separate polarity, 2 histogram, 3 trilinear)", what, (int)flavour);
   int rc = check_representation(what, flavour == STORE_TRILINEAR ? EVENT_REP_SIGNED : flavour, channels);
@@ -1315,15 +1367,27 @@ extern "C" int ess_event_scatter_store(const void* t, const void* x, const void*
   ESS_CHECK_ARG(window_capacity >= 1 && window_capacity <= INGEST_MAX_CAPACITY,
                 "%s: window_capacity=%lld events per window (1..%lld: the int64 sums hold 2^22 contributions of magnitude 1 at scale 2^40)",
                 what, (long long)window_capacity, (long long)INGEST_MAX_CAPACITY);
-  ESS_CHECK_ARG(capacity >= COLUMN_STRIDE_ALIGN && capacity <= STORE_MAX_CAPACITY && capacity % COLUMN_STRIDE_ALIGN == 0,
-                "%s: capacity=%lld events must be a multiple of %d in [%d, 2^40] (a window's last group of 4 events stays inside the columns)",
-                what, (long long)capacity, COLUMN_STRIDE_ALIGN, COLUMN_STRIDE_ALIGN);
-  ESS_CHECK_ARG(total >= 0 && total <= capacity, "%s: total=%lld events (0..capacity=%lld)", what, (long long)total, (long long)capacity);
+  rc = check_store_extent(what, capacity, total);
+  if (rc) return rc;
   const size_t need = ess_event_ingest_workspace(n_slots, channels, height, width);
   ESS_CHECK_ARG(acc_bytes >= need, "%s: acc has %zu bytes, %zu are needed", what, acc_bytes, need);
-  ESS_CHECK_ARG((((uintptr_t)t | (uintptr_t)x | (uintptr_t)y | (uintptr_t)p | (uintptr_t)acc) & 15) == 0 && (((uintptr_t)starts) & 7) == 0 &&
-                    ((((uintptr_t)counts) | ((uintptr_t)formats)) & 3) == 0,
-                "%s: t, x, y, p and acc must be 16-byte, starts 8-byte, counts and formats 4-byte aligned", what);
+  ESS_CHECK_ARG((((uintptr_t)t | (uintptr_t)x | (uintptr_t)y | (uintptr_t)p | (uintptr_t)acc | (uintptr_t)out) & 15) == 0 &&
+                    (((uintptr_t)starts) & 7) == 0 && ((((uintptr_t)counts) | ((uintptr_t)formats)) & 3) == 0,
+                "%s: t, x, y, p%s acc must be 16-byte, starts 8-byte, counts and formats 4-byte aligned", what,
+                with_out ? ", out and" : " and");
+  return ESS_OK;
+}
+}  // namespace
+
+extern "C" int ess_event_scatter_store(const void* t, const void* x, const void* y, const void* p, const int64_t* starts,
+                                       const int32_t* counts, const int32_t* formats, int64_t capacity, int64_t total,
+                                       int64_t window_capacity, int32_t n_slots, int32_t channels, int32_t height, int32_t width,
+                                       void* acc, size_t acc_bytes, int32_t flavour, const float* maps, const int32_t* map_of,
+                                       int32_t n_maps, int32_t map_height, int32_t map_width, ess_stream_t stream) {
+  const char* what = "event_scatter_store";
+  int rc = check_store(what, t, x, y, p, starts, counts, formats, capacity, total, window_capacity, n_slots, channels, height, width, acc,
+                       acc_bytes, nullptr, false, flavour);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (flavour == STORE_TRILINEAR) {
     Rectify rect;
@@ -1342,25 +1406,102 @@ extern "C" int ess_event_scatter_store(const void* t, const void* x, const void*
                                                width, acc, st);
 }
 
-extern "C" int ess_event_hot_pixel_mask(const int64_t* sums, int32_t n, int32_t height, int32_t width, const int64_t* thresholds,
-                                        uint32_t* masks, int32_t mode, ess_stream_t stream) {
-  ESS_CHECK_ARG(sums && thresholds && masks, "event_hot_pixel_mask: null sums, thresholds or masks");
-  ESS_CHECK_ARG(n >= 1 && n <= 65535, "event_hot_pixel_mask: n=%d (1..65535)", (int)n);
+// the store source behind hot-pixel masks, both halves: every launch a Masked<Flavour> instantiation of event_scatter_store_kernel
+// (the unmasked ones above stay what they are); with out, the plain finish follows as behind the ring ingest
+extern "C" int ess_event_ingest_store(const void* t, const void* x, const void* y, const void* p, const int64_t* starts,
+                                      const int32_t* counts, const int32_t* formats, int64_t capacity, int64_t total,
+                                      int64_t window_capacity, int32_t n_slots, int32_t channels, int32_t height, int32_t width, void* acc,
+                                      size_t acc_bytes, float* out, int32_t flavour, const float* maps, const int32_t* map_of,
+                                      int32_t n_maps, int32_t map_height, int32_t map_width, const uint32_t* masks, const int32_t* mask_of,
+                                      int32_t n_masks, int32_t mask_height, int32_t mask_width, ess_stream_t stream) {
+  const char* what = "event_ingest_store";
+  int rc = check_store(what, t, x, y, p, starts, counts, formats, capacity, total, window_capacity, n_slots, channels, height, width, acc,
+                       acc_bytes, out, true, flavour);
+  if (rc) return rc;
+  ESS_CHECK_ARG(flavour == STORE_TRILINEAR || (maps == nullptr && map_of == nullptr && n_maps == 0),
+                "%s: maps, map_of and n_maps belong to flavour=3 (trilinear): flavour=%d needs them null and 0", what, (int)flavour);
+  Rectify rect = {nullptr, nullptr, 0, 1, 1};
+  if (flavour == STORE_TRILINEAR) {
+    rc = check_rectify(what, maps, map_of, n_maps, map_height, map_width, rect);
+    if (rc) return rc;
+  }
+  Masks m;
+  rc = check_masks(what, masks, mask_of, n_masks, mask_height, mask_width, m);
+  if (rc) return rc;
+  ESS_CHECK_ARG((((uintptr_t)mask_of) & 3) == 0, "%s: mask_of must be 4-byte aligned", what);
+  hipStream_t st = (hipStream_t)stream;
+  const char* status = out ? "event_ingest_store(scatter)" : what;
+  if (flavour == STORE_TRILINEAR)
+    rc = launch_scatter_store<Masked<TrilinearFlavour>>(status, t, x, y, p, starts, counts, formats, total, window_capacity, n_slots, channels,
+                                                        height, width, acc, st, m, rect);
+  else if (flavour == STORE_SEPARATE)
+    rc = launch_scatter_store<Masked<SeparateFlavour>>(status, t, x, y, p, starts, counts, formats, total, window_capacity, n_slots, channels,
+                                                       height, width, acc, st, m);
+  else if (flavour == STORE_HISTOGRAM)
+    rc = launch_scatter_store<Masked<HistogramFlavour>>(status, t, x, y, p, starts, counts, formats, total, window_capacity, n_slots, channels,
+                                                        height, width, acc, st, m);
+  else
+    rc = launch_scatter_store<Masked<TemporalFlavour>>(status, t, x, y, p, starts, counts, formats, total, window_capacity, n_slots, channels,
+                                                       height, width, acc, st, m);
+  if (rc || !out) return rc;
+  launch_finish<false>(counts, n_slots, (int64_t)channels * height * width, acc, nullptr, out, st);
+  return ess_launch_status("event_ingest_store(finish)");
+}
+
+extern "C" int ess_event_store_pixel_counts(const void* x, const void* y, int64_t capacity, int64_t total, const int64_t* begins,
+                                            const int64_t* ends, const int32_t* formats, int32_t n, int32_t height, int32_t width,
+                                            int64_t* counts, ess_stream_t stream) {
+  const char* what = "event_store_pixel_counts";
+  ESS_CHECK_ARG(x && y && begins && ends && formats && counts, "%s: null x, y, begins, ends, formats or counts", what);
+  ESS_CHECK_ARG(n >= 1 && n <= 65535, "%s: n=%d (1..65535)", what, (int)n);
   ESS_CHECK_ARG(height >= 1 && height <= MASK_MAX_SIDE && width >= 1 && width <= MASK_MAX_SIDE,
-                "event_hot_pixel_mask: height=%d width=%d (1..32768 each: the sensor's size)", (int)height, (int)width);
-  ESS_CHECK_ARG(mode == MASK_REPLACE || mode == MASK_OR, "event_hot_pixel_mask: mode=%d (0 replace, 1 or)", (int)mode);
+                "%s: height=%d width=%d (1..32768 each: the sensor's size)", what, (int)height, (int)width);
+  int rc = check_store_extent(what, capacity, total);
+  if (rc) return rc;
+  ESS_CHECK_ARG((((uintptr_t)x | (uintptr_t)y) & 15) == 0 && ((((uintptr_t)begins) | ((uintptr_t)ends) | ((uintptr_t)counts)) & 7) == 0 &&
+                    (((uintptr_t)formats) & 3) == 0,
+                "%s: x and y must be 16-byte, begins, ends and counts 8-byte, formats 4-byte aligned", what);
+  // the grid follows the store's capacity, capped as the scatters': a range of any length is strided over
+  hipLaunchKernelGGL(event_store_pixel_counts_kernel, dim3(scatter_blocks(capacity), (unsigned)n), dim3(INGEST_THREADS), 0,
+                     (hipStream_t)stream, (const unsigned short*)x, (const unsigned short*)y, (const long long*)begins,
+                     (const long long*)ends, formats, total, (int)height, (int)width, (long long*)counts);
+  return ess_launch_status(what);
+}
+
+namespace {
+// counts -> masks behind ess_event_hot_pixel_mask (PLAIN false: the histogram flavour's two planes at scale 2^40) and
+// ess_event_count_mask (PLAIN true: plain counts, one plane); sums_name: what the entry point calls its first argument
+template <bool PLAIN>
+int count_mask(const char* what, const char* sums_name, const int64_t* sums, int32_t n, int32_t height, int32_t width,
+               const int64_t* thresholds, uint32_t* masks, int32_t mode, hipStream_t st) {
+  ESS_CHECK_ARG(sums && thresholds && masks, "%s: null %s, thresholds or masks", what, sums_name);
+  ESS_CHECK_ARG(n >= 1 && n <= 65535, "%s: n=%d (1..65535)", what, (int)n);
+  ESS_CHECK_ARG(height >= 1 && height <= MASK_MAX_SIDE && width >= 1 && width <= MASK_MAX_SIDE,
+                "%s: height=%d width=%d (1..32768 each: the sensor's size)", what, (int)height, (int)width);
+  ESS_CHECK_ARG(mode == MASK_REPLACE || mode == MASK_OR, "%s: mode=%d (0 replace, 1 or)", what, (int)mode);
   ESS_CHECK_ARG(((((uintptr_t)sums) | ((uintptr_t)masks)) & 15) == 0 && (((uintptr_t)thresholds) & 7) == 0,
-                "event_hot_pixel_mask: sums and masks must be 16-byte, thresholds 8-byte aligned");
+                "%s: %s and masks must be 16-byte, thresholds 8-byte aligned", what, sums_name);
   const int64_t chunks = (int64_t)height * ((width + 63) >> 6);  // (<= 2^24)
   const dim3 grid((unsigned)ceil_div64(chunks, (int64_t)MASK_WAVES), (unsigned)n);
-  hipStream_t st = (hipStream_t)stream;
   if (mode == MASK_OR)
-    hipLaunchKernelGGL(hot_pixel_mask_kernel<true>, grid, dim3(INGEST_THREADS), 0, st, (const long long*)sums, (const long long*)thresholds,
-                       (int)height, (int)width, masks);
+    hipLaunchKernelGGL((hot_pixel_mask_kernel<true, PLAIN>), grid, dim3(INGEST_THREADS), 0, st, (const long long*)sums,
+                       (const long long*)thresholds, (int)height, (int)width, masks);
   else
-    hipLaunchKernelGGL(hot_pixel_mask_kernel<false>, grid, dim3(INGEST_THREADS), 0, st, (const long long*)sums, (const long long*)thresholds,
-                       (int)height, (int)width, masks);
-  return ess_launch_status("event_hot_pixel_mask");
+    hipLaunchKernelGGL((hot_pixel_mask_kernel<false, PLAIN>), grid, dim3(INGEST_THREADS), 0, st, (const long long*)sums,
+                       (const long long*)thresholds, (int)height, (int)width, masks);
+  return ess_launch_status(what);
+}
+}  // namespace
+
+extern "C" int ess_event_hot_pixel_mask(const int64_t* sums, int32_t n, int32_t height, int32_t width, const int64_t* thresholds,
+                                        uint32_t* masks, int32_t mode, ess_stream_t stream) {
+  return count_mask<false>("event_hot_pixel_mask", "sums", sums, n, height, width, thresholds, masks, mode, (hipStream_t)stream);
+}
+
+// ess_event_hot_pixel_mask's rule on plain counts: int64 [n][height][width], no 2^40 scale, one plane
+extern "C" int ess_event_count_mask(const int64_t* counts, int32_t n, int32_t height, int32_t width, const int64_t* thresholds,
+                                    uint32_t* masks, int32_t mode, ess_stream_t stream) {
+  return count_mask<true>("event_count_mask", "counts", counts, n, height, width, thresholds, masks, mode, (hipStream_t)stream);
 }
 
 // workspace: [n_slots] GridStat, then [n_slots][grid_stats_blocks][3] 8-byte partials

@@ -180,6 +180,34 @@ class EventStore:
         d['table'][rid].copy_(d['row'], non_blocking=True)
         d['row_done'].record()
 
+    # ---- hot-pixel calibration (datasets.hot_pixels.HotPixelMask.from_store checks the arguments; nothing of the store is written)
+    def range_time_span(self, rid, begin, end):
+        """float(t of event end - 1) - float(t of event begin) of recording `rid`, indices relative to the recording, in the unit of
+        its time column (0.0 for an empty range): one download of two time words"""
+        r = self._rec(rid, 'range_time_span')
+        if end <= begin:
+            return 0.0
+        t = self.columns[0]
+        words = torch.cat([t[r[0] + begin:r[0] + begin + 1], t[r[0] + end - 1:r[0] + end]]).cpu().numpy()
+        times = words if r[2] & hip.EVCOL_T_I64 else words.view(np.float64)
+        return float(times[1]) - float(times[0])
+
+    def count_mask_words(self, rid, begin, end, size, threshold):
+        """the events begin .. end - 1 of recording `rid` (relative indices) counted per pixel of a size = (h, w) sensor, and the
+        pixels with MORE than `threshold` events as mask words, host uint32 [h, ceil(w / 32)]: one zero fill, hip.
+        event_store_pixel_counts, hip.event_count_mask, one download.  Plain int64 counts: a pixel may hold any number of events."""
+        r = self._rec(rid, 'count_mask_words')
+        h, w = size
+        x, y = self.columns[1], self.columns[2]
+        dev = x.device
+        job = torch.tensor([r[0] + begin, r[0] + end, min(int(threshold), 1 << 62)], dtype=torch.int64).to(dev)
+        fmt = torch.tensor([r[2]], dtype=torch.int32).to(dev)
+        counts = torch.zeros(1, h, w, dtype=torch.int64, device=dev)
+        hip.event_store_pixel_counts(x, y, job[0:1], job[1:2], fmt, counts, self.n_events)
+        words = torch.empty(1, h, hip.mask_words(w), dtype=torch.int32, device=dev)
+        hip.event_count_mask(counts, job[2:3], words, hip.MASK_REPLACE)
+        return words[0].cpu().numpy().view(np.uint32)
+
     # ---- the checks of an upload: nothing is written
     @staticmethod
     def _packets(what, columns_or_packets, fmt, last_t):

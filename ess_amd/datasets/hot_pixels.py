@@ -78,6 +78,46 @@ class HotPixelMask:
             return cls.from_locations(np.zeros((0, 2), dtype=np.int64), height, width)
         return cls.from_locations(np.loadtxt(path, delimiter=',', ndmin=2), height, width)
 
+    @classmethod
+    def from_store(cls, store, recording, size, max_events_per_pixel=None, max_rate_hz=None, begin=None, end=None):
+        """A mask calibrated from a recording of a device EventStore, by MultiStreamSegmenter.calibrate_hot_pixels' rule: a pixel of
+        the size = (h, w) sensor is hot when it fired MORE than max_events_per_pixel=k events, or more than
+        floor(max_rate_hz * (t_last - t_first)) events, the times of the range's first and last event in the unit of the
+        recording's time column -- exactly one of the two limits.  begin, end: event indices relative to the recording (default:
+        all of it).  The counts are plain 64-bit integers (hip.event_store_pixel_counts): a whole recording fits, where the
+        histogram sums of the ring calibration end at 2^22 events a pixel.  Outside any capture; the store is not modified.
+        Refused with ValueError before any device call: an unknown recording, a range outside it, both limits or neither, a size
+        outside 1 .. 32768."""
+        from .event_store import EventStore
+        what = 'HotPixelMask.from_store'
+        if not isinstance(store, EventStore):
+            raise ValueError(f'{what}: store must be an EventStore, got {type(store).__name__}')
+        is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))  # noqa: E731
+        if not is_int(recording) or not 0 <= recording < store.n_recordings:
+            raise ValueError(f'{what}: recording {recording!r} of {store.n_recordings}')
+        if not isinstance(size, (tuple, list)) or len(size) != 2:
+            raise ValueError(f'{what}: size={size!r} must be (h, w), the sensor\'s size')
+        h, w = _side('size[0]', size[0]), _side('size[1]', size[1])
+        if (max_events_per_pixel is None) == (max_rate_hz is None):
+            raise ValueError(f'{what}: give max_events_per_pixel=k or max_rate_hz=r, exactly one of the two')
+        by_rate = max_rate_hz is not None
+        limit = max_rate_hz if by_rate else max_events_per_pixel
+        ok = isinstance(limit, (int, float, np.integer, np.floating)) if by_rate else isinstance(limit, (int, np.integer))
+        if isinstance(limit, (bool, np.bool_)) or not ok or not 0 <= limit < float('inf'):
+            raise ValueError(f'{what}: the limit {limit!r} must be a non-negative ' + ('number' if by_rate else 'int'))
+        first, last = store.extent(int(recording))
+        n = last - first
+        b, e = 0 if begin is None else begin, n if end is None else end
+        if not is_int(b) or not is_int(e) or not 0 <= b <= e <= n:
+            raise ValueError(f'{what}: the range begin={begin!r}, end={end!r} lies outside recording {recording} of {n} events '
+                             '(0 <= begin <= end <= its events, relative to the recording)')
+        import torch
+        if torch.cuda.is_current_stream_capturing():
+            raise ValueError(f'{what}: a calibration downloads its mask: it runs outside any capture')
+        b, e = int(b), int(e)
+        threshold = int(np.floor(float(limit) * store.range_time_span(int(recording), b, e))) if by_rate else int(limit)
+        return cls.from_words(store.count_mask_words(int(recording), b, e, (h, w), threshold), h, w)
+
     def to_bool(self):
         bits = (self.words[:, :, None] >> np.arange(32, dtype=np.uint32)) & np.uint32(1)
         return bits.reshape(self.height, -1)[:, :self.width].astype(np.bool_)

@@ -84,6 +84,7 @@ EXPORTS = [
     'ess_event_scatter_ring_rep', 'ess_event_ingest_ring_rep', 'ess_event_ingest_columns_rep',
     'ess_event_ingest_masked', 'ess_event_hot_pixel_mask',
     'ess_event_scatter_store', 'ess_event_store_windows',
+    'ess_event_ingest_store', 'ess_event_store_pixel_counts', 'ess_event_count_mask',
     'ess_recon_post_frame', 'ess_recon_post_bounds', 'ess_event_preview',
     'ess_viz_semseg', 'ess_viz_events', 'ess_viz_overlay',
 ]
@@ -205,6 +206,9 @@ def lib():
             'ess_event_hot_pixel_mask': [P, I, I, I, P, P, I, P],
             'ess_event_scatter_store': [P, P, P, P, P, P, P, I64, I64, I64, I, I, I, I, P, c_size_t, I, P, P, I, I, I, P],
             'ess_event_store_windows': [P, I64, I64, P, I, P, P, P, I, I, I, I64, I64, P, P, P, P, P, P],
+            'ess_event_ingest_store': [P, P, P, P, P, P, P, I64, I64, I64, I, I, I, I, P, c_size_t, P, I, P, P, I, I, I, P, P, I, I, I, P],
+            'ess_event_store_pixel_counts': [P, P, I64, I64, P, P, P, I, I, I, P, P],
+            'ess_event_count_mask': [P, I, I, I, P, P, I, P],
             'ess_recon_post_frame': [P, P, F, F, P, P, P, I, I, I, I, I, I, I, P],
             'ess_recon_post_bounds': [P, P, F, F, I, I, I, P, c_size_t, P, P, I, P, P],
             'ess_event_preview': [P, P, I, I, I, I, I, I, P],
@@ -1514,6 +1518,107 @@ def event_store_windows(t, table, recording, bounds, rule, sequence_steps, start
                                          int(rule), n_per_window, window_capacity, P(starts), P(counts), P(formats), P(map_of), P(flags),
                                          stream()), 'ess_' + fn)
     return flags
+
+
+def event_ingest_store(t, x, y, p, starts, counts, formats, out, flavour, total, window_capacity, masks=None, mask_of=None,
+                       mask_size=None, maps=None, map_of=None, acc=None):
+    """event_ingest_masked on the device event store: the four flavours, both halves, with or without hot-pixel masks.
+    t .. formats, flavour, total, window_capacity, maps, map_of: as event_scatter_store takes them, with its slot refusals.
+    out: fp32 [n_slots, C, H, W], returned -- the plain finish follows the scatter, the bits of event_ingest_ring* /
+    event_ingest_ring_rep on the same events, acc (int64 [n_slots, C, H, W], all zero before; None: allocated and zeroed here) all zero again --
+    or None: scatter only, acc (then required) keeps the sums for event_grid_finish*, and is returned.
+    masks, mask_of, mask_size: as event_ingest_masked takes them -- a hot event is dropped on its raw (x, y) before a rectify map
+    sees it, the window's time base comes from its first and last event whether masked or not, a mask word that is neither
+    MASK_NONE nor in 0 .. n_masks - 1 leaves the slot empty.  masks=None and mask_of=None: event_scatter_store's sums, bit for bit."""
+    fn = 'event_ingest_store'
+    cols = (('t', t), ('x', x), ('y', y), ('p', p))
+    words = (('starts', starts), ('counts', counts), ('formats', formats))
+    if out is None and acc is None:
+        raise EssHipError(f'{fn}: out=None (scatter only) needs acc, the int64 [n_slots, C, H, W] sums it leaves')
+    named = cols + words + ((('out', out),) if out is not None else ()) + ((('acc', acc),) if acc is not None else ())
+    _are_tensors(fn, named)
+    n_slots, C, H, W = _ingest_out(fn, out, 'n_slots') if out is not None else _finish_acc(fn, acc, 'H, W')
+    if isinstance(flavour, bool) or flavour not in _EVENT_STORE_FLAVOURS:
+        raise EssHipError(f'{fn}: flavour={flavour!r} must be EVENT_STORE_SIGNED, _SEPARATE, _HISTOGRAM or _TRILINEAR')
+    if flavour != EVENT_STORE_TRILINEAR:
+        _event_rep_of(fn, int(flavour), C, 'out' if out is not None else 'acc')
+        if maps is not None or map_of is not None:
+            raise EssHipError(f'{fn}: maps / map_of belong to flavour=EVENT_STORE_TRILINEAR')
+    capacity, total = _store_columns(fn, cols, total)
+    window_capacity = _int_in(fn, 'window_capacity', window_capacity, 1, INGEST_MAX_CAPACITY)
+    _formed_words(fn, words[:1], torch.int64, (n_slots,))
+    _formed_words(fn, words[1:], torch.int32, (n_slots,))
+    form = _mask_form(fn, masks, mask_of, mask_size, n_slots)
+    if out is not None:
+        acc = _ingest_acc(fn, named, acc, out)
+    else:
+        _on_device(fn, named)
+    dev = acc.device
+    rect = _rectify_args(fn, maps, map_of, n_slots, dev) if flavour == EVENT_STORE_TRILINEAR else (c_void_p(0), c_void_p(0), 0, 1, 1)
+    mask = _mask_args(fn, masks, mask_of, form, n_slots, dev)
+    _check(lib().ess_event_ingest_store(*(c_void_p(v.data_ptr()) for _, v in cols), ptr(starts, torch.int64), ptr(counts, torch.int32),
+                                        ptr(formats, torch.int32), capacity, total, window_capacity, n_slots, C, H, W,
+                                        c_void_p(acc.data_ptr()), acc.numel() * 8, c_void_p(0 if out is None else out.data_ptr()),
+                                        int(flavour), *rect, *mask, stream()), 'ess_' + fn)
+    return out if out is not None else acc
+
+
+def event_store_pixel_counts(x, y, begins, ends, formats, counts, total):
+    """Plain per-pixel event counts of index ranges of the device event store.  x, y: the store's coordinate columns, device int16 /
+    uint16 [capacity].  begins, ends: device int64 [n], ABSOLUTE event indices, job j counts the events begins[j] .. ends[j] - 1;
+    formats: device int32 [n], the EVCOL_* word the job's coordinates are decoded under.  counts: device int64 [n, H, W], ADDED TO
+    and returned: one per event whose decoded (x, y) lies inside H x W, both polarities together, whatever the range's length (no
+    2^22 bound: these are not the ingest's scaled sums).  A range outside [0, total], begin > end or an unknown format bit: the job
+    counts nothing.  One launch shaped by the capacity and n alone, every word read on the device: capturable."""
+    fn = 'event_store_pixel_counts'
+    named = (('x', x), ('y', y), ('begins', begins), ('ends', ends), ('formats', formats), ('counts', counts))
+    _are_tensors(fn, named)
+    if x.dim() != 1 or x.shape[0] < EVCOL_STRIDE_ALIGN or x.shape[0] % EVCOL_STRIDE_ALIGN or x.shape[0] > EVENT_STORE_MAX_CAPACITY:
+        raise EssHipError(f'{fn}: x must be [capacity], capacity a multiple of {EVCOL_STRIDE_ALIGN} in [{EVCOL_STRIDE_ALIGN}, 2^40], '
+                          f'got {tuple(x.shape)}')
+    for name, v in named[:2]:
+        if v.dtype not in _EVCOL_DTYPES[name] or v.shape != x.shape:
+            raise EssHipError(f'{fn}: {name} must be {" / ".join(str(d) for d in _EVCOL_DTYPES[name])} '
+                              f'{list(x.shape)}, got {v.dtype}{tuple(v.shape)}')
+    total = _int_in(fn, 'total', total, 0, x.shape[0])
+    if counts.dim() != 3 or counts.dtype != torch.int64 or counts.numel() == 0 or not 1 <= counts.shape[0] <= 65535 or \
+            counts.shape[1] > MASK_MAX_SIDE or counts.shape[2] > MASK_MAX_SIDE:
+        raise EssHipError(f'{fn}: counts must be a non-empty int64 [n, H, W] tensor, n in 1..65535, H and W in 1..{MASK_MAX_SIDE}, '
+                          f'got {counts.dtype}{tuple(counts.shape)}')
+    n, H, W = counts.shape
+    _formed_words(fn, named[2:4], torch.int64, (n,))
+    _formed_words(fn, named[4:5], torch.int32, (n,))
+    _on_device(fn, named)
+    _check(lib().ess_event_store_pixel_counts(c_void_p(x.data_ptr()), c_void_p(y.data_ptr()), x.shape[0], total, ptr(begins, torch.int64),
+                                              ptr(ends, torch.int64), ptr(formats, torch.int32), n, H, W, c_void_p(counts.data_ptr()),
+                                              stream()), 'ess_' + fn)
+    return counts
+
+
+def event_count_mask(counts, thresholds, masks, mode=MASK_REPLACE):
+    """event_hot_pixel_mask's rule on PLAIN counts.  counts: device int64 [n, H, W], what event_store_pixel_counts leaves (one per
+    event, no 2^40 scale, read only).  thresholds: device int64 [n], in events: >= 0 -- bit (y, x) of masks[i] is set iff
+    counts[i, y, x] > thresholds[i]; < 0 -- masks[i] is neither read nor written.  masks, mode: as event_hot_pixel_mask takes them
+    (the same kernel, the same word layout and tail-bit rule).  -> masks"""
+    fn = 'event_count_mask'
+    named = (('counts', counts), ('thresholds', thresholds), ('masks', masks))
+    _are_tensors(fn, named)
+    if counts.dim() != 3 or counts.dtype != torch.int64 or counts.numel() == 0:
+        raise EssHipError(f'{fn}: counts must be a non-empty int64 [n, H, W] tensor (plain per-pixel counts), '
+                          f'got {counts.dtype}{tuple(counts.shape)}')
+    n, H, W = counts.shape
+    if H > MASK_MAX_SIDE or W > MASK_MAX_SIDE:
+        raise EssHipError(f'{fn}: counts of {H} x {W} pixels: a side is 1..{MASK_MAX_SIDE}')
+    if thresholds.dtype != torch.int64 or tuple(thresholds.shape) != (n,):
+        raise EssHipError(f'{fn}: thresholds must be int64 [{n}], got {thresholds.dtype}{tuple(thresholds.shape)}')
+    if _mask_tensor(fn, masks, (H, W), n)[0] != n:
+        raise EssHipError(f'{fn}: masks must hold {n} masks, one per plane of counts, got {tuple(masks.shape)}')
+    if isinstance(mode, bool) or mode not in (MASK_REPLACE, MASK_OR):
+        raise EssHipError(f'{fn}: mode={mode!r} must be MASK_REPLACE or MASK_OR')
+    _on_device(fn, named)
+    _check(lib().ess_event_count_mask(c_void_p(counts.data_ptr()), n, H, W, c_void_p(thresholds.data_ptr()), c_void_p(masks.data_ptr()),
+                                      int(mode), stream()), 'ess_' + fn)
+    return masks
 
 
 def event_grid_finish(counts, acc, out, crop_rows=None, resize=None, normalize=GRID_NORM_NONE):

@@ -36,6 +36,52 @@ class _SequenceStage(_RingStage):
         self.gt, self.gt_np = gt, gt.numpy()
 
 
+class _RecordingMasks:
+    """The hot-pixel masks of a store-fed segmenter, keyed by RECORDING (a mask belongs to a sensor, and a lane of a round may name any
+    recording): ONE static device buffer words int32 [n_slots, mask_h, ceil(mask_w / 32)] under the capture, and the host's books --
+    which HotPixelMask each slot holds (entries that are the same object share a slot) and slot_of, recording -> slot."""
+
+    def __init__(self, n_slots, size, device):
+        self.n_slots, self.size = n_slots, (int(size[0]), int(size[1]))
+        self.words = torch.zeros(n_slots, self.size[0], hip.mask_words(self.size[1]), dtype=torch.int32, device=device)
+        self.held = [None] * n_slots
+        self.slot_of = {}
+
+    @staticmethod
+    def check(what, recording, mask, size):
+        from .datasets.hot_pixels import HotPixelMask
+        if isinstance(recording, bool) or not isinstance(recording, (int, np.integer)) or recording < 0:
+            raise hip.EssHipError(f'{what}: recording {recording!r} must be a non-negative int (a recording of the store)')
+        if mask is not None and not isinstance(mask, HotPixelMask):
+            raise hip.EssHipError(f'{what}: recording {recording} needs a datasets.hot_pixels.HotPixelMask or None, got {type(mask).__name__}')
+        if mask is not None and (mask.height, mask.width) != tuple(size):
+            raise hip.EssHipError(f'{what}: the mask of recording {recording} is {mask.height} x {mask.width}, the masks of this segmenter '
+                                  f'{size[0]} x {size[1]} (the rectify maps\' size, else the size the events are voxelised at)')
+
+    def assign(self, recording, mask):
+        """recording reads `mask` (None: none) from the next round on; refused, nothing changed, when no slot is free"""
+        recording = int(recording)
+        if mask is None:
+            self.slot_of.pop(recording, None)
+            return
+        for k, o in enumerate(self.held):
+            if o is mask:
+                self.slot_of[recording] = k
+                return
+        named = {k for r, k in self.slot_of.items() if r != recording}
+        free = [k for k in range(self.n_slots) if k not in named]
+        if not free:
+            raise hip.EssHipError(f'set_recording_hot_pixels: all mask_slots={self.n_slots} hold masks that recordings read: build the '
+                                  'segmenter with more mask_slots, or take a mask from a recording first (None)')
+        k = free[0]
+        self.words[k].copy_(torch.from_numpy(mask.words.view(np.int32).copy()))  # (outside any capture)
+        self.held[k] = mask
+        self.slot_of[recording] = k
+
+    def word(self, recording):
+        return self.slot_of.get(int(recording), hip.MASK_NONE)
+
+
 class _SequenceFeed:
     """one stream's side of the feed: the events fed so far (absolute index of the next one; position in the ring = index mod R),
     the last time fed, the dtypes of its first packet with the format word they give, and the uploads out of the pinned mirror
@@ -89,12 +135,33 @@ class SequenceSegmenter:
     hot_pixel_masks=[...]: as MultiStreamSegmenter's -- per stream None or a HotPixelMask of the sensor's size (with every entry
     None: the rectify maps' size, else the size the events are voxelised at), applied to the raw events by hip.event_ingest_masked
     on both ingest heads (with a loader grid: its scatter half, out=None, in front of hip.event_grid_finish); every one of a
-    stream's T windows reads that stream's mask.  set_hot_pixels(stream, mask | None) changes it between rounds."""
+    stream's T windows reads that stream's mask.  set_hot_pixels(stream, mask | None) changes it between rounds.
+
+    store=EventStore (datasets/event_store.py), with window_events=N or window_duration=d and window_capacity= as
+    EventBatchBuilder(store=) takes them: the rounds are cut on the device out of recordings that lie in device memory already.  No
+    rings and no pinned mirrors exist (ring_capacity is refused; feed, fed and drop_feed refuse), and a round is
+    segment_at(samples=[StoreSample | None per lane], labels=None).  A LANE is a batch position, not a sensor: any lane may name any
+    recording, two lanes may name the same one; n_streams is the number of lanes.  The samples select the window rule -- t_end with
+    window_events: the count rule by time, end: by index, t_end with window_duration: the fixed-duration rule -- and all samples of
+    a round share it; one capture per rule serves every round.  Inside the capture: hip.event_store_windows over the S lanes (slot
+    b T + i), the slot words transposed on the device to the order the encoder reads the grids in (slot i S + s; the grids are not
+    moved), hip.event_ingest_store (with a loader grid: its scatter half in front of hip.event_grid_finish), then the round as
+    above.  rectify_maps=[...] is then a list of maps and StoreSample.map names an entry.  Ground truth: StoreSample.label, a row of
+    the store's labels (store.label_hw must be out_hw; gathered on the device), or labels=[...] from the host, one of the two per
+    lane.  last_flags: device int32 [S], hip.EVENT_STORE_FLAG_* as event_store_windows sets them (a lane given None: RANGE); a
+    flagged sample or an idle lane does not score -- its ground-truth row is the ignore value, decided on the device from the flag
+    word -- and valid[s] says a sample was given.  A round uploads one pinned table of 40 bytes a lane (8 T + 40 under the duration
+    rule) and the host labels that were given.  Hot pixels belong to sensors, so here they are keyed by recording:
+    recording_hot_pixels={recording: HotPixelMask}, mask_slots=M static slots under the capture (entries that are the same object
+    share one), set_recording_hot_pixels(recording, mask | None) between rounds without re-capture; hot_pixel_masks= and
+    set_hot_pixels are refused.  Everything is refused before the first device allocation: a store on another device, neither or
+    both of window_events / window_duration, window_capacity outside [window_events or 1, 2^22], labels of another size."""
 
     def __init__(self, encoder, decoder, height, width, options, n_streams, sequence_steps=None, window_events=None, ring_capacity=None,
                  voxel='temporal', rectify_maps=None, graph=False, copy=True, palette=None, want_confidence=False, out_hw=None,
                  ignore_index=255, device=None, window_duration=None, grid_hw=None, grid_rows=None, grid_resize=None,
-                 grid_normalize=None, representation=None, hot_pixel_masks=None):
+                 grid_normalize=None, representation=None, hot_pixel_masks=None, store=None, window_capacity=None,
+                 recording_hot_pixels=None, mask_slots=16):
         if not isinstance(n_streams, int) or isinstance(n_streams, bool) or n_streams < 1:
             raise hip.EssHipError(f'n_streams={n_streams!r}: a positive number of streams is needed')
         T = sequence_steps
@@ -104,6 +171,12 @@ class SequenceSegmenter:
             raise hip.EssHipError('give window_events=N or window_duration=d, not both: a sequence is cut by count or by time')
         if window_events is None and window_duration is None:
             raise hip.EssHipError('window_events is needed: the events per window (DSEC: nr_events_window = 100000)')
+        self.store = store
+        if store is None and (window_capacity is not None or recording_hot_pixels is not None):
+            raise hip.EssHipError('window_capacity / recording_hot_pixels belong to a store-fed segmenter: they need store=')
+        if store is not None:
+            self._check_store(store, device, ring_capacity, hot_pixel_masks, window_events, window_duration, window_capacity, mask_slots,
+                              out_hw if out_hw is not None else (height, width))
         self._loader_grid = any(v is not None for v in (grid_hw, grid_rows, grid_resize, grid_normalize))
         Hs, Ws, self._grid = height, width, None
         if self._loader_grid:
@@ -112,7 +185,7 @@ class SequenceSegmenter:
             d = window_duration
             if isinstance(d, bool) or not isinstance(d, (int, float, np.integer, np.floating)) or not d > 0 or d == float('inf'):
                 raise hip.EssHipError(f'window_duration={d!r}: the duration of one window in the unit of t, a positive number')
-            if ring_capacity is None:
+            if ring_capacity is None and store is None:
                 raise hip.EssHipError('window_duration needs ring_capacity: no event count follows from a duration')
             N_w = 0
             _event_capacity(1, Hs, Ws)  # (the coordinates must fit the columns)
@@ -124,16 +197,22 @@ class SequenceSegmenter:
         if not isinstance(ignore_index, int) or isinstance(ignore_index, bool) or not 0 <= ignore_index <= 255:
             raise hip.EssHipError(f'ignore_index={ignore_index!r}: a value of the uint8 ground truth is needed')
         R = 2 * T * N_w if ring_capacity is None else ring_capacity
-        if not isinstance(R, int) or isinstance(R, bool) or R < max(1, T * N_w) or hip.event_column_stride(R) > hip.INGEST_MAX_CAPACITY:
+        # (with a store no ring exists: the windows are read where the store keeps them)
+        if store is None and (not isinstance(R, int) or isinstance(R, bool) or R < max(1, T * N_w) or
+                              hip.event_column_stride(R) > hip.INGEST_MAX_CAPACITY):
             raise hip.EssHipError(f'ring_capacity={R!r}: events per stream the ring holds, an int in [sequence_steps * window_events = '
                                   f'{T * N_w}, {hip.INGEST_MAX_CAPACITY}] (default: twice the lower bound)')
         self.n_streams, self.sequence_steps, self.window_events = n_streams, T, (N_w if window_duration is None else None)
-        self.ring_capacity = R = hip.event_column_stride(R)
+        self.ring_capacity = R = None if store is not None else hip.event_column_stride(R)
         self.voxel, self.ignore_index = voxel, ignore_index
         self.representation = representation
         self._rep = _event_representation(representation, voxel, rectify_maps, encoder.num_bins)
         if hot_pixel_masks is not None:
             _check_hot_pixel_masks(hot_pixel_masks, n_streams, None)  # (the last refusal before the device)
+        if store is not None:  # (the store's own last refusals before the device: the maps' list, the masks' sizes)
+            maps_host, self._map_entry = _rectify_maps(rectify_maps, voxel, len(rectify_maps) if isinstance(rectify_maps, (list, tuple)) else 0)
+            mask_size = tuple(maps_host.shape[1:3]) if maps_host is not None else (Hs, Ws)
+            hot_given = self._check_recording_masks(recording_hot_pixels, mask_size, mask_slots)
         self.copy_outputs = bool(copy)
         self.device = device if device is not None else torch.device('cuda:0')
         self.model = encoder.to(self.device).eval()
@@ -154,33 +233,278 @@ class SequenceSegmenter:
         self.n_captures = 0
         self.compute = hip.compute_name()
         self.num_classes = K = int(self.decoder.decoder_scale_5[0].weight.shape[0])
+        S, dev = n_streams, self.device
+        self._hot = None
+        self._g = self._outputs = None
+        self._in = torch.zeros(T * S, self.num_bins, height, width, dtype=torch.float32, device=dev)
+        self._acc = torch.zeros(T * S, self.num_bins, Hs, Ws, dtype=torch.int64, device=dev)  # (the size the events are voxelised at)
+        self._gt = torch.full((S,) + self.out_hw, ignore_index, dtype=torch.uint8, device=dev)
+        self.confusion = torch.zeros(S, K, K, dtype=torch.int64, device=dev)
+        if store is not None:  # no rings, no mirrors, no ring words: one small table a round
+            self._maps = None if maps_host is None else maps_host.to(dev)
+            self._feeds = self._ring = self._ring_host = self._ring_np = self._words = None
+            self._stage, self._gt_live = [], [False] * S
+            self._rec_hot = _RecordingMasks(mask_slots, mask_size, dev)
+            for r, m in hot_given:
+                self._rec_hot.assign(r, m)
+            self._allocate_store()
+            return
         maps, self._map_of = _rectify_maps(rectify_maps, voxel, n_streams)
         self._maps = None if maps is None else maps.to(self.device)  # (uploaded once, here)
-        S, dev = n_streams, self.device
         dtypes = (torch.int64, torch.int16, torch.int16, torch.uint8)
         self._feeds = [_SequenceFeed() for _ in range(S)]
         self._ring = tuple(torch.zeros(S, R, dtype=d, device=dev) for d in dtypes)
         self._ring_host = tuple(torch.zeros(S, R, dtype=d).pin_memory() for d in dtypes)
         self._ring_np = tuple(c.numpy() for c in self._ring_host)
         n_words = 5 if voxel == 'trilinear' else 4  # (rows, starts, counts, formats; the map words behind them)
-        self._hot = None
         if hot_pixel_masks is not None:  # (the mask words behind the map words, which are then always there: -1 is NONE for both)
             n_words = 6
             self._hot = _HotPixelSlots(hot_pixel_masks, n_streams, tuple(maps.shape[1:3]) if maps is not None else (Hs, Ws), dev)
         self._words = torch.zeros(n_words, T * S, dtype=torch.int32, device=dev)
         self._words[4:].fill_(hip.RECTIFY_NONE)
-        self._in = torch.zeros(T * S, self.num_bins, height, width, dtype=torch.float32, device=dev)
-        self._acc = torch.zeros(T * S, self.num_bins, Hs, Ws, dtype=torch.int64, device=dev)  # (the size the events are voxelised at)
-        self._gt = torch.full((S,) + self.out_hw, ignore_index, dtype=torch.uint8, device=dev)
         self._gt_live = [False] * S  # (host: the stream's row of _gt holds a ground truth, not the ignore fill)
-        self.confusion = torch.zeros(S, K, K, dtype=torch.int64, device=dev)
         self._stage = []
         for _ in range(2):
             words = torch.zeros(n_words, T * S, dtype=torch.int32).pin_memory()
             words[4:].fill_(hip.RECTIFY_NONE)
             self._stage.append(_SequenceStage(words, torch.zeros((S,) + self.out_hw, dtype=torch.uint8).pin_memory(), torch.cuda.Event()))
         self._stage_next = 0
-        self._g = self._outputs = None
+
+    # ---- the store source (store=EventStore): no rings, no mirrors; one small table a round
+    def _check_store(self, store, device, ring_capacity, hot_pixel_masks, window_events, window_duration, window_capacity, mask_slots, out_hw):
+        """the store keywords, checked on the host -> self.window_capacity"""
+        from .datasets.event_store import EventStore
+        if not isinstance(store, EventStore):
+            raise hip.EssHipError(f'store must be an EventStore, got {type(store).__name__}')
+        if device is not None and torch.device(device) != torch.device(store.device):
+            raise hip.EssHipError(f'device={device!r}: a store-fed segmenter runs where the store lies ({store.device})')
+        if ring_capacity is not None:
+            raise hip.EssHipError(f'ring_capacity={ring_capacity!r} together with store=: a store-fed segmenter has no rings, its windows are '
+                                  'read where the store keeps them')
+        if hot_pixel_masks is not None:
+            raise hip.EssHipError('hot_pixel_masks= is keyed by stream; with store= a lane may name any recording: give '
+                                  'recording_hot_pixels={recording: HotPixelMask}')
+        low = 1
+        if window_events is not None:
+            if isinstance(window_events, bool) or not isinstance(window_events, int) or not 1 <= window_events <= hip.INGEST_MAX_CAPACITY:
+                raise hip.EssHipError(f'window_events={window_events!r}: an int in [1, {hip.INGEST_MAX_CAPACITY}]')
+            low = window_events
+            window_capacity = window_events if window_capacity is None else window_capacity
+        elif window_capacity is None:
+            raise hip.EssHipError('window_duration needs window_capacity=: the most events a window may hold (a larger one flags its sample)')
+        if isinstance(window_capacity, bool) or not isinstance(window_capacity, int) or not low <= window_capacity <= hip.INGEST_MAX_CAPACITY:
+            raise hip.EssHipError(f'window_capacity={window_capacity!r}: an int in [window_events or 1 = {low}, {hip.INGEST_MAX_CAPACITY}]')
+        if isinstance(mask_slots, bool) or not isinstance(mask_slots, int) or not 1 <= mask_slots <= 65535:
+            raise hip.EssHipError(f'mask_slots={mask_slots!r}: the static hot-pixel mask slots under the capture, an int in [1, 65535]')
+        if store.label_hw is not None and tuple(store.label_hw) != (int(out_hw[0]), int(out_hw[1])):
+            raise hip.EssHipError(f'the store keeps labels of {store.label_hw}, this segmenter scores at out_hw={tuple(out_hw)}: a '
+                                  'StoreSample.label is compared as it lies in the store')
+        self.window_capacity = window_capacity
+
+    @staticmethod
+    def _check_recording_masks(given, size, mask_slots):
+        """recording_hot_pixels={recording: HotPixelMask | None}, checked on the host -> [(recording, mask)]"""
+        if given is None:
+            return []
+        if not isinstance(given, dict):
+            raise hip.EssHipError(f'recording_hot_pixels must be a dict recording -> HotPixelMask, got {type(given).__name__}')
+        for r, m in given.items():
+            _RecordingMasks.check('recording_hot_pixels', r, m, size)
+        distinct = {id(m) for m in given.values() if m is not None}
+        if len(distinct) > mask_slots:
+            raise hip.EssHipError(f'recording_hot_pixels names {len(distinct)} distinct masks, mask_slots={mask_slots} slots hold them')
+        return [(int(r), m) for r, m in given.items() if m is not None]
+
+    def _store_layout(self):
+        """the per-round table, in bytes: name -> (offset, dtype, shape); 40 bytes a lane (8 T + 40 under the duration rule)"""
+        S, T = self.n_streams, self.sequence_steps
+        n_bounds = T + 1 if self.window_duration is not None else 1
+        at, out = 0, {}
+        for name, dtype, shape in (('bounds', torch.int64, (S, n_bounds)), ('label_of', torch.int64, (S,)), ('recording', torch.int32, (S,)),
+                                   ('sample_map', torch.int32, (S,)), ('mask_of', torch.int32, (S,)), ('gt_mode', torch.int32, (S,)),
+                                   ('reserved', torch.int64, (S,))):
+            out[name] = (at, dtype, shape)
+            at += -(-int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size() // 16) * 16
+        return out, at
+
+    def _allocate_store(self):
+        S, T, dev = self.n_streams, self.sequence_steps, self.device
+        layout, nbytes = self._store_layout()
+        views = lambda buf: {name: buf[at:at + int(np.prod(shape)) * torch.empty(0, dtype=d).element_size()].view(d).view(shape)  # noqa: E731
+                             for name, (at, d, shape) in layout.items()}
+        table = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        stage = []
+        for _ in range(2):
+            host = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+            gt = torch.zeros((S,) + self.out_hw, dtype=torch.uint8).pin_memory()
+            stage.append({'buf': host, 'np': {n: v.numpy() for n, v in views(host).items()}, 'gt': gt, 'gt_np': gt.numpy(),
+                          'done': torch.cuda.Event()})
+        self._st = {
+            'table': table, 'in': views(table), 'stage': stage,
+            'starts_bt': torch.zeros(S * T, dtype=torch.int64, device=dev),           # as event_store_windows writes them: slot b T + i
+            'words_bt': torch.zeros(3, S * T, dtype=torch.int32, device=dev),        # counts, formats, map words
+            'starts': torch.zeros(T * S, dtype=torch.int64, device=dev),              # as the encoder reads the grids: slot i S + s
+            'words': torch.zeros(4, T * S, dtype=torch.int32, device=dev),           # counts, formats, map words, mask words
+            'flags': torch.zeros(S, dtype=torch.int32, device=dev),
+            'gt_host': torch.full((S,) + self.out_hw, self.ignore_index, dtype=torch.uint8, device=dev),
+            'gt_store': None if self.store.label_hw is None else torch.zeros((S,) + self.out_hw, dtype=torch.uint8, device=dev),
+        }
+        self._stage_next = 0
+        self._store_graphs = {}
+        self.last_flags = self._st['flags']
+
+    def _round_store(self, rule):
+        """the device work of one store round, all of it capturable: the window search over the S lanes, the slot words transposed from
+        sample-major to step-major, the (masked) store ingest, the ground truth picked per lane from its flag word, the round"""
+        st, store, T, S = self._st, self.store, self.sequence_steps, self.n_streams
+        tin, ev = st['in'], self._in
+        counts_bt, formats_bt, maps_bt = st['words_bt']
+        with torch.no_grad():
+            # (total = the capacity: the search keeps every window inside its recording's table row, so a replayed graph serves
+            # recordings that were added after its capture)
+            hip.event_store_windows(store.columns[0], store.table, tin['recording'], tin['bounds'], rule, T, st['starts_bt'], counts_bt,
+                                    formats_bt, st['flags'], store.capacity, self.window_capacity,
+                                    n_per_window=self.window_events if self.window_duration is None else None,
+                                    sample_map=tin['sample_map'], map_of=maps_bt)
+            w = st['words']
+            st['starts'].view(T, S).copy_(st['starts_bt'].view(S, T).t())
+            w[:3].view(3, T, S).copy_(st['words_bt'].view(3, S, T).transpose(1, 2))
+            w[3].view(T, S).copy_(tin['mask_of'].view(1, S).expand(T, S))  # (a lane's T windows read the mask of its sample's recording)
+            tri = self.voxel == 'trilinear'
+            hip.event_ingest_store(*store.columns, st['starts'], w[0], w[1], None if self._loader_grid else ev,
+                                   hip.EVENT_STORE_TRILINEAR if tri else self._rep, store.capacity, self.window_capacity,
+                                   masks=self._rec_hot.words, mask_of=w[3], mask_size=self._rec_hot.size,
+                                   maps=self._maps if tri else None, map_of=w[2] if tri else None, acc=self._acc)
+            if self._loader_grid:
+                crop_rows, resize, normalize = self._grid
+                hip.event_grid_finish(w[0], self._acc, ev, crop_rows=crop_rows, resize=resize, normalize=normalize)
+            # the ground truth: gt_mode 0 none, 1 the store's label, 2 the host's; a flagged lane must not score, whatever it was handed
+            mode, gt = tin['gt_mode'].view(S, 1, 1), st['gt_host']
+            if st['gt_store'] is not None:
+                torch.index_select(store.labels, 0, tin['label_of'], out=st['gt_store'])
+                gt = torch.where(mode == 1, st['gt_store'], gt)
+            live = (st['flags'].view(S, 1, 1) == 0) & (mode != 0)
+            self._gt.copy_(torch.where(live, gt, torch.full_like(gt, self.ignore_index)))
+            return self._round_from(ev)
+
+    def _capture_store(self, rule):
+        """one eager run on a side stream, then the recording.  Neither may score: every lane is idle (recording -1) in the table"""
+        st = self._st
+        st['table'].zero_()
+        st['in']['recording'].fill_(-1)
+        st['in']['mask_of'].fill_(hip.MASK_NONE)
+        st['in']['sample_map'].fill_(hip.RECTIFY_NONE)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._round_store(rule)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            out = self._round_store(rule)
+        self._store_graphs[rule] = (g, out)
+        self.n_captures += 1
+
+    def _check_samples(self, samples):
+        """segment_at's samples=[...] of a store-fed segmenter, checked; nothing is written -> (rule, bound words per lane or None)"""
+        from .datasets.event_store import StoreSample, duration_bounds, time_bound
+        S, T, store = self.n_streams, self.sequence_steps, self.store
+        if not isinstance(samples, (list, tuple)) or len(samples) != S or any(s is not None and not isinstance(s, StoreSample) for s in samples):
+            n = len(samples) if isinstance(samples, (list, tuple)) else type(samples).__name__
+            raise hip.EssHipError(f'samples must be a list with one entry per lane (a StoreSample, or None: idle): got {n}, n_streams={S}')
+        given = [s for s in samples if s is not None]
+        by_time = given[0].t_end is not None if given else True
+        if any((s.t_end is not None) != by_time for s in given):
+            raise hip.EssHipError('samples: t_end for every sample of the round, or end for every one (one rule per launch)')
+        by_count = self.window_duration is None
+        if not by_time and not by_count:
+            raise hip.EssHipError('window_duration cuts by time: its samples need t_end, not end')
+        rule = hip.EVENT_STORE_RULE_DURATION if not by_count else \
+            (hip.EVENT_STORE_RULE_COUNT_TIME if by_time else hip.EVENT_STORE_RULE_COUNT_INDEX)
+        bounds = []
+        for b, s in enumerate(samples):
+            if s is None:
+                bounds.append(None)
+                continue
+            if s.recording >= store.n_recordings:
+                raise hip.EssHipError(f'samples[{b}] names recording {s.recording}, the store holds {store.n_recordings}')
+            if s.label is not None and (store.label_hw is None or s.label >= store.n_labels):
+                raise hip.EssHipError(f'samples[{b}]: label index {s.label} of the store\'s {store.n_labels} labels')
+            if s.map is not None and s.map >= len(self._map_entry):
+                raise hip.EssHipError(f'samples[{b}]: map index {s.map!r} of the segmenter\'s {len(self._map_entry)} rectify_maps')
+            begin, end = store.extent(s.recording)
+            if not by_time:
+                if s.end > end - begin:
+                    raise hip.EssHipError(f'samples[{b}]: end={s.end} of recording {s.recording}\'s {end - begin} events')
+                bounds.append([s.end])
+                continue
+            t_i64 = bool(store.format_of(s.recording) & hip.EVCOL_T_I64)
+            t_end = s.t_end - store.t_offset(s.recording)
+            bounds.append([time_bound(v, t_i64) for v in ([t_end] if by_count else duration_bounds(t_end, T, self.window_duration))])
+        return rule, bounds
+
+    def _segment_store(self, samples, labels):
+        rule, bounds = self._check_samples(samples)
+        gts = self._check_labels(labels)
+        S = self.n_streams
+        for s, (smp, g) in enumerate(zip(samples, gts)):
+            if smp is not None and smp.label is not None and g is not None:
+                raise hip.EssHipError(f'lane {s} is handed a label by its StoreSample (label={smp.label}) and by labels=[...]: one of the two')
+        if self.store.n_recordings == 0:
+            raise hip.EssHipError('the store holds no recording')
+        if self.use_graph and rule not in self._store_graphs:
+            self._capture_store(rule)
+        st = self._st
+        stage = st['stage'][self._stage_next]
+        self._stage_next ^= 1
+        stage['done'].synchronize()  # (the set's last upload has completed: it is free to be rewritten)
+        w = stage['np']
+        w['bounds'][:] = 0
+        w['label_of'][:] = 0
+        w['reserved'][:] = 0
+        for s, (smp, g) in enumerate(zip(samples, gts)):
+            if smp is None:  # (recording -1: the search flags the lane, its windows are empty, its ground truth is the ignore fill)
+                w['recording'][s], w['sample_map'][s], w['mask_of'][s], w['gt_mode'][s] = -1, hip.RECTIFY_NONE, hip.MASK_NONE, 0
+                continue
+            w['bounds'][s, :len(bounds[s])] = bounds[s]
+            w['recording'][s] = smp.recording
+            w['sample_map'][s] = hip.RECTIFY_NONE if smp.map is None else self._map_entry[smp.map]
+            w['mask_of'][s] = self._rec_hot.word(smp.recording)
+            w['gt_mode'][s] = 1 if smp.label is not None else (2 if g is not None else 0)
+            if smp.label is not None:
+                w['label_of'][s] = smp.label
+            if g is not None:
+                if torch.is_tensor(g):
+                    st['gt_host'][s].copy_(g, non_blocking=True)
+                else:
+                    np.copyto(stage['gt_np'][s], g)
+                    st['gt_host'][s].copy_(stage['gt'][s], non_blocking=True)
+        st['table'].copy_(stage['buf'], non_blocking=True)
+        stage['done'].record()
+        if self.use_graph:
+            g, out = self._store_graphs[rule]
+            g.replay()
+        else:
+            out = self._round_store(rule)
+        self.n_rounds += 1
+        res = MultiSegmentationResult(*out, valid=[smp is not None for smp in samples])
+        return res.clone() if (self.use_graph and self.copy_outputs) else res
+
+    def set_recording_hot_pixels(self, recording, mask):
+        """a store-fed segmenter: the lanes that name `recording` read `mask` (a HotPixelMask of the segmenter's sensor size, or None)
+        in every one of their T windows from the next round on.  The words go into a slot of the static mask buffer here, outside the
+        capture; no re-capture.  Entries that are the same object share a slot; with every slot taken the call is refused and
+        nothing changes."""
+        if self.store is None:
+            raise hip.EssHipError('set_recording_hot_pixels belongs to a store-fed segmenter (store=); this one reads rings: set_hot_pixels')
+        _RecordingMasks.check('set_recording_hot_pixels', recording, mask, self._rec_hot.size)
+        self._rec_hot.assign(recording, mask)
+
+    def _no_feed(self, what):
+        if self.store is not None:
+            raise hip.EssHipError(f'{what}: this segmenter reads an EventStore (store=), it has no rings to feed: add recordings to the '
+                                  'store and name them in segment_at(samples=[StoreSample, ...])')
 
     def _grid_geometry(self, height, width, grid_hw, grid_rows, grid_resize, grid_normalize):
         """the loader-grid keywords, checked -> (Hs, Ws); self._grid = (crop_rows, (Hr, Wr), hip.GRID_NORM_*)"""
@@ -224,6 +548,7 @@ class SequenceSegmenter:
         EventColumns, other dtypes than the stream's first packet had (drop_feed forgets them), a packet that goes back in time."""
         from .datasets.data_util import EventColumns
         from .datasets.event_feed import copy_into_ring
+        self._no_feed('feed')
         s = self._stream(stream, 'feed')
         f = self._feeds[s]
         if not isinstance(cols, EventColumns):
@@ -258,11 +583,13 @@ class SequenceSegmenter:
 
     def fed(self, stream):
         """the number of events the stream has been fed (the absolute index of its next event)"""
+        self._no_feed('fed')
         return self._feeds[self._stream(stream, 'fed')].head
 
     def drop_feed(self, streams=None):
         """these streams (default: all) forget their ring contents and their dtypes: the next packet is event 0 of a new recording.
         The confusion rows are reset_metrics' business, not this call's."""
+        self._no_feed('drop_feed')
         for s in (range(self.n_streams) if streams is None else streams):
             s = self._stream(s, 'drop_feed')
             for _, done in self._feeds[s].uploads:  # (the new recording writes the mirror from entry 0 on)
@@ -273,6 +600,9 @@ class SequenceSegmenter:
     def set_hot_pixels(self, stream, mask):
         """stream reads `mask` (a datasets.hot_pixels.HotPixelMask of the segmenter's sensor size, or None) in every one of its T
         windows from the next round on: the words go into the static mask buffer here, outside the capture; no re-capture"""
+        if self.store is not None:
+            raise hip.EssHipError('set_hot_pixels is keyed by stream; this segmenter reads an EventStore (store=), whose masks are keyed by '
+                                  'recording: set_recording_hot_pixels(recording, mask)')
         if self._hot is None:
             raise hip.EssHipError('set_hot_pixels: this segmenter was built without hot_pixel_masks, so no mask buffer exists under its '
                                   'capture: pass hot_pixel_masks=[...] (a list of None will do)')
@@ -465,7 +795,7 @@ class SequenceSegmenter:
                 sequence_windows_fixed_duration(self._ring_np[0][s].view(f.dtypes[0]), f.head, R, v, self.sequence_steps, self.window_duration)
                 for s, (v, f) in enumerate(zip(t_end, self._feeds))]
 
-    def segment_at(self, t_end=None, end=None, labels=None, windows=None):
+    def segment_at(self, t_end=None, end=None, labels=None, windows=None, samples=None):
         """One sequence round.  t_end / end: S entries -- a time (the sequence ends in front of the first event with t >= t_end, as
         the reference's get_events_fixed_num; with window_duration: the T windows of that duration in front of t_end) / an absolute
         event index, or None for an idle stream; windows: S entries, each None or sequence_steps pairs (start, count) in absolute
@@ -474,6 +804,13 @@ class SequenceSegmenter:
         anything is written.  -> MultiSegmentationResult"""
         from .datasets.event_feed import sequence_windows
         self._check_compute()
+        if self.store is not None:
+            if samples is None or t_end is not None or end is not None or windows is not None:
+                raise hip.EssHipError('segment_at: a store-fed segmenter (store=) takes samples=[StoreSample | None per lane] alone: the '
+                                      'samples name their recordings and their ends')
+            return self._segment_store(samples, labels)
+        if samples is not None:
+            raise hip.EssHipError('segment_at: samples=[...] name recordings of an EventStore: build the segmenter with store=')
         T, S, R = self.sequence_steps, self.n_streams, self.ring_capacity
         if windows is not None:
             if t_end is not None or end is not None:

@@ -660,7 +660,7 @@ int ess_label_window(const uint8_t* src, int32_t n, int32_t src_height, int32_t 
  * bound) shapes the launch, NOT the store's size; every index on the path is 64-bit.  flavour: ESS_EVENT_STORE_SIGNED, _SEPARATE,
  * _HISTOGRAM (the ESS_EVENT_REP_* words and their rules for `channels`) or _TRILINEAR (maps .. map_width as for
  * ess_event_scatter_ring_trilinear; with any other flavour they are not read).  The sums are, bit for bit, what the ring source
- * leaves for the same events.  Hot-pixel masks are not offered on this source.
+ * leaves for the same events.  Hot-pixel masks on this source: ess_event_ingest_store, below.
  *
  * ess_event_store_windows: a batch's sample table -> the n_samples * T slot words.  table (device, int64 [n_recordings][4]):
  * (begin, end, format, reserved) per recording, absolute indices with 0 <= begin <= end <= total; a negative format word marks an
@@ -691,6 +691,44 @@ int ess_event_store_windows(const void* t, int64_t capacity, int64_t total, cons
                             const int32_t* recording, const int64_t* bounds, const int32_t* sample_map, int32_t n_samples, int32_t T,
                             int32_t rule, int64_t n_per_window, int64_t window_capacity, int64_t* starts, int32_t* counts,
                             int32_t* formats, int32_t* map_of, int32_t* flags, ess_stream_t stream);
+
+/* HOT-PIXEL MASKS ON THE STORE SOURCE, and masks calibrated from a stored recording -- PURELY ADDITIVE to ABI 110 (no enumerator is
+ * added: the ESS_EVENT_STORE_* flavours, ESS_MASK_* and ESS_EVCOL_* words above are reused; ess_event_scatter_store launches the
+ * kernels it launched before).
+ *
+ * ess_event_ingest_store: ess_event_ingest_masked's counterpart on the store -- one entry point for the four flavours, both halves,
+ * with or without masks.  t .. acc_bytes, flavour, maps .. map_width: the arguments of ess_event_scatter_store, with its slot
+ * refusals (a negative start, start + count > total, count > window_capacity, an unknown format bit or map word: the slot counts as
+ * empty); with a flavour other than ESS_EVENT_STORE_TRILINEAR maps and map_of must be null and n_maps 0 (ESS_EINVAL otherwise).
+ * out (nullable, 16-byte aligned): fp32 [n_slots][channels][height][width] -- the plain finish follows the scatter as behind
+ * ess_event_ingest_ring*: the same bits, acc all zero again; NULL: scatter only, acc keeps the sums for ess_event_grid_finish*.
+ * masks .. mask_width: the five mask arguments of ess_event_ingest_masked, with its semantics word for word -- a hot event is dropped
+ * on its RAW (x, y), before a rectify map sees it; the window's time base comes from its first and last event, masked or not; a
+ * mask word that is neither ESS_MASK_NONE nor in 0 .. n_masks - 1 makes the slot empty.  mask_of is never null; masks null with
+ * n_masks 0 and every word ESS_MASK_NONE: no masking, the sums of ess_event_scatter_store bit for bit.
+ *
+ * ess_event_store_pixel_counts: plain per-pixel event counts of n index ranges of the store.  Job j: the events begins[j] ..
+ * ends[j] - 1 (device int64 words, ABSOLUTE indices, a range as long as the store: up to 2^40 events), decoded under formats[j]
+ * (device int32, ESS_EVCOL_XY_U16 read; ESS_EVCOL_T_I64 accepted, the time column is not read).  counts (device, int64
+ * [n][height][width], 8-byte aligned) is ADDED TO: one per event, both polarities together; an event whose decoded coordinate lies
+ * outside [0, width) x [0, height) is dropped.  A range outside [0, total], begins[j] > ends[j] or an unknown format bit: the job
+ * counts nothing.  Only x and y are read (4 bytes an event); every index is 64-bit; the launch follows from capacity, n alone:
+ * capturable.  Plain counts hold what the histogram flavour's sums cannot: more than 2^22 events on one pixel.
+ *
+ * ess_event_count_mask: ess_event_hot_pixel_mask's rule on such counts -- int64 [n][height][width], one plane, no 2^40 scale: bit
+ * (y, x) of masks[i] is set iff counts[i][y][x] > thresholds[i]; thresholds[i] < 0: masks[i] is neither read nor written.  masks,
+ * mode, the word layout, the tail-bit rule and the limits: as for ess_event_hot_pixel_mask (the same kernel).                  */
+int ess_event_ingest_store(const void* t, const void* x, const void* y, const void* p, const int64_t* starts, const int32_t* counts,
+                           const int32_t* formats, int64_t capacity, int64_t total, int64_t window_capacity, int32_t n_slots,
+                           int32_t channels, int32_t height, int32_t width, void* acc, size_t acc_bytes, float* out, int32_t flavour,
+                           const float* maps, const int32_t* map_of, int32_t n_maps, int32_t map_height, int32_t map_width,
+                           const uint32_t* masks, const int32_t* mask_of, int32_t n_masks, int32_t mask_height, int32_t mask_width,
+                           ess_stream_t stream);
+int ess_event_store_pixel_counts(const void* x, const void* y, int64_t capacity, int64_t total, const int64_t* begins,
+                                 const int64_t* ends, const int32_t* formats, int32_t n, int32_t height, int32_t width, int64_t* counts,
+                                 ess_stream_t stream);
+int ess_event_count_mask(const int64_t* counts, int32_t n, int32_t height, int32_t width, const int64_t* thresholds, uint32_t* masks,
+                         int32_t mode, ess_stream_t stream);
 
 /* ---- image-branch augmentation on the device: the geometric + photometric core of the albumentations
  * pipeline of datasets/cityscapes_loader.py:39-74 (HorizontalFlip, ShiftScaleRotate with rotate 0 and a constant-0 border,

@@ -77,10 +77,16 @@ K = 11, trilinear, VoxelGrid(normalize=True)), two ways on ONE segmenter's rings
                hip.voxel_normalize_, torch's F.interpolate on the device, a slice made contiguous, then the round behind its grids
                (one captured graph as well; it reads the slot words the other way uploaded, so it pays no upload of its own).
 
+--sequence T --store measures the sequence round cut on the device out of an EventStore, SequenceSegmenter(store=).segment_at(samples=),
+against the ring-fed path on the same events and 50 %-overlapping consecutive labels -- feed() of the label's events and
+segment_at(end=), inside the clock: only the half a lane has not been fed yet (ring_feed_new_half), or the whole sample after
+drop_feed() (ring_refeed_sample) --, the three ways alternating inside every round, to synchronised labels.
+
 usage: python tools/bench_seg_stream.py [--compute mixed,bf16 --windows 40 --warmup 8 --reps 3 --recurrent convlstm --streams 1,2,4,8
                                          [--active 1,2,4,6,8 [--buckets 1,2,4]] | --streams 8 --events 100000 --ingest | --streams 8 --events 100000 --feed [--voxel trilinear]
                                          | --streams 8 --events 100000 --sequence 20 --height 440 --windows 6 --warmup 2
-                                         | --streams 8 --events 100000 --sequence 20 --loader-grid dsec --windows 6 --warmup 2]"""
+                                         | --streams 8 --events 100000 --sequence 20 --loader-grid dsec --windows 6 --warmup 2
+                                         | --streams 8 --events 100000 --sequence 20 --store --height 440 --windows 6 --warmup 2]"""
 import argparse
 import json
 import os
@@ -122,6 +128,8 @@ def main():
     ap.add_argument('--loader-grid', default=None, choices=tuple(LOADER_PRESETS),
                     help="(with --sequence) the round on a reference loader's grid against the composition of the older pieces; sets "
                          '--height, --width (the sensor) and --classes')
+    ap.add_argument('--store', action='store_true', help='(with --sequence) rounds cut on the device out of an EventStore, '
+                    'segment_at(samples=), against the ring-fed path on the same events: feed() of each label\'s events, then segment_at(end=)')
     a = ap.parse_args()
     if a.loader_grid and a.sequence is None:
         ap.error('--loader-grid belongs to --sequence')
@@ -168,6 +176,10 @@ def main():
 
     if a.sequence is not None and a.loader_grid:
         sequence_loader_grid(a, hip, cfg, [w.cpu().numpy() for w in wins], out, E2VIDRecurrent, SemSegE2VID, default_options)
+        print(json.dumps(out))
+        return
+    if a.sequence is not None and a.store:
+        sequence_store(a, hip, cfg, [w.cpu().numpy() for w in wins], out, E2VIDRecurrent, SemSegE2VID, default_options)
         print(json.dumps(out))
         return
     if a.sequence is not None:
@@ -637,6 +649,104 @@ def sequence_loader_grid(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, de
                 out['labels_equal_fraction'][key] = round(min(same), 6) if same else None
                 assert seq.n_captures == 1 and not bool(seq._acc.any()) and not bool(acc_big.any())
                 del seq, big, acc_big, graph
+                torch.cuda.empty_cache()
+        finally:
+            hip.set_compute('fp32')
+
+
+def sequence_store(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, default_options):
+    """--sequence T --store: consecutive labels of S recordings, each label's sequence overlapping the one before by 50 %.  The store
+    way: the recordings lie in an EventStore (uploaded once, outside the clock), a round is segment_at(samples=[StoreSample(s, end=e)])
+    to synchronised labels.  The ring-fed ways, the parent's path on the same events, inside the clock: 'ring_feed_new_half' -- feed()
+    of the T N / 2 events a lane has not been fed yet, then segment_at(end=) -- and 'ring_refeed_sample' -- drop_feed(), feed() of the
+    label's whole T N events, segment_at(end=), what scoring labels in any order costs.  The ways alternate inside every round."""
+    from ess_amd.datasets.data_util import EventColumns
+    from ess_amd.datasets.event_store import EventStore, StoreSample
+    from ess_amd.run_sequence_segmentation import SequenceSegmenter
+    T, N, K = a.sequence, a.events, a.classes
+    out['shape'] = f'S lanes of {a.bins}x{a.height}x{a.width} K={K}, sequence rounds of T={T} windows of {N} events, graph replay, labels overlap 50 %'
+    del out['ms_per_window']
+    out['ms_per_round'], out['ring_minus_store_ms'], out['store_SLOWER_than_ring'] = {}, {}, {}
+    rounds = a.warmup + a.windows
+    dev = torch.device('cuda:0')
+    half = T * N // 2
+    length = T * N + rounds * half
+
+    def models():
+        torch.manual_seed(6)
+        return E2VIDRecurrent(dict(cfg)), SemSegE2VID(256, K, skip_connect=True, skip_type='concat')
+
+    base = np.concatenate(wins)
+    us = np.round(base[:, 0] * 1e6).astype(np.int64)
+    period = int(us[-1] - us[0]) + 1
+
+    def piece(lo, hi):
+        idx = np.arange(lo, hi)
+        r, k = idx // len(us), idx % len(us)
+        return EventColumns(us[k] + r * period, base[k, 1].astype(np.uint16), base[k, 2].astype(np.uint16), base[k, 3].astype(np.uint8))
+
+    for compute in a.compute.split(','):
+        hip.set_compute(compute)
+        try:
+            for S in (int(v) for v in a.streams.split(',')):
+                recs = [piece(s * 1237, s * 1237 + length) for s in range(S)]
+                store = EventStore(S * length)
+                for c in recs:
+                    store.add_recording(c)
+                by_store = SequenceSegmenter(*models(), a.height, a.width, default_options(), S, sequence_steps=T, window_events=N, graph=True,
+                                             store=store)
+                rings = {w: SequenceSegmenter(*models(), a.height, a.width, default_options(), S, sequence_steps=T, window_events=N, graph=True)
+                         for w in ('ring_feed_new_half', 'ring_refeed_sample')}
+                g = torch.Generator().manual_seed(1)
+                gt = list(torch.randint(0, K, (S, a.height, a.width), generator=g, dtype=torch.uint8).to(dev))
+                cut = lambda c, lo, hi: EventColumns(c.t[lo:hi], c.x[lo:hi], c.y[lo:hi], c.p[lo:hi])  # noqa: E731
+                for s in range(S):  # the first label's older half is there already
+                    rings['ring_feed_new_half'].feed(s, cut(recs[s], 0, T * N - half))
+                ms = {'store': [], 'ring_feed_new_half': [], 'ring_refeed_sample': []}
+                same = True
+                for k in range(rounds):
+                    end = T * N + k * half
+
+                    def store_round():
+                        return by_store.segment_at(samples=[StoreSample(s, end=end) for s in range(S)], labels=gt).labels
+
+                    def new_half_round():
+                        seg = rings['ring_feed_new_half']
+                        for s in range(S):
+                            seg.feed(s, cut(recs[s], end - half, end))
+                        return seg.segment_at(end=[end] * S, labels=gt).labels
+
+                    def refeed_round():
+                        seg = rings['ring_refeed_sample']
+                        seg.drop_feed()
+                        for s in range(S):
+                            seg.feed(s, cut(recs[s], end - T * N, end))
+                        return seg.segment_at(end=[T * N] * S, labels=gt).labels
+                    ways = [('store', store_round), ('ring_feed_new_half', new_half_round), ('ring_refeed_sample', refeed_round)]
+                    took, res = {}, {}
+                    for way, fn in ways[k % 3:] + ways[:k % 3]:
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        res[way] = fn()
+                        torch.cuda.synchronize()
+                        took[way] = (time.perf_counter() - t0) * 1e3
+                    same = same and all(torch.equal(res['store'], res[w]) for w in rings)
+                    if k >= a.warmup:
+                        for way in ms:
+                            ms[way].append(took[way])
+                key = f'{compute}/S={S}/T={T}'
+                for way, v in ms.items():
+                    out['ms_per_round'][f'{key}/{way}'] = {'median': round(statistics.median(v), 4), 'min': round(min(v), 4), 'max': round(max(v), 4)}
+                out.setdefault('same_labels', {})[key] = bool(same)
+                out.setdefault('same_confusion', {})[key] = bool(all(torch.equal(by_store.confusion, r.confusion) for r in rings.values()))
+                for way in rings:
+                    diff = statistics.median(ms[way]) - statistics.median(ms['store'])
+                    out['ring_minus_store_ms'][f'{key}/{way}'] = round(diff, 4)
+                    out['store_SLOWER_than_ring'][f'{key}/{way}'] = bool(diff < 0)
+                    out.setdefault('ring_spread_ms', {})[f'{key}/{way}'] = round(max(ms[way]) - min(ms[way]), 4)
+                out.setdefault('store_bytes', {})[key] = store.bytes()
+                assert by_store.n_captures == 1 and all(r.n_captures == 1 for r in rings.values())
+                del by_store, rings, store
                 torch.cuda.empty_cache()
         finally:
             hip.set_compute('fp32')

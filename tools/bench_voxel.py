@@ -34,11 +34,17 @@ that carry 5 % of the events -- and hip.event_hot_pixel_mask on one histogram a 
 And the DEVICE EVENT STORE (store(), --store: these rows alone): hip.event_scatter_store against hip.event_scatter_ring on the same
 events from start residues 0 and 3, and hip.event_store_windows alone on a time column of --store-events events.
 
+And HOT-PIXEL MASKS ON THE STORE (store_masked(), --store-masked: these rows alone): the scatter half of hip.event_ingest_store -- no
+mask tensor, an all-zero mask, 100 hot pixels that carry 5 % of the events -- beside hip.event_scatter_store on the same windows;
+hip.event_store_pixel_counts + hip.event_count_mask on 10 M and 100 M events; and, with --parent-lib, ess_event_scatter_store of a
+library built from the parent commit beside this build's, in the same run.
+
 usage: python tools/bench_voxel.py --ingest --slices 8 --events 100000 --bins 5
        python tools/bench_voxel.py --ingest --masked --slices 8 --events 100000 --bins 5
        python tools/bench_voxel.py --ingest --representations-only --slices 8 --events 100000 --bins 5
        python tools/bench_voxel.py --ingest --loader-finish-only --slices 160 --events 100000 --bins 5 --reps 20
-       python tools/bench_voxel.py --ingest --store --slices 8 --events 100000 --bins 5"""
+       python tools/bench_voxel.py --ingest --store --slices 8 --events 100000 --bins 5
+       python tools/bench_voxel.py --ingest --store-masked --slices 8 --events 100000 --bins 5 [--parent-lib PATH]"""
 import argparse
 import json
 import os
@@ -64,6 +70,9 @@ def main():
     ap.add_argument('--representations-only', action='store_true', help='(with --ingest) only the event-representation rows')
     ap.add_argument('--masked', action='store_true', help='(with --ingest) only the hot-pixel mask rows')
     ap.add_argument('--store', action='store_true', help='(with --ingest) only the device event store rows')
+    ap.add_argument('--store-masked', action='store_true', help='(with --ingest) only the rows of hot-pixel masks on the store source')
+    ap.add_argument('--parent-lib', default=None, help="(with --store-masked) a libess_hip.so built from the parent commit: its "
+                    'ess_event_scatter_store is timed beside this build\'s in the same run')
     ap.add_argument('--store-events', type=int, default=100_000_000, help='(with --store) events of the column the window search runs on')
     a = ap.parse_args()
     if a.ingest:
@@ -436,11 +445,143 @@ def store(a):
     return {'workload': f'{S} windows x {n} events, bins={C}, {H} x {W}; ring of {ring} / a flat store of {S * ring}', 'reps': a.reps, 'rows': rows}
 
 
+def store_masked(a):
+    """Hot-pixel masks on the store source, three things in one run.  (1) hip.event_ingest_store, scatter half, against
+    hip.event_scatter_store on the SAME windows (S windows of n int64 / uint16 events from start residue 3): no mask tensor, an
+    all-zero mask, and 100 hot pixels that carry 5 % of the events.  (2) hip.event_store_pixel_counts + hip.event_count_mask on 10 M
+    and 100 M events made on the device, 5 % of them on 100 pixels (a pixel takes 50 000 / 500 000 atomics).  (3) --parent-lib:
+    ess_event_scatter_store of a library built from the parent commit, called on the same pointers, alternating with this build's.
+    -> rows for the JSON"""
+    import ctypes
+    import numpy as np
+    from ess_amd import hip
+    S, n, C, H, W = a.slices, a.events, a.bins, a.height, a.width
+    dev = torch.device('cuda:0')
+    stride = hip.event_column_stride(n)
+    ring, start = 2 * stride, 3
+    g = np.random.default_rng(1)
+    hot = g.permutation(H * W)[:100]
+    pix = g.integers(0, H * W, (S, n))
+    on_hot = g.random((S, n)) < 0.05
+    pix[on_hot] = hot[g.integers(0, 100, int(on_hot.sum()))]
+    ev = [np.sort(g.integers(0, 30_000, (S, n)), axis=1).astype(np.int64), (pix % W).astype(np.uint16), (pix // W).astype(np.uint16),
+          g.integers(0, 2, (S, n)).astype(np.uint8)]
+    flat = []
+    for c in ev:
+        r = np.zeros((S, ring), c.dtype)
+        r[:, start:start + n] = c
+        flat.append(torch.from_numpy(r.reshape(-1).view(np.int16) if c.dtype == np.uint16 else r.reshape(-1)).to(dev))
+    i32 = lambda v: torch.as_tensor(v, dtype=torch.int32, device=dev)  # noqa: E731
+    fmt, counts = i32([hip.EVCOL_XY_U16 | hip.EVCOL_T_I64] * S), i32([n] * S)
+    starts = torch.as_tensor([s * ring + start for s in range(S)], dtype=torch.int64, device=dev)
+    acc = torch.zeros(S, C, H, W, dtype=torch.int64, device=dev)
+    bits = np.zeros((H, W), dtype=bool)
+    bits[hot // W, hot % W] = True
+    from ess_amd.datasets.hot_pixels import HotPixelMask
+    mask = HotPixelMask.from_bool(bits)
+    dmasks = torch.from_numpy(np.stack([np.zeros_like(mask.words), mask.words]).view(np.int32)).to(dev)
+    total = S * ring
+    ways = {'scatter_store': lambda: hip.event_scatter_store(*flat, starts, counts, fmt, acc, hip.EVENT_STORE_SIGNED, total, stride),
+            'ingest_store_no_masks': lambda: hip.event_ingest_store(*flat, starts, counts, fmt, None, hip.EVENT_STORE_SIGNED, total, stride, acc=acc),
+            'ingest_store_all_zero_mask': lambda: hip.event_ingest_store(*flat, starts, counts, fmt, None, hip.EVENT_STORE_SIGNED, total, stride,
+                                                                         masks=dmasks, mask_of=i32([0] * S), mask_size=(H, W), acc=acc),
+            'ingest_store_hot_100_pixels': lambda: hip.event_ingest_store(*flat, starts, counts, fmt, None, hip.EVENT_STORE_SIGNED, total, stride,
+                                                                          masks=dmasks, mask_of=i32([1] * S), mask_size=(H, W), acc=acc)}
+    if a.parent_lib:
+        parent = ctypes.CDLL(a.parent_lib)
+        parent.ess_event_scatter_store.argtypes = hip.lib().ess_event_scatter_store.argtypes
+        P = ctypes.c_void_p
+        args = [P(c.data_ptr()) for c in flat] + [P(starts.data_ptr()), P(counts.data_ptr()), P(fmt.data_ptr()), total, total, stride, S, C, H, W,
+                                                  P(acc.data_ptr()), acc.numel() * 8, hip.EVENT_STORE_SIGNED, P(0), P(0), 0, 1, 1]
+
+        def by_parent():
+            assert parent.ess_event_scatter_store(*args, hip.stream()) == 0
+        ways['scatter_store_parent_commit'] = by_parent
+    sums = {}
+    for k, fn in ways.items():  # (what is timed gives the sums it should) + warm-up
+        acc.zero_()
+        fn()
+        sums[k] = acc.clone()
+        for _ in range(20):
+            fn()
+    same = {k: bool(torch.equal(v, sums['scatter_store'])) for k, v in sums.items()}
+    assert all(v for k, v in same.items() if k != 'ingest_store_hot_100_pixels') and not same['ingest_store_hot_100_pixels'], same
+    assert not bool(sums['ingest_store_hot_100_pixels'][:, :, torch.from_numpy(hot // W).to(dev), torch.from_numpy(hot % W).to(dev)].any())
+    torch.cuda.synchronize()
+    ms = {k: [] for k in ways}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(3):  # alternating: drift of the box hits every way alike
+        for k, fn in ways.items():
+            spent = 0.0
+            for _ in range(a.reps):
+                acc.zero_()
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                spent += e0.elapsed_time(e1)
+            ms[k].append(spent / a.reps)
+    med = {k: sorted(v)[1] for k, v in ms.items()}
+    spread = max(ms['scatter_store']) - min(ms['scatter_store'])
+    rows = {'ms_per_batch': {k: {'median': round(med[k], 5), 'min': round(min(v), 5), 'max': round(max(v), 5)} for k, v in ms.items()},
+            'scatter_store_spread_ms': round(spread, 5)}
+    for k in ways:
+        if k != 'scatter_store':
+            d = med[k] - med['scatter_store']
+            rows[f'{k}_minus_scatter_store_ms'] = round(d, 5)
+            rows[f'{k}_SLOWER_than_scatter_store'] = bool(d > spread)
+    if a.parent_lib:
+        d = med['scatter_store'] - med['scatter_store_parent_commit']
+        both = max(spread, max(ms['scatter_store_parent_commit']) - min(ms['scatter_store_parent_commit']))
+        rows['scatter_store_minus_parent_commit_ms'] = round(d, 5)
+        rows['scatter_store_MOVED_against_parent_commit'] = bool(abs(d) > both)
+    # -- the calibration pair on whole recordings
+    rows['count_and_mask'] = {}
+    for N in (10_000_000, 100_000_000):
+        cap = hip.event_column_stride(N)
+        p = torch.randint(0, H * W, (cap,), device=dev)
+        sel = torch.rand(cap, device=dev) < 0.05
+        p[sel] = torch.from_numpy(hot).to(dev)[torch.randint(0, 100, (int(sel.sum()),), device=dev)]
+        x, y = (p % W).to(torch.int16), (p // W).to(torch.int16)
+        del p, sel
+        job = torch.tensor([0, N, N // 20000], dtype=torch.int64, device=dev)  # (threshold: a tenth of a hot pixel's share of N / 2000)
+        cnt = torch.zeros(1, H, W, dtype=torch.int64, device=dev)
+        found = torch.zeros(1, H, hip.mask_words(W), dtype=torch.int32, device=dev)
+        f0 = i32([0])
+        pair = {'event_store_pixel_counts': lambda: hip.event_store_pixel_counts(x, y, job[0:1], job[1:2], f0, cnt, N),
+                'event_count_mask': lambda: hip.event_count_mask(cnt, job[2:3], found)}
+        cms = {k: [] for k in pair}
+        reps = max(3, min(a.reps, 20))
+        for _ in range(3):
+            for k, fn in pair.items():
+                spent = 0.0
+                for _ in range(reps):
+                    if k == 'event_store_pixel_counts':
+                        cnt.zero_()
+                    e0.record()
+                    fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    spent += e0.elapsed_time(e1)
+                cms[k].append(spent / reps)
+        assert int(cnt.sum()) == N and np.array_equal(found.cpu().numpy().view(np.uint32)[0], mask.words), 'the calibration does not find the 100'
+        rows['count_and_mask'][str(N)] = {k: {'median_ms': round(sorted(v)[1], 4), 'min_ms': round(min(v), 4), 'max_ms': round(max(v), 4)}
+                                          for k, v in cms.items()}
+        rows['count_and_mask'][str(N)]['GB_per_s_of_x_and_y'] = round(4 * N / (sorted(cms['event_store_pixel_counts'])[1] * 1e-3) / 1e9, 1)
+        del x, y
+    return {'workload': f'{S} windows x {n} events from start residue {start}, bins={C}, {H} x {W}, a flat store of {total}; 100 hot pixels '
+                        f'carry 5 % of the events', 'reps': a.reps, 'rows': rows, 'UNMEASURED': 'index ranges above 2^31 events'}
+
+
 def ingest(a):
     import numpy as np
     from ess_amd import hip
     from ess_amd.datasets.data_util import pack_event_records
     hip.lib()
+    if a.store_masked:
+        print(json.dumps({'metric': 'hot-pixel masks on the store source: masked ingest beside the scatter; counts + mask; the scatter '
+                                    'beside the parent commit', 'unit': 'ms', 'store_masked': store_masked(a), 'data': 'synthetic'}))
+        return
     if a.store:
         print(json.dumps({'metric': 'store events -> sums beside the ring scatter; the window search alone', 'unit': 'ms', 'store': store(a),
                           'data': 'synthetic'}))
