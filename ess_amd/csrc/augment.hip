@@ -22,8 +22,35 @@ __device__ __forceinline__ unsigned hash32(unsigned x) {  // (lowbias32)
   return x;
 }
 
-__global__ __launch_bounds__(256) void augment_kernel(const float* __restrict__ img, const int64_t* __restrict__ lab,
-                                                      const float* __restrict__ params, const int64_t* __restrict__ lut,
+// The pixel source of stage 1: where sample n's Hs x Ws image and label are read.  FloatSource: fp32 [N][Hs][Ws] images and int64
+// labels, one behind the other.  StoreSource: the uint8 slots of an image store, [n_slots][slot_h][Ws], sample n = slot index[n],
+// of which the top Hs rows are the image (a word outside the table: an all-zero sample).  One kernel body serves both.
+struct FloatSource {
+  const float* __restrict__ img;
+  const int64_t* __restrict__ lab;
+  __device__ __forceinline__ bool labelled() const { return lab != nullptr; }
+  __device__ __forceinline__ float pixel(int n, int Hs, int Ws, int yy, int xx) const { return img[((size_t)n * Hs + yy) * Ws + xx]; }
+  __device__ __forceinline__ int64_t label(int n, int Hs, int Ws, int yy, int xx) const { return lab[((size_t)n * Hs + yy) * Ws + xx]; }
+};
+
+struct StoreSource {
+  const uint8_t* __restrict__ img;
+  const uint8_t* __restrict__ lab;
+  const int32_t* __restrict__ index;
+  int n_slots, slot_h;
+  __device__ __forceinline__ bool labelled() const { return lab != nullptr; }
+  __device__ __forceinline__ float pixel(int n, int Hs, int Ws, int yy, int xx) const {
+    const int slot = index[n];
+    return (slot >= 0 && slot < n_slots) ? (float)img[((size_t)slot * slot_h + yy) * Ws + xx] : 0.f;
+  }
+  __device__ __forceinline__ int64_t label(int n, int Hs, int Ws, int yy, int xx) const {
+    const int slot = index[n];
+    return (slot >= 0 && slot < n_slots) ? (int64_t)lab[((size_t)slot * slot_h + yy) * Ws + xx] : 0;
+  }
+};
+
+template <typename Source>
+__global__ __launch_bounds__(256) void augment_kernel(const Source src, const float* __restrict__ params, const int64_t* __restrict__ lut,
                                                       float* __restrict__ out_img, int64_t* __restrict__ out_lab, int N, int Hs,
                                                       int Ws, int H, int W) {
   const int64_t total = (int64_t)N * H * W;
@@ -44,11 +71,11 @@ __global__ __launch_bounds__(256) void augment_kernel(const float* __restrict__ 
       const float uf = floorf(u), wf = floorf(w);
       const int x0 = (int)uf, y0 = (int)wf;
       const float fx = u - uf, fy = w - wf;
-      auto at = [&](int yy, int xx) { return (yy >= 0 && yy < Hs && xx >= 0 && xx < Ws) ? img[((size_t)n * Hs + yy) * Ws + xx] : 0.f; };
+      auto at = [&](int yy, int xx) { return (yy >= 0 && yy < Hs && xx >= 0 && xx < Ws) ? src.pixel(n, Hs, Ws, yy, xx) : 0.f; };
       const float top = at(y0, x0) * (1.f - fx) + at(y0, x0 + 1) * fx, bot = at(y0 + 1, x0) * (1.f - fx) + at(y0 + 1, x0 + 1) * fx;
       v = floorf(top * (1.f - fy) + bot * fy + 0.5f);
       const int xn = (int)floorf(u + 0.5f), yn = (int)floorf(w + 0.5f);
-      if (lab && xn >= 0 && xn < Ws && yn >= 0 && yn < Hs) l = lab[((size_t)n * Hs + yn) * Ws + xn];
+      if (src.labelled() && xn >= 0 && xn < Ws && yn >= 0 && yn < Hs) l = src.label(n, Hs, Ws, yn, xn);
     }
     const float sigma = p[10];
     if (sigma > 0.f) {  // GaussNoise: N(0, sigma^2) on the 0..255 scale, Box-Muller over two hashed uniforms
@@ -191,7 +218,27 @@ extern "C" int ess_augment_image_label(const float* img, const int64_t* label, c
   const int64_t total = (int64_t)N * H * W;
   int64_t blocks = ceil_div64(total, 256);
   if (blocks > 65535 * 16) blocks = 65535 * 16;
-  hipLaunchKernelGGL(augment_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, img, label, params, id_lut, out_img,
-                     out_label, N, H_src, W_src, H, W);
+  hipLaunchKernelGGL(augment_kernel<FloatSource>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, FloatSource{img, label},
+                     params, id_lut, out_img, out_label, N, H_src, W_src, H, W);
   return ess_launch_status("augment_image_label");
+}
+
+extern "C" int ess_augment_image_label_store(const uint8_t* images, const uint8_t* labels, const int32_t* index, int32_t n_slots,
+                                             int32_t H_slot, int32_t W_slot, int32_t rows, const float* params, const int64_t* id_lut,
+                                             float* out_img, int64_t* out_label, int32_t N, int32_t H, int32_t W, ess_stream_t stream) {
+  const char* me = "augment_image_label_store";
+  ESS_CHECK_ARG(images && index && params && out_img, "%s: null images, index, params or out_img", me);
+  ESS_CHECK_ARG(N > 0 && H > 0 && W > 0 && n_slots > 0 && H_slot > 0 && W_slot > 0, "%s: N=%d, H=%d, W=%d, n_slots=%d, slots of %d x %d: all must be positive",
+                me, N, H, W, n_slots, H_slot, W_slot);
+  ESS_CHECK_ARG(rows >= 1 && rows <= H_slot, "%s: rows=%d must lie in [1, %d]: the top rows of a slot", me, rows, H_slot);
+  ESS_CHECK_ARG((labels == nullptr) == (out_label == nullptr), "%s: labels and out_label come together", me);
+  ESS_CHECK_ARG((uintptr_t)index % 4 == 0 && (uintptr_t)params % 4 == 0 && (uintptr_t)out_img % 4 == 0 && (uintptr_t)out_label % 8 == 0 &&
+                    (uintptr_t)id_lut % 8 == 0,
+                "%s: index, params and out_img must be 4-byte aligned, out_label and id_lut 8-byte aligned", me);
+  const int64_t total = (int64_t)N * H * W;
+  int64_t blocks = ceil_div64(total, 256);
+  if (blocks > 65535 * 16) blocks = 65535 * 16;
+  hipLaunchKernelGGL(augment_kernel<StoreSource>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                     StoreSource{images, labels, index, n_slots, H_slot}, params, id_lut, out_img, out_label, N, rows, W_slot, H, W);
+  return ess_launch_status(me);
 }

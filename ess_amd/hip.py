@@ -87,6 +87,7 @@ EXPORTS = [
     'ess_event_ingest_store', 'ess_event_store_pixel_counts', 'ess_event_count_mask',
     'ess_recon_post_frame', 'ess_recon_post_bounds', 'ess_event_preview',
     'ess_viz_semseg', 'ess_viz_events', 'ess_viz_overlay',
+    'ess_image_ingest', 'ess_augment_image_label_store',
 ]
 
 
@@ -215,6 +216,8 @@ def lib():
             'ess_viz_semseg': [P, I, P, P, c_size_t, POINTER(EssVizDst), I, I, I, I, I, P],
             'ess_viz_events': [P, P, c_size_t, POINTER(EssVizDst), I, I, I, I, I, I, P],
             'ess_viz_overlay': [P, P, P, P, I, I, I, I, F, P],
+            'ess_image_ingest': [P, I, I, I, P, I, P, I, P, P, I, I, I, P, P, P, P, P, P],
+            'ess_augment_image_label_store': [P, P, P, I, I, I, I, P, P, P, P, I, I, I, P],
         }
         for name, argtypes in sig.items():
             fn = getattr(L, name)
@@ -1799,18 +1802,141 @@ def augment_image_label(img, label, params, height, width, id_lut=None):
     return out, out_l
 
 
-def augment_perspective_filter(img, label, params, id_lut=None):
+IMAGE_MAX_TAPS = 33     # ESS_IMAGE_MAX_TAPS: 2 * ceil(in / out) + 1 coefficients a window at the most, a side shrinks by at most 16
+IMAGE_MAX_SIDE = 32768  # ESS_IMAGE_MAX_SIDE
+
+
+def _image_table(fn, name, t, n_in, n_out):
+    """a pass's table [2 + taps, n_out] (datasets.image_store.pil_bilinear_tables), None exactly where the size stays -> taps"""
+    if n_in == n_out:
+        if t is not None:
+            raise EssHipError(f'{fn}: {name} belongs to a pass that changes the size; {n_in} -> {n_out} is skipped, as PIL skips it: pass None')
+        return 0
+    if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != n_out or not 3 <= t.shape[0] <= 2 + IMAGE_MAX_TAPS \
+            or not t.is_contiguous():
+        got = f'{t.dtype}{tuple(t.shape)}' if torch.is_tensor(t) else type(t).__name__
+        raise EssHipError(f'{fn}: {name} must be a contiguous int32 [2 + taps, {n_out}] table with taps <= {IMAGE_MAX_TAPS} for the pass '
+                          f'{n_in} -> {n_out}, got {got}')
+    return t.shape[0] - 2
+
+
+def image_ingest(frame, out, h_table=None, v_table=None, scratch=None, standardize=False, minmax=None, label=None, label_rows=None,
+                 label_cols=None, out_label=None):
+    """One decoded frame -> its store slot (ess_image_ingest), in PIL's integer arithmetic: frame uint8 [H, W, 3] (RGB; convert('L'))
+    or [H, W] (gray) -> out uint8 [Hr, Wr] = Image.resize((Wr, Hr), BILINEAR) of the gray frame.  h_table / v_table: the passes'
+    int32 [2 + taps, Wr] / [2 + taps, Hr] tables of datasets.image_store.pil_bilinear_tables, None exactly where the size stays.
+    scratch: uint8 [H, Wr] (RGB input or a horizontal pass; allocated when None).  minmax: int32 [2], receives the resized frame's
+    min and max; standardize=True (needs it) then stretches v -> trunc(255.0 (v - min) / (max - min)), a constant frame to 0.
+    label uint8 [H, W] with label_rows int32 [Hr], label_cols int32 [Wr] (pil_nearest_table) -> out_label uint8 [Hr, Wr].
+    Returns out.  Everything is checked before a pointer is taken."""
+    fn = 'image_ingest'
+    if not torch.is_tensor(frame) or frame.dtype != torch.uint8 or frame.dim() not in (2, 3) or (frame.dim() == 3 and frame.shape[2] != 3) \
+            or frame.numel() == 0 or not frame.is_contiguous():
+        got = f'{frame.dtype}{tuple(frame.shape)}' if torch.is_tensor(frame) else type(frame).__name__
+        raise EssHipError(f'{fn}: frame must be a non-empty contiguous uint8 [H, W, 3] (RGB) or [H, W] (gray) tensor, got {got}')
+    H, W = int(frame.shape[0]), int(frame.shape[1])
+    channels = 3 if frame.dim() == 3 else 1
+    if not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 2 or out.numel() == 0 or not out.is_contiguous():
+        got = f'{out.dtype}{tuple(out.shape)}' if torch.is_tensor(out) else type(out).__name__
+        raise EssHipError(f'{fn}: out must be a non-empty contiguous uint8 [Hr, Wr] tensor, got {got}')
+    Hr, Wr = int(out.shape[0]), int(out.shape[1])
+    if max(H, W, Hr, Wr) > IMAGE_MAX_SIDE:
+        raise EssHipError(f'{fn}: source {H} x {W}, slot {Hr} x {Wr}: a side is at most {IMAGE_MAX_SIDE}')
+    h_taps, v_taps = _image_table(fn, 'h_table', h_table, W, Wr), _image_table(fn, 'v_table', v_table, H, Hr)
+    tensors = [('frame', frame), ('out', out)] + [(n, t) for n, t in (('h_table', h_table), ('v_table', v_table)) if t is not None]
+    need_scratch = channels == 3 or h_table is not None
+    if scratch is not None:
+        tensors.append(('scratch', _formed(fn, 'scratch', scratch, torch.uint8, (H, Wr))))
+    if minmax is not None:
+        tensors.append(('minmax', _formed(fn, 'minmax', minmax, torch.int32, (2,))))
+    elif standardize:
+        raise EssHipError(f'{fn}: standardize needs minmax, an int32 [2] tensor for the frame\'s min and max')
+    if (label is None) != (out_label is None) or (label is None) != (label_rows is None) or (label is None) != (label_cols is None):
+        raise EssHipError(f'{fn}: label, label_rows, label_cols and out_label are given together or not at all')
+    if label is not None:
+        tensors += [('label', _formed(fn, 'label', label, torch.uint8, (H, W))), ('label_rows', _formed(fn, 'label_rows', label_rows, torch.int32, (Hr,))),
+                    ('label_cols', _formed(fn, 'label_cols', label_cols, torch.int32, (Wr,))),
+                    ('out_label', _formed(fn, 'out_label', out_label, torch.uint8, (Hr, Wr)))]
+    _on_device(fn, tensors)
+    if any(t.device != frame.device for _, t in tensors):
+        raise EssHipError(f'{fn}: every tensor must lie on the frame\'s device ({frame.device})')
+    if scratch is None and need_scratch:
+        scratch = torch.empty(H, Wr, dtype=torch.uint8, device=frame.device)
+    _check(lib().ess_image_ingest(ptr(frame, torch.uint8), channels, H, W, ptr(h_table, torch.int32), h_taps, ptr(v_table, torch.int32), v_taps,
+                                  ptr(scratch if need_scratch else None, torch.uint8), ptr(out, torch.uint8), Hr, Wr, int(bool(standardize)),
+                                  ptr(minmax, torch.int32), ptr(label, torch.uint8), ptr(label_rows, torch.int32), ptr(label_cols, torch.int32),
+                                  ptr(out_label, torch.uint8), stream()), 'ess_image_ingest')
+    return out
+
+
+def augment_image_label_store(images, labels, index, rows, params, height, width, id_lut=None, out=None):
+    """Stage 1 of the augmentation (ess_augment_image_label_store: augment_image_label's kernel body with another pixel source) reading
+    the uint8 slots of an ImageStore through an index: images uint8 [n_slots, Hr, Wr], labels uint8 of the same shape or None,
+    index int32 [B] on the device (a word outside the slots: an all-zero sample), rows: the top rows of a slot that exist (the loader's
+    img[:height]), params fp32 [B, 12] -> (fp32 [B, 1, height, width] in [0, 1], int64 [B, height, width] or None): the bits of
+    augment_image_label(images[index][:, :rows].float(), labels[index][:, :rows].long(), params, height, width, id_lut), with no float
+    copy of the source.  out=(img, label): the tensors to fill."""
+    fn = 'augment_image_label_store'
+    if not torch.is_tensor(images) or images.dtype != torch.uint8 or images.dim() != 3 or images.numel() == 0 or not images.is_contiguous():
+        got = f'{images.dtype}{tuple(images.shape)}' if torch.is_tensor(images) else type(images).__name__
+        raise EssHipError(f'{fn}: images must be a non-empty contiguous uint8 [n_slots, Hr, Wr] tensor, got {got}')
+    n_slots, Hr, Wr = (int(v) for v in images.shape)
+    if labels is not None:
+        _formed(fn, 'labels', labels, torch.uint8, (n_slots, Hr, Wr))
+    if not torch.is_tensor(index) or index.dtype != torch.int32 or index.dim() != 1 or index.numel() == 0 or not index.is_contiguous():
+        got = f'{index.dtype}{tuple(index.shape)}' if torch.is_tensor(index) else type(index).__name__
+        raise EssHipError(f'{fn}: index must be a non-empty contiguous int32 [B] tensor, got {got}')
+    B = int(index.shape[0])
+    if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or not 1 <= rows <= Hr:
+        raise EssHipError(f'{fn}: rows={rows!r} must be an int in [1, {Hr}]: the top rows of a slot')
+    for name, v in (('height', height), ('width', width)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= IMAGE_MAX_SIDE:
+            raise EssHipError(f'{fn}: {name}={v!r} must be an int in [1, {IMAGE_MAX_SIDE}]')
+    _formed(fn, 'params', params, torch.float32, (B, 12))
+    if id_lut is not None and (not torch.is_tensor(id_lut) or id_lut.dtype != torch.int64 or id_lut.numel() < 256 or not id_lut.is_contiguous()):
+        raise EssHipError(f'{fn}: id_lut must be a contiguous int64 tensor of 256 entries (the kernel indexes it with the label id)')
+    tensors = [('images', images), ('index', index), ('params', params)] + [(n, t) for n, t in (('labels', labels), ('id_lut', id_lut)) if t is not None]
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2 or (out[1] is None) != (labels is None):
+            raise EssHipError(f'{fn}: out must be (img, label) with a label tensor exactly where labels are given')
+        tensors.append(('out[0]', _formed(fn, 'out[0]', out[0], torch.float32, (B, 1, height, width))))
+        if labels is not None:
+            tensors.append(('out[1]', _formed(fn, 'out[1]', out[1], torch.int64, (B, height, width))))
+    _on_device(fn, tensors)
+    if any(t.device != images.device for _, t in tensors):
+        raise EssHipError(f'{fn}: every tensor must lie on the store\'s device ({images.device})')
+    if out is None:
+        out = (torch.empty(B, 1, height, width, dtype=torch.float32, device=images.device),
+               torch.empty(B, height, width, dtype=torch.int64, device=images.device) if labels is not None else None)
+    _check(lib().ess_augment_image_label_store(ptr(images, torch.uint8), ptr(labels, torch.uint8), ptr(index, torch.int32), n_slots, Hr, Wr,
+                                               int(rows), ptr(params), ptr(id_lut, torch.int64), ptr(out[0]), ptr(out[1], torch.int64), B,
+                                               int(height), int(width), stream()), 'ess_augment_image_label_store')
+    return out[0], out[1]
+
+
+def augment_perspective_filter(img, label, params, id_lut=None, out=None, scratch=None):
     """Second augmentation stage (ess_augment_perspective_filter): Perspective, brightness / contrast, the Sharpen / Blur /
     MotionBlur stencil.  img fp32 [N, 1, H, W] in [0, 1] (stage 1's output), label int64 [N, H, W] raw ids or None, params fp32
-    [N, 24] (datasets/augment.py draws them) -> (fp32 [N, 1, H, W], int64 [N, H, W])."""
+    [N, 24] (datasets/augment.py draws them) -> (fp32 [N, 1, H, W], int64 [N, H, W]).  out=(img, label) and scratch= (fp32 [N, H, W]):
+    the tensors to fill and the stage's workspace, for a caller with static buffers (allocated here when None)."""
     N, _, H, W = img.shape
     if params.shape != (N, 24):
         raise EssHipError('augment_perspective_filter: params must be [N, 24]')
     if id_lut is not None and id_lut.numel() < 256:
         raise EssHipError('augment_perspective_filter: id_lut must have 256 entries')
-    scratch = torch.empty(N, H, W, dtype=torch.float32, device=img.device)
-    out = torch.empty(N, 1, H, W, dtype=torch.float32, device=img.device)
-    out_l = torch.empty(N, H, W, dtype=torch.int64, device=img.device) if label is not None else None
+    if scratch is None:
+        scratch = torch.empty(N, H, W, dtype=torch.float32, device=img.device)
+    else:
+        _formed('augment_perspective_filter', 'scratch', scratch, torch.float32, (N, H, W))
+    if out is None:
+        out = torch.empty(N, 1, H, W, dtype=torch.float32, device=img.device)
+        out_l = torch.empty(N, H, W, dtype=torch.int64, device=img.device) if label is not None else None
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != 2 or (out[1] is None) != (label is None):
+            raise EssHipError('augment_perspective_filter: out must be (img, label) with a label tensor exactly where a label is given')
+        out, out_l = _formed('augment_perspective_filter', 'out[0]', out[0], torch.float32, (N, 1, H, W)), out[1]
+        if out_l is not None:
+            _formed('augment_perspective_filter', 'out[1]', out_l, torch.int64, (N, H, W))
     _check(lib().ess_augment_perspective_filter(ptr(img), ptr(label, torch.int64), ptr(params), ptr(id_lut, torch.int64), ptr(scratch),
                                                 ptr(out), ptr(out_l, torch.int64), N, H, W, stream()), 'ess_augment_perspective_filter')
     return out, out_l

@@ -753,6 +753,35 @@ int ess_augment_perspective_filter(const float* img, const int64_t* label, const
                                    float* scratch, float* out_img, int64_t* out_label, int32_t N, int32_t H, int32_t W,
                                    ess_stream_t stream);
 
+/* stage 1 of the pipeline above (ess_augment_image_label: the same kernel body, another pixel source) reading uint8 STORE SLOTS
+ * through an index: sample n is slot index[n] of images / labels, uint8 [n_slots][H_slot][W_slot] (datasets/image_store.py), of
+ * which only the top `rows` rows exist for the augmentation (the loader's img[:height] under random_crop): H_src = rows,
+ * W_src = W_slot.  No float [N][H_src][W_src] copy is made.  index: int32 [N] on the device; a word outside [0, n_slots) gives an
+ * all-zero sample (image 0, label id 0).  labels (nullable, with out_label).  The output bits are those of
+ * ess_augment_image_label on (float) images[index][:, :rows] and (int64) labels[index][:, :rows].                              */
+int ess_augment_image_label_store(const uint8_t* images, const uint8_t* labels, const int32_t* index, int32_t n_slots,
+                                  int32_t H_slot, int32_t W_slot, int32_t rows, const float* params, const int64_t* id_lut,
+                                  float* out_img, int64_t* out_label, int32_t N, int32_t H, int32_t W, ess_stream_t stream);
+
+/* ---- image ingest for the device image store (csrc/image_store.hip; datasets/cityscapes_loader.py:26-29, 86-96): one decoded
+ * frame -> its uint8 [Hr][Wr] slot in PIL's own integer arithmetic: convert('L') (channels == 3:
+ * L = (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16), Image.resize(BILINEAR) in two passes with an 8-bit intermediate,
+ * horizontal first -- pixel = clip8((2^21 + sum_i k_i p_i) >> 22) over the window (first, count) of an output index --, the
+ * label's Image.resize(NEAREST) as a gather, and (standardize != 0) the loader's stretch
+ * v -> (uint8) trunc(255.0 * (v - min) / (max - min)) in IEEE fp64 over the whole resized frame (a constant frame: all 0).
+ * frame: uint8 [H][W][channels], channels 1 | 3.  h_table: int32 [2 + h_taps][Wr] = first input index, count, then h_taps planes of
+ * 22-bit fixed-point coefficients (count <= h_taps <= ESS_IMAGE_MAX_TAPS), built by the host in float64; NULL exactly where
+ * W == Wr (PIL skips a pass that changes nothing); v_table: int32 [2 + v_taps][Hr] likewise.  scratch: uint8 [H][Wr] (needed with
+ * channels == 3 or a horizontal pass).  minmax (nullable; needed with standardize): 2 int32 words that receive the resized frame's
+ * min and max BEFORE the stretch.  label (nullable, with out_label, label_rows int32 [Hr], label_cols int32 [Wr]): uint8 [H][W]
+ * -> out_label uint8 [Hr][Wr] = label[label_rows[y]][label_cols[x]].  Every buffer on the device; up to five launches.            */
+#define ESS_IMAGE_MAX_TAPS 33     /* 2 * ceil(in / out) + 1: a side shrinks by at most 16 */
+#define ESS_IMAGE_MAX_SIDE 32768
+int ess_image_ingest(const uint8_t* frame, int32_t channels, int32_t H, int32_t W, const int32_t* h_table, int32_t h_taps,
+                     const int32_t* v_table, int32_t v_taps, uint8_t* scratch, uint8_t* out, int32_t Hr, int32_t Wr,
+                     int32_t standardize, int32_t* minmax, const uint8_t* label, const int32_t* label_rows,
+                     const int32_t* label_cols, uint8_t* out_label, ess_stream_t stream);
+
 /* TaskLoss = Dice + CrossEntropy (utils/loss_functions.py:6-24,96-135), forward AND gradient w.r.t.
  * logits in one pass pair.  logits [N][K][H][W], labels int64 [N][H][W].  loss: 1 float.
  * dlogits (nullable): d(loss*loss_scale)/dlogits.  workspace: ess_task_loss_workspace(K) bytes.     */
