@@ -5,9 +5,14 @@
 //   ess_recon_post_frame   unsharp mask + rescale + quantisation in ONE pass over the output window: fp32 in, uint8 (and / or the
 //                          reference's float(u8) / 255) out.  The bounds (Imin, Imax - Imin) are read from device memory per sample.
 //   ess_recon_post_bounds  the auto-HDR step: (a) min / max of the SHARPENED source per sample, one partial pair per workgroup into the
-//                          caller's workspace (every slot written on every call, no atomics); (b) one wave per sample: clip in fp64,
+//                          caller's workspace (every slot written on every call -- steered: every TAKEN slot --, no atomics); (b) one wave per sample: clip in fp64,
 //                          push into the sample's ring of filter_size + 1 entries, np.median of the held mins / maxs, write the bounds.
 //   ess_event_preview      make_event_preview: bin sum -> red-blue BGR bytes or the grey ramp.
+//
+// ess_recon_post_bounds_steered / ess_recon_post_frame_steered are the same kernel text with STEER = true: a mode word per SLOT of the
+// batch in device memory (the state carry's HOLD / TAKE / ZERO) decides whether the slot is processed at all, and an optional index
+// table names the HISTORY ROW a slot's frame belongs to -- what a multi-stream round needs, whose one captured graph serves every mix
+// of advancing, idle and restarting streams.  The STEER = false instantiations are the unsteered entry points' kernels, unchanged.
 //
 // The arithmetic of a pixel is FIXED -- fp32 multiply, add and divide, each rounded once, in the order written in sharpen4 / quantise
 // (no fused multiply-add, no reciprocal) -- so that a numpy float32 restatement reproduces every output bit; 50 VALU instructions per
@@ -65,13 +70,36 @@ __device__ __forceinline__ uint32_t quantise(float s, float imin, float range) {
   return (uint32_t)fminf(fmaxf(q, 0.f), 255.f);
 }
 
+// The steering words (ess_hip.h: ESS_CARRY_HOLD / TAKE / ZERO, as ess_state_carry_masked reads them).  A slot is processed when its
+// word is TAKE or ZERO; HOLD and every other word skip it.
+constexpr int32_t MODE_TAKE = 1, MODE_ZERO = 2;
+__device__ __forceinline__ bool mode_taken(int32_t m) { return m == MODE_TAKE || m == MODE_ZERO; }
+
+// The steering arguments of a kernel: a trailing parameter pack STEER that is EMPTY for the unsteered entry points -- their kernels
+// then have the parameter lists and the code they had before steering existed -- and one Steer for the steered ones.
+struct Steer {
+  const int32_t* mode;  // [N] per slot
+  const int32_t* rows;  // [N] the slot's history row, or null: row = slot (the frame kernel reads neither rows nor R)
+  int R;                // history rows
+};
+__device__ __forceinline__ const Steer& the(const Steer& st) { return st; }  // (the one member of a non-empty pack)
+
+// The history row of slot n in a steered bounds step, or -1 where the slot is skipped: its word does not take it, or its row lies
+// outside [0, R).  Both words depend on the slot alone: every lane of a workgroup gets the same answer (scalar loads).
+__device__ __forceinline__ int steered_row(const Steer& st, size_t n) {
+  if (!mode_taken(st.mode[n])) return -1;
+  const int r = st.rows ? st.rows[n] : (int)n;
+  return (unsigned)r < (unsigned)st.R ? r : -1;
+}
+
 // One lane = 4 consecutive pixels of one output row.  vec8 / vec32: W % 4 == 0 and the output pointer aligned for one 4-byte / 16-byte
-// store per lane; otherwise single elements (DDD17's W = 346).
-template <bool SHARP>
+// store per lane; otherwise single elements (DDD17's W = 346).  STEER: the items of a slot whose mode word does not take it are
+// neither read nor written.
+template <bool SHARP, typename... STEER>
 __global__ __launch_bounds__(256) void frame_kernel(const float* __restrict__ img, const Taps k, float c1, float a,
                                                     const float* __restrict__ bounds, uint8_t* __restrict__ out8,
                                                     float* __restrict__ out32, int N, int Hs, int Ws, int y0, int x0, int H, int W,
-                                                    int vec8, int vec32) {
+                                                    int vec8, int vec32, const STEER... steer) {
   const int G = (W + 3) >> 2;
   const size_t total = (size_t)N * H * G, plane = (size_t)Hs * Ws;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -79,6 +107,9 @@ __global__ __launch_bounds__(256) void frame_kernel(const float* __restrict__ im
     const size_t r = i / G;
     const int oy = (int)(r % H);
     const size_t n = r / H;
+    if constexpr (sizeof...(STEER) > 0) {
+      if (!mode_taken(the(steer...).mode[n])) continue;
+    }
     float s[4];
     sharpen4<SHARP>(img + n * plane, Hs, Ws, y0 + oy, x0 + ox, k, c1, a, s);
     const float imin = bounds[2 * n], range = bounds[2 * n + 1];
@@ -105,11 +136,16 @@ __global__ __launch_bounds__(256) void frame_kernel(const float* __restrict__ im
 
 // Pass (a) of the auto-HDR step: min and max of the sharpened plane of sample blockIdx.y over this workgroup's share of the 4-pixel
 // groups -> part[(n * PARTIALS + blockIdx.x) * 2 + {0, 1}].  A workgroup without pixels writes (+inf, -inf); NaN pixels are skipped.
-template <bool SHARP>
+// STEER: the workgroups of a skipped slot return at once -- no image read, no partial written; the exit depends on blockIdx.y
+// only and comes before the barrier.
+template <bool SHARP, typename... STEER>
 __global__ __launch_bounds__(256) void minmax_kernel(const float* __restrict__ img, const Taps k, float c1, float a, int Hs, int Ws,
-                                                     float* __restrict__ part) {
+                                                     float* __restrict__ part, const STEER... steer) {
   __shared__ float red[2][4];
   const size_t n = blockIdx.y;
+  if constexpr (sizeof...(STEER) > 0) {
+    if (steered_row(the(steer...), n) < 0) return;
+  }
   const int G = (Ws + 3) >> 2;
   const size_t total = (size_t)Hs * G;
   const float* p = img + n * (size_t)Hs * Ws;
@@ -154,9 +190,21 @@ __device__ __forceinline__ double wave_pick_sum(double v) {  // (all addends but
 // filter_size + 1 entries: a ring of that capacity whose oldest entry the new one overwrites.  The median does not depend on the
 // order of the entries, so lane i holds physical slot i; the lane of the slot written in this call takes the new pair from
 // registers, not from memory.
+// STEER: the partials and the bounds are indexed by the SLOT n, ring and state by the slot's history row (R rows); a skipped slot's
+// wave returns without touching anything; a ZERO slot takes head = count = 0 in place of the stored state, which empties the row's
+// history before this frame enters it.
+template <typename... STEER>
 __global__ __launch_bounds__(64) void bounds_kernel(const float* __restrict__ part, double* __restrict__ ring, int32_t* __restrict__ state,
-                                                    int cap, float* __restrict__ bounds) {
+                                                    int cap, float* __restrict__ bounds, const STEER... steer) {
   const size_t n = blockIdx.x;
+  size_t row = n;
+  bool restart = false;
+  if constexpr (sizeof...(STEER) > 0) {
+    const int r = steered_row(the(steer...), n);
+    if (r < 0) return;
+    row = (size_t)r;
+    restart = the(steer...).mode[n] == MODE_ZERO;
+  }
   const int lane = threadIdx.x;
   float mn = INFINITY, mx = -INFINITY;
   for (int i = lane; i < PARTIALS; i += 64) {
@@ -170,7 +218,8 @@ __global__ __launch_bounds__(64) void bounds_kernel(const float* __restrict__ pa
   }
   const double lo = fmin(fmax((double)mn, 0.0), 0.45);  // np.clip(Imin, 0.0, 0.45)
   const double hi = fmin(fmax((double)mx, 0.55), 1.0);  // np.clip(Imax, 0.55, 1.0)
-  int head = state[2 * n], count = state[2 * n + 1];
+  int head = state[2 * row], count = state[2 * row + 1];
+  if (restart) head = count = 0;
   head = min(max(head, 0), cap - 1);  // (a state the caller corrupted must not send a store outside the ring)
   count = min(max(count, 0), cap);
   int slot;
@@ -181,7 +230,7 @@ __global__ __launch_bounds__(64) void bounds_kernel(const float* __restrict__ pa
     slot = head + count >= cap ? head + count - cap : head + count;
     ++count;
   }
-  double* rg = ring + n * (size_t)cap * 2;
+  double* rg = ring + row * (size_t)cap * 2;
   // the held entries are the `count` slots from `head` on (cyclically); with count < cap they need not start at slot 0
   int phys = head + lane;
   if (phys >= cap) phys -= cap;
@@ -213,8 +262,8 @@ __global__ __launch_bounds__(64) void bounds_kernel(const float* __restrict__ pa
   if (lane == 0) {
     rg[2 * slot] = lo;
     rg[2 * slot + 1] = hi;
-    state[2 * n] = head;
-    state[2 * n + 1] = count;
+    state[2 * row] = head;
+    state[2 * row + 1] = count;
     bounds[2 * n] = (float)smin;
     bounds[2 * n + 1] = (float)(smax - smin);
   }
@@ -302,50 +351,105 @@ Taps taps_of(const float* weights, float amount) {
 
 }  // namespace
 
-extern "C" int ess_recon_post_frame(const float* img, const float* weights, float c1, float amount, const float* bounds,
-                                    uint8_t* frame_u8, float* frame_f32, int32_t N, int32_t Hs, int32_t Ws, int32_t win_y0,
-                                    int32_t win_x0, int32_t win_h, int32_t win_w, ess_stream_t stream) {
-  if (int rc = check_image("recon_post_frame", img, weights, c1, amount, N, Hs, Ws)) return rc;
-  ESS_CHECK_ARG(bounds, "recon_post_frame: null bounds");
-  ESS_CHECK_ARG(((uintptr_t)bounds & 3) == 0 && ((uintptr_t)frame_f32 & 3) == 0, "recon_post_frame: bounds and frame_f32 must be 4-byte aligned");
-  ESS_CHECK_ARG(frame_u8 || frame_f32, "recon_post_frame: frame_u8 and frame_f32 are both null");
+// both frame entry points: mode null = the unsteered kernels (named first here and in launch_bounds: the instantiations then keep
+// their places at the head of the code object)
+static int launch_frame(const char* who, const float* img, const float* weights, float c1, float amount, const float* bounds,
+                        uint8_t* frame_u8, float* frame_f32, int32_t N, int32_t Hs, int32_t Ws, int32_t win_y0, int32_t win_x0,
+                        int32_t win_h, int32_t win_w, const int32_t* mode, ess_stream_t stream) {
+  if (int rc = check_image(who, img, weights, c1, amount, N, Hs, Ws)) return rc;
+  ESS_CHECK_ARG(bounds, "%s: null bounds", who);
+  ESS_CHECK_ARG(((uintptr_t)bounds & 3) == 0 && ((uintptr_t)frame_f32 & 3) == 0, "%s: bounds and frame_f32 must be 4-byte aligned", who);
+  ESS_CHECK_ARG(frame_u8 || frame_f32, "%s: frame_u8 and frame_f32 are both null", who);
   ESS_CHECK_ARG(win_y0 >= 0 && win_x0 >= 0 && win_h > 0 && win_w > 0 && (int64_t)win_y0 + win_h <= Hs && (int64_t)win_x0 + win_w <= Ws,
-                "recon_post_frame: window (%d, %d, %d, %d) leaves the %d x %d source", win_y0, win_x0, win_h, win_w, Hs, Ws);
+                "%s: window (%d, %d, %d, %d) leaves the %d x %d source", who, win_y0, win_x0, win_h, win_w, Hs, Ws);
   const size_t items = (size_t)N * win_h * ((win_w + 3) >> 2);
   const unsigned grid = capped_grid(items, 2048);
   const int vec8 = win_w % 4 == 0 && ((uintptr_t)frame_u8 & 3) == 0, vec32 = win_w % 4 == 0 && ((uintptr_t)frame_f32 & 15) == 0;
   hipStream_t st = (hipStream_t)stream;
   const Taps k = taps_of(weights, amount);
-  if (amount > 0.f)
-    hipLaunchKernelGGL(frame_kernel<true>, dim3(grid), dim3(256), 0, st, img, k, c1, amount, bounds, frame_u8, frame_f32, N, Hs, Ws, win_y0,
-                       win_x0, win_h, win_w, vec8, vec32);
+  if (!mode) {
+    if (amount > 0.f)
+      hipLaunchKernelGGL(frame_kernel<true>, dim3(grid), dim3(256), 0, st, img, k, c1, amount, bounds, frame_u8, frame_f32, N, Hs, Ws,
+                         win_y0, win_x0, win_h, win_w, vec8, vec32);
+    else
+      hipLaunchKernelGGL(frame_kernel<false>, dim3(grid), dim3(256), 0, st, img, k, c1, amount, bounds, frame_u8, frame_f32, N, Hs, Ws,
+                         win_y0, win_x0, win_h, win_w, vec8, vec32);
+  } else {
+    const Steer steer{mode, nullptr, N};
+    if (amount > 0.f)
+      hipLaunchKernelGGL((frame_kernel<true, Steer>), dim3(grid), dim3(256), 0, st, img, k, c1, amount, bounds, frame_u8, frame_f32, N, Hs,
+                         Ws, win_y0, win_x0, win_h, win_w, vec8, vec32, steer);
+    else
+      hipLaunchKernelGGL((frame_kernel<false, Steer>), dim3(grid), dim3(256), 0, st, img, k, c1, amount, bounds, frame_u8, frame_f32, N, Hs,
+                         Ws, win_y0, win_x0, win_h, win_w, vec8, vec32, steer);
+  }
+  return ess_launch_status(who);
+}
+
+extern "C" int ess_recon_post_frame(const float* img, const float* weights, float c1, float amount, const float* bounds,
+                                    uint8_t* frame_u8, float* frame_f32, int32_t N, int32_t Hs, int32_t Ws, int32_t win_y0,
+                                    int32_t win_x0, int32_t win_h, int32_t win_w, ess_stream_t stream) {
+  return launch_frame("recon_post_frame", img, weights, c1, amount, bounds, frame_u8, frame_f32, N, Hs, Ws, win_y0, win_x0, win_h, win_w,
+                      nullptr, stream);
+}
+
+extern "C" int ess_recon_post_frame_steered(const float* img, const float* weights, float c1, float amount, const float* bounds,
+                                            uint8_t* frame_u8, float* frame_f32, int32_t N, int32_t Hs, int32_t Ws, int32_t win_y0,
+                                            int32_t win_x0, int32_t win_h, int32_t win_w, const int32_t* mode, ess_stream_t stream) {
+  ESS_CHECK_ARG(mode && ((uintptr_t)mode & 3) == 0, "recon_post_frame_steered: mode is null or not 4-byte aligned");
+  return launch_frame("recon_post_frame_steered", img, weights, c1, amount, bounds, frame_u8, frame_f32, N, Hs, Ws, win_y0, win_x0, win_h,
+                      win_w, mode, stream);
+}
+
+// both bounds entry points: mode null = the unsteered kernels on R = N histories
+static int launch_bounds(const char* who, const float* img, const float* weights, float c1, float amount, int32_t N, int32_t Hs,
+                         int32_t Ws, float* workspace, size_t workspace_bytes, double* ring, int32_t* ring_state, int32_t R,
+                         int32_t filter_size, float* bounds, const int32_t* mode, const int32_t* rows, ess_stream_t stream) {
+  if (int rc = check_image(who, img, weights, c1, amount, N, Hs, Ws)) return rc;
+  ESS_CHECK_ARG(filter_size >= 0 && filter_size <= ESS_RECON_POST_MAX_FILTER, "%s: filter_size=%d outside 0..%d", who, filter_size,
+                ESS_RECON_POST_MAX_FILTER);
+  ESS_CHECK_ARG(N <= 65535, "%s: N=%d samples exceed the grid's 65535 rows", who, N);
+  ESS_CHECK_ARG(R > 0, "%s: R=%d history rows", who, R);
+  ESS_CHECK_ARG(workspace && ring && ring_state && bounds, "%s: null workspace, ring, ring_state or bounds", who);
+  ESS_CHECK_ARG(workspace_bytes >= (size_t)N * PARTIALS * 2 * sizeof(float), "%s: workspace has %zu bytes, N=%d needs %zu", who,
+                workspace_bytes, N, (size_t)N * PARTIALS * 2 * sizeof(float));
+  ESS_CHECK_ARG(((uintptr_t)workspace & 3) == 0 && ((uintptr_t)ring & 7) == 0 && ((uintptr_t)ring_state & 3) == 0 && ((uintptr_t)bounds & 3) == 0,
+                "%s: workspace, ring_state, bounds must be 4-byte and ring 8-byte aligned", who);
+  hipStream_t st = (hipStream_t)stream;
+  const Taps k = taps_of(weights, amount);
+  const Steer steer{mode, rows, R};
+  if (!mode) {
+    if (amount > 0.f)
+      hipLaunchKernelGGL(minmax_kernel<true>, dim3(PARTIALS, N), dim3(256), 0, st, img, k, c1, amount, Hs, Ws, workspace);
+    else
+      hipLaunchKernelGGL(minmax_kernel<false>, dim3(PARTIALS, N), dim3(256), 0, st, img, k, c1, amount, Hs, Ws, workspace);
+  } else if (amount > 0.f)
+    hipLaunchKernelGGL((minmax_kernel<true, Steer>), dim3(PARTIALS, N), dim3(256), 0, st, img, k, c1, amount, Hs, Ws, workspace, steer);
   else
-    hipLaunchKernelGGL(frame_kernel<false>, dim3(grid), dim3(256), 0, st, img, k, c1, amount, bounds, frame_u8, frame_f32, N, Hs, Ws, win_y0,
-                       win_x0, win_h, win_w, vec8, vec32);
-  return ess_launch_status("recon_post_frame");
+    hipLaunchKernelGGL((minmax_kernel<false, Steer>), dim3(PARTIALS, N), dim3(256), 0, st, img, k, c1, amount, Hs, Ws, workspace, steer);
+  if (int rc = ess_launch_status(mode ? "recon_post_bounds_steered (min / max)" : "recon_post_bounds (min / max)")) return rc;
+  if (!mode)
+    hipLaunchKernelGGL(bounds_kernel<>, dim3(N), dim3(64), 0, st, (const float*)workspace, ring, ring_state, filter_size + 1, bounds);
+  else
+    hipLaunchKernelGGL(bounds_kernel<Steer>, dim3(N), dim3(64), 0, st, (const float*)workspace, ring, ring_state, filter_size + 1, bounds,
+                       steer);
+  return ess_launch_status(mode ? "recon_post_bounds_steered (median)" : "recon_post_bounds (median)");
 }
 
 extern "C" int ess_recon_post_bounds(const float* img, const float* weights, float c1, float amount, int32_t N, int32_t Hs, int32_t Ws,
                                      float* workspace, size_t workspace_bytes, double* ring, int32_t* ring_state, int32_t filter_size,
                                      float* bounds, ess_stream_t stream) {
-  if (int rc = check_image("recon_post_bounds", img, weights, c1, amount, N, Hs, Ws)) return rc;
-  ESS_CHECK_ARG(filter_size >= 0 && filter_size <= ESS_RECON_POST_MAX_FILTER, "recon_post_bounds: filter_size=%d outside 0..%d", filter_size,
-                ESS_RECON_POST_MAX_FILTER);
-  ESS_CHECK_ARG(N <= 65535, "recon_post_bounds: N=%d samples exceed the grid's 65535 rows", N);
-  ESS_CHECK_ARG(workspace && ring && ring_state && bounds, "recon_post_bounds: null workspace, ring, ring_state or bounds");
-  ESS_CHECK_ARG(workspace_bytes >= (size_t)N * PARTIALS * 2 * sizeof(float), "recon_post_bounds: workspace has %zu bytes, N=%d needs %zu",
-                workspace_bytes, N, (size_t)N * PARTIALS * 2 * sizeof(float));
-  ESS_CHECK_ARG(((uintptr_t)workspace & 3) == 0 && ((uintptr_t)ring & 7) == 0 && ((uintptr_t)ring_state & 3) == 0 && ((uintptr_t)bounds & 3) == 0,
-                "recon_post_bounds: workspace, ring_state, bounds must be 4-byte and ring 8-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const Taps k = taps_of(weights, amount);
-  if (amount > 0.f)
-    hipLaunchKernelGGL(minmax_kernel<true>, dim3(PARTIALS, N), dim3(256), 0, st, img, k, c1, amount, Hs, Ws, workspace);
-  else
-    hipLaunchKernelGGL(minmax_kernel<false>, dim3(PARTIALS, N), dim3(256), 0, st, img, k, c1, amount, Hs, Ws, workspace);
-  if (int rc = ess_launch_status("recon_post_bounds (min / max)")) return rc;
-  hipLaunchKernelGGL(bounds_kernel, dim3(N), dim3(64), 0, st, (const float*)workspace, ring, ring_state, filter_size + 1, bounds);
-  return ess_launch_status("recon_post_bounds (median)");
+  return launch_bounds("recon_post_bounds", img, weights, c1, amount, N, Hs, Ws, workspace, workspace_bytes, ring, ring_state, N,
+                       filter_size, bounds, nullptr, nullptr, stream);
+}
+
+extern "C" int ess_recon_post_bounds_steered(const float* img, const float* weights, float c1, float amount, int32_t N, int32_t Hs,
+                                             int32_t Ws, float* workspace, size_t workspace_bytes, double* ring, int32_t* ring_state,
+                                             int32_t R, int32_t filter_size, float* bounds, const int32_t* mode, const int32_t* rows,
+                                             ess_stream_t stream) {
+  ESS_CHECK_ARG(mode && ((uintptr_t)mode & 3) == 0 && ((uintptr_t)rows & 3) == 0, "recon_post_bounds_steered: mode is null, or mode / rows not 4-byte aligned");
+  return launch_bounds("recon_post_bounds_steered", img, weights, c1, amount, N, Hs, Ws, workspace, workspace_bytes, ring, ring_state, R,
+                       filter_size, bounds, mode, rows, stream);
 }
 
 extern "C" int ess_event_preview(const float* grids, uint8_t* out, int32_t N, int32_t C, int32_t H, int32_t W, int32_t num_bins_to_show,

@@ -163,7 +163,11 @@ class PostProcessor:
     auto-HDR history in a deque.  Each call advances the auto-HDR history (one per sample: the one extension; n = 1 is the reference).
     crop: a CropParameters -- or a window (y0, x0, H, W) -- when the frame comes at the model's reflection-padded size: the unsharp
     mask and the auto-HDR min / max see the whole padded frame (as the reference's, which filters before it crops), only the
-    sensor's window is written.  bilateral_filter_sigma > 0 is refused (ImageFilter)."""
+    sensor's window is written.  bilateral_filter_sigma > 0 is refused (ImageFilter).
+    mode= / rows= (both calls; default None: the calls above, launch for launch): the steered form a multi-stream round uses -- `n`
+    counts the auto-HDR HISTORIES, the frame holds N <= n slots, mode int32 [N] on the device says per slot whether its history takes
+    the frame (CARRY_TAKE), is emptied and then takes it (CARRY_ZERO) or the slot is skipped (anything else: no history moves, its
+    output rows are unspecified), rows int32 [N] names each slot's history (default: its own number).  IntensityRescaler.rescale."""
 
     def __init__(self, device, options, n=1, crop=None):
         self.device = device
@@ -180,14 +184,14 @@ class PostProcessor:
     def state_tensors(self):
         return self.intensity_rescaler.state_tensors()
 
-    def _run(self, frame, want_u8, want_f32):
+    def _run(self, frame, want_u8, want_f32, mode=None, rows=None):
         f = self.unsharp_mask_filter
         with torch.no_grad():
             return self.intensity_rescaler.rescale(frame, f.weights, f.unsharp_mask_amount, window=self.window, want_u8=want_u8,
-                                                   want_f32=want_f32)
+                                                   want_f32=want_f32, mode=mode, rows=rows)
 
-    def process(self, new_predicted_frame):
-        return self.image_filter(self._run(new_predicted_frame, False, True)[1])
+    def process(self, new_predicted_frame, mode=None, rows=None):
+        return self.image_filter(self._run(new_predicted_frame, False, True, mode, rows)[1])
 
-    def process_u8(self, new_predicted_frame):
-        return self._run(new_predicted_frame, True, False)[0]
+    def process_u8(self, new_predicted_frame, mode=None, rows=None):
+        return self._run(new_predicted_frame, True, False, mode, rows)[0]

@@ -157,15 +157,33 @@ class IntensityRescaler:
         """the device tensors a call changes (a driver that runs a warm-up window saves and restores them)"""
         return [t for t in (self.bounds, self.ring, self.ring_state) if t is not None]
 
-    def rescale(self, img, weights=None, amount=0.0, window=None, want_u8=True, want_f32=False):
+    def rescale(self, img, weights=None, amount=0.0, window=None, want_u8=True, want_f32=False, mode=None, rows=None):
         """(unsharp mask with `weights`, `amount` +) rescale of img fp32 [n, 1, Hs, Ws] -> (uint8 [n, H, W] or None, fp32 [n, 1, H, W] or
-        None); with auto_hdr the bounds are first updated from this frame."""
-        if torch.is_tensor(img) and img.dim() == 4 and img.shape[0] != self.n:
-            raise hip.EssHipError(f'IntensityRescaler: made for {self.n} samples, got {img.shape[0]}')
+        None); with auto_hdr the bounds are first updated from this frame.
+        mode / rows (default None: the call above, launch for launch): the steered call of a multi-stream round.  `n` is then the number
+        of history ROWS and img holds N SLOTS (N <= n with rows, N == n without); mode int32 [N] on the device: CARRY_TAKE -- the slot's
+        history row takes this frame --, CARRY_ZERO -- the row is emptied first (the restart) --, anything else: the slot is skipped, no
+        history moves and its output rows are unspecified; rows int32 [N] on the device (or a host list): the history row of each slot,
+        default the slot's number.  bounds and workspace are indexed by slot: their first N entries are used.  With fixed bounds only
+        the steered frame launch runs."""
+        if mode is None:
+            if rows is not None:
+                raise hip.EssHipError('IntensityRescaler: rows= belongs to the steered call: pass mode= with it')
+            if torch.is_tensor(img) and img.dim() == 4 and img.shape[0] != self.n:
+                raise hip.EssHipError(f'IntensityRescaler: made for {self.n} samples, got {img.shape[0]}')
+            if self.auto_hdr:
+                hip.recon_post_bounds(img, weights, amount, self.workspace, self.ring, self.ring_state, int(self.auto_hdr_median_filter_size),
+                                      self.bounds)
+            return hip.recon_post_frame(img, weights, amount, self.bounds, window=window, want_u8=want_u8, want_f32=want_f32)
+        N = img.shape[0] if torch.is_tensor(img) and img.dim() == 4 else self.n
+        if N > self.n or (rows is None and N != self.n):
+            raise hip.EssHipError(f'IntensityRescaler: made for {self.n} history rows, got {N} slots' + (' without rows=' if N < self.n else ''))
         if self.auto_hdr:
-            hip.recon_post_bounds(img, weights, amount, self.workspace, self.ring, self.ring_state, int(self.auto_hdr_median_filter_size),
-                                  self.bounds)
-        return hip.recon_post_frame(img, weights, amount, self.bounds, window=window, want_u8=want_u8, want_f32=want_f32)
+            hip.recon_post_bounds(img, weights, amount, self.workspace[:N], self.ring, self.ring_state, int(self.auto_hdr_median_filter_size),
+                                  self.bounds[:N], mode=mode, rows=rows)
+        elif rows is not None and not torch.is_tensor(rows) and len(rows) != N:
+            raise hip.EssHipError(f'IntensityRescaler: rows has {len(rows)} entries for {N} slots')
+        return hip.recon_post_frame(img, weights, amount, self.bounds[:N], window=window, want_u8=want_u8, want_f32=want_f32, mode=mode)
 
     def __call__(self, img):
         """the reference's call: fp32 [n, 1, H, W] in [0, 1] -> float(uint8) / 255"""

@@ -86,6 +86,7 @@ EXPORTS = [
     'ess_event_scatter_store', 'ess_event_store_windows',
     'ess_event_ingest_store', 'ess_event_store_pixel_counts', 'ess_event_count_mask',
     'ess_recon_post_frame', 'ess_recon_post_bounds', 'ess_event_preview',
+    'ess_recon_post_frame_steered', 'ess_recon_post_bounds_steered',
     'ess_viz_semseg', 'ess_viz_events', 'ess_viz_overlay',
     'ess_image_ingest', 'ess_augment_image_label_store',
 ]
@@ -212,6 +213,8 @@ def lib():
             'ess_event_count_mask': [P, I, I, I, P, P, I, P],
             'ess_recon_post_frame': [P, P, F, F, P, P, P, I, I, I, I, I, I, I, P],
             'ess_recon_post_bounds': [P, P, F, F, I, I, I, P, c_size_t, P, P, I, P, P],
+            'ess_recon_post_frame_steered': [P, P, F, F, P, P, P, I, I, I, I, I, I, I, P, P],
+            'ess_recon_post_bounds_steered': [P, P, F, F, I, I, I, P, c_size_t, P, P, I, I, P, P, P, P],
             'ess_event_preview': [P, P, I, I, I, I, I, I, P],
             'ess_viz_semseg': [P, I, P, P, c_size_t, POINTER(EssVizDst), I, I, I, I, I, P],
             'ess_viz_events': [P, P, c_size_t, POINTER(EssVizDst), I, I, I, I, I, I, P],
@@ -2121,13 +2124,24 @@ def _recon_post_image(fn, img, weights, amount):
     return img.shape[0], img.shape[2], img.shape[3], w, c1, float(np.float32(amount))
 
 
-def recon_post_frame(img, weights, amount, bounds, window=None, out_u8=None, out_f32=None, want_u8=True, want_f32=False):
+def _steer_words(fn, name, t, N):
+    """a steering table of a steered recon_post call: int32 [N], contiguous (its memory is _on_device's question)"""
+    if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != (N,) or not t.is_contiguous():
+        got = f'{t.dtype}{tuple(t.shape)}' if torch.is_tensor(t) else type(t).__name__
+        raise EssHipError(f'{fn}: {name} must be a contiguous int32 [{N}] tensor (one word per slot), got {got}')
+    return t
+
+
+def recon_post_frame(img, weights, amount, bounds, window=None, out_u8=None, out_f32=None, want_u8=True, want_f32=False, mode=None):
     """Unsharp mask + intensity rescale + 8-bit quantisation in one pass (ess_recon_post_frame) -> (frame_u8 [N, H, W] uint8 or None,
     frame_f32 [N, 1, H, W] = float(u8) / 255 or None).  img: fp32 [N, 1, Hs, Ws]; weights: the 5 x 5 Gaussian (host values; unused for
     amount <= 0, which skips the stencil); bounds: fp32 [N, 2] ON THE DEVICE = (Imin, Imax - Imin) per sample; window (y0, x0, H, W): the
     part of the source that is written (default: all) -- the stencil still sees the whole source, zero beyond its borders.  out_u8 /
     out_f32: the caller's output tensors.  Per pixel, in fp32 without fused operations: blur = sum of w * v in row-major tap order,
-    s = c1 v - amount blur, q = (255 (s - Imin)) / range, clamped to [0, 255] and truncated.  A NaN pixel gives 0."""
+    s = c1 v - amount blur, q = (255 (s - Imin)) / range, clamped to [0, 255] and truncated.  A NaN pixel gives 0.
+    mode (default None: the call above, launch for launch): int32 [N] ON THE DEVICE, one word per slot (ess_recon_post_frame_steered): a
+    slot whose word is neither CARRY_TAKE nor CARRY_ZERO is neither read nor written -- its rows of out_u8 / out_f32 keep what they
+    held (of a tensor allocated here: unspecified) --, every other slot gets the unsteered call's bits."""
     fn = 'recon_post_frame'
     N, Hs, Ws, w, c1, amount = _recon_post_image(fn, img, weights, amount)
     y0, x0, H, W = (0, 0, Hs, Ws) if window is None else (int(v) for v in window)
@@ -2140,34 +2154,76 @@ def recon_post_frame(img, weights, amount, bounds, window=None, out_u8=None, out
         _formed(fn, 'out_u8', out_u8, torch.uint8, (N, H, W))
     if out_f32 is not None:
         _formed(fn, 'out_f32', out_f32, torch.float32, (N, 1, H, W))
-    _on_device(fn, [(k, v) for k, v in (('img', img), ('bounds', bounds), ('out_u8', out_u8), ('out_f32', out_f32)) if v is not None])
+    if mode is not None:
+        _steer_words(fn, 'mode', mode, N)
+    _on_device(fn, [(k, v) for k, v in (('mode', mode), ('img', img), ('bounds', bounds), ('out_u8', out_u8), ('out_f32', out_f32))
+                    if v is not None])
     if out_u8 is None and want_u8:
         out_u8 = torch.empty(N, H, W, dtype=torch.uint8, device=img.device)
     if out_f32 is None and want_f32:
         out_f32 = torch.empty(N, 1, H, W, dtype=torch.float32, device=img.device)
+    if mode is not None:
+        _check(lib().ess_recon_post_frame_steered(ptr(img), w, c1, amount, ptr(bounds), ptr(out_u8, torch.uint8), ptr(out_f32), N, Hs, Ws,
+                                                  y0, x0, H, W, ptr(mode, torch.int32), stream()), 'ess_recon_post_frame_steered')
+        return out_u8, out_f32
     _check(lib().ess_recon_post_frame(ptr(img), w, c1, amount, ptr(bounds), ptr(out_u8, torch.uint8), ptr(out_f32), N, Hs, Ws, y0, x0, H, W,
                                       stream()), 'ess_recon_post_frame')
     return out_u8, out_f32
 
 
-def recon_post_bounds(img, weights, amount, workspace, ring, ring_state, filter_size, bounds):
+def recon_post_bounds(img, weights, amount, workspace, ring, ring_state, filter_size, bounds, mode=None, rows=None):
     """The auto-HDR step of IntensityRescaler with its history on the device (ess_recon_post_bounds; two launches, no
     synchronisation): min / max of the SHARPENED source per sample -> clip to [0, 0.45] / [0.55, 1] in fp64 -> push into the sample's
     history (ring fp64 [N, filter_size + 1, 2], ring_state int32 [N, 2] = (head, count); zeros = empty) -> bounds[n] = (median of the
     held mins, median of the held maxs minus it), np.median's rule.  workspace: fp32 [N, RECON_POST_PARTIALS, 2], fully rewritten.
-    Deviation: NaN pixels are skipped by the min / max (torch.min / max would hand NaN on)."""
+    Deviation: NaN pixels are skipped by the min / max (torch.min / max would hand NaN on).
+    mode / rows (default None, None: the call above, launch for launch; rows needs mode): the step STEERED per slot
+    (ess_recon_post_bounds_steered).  img then holds N SLOTS, workspace [N, PARTIALS, 2] and bounds [N, 2] are indexed by slot, ring
+    [R, filter_size + 1, 2] and ring_state [R, 2] hold R history ROWS (without rows: R == N and slot n's row is n).  mode: int32 [N] ON
+    THE DEVICE -- CARRY_TAKE: the step above on the slot's row; CARRY_ZERO: the same from an EMPTIED history (the restart);
+    CARRY_HOLD, any other word, or a row outside [0, R): the slot is skipped -- no image read, its workspace, bounds and every history
+    untouched.  rows: int32 [N] on the device, or a host list of N ints (checked here: two slots naming one row are refused; then
+    uploaded, which a capture cannot record -- a captured caller hands a device tensor whose rows are distinct by construction)."""
     fn = 'recon_post_bounds'
     N, Hs, Ws, w, c1, amount = _recon_post_image(fn, img, weights, amount)
+    if rows is not None and mode is None:
+        raise EssHipError(f'{fn}: rows= belongs to the steered step: pass mode= (int32 [{N}] on the device) with it')
+    R = N
+    if mode is not None:
+        _steer_words(fn, 'mode', mode, N)
+        if not torch.is_tensor(ring_state) or ring_state.dim() != 2 or ring_state.shape[0] < 1:
+            got = f'{ring_state.dtype}{tuple(ring_state.shape)}' if torch.is_tensor(ring_state) else type(ring_state).__name__
+            raise EssHipError(f'{fn}: ring_state must be an int32 [R, 2] tensor of R >= 1 history rows, got {got}')
+        if rows is not None:
+            R = ring_state.shape[0]
+            if not torch.is_tensor(rows):
+                if isinstance(rows, (str, bytes)) or not hasattr(rows, '__len__') or len(rows) != N or \
+                        any(isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not -2 ** 31 <= r < 2 ** 31 for r in rows):
+                    raise EssHipError(f'{fn}: rows must be an int32 [{N}] device tensor or a host list of {N} ints, got {rows!r}')
+                named = [int(r) for r in rows if 0 <= r < R]
+                if len(set(named)) != len(named):
+                    raise EssHipError(f'{fn}: rows={list(rows)} names a history row twice: one call takes one frame per row')
+            else:
+                _steer_words(fn, 'rows', rows, N)
     if isinstance(filter_size, bool) or int(filter_size) != filter_size or not 0 <= filter_size <= RECON_POST_MAX_FILTER:
         raise EssHipError(f'{fn}: filter_size={filter_size} outside 0..{RECON_POST_MAX_FILTER}')
     filter_size = int(filter_size)
     if N > 65535:
         raise EssHipError(f'{fn}: N={N} samples, at most 65535')
     for name, t, dtype, shape in (('workspace', workspace, torch.float32, (N, RECON_POST_PARTIALS, 2)),
-                                  ('ring', ring, torch.float64, (N, filter_size + 1, 2)),
-                                  ('ring_state', ring_state, torch.int32, (N, 2)), ('bounds', bounds, torch.float32, (N, 2))):
+                                  ('ring', ring, torch.float64, (R, filter_size + 1, 2)),
+                                  ('ring_state', ring_state, torch.int32, (R, 2)), ('bounds', bounds, torch.float32, (N, 2))):
         _formed(fn, name, t, dtype, shape)
-    _on_device(fn, (('img', img), ('workspace', workspace), ('ring', ring), ('ring_state', ring_state), ('bounds', bounds)))
+    steer = [(k, v) for k, v in (('mode', mode), ('rows', rows)) if torch.is_tensor(v)]
+    _on_device(fn, steer + [('img', img), ('workspace', workspace), ('ring', ring), ('ring_state', ring_state), ('bounds', bounds)])
+    if mode is not None:
+        if rows is not None and not torch.is_tensor(rows):
+            rows = torch.tensor([int(r) for r in rows], dtype=torch.int32).to(img.device)
+        _check(lib().ess_recon_post_bounds_steered(ptr(img), w, c1, amount, N, Hs, Ws, ptr(workspace), c_size_t(workspace.numel() * 4),
+                                                   ptr(ring, torch.float64), ptr(ring_state, torch.int32), R, filter_size, ptr(bounds),
+                                                   ptr(mode, torch.int32), ptr(rows, torch.int32), stream()),
+               'ess_recon_post_bounds_steered')
+        return bounds
     _check(lib().ess_recon_post_bounds(ptr(img), w, c1, amount, N, Hs, Ws, ptr(workspace), c_size_t(workspace.numel() * 4),
                                        ptr(ring, torch.float64), ptr(ring_state, torch.int32), filter_size, ptr(bounds), stream()),
            'ess_recon_post_bounds')

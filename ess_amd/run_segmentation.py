@@ -36,6 +36,16 @@ the batch's compute.  With compact=True a round runs only its A active streams, 
 padded slots arriving as zeros, the step runs at the bucket's batch size, and an indexed scatter takes the new states home.  The
 plan of such a round is a function on host lists (compact_plan); a round with more active streams than the largest bucket rides
 along as before.
+
+MultiStreamSegmenter(reconstruct=True, postprocess=True, overlay=alpha) is the display of a rig: beside the labels a round returns,
+per stream, the E2VID image (the FULL recurrent step in place of the encoder-only one, on the same encoder pass), the displayable
+uint8 frame (PostProcessor.process_u8: unsharp mask, auto-HDR rescale) and the label overlay (hip.viz_overlay), inside the one
+captured graph.  Every stream has its own auto-HDR history in device memory, and the round steers them by words in device memory as
+it steers the state (display_words; hip.recon_post_bounds(mode=, rows=) / hip.recon_post_frame(mode=)): the history of an idle
+stream does not move -- a zero grid's blank frame never enters its bounds --, the history of a stream whose restart is carried out in
+this round is emptied first, and a compacted round names each slot's history by an index table.  Captures and warm_up() run with
+every history on HOLD.  Out of scope: SequenceSegmenter (its rounds score labels, nobody looks at them), image writers and
+displays, and the bilateral filter (ImageFilter refuses it, as for the single-stream driver).
 """
 import collections
 
@@ -212,15 +222,19 @@ class StreamingSegmenter(GraphedWindowState):
 # ---------------------------------------------------------------------------------------------- S streams in one batch
 class MultiSegmentationResult:
     """labels uint8 [S, H, W]; colour uint8 [S, H, W, 3] or None (no palette); confidence fp32 [S, H, W] or None; valid: a host
-    tuple of S bools -- stream s had a window this round.  The rows of the other (idle) streams are UNSPECIFIED."""
-    __slots__ = ('labels', 'colour', 'confidence', 'valid')
+    tuple of S bools -- stream s had a window this round.  With MultiStreamSegmenter(reconstruct=True): image fp32 [S, 1, Hs, Ws], each
+    stream's E2VID reconstruction; (postprocess=True): frame uint8 [S, H, W], the displayable frames; (overlay=alpha): overlay uint8
+    [S, H, W, 3], the label colours over the frames -- each None where it was not asked for.  The rows of the other (idle) streams
+    are UNSPECIFIED, in every tensor."""
+    __slots__ = ('labels', 'colour', 'confidence', 'valid', 'image', 'frame', 'overlay')
 
-    def __init__(self, labels, colour=None, confidence=None, valid=()):
+    def __init__(self, labels, colour=None, confidence=None, valid=(), image=None, frame=None, overlay=None):
         self.labels, self.colour, self.confidence, self.valid = labels, colour, confidence, tuple(bool(v) for v in valid)
+        self.image, self.frame, self.overlay = image, frame, overlay
 
     def clone(self):
-        return MultiSegmentationResult(*(None if t is None else t.clone() for t in (self.labels, self.colour, self.confidence)),
-                                       valid=self.valid)
+        c = [None if t is None else t.clone() for t in (self.labels, self.colour, self.confidence, self.image, self.frame, self.overlay)]
+        return MultiSegmentationResult(*c[:3], valid=self.valid, image=c[3], frame=c[4], overlay=c[5])
 
 
 def stream_modes(pending, active):
@@ -281,6 +295,25 @@ def compact_plan(pending, active, buckets):
                        gather_src=[hip.CARRY_SRC_ZERO if pending[s] else s for s in rows] + [hip.CARRY_SRC_ZERO] * pad,
                        norm_mode=[1] * A + [0] * pad, scatter_dst=rows + [SCATTER_SKIP] * pad, scatter_src=list(range(b)),
                        pending_after=[bool(p and not a) for p, a in zip(pending, active)])
+
+
+def display_words(pending, active, plan=None):
+    """The display words of one round, from host lists -> (words, rows): what steers the auto-HDR histories of the round's frames
+    (PostProcessor.process_u8(mode=words, rows=rows)).  pending: the restart flags IN FRONT of the round.  A slot's word is CARRY_ZERO
+    where its stream restarts now (pending and active: the history empties and takes this frame), CARRY_TAKE where it is active,
+    CARRY_HOLD otherwise -- a pending restart of an idle stream stays pending, and its history stays as it is until then.
+    plan None (a ride-along round): one word per stream, rows None (slot s holds stream s).  plan: a CompactPlan of the same
+    lists: one word and one history row per SLOT -- the row is the stream's number; a padded slot gets CARRY_HOLD and the row
+    SCATTER_SKIP, which lies outside every history."""
+    if len(pending) != len(active):
+        raise hip.EssHipError(f'display_words: {len(pending)} pending flags for {len(active)} streams')
+    word = [hip.CARRY_HOLD if not a else (hip.CARRY_ZERO if p else hip.CARRY_TAKE) for p, a in zip(pending, active)]
+    if plan is None:
+        return word, None
+    if plan.rows != [s for s, a in enumerate(active) if a]:
+        raise hip.EssHipError(f'display_words: the plan serves streams {plan.rows}, active says {[s for s, a in enumerate(active) if a]}')
+    pad = plan.bucket - len(plan.rows)
+    return [word[s] for s in plan.rows] + [hip.CARRY_HOLD] * pad, list(plan.rows) + [SCATTER_SKIP] * pad
 
 
 def check_active(active, n_streams):
@@ -613,14 +646,38 @@ class MultiStreamSegmenter(GraphedWindowState):
     the same object share one device copy.  The masks live in one static buffer of n_streams slots; a stream's mask word travels
     with its count and format (the words grow to [4, S] / [6, S], the map words always among them), and a compacted round writes
     it per slot.  set_hot_pixels(stream, mask | None) and calibrate_hot_pixels(...) change masks between rounds without a
-    re-capture.  The window's time base still counts the hot events, as the reference's does."""
+    re-capture.  The window's time base still counts the hot events, as the reference's does.
+
+    The display (all off by default: a round is then launch for launch what it was, and the mode words and bucket tables keep their
+    shapes; orthogonal to everything above -- the keywords only add to the tail of the round), with StreamingSegmenter's rules and
+    refusals:
+    reconstruct=True   the round's recurrent step is the FULL one; the result carries `image` fp32 [S, 1, Hs, Ws].  Labels, colours
+                       and confidences stay bit-identical to the plain driver's.
+    postprocess=True   (needs reconstruct) `frame` uint8 [S, H, W]: PostProcessor.process_u8 of each stream's image, cropped to the
+                       sensor, with ONE auto-HDR history per stream (a PostProcessor(n=S) of the driver's).  A history takes a frame only
+                       in a round its stream is active in; reset(streams) stays a pending flag, and a stream's history empties in
+                       the round its restart is carried out, not before.  A third row of mode words carries that (display_words); in
+                       a compacted round the bucket table gains the display word and the history row of every slot.  Captures and
+                       warm_up() move no history: every stream is on HOLD during them, nothing is saved or restored.
+    overlay=alpha      (needs postprocess and a palette; labels at the frames' size) `overlay` uint8 [S, H, W, 3]: hip.viz_overlay.
+    Rows of idle streams are unspecified in all three, as in the labels."""
 
     def __init__(self, encoder, decoder, height, width, options, n_streams, device=None, graph=False, copy=True, palette=None,
                  want_confidence=False, out_hw=None, compact=False, compact_buckets=None, event_capacity=None, event_layout='records',
                  ring_capacity=None, window_events=None, window_duration=None, window_stride=None, voxel='temporal', rectify_maps=None,
-                 representation=None, hot_pixel_masks=None):
+                 representation=None, hot_pixel_masks=None, reconstruct=False, postprocess=False, overlay=None):
         if not isinstance(n_streams, int) or isinstance(n_streams, bool) or n_streams < 1:
             raise hip.EssHipError(f'n_streams={n_streams!r}: a positive number of streams is needed')
+        if postprocess and not reconstruct:  # (the display's refusals are StreamingSegmenter's, made before the models reach the device)
+            raise hip.EssHipError('MultiStreamSegmenter: postprocess=True needs reconstruct=True (the frames are made from the images)')
+        if overlay is not None:
+            if not postprocess or palette is None:
+                raise hip.EssHipError('MultiStreamSegmenter: overlay= needs postprocess=True (the frames) and a palette (the colours)')
+            if not 0.0 <= float(overlay) <= 1.0:
+                raise hip.EssHipError(f'MultiStreamSegmenter: overlay={overlay} outside [0, 1]')
+            if out_hw is not None and (int(out_hw[0]), int(out_hw[1])) != (height, width):
+                raise hip.EssHipError(f'MultiStreamSegmenter: overlay= needs labels at the frames\' size {(height, width)}, out_hw is '
+                                      f'{tuple(out_hw)}')
         if hot_pixel_masks is not None:  # (refused before the models reach the device)
             if event_capacity is None or event_layout not in ('columns', 'ring'):
                 raise hip.EssHipError(f"hot_pixel_masks are applied to raw events, where (x, y) is still the sensor's pixel: that needs the "
@@ -660,7 +717,11 @@ class MultiStreamSegmenter(GraphedWindowState):
         self.compute = hip.compute_name()
         S = n_streams
         self._in = torch.zeros(S, self.num_bins, height, width, dtype=torch.float32, device=self.device)
-        self._modes = torch.zeros(2, S, dtype=torch.int32, device=self.device)  # [0]: in front of the step, [1]: behind it
+        self.reconstruct = bool(reconstruct)
+        self.post = PostProcessor(self.device, options, n=S, crop=crop) if postprocess else None  # (one history per STREAM)
+        self.overlay_alpha = None if overlay is None else float(overlay)
+        # [0]: in front of the step, [1]: behind it; postprocess: [2]: the display word of each stream's auto-HDR history
+        self._modes = torch.zeros(3 if postprocess else 2, S, dtype=torch.int32, device=self.device)
         self._pending = [True] * S
         self.event_layout = _event_layout(event_layout, event_capacity)
         self.event_capacity = None if event_capacity is None else _event_capacity(event_capacity, height, width)
@@ -1054,21 +1115,35 @@ class MultiStreamSegmenter(GraphedWindowState):
 
     @classmethod
     def from_checkpoints(cls, e2vid_path, ess_checkpoint_path, settings_or_kwargs, n_streams, **kw):
-        """as StreamingSegmenter.from_checkpoints, plus the number of streams (compact, compact_buckets: keyword arguments)"""
+        """as StreamingSegmenter.from_checkpoints, plus the number of streams (compact, compact_buckets, reconstruct, postprocess,
+        overlay, ...: keyword arguments, handed to the constructor)"""
         encoder, decoder, height, width, options, palette = _models_from_checkpoints(e2vid_path, ess_checkpoint_path, settings_or_kwargs)
         kw.setdefault('palette', palette)
         return cls(encoder, decoder, height, width, options, n_streams, **kw)
 
     # ---- state: static [S, ...] buffers from construction, never None
     def _step(self, ev, carried=None):
-        """one encoder-only step of the whole batch from the carried state (carried: a compact batch's work state instead); the
-        carried state stays the static buffers"""
+        """one encoder-only step of the whole batch from the carried state (carried: a compact batch's work state instead) --
+        reconstruct: the FULL step on the same encoder pass, as StreamingSegmenter._window runs it -> (states, latent, image or
+        None); the carried state stays the static buffers"""
         rec = self.rec
         if carried is not None:
             rec.last_states_for_each_channel['grayscale'] = carried
-        _, states, latent = rec._step(ev, False, False, final_lean=not hip.mixed())
+        img, states, latent = rec._step(ev, self.reconstruct, False, final_lean=not hip.mixed())
         rec.last_states_for_each_channel['grayscale'] = self._carried
-        return states, latent
+        return states, latent, img
+
+    def _display(self, out, img, mode, rows=None):
+        """the tail of a round behind predict: (labels, colour, confidence) -> + (image, frame, overlay) where the display is on.
+        mode / rows steer the auto-HDR histories: only the streams that advance in this round push their frame."""
+        if not self.reconstruct:
+            return out
+        frame = None if self.post is None else self.post.process_u8(img, mode=mode, rows=rows)
+        over = None if self.overlay_alpha is None else hip.viz_overlay(out[0], frame, self.palette, self.overlay_alpha)
+        return tuple(out) + (img, frame, over)
+
+    def _result(self, out, active):
+        return MultiSegmentationResult(*out[:3], valid=active, **dict(zip(('image', 'frame', 'overlay'), out[3:])))
 
     def _build_state(self):
         """Learn the state's forms from the zero-input step (run once without and once WITH a state: the form must be a fixed point of
@@ -1080,10 +1155,10 @@ class MultiStreamSegmenter(GraphedWindowState):
             ev = rec.crop.pad(self._in)
             if not ev.is_contiguous():
                 ev = ev.contiguous()
-            states, _ = self._step(ev)
+            states = self._step(ev)[0]
             self._adopt_state(states)  # (allocates the static buffers in the forms this step left)
             self._carried = rec.last_states_for_each_channel['grayscale']
-            states, _ = self._step(ev)
+            states = self._step(ev)[0]
             self._src_parts(states)  # (raises when the with-state step leaves another form)
         self._dst = [st[0][k] for st in self._static for k in _PARTS if st[0][k] is not None]
         self._pre = hip.StateCarryTable(self._dst)  # (no source: ZERO / HOLD)
@@ -1126,29 +1201,32 @@ class MultiStreamSegmenter(GraphedWindowState):
                 static.append(st)
             carried = [st[3] if st[0]['c'] is None else (st[3], st[0]['c']) for st in static]
             wdst = [st[0][k] for st in static for k in _PARTS if st[0][k] is not None]
-            # rows: gather_dst, gather_src, norm_mode, scatter_dst, scatter_src
-            tab = torch.zeros(5, b, dtype=torch.int32, device=self.device)
+            # rows: gather_dst, gather_src, norm_mode, scatter_dst, scatter_src; postprocess: + the display word and history row
+            tab = torch.zeros(5 if self.post is None else 7, b, dtype=torch.int32, device=self.device)
             self._bucket[b] = (static, carried, hip.StateMoveTable(wdst, self._dst), tab)
             self._idle_tables(b)
             with torch.no_grad():
                 ev = self.rec.crop.pad(self.compact_input[:b])
                 if not ev.is_contiguous():
                     ev = ev.contiguous()
-                states, _ = self._step(ev, carried)
+                states = self._step(ev, carried)[0]
                 self._src_parts(states, static)  # (raises when the step at batch b leaves another form)
 
     def _idle_tables(self, b):
         """bucket b's tables for a round that touches nothing at home: every slot padded"""
-        plan = compact_plan([False] * self.n_streams, [False] * self.n_streams, (b,))
-        self._write_tables(plan)
+        idle = [False] * self.n_streams
+        plan = compact_plan(idle, idle, (b,))
+        self._write_tables(plan, display_words(idle, idle, plan))  # (no history moves either: every slot on HOLD)
 
-    def _write_tables(self, plan):
+    def _write_tables(self, plan, display):
         rows = [plan.gather_dst, plan.gather_src, plan.norm_mode, plan.scatter_dst, plan.scatter_src]
+        if self.post is not None:
+            rows += list(display)
         self._bucket[plan.bucket][3].copy_(torch.tensor(rows, dtype=torch.int32), non_blocking=True)
 
     def _round_compact(self, b):
         """the device work of one compacted round at batch b on the static compact input and bucket b's index tables
-        -> (labels, colour, confidence) of the b slots"""
+        -> (labels, colour, confidence) of the b slots (+ image, frame, overlay: _display)"""
         rec, pre = self.rec, self.rec.event_preprocessor
         static, carried, gather, tab = self._bucket[b]
         with torch.no_grad():
@@ -1163,11 +1241,12 @@ class MultiStreamSegmenter(GraphedWindowState):
             ev = rec.crop.pad(hip.event_normalize_samples(ev, tab[2]))  # (padded slots: a zero grid)
             if not ev.is_contiguous():
                 ev = ev.contiguous()
-            states, latent = self._step(ev, carried)
+            states, latent, img = self._step(ev, carried)
             src = self._src_parts(states, static)
             self.last_latent = latent
             out = self.decoder.predict(latent, out_hw=self.out_hw, window=self.window, palette=self.palette,
                                        want_confidence=self.want_confidence)
+            out = self._display(out, img, *((tab[5], tab[6]) if self.post is not None else (None,)))
             hip.StateMoveTable(self._dst, src).run(tab[3], tab[4])  # stream <- its slot's new state; padded slots skipped
         return out
 
@@ -1207,10 +1286,11 @@ class MultiStreamSegmenter(GraphedWindowState):
         compact grids [bucket, ...] themselves, or None: the round's ingest builds them from the staged records.  stage: the
         ingest's staging set of this round (event_capacity)"""
         b, A = plan.bucket, len(plan.rows)
+        display = display_words(self._pending, active, plan)  # (from the restart flags in FRONT of the round)
         self._pending = plan.pending_after
         if self.use_graph and b not in self._cg:
             self._capture_compact(b)
-        self._write_tables(plan)
+        self._write_tables(plan, display)
         if stage is not None:
             self._upload(stage)
         if grids is None:
@@ -1238,7 +1318,7 @@ class MultiStreamSegmenter(GraphedWindowState):
             for r, t in zip(res, out):
                 if t is not None:
                     r.index_copy_(0, rows, t[:A])
-        return MultiSegmentationResult(*res, valid=active)
+        return self._result(res, active)
 
     _cres = None
 
@@ -1250,7 +1330,8 @@ class MultiStreamSegmenter(GraphedWindowState):
 
     # ---- one round
     def _round(self):
-        """the device work of one round on the static input and mode buffers -> (labels, colour, confidence)"""
+        """the device work of one round on the static input and mode buffers -> (labels, colour, confidence) (+ image, frame,
+        overlay: _display)"""
         rec, pre = self.rec, self.rec.event_preprocessor
         with torch.no_grad():
             self._pre.run(self._modes[0])  # restarting streams: state = 0
@@ -1264,17 +1345,19 @@ class MultiStreamSegmenter(GraphedWindowState):
             ev = rec.crop.pad(hip.event_normalize_samples(ev, self._modes[1]))  # (idle streams: a zero grid)
             if not ev.is_contiguous():
                 ev = ev.contiguous()
-            states, latent = self._step(ev)
+            states, latent, img = self._step(ev)
             src = self._src_parts(states)  # (taken in front of predict, which may attach further copies to the latents)
             self.last_latent = latent
             out = self.decoder.predict(latent, out_hw=self.out_hw, window=self.window, palette=self.palette,
                                        want_confidence=self.want_confidence)
+            out = self._display(out, img, self._modes[2] if self.post is not None else None)
             hip.StateCarryTable(self._dst, src).run(self._modes[1])  # active streams: state = new state
         return out
 
     def _capture(self):
         """GraphedWindowState's recipe -- one eager run on a side stream, then the recording on the current stream -- with the
-        warm-up run's effect on the state avoided instead of undone: every stream is on HOLD during it."""
+        warm-up run's effect on the state avoided instead of undone: every stream is on HOLD during it (the display word too: no
+        auto-HDR history moves)."""
         self._modes.zero_()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -1307,10 +1390,11 @@ class MultiStreamSegmenter(GraphedWindowState):
     def _ride_along(self, grids, active, stage=None):
         """one round at the full batch; grids None: the round's ingest builds them from the staged records.  stage: the ingest's
         staging set of this round (event_capacity)"""
+        words = [display_words(self._pending, active)[0]] if self.post is not None else []
         pre, post, self._pending = stream_modes(self._pending, active)
         if self.use_graph and self._g is None:
             self._capture()
-        self._modes.copy_(torch.tensor([pre, post], dtype=torch.int32), non_blocking=True)
+        self._modes.copy_(torch.tensor([pre, post] + words, dtype=torch.int32), non_blocking=True)
         if stage is not None:
             self._upload(stage)
         if grids is not None:
@@ -1321,7 +1405,7 @@ class MultiStreamSegmenter(GraphedWindowState):
         else:
             out = self._round()
         self.n_windows += 1
-        res = MultiSegmentationResult(*out, valid=active)
+        res = self._result(out, active)
         return res.clone() if (self.use_graph and self.copy_outputs) else res
 
     def update_from_events(self, events):

@@ -879,7 +879,8 @@ int ess_recon_post_frame(const float* img, const float* weights, float c1, float
 
 /* The auto-HDR step of IntensityRescaler with its state in device memory, two launches:
  * (a) min / max of s over the WHOLE source plane of each sample (NaN pixels skipped -- fminf / fmaxf; torch.min / max would return
- *     NaN), one partial pair per workgroup: workspace fp32 [N][ESS_RECON_POST_PARTIALS][2], every slot written on every call;
+ *     NaN), one partial pair per workgroup: workspace fp32 [N][ESS_RECON_POST_PARTIALS][2], every slot written on every call
+ *     (of THIS entry point; the steered one below writes the taken slots only);
  * (b) per sample, in fp64: Imin = clip(min, 0, 0.45), Imax = clip(max, 0.55, 1); the pair is pushed into the sample's history -- ring
  *     fp64 [N][filter_size + 1][2], ring_state int32 [N][2] = (head, count): the reference pops only when the history is LONGER than
  *     filter_size, so it settles at filter_size + 1 entries --; bounds[n] = ((float)median(mins), (float)(median(maxs) - median(mins)))
@@ -890,6 +891,33 @@ int ess_recon_post_frame(const float* img, const float* weights, float c1, float
 int ess_recon_post_bounds(const float* img, const float* weights, float c1, float amount, int32_t N, int32_t Hs, int32_t Ws,
                           float* workspace, size_t workspace_bytes, double* ring, int32_t* ring_state, int32_t filter_size,
                           float* bounds, ess_stream_t stream);
+
+/* The two calls above STEERED per slot of the batch by words in device memory -- what a multi-stream round needs, whose one captured
+ * graph serves every mix of advancing, idle and restarting streams.  PURELY ADDITIVE to ABI 110: ess_version() is unchanged, and the
+ * unsteered entry points keep their signatures and their kernels.
+ *
+ * ess_recon_post_bounds_steered: img fp32 [N][1][Hs][Ws] holds N SLOTS; workspace fp32 [N][ESS_RECON_POST_PARTIALS][2] and bounds fp32
+ * [N][2] are indexed by slot (bounds[n] is what the frame call reads for slot n); ring fp64 [R][filter_size + 1][2] and ring_state int32
+ * [R][2] hold R HISTORY ROWS.  mode int32 [N] and rows int32 [N] lie in device memory; rows == NULL: the row of slot n is n.  Per slot
+ * n, with r = rows ? rows[n] : n:
+ *   mode[n] == ESS_CARRY_TAKE (1)   ess_recon_post_bounds' step on history row r, expression for expression; the new pair -> bounds[n];
+ *   mode[n] == ESS_CARRY_ZERO (2)   the same with head = count = 0 taken in place of the stored state: the restart -- the history is
+ *                                   emptied, then takes this frame;
+ *   ESS_CARRY_HOLD (0), any other word, or r outside [0, R)
+ *                                   the slot is skipped: its min / max workgroups return after reading the words (no image read, no
+ *                                   workspace write), its wave of the median pass returns; no ring, state or bounds is touched.
+ * So the workspace slots of the TAKEN slots only are written by a call (the unsteered call writes every slot).  Two taken slots that
+ * name one row in one call are the caller's error (the row's history is then that of either).  R >= 1; the other limits as above.
+ *
+ * ess_recon_post_frame_steered: ess_recon_post_frame plus mode int32 [N] in device memory.  A slot whose word is neither TAKE nor
+ * ZERO is neither read (image, bounds) nor written: its output rows keep what they held.  Every other slot gets ess_recon_post_frame's
+ * bits.                                                                                                                          */
+int ess_recon_post_bounds_steered(const float* img, const float* weights, float c1, float amount, int32_t N, int32_t Hs, int32_t Ws,
+                                  float* workspace, size_t workspace_bytes, double* ring, int32_t* ring_state, int32_t R,
+                                  int32_t filter_size, float* bounds, const int32_t* mode, const int32_t* rows, ess_stream_t stream);
+int ess_recon_post_frame_steered(const float* img, const float* weights, float c1, float amount, const float* bounds, uint8_t* frame_u8,
+                                 float* frame_f32, int32_t N, int32_t Hs, int32_t Ws, int32_t win_y0, int32_t win_x0, int32_t win_h,
+                                 int32_t win_w, const int32_t* mode, ess_stream_t stream);
 
 /* make_event_preview for every sample: s = sum of the last num_bins_to_show planes of grids fp32 [N][C][H][W] in plane order (fp32;
  * num_bins_to_show < 0, 0 or >= C: all planes, as the reference's slice).  ESS_PREVIEW_RED_BLUE: out uint8 [N][H][W][3] in BGR order,

@@ -24,6 +24,19 @@ same process with the same repetition scheme:
   ride_along   MultiStreamSegmenter(compact=False): the round runs all S streams, the idle ones on a zero grid;
   compact      MultiStreamSegmenter(compact=True[, compact_buckets=--buckets]): the round runs the smallest bucket >= k.
 
+--streams S[,S...] --display measures DISPLAY ROUNDS INSTEAD -- MultiStreamSegmenter(reconstruct=True, postprocess=True, overlay=0.6), auto_hdr on:
+labels plus each stream's image, displayable frame and label overlay --, every round timed from the call to the synchronised
+result, all replayed, alternating in the same process:
+
+  plain        MultiStreamSegmenter(graph=True): labels only (what the display costs is read against this);
+  image        ... (reconstruct=True): the full recurrent step, no frame;
+  display      ... (reconstruct=True, postprocess=True, overlay=0.6);
+  round_robin  S StreamingSegmenter(graph=True, reconstruct=True, postprocess=True, overlay=0.6) served one after the other.
+
+With --active k[,k...]: display rounds with k of the S streams active, compact=True against ride-along (both with the display).
+Beside them the steered launches alone at N = S, 480 x 640 (device time over 200 launches): hip.recon_post_bounds + hip.recon_post_frame
+unsteered, steered with every slot taken, and steered with 1 slot of S taken.  SLOWER is reported wherever that is the result.
+
 --streams S[,S...] --ingest measures rounds FROM HOST EVENT ARRAYS INSTEAD: per round the wall time from S numpy [N, 4] arrays in host
 memory to synchronised labels (a device synchronisation behind every round), three ways, all replayed, alternating in the same
 process with the same repetition scheme:
@@ -116,6 +129,8 @@ def main():
     ap.add_argument('--active', default=None, help='(with --streams) comma-separated counts of active streams per round: measure compacted '
                                                    'against ride-along rounds')
     ap.add_argument('--buckets', default=None, help="(with --active) the compacting segmenter's compact_buckets, comma-separated (default: its own)")
+    ap.add_argument('--display', action='store_true', help='(with --streams) display rounds: image, frame and overlay per stream, against '
+                                                           'round-robin single-stream display segmenters; with --active: compacted against ride-along')
     ap.add_argument('--ingest', action='store_true', help='(with --streams) rounds from host event arrays: event_capacity=--events against '
                                                           'event_capacity=None')
     ap.add_argument('--feed', action='store_true', help="(with --streams) rounds from a continuous packet feed: event_layout='ring' against "
@@ -145,6 +160,8 @@ def main():
         ap.error('--active needs --streams')
     if a.ingest and (not a.streams or a.active):
         ap.error('--ingest needs --streams and excludes --active')
+    if a.display and (not a.streams or a.ingest or a.feed or a.sequence is not None):
+        ap.error('--display needs --streams and excludes --ingest, --feed and --sequence')
     from ess_amd import hip
     from ess_amd.e2vid.model.model import E2VIDRecurrent
     from ess_amd.e2vid.options.inference_options import default_options
@@ -188,6 +205,10 @@ def main():
         return
     if a.feed:
         from_packet_feed(a, hip, cfg, [w.cpu().numpy() for w in wins], out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, default_options)
+        print(json.dumps(out))
+        return
+    if a.display:
+        display_rounds(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, StreamingSegmenter, default_options)
         print(json.dumps(out))
         return
     if a.ingest:
@@ -331,6 +352,115 @@ def partly_active(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiStre
                 torch.cuda.empty_cache()
         finally:
             hip.set_compute('fp32')
+
+
+def display_rounds(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, StreamingSegmenter, default_options):
+    from ess_amd.e2vid.image_reconstructor import PostProcessor
+    out['shape'] = f'S streams of {a.bins}x{a.height}x{a.width} K={a.classes}, display rounds, graph replay, synchronised per round'
+    del out['ms_per_window']
+    out['ms_per_round'], out['recon_post_pair_us'], out['SLOWER'] = {}, {}, []
+    alpha = 0.6
+    palette = torch.from_numpy(np.random.default_rng(1).integers(0, 255, (a.classes, 3)).astype(np.uint8))
+    shown = dict(reconstruct=True, postprocess=True, overlay=alpha, palette=palette)
+
+    def options():  # auto-HDR on (filter size 10, the default): the frame costs its bounds step too
+        o = default_options()
+        o.auto_hdr = True
+        return o
+
+    def models():
+        torch.manual_seed(6)
+        return E2VIDRecurrent(dict(cfg)), SemSegE2VID(256, a.classes, skip_connect=True, skip_type='concat')
+
+    def timed(step):  # every round from the call to the synchronised result
+        for i in range(a.warmup):
+            step(i)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(a.windows):
+            step(i)
+            torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / a.windows * 1e3
+
+    def measure(ways, key):
+        ms = {k: [] for k in ways}
+        for _ in range(a.reps):  # alternating: drift of the box hits every way alike
+            for k, fn in ways.items():
+                ms[k].append(timed(fn))
+        for k, v in ms.items():
+            out['ms_per_round'][f'{key}/{k}'] = {'median': round(statistics.median(v), 4), 'min': round(min(v), 4), 'max': round(max(v), 4)}
+        return {k: statistics.median(v) for k, v in ms.items()}
+
+    def pair_us(S, options):
+        """the bounds + frame launches alone, device time per pair over 200 launches"""
+        post = {k: PostProcessor(torch.device('cuda:0'), options, n=S) for k in ('unsteered', 'steered_all', 'steered_1')}
+        img = torch.rand(S, 1, a.height, a.width, device='cuda')
+        mode = {'unsteered': None, 'steered_all': torch.full((S,), hip.CARRY_TAKE, dtype=torch.int32, device='cuda'),
+                'steered_1': torch.tensor([hip.CARRY_TAKE] + [hip.CARRY_HOLD] * (S - 1), dtype=torch.int32, device='cuda')}
+        us = {k: [] for k in post}
+        for _ in range(a.reps):
+            for k, p in post.items():
+                for _ in range(20):
+                    p.process_u8(img, mode=mode[k])
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(200):
+                    p.process_u8(img, mode=mode[k])
+                e1.record()
+                torch.cuda.synchronize()
+                us[k].append(e0.elapsed_time(e1) * 1e3 / 200)
+        return {k: {'median': round(statistics.median(v), 2), 'min': round(min(v), 2), 'max': round(max(v), 2)} for k, v in us.items()}
+
+    for compute in a.compute.split(','):
+        hip.set_compute(compute)
+        try:
+            for S in (int(v) for v in a.streams.split(',')):
+                key = f'{compute}/S={S}'
+                if not a.active:
+                    multis = {'plain': MultiStreamSegmenter(*models(), a.height, a.width, options(), S, graph=True),
+                              'image': MultiStreamSegmenter(*models(), a.height, a.width, options(), S, graph=True, reconstruct=True),
+                              'display': MultiStreamSegmenter(*models(), a.height, a.width, options(), S, graph=True, **shown)}
+                    solos = [StreamingSegmenter(*models(), a.height, a.width, options(), graph=True, **shown) for _ in range(S)]
+
+                    def round_robin(i):
+                        for s, seg in enumerate(solos):
+                            seg.update_from_events(wins[(i + s) % 4])
+                    ways = {k: (lambda seg: lambda i: seg.update_from_events([wins[(i + s) % 4] for s in range(S)]))(seg)
+                            for k, seg in multis.items()}
+                    ways['round_robin'] = round_robin
+                    med = measure(ways, key)
+                    if med['display'] > med['round_robin']:
+                        out['SLOWER'].append(f'{key}: display round {med["display"]:.3f} ms against round-robin {med["round_robin"]:.3f} ms')
+                    assert all(seg.n_captures == 1 for seg in multis.values())
+                    del solos, multis, ways
+                else:
+                    segs = {'ride_along': MultiStreamSegmenter(*models(), a.height, a.width, options(), S, graph=True, **shown),
+                            'compact': MultiStreamSegmenter(*models(), a.height, a.width, options(), S, graph=True, compact=True, **shown)}
+                    for seg in segs.values():
+                        seg.warm_up()
+                    captures = {k: seg.n_captures for k, seg in segs.items()}
+                    for k_active in (int(v) for v in a.active.split(',')):
+                        if not 0 <= k_active <= S:
+                            raise SystemExit(f'--active {k_active} of --streams {S}')
+
+                        def events(i):
+                            on = {(i + j) % S for j in range(k_active)}
+                            return [wins[(i + s) % 4] if s in on else None for s in range(S)]
+                        ways = {k: (lambda seg: lambda i: seg.update_from_events(events(i)))(seg) for k, seg in segs.items()}
+                        med = measure(ways, f'{key}/active={k_active}')
+                        if med['compact'] > med['ride_along']:
+                            out['SLOWER'].append(f'{key}/active={k_active}: compact {med["compact"]:.3f} ms against ride-along {med["ride_along"]:.3f} ms')
+                    assert captures == {k: seg.n_captures for k, seg in segs.items()}  # (no round in the timed regions paid a capture)
+                    del segs, ways
+                torch.cuda.empty_cache()
+        finally:
+            hip.set_compute('fp32')
+    for S in (int(v) for v in a.streams.split(',')):
+        us = pair_us(S, options())
+        out['recon_post_pair_us'][f'N={S}'] = us
+        for k in ('steered_all', 'steered_1'):
+            if us[k]['median'] > us['unsteered']['median']:
+                out['SLOWER'].append(f'N={S}: {k} pair {us[k]["median"]} us against unsteered {us["unsteered"]["median"]} us')
 
 
 def from_host_events(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, MultiStreamSegmenter, default_options):
