@@ -15,7 +15,9 @@
 // Behind the scatter, one kernel per job: event_finish_kernel<VEC, TAP> turns sums into a grid and zeroes them where each sum has
 // one reader -- the plain ingest (TAP false) and the loader finish at the identity geometry (TAP true); grid_map_kernel<VEC,
 // IDENTITY, WINDOW> is the loader finish's crop / resize pass, with or without the training window.  One routine checks the
-// arguments of every source's entry points (check_source), one drives both loader finishes (grid_finish).
+// arguments of every source's entry points (check_source), one drives both loader finishes (grid_finish), and the twelve column,
+// ring and store entry points are wrappers that describe their call to one routine a source (ingest_call, store_call), which
+// picks the flavour through one visitor (visit_flavour).
 //
 // voxel_temporal_kernel (voxel.hip) adds its fp32 contributions with fp32 global atomics: a voxel's value depends on which event
 // got there first, two builds of one window differ in the last bits.  Here every contribution is the SAME fp32 value (the same
@@ -435,14 +437,13 @@ unsigned scatter_blocks(int64_t capacity) {
 
 // one launch for the column (RING false: rows, starts null, n_rows unused) and the ring source, in either flavour
 template <class Flavour, bool RING, class... Extra>
-int launch_scatter(const char* status, const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
-                   const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots, int32_t bins, int32_t height,
-                   int32_t width, void* acc, hipStream_t st, const Extra... extra) {
+void launch_scatter(const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
+                    const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots, int32_t bins, int32_t height,
+                    int32_t width, void* acc, hipStream_t st, const Extra... extra) {
   hipLaunchKernelGGL((event_scatter_columns_kernel<Flavour, RING, Extra...>), dim3(scatter_blocks(ring), (unsigned)n_slots),
                      dim3(INGEST_THREADS), 0, st, (const long long*)t, (const unsigned short*)x, (const unsigned short*)y,
                      (const unsigned char*)p, rows, starts, counts, formats, ring, (int)n_rows, (int)bins, (int)height, (int)width,
                      (long long*)acc, extra...);
-  return ess_launch_status(status);
 }
 
 // ---- the store source (ess_event_scatter_store): the same four columns as ONE flat set of `capacity` events, recordings laid one
@@ -508,14 +509,13 @@ __global__ __launch_bounds__(INGEST_THREADS) void event_scatter_store_kernel(con
 
 // the grid follows window_capacity, not the store's size
 template <class Flavour, class... Extra>
-int launch_scatter_store(const char* status, const void* t, const void* x, const void* y, const void* p, const int64_t* starts,
-                         const int32_t* counts, const int32_t* formats, int64_t total, int64_t window_capacity, int32_t n_slots,
-                         int32_t channels, int32_t height, int32_t width, void* acc, hipStream_t st, const Extra... extra) {
+void launch_scatter_store(const void* t, const void* x, const void* y, const void* p, const int64_t* starts, const int32_t* counts,
+                          const int32_t* formats, int64_t total, int64_t window_capacity, int32_t n_slots, int32_t channels, int32_t height,
+                          int32_t width, void* acc, hipStream_t st, const Extra... extra) {
   hipLaunchKernelGGL((event_scatter_store_kernel<Flavour, Extra...>), dim3(scatter_blocks(window_capacity), (unsigned)n_slots),
                      dim3(INGEST_THREADS), 0, st, (const long long*)t, (const unsigned short*)x, (const unsigned short*)y,
                      (const unsigned char*)p, (const long long*)starts, counts, formats, total, window_capacity, (int)channels,
                      (int)height, (int)width, (long long*)acc, extra...);
-  return ess_launch_status(status);
 }
 
 // ---- plain per-pixel counts of an index range of the store (ess_event_store_pixel_counts): job j counts the events begins[j] ..
@@ -942,36 +942,6 @@ int check_source(const char* what, const SourceNames& k, bool given, uintptr_t a
   return ESS_OK;
 }
 
-int check_columns(const char* what, const void* t, const void* x, const void* y, const void* p, const int32_t* counts,
-                  const int32_t* formats, int64_t stride, int32_t n_streams, int32_t bins, int32_t height, int32_t width, const void* acc,
-                  size_t acc_bytes, const float* out) {
-  return check_source(what, SOURCE_COLUMNS, t && x && y && p && counts && formats, (uintptr_t)t | (uintptr_t)x | (uintptr_t)y | (uintptr_t)p,
-                      stride, 1, n_streams, bins, height, width, acc, acc_bytes, out);
-}
-
-int check_ring(const char* what, const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
-               const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots, int32_t bins, int32_t height,
-               int32_t width, const void* acc, size_t acc_bytes, const float* out, bool with_out = true) {
-  return check_source(what, SOURCE_RING, t && x && y && p && rows && starts && counts && formats,
-                      (uintptr_t)t | (uintptr_t)x | (uintptr_t)y | (uintptr_t)p, ring, n_rows, n_slots, bins, height, width, acc, acc_bytes,
-                      out, with_out);
-}
-
-// the rectify arguments of the trilinear flavour -> the kernels' Rectify
-int check_rectify(const char* what, const float* maps, const int32_t* map_of, int32_t n_maps, int32_t map_height, int32_t map_width,
-                  Rectify& r) {
-  ESS_CHECK_ARG(map_of, "%s: null map_of", what);
-  ESS_CHECK_ARG(n_maps >= 0, "%s: n_maps=%d must not be negative", what, (int)n_maps);
-  ESS_CHECK_ARG((maps != nullptr) == (n_maps > 0), "%s: maps must be null with n_maps=0 and only then (n_maps=%d, maps %s)", what,
-                (int)n_maps, maps ? "given" : "null");
-  ESS_CHECK_ARG(map_height >= 1 && map_height <= 32768 && map_width >= 1 && map_width <= 32768,
-                "%s: map_height=%d map_width=%d (1..32768 each: the sensor's size, whatever the grid's)", what, (int)map_height,
-                (int)map_width);
-  ESS_CHECK_ARG((((uintptr_t)maps) & 15) == 0, "%s: maps must be 16-byte aligned", what);
-  r = Rectify{(const float2*)maps, map_of, n_maps, map_height, map_width};
-  return ESS_OK;
-}
-
 // the training window's arguments of ess_event_grid_finish_window
 struct WindowArgs {
   const int32_t* words;
@@ -1081,104 +1051,18 @@ extern "C" int ess_event_ingest(const void* records, const int32_t* counts, int6
   return ess_launch_status("event_ingest(finish)");
 }
 
-extern "C" int ess_event_ingest_columns(const void* t, const void* x, const void* y, const void* p, const int32_t* counts,
-                                        const int32_t* formats, int64_t stride, int32_t n_streams, int32_t bins, int32_t height,
-                                        int32_t width, void* acc, size_t acc_bytes, float* out, ess_stream_t stream) {
-  int rc = check_columns("event_ingest_columns", t, x, y, p, counts, formats, stride, n_streams, bins, height, width, acc, acc_bytes, out);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  rc = launch_scatter<TemporalFlavour, false>("event_ingest_columns(scatter)", t, x, y, p, nullptr, nullptr, counts, formats, stride, 1,
-                                              n_streams, bins, height, width, acc, st);
-  if (rc) return rc;
-  launch_finish<false>(counts, n_streams, (int64_t)bins * height * width, acc, nullptr, out, st);
-  return ess_launch_status("event_ingest_columns(finish)");
-}
-
-extern "C" int ess_event_ingest_columns_trilinear(const void* t, const void* x, const void* y, const void* p, const int32_t* counts,
-                                                  const int32_t* formats, int64_t stride, int32_t n_streams, int32_t bins,
-                                                  int32_t height, int32_t width, void* acc, size_t acc_bytes, float* out,
-                                                  const float* maps, const int32_t* map_of, int32_t n_maps, int32_t map_height,
-                                                  int32_t map_width, ess_stream_t stream) {
-  const char* what = "event_ingest_columns_trilinear";
-  int rc = check_columns(what, t, x, y, p, counts, formats, stride, n_streams, bins, height, width, acc, acc_bytes, out);
-  if (rc) return rc;
-  Rectify rect;
-  rc = check_rectify(what, maps, map_of, n_maps, map_height, map_width, rect);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  rc = launch_scatter<TrilinearFlavour, false>("event_ingest_columns_trilinear(scatter)", t, x, y, p, nullptr, nullptr, counts, formats,
-                                               stride, 1, n_streams, bins, height, width, acc, st, rect);
-  if (rc) return rc;
-  launch_finish<false>(counts, n_streams, (int64_t)bins * height * width, acc, nullptr, out, st);
-  return ess_launch_status("event_ingest_columns_trilinear(finish)");
-}
-
-extern "C" int ess_event_ingest_ring(const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
-                                     const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots,
-                                     int32_t bins, int32_t height, int32_t width, void* acc, size_t acc_bytes, float* out,
-                                     ess_stream_t stream) {
-  int rc = check_ring("event_ingest_ring", t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, bins, height, width, acc,
-                      acc_bytes, out);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  rc = launch_scatter<TemporalFlavour, true>("event_ingest_ring(scatter)", t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots,
-                                             bins, height, width, acc, st);
-  if (rc) return rc;
-  launch_finish<false>(counts, n_slots, (int64_t)bins * height * width, acc, nullptr, out, st);
-  return ess_launch_status("event_ingest_ring(finish)");
-}
-
-extern "C" int ess_event_ingest_ring_trilinear(const void* t, const void* x, const void* y, const void* p, const int32_t* rows,
-                                               const int32_t* starts, const int32_t* counts, const int32_t* formats, int64_t ring,
-                                               int32_t n_rows, int32_t n_slots, int32_t bins, int32_t height, int32_t width, void* acc,
-                                               size_t acc_bytes, float* out, const float* maps, const int32_t* map_of, int32_t n_maps,
-                                               int32_t map_height, int32_t map_width, ess_stream_t stream) {
-  const char* what = "event_ingest_ring_trilinear";
-  int rc = check_ring(what, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, bins, height, width, acc, acc_bytes, out);
-  if (rc) return rc;
-  Rectify rect;
-  rc = check_rectify(what, maps, map_of, n_maps, map_height, map_width, rect);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  rc = launch_scatter<TrilinearFlavour, true>("event_ingest_ring_trilinear(scatter)", t, x, y, p, rows, starts, counts, formats, ring, n_rows,
-                                              n_slots, bins, height, width, acc, st, rect);
-  if (rc) return rc;
-  launch_finish<false>(counts, n_slots, (int64_t)bins * height * width, acc, nullptr, out, st);
-  return ess_launch_status("event_ingest_ring_trilinear(finish)");
-}
-
-// ---- the ring ingest in two halves: scatter alone (acc keeps the sums), and the loader finish that turns sums into the loader's grid
-extern "C" int ess_event_scatter_ring(const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
-                                      const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots,
-                                      int32_t bins, int32_t height, int32_t width, void* acc, size_t acc_bytes, ess_stream_t stream) {
-  int rc = check_ring("event_scatter_ring", t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, bins, height, width, acc,
-                      acc_bytes, nullptr, false);
-  if (rc) return rc;
-  return launch_scatter<TemporalFlavour, true>("event_scatter_ring", t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, bins,
-                                               height, width, acc, (hipStream_t)stream);
-}
-
-extern "C" int ess_event_scatter_ring_trilinear(const void* t, const void* x, const void* y, const void* p, const int32_t* rows,
-                                                const int32_t* starts, const int32_t* counts, const int32_t* formats, int64_t ring,
-                                                int32_t n_rows, int32_t n_slots, int32_t bins, int32_t height, int32_t width, void* acc,
-                                                size_t acc_bytes, const float* maps, const int32_t* map_of, int32_t n_maps,
-                                                int32_t map_height, int32_t map_width, ess_stream_t stream) {
-  const char* what = "event_scatter_ring_trilinear";
-  int rc = check_ring(what, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, bins, height, width, acc, acc_bytes, nullptr,
-                      false);
-  if (rc) return rc;
-  Rectify rect;
-  rc = check_rectify(what, maps, map_of, n_maps, map_height, map_width, rect);
-  if (rc) return rc;
-  return launch_scatter<TrilinearFlavour, true>(what, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, bins, height, width,
-                                                acc, (hipStream_t)stream, rect);
-}
-
-// ---- the event representations: the column / ring ingest and the ring scatter with `channels` planes a slot and a representation
-// word that picks the loader's flavour.  ESS_EVENT_REP_SIGNED launches the very kernel of the entry points above.
+// ---- the column, ring and store entry points.  Twelve of them -- two sources with or without rows, the trilinear flavour, the
+// representations (`channels` planes a slot and a word that picks the flavour), the scatter-only halves (acc keeps the sums for
+// ess_event_grid_finish*), hot-pixel masks -- are ONE description of a call (IngestCall, StoreCall) carried out by ONE routine a
+// source (ingest_call, store_call): the checks in the order that decides which refusal a caller sees, the flavour picked by one
+// visitor (visit_flavour), the launch, and the plain finish exactly where there is an out.  An entry point fills the description.
 namespace {
 
 constexpr int EVENT_REP_SIGNED = 0, EVENT_REP_SEPARATE = 1, EVENT_REP_HISTOGRAM = 2;  // (ESS_EVENT_REP_* of include/ess_hip.h)
+constexpr int STORE_SIGNED = 0, STORE_SEPARATE = 1, STORE_HISTOGRAM = 2, STORE_TRILINEAR = 3;  // (ESS_EVENT_STORE_* of include/ess_hip.h)
+static_assert(STORE_SIGNED == EVENT_REP_SIGNED && STORE_SEPARATE == EVENT_REP_SEPARATE && STORE_HISTOGRAM == EVENT_REP_HISTOGRAM,
+              "the first three flavour words are the representation words");
+constexpr int MASK_MAX_SIDE = 32768;
 
 // (in front of check_source, which sizes the workspace from `channels` where the signed entry points pass bins)
 int check_representation(const char* what, int32_t representation, int32_t channels) {
@@ -1192,111 +1076,295 @@ int check_representation(const char* what, int32_t representation, int32_t chann
   return ESS_OK;
 }
 
-template <bool RING>
-int launch_scatter_rep(const char* status, int32_t representation, const void* t, const void* x, const void* y, const void* p,
-                       const int32_t* rows, const int32_t* starts, const int32_t* counts, const int32_t* formats, int64_t ring,
-                       int32_t n_rows, int32_t n_slots, int32_t channels, int32_t height, int32_t width, void* acc, hipStream_t st) {
-  if (representation == EVENT_REP_SEPARATE)
-    return launch_scatter<SeparateFlavour, RING>(status, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels, height,
-                                                 width, acc, st);
-  if (representation == EVENT_REP_HISTOGRAM)
-    return launch_scatter<HistogramFlavour, RING>(status, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels, height,
-                                                  width, acc, st);
-  return launch_scatter<TemporalFlavour, RING>(status, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels, height,
-                                               width, acc, st);
+// the rectify arguments of the trilinear flavour, as an entry point takes them -> the kernels' Rectify
+struct RectifyArgs {
+  const float* maps;
+  const int32_t* map_of;
+  int32_t n_maps, map_height, map_width;
+};
+
+int check_rectify(const char* what, const RectifyArgs& a, Rectify& r) {
+  ESS_CHECK_ARG(a.map_of, "%s: null map_of", what);
+  ESS_CHECK_ARG(a.n_maps >= 0, "%s: n_maps=%d must not be negative", what, (int)a.n_maps);
+  ESS_CHECK_ARG((a.maps != nullptr) == (a.n_maps > 0), "%s: maps must be null with n_maps=0 and only then (n_maps=%d, maps %s)", what,
+                (int)a.n_maps, a.maps ? "given" : "null");
+  ESS_CHECK_ARG(a.map_height >= 1 && a.map_height <= 32768 && a.map_width >= 1 && a.map_width <= 32768,
+                "%s: map_height=%d map_width=%d (1..32768 each: the sensor's size, whatever the grid's)", what, (int)a.map_height,
+                (int)a.map_width);
+  ESS_CHECK_ARG((((uintptr_t)a.maps) & 15) == 0, "%s: maps must be 16-byte aligned", what);
+  r = Rectify{(const float2*)a.maps, a.map_of, a.n_maps, a.map_height, a.map_width};
+  return ESS_OK;
+}
+
+// the mask arguments -> the kernels' Masks
+struct MaskArgs {
+  const uint32_t* masks;
+  const int32_t* mask_of;
+  int32_t n_masks, mask_height, mask_width;
+};
+
+int check_masks(const char* what, const MaskArgs& a, Masks& m) {
+  ESS_CHECK_ARG(a.mask_of, "%s: null mask_of", what);
+  ESS_CHECK_ARG(a.n_masks >= 0, "%s: n_masks=%d must not be negative", what, (int)a.n_masks);
+  ESS_CHECK_ARG((a.masks != nullptr) == (a.n_masks > 0), "%s: masks must be null with n_masks=0 and only then (n_masks=%d, masks %s)", what,
+                (int)a.n_masks, a.masks ? "given" : "null");
+  ESS_CHECK_ARG(a.mask_height >= 1 && a.mask_height <= MASK_MAX_SIDE && a.mask_width >= 1 && a.mask_width <= MASK_MAX_SIDE,
+                "%s: mask_height=%d mask_width=%d (1..32768 each: the sensor's size, whatever the grid's)", what, (int)a.mask_height,
+                (int)a.mask_width);
+  ESS_CHECK_ARG((((uintptr_t)a.masks) & 15) == 0, "%s: masks must be 16-byte aligned", what);
+  m = Masks{a.masks, a.mask_of, a.n_masks, a.mask_height, a.mask_width};
+  return ESS_OK;
+}
+
+// The one flavour ladder: (flavour word, masked?) -> launch(type tag, the kernel's Extra... in their order).  Every launch behind a
+// mask is a Masked<Flavour> instantiation; without one the four flavours' own instantiations stay what they are.
+template <class Flavour>
+struct FlavourTag {
+  using type = Flavour;
+};
+
+template <class Launch>
+void visit_flavour(int32_t flavour, const Masks* m, const Rectify& r, Launch&& launch) {
+  if (!m) {
+    if (flavour == STORE_TRILINEAR) launch(FlavourTag<TrilinearFlavour>{}, r);
+    else if (flavour == STORE_SEPARATE) launch(FlavourTag<SeparateFlavour>{});
+    else if (flavour == STORE_HISTOGRAM) launch(FlavourTag<HistogramFlavour>{});
+    else launch(FlavourTag<TemporalFlavour>{});
+  } else if (flavour == STORE_TRILINEAR) launch(FlavourTag<Masked<TrilinearFlavour>>{}, *m, r);
+  else if (flavour == STORE_SEPARATE) launch(FlavourTag<Masked<SeparateFlavour>>{}, *m);
+  else if (flavour == STORE_HISTOGRAM) launch(FlavourTag<Masked<HistogramFlavour>>{}, *m);
+  else launch(FlavourTag<Masked<TemporalFlavour>>{}, *m);
+}
+
+// The column / ring loader's sixteen instantiations, named in the order the code object has held them since each was added.  The
+// visitor reaches every one of them whatever stands here; naming them first keeps their ORDER in the code object, and so the code
+// object byte for byte, independent of the order the host code below happens to reach them in.  (The store loader's eight follow
+// the visitor's order.)
+template <class Flavour, bool RING, class... Extra>
+const void* const LOADER = (const void*)&event_scatter_columns_kernel<Flavour, RING, Extra...>;
+[[maybe_unused]] const void* const LOADERS[] = {
+    LOADER<TemporalFlavour, false>, LOADER<TrilinearFlavour, false, Rectify>, LOADER<TemporalFlavour, true>,
+    LOADER<TrilinearFlavour, true, Rectify>, LOADER<SeparateFlavour, true>, LOADER<HistogramFlavour, true>,
+    LOADER<SeparateFlavour, false>, LOADER<HistogramFlavour, false>,
+    LOADER<Masked<TrilinearFlavour>, true, Masks, Rectify>, LOADER<Masked<SeparateFlavour>, true, Masks>,
+    LOADER<Masked<HistogramFlavour>, true, Masks>, LOADER<Masked<TemporalFlavour>, true, Masks>,
+    LOADER<Masked<TrilinearFlavour>, false, Masks, Rectify>, LOADER<Masked<SeparateFlavour>, false, Masks>,
+    LOADER<Masked<HistogramFlavour>, false, Masks>, LOADER<Masked<TemporalFlavour>, false, Masks>};
+
+// what every flavoured call runs behind its source's own checks: the rectify and the mask arguments where the call has them
+int check_flavour(const char* what, const RectifyArgs* rectify, const MaskArgs* masks, Rectify& r, Masks& m) {
+  int rc = rectify ? check_rectify(what, *rectify, r) : ESS_OK;
+  if (rc) return rc;
+  return masks ? check_masks(what, *masks, m) : ESS_OK;
+}
+
+// ... and behind its launch: the scatter's status, and with an out the plain finish, the stages named in the status strings
+int finish_call(const char* what, const int32_t* counts, int32_t n, int64_t per, void* acc, float* out, hipStream_t st) {
+  if (!out) return ess_launch_status(what);
+  int rc = stage_status(what, "scatter");
+  if (rc) return rc;
+  launch_finish<false>(counts, n, per, acc, nullptr, out, st);
+  return stage_status(what, "finish");
+}
+
+// One column (ring false: rows, starts null, n_rows 1) or ring call.
+struct IngestCall {
+  const char* what;  // the entry point's name in every message
+  bool ring;
+  const void *t, *x, *y, *p;
+  const int32_t *rows, *starts, *counts, *formats;
+  int64_t span;  // stride / ring
+  int32_t n_rows, n, planes, height, width;
+  void* acc;
+  size_t acc_bytes;
+  float* out;
+  bool with_out;      // false: scatter only -- an entry point without an out, or one whose out may be null and is
+  int32_t flavour;    // a STORE_* word
+  bool check_rep;     // check_representation runs (else a bad plane count is check_source's to report)
+  const RectifyArgs* rectify;  // nullptr: the call has no rectify arguments (to check)
+  const MaskArgs* masks;       // nullptr: an unmasked entry point
+};
+
+int ingest_call(const IngestCall& c, ess_stream_t stream) {
+  int rc = c.check_rep ? check_representation(c.what, c.flavour, c.planes) : ESS_OK;
+  if (rc) return rc;
+  rc = check_source(c.what, c.ring ? SOURCE_RING : SOURCE_COLUMNS,
+                    c.t && c.x && c.y && c.p && c.counts && c.formats && (!c.ring || (c.rows && c.starts)),
+                    (uintptr_t)c.t | (uintptr_t)c.x | (uintptr_t)c.y | (uintptr_t)c.p, c.span, c.n_rows, c.n, c.planes, c.height, c.width,
+                    c.acc, c.acc_bytes, c.out, c.with_out);
+  if (rc) return rc;
+  Rectify rect = {nullptr, nullptr, 0, 1, 1};
+  Masks m;
+  rc = check_flavour(c.what, c.rectify, c.masks, rect, m);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  visit_flavour(c.flavour, c.masks ? &m : nullptr, rect, [&](auto tag, auto... extra) {
+    using Flavour = typename decltype(tag)::type;
+    if (c.ring)
+      launch_scatter<Flavour, true>(c.t, c.x, c.y, c.p, c.rows, c.starts, c.counts, c.formats, c.span, c.n_rows, c.n, c.planes, c.height,
+                                    c.width, c.acc, st, extra...);
+    else
+      launch_scatter<Flavour, false>(c.t, c.x, c.y, c.p, nullptr, nullptr, c.counts, c.formats, c.span, 1, c.n, c.planes, c.height,
+                                     c.width, c.acc, st, extra...);
+  });
+  return finish_call(c.what, c.counts, c.n, (int64_t)c.planes * c.height * c.width, c.acc, c.out, st);
+}
+
+// the store's own sizes, as every entry point that reads its columns takes them
+int check_store_extent(const char* what, int64_t capacity, int64_t total) {
+  ESS_CHECK_ARG(capacity >= COLUMN_STRIDE_ALIGN && capacity <= STORE_MAX_CAPACITY && capacity % COLUMN_STRIDE_ALIGN == 0,
+                "%s: capacity=%lld events must be a multiple of %d in [%d, 2^40] (a window's last group of 4 events stays inside the columns)",
+                what, (long long)capacity, COLUMN_STRIDE_ALIGN, COLUMN_STRIDE_ALIGN);
+  ESS_CHECK_ARG(total >= 0 && total <= capacity, "%s: total=%lld events (0..capacity=%lld)", what, (long long)total, (long long)capacity);
+  return ESS_OK;
+}
+
+// One store call.  Its list of checks differs from check_source's in texts and order (the store has a capacity, a total and a window
+// capacity where a ring has a span), so it stays a list of its own; what follows it is ingest_call's.
+struct StoreCall {
+  const char* what;
+  const void *t, *x, *y, *p;
+  const int64_t* starts;
+  const int32_t *counts, *formats;
+  int64_t capacity, total, window_capacity;
+  int32_t n, planes, height, width;
+  void* acc;
+  size_t acc_bytes;
+  float* out;
+  bool with_out;  // false: the scatter-only entry point, which has no out;  else out is nullable (NULL: scatter only)
+  int32_t flavour;
+  RectifyArgs rectify;    // read with STORE_TRILINEAR alone; with_out: given with any other flavour they are refused, else ignored
+  const MaskArgs* masks;  // nullptr: the unmasked entry point
+};
+
+int store_call(const StoreCall& c, ess_stream_t stream) {
+  const char* what = c.what;
+  const bool trilinear = c.flavour == STORE_TRILINEAR;
+  ESS_CHECK_ARG(c.flavour >= STORE_SIGNED && c.flavour <= STORE_TRILINEAR,
+                "%s: flavour=%d (0 signed, 1 separate polarity, 2 histogram, 3 trilinear)", what, (int)c.flavour);
+  int rc = check_representation(what, trilinear ? EVENT_REP_SIGNED : c.flavour, c.planes);
+  if (rc) return rc;
+  ESS_CHECK_ARG(c.t && c.x && c.y && c.p && c.starts && c.counts && c.formats && c.acc,
+                "%s: null t, x, y, p, starts, counts, formats or acc", what);
+  ESS_CHECK_ARG(c.n >= 1 && c.n <= 65535, "%s: n_slots=%d (1..65535)", what, (int)c.n);
+  ESS_CHECK_ARG(c.height > 0 && c.width > 0, "%s: height=%d width=%d must be positive", what, (int)c.height, (int)c.width);
+  ESS_CHECK_ARG(c.window_capacity >= 1 && c.window_capacity <= INGEST_MAX_CAPACITY,
+                "%s: window_capacity=%lld events per window (1..%lld: the int64 sums hold 2^22 contributions of magnitude 1 at scale 2^40)",
+                what, (long long)c.window_capacity, (long long)INGEST_MAX_CAPACITY);
+  rc = check_store_extent(what, c.capacity, c.total);
+  if (rc) return rc;
+  const size_t need = ess_event_ingest_workspace(c.n, c.planes, c.height, c.width);
+  ESS_CHECK_ARG(c.acc_bytes >= need, "%s: acc has %zu bytes, %zu are needed", what, c.acc_bytes, need);
+  ESS_CHECK_ARG((((uintptr_t)c.t | (uintptr_t)c.x | (uintptr_t)c.y | (uintptr_t)c.p | (uintptr_t)c.acc | (uintptr_t)c.out) & 15) == 0 &&
+                    (((uintptr_t)c.starts) & 7) == 0 && ((((uintptr_t)c.counts) | ((uintptr_t)c.formats)) & 3) == 0,
+                "%s: t, x, y, p%s acc must be 16-byte, starts 8-byte, counts and formats 4-byte aligned", what,
+                c.with_out ? ", out and" : " and");
+  ESS_CHECK_ARG(!c.with_out || trilinear || (c.rectify.maps == nullptr && c.rectify.map_of == nullptr && c.rectify.n_maps == 0),
+                "%s: maps, map_of and n_maps belong to flavour=3 (trilinear): flavour=%d needs them null and 0", what, (int)c.flavour);
+  Rectify rect = {nullptr, nullptr, 0, 1, 1};
+  Masks m;
+  rc = check_flavour(what, trilinear ? &c.rectify : nullptr, c.masks, rect, m);
+  if (rc) return rc;
+  ESS_CHECK_ARG(!c.masks || (((uintptr_t)c.masks->mask_of) & 3) == 0, "%s: mask_of must be 4-byte aligned", what);
+  hipStream_t st = (hipStream_t)stream;
+  visit_flavour(c.flavour, c.masks ? &m : nullptr, rect, [&](auto tag, auto... extra) {
+    launch_scatter_store<typename decltype(tag)::type>(c.t, c.x, c.y, c.p, c.starts, c.counts, c.formats, c.total, c.window_capacity, c.n,
+                                                       c.planes, c.height, c.width, c.acc, st, extra...);
+  });
+  return finish_call(what, c.counts, c.n, (int64_t)c.planes * c.height * c.width, c.acc, c.out, st);
 }
 
 }  // namespace
 
+extern "C" int ess_event_ingest_columns(const void* t, const void* x, const void* y, const void* p, const int32_t* counts,
+                                        const int32_t* formats, int64_t stride, int32_t n_streams, int32_t bins, int32_t height,
+                                        int32_t width, void* acc, size_t acc_bytes, float* out, ess_stream_t stream) {
+  return ingest_call({"event_ingest_columns", false, t, x, y, p, nullptr, nullptr, counts, formats, stride, 1, n_streams, bins, height, width,
+                      acc, acc_bytes, out, true, STORE_SIGNED, false, nullptr, nullptr},
+                     stream);
+}
+
+extern "C" int ess_event_ingest_columns_trilinear(const void* t, const void* x, const void* y, const void* p, const int32_t* counts,
+                                                  const int32_t* formats, int64_t stride, int32_t n_streams, int32_t bins,
+                                                  int32_t height, int32_t width, void* acc, size_t acc_bytes, float* out,
+                                                  const float* maps, const int32_t* map_of, int32_t n_maps, int32_t map_height,
+                                                  int32_t map_width, ess_stream_t stream) {
+  const RectifyArgs rect = {maps, map_of, n_maps, map_height, map_width};
+  return ingest_call({"event_ingest_columns_trilinear", false, t, x, y, p, nullptr, nullptr, counts, formats, stride, 1, n_streams, bins,
+                      height, width, acc, acc_bytes, out, true, STORE_TRILINEAR, false, &rect, nullptr},
+                     stream);
+}
+
+extern "C" int ess_event_ingest_ring(const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
+                                     const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots,
+                                     int32_t bins, int32_t height, int32_t width, void* acc, size_t acc_bytes, float* out,
+                                     ess_stream_t stream) {
+  return ingest_call({"event_ingest_ring", true, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, bins, height, width, acc,
+                      acc_bytes, out, true, STORE_SIGNED, false, nullptr, nullptr},
+                     stream);
+}
+
+extern "C" int ess_event_ingest_ring_trilinear(const void* t, const void* x, const void* y, const void* p, const int32_t* rows,
+                                               const int32_t* starts, const int32_t* counts, const int32_t* formats, int64_t ring,
+                                               int32_t n_rows, int32_t n_slots, int32_t bins, int32_t height, int32_t width, void* acc,
+                                               size_t acc_bytes, float* out, const float* maps, const int32_t* map_of, int32_t n_maps,
+                                               int32_t map_height, int32_t map_width, ess_stream_t stream) {
+  const RectifyArgs rect = {maps, map_of, n_maps, map_height, map_width};
+  return ingest_call({"event_ingest_ring_trilinear", true, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, bins, height,
+                      width, acc, acc_bytes, out, true, STORE_TRILINEAR, false, &rect, nullptr},
+                     stream);
+}
+
+// the ring ingest in two halves: scatter alone (acc keeps the sums), and the loader finish that turns sums into the loader's grid
+extern "C" int ess_event_scatter_ring(const void* t, const void* x, const void* y, const void* p, const int32_t* rows, const int32_t* starts,
+                                      const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows, int32_t n_slots,
+                                      int32_t bins, int32_t height, int32_t width, void* acc, size_t acc_bytes, ess_stream_t stream) {
+  return ingest_call({"event_scatter_ring", true, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, bins, height, width, acc,
+                      acc_bytes, nullptr, false, STORE_SIGNED, false, nullptr, nullptr},
+                     stream);
+}
+
+extern "C" int ess_event_scatter_ring_trilinear(const void* t, const void* x, const void* y, const void* p, const int32_t* rows,
+                                                const int32_t* starts, const int32_t* counts, const int32_t* formats, int64_t ring,
+                                                int32_t n_rows, int32_t n_slots, int32_t bins, int32_t height, int32_t width, void* acc,
+                                                size_t acc_bytes, const float* maps, const int32_t* map_of, int32_t n_maps,
+                                                int32_t map_height, int32_t map_width, ess_stream_t stream) {
+  const RectifyArgs rect = {maps, map_of, n_maps, map_height, map_width};
+  return ingest_call({"event_scatter_ring_trilinear", true, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, bins, height,
+                      width, acc, acc_bytes, nullptr, false, STORE_TRILINEAR, false, &rect, nullptr},
+                     stream);
+}
+
+// the event representations: ESS_EVENT_REP_SIGNED launches the very kernel of the entry points above
 extern "C" int ess_event_scatter_ring_rep(const void* t, const void* x, const void* y, const void* p, const int32_t* rows,
                                           const int32_t* starts, const int32_t* counts, const int32_t* formats, int64_t ring,
                                           int32_t n_rows, int32_t n_slots, int32_t channels, int32_t height, int32_t width, void* acc,
                                           size_t acc_bytes, int32_t representation, ess_stream_t stream) {
-  const char* what = "event_scatter_ring_rep";
-  int rc = check_representation(what, representation, channels);
-  if (rc) return rc;
-  rc = check_ring(what, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels, height, width, acc, acc_bytes, nullptr,
-                  false);
-  if (rc) return rc;
-  return launch_scatter_rep<true>(what, representation, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels, height,
-                                  width, acc, (hipStream_t)stream);
+  return ingest_call({"event_scatter_ring_rep", true, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels, height,
+                      width, acc, acc_bytes, nullptr, false, representation, true, nullptr, nullptr},
+                     stream);
 }
 
 extern "C" int ess_event_ingest_ring_rep(const void* t, const void* x, const void* y, const void* p, const int32_t* rows,
                                          const int32_t* starts, const int32_t* counts, const int32_t* formats, int64_t ring,
                                          int32_t n_rows, int32_t n_slots, int32_t channels, int32_t height, int32_t width, void* acc,
                                          size_t acc_bytes, float* out, int32_t representation, ess_stream_t stream) {
-  const char* what = "event_ingest_ring_rep";
-  int rc = check_representation(what, representation, channels);
-  if (rc) return rc;
-  rc = check_ring(what, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels, height, width, acc, acc_bytes, out);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  rc = launch_scatter_rep<true>("event_ingest_ring_rep(scatter)", representation, t, x, y, p, rows, starts, counts, formats, ring, n_rows,
-                                n_slots, channels, height, width, acc, st);
-  if (rc) return rc;
-  launch_finish<false>(counts, n_slots, (int64_t)channels * height * width, acc, nullptr, out, st);
-  return ess_launch_status("event_ingest_ring_rep(finish)");
+  return ingest_call({"event_ingest_ring_rep", true, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels, height,
+                      width, acc, acc_bytes, out, true, representation, true, nullptr, nullptr},
+                     stream);
 }
 
 extern "C" int ess_event_ingest_columns_rep(const void* t, const void* x, const void* y, const void* p, const int32_t* counts,
                                             const int32_t* formats, int64_t stride, int32_t n_streams, int32_t channels, int32_t height,
                                             int32_t width, void* acc, size_t acc_bytes, float* out, int32_t representation,
                                             ess_stream_t stream) {
-  const char* what = "event_ingest_columns_rep";
-  int rc = check_representation(what, representation, channels);
-  if (rc) return rc;
-  rc = check_columns(what, t, x, y, p, counts, formats, stride, n_streams, channels, height, width, acc, acc_bytes, out);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  rc = launch_scatter_rep<false>("event_ingest_columns_rep(scatter)", representation, t, x, y, p, nullptr, nullptr, counts, formats, stride,
-                                 1, n_streams, channels, height, width, acc, st);
-  if (rc) return rc;
-  launch_finish<false>(counts, n_streams, (int64_t)channels * height * width, acc, nullptr, out, st);
-  return ess_launch_status("event_ingest_columns_rep(finish)");
+  return ingest_call({"event_ingest_columns_rep", false, t, x, y, p, nullptr, nullptr, counts, formats, stride, 1, n_streams, channels,
+                      height, width, acc, acc_bytes, out, true, representation, true, nullptr, nullptr},
+                     stream);
 }
 
-// ---- hot-pixel masks: ONE entry point for both sources, all four flavours and both halves (ess_event_ingest_masked), every one a
-// Masked<Flavour> instantiation of the loader; and the kernel that turns the histogram flavour's counts into masks.
-namespace {
-
-constexpr int MASK_MAX_SIDE = 32768;
-
-// the mask arguments -> the kernels' Masks
-int check_masks(const char* what, const uint32_t* masks, const int32_t* mask_of, int32_t n_masks, int32_t mask_height, int32_t mask_width,
-                Masks& m) {
-  ESS_CHECK_ARG(mask_of, "%s: null mask_of", what);
-  ESS_CHECK_ARG(n_masks >= 0, "%s: n_masks=%d must not be negative", what, (int)n_masks);
-  ESS_CHECK_ARG((masks != nullptr) == (n_masks > 0), "%s: masks must be null with n_masks=0 and only then (n_masks=%d, masks %s)", what,
-                (int)n_masks, masks ? "given" : "null");
-  ESS_CHECK_ARG(mask_height >= 1 && mask_height <= MASK_MAX_SIDE && mask_width >= 1 && mask_width <= MASK_MAX_SIDE,
-                "%s: mask_height=%d mask_width=%d (1..32768 each: the sensor's size, whatever the grid's)", what, (int)mask_height,
-                (int)mask_width);
-  ESS_CHECK_ARG((((uintptr_t)masks) & 15) == 0, "%s: masks must be 16-byte aligned", what);
-  m = Masks{masks, mask_of, n_masks, mask_height, mask_width};
-  return ESS_OK;
-}
-
-template <bool RING>
-int launch_scatter_masked(const char* status, int32_t representation, bool trilinear, const void* t, const void* x, const void* y,
-                          const void* p, const int32_t* rows, const int32_t* starts, const int32_t* counts, const int32_t* formats,
-                          int64_t ring, int32_t n_rows, int32_t n_slots, int32_t channels, int32_t height, int32_t width, void* acc,
-                          hipStream_t st, const Masks m, const Rectify r) {
-  if (trilinear)
-    return launch_scatter<Masked<TrilinearFlavour>, RING>(status, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels,
-                                                          height, width, acc, st, m, r);
-  if (representation == EVENT_REP_SEPARATE)
-    return launch_scatter<Masked<SeparateFlavour>, RING>(status, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels,
-                                                         height, width, acc, st, m);
-  if (representation == EVENT_REP_HISTOGRAM)
-    return launch_scatter<Masked<HistogramFlavour>, RING>(status, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels,
-                                                          height, width, acc, st, m);
-  return launch_scatter<Masked<TemporalFlavour>, RING>(status, t, x, y, p, rows, starts, counts, formats, ring, n_rows, n_slots, channels,
-                                                       height, width, acc, st, m);
-}
-
-}  // namespace
-
+// hot-pixel masks: ONE entry point for both sources, all four flavours and both halves.  Its own checks stand in front of the
+// routine's: which source the call names decides the texts of every check behind them.
 extern "C" int ess_event_ingest_masked(const void* t, const void* x, const void* y, const void* p, const int32_t* rows,
                                        const int32_t* starts, const int32_t* counts, const int32_t* formats, int64_t ring, int32_t n_rows,
                                        int32_t n_slots, int32_t channels, int32_t height, int32_t width, void* acc, size_t acc_bytes,
@@ -1314,138 +1382,37 @@ extern "C" int ess_event_ingest_masked(const void* t, const void* x, const void*
                 "%s: rows and starts are both given (the ring source) or both null (the column source): rows %s, starts %s", what,
                 rows ? "given" : "null", starts ? "given" : "null");
   const bool is_ring = rows != nullptr;
-  const uintptr_t addresses = (uintptr_t)t | (uintptr_t)x | (uintptr_t)y | (uintptr_t)p;
-  rc = check_source(what, is_ring ? SOURCE_RING : SOURCE_COLUMNS, t && x && y && p && counts && formats, addresses, ring,
-                    is_ring ? n_rows : 1, n_slots, channels, height, width, acc, acc_bytes, out, out != nullptr);
-  if (rc) return rc;
-  Rectify rect = {nullptr, nullptr, 0, 1, 1};
-  if (trilinear) {
-    rc = check_rectify(what, maps, map_of, n_maps, map_height, map_width, rect);
-    if (rc) return rc;
-  }
-  Masks m;
-  rc = check_masks(what, masks, mask_of, n_masks, mask_height, mask_width, m);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const char* status = out ? "event_ingest_masked(scatter)" : what;
-  rc = is_ring ? launch_scatter_masked<true>(status, representation, trilinear != 0, t, x, y, p, rows, starts, counts, formats, ring, n_rows,
-                                             n_slots, channels, height, width, acc, st, m, rect)
-               : launch_scatter_masked<false>(status, representation, trilinear != 0, t, x, y, p, nullptr, nullptr, counts, formats, ring, 1,
-                                              n_slots, channels, height, width, acc, st, m, rect);
-  if (rc || !out) return rc;
-  launch_finish<false>(counts, n_slots, (int64_t)channels * height * width, acc, nullptr, out, st);
-  return ess_launch_status("event_ingest_masked(finish)");
+  const RectifyArgs rect = {maps, map_of, n_maps, map_height, map_width};
+  const MaskArgs mask = {masks, mask_of, n_masks, mask_height, mask_width};
+  return ingest_call({what, is_ring, t, x, y, p, rows, starts, counts, formats, ring, is_ring ? n_rows : 1, n_slots, channels, height, width,
+                      acc, acc_bytes, out, out != nullptr, trilinear ? STORE_TRILINEAR : representation, false, trilinear ? &rect : nullptr,
+                      &mask},
+                     stream);
 }
 
-// ---- the store source: ONE entry point for the four flavours, scatter only (acc keeps the sums for ess_event_grid_finish*), and its
-// masked counterpart with both halves (ess_event_ingest_store); one routine checks the arguments of both (check_store)
-namespace {
-constexpr int STORE_SIGNED = 0, STORE_SEPARATE = 1, STORE_HISTOGRAM = 2, STORE_TRILINEAR = 3;  // (ESS_EVENT_STORE_* of include/ess_hip.h)
-static_assert(STORE_SIGNED == EVENT_REP_SIGNED && STORE_SEPARATE == EVENT_REP_SEPARATE && STORE_HISTOGRAM == EVENT_REP_HISTOGRAM,
-              "the first three flavour words are the representation words");
-
-// the store's own sizes, as every entry point that reads its columns takes them
-int check_store_extent(const char* what, int64_t capacity, int64_t total) {
-  ESS_CHECK_ARG(capacity >= COLUMN_STRIDE_ALIGN && capacity <= STORE_MAX_CAPACITY && capacity % COLUMN_STRIDE_ALIGN == 0,
-                "%s: capacity=%lld events must be a multiple of %d in [%d, 2^40] (a window's last group of 4 events stays inside the columns)",
-                what, (long long)capacity, COLUMN_STRIDE_ALIGN, COLUMN_STRIDE_ALIGN);
-  ESS_CHECK_ARG(total >= 0 && total <= capacity, "%s: total=%lld events (0..capacity=%lld)", what, (long long)total, (long long)capacity);
-  return ESS_OK;
-}
-
-// with_out false: the scatter-only entry point, which has no out;  else out is nullable (NULL: scatter only)
-int check_store(const char* what, const void* t, const void* x, const void* y, const void* p, const int64_t* starts, const int32_t* counts,
-                const int32_t* formats, int64_t capacity, int64_t total, int64_t window_capacity, int32_t n_slots, int32_t channels,
-                int32_t height, int32_t width, const void* acc, size_t acc_bytes, const float* out, bool with_out, int32_t flavour) {
-  ESS_CHECK_ARG(flavour >= STORE_SIGNED && flavour <= STORE_TRILINEAR,
-                "%s: flavour=%d (0 signed, 1 separate polarity, 2 histogram, 3 trilinear)", what, (int)flavour);
-  int rc = check_representation(what, flavour == STORE_TRILINEAR ? EVENT_REP_SIGNED : flavour, channels);
-  if (rc) return rc;
-  ESS_CHECK_ARG(t && x && y && p && starts && counts && formats && acc, "%s: null t, x, y, p, starts, counts, formats or acc", what);
-  ESS_CHECK_ARG(n_slots >= 1 && n_slots <= 65535, "%s: n_slots=%d (1..65535)", what, (int)n_slots);
-  ESS_CHECK_ARG(height > 0 && width > 0, "%s: height=%d width=%d must be positive", what, (int)height, (int)width);
-  ESS_CHECK_ARG(window_capacity >= 1 && window_capacity <= INGEST_MAX_CAPACITY,
-                "%s: window_capacity=%lld events per window (1..%lld: the int64 sums hold 2^22 contributions of magnitude 1 at scale 2^40)",
-                what, (long long)window_capacity, (long long)INGEST_MAX_CAPACITY);
-  rc = check_store_extent(what, capacity, total);
-  if (rc) return rc;
-  const size_t need = ess_event_ingest_workspace(n_slots, channels, height, width);
-  ESS_CHECK_ARG(acc_bytes >= need, "%s: acc has %zu bytes, %zu are needed", what, acc_bytes, need);
-  ESS_CHECK_ARG((((uintptr_t)t | (uintptr_t)x | (uintptr_t)y | (uintptr_t)p | (uintptr_t)acc | (uintptr_t)out) & 15) == 0 &&
-                    (((uintptr_t)starts) & 7) == 0 && ((((uintptr_t)counts) | ((uintptr_t)formats)) & 3) == 0,
-                "%s: t, x, y, p%s acc must be 16-byte, starts 8-byte, counts and formats 4-byte aligned", what,
-                with_out ? ", out and" : " and");
-  return ESS_OK;
-}
-}  // namespace
-
+// the store source: the four flavours, scatter only (acc keeps the sums for ess_event_grid_finish*) ...
 extern "C" int ess_event_scatter_store(const void* t, const void* x, const void* y, const void* p, const int64_t* starts,
                                        const int32_t* counts, const int32_t* formats, int64_t capacity, int64_t total,
                                        int64_t window_capacity, int32_t n_slots, int32_t channels, int32_t height, int32_t width,
                                        void* acc, size_t acc_bytes, int32_t flavour, const float* maps, const int32_t* map_of,
                                        int32_t n_maps, int32_t map_height, int32_t map_width, ess_stream_t stream) {
-  const char* what = "event_scatter_store";
-  int rc = check_store(what, t, x, y, p, starts, counts, formats, capacity, total, window_capacity, n_slots, channels, height, width, acc,
-                       acc_bytes, nullptr, false, flavour);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (flavour == STORE_TRILINEAR) {
-    Rectify rect;
-    rc = check_rectify(what, maps, map_of, n_maps, map_height, map_width, rect);
-    if (rc) return rc;
-    return launch_scatter_store<TrilinearFlavour>(what, t, x, y, p, starts, counts, formats, total, window_capacity, n_slots, channels, height,
-                                                  width, acc, st, rect);
-  }
-  if (flavour == STORE_SEPARATE)
-    return launch_scatter_store<SeparateFlavour>(what, t, x, y, p, starts, counts, formats, total, window_capacity, n_slots, channels, height,
-                                                 width, acc, st);
-  if (flavour == STORE_HISTOGRAM)
-    return launch_scatter_store<HistogramFlavour>(what, t, x, y, p, starts, counts, formats, total, window_capacity, n_slots, channels, height,
-                                                  width, acc, st);
-  return launch_scatter_store<TemporalFlavour>(what, t, x, y, p, starts, counts, formats, total, window_capacity, n_slots, channels, height,
-                                               width, acc, st);
+  return store_call({"event_scatter_store", t, x, y, p, starts, counts, formats, capacity, total, window_capacity, n_slots, channels, height,
+                     width, acc, acc_bytes, nullptr, false, flavour, {maps, map_of, n_maps, map_height, map_width}, nullptr},
+                    stream);
 }
 
-// the store source behind hot-pixel masks, both halves: every launch a Masked<Flavour> instantiation of event_scatter_store_kernel
-// (the unmasked ones above stay what they are); with out, the plain finish follows as behind the ring ingest
+// ... and behind hot-pixel masks, both halves: every launch a Masked<Flavour> instantiation of event_scatter_store_kernel; with out,
+// the plain finish follows as behind the ring ingest
 extern "C" int ess_event_ingest_store(const void* t, const void* x, const void* y, const void* p, const int64_t* starts,
                                       const int32_t* counts, const int32_t* formats, int64_t capacity, int64_t total,
                                       int64_t window_capacity, int32_t n_slots, int32_t channels, int32_t height, int32_t width, void* acc,
                                       size_t acc_bytes, float* out, int32_t flavour, const float* maps, const int32_t* map_of,
                                       int32_t n_maps, int32_t map_height, int32_t map_width, const uint32_t* masks, const int32_t* mask_of,
                                       int32_t n_masks, int32_t mask_height, int32_t mask_width, ess_stream_t stream) {
-  const char* what = "event_ingest_store";
-  int rc = check_store(what, t, x, y, p, starts, counts, formats, capacity, total, window_capacity, n_slots, channels, height, width, acc,
-                       acc_bytes, out, true, flavour);
-  if (rc) return rc;
-  ESS_CHECK_ARG(flavour == STORE_TRILINEAR || (maps == nullptr && map_of == nullptr && n_maps == 0),
-                "%s: maps, map_of and n_maps belong to flavour=3 (trilinear): flavour=%d needs them null and 0", what, (int)flavour);
-  Rectify rect = {nullptr, nullptr, 0, 1, 1};
-  if (flavour == STORE_TRILINEAR) {
-    rc = check_rectify(what, maps, map_of, n_maps, map_height, map_width, rect);
-    if (rc) return rc;
-  }
-  Masks m;
-  rc = check_masks(what, masks, mask_of, n_masks, mask_height, mask_width, m);
-  if (rc) return rc;
-  ESS_CHECK_ARG((((uintptr_t)mask_of) & 3) == 0, "%s: mask_of must be 4-byte aligned", what);
-  hipStream_t st = (hipStream_t)stream;
-  const char* status = out ? "event_ingest_store(scatter)" : what;
-  if (flavour == STORE_TRILINEAR)
-    rc = launch_scatter_store<Masked<TrilinearFlavour>>(status, t, x, y, p, starts, counts, formats, total, window_capacity, n_slots, channels,
-                                                        height, width, acc, st, m, rect);
-  else if (flavour == STORE_SEPARATE)
-    rc = launch_scatter_store<Masked<SeparateFlavour>>(status, t, x, y, p, starts, counts, formats, total, window_capacity, n_slots, channels,
-                                                       height, width, acc, st, m);
-  else if (flavour == STORE_HISTOGRAM)
-    rc = launch_scatter_store<Masked<HistogramFlavour>>(status, t, x, y, p, starts, counts, formats, total, window_capacity, n_slots, channels,
-                                                        height, width, acc, st, m);
-  else
-    rc = launch_scatter_store<Masked<TemporalFlavour>>(status, t, x, y, p, starts, counts, formats, total, window_capacity, n_slots, channels,
-                                                       height, width, acc, st, m);
-  if (rc || !out) return rc;
-  launch_finish<false>(counts, n_slots, (int64_t)channels * height * width, acc, nullptr, out, st);
-  return ess_launch_status("event_ingest_store(finish)");
+  const MaskArgs mask = {masks, mask_of, n_masks, mask_height, mask_width};
+  return store_call({"event_ingest_store", t, x, y, p, starts, counts, formats, capacity, total, window_capacity, n_slots, channels, height,
+                     width, acc, acc_bytes, out, true, flavour, {maps, map_of, n_maps, map_height, map_width}, &mask},
+                    stream);
 }
 
 extern "C" int ess_event_store_pixel_counts(const void* x, const void* y, int64_t capacity, int64_t total, const int64_t* begins,

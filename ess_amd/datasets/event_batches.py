@@ -374,12 +374,9 @@ class EventBatchBuilder:
         st = self._static
         ev, lab = st['out'][k]
         words = st['words']
-        if self.voxel == 'trilinear':
-            hip.event_scatter_ring_trilinear(*st['cols'], *words[:4], st['acc'], st['maps'], words[4])
-        elif self._rep != hip.EVENT_REP_SIGNED:
-            hip.event_scatter_ring_rep(*st['cols'], *words, st['acc'], self._rep)
-        else:
-            hip.event_scatter_ring(*st['cols'], *words, st['acc'])
+        tri = self.voxel == 'trilinear'
+        hip.event_voxels('ring', st['cols'], words[:4], None, st['acc'], representation=self._rep, trilinear=tri, maps=st['maps'],
+                         map_of=words[4] if tri else None)
         hip.event_grid_finish_window(words[2], st['acc'], ev, st['params'], self.sequence_steps, crop_rows=self.grid_rows,
                                      resize=self.grid_resize, normalize=self.grid_normalize)
         if with_labels:
@@ -452,11 +449,9 @@ class EventBatchBuilder:
         hip.event_store_windows(t, store.table, tin['recording'], tin['bounds'], rule, T, st['starts'], counts, formats, st['flags'][k],
                                 store.capacity, self.window_capacity, n_per_window=self.window if self.store_by_count else None,
                                 sample_map=tin['sample_map'], map_of=map_of)
-        if self.voxel == 'trilinear':
-            hip.event_scatter_store(*store.columns, st['starts'], counts, formats, st['acc'], hip.EVENT_STORE_TRILINEAR, store.capacity,
-                                    self.window_capacity, st['maps'], map_of)
-        else:
-            hip.event_scatter_store(*store.columns, st['starts'], counts, formats, st['acc'], self._rep, store.capacity, self.window_capacity)
+        hip.event_voxels('store', store.columns, (st['starts'], counts, formats), None, st['acc'], representation=self._rep,
+                         trilinear=self.voxel == 'trilinear', maps=st['maps'], map_of=map_of, total=store.capacity,
+                         window_capacity=self.window_capacity)
         hip.event_grid_finish_window(counts, st['acc'], ev, tin['params'], T, crop_rows=self.grid_rows, resize=self.grid_resize,
                                      normalize=self.grid_normalize)
         if with_labels:

@@ -994,7 +994,7 @@ def event_ingest_columns(t, x, y, p, counts, formats, out, acc=None):
     other bit: the stream counts as empty), a device int32 [S] read by the kernel like counts, so one captured call serves streams
     whose formats change from round to round.  p: +1 where the byte equals 1, -1 otherwise.  stride: a multiple of 16
     (event_column_stride).  counts, out, acc: as event_ingest."""
-    return _event_ingest_columns('event_ingest_columns', t, x, y, p, counts, formats, out, acc, None)
+    return _event_call('event_ingest_columns', 'columns', 'plain', (t, x, y, p), (counts, formats), out, acc, 'required')
 
 
 def _event_columns(fn, named, n, ring):
@@ -1021,18 +1021,79 @@ def _column_pointers(named):
     return [c_void_p(v.data_ptr()) for _, v in named[:4]] + [ptr(v, torch.int32) for _, v in named[4:]]
 
 
-def _event_ingest_columns(fn, t, x, y, p, counts, formats, out, acc, rectify):
-    """event_ingest_columns (rectify None) / event_ingest_columns_trilinear (rectify: (maps, map_of) as given): the checks and the call"""
-    words = (('t', t), ('x', x), ('y', y), ('p', p), ('counts', counts), ('formats', formats))
-    named = words + (('out', out),) + ((('acc', acc),) if acc is not None else ())
+_EVENT_WORDS = {'columns': ('counts', 'formats'), 'ring': ('rows', 'starts', 'counts', 'formats'), 'store': ('starts', 'counts', 'formats')}
+_NO_RECTIFY = (c_void_p(0), c_void_p(0), 0, 1, 1)
+
+
+def _event_call(fn, kind, form, cols, words, out, acc, has_out, representation=None, trilinear=False, rectify=(None, None),
+                masks=(None, None, None), flavour=None, total=None, window_capacity=None):
+    """The one body behind the column / ring / store bindings: the checks in their order -- what is wrong with a tensor's form is said
+    whatever memory it lies in, acc's dtype, the device and contiguity last -- and the call of ess_<fn>.
+    kind: 'columns', 'ring' or 'store', the source: cols = (t, x, y, p), words = its device words (_EVENT_WORDS names them).
+    form: what the entry point takes behind the grids -- 'plain' nothing, 'trilinear' the rectify arguments, 'rep' a representation
+    word, 'masked' representation, trilinear, rectify and mask arguments, 'store' / 'store_masked' a flavour word, rectify (and
+    mask) arguments.  has_out: 'required', 'optional' (None: scatter only, acc keeps the sums and is returned) or 'none' (the
+    entry point has no out).  -> out, or acc where there is no out"""
+    cols, words = tuple(zip('txyp', cols)), tuple(zip(_EVENT_WORDS[kind], words))
+    if has_out == 'optional' and out is None and acc is None:
+        raise EssHipError(f'{fn}: out=None (scatter only) needs acc, the int64 [n_slots, C, H, W] sums it leaves')
+    named = cols + words + ((('out', out),) if out is not None or has_out == 'required' else ()) + \
+        ((('acc', acc),) if acc is not None or has_out == 'none' else ())
     _are_tensors(fn, named)
-    S, bins, H, W = _ingest_out(fn, out, 'S')
-    _event_columns(fn, words, S, ring=False)
-    acc = _ingest_acc(fn, named, acc, out)
-    tail = () if rectify is None else _rectify_args(fn, rectify[0], rectify[1], S, out.device)
-    _check(getattr(lib(), 'ess_' + fn)(*_column_pointers(words), t.shape[1], S, bins, H, W, c_void_p(acc.data_ptr()), acc.numel() * 8,
-                                       c_void_p(out.data_ptr()), *tail, stream()), 'ess_' + fn)
-    return out
+    where = 'out' if out is not None else 'acc'
+    n_name = 'S' if kind == 'columns' and form != 'masked' else 'n_slots'
+    n, C, H, W = _ingest_out(fn, out, n_name) if out is not None else _finish_acc(fn, acc, 'H, W')
+    maps, map_of = rectify
+    tail = ()
+    if kind == 'store':
+        if isinstance(flavour, bool) or flavour not in _EVENT_STORE_FLAVOURS:
+            raise EssHipError(f'{fn}: flavour={flavour!r} must be EVENT_STORE_SIGNED, _SEPARATE, _HISTOGRAM or _TRILINEAR')
+        trilinear = flavour == EVENT_STORE_TRILINEAR
+        if not trilinear:
+            _event_rep_of(fn, int(flavour), C, where)
+            if maps is not None or map_of is not None:
+                raise EssHipError(f'{fn}: maps / map_of belong to flavour=EVENT_STORE_TRILINEAR')
+        tail = (int(flavour),)
+    elif form in ('rep', 'masked'):
+        rep = _event_rep_of(fn, representation, C, where)
+        tail = (rep,)
+    if form == 'masked':
+        if not isinstance(trilinear, (bool, int)) or trilinear not in (0, 1):
+            raise EssHipError(f'{fn}: trilinear={trilinear!r} must be False or True')
+        if trilinear and rep != EVENT_REP_SIGNED:
+            raise EssHipError(f'{fn}: trilinear=True builds the signed grid alone, representation={representation!r} must be EVENT_REP_SIGNED')
+        if not trilinear and (maps is not None or map_of is not None):
+            raise EssHipError(f'{fn}: maps / map_of are read by the trilinear flavour alone (trilinear=False)')
+        tail += (int(trilinear),)
+    t = cols[0][1]
+    if kind == 'store':
+        capacity, total = _store_columns(fn, cols, total)
+        window_capacity = _int_in(fn, 'window_capacity', window_capacity, 1, INGEST_MAX_CAPACITY)
+        _formed_words(fn, words[:1], torch.int64, (n,))
+        _formed_words(fn, words[1:], torch.int32, (n,))
+    else:
+        _event_columns(fn, cols + words, n, ring=kind == 'ring')
+    takes_masks = form in ('masked', 'store_masked')
+    mask_form = _mask_form(fn, *masks, n) if takes_masks else None
+    if out is not None:
+        acc = _ingest_acc(fn, named, acc, out)
+    else:
+        _on_device(fn, named)
+    if form not in ('plain', 'rep'):
+        tail += _rectify_args(fn, maps, map_of, n, acc.device) if trilinear or form == 'trilinear' else _NO_RECTIFY
+    if takes_masks:
+        tail += _mask_args(fn, masks[0], masks[1], mask_form, n, acc.device)
+    if kind == 'store':
+        source = [c_void_p(v.data_ptr()) for _, v in cols] + [ptr(words[0][1], torch.int64)] + [ptr(v, torch.int32) for _, v in words[1:]] + \
+            [capacity, total, window_capacity]
+    else:
+        source = _column_pointers(cols + words)
+        if form == 'masked' and kind == 'columns':  # (the one entry point of both sources: no rows, no starts)
+            source[4:4] = [c_void_p(0), c_void_p(0)]
+        source += [t.shape[1]] + ([t.shape[0]] if kind == 'ring' or form == 'masked' else [])
+    out_arg = () if has_out == 'none' else (c_void_p(0 if out is None else out.data_ptr()),)
+    _check(getattr(lib(), 'ess_' + fn)(*source, n, C, H, W, c_void_p(acc.data_ptr()), acc.numel() * 8, *out_arg, *tail, stream()), 'ess_' + fn)
+    return out if out is not None else acc
 
 
 RECTIFY_NONE = -1  # ESS_RECTIFY_NONE: a map word for a stream whose raw pixels are its coordinates
@@ -1074,7 +1135,8 @@ def event_ingest_columns_trilinear(t, x, y, p, counts, formats, out, maps=None, 
     pixel outside it drops the event), anything else: the stream counts as empty -- or None: RECTIFY_NONE throughout.  A window
     whose last time equals its first gives an all-zero grid.  VoxelGrid(normalize=True)'s own normalisation is not applied.
     Everything else: as event_ingest_columns."""
-    return _event_ingest_columns('event_ingest_columns_trilinear', t, x, y, p, counts, formats, out, acc, (maps, map_of))
+    return _event_call('event_ingest_columns_trilinear', 'columns', 'trilinear', (t, x, y, p), (counts, formats), out, acc, 'required',
+                       rectify=(maps, map_of))
 
 
 def event_ingest_ring(t, x, y, p, rows, starts, counts, formats, out, acc=None):
@@ -1085,29 +1147,15 @@ def event_ingest_ring(t, x, y, p, rows, starts, counts, formats, out, acc=None):
     an all-zero grid, INGEST_KEEP (< 0): out[i] is neither read nor written, a count above ring: ring; a row outside [0, n_rows), a
     start outside [0, ring) or an unknown format bit: the slot counts as empty.  Two slots may name one row.  out: fp32
     [n_slots, bins, H, W], returned; acc: as event_ingest, at least n_slots * bins * H * W elements."""
-    return _event_ingest_ring('event_ingest_ring', t, x, y, p, rows, starts, counts, formats, out, acc, None)
-
-
-def _event_ingest_ring(fn, t, x, y, p, rows, starts, counts, formats, out, acc, rectify):
-    """event_ingest_ring (rectify None) / event_ingest_ring_trilinear (rectify: (maps, map_of) as given): the checks and the call"""
-    words = (('t', t), ('x', x), ('y', y), ('p', p), ('rows', rows), ('starts', starts), ('counts', counts), ('formats', formats))
-    named = words + (('out', out),) + ((('acc', acc),) if acc is not None else ())
-    _are_tensors(fn, named)
-    n_slots, bins, H, W = _ingest_out(fn, out, 'n_slots')
-    _event_columns(fn, words, n_slots, ring=True)
-    acc = _ingest_acc(fn, named, acc, out)
-    n_rows, ring = t.shape
-    tail = () if rectify is None else _rectify_args(fn, rectify[0], rectify[1], n_slots, out.device)
-    _check(getattr(lib(), 'ess_' + fn)(*_column_pointers(words), ring, n_rows, n_slots, bins, H, W, c_void_p(acc.data_ptr()),
-                                       acc.numel() * 8, c_void_p(out.data_ptr()), *tail, stream()), 'ess_' + fn)
-    return out
+    return _event_call('event_ingest_ring', 'ring', 'plain', (t, x, y, p), (rows, starts, counts, formats), out, acc, 'required')
 
 
 def event_ingest_ring_trilinear(t, x, y, p, rows, starts, counts, formats, out, maps=None, map_of=None, acc=None):
     """event_ingest_ring in the trilinear flavour: the same grids, bit for bit, as event_ingest_columns_trilinear gives on the same
     windows laid out from entry 0.  maps, map_of (int32 [n_slots], slot i's map): as event_ingest_columns_trilinear; everything else:
     as event_ingest_ring."""
-    return _event_ingest_ring('event_ingest_ring_trilinear', t, x, y, p, rows, starts, counts, formats, out, acc, (maps, map_of))
+    return _event_call('event_ingest_ring_trilinear', 'ring', 'trilinear', (t, x, y, p), (rows, starts, counts, formats), out, acc,
+                       'required', rectify=(maps, map_of))
 
 
 # The ring ingest in its two halves (ess_event_scatter_ring* / ess_event_grid_finish): the LOADER's grid -- normalised over its
@@ -1121,12 +1169,13 @@ def event_scatter_ring(t, x, y, p, rows, starts, counts, formats, acc):
     """The first half of event_ingest_ring: the windows' events are added into acc and nothing else happens.  acc: device int64
     [n_slots, bins, H, W] -- the grid's geometry is read from it -- ALL ZERO before the call; behind it it holds the sums at scale 2^40
     that event_grid_finish turns into grids (and zeroes again).  t .. formats: as event_ingest_ring.  -> acc"""
-    return _event_scatter_ring('event_scatter_ring', t, x, y, p, rows, starts, counts, formats, acc, None)
+    return _event_call('event_scatter_ring', 'ring', 'plain', (t, x, y, p), (rows, starts, counts, formats), None, acc, 'none')
 
 
 def event_scatter_ring_trilinear(t, x, y, p, rows, starts, counts, formats, acc, maps=None, map_of=None):
     """event_scatter_ring in the trilinear flavour: the first half of event_ingest_ring_trilinear; maps, map_of: as there."""
-    return _event_scatter_ring('event_scatter_ring_trilinear', t, x, y, p, rows, starts, counts, formats, acc, (maps, map_of))
+    return _event_call('event_scatter_ring_trilinear', 'ring', 'trilinear', (t, x, y, p), (rows, starts, counts, formats), None, acc,
+                       'none', rectify=(maps, map_of))
 
 
 # The event REPRESENTATIONS of the column / ring ingest (ess_event_*_rep): what the reference's loaders hand the network
@@ -1192,52 +1241,23 @@ def event_scatter_ring_rep(t, x, y, p, rows, starts, counts, formats, acc, repre
                              neither checks nor drops them (x + width * y wraps into a neighbouring row, or raises): not reproduced.
     Counts, rows, starts, format words and INGEST_KEEP: as event_ingest_ring.  The sums stay a pure function of the SET of events;
     event_grid_finish* turn them into grids over all C planes of a slot.  -> acc"""
-    fn = 'event_scatter_ring_rep'
-    words = (('t', t), ('x', x), ('y', y), ('p', p), ('rows', rows), ('starts', starts), ('counts', counts), ('formats', formats))
-    named = words + (('acc', acc),)
-    _are_tensors(fn, named)
-    n_slots, C, H, W = _finish_acc(fn, acc, 'H, W')
-    rep = _event_rep_of(fn, representation, C, 'acc')
-    _event_columns(fn, words, n_slots, ring=True)
-    _on_device(fn, named)
-    n_rows, ring = t.shape
-    _check(lib().ess_event_scatter_ring_rep(*_column_pointers(words), ring, n_rows, n_slots, C, H, W, c_void_p(acc.data_ptr()),
-                                            acc.numel() * 8, rep, stream()), 'ess_' + fn)
-    return acc
+    return _event_call('event_scatter_ring_rep', 'ring', 'rep', (t, x, y, p), (rows, starts, counts, formats), None, acc, 'none',
+                       representation=representation)
 
 
 def event_ingest_ring_rep(t, x, y, p, rows, starts, counts, formats, out, representation, acc=None):
     """event_ingest_ring in one of the three event representations (event_scatter_ring_rep names them): the scatter and the plain
     finish, out fp32 [n_slots, C, H, W] = (float)sums * 2^-40, returned.  EVENT_REP_SIGNED gives event_ingest_ring's bits.
     Everything else: as event_ingest_ring; acc: at least n_slots * C * H * W elements."""
-    fn = 'event_ingest_ring_rep'
-    words = (('t', t), ('x', x), ('y', y), ('p', p), ('rows', rows), ('starts', starts), ('counts', counts), ('formats', formats))
-    named = words + (('out', out),) + ((('acc', acc),) if acc is not None else ())
-    _are_tensors(fn, named)
-    n_slots, C, H, W = _ingest_out(fn, out, 'n_slots')
-    rep = _event_rep_of(fn, representation, C, 'out')
-    _event_columns(fn, words, n_slots, ring=True)
-    acc = _ingest_acc(fn, named, acc, out)
-    n_rows, ring = t.shape
-    _check(lib().ess_event_ingest_ring_rep(*_column_pointers(words), ring, n_rows, n_slots, C, H, W, c_void_p(acc.data_ptr()),
-                                           acc.numel() * 8, c_void_p(out.data_ptr()), rep, stream()), 'ess_' + fn)
-    return out
+    return _event_call('event_ingest_ring_rep', 'ring', 'rep', (t, x, y, p), (rows, starts, counts, formats), out, acc, 'required',
+                       representation=representation)
 
 
 def event_ingest_columns_rep(t, x, y, p, counts, formats, out, representation, acc=None):
     """event_ingest_columns in one of the three event representations (event_scatter_ring_rep names them): out fp32 [S, C, H, W],
     returned.  EVENT_REP_SIGNED gives event_ingest_columns' bits.  Everything else: as event_ingest_columns."""
-    fn = 'event_ingest_columns_rep'
-    words = (('t', t), ('x', x), ('y', y), ('p', p), ('counts', counts), ('formats', formats))
-    named = words + (('out', out),) + ((('acc', acc),) if acc is not None else ())
-    _are_tensors(fn, named)
-    S, C, H, W = _ingest_out(fn, out, 'S')
-    rep = _event_rep_of(fn, representation, C, 'out')
-    _event_columns(fn, words, S, ring=False)
-    acc = _ingest_acc(fn, named, acc, out)
-    _check(lib().ess_event_ingest_columns_rep(*_column_pointers(words), t.shape[1], S, C, H, W, c_void_p(acc.data_ptr()),
-                                              acc.numel() * 8, c_void_p(out.data_ptr()), rep, stream()), 'ess_' + fn)
-    return out
+    return _event_call('event_ingest_columns_rep', 'columns', 'rep', (t, x, y, p), (counts, formats), out, acc, 'required',
+                       representation=representation)
 
 
 # Hot-pixel masks (ess_event_ingest_masked / ess_event_hot_pixel_mask): per-sensor bit masks applied to the RAW events
@@ -1314,38 +1334,9 @@ def event_ingest_masked(t, x, y, p, rows, starts, counts, formats, out, masks=No
     fn = 'event_ingest_masked'
     if (rows is None) != (starts is None):
         raise EssHipError(f'{fn}: rows and starts are both given (the ring source) or both None (the column source)')
-    ring = rows is not None
-    words = (('t', t), ('x', x), ('y', y), ('p', p)) + ((('rows', rows), ('starts', starts)) if ring else ()) + \
-        (('counts', counts), ('formats', formats))
-    if out is None and acc is None:
-        raise EssHipError(f'{fn}: out=None (scatter only) needs acc, the int64 [n_slots, C, H, W] sums it leaves')
-    named = words + ((('out', out),) if out is not None else ()) + ((('acc', acc),) if acc is not None else ())
-    _are_tensors(fn, named)
-    n_slots, C, H, W = _ingest_out(fn, out, 'n_slots') if out is not None else _finish_acc(fn, acc, 'H, W')
-    rep = _event_rep_of(fn, representation, C, 'out' if out is not None else 'acc')
-    if not isinstance(trilinear, (bool, int)) or trilinear not in (0, 1):
-        raise EssHipError(f'{fn}: trilinear={trilinear!r} must be False or True')
-    if trilinear and rep != EVENT_REP_SIGNED:
-        raise EssHipError(f'{fn}: trilinear=True builds the signed grid alone, representation={representation!r} must be EVENT_REP_SIGNED')
-    if not trilinear and (maps is not None or map_of is not None):
-        raise EssHipError(f'{fn}: maps / map_of are read by the trilinear flavour alone (trilinear=False)')
-    _event_columns(fn, words, n_slots, ring=ring)
-    form = _mask_form(fn, masks, mask_of, mask_size, n_slots)
-    if out is not None:
-        acc = _ingest_acc(fn, named, acc, out)
-    else:
-        _on_device(fn, named)
-    dev = acc.device
-    rect = _rectify_args(fn, maps, map_of, n_slots, dev) if trilinear else (c_void_p(0), c_void_p(0), 0, 1, 1)
-    mask = _mask_args(fn, masks, mask_of, form, n_slots, dev)
-    cols = _column_pointers(words)
-    if not ring:
-        cols = cols[:4] + [c_void_p(0), c_void_p(0)] + cols[4:]
-    n_rows, span = t.shape
-    _check(lib().ess_event_ingest_masked(*cols, span, n_rows, n_slots, C, H, W, c_void_p(acc.data_ptr()), acc.numel() * 8,
-                                         c_void_p(0 if out is None else out.data_ptr()), rep, int(trilinear), *rect, *mask, stream()),
-           'ess_' + fn)
-    return out if out is not None else acc
+    kind, words = ('columns', (counts, formats)) if rows is None else ('ring', (rows, starts, counts, formats))
+    return _event_call(fn, kind, 'masked', (t, x, y, p), words, out, acc, 'optional', representation=representation, trilinear=trilinear,
+                       rectify=(maps, map_of), masks=(masks, mask_of, mask_size))
 
 
 def event_hot_pixel_mask(sums, thresholds, masks, mode=MASK_REPLACE):
@@ -1382,20 +1373,6 @@ def _finish_acc(fn, acc, dims):
     if acc.dim() != 4 or acc.dtype != torch.int64 or acc.numel() == 0:
         raise EssHipError(f'{fn}: acc must be a non-empty int64 [n_slots, bins, {dims}] tensor, got {acc.dtype}{tuple(acc.shape)}')
     return acc.shape
-
-
-def _event_scatter_ring(fn, t, x, y, p, rows, starts, counts, formats, acc, rectify):
-    words = (('t', t), ('x', x), ('y', y), ('p', p), ('rows', rows), ('starts', starts), ('counts', counts), ('formats', formats))
-    named = words + (('acc', acc),)
-    _are_tensors(fn, named)
-    n_slots, bins, H, W = _finish_acc(fn, acc, 'H, W')
-    _event_columns(fn, words, n_slots, ring=True)
-    _on_device(fn, named)
-    n_rows, ring = t.shape
-    tail = () if rectify is None else _rectify_args(fn, rectify[0], rectify[1], n_slots, acc.device)
-    _check(getattr(lib(), 'ess_' + fn)(*_column_pointers(words), ring, n_rows, n_slots, bins, H, W, c_void_p(acc.data_ptr()),
-                                       acc.numel() * 8, *tail, stream()), 'ess_' + fn)
-    return acc
 
 
 # The device event store (ess_event_scatter_store / ess_event_store_windows): windows cut on the device out of recordings that were
@@ -1450,28 +1427,8 @@ def event_scatter_store(t, x, y, p, starts, counts, formats, acc, flavour, total
     acc stay as they are.  window_capacity (1 .. 2^22) shapes the launch, not the store's size.  acc: device int64 [n_slots, C, H, W],
     the sums are added to it.  flavour: EVENT_STORE_SIGNED / _SEPARATE / _HISTOGRAM (the EVENT_REP_* rules for C) or
     EVENT_STORE_TRILINEAR with maps, map_of as event_scatter_ring_trilinear takes them (refused with any other flavour).  -> acc"""
-    fn = 'event_scatter_store'
-    cols = (('t', t), ('x', x), ('y', y), ('p', p))
-    words = (('starts', starts), ('counts', counts), ('formats', formats))
-    named = cols + words + (('acc', acc),)
-    _are_tensors(fn, named)
-    n_slots, C, H, W = _finish_acc(fn, acc, 'H, W')
-    if isinstance(flavour, bool) or flavour not in _EVENT_STORE_FLAVOURS:
-        raise EssHipError(f'{fn}: flavour={flavour!r} must be EVENT_STORE_SIGNED, _SEPARATE, _HISTOGRAM or _TRILINEAR')
-    if flavour != EVENT_STORE_TRILINEAR:
-        _event_rep_of(fn, int(flavour), C, 'acc')
-        if maps is not None or map_of is not None:
-            raise EssHipError(f'{fn}: maps / map_of belong to flavour=EVENT_STORE_TRILINEAR')
-    capacity, total = _store_columns(fn, cols, total)
-    window_capacity = _int_in(fn, 'window_capacity', window_capacity, 1, INGEST_MAX_CAPACITY)
-    _formed_words(fn, words[:1], torch.int64, (n_slots,))
-    _formed_words(fn, words[1:], torch.int32, (n_slots,))
-    _on_device(fn, named)
-    tail = _rectify_args(fn, maps, map_of, n_slots, acc.device) if flavour == EVENT_STORE_TRILINEAR else (c_void_p(0), c_void_p(0), 0, 1, 1)
-    _check(lib().ess_event_scatter_store(*(c_void_p(v.data_ptr()) for _, v in cols), ptr(starts, torch.int64), ptr(counts, torch.int32),
-                                         ptr(formats, torch.int32), capacity, total, window_capacity, n_slots, C, H, W,
-                                         c_void_p(acc.data_ptr()), acc.numel() * 8, int(flavour), *tail, stream()), 'ess_' + fn)
-    return acc
+    return _event_call('event_scatter_store', 'store', 'store', (t, x, y, p), (starts, counts, formats), None, acc, 'none', flavour=flavour,
+                       rectify=(maps, map_of), total=total, window_capacity=window_capacity)
 
 
 def event_store_windows(t, table, recording, bounds, rule, sequence_steps, starts, counts, formats, flags, total, window_capacity,
@@ -1536,37 +1493,46 @@ def event_ingest_store(t, x, y, p, starts, counts, formats, out, flavour, total,
     masks, mask_of, mask_size: as event_ingest_masked takes them -- a hot event is dropped on its raw (x, y) before a rectify map
     sees it, the window's time base comes from its first and last event whether masked or not, a mask word that is neither
     MASK_NONE nor in 0 .. n_masks - 1 leaves the slot empty.  masks=None and mask_of=None: event_scatter_store's sums, bit for bit."""
-    fn = 'event_ingest_store'
-    cols = (('t', t), ('x', x), ('y', y), ('p', p))
-    words = (('starts', starts), ('counts', counts), ('formats', formats))
-    if out is None and acc is None:
-        raise EssHipError(f'{fn}: out=None (scatter only) needs acc, the int64 [n_slots, C, H, W] sums it leaves')
-    named = cols + words + ((('out', out),) if out is not None else ()) + ((('acc', acc),) if acc is not None else ())
-    _are_tensors(fn, named)
-    n_slots, C, H, W = _ingest_out(fn, out, 'n_slots') if out is not None else _finish_acc(fn, acc, 'H, W')
-    if isinstance(flavour, bool) or flavour not in _EVENT_STORE_FLAVOURS:
-        raise EssHipError(f'{fn}: flavour={flavour!r} must be EVENT_STORE_SIGNED, _SEPARATE, _HISTOGRAM or _TRILINEAR')
-    if flavour != EVENT_STORE_TRILINEAR:
-        _event_rep_of(fn, int(flavour), C, 'out' if out is not None else 'acc')
-        if maps is not None or map_of is not None:
-            raise EssHipError(f'{fn}: maps / map_of belong to flavour=EVENT_STORE_TRILINEAR')
-    capacity, total = _store_columns(fn, cols, total)
-    window_capacity = _int_in(fn, 'window_capacity', window_capacity, 1, INGEST_MAX_CAPACITY)
-    _formed_words(fn, words[:1], torch.int64, (n_slots,))
-    _formed_words(fn, words[1:], torch.int32, (n_slots,))
-    form = _mask_form(fn, masks, mask_of, mask_size, n_slots)
-    if out is not None:
-        acc = _ingest_acc(fn, named, acc, out)
-    else:
-        _on_device(fn, named)
-    dev = acc.device
-    rect = _rectify_args(fn, maps, map_of, n_slots, dev) if flavour == EVENT_STORE_TRILINEAR else (c_void_p(0), c_void_p(0), 0, 1, 1)
-    mask = _mask_args(fn, masks, mask_of, form, n_slots, dev)
-    _check(lib().ess_event_ingest_store(*(c_void_p(v.data_ptr()) for _, v in cols), ptr(starts, torch.int64), ptr(counts, torch.int32),
-                                        ptr(formats, torch.int32), capacity, total, window_capacity, n_slots, C, H, W,
-                                        c_void_p(acc.data_ptr()), acc.numel() * 8, c_void_p(0 if out is None else out.data_ptr()),
-                                        int(flavour), *rect, *mask, stream()), 'ess_' + fn)
-    return out if out is not None else acc
+    return _event_call('event_ingest_store', 'store', 'store_masked', (t, x, y, p), (starts, counts, formats), out, acc, 'optional',
+                       flavour=flavour, rectify=(maps, map_of), masks=(masks, mask_of, mask_size), total=total,
+                       window_capacity=window_capacity)
+
+
+def event_voxels(kind, cols, words, out, acc, representation=EVENT_REP_SIGNED, trilinear=False, maps=None, map_of=None, masks=None,
+                 total=None, window_capacity=None):
+    """The one route from a caller's configuration to the binding above that serves it; no kernel path and no check of its own.
+    kind, cols, words: the source as _event_call takes it -- 'ring' (rows, starts, counts, formats), 'columns' (counts, formats) or
+    'store' (starts, counts, formats), the latter with total and window_capacity.  out: the grids, or None: scatter only into acc.
+    trilinear: the trilinear flavour with maps / map_of (handed on under trilinear alone), else `representation`.  masks: None, or
+    (masks, mask_of, mask_size) of a caller that was configured with hot-pixel masks:
+        masks                      -> event_ingest_masked, the store: event_ingest_store
+        no masks, trilinear        -> event_ingest_<kind>_trilinear / event_scatter_ring_trilinear
+        no masks, not signed       -> event_ingest_<kind>_rep / event_scatter_ring_rep
+        no masks, signed           -> event_ingest_<kind> / event_scatter_ring
+        the store without masks    -> event_scatter_store (out None), event_ingest_store"""
+    if not trilinear:
+        maps = map_of = None
+    if kind == 'store':
+        flavour = EVENT_STORE_TRILINEAR if trilinear else representation
+        if masks is None and out is None:
+            return event_scatter_store(*cols, *words, acc, flavour, total, window_capacity, maps, map_of)
+        m = (None, None, None) if masks is None else masks
+        return event_ingest_store(*cols, *words, out, flavour, total, window_capacity, masks=m[0], mask_of=m[1], mask_size=m[2], maps=maps,
+                                  map_of=map_of, acc=acc)
+    if masks is not None:
+        rows, starts = words[:2] if kind == 'ring' else (None, None)
+        return event_ingest_masked(*cols, rows, starts, *words[-2:], out, *masks, representation=representation, trilinear=trilinear,
+                                   maps=maps, map_of=map_of, acc=acc)
+    if out is None and kind != 'ring':
+        raise EssHipError(f"event_voxels: out=None (scatter only) without masks is the ring's and the store's (kind={kind!r})")
+    name = f'event_ingest_{kind}' if out is not None else 'event_scatter_ring'
+    grids = (acc,) if out is None else (out,)
+    after = () if out is None else (acc,)
+    if trilinear:
+        return globals()[name + '_trilinear'](*cols, *words, *grids, maps, map_of, *after)
+    if representation != EVENT_REP_SIGNED:
+        return globals()[name + '_rep'](*cols, *words, *grids, representation, *after)
+    return globals()[name](*cols, *words, *grids, *after)
 
 
 def event_store_pixel_counts(x, y, begins, ends, formats, counts, total):

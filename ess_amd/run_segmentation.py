@@ -923,32 +923,16 @@ class MultiStreamSegmenter(GraphedWindowState):
     def _ingest(self, ev, b=None):
         """the round's first launches: the static event buffers (b: their first b slots) -> the grids ev, inside the capture"""
         cut = (lambda v: v) if b is None else (lambda v: v[:b])
-        tri, rep = self.voxel == 'trilinear', self._rep
-        if self._hot is not None:  # (hot_pixel_masks: one entry point for both sources and every flavour)
-            w = [cut(v) for v in self._words]
-            if self._ring is not None:
-                cols, (rows, starts, counts, formats, map_of, mask_of) = self._ring, w
-            else:
-                cols, rows, starts, (counts, formats, map_of, mask_of) = tuple(cut(c) for c in self._columns), None, None, w
-            hip.event_ingest_masked(*cols, rows, starts, counts, formats, ev, self._hot.words, mask_of, self._hot.size, representation=rep,
-                                    trilinear=tri, maps=self._maps if tri else None, map_of=map_of if tri else None, acc=self._acc)
-        elif self._ring is not None:  # (every row of the rings stays in reach: a slot names its row)
-            if tri:
-                hip.event_ingest_ring_trilinear(*self._ring, *(cut(w) for w in self._words[:4]), ev, self._maps, cut(self._words[4]), self._acc)
-            elif rep != hip.EVENT_REP_SIGNED:
-                hip.event_ingest_ring_rep(*self._ring, *(cut(w) for w in self._words), ev, rep, self._acc)
-            else:
-                hip.event_ingest_ring(*self._ring, *(cut(w) for w in self._words), ev, self._acc)
-        elif self._columns is not None:
-            if tri:
-                hip.event_ingest_columns_trilinear(*(cut(c) for c in self._columns), cut(self._counts), cut(self._formats), ev, self._maps,
-                                                   cut(self._words[2]), self._acc)
-            elif rep != hip.EVENT_REP_SIGNED:
-                hip.event_ingest_columns_rep(*(cut(c) for c in self._columns), cut(self._counts), cut(self._formats), ev, rep, self._acc)
-            else:
-                hip.event_ingest_columns(*(cut(c) for c in self._columns), cut(self._counts), cut(self._formats), ev, self._acc)
-        else:
+        if self._ring is None and self._columns is None:
             hip.event_ingest(cut(self._records), cut(self._counts), ev, self._acc)
+            return
+        # the words: the source's own (rows, starts, counts, formats / counts, formats), the map words where there are any, the mask
+        # words behind them.  Every row of the rings stays in reach (a slot names its row); the columns are cut like the words.
+        kind, cols, k = ('ring', self._ring, 4) if self._ring is not None else ('columns', tuple(cut(c) for c in self._columns), 2)
+        w = [cut(v) for v in self._words]
+        tri = self.voxel == 'trilinear'
+        hip.event_voxels(kind, cols, w[:k], ev, self._acc, representation=self._rep, trilinear=tri, maps=self._maps,
+                         map_of=w[k] if tri else None, masks=None if self._hot is None else (self._hot.words, w[k + 1], self._hot.size))
 
     # ---- hot-pixel masks (hot_pixel_masks=[...]): per-sensor bit masks the ingest applies to the raw events
     def _hot_slots(self, what):

@@ -633,29 +633,14 @@ class SequenceSegmenter:
         """the device work of one sequence round on the static rings, words and ground truth -> (labels, colour, confidence)"""
         with torch.no_grad():
             ev = self._in
-            if self._hot is not None:  # hot_pixel_masks: both heads through the one masked entry point
-                tri, w = self.voxel == 'trilinear', self._words
-                out = None if self._loader_grid else ev
-                hip.event_ingest_masked(*self._ring, *w[:4], out, self._hot.words, w[5], self._hot.size, representation=self._rep,
-                                        trilinear=tri, maps=self._maps if tri else None, map_of=w[4] if tri else None, acc=self._acc)
-                if self._loader_grid:
-                    crop_rows, resize, normalize = self._grid
-                    hip.event_grid_finish(w[2], self._acc, ev, crop_rows=crop_rows, resize=resize, normalize=normalize)
-            elif self._loader_grid:  # the loader's grid: the sums at the size the loader voxelises at, then its normalise / cut / resize
-                if self.voxel == 'trilinear':
-                    hip.event_scatter_ring_trilinear(*self._ring, *self._words[:4], self._acc, self._maps, self._words[4])
-                elif self._rep != hip.EVENT_REP_SIGNED:
-                    hip.event_scatter_ring_rep(*self._ring, *self._words, self._acc, self._rep)
-                else:
-                    hip.event_scatter_ring(*self._ring, *self._words, self._acc)
+            tri, w = self.voxel == 'trilinear', self._words  # (rows, starts, counts, formats; the map words; the mask words)
+            # the loader's grid: scatter only -- the sums at the size the loader voxelises at -- then its normalise / cut / resize
+            hip.event_voxels('ring', self._ring, w[:4], None if self._loader_grid else ev, self._acc, representation=self._rep, trilinear=tri,
+                             maps=self._maps, map_of=w[4] if tri else None,
+                             masks=None if self._hot is None else (self._hot.words, w[5], self._hot.size))
+            if self._loader_grid:
                 crop_rows, resize, normalize = self._grid
-                hip.event_grid_finish(self._words[2], self._acc, ev, crop_rows=crop_rows, resize=resize, normalize=normalize)
-            elif self.voxel == 'trilinear':
-                hip.event_ingest_ring_trilinear(*self._ring, *self._words[:4], ev, self._maps, self._words[4], self._acc)
-            elif self._rep != hip.EVENT_REP_SIGNED:
-                hip.event_ingest_ring_rep(*self._ring, *self._words, ev, self._rep, self._acc)
-            else:
-                hip.event_ingest_ring(*self._ring, *self._words, ev, self._acc)
+                hip.event_grid_finish(w[2], self._acc, ev, crop_rows=crop_rows, resize=resize, normalize=normalize)
             return self._round_from(ev)
 
     def _round_from(self, ev):

@@ -721,10 +721,9 @@ def sequence_loader_grid(a, hip, cfg, wins, out, E2VIDRecurrent, SemSegE2VID, de
                 acc_big = torch.zeros(T * S, a.bins, Hs, Ws, dtype=torch.int64, device=dev)
 
                 def composed_round():
-                    if seq.voxel == 'trilinear':
-                        hip.event_ingest_ring_trilinear(*seq._ring, *seq._words[:4], big, seq._maps, seq._words[4], acc_big)
-                    else:
-                        hip.event_ingest_ring(*seq._ring, *seq._words, big, acc_big)
+                    tri = seq.voxel == 'trilinear'
+                    hip.event_voxels('ring', seq._ring, seq._words[:4], big, acc_big, trilinear=tri, maps=seq._maps,
+                                     map_of=seq._words[4] if tri else None)
                     hip.voxel_normalize_(big, 0 if norm == hip.GRID_NORM_UNBIASED else 1)
                     ev = F.interpolate(big[:, :, :crop_rows], size=(Hr, Wr), mode='bilinear', align_corners=True)[:, :, :Hn].contiguous()
                     return seq._round_from(ev)

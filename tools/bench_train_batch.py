@@ -42,10 +42,8 @@ class ComposedBuilder(EventBatchBuilder):
         if 'full' not in st:
             st['full'] = torch.zeros(B * T, self.bins, self.height, self.width, dtype=torch.float32, device=self.device)
         full = st['full']
-        if self.voxel == 'trilinear':
-            hip.event_scatter_ring_trilinear(*st['cols'], *words[:4], st['acc'], st['maps'], words[4])
-        else:
-            hip.event_scatter_ring(*st['cols'], *words, st['acc'])
+        tri = self.voxel == 'trilinear'
+        hip.event_voxels('ring', st['cols'], words[:4], None, st['acc'], trilinear=tri, maps=st['maps'], map_of=words[4] if tri else None)
         hip.event_grid_finish(words[2], st['acc'], full, crop_rows=self.grid_rows, resize=self.grid_resize, normalize=self.grid_normalize)
         flip_slice(full, ev, self.last_words, T)
         if with_labels:
@@ -210,10 +208,8 @@ def main():
     host_words = params[1].tolist()
 
     def scatter():
-        if new.voxel == 'trilinear':
-            hip.event_scatter_ring_trilinear(*st['cols'], *words[:4], st['acc'], st['maps'], words[4])
-        else:
-            hip.event_scatter_ring(*st['cols'], *words, st['acc'])
+        tri = new.voxel == 'trilinear'
+        hip.event_voxels('ring', st['cols'], words[:4], None, st['acc'], trilinear=tri, maps=st['maps'], map_of=words[4] if tri else None)
 
     def finish():
         hip.event_grid_finish(words[2], st['acc'], full, crop_rows=new.grid_rows, resize=new.grid_resize, normalize=new.grid_normalize)

@@ -1,5 +1,6 @@
 // Stand-alone host program: the argument checks of every entry point of voxel_ingest.hip -- the ingest from records, columns and
-// rings in both flavours, the scatter-only ring calls, the three representation calls, the two loader finishes and the label window.  The checks all come in front
+// rings in both flavours, the scatter-only ring calls, the three representation calls, the masked ingest (both sources, with and
+// without out), the two store calls, the two loader finishes and the label window.  The checks all come in front
 // of any launch, so no device is needed.  Meant to be built with the host sanitizers and run on its own (a library loaded into python
 // is out of their reach):
 //
@@ -52,7 +53,14 @@ struct Args {
   void* out = a;
   const float* maps = nullptr;  // (n_maps = 0: maps must be null)
   const int32_t* map_of = w;
-  int32_t channels = NB, representation = 0;  // (the _rep entry points: the signed grid of NB planes)
+  int32_t channels = NB, representation = 0;  // (the _rep entry points: the signed grid of NB planes; the store's flavour word)
+  // the masked ingest and the store calls alone
+  const int32_t* rows = w;    // (the masked ring calls: words is their formats alone)
+  const int32_t* starts = w;
+  int32_t trilinear = 0;
+  const uint32_t* masks = nullptr;  // (n_masks = 0: masks must be null)
+  const int32_t* mask_of = w;
+  int64_t capacity = 64, total = 48;  // the store's; span is its window_capacity
 };
 
 struct Source {
@@ -61,8 +69,16 @@ struct Source {
   const char* n;     // the count's
   bool ring, with_out, rectify;
   int (*call)(const Args&);
-  bool rep = false;  // takes channels and a representation word
+  bool rep = false;           // takes channels and a representation word
+  bool nullable_out = false;  // out NULL: scatter only, no refusal
+  bool masked = false, store = false, paired = false;  // paired: the masked ingest with rows and starts
 };
+
+int masked(const Args& g, const int32_t* rows, const int32_t* starts, int32_t n_rows, void* out) {
+  return ess_event_ingest_masked(g.t, a, a, g.p, rows, starts, w, g.words, g.span, n_rows, g.n, g.channels, H, W, g.acc, g.acc_bytes,
+                                 (float*)out, g.representation, g.trilinear, g.maps, g.map_of, 0, 28, 44, g.masks, g.mask_of, 0, 28, 44,
+                                 nullptr);
+}
 
 const Source SOURCES[] = {
     {"event_ingest:", "capacity=", "n_streams=", false, true, false,
@@ -113,6 +129,27 @@ const Source SOURCES[] = {
                                            g.representation, nullptr);
      },
      true},
+    {"event_ingest_masked:", "ring=", "n_slots=", true, true, false,
+     [](const Args& g) { return masked(g, g.rows, g.starts, g.n_rows, g.out); }, true, true, true, false, true},
+    {"event_ingest_masked:", "ring=", "n_slots=", true, false, false,
+     [](const Args& g) { return masked(g, g.rows, g.starts, g.n_rows, nullptr); }, true, true, true, false, true},
+    {"event_ingest_masked:", "stride=", "n_streams=", false, true, false,
+     [](const Args& g) { return masked(g, nullptr, nullptr, g.n_rows, g.out); }, true, true, true},
+    {"event_ingest_masked:", "stride=", "n_streams=", false, false, false,
+     [](const Args& g) { return masked(g, nullptr, nullptr, g.n_rows, nullptr); }, true, true, true},
+    {"event_scatter_store:", "window_capacity=", "n_slots=", false, false, false,
+     [](const Args& g) {
+       return ess_event_scatter_store(g.t, a, a, g.p, (const int64_t*)a, w, g.words, g.capacity, g.total, g.span, g.n, g.channels, H, W, g.acc,
+                                      g.acc_bytes, g.representation, g.maps, g.map_of, 0, 28, 44, nullptr);
+     },
+     false, false, false, true},
+    {"event_ingest_store:", "window_capacity=", "n_slots=", false, true, false,
+     [](const Args& g) {
+       return ess_event_ingest_store(g.t, a, a, g.p, (const int64_t*)a, w, g.words, g.capacity, g.total, g.span, g.n, g.channels, H, W, g.acc,
+                                     g.acc_bytes, (float*)g.out, g.representation, g.maps, g.representation == 3 ? g.map_of : nullptr, 0, 28, 44,
+                                     g.masks, g.mask_of, 0, 28, 44, nullptr);
+     },
+     false, true, true, true},
 };
 
 template <class F>
@@ -124,22 +161,56 @@ Args with(F&& change) {
 
 void check_source(const Source& s) {
   auto refused = [&](const Args& g, const char* needle, const char* what) { expect_refused(s.call(g), needle, s.entry, what); };
+  const char* aligned = s.store ? "must be 16-byte, starts 8-byte" : "16-byte aligned";
   refused(with([](Args& g) { g.t = nullptr; }), "null", "a null first pointer");
   refused(with([](Args& g) { g.words = nullptr; }), "null", "a null device word");
   refused(with([](Args& g) { g.acc = nullptr; }), "null", "a null acc");
-  if (s.with_out) refused(with([](Args& g) { g.out = nullptr; }), "null", "a null out");
+  if (s.with_out && !s.nullable_out) refused(with([](Args& g) { g.out = nullptr; }), "null", "a null out");
   for (int32_t n : {0, -1, 65536}) refused(with([&](Args& g) { g.n = n; }), s.n, "a count out of range");
   const int64_t bad_spans[] = {0, -16, ((int64_t)1 << 22) + 16, INT64_MAX, INT64_MIN};
   for (int64_t span : bad_spans) refused(with([&](Args& g) { g.span = span; }), s.span, "a span out of range");
-  if (std::strcmp(s.span, "capacity=") != 0)
+  if (std::strcmp(s.span, "capacity=") != 0 && !s.store)
     for (int64_t span : {8, 24, 1003}) refused(with([&](Args& g) { g.span = span; }), "multiple of 16", "a span that misaligns the rows");
   if (s.ring) refused(with([](Args& g) { g.n_rows = 0; }), "n_rows=0", "n_rows 0");
   refused(with([](Args& g) { g.acc_bytes -= 8; }), "acc has", "a short acc");
   refused(with([](Args& g) { g.n = 2; }), "acc has", "acc sized for one grid of two");
-  refused(with([](Args& g) { g.t = block + 8; }), "16-byte aligned", "a misaligned first pointer");
-  if (std::strcmp(s.span, "capacity=") != 0) refused(with([](Args& g) { g.p = block + 1; }), "16-byte aligned", "a misaligned p");
-  refused(with([](Args& g) { g.acc = block + 8; }), "16-byte aligned", "a misaligned acc");
-  if (s.with_out) refused(with([](Args& g) { g.out = block + 4; }), "16-byte aligned", "a misaligned out");
+  refused(with([](Args& g) { g.t = block + 8; }), aligned, "a misaligned first pointer");
+  if (std::strcmp(s.span, "capacity=") != 0) refused(with([](Args& g) { g.p = block + 1; }), aligned, "a misaligned p");
+  refused(with([](Args& g) { g.acc = block + 8; }), aligned, "a misaligned acc");
+  if (s.with_out) refused(with([](Args& g) { g.out = block + 4; }), aligned, "a misaligned out");
+  if (s.paired) {
+    refused(with([](Args& g) { g.rows = nullptr; }), "rows null, starts given", "starts without rows");
+    refused(with([](Args& g) { g.starts = nullptr; }), "rows given, starts null", "rows without starts");
+  }
+  if (s.masked) {
+    refused(with([](Args& g) { g.mask_of = nullptr; }), "null mask_of", "a null mask_of");
+    refused(with([](Args& g) { g.masks = (const uint32_t*)block; }), "masks must be null", "masks with n_masks 0");
+  }
+  if (s.masked && !s.store) {  // (trilinear is a word of its own, in front of the representation's checks of the source)
+    for (int32_t v : {-1, 2}) refused(with([&](Args& g) { g.trilinear = v; }), "trilinear=", "an unknown trilinear word");
+    for (int32_t r : {1, 2})
+      refused(with([&](Args& g) { g.trilinear = 1; g.representation = r; g.channels = 2; }), "trilinear=1 builds the signed grid alone",
+              "trilinear with a non-signed representation");
+    refused(with([](Args& g) { g.trilinear = 1; g.map_of = nullptr; }), "null map_of", "a null map_of");
+    refused(with([](Args& g) { g.trilinear = 1; g.maps = (const float*)block; }), "maps must be null", "maps with n_maps 0");
+  }
+  if (s.store) {
+    for (int32_t f : {-1, 4, 1 << 20}) refused(with([&](Args& g) { g.representation = f; }), "flavour=", "an unknown flavour");
+    refused(with([](Args& g) { g.representation = 1; }), "channels=5 must be even", "separate polarity with an odd channels");
+    for (int32_t c : {1, 4}) refused(with([&](Args& g) { g.representation = 2; g.channels = c; }), "must be 2", "a histogram of other than 2 planes");
+    refused(with([](Args& g) { g.channels = 0; }), "channels=0 must be positive", "channels 0");
+    const int64_t bad_capacities[] = {0, 8, 72, ((int64_t)1 << 40) + 16};
+    for (int64_t c : bad_capacities) refused(with([&](Args& g) { g.capacity = c; g.total = 0; }), "capacity=", "a capacity out of range");
+    for (int64_t t : {-1, 65}) refused(with([&](Args& g) { g.total = t; }), "total=", "a total outside the capacity");
+    refused(with([](Args& g) { g.representation = 3; g.map_of = nullptr; }), "null map_of", "a null map_of");
+    refused(with([](Args& g) { g.representation = 3; g.maps = (const float*)block; }), "maps must be null", "maps with n_maps 0");
+    if (s.masked) {
+      for (int32_t f : {0, 1, 2})
+        refused(with([&](Args& g) { g.representation = f; g.channels = 2; g.maps = (const float*)block; }), "belong to flavour=3",
+                "maps with a non-trilinear flavour");
+      refused(with([](Args& g) { g.mask_of = (const int32_t*)(block + 2); }), "mask_of must be 4-byte aligned", "a misaligned mask_of");
+    }
+  }
   if (s.rectify) {
     refused(with([](Args& g) { g.map_of = nullptr; }), "null map_of", "a null map_of");
     refused(with([](Args& g) { g.maps = (const float*)block; }), "maps must be null", "maps with n_maps 0");
