@@ -20,6 +20,7 @@ import torch
 from .. import hip
 from .data_util import EventColumns, stage_event_columns
 from .event_store import EventStore, StoreSample, duration_bounds, time_bound
+from .image_store import ImageStore
 
 VOXEL_FLAVOURS = ('temporal', 'trilinear')
 _NORMS = {None: hip.GRID_NORM_NONE, 'unbiased': hip.GRID_NORM_UNBIASED, 'population': hip.GRID_NORM_POPULATION}
@@ -147,12 +148,20 @@ class EventBatchBuilder:
     hip.event_grid_finish_window, a torch.index_select of the store's labels and hip.label_window, all inside the captured graph with
     graph=True (one capture per output set, kind of batch and rule).  last_flags: the device int32 [B] flag words of the batch just
     built (hip.EVENT_STORE_FLAG_*; a flagged sample is all zero, as a sample with n < T is); reading them is the caller's
-    synchronisation."""
+    synchronisation.
+
+    frames=ImageStore (store path only; ImageStore.dsec_frames / ddd17_frames): the loaders' PAIRED camera frame.  Every StoreSample
+    then names its frame's slot (frame=), and build() returns (events, frames fp32 [B, 1, Hf, Wf] in [0, 1], labels) -- the tuple the
+    reference loaders return with require_paired_data_*_b.  The slot numbers travel in the batch's one table; hip.image_gather_unit
+    (slot / 255, ToTensor's bits) runs behind label_window, inside the capture.  The frame is NOT flipped or cropped by the window
+    parameters: the reference flips events and label only (sequence.py:291-295), and DDD17 pairs frames in its validation split.
+    original_labels=True (store path, augmentation=False): the sample's stored label, int64 [B, label_hw] as it is, is appended --
+    DDD17's (events, img, label, label_original)."""
 
     def __init__(self, batch_size, sequence_steps, bins, event_capacity, grid_hw, height, width, label_hw, grid_rows=None,
                  grid_resize=None, grid_normalize=None, crop_hw=None, crop_band=None, voxel='temporal', rectify_maps=None,
                  augmentation=True, seed=0, device=None, graph=False, representation=None, store=None, window_events=None,
-                 window_duration=None, window_capacity=None):
+                 window_duration=None, window_capacity=None, frames=None, original_labels=False):
         for name, v in (('batch_size', batch_size), ('sequence_steps', sequence_steps), ('bins', bins)):
             if isinstance(v, bool) or not isinstance(v, int) or v < 1:
                 raise hip.EssHipError(f'{name}={v!r}: a positive int is needed')
@@ -160,6 +169,7 @@ class EventBatchBuilder:
             raise hip.EssHipError(f'batch_size * sequence_steps = {batch_size * sequence_steps}: one launch serves at most 65535 windows')
         Hs, Ws = _pair('grid_hw', grid_hw)
         self._check_store(store, window_events, window_duration, window_capacity, device)
+        self._check_frames(frames, original_labels, augmentation)
         if store is not None:
             event_capacity = None  # (no static columns: the windows are read where the store keeps them)
         elif isinstance(event_capacity, bool) or not isinstance(event_capacity, int) or event_capacity < 1 or \
@@ -213,9 +223,10 @@ class EventBatchBuilder:
     @classmethod
     def ddd17(cls, batch_size, sequence_steps=20, bins=5, event_capacity=2000000, **kw):
         """the DDD17 loader (ddd17_events_loader.py:162-183): 260 x 346 -> 260 x 352 -> the top 200 rows, flip, a 120 x 216 crop
-        inside the bottom 120 rows"""
-        geo = dict(grid_hw=(260, 346), grid_resize=(260, 352), height=200, width=352, label_hw=(200, 346), crop_hw=(120, 216),
-                   crop_band=(80, 120))
+        inside the bottom 120 rows; augmentation=False (its validation split, :187-213): neither flip nor crop, the 200 x 352 grid"""
+        geo = dict(grid_hw=(260, 346), grid_resize=(260, 352), height=200, width=352, label_hw=(200, 346))
+        if kw.get('augmentation', True):
+            geo.update(crop_hw=(120, 216), crop_band=(80, 120))
         return cls(batch_size, sequence_steps, bins, event_capacity, **{**geo, **kw})
 
     def _check_store(self, store, window_events, window_duration, window_capacity, device):
@@ -249,6 +260,24 @@ class EventBatchBuilder:
                 not (self.window if self.store_by_count else 1) <= window_capacity <= hip.INGEST_MAX_CAPACITY:
             raise hip.EssHipError(f'window_capacity={window_capacity!r}: an int in [window_events or 1, {hip.INGEST_MAX_CAPACITY}]')
         self.window_capacity = window_capacity
+
+    def _check_frames(self, frames, original_labels, augmentation):
+        """frames=, original_labels= -> self.frames, self.original_labels: both belong to the store path"""
+        if frames is not None:
+            if self.store is None:
+                raise hip.EssHipError('frames= pairs camera frames with the samples of an EventStore: it needs store=')
+            if not isinstance(frames, ImageStore):
+                raise hip.EssHipError(f'frames must be an ImageStore (ImageStore.dsec_frames / ddd17_frames), got {type(frames).__name__}')
+            if torch.device(frames.device) != torch.device(self.store.device):
+                raise hip.EssHipError(f'frames lies on {frames.device}, the event store on {self.store.device}: a batch is built on one device')
+        if not isinstance(original_labels, bool):
+            raise hip.EssHipError(f'original_labels={original_labels!r} must be True or False')
+        if original_labels and self.store is None:
+            raise hip.EssHipError('original_labels=True returns the labels an EventStore keeps: it needs store=')
+        if original_labels and augmentation:
+            raise hip.EssHipError('original_labels=True with augmentation=True: the stored label is returned as it is, beside a label that '
+                                  'was flipped and cropped (the DDD17 loader returns it in its validation split only)')
+        self.frames, self.original_labels = frames, original_labels
 
     def _check_store_samples(self, samples, params):
         """the checks of one store batch: nothing is written -> (rule, bound words [B][n_bounds], label indices or None, map words, params)"""
@@ -287,6 +316,14 @@ class EventBatchBuilder:
             raise hip.EssHipError('samples: a label for every sample of the batch, or for none')
         if all(labelled) and (store.label_hw != self.label_hw):
             raise hip.EssHipError(f'the store keeps labels of {store.label_hw}, the builder takes label_hw={self.label_hw}')
+        if self.original_labels and not all(labelled):
+            raise hip.EssHipError('original_labels=True: every sample of the batch needs a label')
+        if self.frames is not None:
+            for b, s in enumerate(samples):
+                if s.frame is None:
+                    raise hip.EssHipError(f'samples[{b}] has no frame: with frames= every sample names its paired frame\'s slot')
+                if s.frame >= self.frames.n_images:
+                    raise hip.EssHipError(f'samples[{b}]: frame slot {s.frame}, the frame store holds {self.frames.n_images} images')
         grid, win = (self.height, self.width), self.crop_hw
         if params is None:
             p = draw_window_params(B, grid, win, self.crop_band, self.generator, self.augmentation)  # (the last check: it cannot fail)
@@ -408,8 +445,11 @@ class EventBatchBuilder:
         B, T = self.batch_size, self.sequence_steps
         n_bounds = T + 1 if not self.store_by_count else 1
         at, out = 0, {}
-        for name, dtype, shape in (('bounds', torch.int64, (B, n_bounds)), ('label_of', torch.int64, (B,)),
-                                   ('recording', torch.int32, (B,)), ('sample_map', torch.int32, (B,)), ('params', torch.int32, (B, 4))):
+        sections = [('bounds', torch.int64, (B, n_bounds)), ('label_of', torch.int64, (B,)), ('recording', torch.int32, (B,)),
+                    ('sample_map', torch.int32, (B,)), ('params', torch.int32, (B, 4))]
+        if self.frames is not None:
+            sections.append(('frame_of', torch.int32, (B,)))  # (the paired frames' slots travel in the same table: one upload a batch)
+        for name, dtype, shape in sections:
             out[name] = (at, dtype, shape)
             at += -(-int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size() // 16) * 16
         return out, at
@@ -436,6 +476,9 @@ class EventBatchBuilder:
                      torch.zeros(B, h, w, dtype=torch.int64, device=dev)) for _ in range(2)],
             'maps': None if self.maps is None else self.maps.to(dev),
             'graphs': [None, None],
+            'frames': None if self.frames is None else
+            [torch.zeros((B, 1) + self.frames.slot_hw, dtype=torch.float32, device=dev) for _ in range(2)],
+            'original': [torch.zeros((B,) + self.label_hw, dtype=torch.int64, device=dev) for _ in range(2)] if self.original_labels else None,
         }
 
     def _launch_store(self, k, with_labels, rule):
@@ -457,6 +500,10 @@ class EventBatchBuilder:
         if with_labels:
             torch.index_select(store.labels, 0, tin['label_of'], out=st['labels'])
             hip.label_window(st['labels'], lab, tin['params'], resize=(self.height, self.width))
+            if self.original_labels:
+                st['original'][k].copy_(st['labels'])  # (the stored label as it is: not resized, flipped or cropped)
+        if self.frames is not None:  # (the frame is neither flipped nor cropped: the loaders flip the events and the label only)
+            hip.image_gather_unit(self.frames.images, tin['frame_of'], out=st['frames'][k])
 
     def _build_store(self, samples, params):
         rule, bounds, label_of, map_of, p = self._check_store_samples(samples, params)
@@ -476,6 +523,8 @@ class EventBatchBuilder:
         w['recording'][:] = [s.recording for s in samples]
         w['sample_map'][:] = map_of
         w['params'][:] = p.numpy()
+        if self.frames is not None:
+            w['frame_of'][:] = [s.frame for s in samples]
         st['table'].copy_(stage['buf'], non_blocking=True)
         stage['done'].record()
         if self.use_graph:
@@ -486,7 +535,12 @@ class EventBatchBuilder:
         self.last_params, self.last_flags = p, st['flags'][k]
         ev, lab = st['out'][k]
         h, wd = self.crop_hw
-        return ev.view(B, T * self.channels, h, wd), (lab if label_of is not None else None)
+        batch = [ev.view(B, T * self.channels, h, wd), (lab if label_of is not None else None)]
+        if self.frames is not None:  # (the loaders' tuple: events, paired frame, label)
+            batch.insert(1, st['frames'][k])
+        if self.original_labels:
+            batch.append(st['original'][k])
+        return tuple(batch)
 
     def build(self, samples, params=None):
         """-> (events fp32 [B, T * bins, h, w], labels int64 [B, h, w] or None) on the device, valid until the build after the next"""
@@ -535,7 +589,8 @@ class EventBatchLoader:
     train_loader / val_loader_sensor_b of ESSSupervisedModel.  sample_source: an iterable of batches -- each a list of batch_size
     samples (EventColumns, label[, map index]) -- or a callable that returns one (called anew by createIterators: one epoch each).
     steps: the batches of an epoch (default: len(sample_source)); the iteration also ends where the source does.  Yields
-    [events, labels] (builder.build): a batch stays valid until the one after the next is built."""
+    [events, labels] (builder.build; with frames= / original_labels= the longer tuples, as a list): a batch stays valid until the one
+    after the next is built."""
 
     def __init__(self, sample_source, builder, steps=None):
         if not isinstance(builder, EventBatchBuilder):
@@ -563,5 +618,4 @@ class EventBatchLoader:
             self.createIterators()
         it, self._it = self._it, None
         for _, samples in zip(range(self.steps), it):
-            ev, lab = self.builder.build(samples)
-            yield [ev, lab]
+            yield list(self.builder.build(samples))

@@ -282,10 +282,11 @@ class EventStore:
 class StoreSample:
     """One training sample of an EventStore: recording (its number), its end -- t_end: a time in the unit of the recording's file
     (the recording's t_offset is subtracted before the search), or end: an event index relative to the recording -- exactly one of
-    the two; label: the index of its label in the store's label tensor, or None; map: the number of its rectify map, or None."""
-    __slots__ = ('recording', 't_end', 'end', 'label', 'map')
+    the two; label: the index of its label in the store's label tensor, or None; map: the number of its rectify map, or None;
+    frame: the slot of its paired camera frame in a frame store (image_store.ImageStore, EventBatchBuilder(frames=)), or None."""
+    __slots__ = ('recording', 't_end', 'end', 'label', 'map', 'frame')
 
-    def __init__(self, recording, t_end=None, end=None, label=None, map=None):
+    def __init__(self, recording, t_end=None, end=None, label=None, map=None, frame=None):
         if not _is_int(recording) or recording < 0:
             raise hip.EssHipError(f'StoreSample: recording={recording!r} must be a non-negative int')
         if (t_end is None) == (end is None):
@@ -294,17 +295,17 @@ class StoreSample:
             raise hip.EssHipError(f'StoreSample: t_end={t_end!r} must be a finite time')
         if end is not None and (not _is_int(end) or end < 0):
             raise hip.EssHipError(f'StoreSample: end={end!r} must be a non-negative int')
-        for name, v in (('label', label), ('map', map)):
+        for name, v in (('label', label), ('map', map), ('frame', frame)):
             if v is not None and (not _is_int(v) or v < 0):
                 raise hip.EssHipError(f'StoreSample: {name}={v!r} must be a non-negative int or None')
-        for name, v in zip(self.__slots__, (int(recording), t_end, None if end is None else int(end), label, map)):
+        for name, v in zip(self.__slots__, (int(recording), t_end, None if end is None else int(end), label, map, frame)):
             object.__setattr__(self, name, v)
 
     def __setattr__(self, name, value):
         raise AttributeError('StoreSample is immutable')
 
     def __repr__(self):
-        return f'StoreSample(recording={self.recording}, t_end={self.t_end!r}, end={self.end!r}, label={self.label!r}, map={self.map!r})'
+        return f'StoreSample(recording={self.recording}, t_end={self.t_end!r}, end={self.end!r}, label={self.label!r}, map={self.map!r}, frame={self.frame!r})'
 
 
 class StoreSampler:

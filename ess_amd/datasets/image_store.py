@@ -17,6 +17,11 @@ add int32.  NOT pinned, as before: the albumentations half (datasets/augment.py 
 Deviation: the reference's stretch divides by zero on a constant frame (numpy: NaN -> an undefined uint8); here such a frame becomes
 all 0.  A.Normalize is constructed by the reference and never applied: it has no counterpart.
 
+The PAIRED CAMERA FRAMES of the event loaders (DSEC/dataset/sequence.py:166-176, datasets/ddd17_events_loader.py:187-213) go through
+the same store with other settings -- Image.resize's default filter (bicubic) on the RGB image, the gray conversion behind it, the
+top rows kept: pil_resize_tables, hip.image_ingest_frame, ImageStore(resample=, gray=, keep_rows=), pinned to PIL in the same way
+(tests/test_host_frame_store.py) -- and reach a batch through EventBatchBuilder(frames=) (datasets/event_batches.py).
+
 File readers (png) stay outside: a frame arrives as a uint8 array.  Numpy and torch only."""
 import math
 
@@ -75,6 +80,58 @@ def pil_bilinear_tables(n_in, n_out):
     return np.ascontiguousarray(np.concatenate([xmin[None], count[None], k]).astype(np.int32))
 
 
+RESAMPLE = ('bilinear', 'bicubic')
+
+
+def _bicubic(x):
+    """PIL's bicubic filter (Keys' kernel, a = -0.5, support 2) on a float64 array, in PIL's order of operations"""
+    a = -0.5
+    x = np.abs(x)
+    return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1, np.where(x < 2.0, (((x - 5) * x + 8) * x - 4) * a, 0.0))
+
+
+def pil_resize_tables(n_in, n_out, resample='bilinear'):
+    """pil_bilinear_tables for either filter of PIL's 8-bit Image.resize: resample='bilinear' is that function itself, 'bicubic' (the
+    default of Image.resize on an 'RGB' or 'L' image where the reference's event loaders call it without a filter) has the same
+    int32 [2 + ksize, n_out] layout and window rule with the support doubled -- support = 2 max(n_in / n_out, 1),
+    ksize = 2 ceil(support) + 1 --, the weight ((a + 2)|x| - (a + 3)) x^2 + 1 below 1, (((|x| - 5)|x| + 8)|x| - 4) a below 2, a = -0.5,
+    at x = (i + xmin - center + 0.5) (1 / max(n_in / n_out, 1)), normalised by the sum accumulated in order.  A coefficient is rounded
+    AWAY from zero, as PIL rounds it: int(0.5 + w 2^22) for w >= 0, int(-0.5 + w 2^22) for w < 0.  Refused: a ksize above
+    hip.IMAGE_MAX_TAPS (bicubic: a side shrinking by more than 8)."""
+    if not isinstance(resample, str) or resample not in RESAMPLE:
+        raise hip.EssHipError(f'pil_resize_tables: resample={resample!r}: one of {RESAMPLE}')
+    if resample == 'bilinear':
+        return pil_bilinear_tables(n_in, n_out)
+    for name, v in (('n_in', n_in), ('n_out', n_out)):
+        if not _is_int(v) or not 1 <= v <= hip.IMAGE_MAX_SIDE:
+            raise hip.EssHipError(f'pil_resize_tables: {name}={v!r} must be an int in [1, {hip.IMAGE_MAX_SIDE}]')
+    n_in, n_out = int(n_in), int(n_out)
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = 2.0 * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    if ksize > hip.IMAGE_MAX_TAPS:
+        raise hip.EssHipError(f'pil_resize_tables: {n_in} -> {n_out} needs bicubic windows of {ksize} coefficients, the kernels hold '
+                              f'{hip.IMAGE_MAX_TAPS}: a side shrinks by at most {hip.IMAGE_MAX_TAPS // 4}')
+    ss = 1.0 / fs
+    center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)
+    xmax = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), n_in)
+    count = xmax - xmin
+    w = np.zeros((ksize, n_out), dtype=np.float64)
+    ww = np.zeros(n_out, dtype=np.float64)
+    for i in range(ksize):
+        live = i < count
+        w[i] = np.where(live, _bicubic(((i + xmin).astype(np.float64) - center + 0.5) * ss), 0.0)
+        ww = np.where(live, ww + w[i], ww)  # (accumulated in order, as PIL accumulates it)
+    w = np.where(ww != 0.0, w / np.where(ww != 0.0, ww, 1.0), w)
+    k = np.trunc(np.where(w < 0.0, -0.5, 0.5) + w * float(1 << PRECISION_BITS)).astype(np.int64)
+    # (the kernels add in int32: 2^21 + sum |k| 255 stays below 2^31 while sum |w| < 2, and bicubic's is at most about 1.3)
+    if int(np.abs(k).sum(axis=0).max()) * 255 + (1 << (PRECISION_BITS - 1)) >= 1 << 31:
+        raise hip.EssHipError(f'pil_resize_tables: {n_in} -> {n_out}: a window\'s coefficients overflow the kernels\' int32 sums')
+    return np.ascontiguousarray(np.concatenate([xmin[None], count[None], k]).astype(np.int32))
+
+
 def pil_nearest_table(n_in, n_out):
     """The source index of every output index of PIL's Image.resize(NEAREST) along one axis -> int32 [n_out]: min(int(xo), n_in - 1)
     with xo starting at 0.5 n_in / n_out and advanced by repeated float64 ADDITION of n_in / n_out -- a running sum, which differs
@@ -123,7 +180,8 @@ class _FrameStage:
 
 
 class ImageStore:
-    """ImageStore(capacity_images, resize_hw=(256, 512), source_hw=(1024, 2048), standardization=False, staging_images=2, device=None)
+    """ImageStore(capacity_images, resize_hw=(256, 512), source_hw=(1024, 2048), standardization=False, staging_images=2, device=None,
+               resample='bilinear', gray='first', keep_rows=None)
 
     add_images(frames, labels=None) -> the slot numbers.  frames: a list (or one array [n, ...]) of host uint8 frames, each
     [H, W, 3] RGB or [H, W] gray with (H, W) = source_hw; labels: None, or one host uint8 [H, W] label-id map per frame.  Every frame is
@@ -137,18 +195,44 @@ class ImageStore:
     a full store, labels for some frames but not others, labels where the store keeps none (or none where it keeps them).
 
     Device memory, allocated at the first accepted frame: Hr Wr bytes a slot, as much again with labels, 8 bytes a slot of min / max,
-    the tables, the staging sets and an [H, Wr] scratch.  Cityscapes train, 2975 frames at 256 x 512 with labels: 0.78 GB."""
+    the tables, the staging sets and an [H, Wr] scratch.  Cityscapes train, 2975 frames at 256 x 512 with labels: 0.78 GB.
 
-    def __init__(self, capacity_images, resize_hw=(256, 512), source_hw=(1024, 2048), standardization=False, staging_images=2, device=None):
+    The PAIRED FRAMES of the event loaders (img_left of DSEC, img of DDD17's validation split) are resized otherwise, and three
+    keywords say how; their defaults are the Cityscapes loader's.  resample='bilinear' | 'bicubic': the filter of Image.resize --
+    called without one, as those loaders call it, PIL takes BICUBIC (pil_resize_tables).  gray='first' | 'last': convert('L') in front
+    of the resize, or behind the resize of the RGB image (transforms.Grayscale() follows Image.resize there; the bits differ).
+    keep_rows=n: a slot holds the top n rows of the resized frame, uint8 [n, Wr] (slot_hw).  resize_hw=None: no resize, the gray
+    conversion alone.  A store with gray='last' or keep_rows is a FRAME store: its frames go through hip.image_ingest_frame, it keeps
+    no labels (add_images(labels=...) is refused) and no min / max, and EventBatchBuilder(frames=) gathers its slots beside the events.
+    standardization is refused with any of the three.  ImageStore.dsec_frames(capacity, resize=True) and
+    ImageStore.ddd17_frames(capacity) are the two loaders' settings."""
+
+    def __init__(self, capacity_images, resize_hw=(256, 512), source_hw=(1024, 2048), standardization=False, staging_images=2, device=None,
+                 resample='bilinear', gray='first', keep_rows=None):
         if not _is_int(capacity_images) or not 1 <= capacity_images <= 1 << 24:
             raise hip.EssHipError(f'ImageStore: capacity_images={capacity_images!r} must be an int in [1, 2^24]')
         if not _is_int(staging_images) or not 2 <= staging_images <= 16:
             raise hip.EssHipError(f'ImageStore: staging_images={staging_images!r} must be an int in [2, 16]: one set copies while another is read')
-        self.resize_hw, self.source_hw = _pair('ImageStore: resize_hw', resize_hw), _pair('ImageStore: source_hw', source_hw)
+        self.source_hw = _pair('ImageStore: source_hw', source_hw)
+        self.resize_hw = self.source_hw if resize_hw is None else _pair('ImageStore: resize_hw', resize_hw)  # (None: no resize)
         (Hr, Wr), (H, W) = self.resize_hw, self.source_hw
+        if not isinstance(resample, str) or resample not in RESAMPLE:
+            raise hip.EssHipError(f'ImageStore: resample={resample!r}: one of {RESAMPLE}')
+        if not isinstance(gray, str) or gray not in ('first', 'last'):
+            raise hip.EssHipError(f"ImageStore: gray={gray!r}: 'first' (convert, then resize: the Cityscapes loader) or 'last' (resize the RGB "
+                                  'image, then convert: the event loaders\' paired frame)')
+        if keep_rows is not None and (not _is_int(keep_rows) or not 1 <= keep_rows <= Hr):
+            raise hip.EssHipError(f'ImageStore: keep_rows={keep_rows!r}: the top rows of the {Hr} resized rows a slot holds, an int in [1, {Hr}]')
+        # (a FRAME store -- the paired frames of an event loader -- goes through hip.image_ingest_frame and keeps no labels)
+        self.resample, self.gray, self.keep_rows = resample, gray, None if keep_rows is None else int(keep_rows)
+        self.frame_store = gray == 'last' or keep_rows is not None
+        if standardization and (self.frame_store or resample != 'bilinear'):
+            raise hip.EssHipError('ImageStore: standardization belongs to the Cityscapes loader: it is not applied with resample=, gray= or '
+                                  'keep_rows= (the event loaders do not stretch their paired frames)')
+        self.slot_hw = (Hr if keep_rows is None else int(keep_rows), Wr)
         # (the host tables of both passes and of the label: a size beyond the kernels' windows is refused here)
         self._tables = {
-            'h': None if W == Wr else pil_bilinear_tables(W, Wr), 'v': None if H == Hr else pil_bilinear_tables(H, Hr),
+            'h': None if W == Wr else pil_resize_tables(W, Wr, resample), 'v': None if H == Hr else pil_resize_tables(H, Hr, resample),
             'rows': pil_nearest_table(H, Hr), 'cols': pil_nearest_table(W, Wr),
         }
         self.capacity, self.staging_images, self.standardization = int(capacity_images), int(staging_images), bool(standardization)
@@ -157,14 +241,26 @@ class ImageStore:
         self.has_labels = None  # (decided by the first accepted call)
         self._dev = None
 
+    @classmethod
+    def dsec_frames(cls, capacity_images, resize=True, **kw):
+        """the DSEC loader's paired img_left (sequence.py:166-176): 480 x 640 RGB, with resize all 480 rows -> 448 x 640 by
+        Image.resize's default filter (bicubic) -- the bottom 40 rows are NOT cut first, although the events' are --, then Grayscale"""
+        return cls(capacity_images, resize_hw=(448, 640) if resize else None, source_hw=(480, 640), resample='bicubic', gray='last', **kw)
+
+    @classmethod
+    def ddd17_frames(cls, capacity_images, **kw):
+        """the DDD17 loader's paired frame (ddd17_events_loader.py:187-213): 260 x 346 -> 260 x 352 by Image.resize's default filter
+        (bicubic), Grayscale, and the top 200 rows (img_tensor[:, :-60, :])"""
+        return cls(capacity_images, resize_hw=(260, 352), source_hw=(260, 346), resample='bicubic', gray='last', keep_rows=200, **kw)
+
     def bytes(self):
         """the device memory of the slots (allocated or not yet), labels included unless the store is known to keep none"""
-        Hr, Wr = self.resize_hw
-        return self.capacity * (Hr * Wr * (1 if self.has_labels is False else 2) + 8)
+        Hs, Ws = self.slot_hw
+        return self.capacity * (Hs * Ws * (1 if self.has_labels is False or self.frame_store else 2) + 8)
 
     @property
     def images(self):
-        """uint8 [capacity, Hr, Wr]"""
+        """uint8 [capacity, Hr, Wr] ([capacity, keep_rows, Wr] with keep_rows)"""
         return self._device()['images']
 
     @property
@@ -181,13 +277,14 @@ class ImageStore:
         if self._dev is None:
             if self.has_labels is None:
                 raise hip.EssHipError('ImageStore: the store is empty: its device tensors exist from the first accepted frame on')
-            dev, (Hr, Wr), (H, W) = self.device, self.resize_hw, self.source_hw
+            dev, (Hr, Wr), (H, W), (Hs, Ws) = self.device, self.resize_hw, self.source_hw, self.slot_hw
             up = lambda a: None if a is None else torch.from_numpy(a).to(dev)  # noqa: E731
             self._dev = {
-                'images': torch.zeros(self.capacity, Hr, Wr, dtype=torch.uint8, device=dev),
+                'images': torch.zeros(self.capacity, Hs, Ws, dtype=torch.uint8, device=dev),
                 'labels': torch.zeros(self.capacity, Hr, Wr, dtype=torch.uint8, device=dev) if self.has_labels else None,
                 'minmax': torch.zeros(self.capacity, 2, dtype=torch.int32, device=dev),
-                'scratch': torch.zeros(H, Wr, dtype=torch.uint8, device=dev),
+                # (gray last: the horizontal pass leaves three channels)
+                'scratch': torch.zeros((H, Wr, 3) if self.gray == 'last' else (H, Wr), dtype=torch.uint8, device=dev),
                 'tables': {k: up(v) for k, v in self._tables.items()},
                 'stage': {}, 'copy_stream': torch.cuda.Stream(device=dev), 'frames': 0,
             }
@@ -209,6 +306,9 @@ class ImageStore:
                                       f'(source_hw), got {got}')
             out.append(f)
         labs = None
+        if labels is not None and self.frame_store:
+            raise hip.EssHipError("ImageStore.add_images: a frame store (gray='last' or keep_rows) keeps no labels: the paired frame's label "
+                                  'is the event sample\'s')
         if labels is not None:
             if isinstance(labels, np.ndarray) and labels.ndim == 3:
                 labels = list(labels)
@@ -263,9 +363,15 @@ class ImageStore:
             compute.wait_event(st.copied)
             slot = self.n_images
             with torch.cuda.device(self.device):
-                hip.image_ingest(st.dev, d['images'][slot], tabs['h'], tabs['v'], d['scratch'], self.standardization, d['minmax'][slot],
-                                 **({} if labs is None else dict(label=st.lab_dev, label_rows=tabs['rows'], label_cols=tabs['cols'],
-                                                                 out_label=d['labels'][slot])))
+                if self.frame_store:
+                    rgb_last = f.ndim == 3 and self.gray == 'last'
+                    scratch = d['scratch'] if rgb_last or self.gray == 'first' else d['scratch'].view(-1)[:H * self.resize_hw[1]].view(H, -1)
+                    hip.image_ingest_frame(st.dev, d['images'][slot], tabs['h'], tabs['v'], scratch, resized_rows=self.resize_hw[0],
+                                           gray_last=self.gray == 'last')
+                else:
+                    hip.image_ingest(st.dev, d['images'][slot], tabs['h'], tabs['v'], d['scratch'], self.standardization, d['minmax'][slot],
+                                     **({} if labs is None else dict(label=st.lab_dev, label_rows=tabs['rows'], label_cols=tabs['cols'],
+                                                                     out_label=d['labels'][slot])))
             st.consumed.record(compute)
             self.n_images += 1
             slots.append(slot)
@@ -298,7 +404,7 @@ class ImageBatchBuilder:
         self.id_lut = None if semseg_num_classes is None else cityscapes_id_lut(semseg_num_classes)
         self.store, self.device = store, store.device
         self.augmentation, self.random_crop, self.use_graph = bool(augmentation), bool(random_crop), bool(graph)
-        self.rows = min(self.height, store.resize_hw[0]) if self.random_crop else store.resize_hw[0]
+        self.rows = min(self.height, store.slot_hw[0]) if self.random_crop else store.slot_hw[0]
         self.shift_limit = 0.0 if self.random_crop else 0.1
         self.generator = torch.Generator().manual_seed(int(seed))
         self.batch_size = None
@@ -371,7 +477,7 @@ class ImageBatchBuilder:
         B = idx.size
         if self.store.n_images == 0:
             raise hip.EssHipError('ImageBatchBuilder.build: the store holds no image')
-        Hs, Ws = self.rows, self.store.resize_hw[1]
+        Hs, Ws = self.rows, self.store.slot_hw[1]
         p1 = draw_params(B, (Hs, Ws), (self.height, self.width), self.shift_limit, self.generator, self.augmentation)
         p2 = None
         if self.augmentation:

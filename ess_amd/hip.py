@@ -89,6 +89,7 @@ EXPORTS = [
     'ess_recon_post_frame_steered', 'ess_recon_post_bounds_steered',
     'ess_viz_semseg', 'ess_viz_events', 'ess_viz_overlay',
     'ess_image_ingest', 'ess_augment_image_label_store',
+    'ess_image_ingest_frame', 'ess_image_gather_unit',
 ]
 
 
@@ -221,6 +222,8 @@ def lib():
             'ess_viz_overlay': [P, P, P, P, I, I, I, I, F, P],
             'ess_image_ingest': [P, I, I, I, P, I, P, I, P, P, I, I, I, P, P, P, P, P, P],
             'ess_augment_image_label_store': [P, P, P, I, I, I, I, P, P, P, P, I, I, I, P],
+            'ess_image_ingest_frame': [P, I, I, I, P, I, P, I, P, P, I, I, I, I, P],
+            'ess_image_gather_unit': [P, I64, I, I, P, I, I, P, P],
         }
         for name, argtypes in sig.items():
             fn = getattr(L, name)
@@ -1835,6 +1838,80 @@ def image_ingest(frame, out, h_table=None, v_table=None, scratch=None, standardi
                                   ptr(scratch if need_scratch else None, torch.uint8), ptr(out, torch.uint8), Hr, Wr, int(bool(standardize)),
                                   ptr(minmax, torch.int32), ptr(label, torch.uint8), ptr(label_rows, torch.int32), ptr(label_cols, torch.int32),
                                   ptr(out_label, torch.uint8), stream()), 'ess_image_ingest')
+    return out
+
+
+def image_ingest_frame(frame, out, h_table=None, v_table=None, scratch=None, resized_rows=None, gray_last=True):
+    """One paired camera frame of an event loader -> its store slot (ess_image_ingest_frame), in PIL's integer arithmetic: frame uint8
+    [H, W, 3] or [H, W] -> out uint8 [out_rows, Wr], the top out_rows rows of Image.resize((Wr, Hr)) -- with the tables of
+    datasets.image_store.pil_resize_tables, bicubic as the loaders' default filter is -- and, for an RGB frame, convert('L') BEHIND the
+    resize (gray_last=True, the loaders' order) or in front of it (False: image_ingest's bits).  resized_rows: Hr (default: out_rows,
+    nothing cut).  h_table / v_table: int32 [2 + taps, Wr] / [2 + taps, Hr], None exactly where the side stays.  scratch: uint8
+    [H, Wr, 3] (RGB, gray last) or [H, Wr], needed with a horizontal pass (or gray first); allocated when None.  Returns out.
+    Everything is checked before a pointer is taken."""
+    fn = 'image_ingest_frame'
+    if not torch.is_tensor(frame) or frame.dtype != torch.uint8 or frame.dim() not in (2, 3) or (frame.dim() == 3 and frame.shape[2] != 3) \
+            or frame.numel() == 0 or not frame.is_contiguous():
+        got = f'{frame.dtype}{tuple(frame.shape)}' if torch.is_tensor(frame) else type(frame).__name__
+        raise EssHipError(f'{fn}: frame must be a non-empty contiguous uint8 [H, W, 3] (RGB) or [H, W] (gray) tensor, got {got}')
+    H, W = int(frame.shape[0]), int(frame.shape[1])
+    channels = 3 if frame.dim() == 3 else 1
+    if not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 2 or out.numel() == 0 or not out.is_contiguous():
+        got = f'{out.dtype}{tuple(out.shape)}' if torch.is_tensor(out) else type(out).__name__
+        raise EssHipError(f'{fn}: out must be a non-empty contiguous uint8 [out_rows, Wr] tensor, got {got}')
+    out_rows, Wr = int(out.shape[0]), int(out.shape[1])
+    Hr = out_rows if resized_rows is None else resized_rows
+    if isinstance(Hr, bool) or not isinstance(Hr, (int, np.integer)) or Hr < out_rows:
+        raise EssHipError(f'{fn}: resized_rows={Hr!r}: the rows of the resized frame, an int >= out\'s {out_rows} rows')
+    Hr = int(Hr)
+    if max(H, W, Hr, Wr) > IMAGE_MAX_SIDE:
+        raise EssHipError(f'{fn}: source {H} x {W}, resized {Hr} x {Wr}: a side is at most {IMAGE_MAX_SIDE}')
+    if not isinstance(gray_last, (bool, int, np.integer)) or gray_last not in (0, 1):
+        raise EssHipError(f'{fn}: gray_last={gray_last!r} must be True or False')
+    h_taps, v_taps = _image_table(fn, 'h_table', h_table, W, Wr), _image_table(fn, 'v_table', v_table, H, Hr)
+    tensors = [('frame', frame), ('out', out)] + [(n, t) for n, t in (('h_table', h_table), ('v_table', v_table)) if t is not None]
+    rgb_last = channels == 3 and bool(gray_last)
+    need_scratch = h_table is not None or (channels == 3 and not rgb_last)
+    scratch_shape = (H, Wr, 3) if rgb_last else (H, Wr)
+    if scratch is not None:
+        tensors.append(('scratch', _formed(fn, 'scratch', scratch, torch.uint8, scratch_shape)))
+    _on_device(fn, tensors)
+    if any(t.device != frame.device for _, t in tensors):
+        raise EssHipError(f'{fn}: every tensor must lie on the frame\'s device ({frame.device})')
+    if scratch is None and need_scratch:
+        scratch = torch.empty(scratch_shape, dtype=torch.uint8, device=frame.device)
+    _check(lib().ess_image_ingest_frame(ptr(frame, torch.uint8), channels, H, W, ptr(h_table, torch.int32), h_taps, ptr(v_table, torch.int32),
+                                        v_taps, ptr(scratch if need_scratch else None, torch.uint8), ptr(out, torch.uint8), Hr, Wr, out_rows,
+                                        int(bool(gray_last)), stream()), 'ess_image_ingest_frame')
+    return out
+
+
+def image_gather_unit(images, index, out=None):
+    """transforms.ToTensor() on stored frames (ess_image_gather_unit): images uint8 [capacity, Hs, Ws], index int32 or int64 [B] on the
+    device (read there: the launch is capturable) -> out fp32 [B, 1, Hs, Ws] = images[index] / 255, the bits of
+    torch.from_numpy(u8).float().div(255) on the host; an index outside [0, capacity) gives an all-zero frame."""
+    fn = 'image_gather_unit'
+    if not torch.is_tensor(images) or images.dtype != torch.uint8 or images.dim() != 3 or images.numel() == 0 or not images.is_contiguous():
+        got = f'{images.dtype}{tuple(images.shape)}' if torch.is_tensor(images) else type(images).__name__
+        raise EssHipError(f'{fn}: images must be a non-empty contiguous uint8 [capacity, Hs, Ws] tensor, got {got}')
+    capacity, Hs, Ws = (int(v) for v in images.shape)
+    if max(Hs, Ws) > IMAGE_MAX_SIDE:
+        raise EssHipError(f'{fn}: slots of {Hs} x {Ws}: a side is at most {IMAGE_MAX_SIDE}')
+    if not torch.is_tensor(index) or index.dtype not in (torch.int32, torch.int64) or index.dim() != 1 or not 1 <= index.numel() <= 65535 \
+            or not index.is_contiguous():
+        got = f'{index.dtype}{tuple(index.shape)}' if torch.is_tensor(index) else type(index).__name__
+        raise EssHipError(f'{fn}: index must be a contiguous int32 or int64 [B] tensor with 1 <= B <= 65535, got {got}')
+    B = int(index.shape[0])
+    tensors = [('images', images), ('index', index)]
+    if out is not None:
+        tensors.append(('out', _formed(fn, 'out', out, torch.float32, (B, 1, Hs, Ws))))
+    _on_device(fn, tensors)
+    if any(t.device != images.device for _, t in tensors):
+        raise EssHipError(f'{fn}: every tensor must lie on the store\'s device ({images.device})')
+    if out is None:
+        out = torch.empty(B, 1, Hs, Ws, dtype=torch.float32, device=images.device)
+    _check(lib().ess_image_gather_unit(ptr(images, torch.uint8), capacity, Hs, Ws, ptr(index, index.dtype), int(index.dtype == torch.int64), B,
+                                       ptr(out), stream()), 'ess_image_gather_unit')
     return out
 
 

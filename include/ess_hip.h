@@ -782,6 +782,31 @@ int ess_image_ingest(const uint8_t* frame, int32_t channels, int32_t H, int32_t 
                      int32_t standardize, int32_t* minmax, const uint8_t* label, const int32_t* label_rows,
                      const int32_t* label_cols, uint8_t* out_label, ess_stream_t stream);
 
+/* ---- PAIRED CAMERA FRAMES of the event loaders (DSEC/dataset/sequence.py:166-176, datasets/ddd17_events_loader.py:187-213) --
+ * PURELY ADDITIVE to ABI 110 (ess_version() is unchanged; no existing entry point changes).  The loaders call Image.resize without a
+ * filter -- PIL's default is BICUBIC there, whose tables hold negative coefficients -- on the RGB image, and transforms.Grayscale()
+ * behind it; DDD17 keeps the top 200 of its 260 resized rows.  One frame -> the top out_rows (<= Hr) rows of its resized gray
+ * image, uint8 [out_rows][Wr], with the tables of either filter (the layout above, built by the host):
+ *   channels == 3, gray_last == 1   the horizontal pass on all three channels with one window's coefficients, each channel to
+ *                                   clip8((2^21 + sum k p) >> 22), into scratch uint8 [H][Wr][3]; the vertical pass per channel
+ *                                   likewise, and L = (R 19595 + G 38470 + B 7471 + 0x8000) >> 16 at its end.  A pass whose side
+ *                                   stays is skipped (its table NULL); the conversion still runs last.
+ *   channels == 1, or gray_last == 0  ess_image_ingest's arithmetic on one channel (channels == 3: gray first), scratch uint8 [H][Wr]
+ * The sums are int32, the shift of a negative sum is arithmetic and the clip cuts on both sides: a bicubic window overshoots.  A
+ * table must keep 2^21 + 255 sum |k| below 2^31 (bicubic: sum |k| <= 1.3 x 2^22).  Only the source rows that a kept output row's
+ * window reads go through the horizontal pass; rows of `out` behind out_rows are not written.  scratch is needed where a horizontal
+ * pass runs (h_table, or channels == 3 with gray_last == 0).  Every buffer on the device; one or two launches, no float.          */
+int ess_image_ingest_frame(const uint8_t* frame, int32_t channels, int32_t H, int32_t W, const int32_t* h_table, int32_t h_taps,
+                           const int32_t* v_table, int32_t v_taps, uint8_t* scratch, uint8_t* out, int32_t Hr, int32_t Wr,
+                           int32_t out_rows, int32_t gray_last, ess_stream_t stream);
+
+/* transforms.ToTensor() on B stored frames -- ADDITIVE as well: out fp32 [B][1][Hs][Ws] = images[index[b]] / 255, images uint8
+ * [capacity][Hs][Ws], one IEEE fp32 division per byte value (the bits of torch's .float().div(255) on the host; no reciprocal).
+ * index: B words on the device, int32 (index_i64 == 0) or int64 (1), read by the kernel; a word outside [0, capacity) gives an
+ * all-zero frame.  One launch.                                                                                                   */
+int ess_image_gather_unit(const uint8_t* images, int64_t capacity, int32_t Hs, int32_t Ws, const void* index, int32_t index_i64,
+                          int32_t B, float* out, ess_stream_t stream);
+
 /* TaskLoss = Dice + CrossEntropy (utils/loss_functions.py:6-24,96-135), forward AND gradient w.r.t.
  * logits in one pass pair.  logits [N][K][H][W], labels int64 [N][H][W].  loss: 1 float.
  * dlogits (nullable): d(loss*loss_scale)/dlogits.  workspace: ess_task_loss_workspace(K) bytes.     */

@@ -12,7 +12,18 @@
 The ways alternate.  Every figure is ms, median (min - max) over the rounds; one JSON line per figure.  Before anything is timed a
 slot of the store is compared with PIL itself, where it imports (slot_equals_pil in the first line).
 
-    python tools/bench_image_batch.py [--batch 8] [--height 200 --width 352] [--rounds 2] [--batches 64] [--standardization]"""
+    python tools/bench_image_batch.py [--batch 8] [--height 200 --width 352] [--rounds 2] [--batches 64] [--standardization]
+
+--frames (without a number) times the PAIRED CAMERA FRAMES of the event loaders instead, at both their sizes -- DSEC 480 x 640 RGB ->
+448 x 640, DDD17 260 x 346 -> 260 x 352 (the top 200 rows kept):
+
+    frame_ingest_launches      hip.image_ingest_frame on a frame that is on the device already (bicubic, gray last)
+    frame_ingest_with_upload   ImageStore.add_images on a frame store, one frame a call
+    pil_host                   Image.fromarray(f).resize((Wr, Hr)).convert('L'), / 255 and the float upload, per frame
+    batch_with_frames / batch_without_frames   EventBatchBuilder(graph=True, augmentation=False) at --batch over a synthetic event store
+                               (5 windows of 20000 events a sample) with frames= and without it
+
+    python tools/bench_image_batch.py --frames [--batch 8] [--rounds 2] [--batches 64]"""
 import argparse
 import json
 import os
@@ -49,6 +60,91 @@ def device_ms(fn, reps):
     return a.elapsed_time(b) / reps
 
 
+def paired_frames(a):
+    """--frames without a number: the paired camera frames of the two event loaders (module docstring)"""
+    from ess_amd.datasets.data_util import EventColumns
+    from ess_amd.datasets.event_batches import EventBatchBuilder
+    from ess_amd.datasets.event_store import EventStore, StoreSample
+    dev = torch.device('cuda:0')
+    try:
+        from PIL import Image
+    except ImportError:
+        Image = None
+    B, T, n_win = a.batch, 5, 20000
+    rng = np.random.default_rng(0)
+    for name, shape, (Hr, Wr), keep, label_hw in (('dsec', (480, 640, 3), (448, 640), None, (440, 640)), ('ddd17', (260, 346), (260, 352), 200, (200, 346))):
+        H, W = shape[:2]
+        frames = [rng.integers(0, 256, shape, dtype=np.uint8) for _ in range(4)]
+        timed = a.rounds * a.upload_frames
+        make = ImageStore.dsec_frames if name == 'dsec' else ImageStore.ddd17_frames
+        store = make(B + timed)
+        store.add_images([frames[k % 4] for k in range(B)])
+        head = dict(frames=name, source=list(shape), resize=[Hr, Wr], keep_rows=keep, batch=B, sequence_steps=T, window_events=n_win,
+                    store_bytes=store.bytes(), pil=None if Image is None else Image.__version__)
+
+        def pil_frame(f):
+            r = Image.fromarray(f).resize((Wr, Hr))
+            return np.array(r.convert('L') if f.ndim == 3 else r)[:keep]
+        if Image is not None:
+            head['slot_equals_pil'] = bool(np.array_equal(store.images[1].cpu().numpy(), pil_frame(frames[1])))
+        print(json.dumps(head), flush=True)
+        d = store._device()
+        tabs = d['tables']
+        frame_dev, slot = torch.from_numpy(frames[0]).to(dev), torch.zeros_like(store.images[0])
+        n_added = [0]
+        scratch = d['scratch'] if len(shape) == 3 else d['scratch'].view(-1)[:H * Wr].view(H, Wr)  # (a gray frame's pass leaves one channel)
+
+        def launches():
+            hip.image_ingest_frame(frame_dev, slot, tabs['h'], tabs['v'], scratch, resized_rows=Hr)
+
+        def with_upload():
+            n_added[0] += 1
+            store.add_images([frames[n_added[0] % 4]])
+
+        def pil_host():
+            return torch.from_numpy(pil_frame(frames[0])).float().div(255).to(dev)
+        n = B * T * n_win + 1000
+        events = EventStore(n, label_hw=label_hw, label_capacity=B)
+        cols = EventColumns(np.cumsum(rng.integers(0, 3, n)).astype(np.int64), rng.integers(0, W, n).astype(np.int16),
+                            rng.integers(0, H, n).astype(np.int16), rng.integers(0, 2, n).astype(np.uint8))
+        events.add_recording(cols, labels=rng.integers(0, 6, (B,) + label_hw, dtype=np.uint8))
+        samples = [StoreSample(0, end=(b + 1) * T * n_win, label=b, frame=b) for b in range(B)]
+        common = dict(sequence_steps=T, store=events, window_events=n_win, graph=True, augmentation=False)
+        preset = getattr(EventBatchBuilder, name)
+        with_frames, without = preset(B, frames=store, **common), preset(B, **common)
+        ways = {
+            'frame_ingest_launches': lambda: device_ms(launches, a.reps),
+            'frame_ingest_with_upload': lambda: statistics.mean(host_ms(with_upload) for _ in range(a.upload_frames)),
+            'batch_with_frames': lambda: statistics.mean(host_ms(lambda: with_frames.build(samples)) for _ in range(a.batches)),
+            'batch_without_frames': lambda: statistics.mean(host_ms(lambda: without.build(samples)) for _ in range(a.batches)),
+        }
+        if Image is not None:
+            ways['pil_host'] = lambda: statistics.mean(host_ms(pil_host) for _ in range(16))
+        else:
+            print(json.dumps(dict(frames=name, way='pil_host', note='PIL is absent on this machine: the host path is not measured')), flush=True)
+        for _ in range(3):  # (the warm-up of every shape that is timed, and the captures)
+            launches(), with_frames.build(samples), without.build(samples)
+            if Image is not None:
+                pil_host()
+        torch.cuda.synchronize()
+        times = {k: [] for k in ways}
+        for _ in range(a.rounds):
+            for k, fn in ways.items():
+                times[k].append(fn())
+        unit = {'frame_ingest_launches': f'ms per frame, device events, {a.reps} calls'}
+        for k, v in times.items():
+            per = f'ms per batch of {B}' if k.startswith('batch') else 'ms per frame'
+            print(json.dumps(dict(frames=name, way=k, ms_median=round(statistics.median(v), 3), ms_min=round(min(v), 3), ms_max=round(max(v), 3),
+                                  clock=unit.get(k, f'{per}, host clock to a device synchronise'))), flush=True)
+        med = {k: statistics.median(v) for k, v in times.items()}
+        spread = max(times['batch_without_frames']) - min(times['batch_without_frames'])
+        verdict = dict(frames=name, batch_spread_ms=round(spread, 3), frames_cost_ms=round(med['batch_with_frames'] - med['batch_without_frames'], 3))
+        verdict['batch_with_frames_SLOWER'] = bool(med['batch_with_frames'] - med['batch_without_frames'] > spread)
+        if Image is not None:
+            verdict['frame_ingest_with_upload_SLOWER_than_pil_host'] = bool(med['frame_ingest_with_upload'] > med['pil_host'])
+        print(json.dumps(verdict), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--source', type=int, nargs=2, default=(1024, 2048))
@@ -56,7 +152,8 @@ def main():
     ap.add_argument('--height', type=int, default=200)
     ap.add_argument('--width', type=int, default=352)
     ap.add_argument('--batch', type=int, default=8)
-    ap.add_argument('--frames', type=int, default=16, help='frames the store holds for the batches')
+    ap.add_argument('--frames', type=int, nargs='?', const=-1, default=16,
+                    help='with a number: frames the store holds for the batches; without one: time the paired camera frames instead')
     ap.add_argument('--batches', type=int, default=64, help='timed batches per way and round')
     ap.add_argument('--upload-frames', type=int, default=64, help='timed add_images calls per round')
     ap.add_argument('--reps', type=int, default=200, help='calls between the device events')
@@ -65,6 +162,8 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_image_batch needs an MI355X: there is no CPU path and no figure without one')
+    if a.frames == -1:
+        return paired_frames(a)
     dev = torch.device('cuda:0')
     (H, W), (Hr, Wr) = a.source, a.resize
     rng = np.random.default_rng(0)
